@@ -3,7 +3,10 @@
 BIC clustering (the exact flags spk-diarization2.py passes) over a batch of
 synthetic 1 h / 4-speaker feature files resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--dump-outputs writes the rows of every file from the last timed step (seeded inputs: two
+builds run with the same arguments can be compared array for array).
 
 One process per GPU (torchrun sets RANK / LOCAL_RANK / WORLD_SIZE).  Files are
 independent, so ranks share nothing on the data path: each rank owns its own
@@ -57,6 +60,7 @@ FLOP_PER_DET = 2 * (9880 + 780 + 780)
 FLOP_PER_FRAME = 2 * 820
 FP64_PEAK_TFLOPS = 78.6
 TRAFFIC_PROFILE = os.path.join(ROOT, 'profiles', 'r03_bench256_hbm_traffic.json')
+DUMP_CAP_BYTES = 64 << 20      # --dump-outputs: total .npy payload
 
 CD_ARGS = ['-m', 'gw', '-d', 'BIC', '-w', '1.0', '-st', '3.0', '-dws', '0.1', '-l', '1.0']
 CL_ARGS = ['-m', 'hi', '-l', '1.3']
@@ -88,12 +92,19 @@ def parse():
     ap.add_argument('--share-device', action='store_true',
                     help='rehearsal only: every rank uses GPU 0 (needs --backend gloo)')
     ap.add_argument('--dump-rows', default='', help='rank 0 writes the gathered rows of the last step here (.npz)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='rank 0 writes what the last timed step returned as DIR/<name>.npy (float64): per file '
+                         'file_<global index>.npy = its rows [start_s, end_s, speaker] (with --long-file: rows.npy); '
+                         'at most %d MB in all, a seeded sample of the files beyond that' % (DUMP_CAP_BYTES >> 20))
     ap.add_argument('--long-file', action='store_true',
                     help='BASELINE config 5 instead of the batch: ONE file of --seconds (default 36000) / --speakers '
                          '(default 8) sharded in time over the ranks (distributed.diarize_long_file: all_gather of the '
                          'segment records, a row block of the N x N matrix per rank, merge loop replicated); the line '
                          'carries the per-phase times of the slowest rank')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def cpu_info():
@@ -179,6 +190,28 @@ def rows_digest(rows_by_file):
         h.update(np.int64(i).tobytes())
         h.update(np.ascontiguousarray(rows_by_file[i], dtype=np.float64).tobytes())
     return h.hexdigest()
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES):
+    """Writes {name: array} as out_dir/<name>.npy in float64.  When the set is larger than `cap`
+    bytes, the names are taken in one fixed seeded order and written up to the first that would
+    pass the cap: two builds whose arrays differ in size still share a prefix of that order.
+    Returns the names written."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    names = sorted(arrays)
+    size = lambda k: arrays[k].nbytes + 128          # + the .npy header
+    if sum(size(k) for k in names) > cap:
+        keep, used = [], 0
+        for i in np.random.default_rng(0).permutation(len(names)):
+            if used + size(names[i]) > cap:
+                break
+            keep.append(names[i])
+            used += size(names[i])
+        names = sorted(keep)
+    os.makedirs(out_dir, exist_ok=True)
+    for k in names:
+        np.save(os.path.join(out_dir, k + '.npy'), arrays[k])
+    return names
 
 
 def spawn_ranks(args):
@@ -384,6 +417,8 @@ def main():
         verified['files_gathered'] = len(out)
         if args.dump_rows:
             np.savez(args.dump_rows, **{'f%d' % i: r for i, r in out.items()})
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {'file_%05d' % i: r for i, r in out.items()})
     hours = world * args.files * (args.seconds / 3600.0) * args.steps
     value = hours / dt
 
@@ -576,6 +611,8 @@ def long_file_main(args, rank, local, world):
     else:
         every = mine
     dt = float(every[:, -1].max())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'rows': rows})
     if rank == 0:
         hours = (seconds / 3600.0) * args.steps
         res = {'metric': 'diarized audio throughput, ONE long file sharded in time over the GPUs (CD gw/BIC + CL hi/BIC)',

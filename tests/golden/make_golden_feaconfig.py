@@ -2,9 +2,8 @@
 """Writes tests/golden/feaconfig.json: the STRUCTURAL parameters of the reference's feature
 configuration (fconfig.cfg:1-101) as parsed by speaker-diarization_amd/feaconfig.py, and a
 SHA-256 of its trained arrays (normalization mean / scale, the 39x39 transform: 1 599
-numbers of model data, which are NOT stored -- ADVICE r2).  Runs only where /root/reference
-exists; the tests read the real arrays from there when it does and use synthetic ones
-otherwise."""
+numbers of model data, which are NOT stored -- ADVICE r2).  Runs only where the reference
+tree exists (SPKD_REFERENCE); the tests use synthetic arrays of the same shapes."""
 import hashlib
 
 import numpy as np
