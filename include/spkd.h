@@ -273,10 +273,12 @@ spkd_status spkd_sw(spkd_ctx *ctx, const float *d_frames, int64_t n_frames,
  *   finite distance evaluated (NaN when never updated from the reference's
  *   initial 0 / maxint); variant 2 = max / min of the final matrix.
  */
-/* Launch shape of the merge loop.  MONO: one workgroup per problem, the whole loop in
- * one launch (many files per call).  WIDE: every merge round is a pair of launches
- * whose log-det work spreads over all CUs (one long file).  AUTO picks by problem
- * count.  Results are identical. */
+/* Launch shape of the merge loop.  MONO: one launch, one workgroup per problem, the whole
+ * loop inside it (many files per call).  WIDE: one launch per merge, its log-det work spread
+ * over all CUs (one long file).  AUTO: WIDE up to 64 problems, MONO above.  Results are
+ * identical.  MONO with a problem of more than 38 396 records (its ids outgrow the LDS) runs
+ * WIDE instead.  WIDE refuses a problem of more than 16 384 records with SPKD_EINVAL before
+ * any work, as every shape does one of more than 65 536. */
 enum { SPKD_AHC_AUTO = 0, SPKD_AHC_MONO = 1, SPKD_AHC_WIDE = 2 };
 
 typedef struct {

@@ -10,8 +10,8 @@
 //                    spk-clustering2.py:185-222), one workgroup per problem,
 //                    device resident: arg-min with numpy semantics, statistics
 //                    merge, row recompute, v1 / v2 matrix update rules.
-//   k_ahc_update / k_ahc_select / k_ahc_pairs / k_ahc_final : the same loop as a chain
-//                    of chip-wide launches, for calls with few (long) problems.
+//   k_step_init / k_ahc_step / k_step_final : the same loop as a chain of
+//                    chip-wide launches, one per merge, for calls with few (long) problems.
 //
 // Per evaluated pair the algorithmic traffic is two records in, one double out
 // = 13 128 B; one factorisation per pair (the union), because
@@ -612,17 +612,6 @@ __global__ __launch_bounds__(MX_WAVES * WAVE, 2) void k_matrix(
 constexpr int AHC_WAVES = 8;
 constexpr int AHC_TPB = AHC_WAVES * WAVE;
 
-struct ArgMin {
-    double v;
-    long long idx;
-    long long nan_idx;
-};
-
-__device__ __forceinline__ void argmin_merge(ArgMin& x, const ArgMin& y) {
-    if (y.v < x.v || (y.v == x.v && y.idx < x.idx)) { x.v = y.v; x.idx = y.idx; }
-    if (y.nan_idx < x.nan_idx) x.nan_idx = y.nan_idx;
-}
-
 // One workgroup per problem.  ex is a private working copy of the quad records
 // (summed in place as clusters merge).  Dynamic LDS: int32 ids[N + 1].
 //
@@ -993,55 +982,6 @@ __global__ __launch_bounds__(AHC_TPB) void k_ahc(
     }
 }
 
-
-// ---------------------------------------------------------------------------
-// The same merge loop split over kernel launches ("wide" form): when there are
-// few problems (one long file, BASELINE.json configs 2 / 5) one workgroup per
-// problem leaves the chip idle and the loop is a serial chain of N - 1 rounds.
-// Here a round is ONE launch, k_ahc_round, of ceil(partners / 31) workgroups per
-// problem:
-//   every workgroup  the log dets of the merged cluster with its 31 partners (and the
-//                merged cluster's own, which each of them needs), the finished distances,
-//                row / column sa of the matrix and the row caches of its partner rows
-//                (rows whose cached minimum was invalidated are rescanned on the spot);
-//   the workgroup that finishes last (an arrival ticket behind an agent-scope release;
-//                it takes an agent-scope acquire)  the next round's selection: row sa's
-//                own cache, arg-min over the row caches, the stop decision, the merge
-//                of the two records, the partner list.
-// Two small launches start the chain (row caches of the full matrix, first selection).
-// The host enqueues N - 1 rounds back to back without reading anything: a problem
-// that stopped sets state.done and its later launches return at once.  Nothing ever
-// waits for another workgroup, so there is no co-residency requirement.  Round 1's
-// three launches per merge (update / select / pairs) took 30 - 45 us per merge.
-// Arithmetic, tie-breaks and NaN rules are those of k_ahc.
-struct AhcState {
-    int32_t done, n_merges, nids, ticket;
-    long long sa, sb;
-    double nA, fmin;
-};
-
-// distance of the merged cluster sa to cluster c from the finished log dets
-// (k_ahc step 4; KL2 from the auxiliary records, 39 terms in index order)
-__device__ __forceinline__ double ahc_finish(int kind, double lambdac, const double* __restrict__ ex,
-                                             const double* __restrict__ aux, const double* __restrict__ ldp,
-                                             double ldx, int64_t off, long long sa,
-                                             long long c, double nA, double ldA) {
-    if (kind == SPKD_KL2) {
-        const double* a1 = aux + (off + sa) * AUX;
-        const double* a2 = aux + (off + c) * AUX;
-        double t1 = 0.0, t2 = 0.0;
-        for (int i = 0; i < D; ++i) {
-            const float dm = (float)a1[2 * DA + i] - (float)a2[2 * DA + i];
-            const double delta = (double)dm;
-            t1 += (a1[i] - a2[i]) * (a2[DA + i] - a1[DA + i]);
-            t2 += ((a1[DA + i] + a2[DA + i]) * delta) * delta;
-        }
-        return 0.5 * t1 + 0.5 * t2;
-    }
-    const double nC = qr_count(ex + (off + c) * QREC);
-    return finish_distance(kind, lambdac, nA, ldA, nC, ldp[c], ldx);
-}
-
 // wave-wide (min, first column, first NaN column) of one row; sub_col >= 0
 // replaces that column's stored value by sub_val (the caller's own fresh write)
 __device__ __forceinline__ void ahc_scan_row(const double* __restrict__ row, long long N,
@@ -1079,389 +1019,6 @@ __device__ __forceinline__ void ahc_scan_row(const double* __restrict__ row, lon
     }
 }
 
-// grid (ceil(n_max / 8), n_prob); wave w of block x owns row 8 x + w: the row caches of
-// the full initial matrix, every record alive
-__global__ __launch_bounds__(AHC_TPB) void k_ahc_init_rows(
-        const int64_t* __restrict__ seg_off, const double* __restrict__ mat,
-        const int64_t* __restrict__ mat_off, int32_t* __restrict__ alive,
-        double* __restrict__ rmin_all, int32_t* __restrict__ rcache_all) {
-    const int lane = lane_id(), wave = threadIdx.x >> 6;
-    const int p = blockIdx.y;
-    const int64_t off = seg_off[p];
-    const long long N = seg_off[p + 1] - off;
-    const long long r = (long long)blockIdx.x * AHC_WAVES + wave;
-    if (r >= N) return;
-    const double* Dm = mat + mat_off[p];
-    int32_t* al = alive + off;
-    double* rmin = rmin_all + off;
-    int32_t* rarg = rcache_all + 3 * off;
-    int32_t* rnan = rarg + N;
-    double mv;
-    int mc, nc;
-    ahc_scan_row(Dm + r * N, N, al, true, -1, 0.0, lane, mv, mc, nc);
-    if (lane == 0) { rmin[r] = mv; rarg[r] = mc; rnan[r] = nc; al[r] = 1; }
-}
-
-// The selection step of one problem, by one whole workgroup (AHC_TPB threads): with
-// it > 0 first the cache of the merged cluster's own row (this round's workgroups wrote
-// it) and the running statistics of variant 1 over the distances just evaluated; then
-// arg-min over the row caches (k_ahc step 1), the stop decision, the merge of the two
-// records and the partner list of the next round.
-__device__ __forceinline__ void ahc_select_body(
-        int it, int p, double* __restrict__ ex, const int64_t* __restrict__ seg_off,
-        int variant, int kind, int max_spk, double threshold, double* __restrict__ aux,
-        const double* __restrict__ mat, const int64_t* __restrict__ mat_off,
-        int32_t* __restrict__ alive, double* __restrict__ rmin_all,
-        int32_t* __restrict__ rcache_all, int32_t* __restrict__ ids_all,
-        AhcState* __restrict__ state, int32_t* __restrict__ out_a, int32_t* __restrict__ out_b,
-        double* __restrict__ out_d, unsigned long long* stat_max, unsigned long long* stat_min,
-        int* err, double* __restrict__ pk) {
-    struct RowRed { double mv, wmax, wmin; int mc, nc; };
-    __shared__ RowRed rred[AHC_WAVES];
-    __shared__ ArgMin red[AHC_WAVES];
-    __shared__ ArgMin best;
-    __shared__ int s_cnt[2];
-    __shared__ int s_nids;
-    const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-    const int64_t off = seg_off[p];
-    const long long N = seg_off[p + 1] - off;
-    int32_t* al = alive + off;
-    double* rmin = rmin_all + off;
-    int32_t* rarg = rcache_all + 3 * off;
-    int32_t* rnan = rarg + N;
-    int32_t* ids = ids_all + off;
-    AhcState* S = state + p;
-    const long long INF_IDX = 0x7fffffffffffffffLL;
-    const int n_merges = it > 0 ? S->n_merges : 0;
-    const long long psa = it > 0 ? S->sa : -1;       // the row the round just rewrote (none before the first merge)
-    const long long m = N - n_merges;
-    // ---- 0 + 1 in ONE pass over x = 0 .. N - 1 (one memory round trip): x as a COLUMN of
-    // row psa -- that row's fresh cache and, variant 1, the running statistics over the
-    // distances just evaluated -- and x as a ROW of the arg-min over the row caches (k_ahc
-    // step 1; row psa enters with its fresh values below)
-    const double* rowp = mat + mat_off[p] + (psa >= 0 ? psa : 0) * N;
-    double mv = __builtin_huge_val(), wmax = __builtin_nan(""), wmin = __builtin_nan("");
-    int mc = NO_COL, nc = NO_COL;
-    ArgMin mine;
-    mine.v = __builtin_huge_val(); mine.idx = INF_IDX; mine.nan_idx = INF_IDX;
-#pragma unroll 2
-    for (long long x = tid; x < N; x += AHC_TPB) {
-        const int a = al[x];
-        const double d = rowp[x];
-        const double v = rmin[x];
-        const int c = rarg[x], rn = rnan[x];
-        if (!a) continue;
-        if (psa >= 0) {
-            if (variant == 1 && x != psa && stat_valid(d)) {
-                wmax = (wmax != wmax || d > wmax) ? d : wmax;
-                wmin = (wmin != wmin || d < wmin) ? d : wmin;
-            }
-            if (d != d) { if ((int)x < nc) nc = (int)x; }
-            else if (d < mv || (d == mv && (int)x < mc)) { mv = d; mc = (int)x; }
-        }
-        if (x != psa) {
-            if (rn != NO_COL) { const long long l = x * N + rn; if (l < mine.nan_idx) mine.nan_idx = l; }
-            if (c != NO_COL) {
-                const long long l = x * N + c;
-                if (v < mine.v || (v == mine.v && l < mine.idx)) { mine.v = v; mine.idx = l; }
-            }
-        }
-    }
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) {
-        const double v2 = __shfl_xor(mv, s);
-        const int c2 = __shfl_xor(mc, s), n2 = __shfl_xor(nc, s);
-        if (v2 < mv || (v2 == mv && c2 < mc)) { mv = v2; mc = c2; }
-        nc = n2 < nc ? n2 : nc;
-        const double x = __shfl_xor(wmax, s), y = __shfl_xor(wmin, s);
-        if (x == x && (wmax != wmax || x > wmax)) wmax = x;
-        if (y == y && (wmin != wmin || y < wmin)) wmin = y;
-        ArgMin o;
-        o.v = __shfl_xor(mine.v, s); o.idx = __shfl_xor(mine.idx, s); o.nan_idx = __shfl_xor(mine.nan_idx, s);
-        argmin_merge(mine, o);
-    }
-    if (lane == 0) {
-        rred[wave].mv = mv; rred[wave].mc = mc; rred[wave].nc = nc; rred[wave].wmax = wmax; rred[wave].wmin = wmin;
-        red[wave] = mine;
-    }
-    if (tid < 2) s_cnt[tid] = 0;
-    if (tid == 0) s_nids = 1;
-    __syncthreads();
-    if (tid == 0) {
-        ArgMin b = red[0];
-        for (int w = 1; w < AHC_WAVES; ++w) argmin_merge(b, red[w]);
-        if (psa >= 0) {
-            for (int w = 1; w < AHC_WAVES; ++w) {
-                const RowRed o = rred[w];
-                if (o.mv < mv || (o.mv == mv && o.mc < mc)) { mv = o.mv; mc = o.mc; }
-                nc = o.nc < nc ? o.nc : nc;
-                if (o.wmax == o.wmax && (wmax != wmax || o.wmax > wmax)) wmax = o.wmax;
-                if (o.wmin == o.wmin && (wmin != wmin || o.wmin < wmin)) wmin = o.wmin;
-            }
-            rmin[psa] = mv; rarg[psa] = mc; rnan[psa] = nc;
-            if (variant == 1) {
-                if (wmax == wmax) atomicMax(stat_max + p, dkey(wmax));
-                if (wmin == wmin) atomicMin(stat_min + p, dkey(wmin));
-            }
-            ArgMin own;                              // row psa as a candidate of the arg-min
-            own.v = mc != NO_COL ? mv : __builtin_huge_val();
-            own.idx = mc != NO_COL ? psa * N + mc : INF_IDX;
-            own.nan_idx = nc != NO_COL ? psa * N + nc : INF_IDX;
-            argmin_merge(b, own);
-        }
-        best = b;
-    }
-    __syncthreads();
-    const bool has_nan = best.nan_idx != INF_IDX;
-    const double mind = has_nan ? __builtin_nan("") : best.v;
-    const long long index = has_nan ? best.nan_idx : best.idx;
-    const bool go = (mind <= threshold) || (max_spk > 0 && m > max_spk);
-    const long long r0 = index / N, c0 = index - r0 * N;
-    if (!go || r0 == c0) {
-        if (tid == 0) {
-            if (go) atomicOr(err, ERR_DEGENERATE_MERGE);
-            S->done = 1;
-            S->n_merges = n_merges;
-            S->fmin = mind;
-        }
-        return;
-    }
-    const long long sa = r0 < c0 ? r0 : c0, sb = r0 < c0 ? c0 : r0;
-    // compacted indices = alive slots in front; partner list (any order)
-    // (one LDS atomic per wave and 64 slots; the lanes take their places from the ballot --
-    // an atomic per alive cluster serialised ~4 000 LDS operations per merge on a 10 h file)
-    {
-        int ca = 0, cb = 0;
-        for (long long c0 = 0; c0 < N; c0 += AHC_TPB) {
-            const long long c = c0 + tid;
-            const bool alive_c = c < N && al[c < N ? c : N - 1];
-            if (alive_c && c < sb) { cb++; if (c < sa) ca++; }
-            const bool take = alive_c && c != sa && c != sb;
-            const unsigned long long mk = __ballot(take);
-            int base = 0;
-            if (lane == 0 && mk) base = atomicAdd(&s_nids, __popcll(mk));
-            base = __shfl(base, 0);
-            if (take) ids[base + __popcll(mk & ((1ull << lane) - 1ull))] = (int32_t)c;
-        }
-        // (summed inside the wave first: one LDS atomic per wave, not per thread)
-#pragma unroll
-        for (int s = 1; s < WAVE; s <<= 1) { ca += __shfl_xor(ca, s); cb += __shfl_xor(cb, s); }
-        if (lane == 0 && ca) atomicAdd(&s_cnt[0], ca);
-        if (lane == 0 && cb) atomicAdd(&s_cnt[1], cb);
-    }
-    // ---- 2. merge the statistics
-    double* A = ex + (off + sa) * QREC;
-    const double* B = ex + (off + sb) * QREC;
-    for (int e = tid; e < QREC; e += AHC_TPB) A[e] = A[e] + B[e];
-    {                                                 // the packed copies the pair passes load from
-        double* Ap = pk + (off + sa) * REC;
-        const double* Bp = pk + (off + sb) * REC;
-        for (int e = tid; e < REC; e += AHC_TPB) Ap[e] = Ap[e] + Bp[e];
-    }
-    __syncthreads();
-    const double nA = A[QREC_COUNT_AT];
-    if (kind == SPKD_KL2 && wave == 0) {
-        double a[DA];
-        single_rows_from_qr(A, a);
-        const double mean_i = a[D] / nA;
-        cov_rows(a, nA);
-        kl2_aux_from_cov(a, mean_i, aux + (off + sa) * AUX);
-    }
-    if (tid == 0) {
-        const int64_t o = off + n_merges;
-        out_a[o] = s_cnt[0]; out_b[o] = s_cnt[1]; out_d[o] = mind;
-        al[sb] = 0;
-        ids[0] = (int32_t)sa;
-        S->done = 0;
-        S->sa = sa; S->sb = sb; S->nA = nA; S->nids = s_nids;
-        S->n_merges = n_merges + 1;
-        S->fmin = mind;
-    }
-}
-
-// the first selection of every problem (grid: n_prob)
-__global__ __launch_bounds__(AHC_TPB) void k_ahc_select0(
-        double* __restrict__ ex, double* __restrict__ pk, const int64_t* __restrict__ seg_off,
-        int variant, int kind, int max_spk, double threshold, double* __restrict__ aux,
-        const double* __restrict__ mat, const int64_t* __restrict__ mat_off,
-        int32_t* __restrict__ alive, double* __restrict__ rmin_all,
-        int32_t* __restrict__ rcache_all, int32_t* __restrict__ ids_all,
-        AhcState* __restrict__ state, int32_t* __restrict__ out_a, int32_t* __restrict__ out_b,
-        double* __restrict__ out_d, unsigned long long* stat_max, unsigned long long* stat_min,
-        int* err) {
-    if (threadIdx.x == 0) state[blockIdx.x].ticket = 0;
-    ahc_select_body(0, blockIdx.x, ex, seg_off, variant, kind, max_spk, threshold, aux, mat, mat_off, alive,
-                    rmin_all, rcache_all, ids_all, state, out_a, out_b, out_d, stat_max, stat_min, err, pk);
-}
-
-// partners per workgroup: every wave pass holds four matrices; the first slot of the
-// workgroup's first pass is the merged cluster itself
-constexpr int RND_PARTNERS = 4 * AHC_WAVES - 1;
-
-// one merge round; grid (ceil((n_max - 1) / RND_PARTNERS), n_prob)
-template <bool TWO>
-__global__ __launch_bounds__(AHC_TPB) void k_ahc_round(
-        int it, double* __restrict__ ex, double* __restrict__ pk, const int64_t* __restrict__ seg_off,
-        int variant, int kind, int max_spk, double lambdac, double threshold,
-        double* __restrict__ ld, double* __restrict__ aux,
-        double* __restrict__ mat, const int64_t* __restrict__ mat_off,
-        int32_t* __restrict__ alive, double* __restrict__ rmin_all,
-        int32_t* __restrict__ rcache_all, int32_t* __restrict__ ids_all,
-        AhcState* __restrict__ state, int32_t* __restrict__ out_a, int32_t* __restrict__ out_b,
-        double* __restrict__ out_d, unsigned long long* stat_max, unsigned long long* stat_min,
-        int* err) {
-    __shared__ double ldsA[QREC];
-    __shared__ double s_ldx[4 * AHC_WAVES];
-    __shared__ double s_dfin[4 * AHC_WAVES];
-    __shared__ int s_rescan[4 * AHC_WAVES];
-    __shared__ int s_last;
-    const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-    const QuadLane L = quad_lane();
-    const int p = blockIdx.y;
-    AhcState* S = state + p;
-    if (S->done) return;
-    const int nids = S->nids;                       // 1 + partners
-    const int nb = nids > 1 ? (nids - 1 + RND_PARTNERS - 1) / RND_PARTNERS : 1;
-    if ((int)blockIdx.x >= nb) return;
-    const int64_t off = seg_off[p];
-    const long long N = seg_off[p + 1] - off;
-    const int32_t* ids = ids_all + off;
-    const long long sa = S->sa, sb = S->sb;
-    const double nA = S->nA;
-    const double* A = ex + (off + sa) * QREC;
-    double* Dm = mat + mat_off[p];
-    int32_t* al = alive + off;
-    double* ldp = ld + off;
-    double* rmin = rmin_all + off;
-    int32_t* rarg = rcache_all + 3 * off;
-    int32_t* rnan = rarg + N;
-    // this workgroup's items: item 0 = the merged cluster itself, item j >= 1 = partner
-    // ids[first + j - 1]
-    const int first = 1 + (int)blockIdx.x * RND_PARTNERS;
-    const int mine = nids - first < RND_PARTNERS ? nids - first : RND_PARTNERS;     // partners here (>= 0)
-    if (kind != SPKD_KL2) {
-        for (int e = tid; e < QREC; e += AHC_TPB) ldsA[e] = A[e];
-        __syncthreads();
-        const int base = 4 * wave;                  // items base .. base + 3 of this wave
-        if (base <= mine) {
-            int j = base + L.m;
-            const bool valid = j <= mine;
-            j = valid ? j : mine;
-            const long long cs = j == 0 ? sa : (long long)ids[first + j - 1];
-            const double* C = ex + (off + cs) * QREC;
-            const double v = quad_pair_det<TWO>(kind, ldsA, nA, A, C, pk + (off + cs) * REC, j == 0, L, err);
-            if (valid && L.t == 0) s_ldx[j] = v;          // determinants
-        }
-        __syncthreads();
-    }
-    const double ldA = kind == SPKD_KL2 ? 0.0 : log(s_ldx[0]);
-    if (kind != SPKD_KL2 && blockIdx.x == 0 && tid == 0) ldp[sa] = ldA;      // the merged cluster's cached term
-    // ---- finish this workgroup's distances, row / column sa, the partner rows' caches: one
-    // THREAD per partner (their loads travel together: one memory round trip for the
-    // chunk, where a wave per row made one per row); the rows whose cached minimum was
-    // invalidated are then rescanned, a wave per row
-    {
-        const int j = tid;                           // partner j = 1 .. mine (<= 31: the first wave)
-        bool rescan = false;
-        double d = 0.0;
-        if (j >= 1 && j <= mine) {
-            const long long r = ids[first + j - 1];
-            d = ahc_finish(kind, lambdac, ex, aux, ldp, kind == SPKD_KL2 ? 0.0 : log(s_ldx[j]), off, sa, r, nA, ldA);
-            const int ra = rarg[r], rn = rnan[r];
-            const double rm = rmin[r];
-            Dm[sa * N + r] = d;
-            if (variant == 1) {
-                Dm[r * N + sa] = d;
-                const bool nan_hit = (rn == sa || rn == sb);
-                if (ra == sa || ra == sb || nan_hit) {
-                    if (!nan_hit && d < rm) { rmin[r] = d; rarg[r] = (int)sa; }    // still (or now) the strict row minimum
-                    else rescan = true;
-                } else if (d != d) {
-                    if ((int)sa < rn) rnan[r] = (int)sa;
-                } else if (d < rm || (d == rm && (int)sa < ra)) {
-                    rmin[r] = d; rarg[r] = (int)sa;
-                }
-            } else if (ra == sb || rn == sb) {       // column sa keeps its stale value (A-9)
-                rescan = true;
-            }
-        }
-        if (tid < 4 * AHC_WAVES) { s_rescan[tid] = rescan ? 1 : 0; s_dfin[tid] = d; }
-        __syncthreads();
-        for (int jj = 1 + wave; jj <= mine; jj += AHC_WAVES) {
-            if (!s_rescan[jj]) continue;             // (wave-uniform)
-            const long long r = ids[first + jj - 1];
-            double mv;
-            int mc, nc;
-            // variant 1: the row's own fresh cell (column sa) is taken from the value just computed
-            ahc_scan_row(Dm + r * N, N, al, false, variant == 1 ? sa : -1, s_dfin[jj], lane, mv, mc, nc);
-            if (lane == 0) { rmin[r] = mv; rarg[r] = mc; rnan[r] = nc; }
-        }
-    }
-    // ---- arrival: everything this workgroup wrote is released at agent scope before its
-    // ticket; the last arriver acquires and runs the next selection
-    __syncthreads();                                 // (waits for every wave's stores)
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const int t = atomicAdd(&S->ticket, 1);
-        const int last = (t == nb - 1);
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            S->ticket = 0;
-        }
-        s_last = last;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    ahc_select_body(it, p, ex, seg_off, variant, kind, max_spk, threshold, aux, mat, mat_off, alive,
-                    rmin_all, rcache_all, ids_all, state, out_a, out_b, out_d, stat_max, stat_min, err, pk);
-}
-
-__global__ __launch_bounds__(AHC_TPB) void k_ahc_final(
-        const int64_t* __restrict__ seg_off, const double* __restrict__ mat,
-        const int64_t* __restrict__ mat_off, const int32_t* __restrict__ alive,
-        const AhcState* __restrict__ state, int32_t* __restrict__ out_n,
-        double* __restrict__ final_max, double* __restrict__ final_min) {
-    __shared__ double s_tmax[AHC_WAVES];
-    const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
-    const int p = blockIdx.x;
-    const int64_t off = seg_off[p];
-    const long long N = seg_off[p + 1] - off;
-    const double* Dm = mat + mat_off[p];
-    const int32_t* al = alive + off;
-    double tmax = -__builtin_huge_val();
-    bool anynan = false;
-    for (long long r = wave; r < N; r += AHC_WAVES) {
-        if (!al[r]) continue;
-        const double* row = Dm + r * N;
-        for (long long c = lane; c < N; c += WAVE) {
-            if (!al[c]) continue;
-            const double v = row[c];
-            if (v != v) anynan = true; else tmax = v > tmax ? v : tmax;
-        }
-    }
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) {
-        const double t2 = __shfl_xor(tmax, s);
-        tmax = t2 > tmax ? t2 : tmax;
-    }
-    anynan = __any(anynan);
-    if (lane == 0) s_tmax[wave] = anynan ? __builtin_nan("") : tmax;
-    __syncthreads();
-    if (tid == 0) {
-        double mx = s_tmax[0];
-        for (int w = 1; w < AHC_WAVES; ++w) {
-            const double x = s_tmax[w];
-            if (mx == mx) mx = (x != x) ? x : (x > mx ? x : mx);
-        }
-        out_n[p] = state[p].n_merges;
-        final_max[p] = mx;
-        final_min[p] = state[p].fmin;
-    }
-}
-
-
 // ---------------------------------------------------------------------------
 // The wide form without hand-offs ("step" chain): one launch per merge, NO workgroup waits
 // for or signals another one inside a launch -- the only synchronisation is the kernel
@@ -1478,10 +1035,8 @@ __global__ __launch_bounds__(AHC_TPB) void k_ahc_final(
 //     death >= k), so the mark may land at any time during the round;
 //   * a merged record goes to a fresh slot (N + k - 1); a cluster's current slot is one 64-bit
 //     word (round | new | old) that reads correctly before and after workgroup 0 replaces it.
-// Against the ticket form (k_ahc_round: release fence, ticket, acquire fence, then one
-// workgroup selects while the others have left) a merge loses ~4 us of fences and atomics and
-// three dependent passes of the last arriver: 25.5 -> 14 us per merge at N = 380 (with the
-// selection in integers, the bookkeeper workgroup and three partners a workgroup, below).
+// It replaced a ticket form, in which the last workgroup to arrive selected the next merge
+// alone, at 25.5 us per merge at N = 380 (this form: 14; DESIGN.md par. 3).
 // Arithmetic, tie-breaks and NaN rules are those of k_ahc; results are bit-identical.
 // ---------------------------------------------------------------------------
 constexpr int STEP_WAVES = 4;

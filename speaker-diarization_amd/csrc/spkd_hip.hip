@@ -33,7 +33,6 @@ struct spkd_ctx {
     unsigned long long init_keys[2] = {0ull, ~0ull};
     int step_waves = 0;          // step chain: waves per workgroup (0 = by problem size, 4, 8)
     int step_partners = 0;       // step chain: partners per workgroup (0 = by problem size, 3, 7, 15)
-    int ahc_chain = 0;           // wide merge loop: 0 / 2 = the step chain (no hand-offs), 1 = the ticket chain
     int64_t last_gw_items = 0;
     std::string err;
     int* d_err = nullptr;
@@ -177,7 +176,6 @@ static spkd_status create_ctx(int device, void* stream, bool borrow, spkd_ctx** 
                    hipFuncSetAttribute((const void*)k_gw<1>, hipFuncAttributeMaxDynamicSharedMemorySize, Gw<1>::LDS_BYTES) == hipSuccess;
     // waves per turn of the growing-window kernel: 0 = by the number of turns (gw_impl)
     if (const char* e = getenv("SPKD_GW_WAVES")) c->gw_waves = atoi(e);
-    if (const char* e = getenv("SPKD_AHC_CHAIN")) c->ahc_chain = atoi(e);
     if (const char* e = getenv("SPKD_STEP_WAVES")) { const int v = atoi(e); c->step_waves = (v == 4 || v == 8) ? v : 0; }
     if (const char* e = getenv("SPKD_STEP_PARTNERS")) { const int v = atoi(e); c->step_partners = (v == 3 || v == 7 || v == 15) ? v : 0; }
     *out = c;
@@ -633,6 +631,18 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
         return fail(c, SPKD_EINVAL, "bad variant / kind");
     for (int64_t p = 0; p < n_prob; ++p)
         if (h_seg_off[p + 1] - h_seg_off[p] < 1) return fail(c, SPKD_EINVAL, "empty clustering problem");
+    int64_t n_max = 0;
+    for (int64_t p = 0; p < n_prob; ++p) n_max = std::max<int64_t>(n_max, h_seg_off[p + 1] - h_seg_off[p]);
+    if (n_max > AHC_MAX_N) return fail(c, SPKD_EINVAL, "clustering problem larger than 65536 records");
+    // one workgroup per problem fills the chip only when there are many problems;
+    // with few, the merge loop runs as a chain of launches over all CUs instead
+    int path = P->path;
+    if (path != SPKD_AHC_MONO && path != SPKD_AHC_WIDE) path = n_prob <= 64 ? SPKD_AHC_WIDE : SPKD_AHC_MONO;
+    const size_t lds = (size_t)(n_max + 4) * sizeof(int32_t);
+    if (path == SPKD_AHC_MONO && lds > 150 * 1024) path = SPKD_AHC_WIDE;
+    // (checked before the n x n matrix is built)
+    if (path == SPKD_AHC_WIDE && n_max > STEP_MAX_N)
+        return fail(c, SPKD_EINVAL, "clustering problem larger than 16384 records (wide merge loop)");
     spkd_status st = begin_call(c);
     if (st != SPKD_OK) return st;
     AhcBuffers B;
@@ -641,32 +651,21 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
     std::vector<int64_t> offs;
     std::vector<int32_t> prob_of;
     if ((st = ahc_prepare(c, d_stats, h_seg_off, n_prob, P->variant, P->kind, P->lambdac, B, n_total, offs, prob_of, plan)) != SPKD_OK) return st;
-    int64_t n_max = 0;
-    for (int64_t p = 0; p < n_prob; ++p) n_max = std::max<int64_t>(n_max, h_seg_off[p + 1] - h_seg_off[p]);
-    if (n_max > AHC_MAX_N) return fail(c, SPKD_EINVAL, "clustering problem larger than 65536 records");
     // outputs + per-slot scratch
     void* op = nullptr;
-    const size_t out_bytes = (size_t)n_total * (7 * sizeof(int32_t) + 3 * sizeof(double)) +
-                             (size_t)n_prob * (sizeof(int32_t) + 2 * sizeof(double) + sizeof(AhcState)) + 64;
+    const size_t out_bytes = (size_t)n_total * (6 * sizeof(int32_t) + 3 * sizeof(double)) +
+                             (size_t)n_prob * (sizeof(int32_t) + 2 * sizeof(double)) + 64;
     if ((st = scratch(c, S_AHC_OUT, out_bytes, &op)) != SPKD_OK) return st;
     double* d_merge_d = (double*)op;
     double* d_tmp = d_merge_d + n_total;
     double* d_rmin = d_tmp + n_total;
     double* d_fmax = d_rmin + n_total;
     double* d_fmin = d_fmax + n_prob;
-    AhcState* d_state = (AhcState*)(d_fmin + n_prob);
-    int32_t* d_a = (int32_t*)(d_state + n_prob);
+    int32_t* d_a = (int32_t*)(d_fmin + n_prob);
     int32_t* d_b = d_a + n_total;
     int32_t* d_alive = d_b + n_total;
     int32_t* d_rcache = d_alive + n_total;           // 3 ints per record: arg col, NaN col, dirty
-    int32_t* d_ids = d_rcache + 3 * n_total;         // wide form: partner list per problem
-    int32_t* d_n = d_ids + n_total;
-    // one workgroup per problem fills the chip only when there are many problems;
-    // with few, the merge loop runs as a chain of launches over all CUs instead
-    int path = P->path;
-    if (path != SPKD_AHC_MONO && path != SPKD_AHC_WIDE) path = n_prob <= 64 ? SPKD_AHC_WIDE : SPKD_AHC_MONO;
-    const size_t lds = (size_t)(n_max + 4) * sizeof(int32_t);
-    if (path == SPKD_AHC_MONO && lds > 150 * 1024) path = SPKD_AHC_WIDE;
+    int32_t* d_n = d_rcache + 3 * n_total;
     if (path == SPKD_AHC_MONO) {
         auto kahc = P->kind == SPKD_GLR ? k_ahc<true> : k_ahc<false>;
         if (lds > 48 * 1024)
@@ -676,7 +675,7 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
                                  B.ex, B.pk, (const int64_t*)B.seg_off, P->variant, P->kind, P->max_spk, P->lambdac,
                                  P->threshold, B.ld, B.aux, B.mat, (const int64_t*)B.mat_off, d_alive, d_tmp,
                                  d_rmin, d_rcache, d_n, d_a, d_b, d_merge_d, B.smax, B.smin, d_fmax, d_fmin, c->d_err));
-    } else if (c->ahc_chain != 1 && n_max <= STEP_MAX_N) {
+    } else {
         // the step chain: one launch per merge, every workgroup selects for itself (spkd_cluster.hpp)
         StepArrays Q;
         void *pm = nullptr, *pe = nullptr, *pp = nullptr;
@@ -745,32 +744,6 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
         hipLaunchKernelGGL(k_step_final, dim3((unsigned)n_prob), dim3(AHC_TPB), 0, c->stream,
                            (int)(n_max - 1), (const int64_t*)B.seg_off, (const double*)B.mat, (const int64_t*)B.mat_off,
                            Q, d_n, d_fmax, d_fmin);
-        (void)hipEventRecord(c->kb[SPKD_T_AHC], c->stream);
-        c->kused[SPKD_T_AHC] = true;
-    } else {
-        auto kround = P->kind == SPKD_GLR ? k_ahc_round<true> : k_ahc_round<false>;
-        (void)hipEventRecord(c->ka[SPKD_T_AHC], c->stream);
-        const unsigned row_blocks = (unsigned)((n_max + AHC_WAVES - 1) / AHC_WAVES);
-        hipLaunchKernelGGL(k_ahc_init_rows, dim3(row_blocks, (unsigned)n_prob), dim3(AHC_TPB), 0, c->stream,
-                           (const int64_t*)B.seg_off, (const double*)B.mat, (const int64_t*)B.mat_off, d_alive,
-                           d_rmin, d_rcache);
-        hipLaunchKernelGGL(k_ahc_select0, dim3((unsigned)n_prob), dim3(AHC_TPB), 0, c->stream,
-                           B.ex, B.pk, (const int64_t*)B.seg_off, P->variant, P->kind, P->max_spk, P->threshold, B.aux,
-                           (const double*)B.mat, (const int64_t*)B.mat_off, d_alive, d_rmin, d_rcache, d_ids,
-                           d_state, d_a, d_b, d_merge_d, B.smax, B.smin, c->d_err);
-        // round `it` finishes merge `it` (its distances, row caches) and selects merge it + 1;
-        // after merge `it` a problem of n records has n - it clusters, i.e. n - it - 1 partners
-        for (int64_t it = 1; it < n_max; ++it) {
-            const int64_t partners = n_max - it - 1;
-            const unsigned blocks = (unsigned)std::max<int64_t>(1, (partners + RND_PARTNERS - 1) / RND_PARTNERS);
-            hipLaunchKernelGGL(kround, dim3(blocks, (unsigned)n_prob), dim3(AHC_TPB), 0, c->stream,
-                               (int)it, B.ex, B.pk, (const int64_t*)B.seg_off, P->variant, P->kind, P->max_spk,
-                               P->lambdac, P->threshold, B.ld, B.aux, B.mat, (const int64_t*)B.mat_off, d_alive,
-                               d_rmin, d_rcache, d_ids, d_state, d_a, d_b, d_merge_d, B.smax, B.smin, c->d_err);
-        }
-        hipLaunchKernelGGL(k_ahc_final, dim3((unsigned)n_prob), dim3(AHC_TPB), 0, c->stream,
-                           (const int64_t*)B.seg_off, (const double*)B.mat, (const int64_t*)B.mat_off,
-                           (const int32_t*)d_alive, (const AhcState*)d_state, d_n, d_fmax, d_fmin);
         (void)hipEventRecord(c->kb[SPKD_T_AHC], c->stream);
         c->kused[SPKD_T_AHC] = true;
     }

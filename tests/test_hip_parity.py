@@ -610,3 +610,26 @@ def test_step_chain_shapes_agree(kind, monkeypatch):
             assert [(x, y) for x, y, _ in a.merges] == [(x, y) for x, y, _ in b.merges]
             assert all(d1 == d2 or (math.isnan(d1) and math.isnan(d2)) for (_, _, d1), (_, _, d2) in zip(a.merges, b.merges))
             assert (a.max_dist, a.min_dist) == (b.max_dist, b.min_dist) or (a.max_dist != a.max_dist)
+
+
+def test_wide_merge_loop_refuses_a_problem_above_its_limit():
+    """The hand-off-free merge chain holds at most 16 384 records a problem (a matrix position
+    is packed as row << 14 | column): one problem of 16 385 is refused with SPKD_EINVAL under
+    WIDE and under AUTO, which picks WIDE for a single problem.  The records are allocated in
+    full, so that a check placed after the n x n matrix is built costs time but reads nothing
+    out of bounds."""
+    hipabi = pkg('hipabi')
+    n = 16385
+    ctx = hipabi.Context(0)
+    try:
+        d_st = ctx.dev_alloc(n * hipabi.REC * 8)
+        ctx.h2d(d_st, np.zeros((n, hipabi.REC), dtype=np.float64))
+        for path in (hipabi.AHC_WIDE, hipabi.AHC_AUTO):
+            p = hipabi.AhcParams(1, hipabi.KINDS['BIC'], 0, path, 1.3, 0.0)
+            with pytest.raises(hipabi.SpkdError) as ei:
+                ctx.ahc(d_st, [0, n], p)
+            assert ei.value.status == hipabi.SPKD_EINVAL
+            assert 'clustering problem larger than 16384 records (wide merge loop)' in str(ei.value)
+        ctx.dev_free(d_st)
+    finally:
+        ctx.close()

@@ -13,6 +13,7 @@
 #include <vector>
 #include "spkd_cluster.hpp"
 #include "spkd_tri.hpp"
+#include "packed_columns.hpp"
 using namespace spkd;
 
 constexpr int WINDOW = 387;
