@@ -13,6 +13,7 @@
  *     independent;
  *   - pointer arguments are prefixed d_ (device memory) or h_ (host memory);
  *   - every call returns an spkd_status; spkd_last_error() gives the text;
+ *   - every call returns with the work it enqueued finished, whatever its status;
  *   - all scores are IEEE binary64; frames are binary32 exactly as feacat wrote
  *     them (spk-change-detection.py:37-41).
  *

@@ -61,6 +61,9 @@ spkd_status fail(spkd_ctx* c, spkd_status s, const std::string& msg) {
             return fail((c), SPKD_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// a step that returns an spkd_status: its failure is the caller's
+#define TRY(expr) do { const spkd_status s_ = (expr); if (s_ != SPKD_OK) return s_; } while (0)
+
 // grow-only scratch buffers (no hipMalloc in the steady state)
 spkd_status scratch(spkd_ctx* c, int slot, size_t bytes, void** out) {
     if (bytes == 0) bytes = 16;
@@ -82,47 +85,58 @@ spkd_status scratch(spkd_ctx* c, int slot, size_t bytes, void** out) {
 }
 
 template <class T>
-spkd_status upload(spkd_ctx* c, int slot, const std::vector<T>& h, T** d) {
+spkd_status upload(spkd_ctx* c, int slot, const T* h, size_t n, T** d) {
     void* p = nullptr;
-    spkd_status s = scratch(c, slot, h.size() * sizeof(T), &p);
-    if (s != SPKD_OK) return s;
-    if (!h.empty()) HIPCHK(c, hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    TRY(scratch(c, slot, n * sizeof(T), &p));
+    if (n) HIPCHK(c, hipMemcpyAsync(p, h, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
     *d = (T*)p;
     return SPKD_OK;
 }
 
-#define TIMED(c, idx, launch)                                   \
-    do {                                                         \
-        (void)hipEventRecord((c)->ka[idx], (c)->stream);         \
-        launch;                                                  \
-        (void)hipEventRecord((c)->kb[idx], (c)->stream);         \
-        (c)->kused[idx] = true;                                  \
-    } while (0)
+// The bracket of an entry point that enqueues device work, opened after its argument checks:
+// whatever its status, the call returns with that work finished (include/spkd.h).  finish()
+// waits for the stream, the destructor whenever finish() did not get through.  Host memory that
+// a copy of the call reads or writes is declared before the Call, so that the wait comes first.
+struct Call {
+    spkd_ctx* const c;
+    spkd_status opened;          // of the constructor: TRY(call.opened)
+    int herr = 0;                // the device error word (a member: its copy may be in flight)
+    bool drained = false;
+    explicit Call(spkd_ctx* ctx) : c(ctx) { opened = open(); }
+    ~Call() { if (!drained) (void)hipStreamSynchronize(c->stream); }
+    spkd_status open() {
+        HIPCHK(c, hipSetDevice(c->device));
+        for (int i = 0; i < SPKD_N_TIMERS; ++i) c->kused[i] = false;
+        HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream));
+        HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+        return SPKD_OK;
+    }
 
-spkd_status begin_call(spkd_ctx* c) {
-    HIPCHK(c, hipSetDevice(c->device));
-    for (int i = 0; i < SPKD_N_TIMERS; ++i) c->kused[i] = false;
-    HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(int), c->stream));
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    return SPKD_OK;
-}
+    // records the end event, waits, folds the device error word into a status
+    spkd_status finish() {
+        HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&herr, c->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        drained = true;
+        HIPCHK(c, hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
+        c->kms[0] = c->last_ms;
+        for (int i = 1; i < SPKD_N_TIMERS; ++i)
+            if (c->kused[i]) HIPCHK(c, hipEventElapsedTime(&c->kms[i], c->ka[i], c->kb[i]));
+        if (herr & ERR_SWEEP) return fail(c, SPKD_EHIP, "internal error: growing-window sweep order");
+        if (herr & 4) return fail(c, SPKD_EOVERFLOW, "device scratch capacity exceeded");
+        if (herr & ERR_DEGENERATE_MERGE) return fail(c, SPKD_EINVAL, "degenerate merge: a diagonal cell was the minimum");
+        if (herr & ERR_NONFINITE) return fail(c, SPKD_ENONFINITE, "array must not contain infs or NaNs");
+        return SPKD_OK;
+    }
+};
 
-// records the end event, waits, folds the device error word into a status
-spkd_status end_call(spkd_ctx* c) {
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    int herr = 0;
-    HIPCHK(c, hipMemcpyAsync(&herr, c->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
-    c->kms[0] = c->last_ms;
-    for (int i = 1; i < SPKD_N_TIMERS; ++i)
-        if (c->kused[i]) HIPCHK(c, hipEventElapsedTime(&c->kms[i], c->ka[i], c->kb[i]));
-    if (herr & ERR_SWEEP) return fail(c, SPKD_EHIP, "internal error: growing-window sweep order");
-    if (herr & 4) return fail(c, SPKD_EOVERFLOW, "device scratch capacity exceeded");
-    if (herr & ERR_DEGENERATE_MERGE) return fail(c, SPKD_EINVAL, "degenerate merge: a diagonal cell was the minimum");
-    if (herr & ERR_NONFINITE) return fail(c, SPKD_ENONFINITE, "array must not contain infs or NaNs");
-    return SPKD_OK;
-}
+// times the work its scope enqueues as kernel timer idx (spkd_last_kernel_ms); closes before finish()
+struct Timer {
+    spkd_ctx* const c;
+    const int idx;
+    Timer(spkd_ctx* ctx, int i) : c(ctx), idx(i) { (void)hipEventRecord(c->ka[idx], c->stream); }
+    ~Timer() { (void)hipEventRecord(c->kb[idx], c->stream); c->kused[idx] = true; }
+};
 
 enum {
     S_CHUNKS = 0, S_SETOFF, S_PARTIAL, S_IDXA, S_IDXB, S_TERMS, S_TURNS, S_SNAP, S_CAND,
@@ -269,7 +283,7 @@ namespace {
 spkd_status set_stats_launch(spkd_ctx* c, const float* d_frames, int64_t n_frames,
                              const int64_t* h_begin, const int64_t* h_end, const int32_t* h_set,
                              int64_t n_ranges, int64_t n_sets, double* d_stats,
-                             std::vector<Chunk>& chunks, std::vector<int64_t>& set_off) {   // both must outlive the stream work
+                             std::vector<Chunk>& chunks, std::vector<int64_t>& set_off) {
     chunks.clear();
     set_off.assign((size_t)n_sets + 1, 0);
     int32_t prev = 0;
@@ -289,20 +303,20 @@ spkd_status set_stats_launch(spkd_ctx* c, const float* d_frames, int64_t n_frame
         }
     }
     for (int64_t s = 0; s < n_sets; ++s) set_off[(size_t)s + 1] += set_off[(size_t)s];
-    spkd_status st;
     Chunk* d_chunks = nullptr;
     int64_t* d_setoff = nullptr;
     void* d_partial = nullptr;
-    if ((st = upload(c, S_CHUNKS, chunks, &d_chunks)) != SPKD_OK) return st;
-    if ((st = upload(c, S_SETOFF, set_off, &d_setoff)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_PARTIAL, chunks.size() * REC * sizeof(double), &d_partial)) != SPKD_OK) return st;
-    if (!chunks.empty())
-        TIMED(c, SPKD_T_CHUNK_STATS,
-              hipLaunchKernelGGL(k_chunk_stats, dim3((unsigned)chunks.size()), dim3(STATS_TPB), 0, c->stream,
-                                 d_frames, d_chunks, (double*)d_partial));
-    TIMED(c, SPKD_T_REDUCE_SETS,
-          hipLaunchKernelGGL(k_reduce_sets, dim3((unsigned)n_sets), dim3(STATS_TPB), 0, c->stream,
-                             (const double*)d_partial, d_setoff, d_stats));
+    TRY(upload(c, S_CHUNKS, chunks.data(), chunks.size(), &d_chunks));
+    TRY(upload(c, S_SETOFF, set_off.data(), set_off.size(), &d_setoff));
+    TRY(scratch(c, S_PARTIAL, chunks.size() * REC * sizeof(double), &d_partial));
+    if (!chunks.empty()) {
+        Timer t(c, SPKD_T_CHUNK_STATS);
+        hipLaunchKernelGGL(k_chunk_stats, dim3((unsigned)chunks.size()), dim3(STATS_TPB), 0, c->stream,
+                           d_frames, d_chunks, (double*)d_partial);
+    }
+    Timer t(c, SPKD_T_REDUCE_SETS);                  // (to the end: nothing else is enqueued)
+    hipLaunchKernelGGL(k_reduce_sets, dim3((unsigned)n_sets), dim3(STATS_TPB), 0, c->stream,
+                       (const double*)d_partial, d_setoff, d_stats);
     HIPCHK(c, hipGetLastError());
     return SPKD_OK;
 }
@@ -314,15 +328,12 @@ spkd_status spkd_set_stats(spkd_ctx* c, const float* d_frames, int64_t n_frames,
     if (!c || !d_stats || n_sets < 0 || n_ranges < 0) return SPKD_EINVAL;
     if (n_sets == 0) return SPKD_OK;
     if (n_ranges > 0 && (!h_begin || !h_end || !h_set || !d_frames)) return fail(c, SPKD_EINVAL, "null range arrays");
-    spkd_status st = begin_call(c);
-    if (st != SPKD_OK) return st;
     std::vector<Chunk> chunks;
     std::vector<int64_t> set_off;
-    if ((st = set_stats_launch(c, d_frames, n_frames, h_begin, h_end, h_set, n_ranges, n_sets, d_stats, chunks, set_off)) != SPKD_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        return st;
-    }
-    return end_call(c);
+    Call call(c);
+    TRY(call.opened);
+    TRY(set_stats_launch(c, d_frames, n_frames, h_begin, h_end, h_set, n_ranges, n_sets, d_stats, chunks, set_off));
+    return call.finish();
 }
 
 // ------------------------------------------------------------------ (2) pair terms
@@ -331,21 +342,22 @@ spkd_status spkd_pair_terms(spkd_ctx* c, const double* d_stats, const int32_t* h
     if (!c || n_pairs < 0) return SPKD_EINVAL;
     if (n_pairs == 0) return SPKD_OK;
     if (!d_stats || !h_a || !h_b || !h_terms) return fail(c, SPKD_EINVAL, "null argument");
-    spkd_status st = begin_call(c);
-    if (st != SPKD_OK) return st;
-    std::vector<int32_t> va(h_a, h_a + n_pairs), vb(h_b, h_b + n_pairs);
+    Call call(c);
+    TRY(call.opened);
     int32_t *d_a = nullptr, *d_b = nullptr;
     void* d_terms = nullptr;
-    if ((st = upload(c, S_IDXA, va, &d_a)) != SPKD_OK) return st;
-    if ((st = upload(c, S_IDXB, vb, &d_b)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_TERMS, (size_t)n_pairs * 8 * sizeof(double), &d_terms)) != SPKD_OK) return st;
+    TRY(upload(c, S_IDXA, h_a, (size_t)n_pairs, &d_a));
+    TRY(upload(c, S_IDXB, h_b, (size_t)n_pairs, &d_b));
+    TRY(scratch(c, S_TERMS, (size_t)n_pairs * 8 * sizeof(double), &d_terms));
     const unsigned blocks = (unsigned)((n_pairs + PT2_WAVES - 1) / PT2_WAVES);
-    TIMED(c, SPKD_T_PAIR_TERMS,
-          hipLaunchKernelGGL(k_pair_terms, dim3(blocks), dim3(PT2_WAVES * WAVE), 0, c->stream,
-                             d_stats, d_a, d_b, n_pairs, flags, (double*)d_terms, c->d_err));
+    {
+        Timer t(c, SPKD_T_PAIR_TERMS);
+        hipLaunchKernelGGL(k_pair_terms, dim3(blocks), dim3(PT2_WAVES * WAVE), 0, c->stream,
+                           d_stats, d_a, d_b, n_pairs, flags, (double*)d_terms, c->d_err);
+    }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_terms, d_terms, (size_t)n_pairs * 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    return end_call(c);
+    return call.finish();
 }
 
 // ------------------------------------------------------------------ clustering internals
@@ -379,7 +391,7 @@ struct MatrixPlan {
 
 spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_off, int64_t n_prob,
                         int variant, int kind, double lambdac, AhcBuffers& B, int64_t& n_total,
-                        std::vector<int64_t>& offs, std::vector<int32_t>& prob_of,      // both must outlive the stream work
+                        std::vector<int64_t>& offs, std::vector<int32_t>& prob_of,
                         const MatrixPlan& plan = MatrixPlan()) {
     n_total = h_seg_off[n_prob];
     offs.clear();                                    // seg_off | mat_off
@@ -435,19 +447,18 @@ spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg
     }
     int64_t* d_offs = nullptr;
     int32_t* d_prob = nullptr;
-    spkd_status st;
-    if ((st = upload(c, S_AHC_OFF, offs, &d_offs)) != SPKD_OK) return st;
-    if ((st = upload(c, S_AHC_PROB, prob_of, &d_prob)) != SPKD_OK) return st;
+    TRY(upload(c, S_AHC_OFF, offs.data(), offs.size(), &d_offs));
+    TRY(upload(c, S_AHC_PROB, prob_of.data(), prob_of.size(), &d_prob));
     B.seg_off = d_offs;
     B.mat_off = d_offs + n_prob + 1;
     void* p = nullptr;
-    if ((st = scratch(c, S_AHC_LD, (size_t)n_total * sizeof(double), &p)) != SPKD_OK) return st;
+    TRY(scratch(c, S_AHC_LD, (size_t)n_total * sizeof(double), &p));
     B.ld = (double*)p;
-    if ((st = scratch(c, S_AHC_AUX, (size_t)n_total * AUX * sizeof(double), &p)) != SPKD_OK) return st;
+    TRY(scratch(c, S_AHC_AUX, (size_t)n_total * AUX * sizeof(double), &p));
     B.aux = (double*)p;
-    if ((st = scratch(c, S_AHC_MAT, (size_t)cells * sizeof(double), &p)) != SPKD_OK) return st;
+    TRY(scratch(c, S_AHC_MAT, (size_t)cells * sizeof(double), &p));
     B.mat = (double*)p;
-    if ((st = scratch(c, S_AHC_MISC, (size_t)n_prob * 2 * sizeof(unsigned long long), &p)) != SPKD_OK) return st;
+    TRY(scratch(c, S_AHC_MISC, (size_t)n_prob * 2 * sizeof(unsigned long long), &p));
     B.smax = (unsigned long long*)p;
     B.smin = B.smax + n_prob;
     HIPCHK(c, hipMemsetAsync(B.smax, 0x00, (size_t)n_prob * sizeof(unsigned long long), c->stream));
@@ -461,31 +472,31 @@ spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg
     }
     // a private working copy of the records (clusters are merged in place), expanded to the
     // quad layout the clustering kernels load from
-    if ((st = scratch(c, S_AHC_STATS, (size_t)n_total * QREC * sizeof(double), &p)) != SPKD_OK) return st;
+    TRY(scratch(c, S_AHC_STATS, (size_t)n_total * QREC * sizeof(double), &p));
     B.ex = (double*)p;
-    if ((st = scratch(c, S_AHC_PACKED, (size_t)n_total * REC * sizeof(double), &p)) != SPKD_OK) return st;
+    TRY(scratch(c, S_AHC_PACKED, (size_t)n_total * REC * sizeof(double), &p));
     B.pk = (double*)p;
     if (n_total > 0) {
         hipLaunchKernelGGL(k_to_quadrec, dim3((unsigned)n_total), dim3(256), 0, c->stream, d_stats, n_total, B.ex);
         HIPCHK(c, hipMemcpyAsync(B.pk, d_stats, (size_t)n_total * REC * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    }
-    if (n_total > 0) {
         // KL2: one wave per record; BIC / GLR: four records per wave
         const int64_t per_block = kind == SPKD_KL2 ? PT_WAVES : 4 * PT_WAVES;
         const unsigned blocks = (unsigned)((n_total + per_block - 1) / per_block);
-        TIMED(c, SPKD_T_CLUSTER_PREP,
-              hipLaunchKernelGGL(k_cluster_prep, dim3(blocks), dim3(PT_WAVES * WAVE), 0, c->stream,
-                                 (const double*)B.ex, n_total, kind, B.ld, B.aux, c->d_err));
+        {
+            Timer t(c, SPKD_T_CLUSTER_PREP);
+            hipLaunchKernelGGL(k_cluster_prep, dim3(blocks), dim3(PT_WAVES * WAVE), 0, c->stream,
+                               (const double*)B.ex, n_total, kind, B.ld, B.aux, c->d_err);
+        }
         auto kmat = kind == SPKD_GLR ? k_matrix<true> : k_matrix<false>;   // GLR has a second rank-one term
         if (plan.d_init) {
             HIPCHK(c, hipMemcpyAsync(B.mat, plan.d_init, (size_t)cells * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         } else if (grid_rows > 0) {
-            TIMED(c, SPKD_T_MATRIX,
-                  hipLaunchKernelGGL(kmat, dim3((unsigned)grid_rows), dim3(MX_WAVES * WAVE), 0, c->stream,
-                                     (const double*)B.ex, (const double*)B.pk, (const int64_t*)B.seg_off, (const int32_t*)d_prob,
-                                     (const int32_t*)d_prob + n_total, variant, kind, lambdac,
-                                     (const double*)B.ld, (const double*)B.aux, B.mat, (const int64_t*)B.mat_off,
-                                     B.smax, B.smin, c->d_err));
+            Timer t(c, SPKD_T_MATRIX);
+            hipLaunchKernelGGL(kmat, dim3((unsigned)grid_rows), dim3(MX_WAVES * WAVE), 0, c->stream,
+                               (const double*)B.ex, (const double*)B.pk, (const int64_t*)B.seg_off, (const int32_t*)d_prob,
+                               (const int32_t*)d_prob + n_total, variant, kind, lambdac,
+                               (const double*)B.ld, (const double*)B.aux, B.mat, (const int64_t*)B.mat_off,
+                               B.smax, B.smin, c->d_err);
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -506,16 +517,16 @@ spkd_status spkd_distance_matrix(spkd_ctx* c, int kind, double lambdac, const do
     if (!c || n < 0 || kind < 0 || kind > 2) return SPKD_EINVAL;
     if (n == 0) return SPKD_OK;
     if (!d_stats || !d_matrix) return fail(c, SPKD_EINVAL, "null argument");
-    spkd_status st = begin_call(c);
-    if (st != SPKD_OK) return st;
     const int64_t seg_off[2] = {0, n};
     AhcBuffers B;
     int64_t n_total = 0;
     std::vector<int64_t> offs;
     std::vector<int32_t> prob_of;
-    if ((st = ahc_prepare(c, d_stats, seg_off, 1, 1, kind, lambdac, B, n_total, offs, prob_of)) != SPKD_OK) return st;
+    Call call(c);
+    TRY(call.opened);
+    TRY(ahc_prepare(c, d_stats, seg_off, 1, 1, kind, lambdac, B, n_total, offs, prob_of));
     HIPCHK(c, hipMemcpyAsync(d_matrix, B.mat, (size_t)n * n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    return end_call(c);
+    return call.finish();
 }
 
 spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int kind, double lambdac, double threshold,
@@ -527,19 +538,20 @@ spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int k
     if (n == 0) return SPKD_OK;
     if (!d_stats || !h_label || !h_dist_off || !h_n_done || !h_n_clusters || (dist_cap > 0 && !h_dist))
         return fail(c, SPKD_EINVAL, "null argument");
-    spkd_status st = begin_call(c);
-    if (st != SPKD_OK) return st;
+    long long done2[2] = {0, 0};
+    Call call(c);
+    TRY(call.opened);
     void *p_ex = nullptr, *p_ld = nullptr, *p_aux = nullptr, *p_cex = nullptr, *p_cpk = nullptr, *p_misc = nullptr, *p_dist = nullptr;
     const size_t nn = (size_t)n;
-    if ((st = scratch(c, S_AHC_STATS, nn * QREC * sizeof(double), &p_ex)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_AHC_LD, nn * sizeof(double), &p_ld)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_AHC_AUX, nn * AUX * sizeof(double), &p_aux)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_STEP_EXM, nn * QREC * sizeof(double), &p_cex)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_STEP_PKM, nn * REC * sizeof(double), &p_cpk)) != SPKD_OK) return st;
+    TRY(scratch(c, S_AHC_STATS, nn * QREC * sizeof(double), &p_ex));
+    TRY(scratch(c, S_AHC_LD, nn * sizeof(double), &p_ld));
+    TRY(scratch(c, S_AHC_AUX, nn * AUX * sizeof(double), &p_aux));
+    TRY(scratch(c, S_STEP_EXM, nn * QREC * sizeof(double), &p_cex));
+    TRY(scratch(c, S_STEP_PKM, nn * REC * sizeof(double), &p_cpk));
     // misc: cluster log dets | determinants of a step | cluster KL2 vectors | dist_off | done | labels
     const size_t misc_bytes = (2 + AUX) * nn * sizeof(double) + (nn + 1 + 2) * sizeof(long long) + nn * sizeof(int32_t) + 64;
-    if ((st = scratch(c, S_STEP_MISC, misc_bytes, &p_misc)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_AHC_MAT, (size_t)std::max<int64_t>(dist_cap, 1) * sizeof(double), &p_dist)) != SPKD_OK) return st;
+    TRY(scratch(c, S_STEP_MISC, misc_bytes, &p_misc));
+    TRY(scratch(c, S_AHC_MAT, (size_t)std::max<int64_t>(dist_cap, 1) * sizeof(double), &p_dist));
     double* clu_ld = (double*)p_misc;
     double* tmp = clu_ld + nn;
     double* clu_aux = tmp + nn;
@@ -554,33 +566,34 @@ spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int k
         const unsigned blocks = (unsigned)((n + per_block - 1) / per_block);
         // (the log dets also for KL2: they are what flags a covariance with infs or NaNs, which the
         // reference's pinv refuses like its det)
-        TIMED(c, SPKD_T_CLUSTER_PREP,
-              hipLaunchKernelGGL(k_cluster_prep, dim3(blocks), dim3(PT_WAVES * WAVE), 0, c->stream,
-                                 (const double*)p_ex, n, kind == SPKD_KL2 ? (int)SPKD_BIC : kind, (double*)p_ld, (double*)p_aux, c->d_err));
+        {
+            Timer t(c, SPKD_T_CLUSTER_PREP);
+            hipLaunchKernelGGL(k_cluster_prep, dim3(blocks), dim3(PT_WAVES * WAVE), 0, c->stream,
+                               (const double*)p_ex, n, kind == SPKD_KL2 ? (int)SPKD_BIC : kind, (double*)p_ld, (double*)p_aux, c->d_err);
+        }
         if (kind == SPKD_KL2) {
             void* p_ld2 = nullptr;                       // (the KL2 pass of the same kernel rewrites ld with zeros)
-            if ((st = scratch(c, S_AHC_OUT, nn * sizeof(double), &p_ld2)) != SPKD_OK) return st;
+            TRY(scratch(c, S_AHC_OUT, nn * sizeof(double), &p_ld2));
             const unsigned blocks1 = (unsigned)((n + PT_WAVES - 1) / PT_WAVES);
             hipLaunchKernelGGL(k_cluster_prep, dim3(blocks1), dim3(PT_WAVES * WAVE), 0, c->stream,
                                (const double*)p_ex, n, (int)SPKD_KL2, (double*)p_ld2, (double*)p_aux, c->d_err);
         }
     }
     auto kin = kind == SPKD_GLR ? k_cluster_in<true> : k_cluster_in<false>;
-    (void)hipEventRecord(c->ka[SPKD_T_AHC], c->stream);
-    hipLaunchKernelGGL(kin, dim3(1), dim3(CIN_TPB), 0, c->stream,
-                       (const double*)p_ex, d_stats, (const double*)p_ld, (const double*)p_aux, (long long)n, kind, lambdac, threshold,
-                       (double*)p_cex, (double*)p_cpk, clu_ld, clu_aux, tmp, d_label, (double*)p_dist, (long long)dist_cap,
-                       d_off, d_done, c->d_err);
-    (void)hipEventRecord(c->kb[SPKD_T_AHC], c->stream);
-    c->kused[SPKD_T_AHC] = true;
+    {
+        Timer t(c, SPKD_T_AHC);
+        hipLaunchKernelGGL(kin, dim3(1), dim3(CIN_TPB), 0, c->stream,
+                           (const double*)p_ex, d_stats, (const double*)p_ld, (const double*)p_aux, (long long)n, kind, lambdac, threshold,
+                           (double*)p_cex, (double*)p_cpk, clu_ld, clu_aux, tmp, d_label, (double*)p_dist, (long long)dist_cap,
+                           d_off, d_done, c->d_err);
+    }
     HIPCHK(c, hipGetLastError());
-    long long done2[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(done2, d_done, sizeof done2, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_label, d_label, nn * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_dist_off, d_off, (nn + 1) * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     if (dist_cap > 0)
         HIPCHK(c, hipMemcpyAsync(h_dist, p_dist, (size_t)dist_cap * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    st = end_call(c);
+    const spkd_status st = call.finish();
     *h_n_done = done2[0];
     *h_n_clusters = done2[1];
     return st;
@@ -595,8 +608,6 @@ spkd_status spkd_distance_rows(spkd_ctx* c, int variant, int kind, double lambda
     if (h_stat_min) *h_stat_min = std::nan("");
     if (n == 0 || row_end == row_begin) return SPKD_OK;
     if (!d_stats || !d_rows) return fail(c, SPKD_EINVAL, "null argument");
-    spkd_status st = begin_call(c);
-    if (st != SPKD_OK) return st;
     const int64_t seg_off[2] = {0, n};
     AhcBuffers B;
     int64_t n_total = 0;
@@ -605,13 +616,15 @@ spkd_status spkd_distance_rows(spkd_ctx* c, int variant, int kind, double lambda
     MatrixPlan plan;
     plan.row_begin = row_begin;
     plan.row_end = row_end;
-    if ((st = ahc_prepare(c, d_stats, seg_off, 1, variant, kind, lambdac, B, n_total, offs, prob_of, plan)) != SPKD_OK) return st;
+    unsigned long long keys[2] = {0ull, ~0ull};
+    Call call(c);
+    TRY(call.opened);
+    TRY(ahc_prepare(c, d_stats, seg_off, 1, variant, kind, lambdac, B, n_total, offs, prob_of, plan));
     HIPCHK(c, hipMemcpyAsync(d_rows, B.mat + row_begin * n, (size_t)(row_end - row_begin) * n * sizeof(double),
                              hipMemcpyDeviceToDevice, c->stream));
-    unsigned long long keys[2] = {0ull, ~0ull};
     HIPCHK(c, hipMemcpyAsync(&keys[0], B.smax, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&keys[1], B.smin, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    st = end_call(c);
+    const spkd_status st = call.finish();
     if (h_stat_max) *h_stat_max = key_to_double(keys[0], true);
     if (h_stat_min) *h_stat_min = key_to_double(keys[1], false);
     return st;
@@ -643,19 +656,21 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
     // (checked before the n x n matrix is built)
     if (path == SPKD_AHC_WIDE && n_max > STEP_MAX_N)
         return fail(c, SPKD_EINVAL, "clustering problem larger than 16384 records (wide merge loop)");
-    spkd_status st = begin_call(c);
-    if (st != SPKD_OK) return st;
     AhcBuffers B;
     int64_t n_total = 0;
-    // ahc_prepare expands the records into a private working copy (merged in place)
     std::vector<int64_t> offs;
     std::vector<int32_t> prob_of;
-    if ((st = ahc_prepare(c, d_stats, h_seg_off, n_prob, P->variant, P->kind, P->lambdac, B, n_total, offs, prob_of, plan)) != SPKD_OK) return st;
+    std::vector<unsigned long long> kmax((size_t)n_prob), kmin((size_t)n_prob);
+    std::vector<double> fmax((size_t)n_prob), fmin((size_t)n_prob);
+    Call call(c);
+    TRY(call.opened);
+    // ahc_prepare expands the records into a private working copy (merged in place)
+    TRY(ahc_prepare(c, d_stats, h_seg_off, n_prob, P->variant, P->kind, P->lambdac, B, n_total, offs, prob_of, plan));
     // outputs + per-slot scratch
     void* op = nullptr;
     const size_t out_bytes = (size_t)n_total * (6 * sizeof(int32_t) + 3 * sizeof(double)) +
                              (size_t)n_prob * (sizeof(int32_t) + 2 * sizeof(double)) + 64;
-    if ((st = scratch(c, S_AHC_OUT, out_bytes, &op)) != SPKD_OK) return st;
+    TRY(scratch(c, S_AHC_OUT, out_bytes, &op));
     double* d_merge_d = (double*)op;
     double* d_tmp = d_merge_d + n_total;
     double* d_rmin = d_tmp + n_total;
@@ -670,11 +685,11 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
         auto kahc = P->kind == SPKD_GLR ? k_ahc<true> : k_ahc<false>;
         if (lds > 48 * 1024)
             (void)hipFuncSetAttribute((const void*)kahc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        TIMED(c, SPKD_T_AHC,
-              hipLaunchKernelGGL(kahc, dim3((unsigned)n_prob), dim3(AHC_TPB), lds, c->stream,
-                                 B.ex, B.pk, (const int64_t*)B.seg_off, P->variant, P->kind, P->max_spk, P->lambdac,
-                                 P->threshold, B.ld, B.aux, B.mat, (const int64_t*)B.mat_off, d_alive, d_tmp,
-                                 d_rmin, d_rcache, d_n, d_a, d_b, d_merge_d, B.smax, B.smin, d_fmax, d_fmin, c->d_err));
+        Timer t(c, SPKD_T_AHC);
+        hipLaunchKernelGGL(kahc, dim3((unsigned)n_prob), dim3(AHC_TPB), lds, c->stream,
+                           B.ex, B.pk, (const int64_t*)B.seg_off, P->variant, P->kind, P->max_spk, P->lambdac,
+                           P->threshold, B.ld, B.aux, B.mat, (const int64_t*)B.mat_off, d_alive, d_tmp,
+                           d_rmin, d_rcache, d_n, d_a, d_b, d_merge_d, B.smax, B.smin, d_fmax, d_fmin, c->d_err);
     } else {
         // the step chain: one launch per merge, every workgroup selects for itself (spkd_cluster.hpp)
         StepArrays Q;
@@ -682,9 +697,9 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
         const size_t nt = (size_t)n_total;
         const size_t misc_bytes = nt * 2 * sizeof(StepSel) + nt * sizeof(double) + nt * sizeof(unsigned long long) +
                                   (size_t)2 * n_prob * sizeof(StepState) + nt * sizeof(int32_t) + 64;
-        if ((st = scratch(c, S_STEP_MISC, misc_bytes, &pm)) != SPKD_OK) return st;
-        if ((st = scratch(c, S_STEP_EXM, nt * QREC * sizeof(double), &pe)) != SPKD_OK) return st;
-        if ((st = scratch(c, S_STEP_PKM, nt * REC * sizeof(double), &pp)) != SPKD_OK) return st;
+        TRY(scratch(c, S_STEP_MISC, misc_bytes, &pm));
+        TRY(scratch(c, S_STEP_EXM, nt * QREC * sizeof(double), &pe));
+        TRY(scratch(c, S_STEP_PKM, nt * REC * sizeof(double), &pp));
         Q.ex = B.ex; Q.pk = B.pk; Q.exm = (double*)pe; Q.pkm = (double*)pp;
         Q.sel2 = (StepSel*)pm;
         Q.cnt = (double*)(Q.sel2 + 2 * nt);
@@ -726,7 +741,7 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
         if (step_lds + 20 * 1024 > 48 * 1024)
             for (int v = 0; v < 3; ++v)
                 (void)hipFuncSetAttribute((const void*)kvar[v], hipFuncAttributeMaxDynamicSharedMemorySize, (int)step_lds);
-        (void)hipEventRecord(c->ka[SPKD_T_AHC], c->stream);
+        Timer t(c, SPKD_T_AHC);
         const unsigned row_blocks = (unsigned)((n_max + AHC_WAVES - 1) / AHC_WAVES);
         hipLaunchKernelGGL(k_step_init, dim3(row_blocks, (unsigned)n_prob), dim3(AHC_TPB), 0, c->stream,
                            (const int64_t*)B.seg_off, (const double*)B.mat, (const int64_t*)B.mat_off, Q);
@@ -744,12 +759,8 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
         hipLaunchKernelGGL(k_step_final, dim3((unsigned)n_prob), dim3(AHC_TPB), 0, c->stream,
                            (int)(n_max - 1), (const int64_t*)B.seg_off, (const double*)B.mat, (const int64_t*)B.mat_off,
                            Q, d_n, d_fmax, d_fmin);
-        (void)hipEventRecord(c->kb[SPKD_T_AHC], c->stream);
-        c->kused[SPKD_T_AHC] = true;
     }
     HIPCHK(c, hipGetLastError());
-    std::vector<unsigned long long> kmax((size_t)n_prob), kmin((size_t)n_prob);
-    std::vector<double> fmax((size_t)n_prob), fmin((size_t)n_prob);
     HIPCHK(c, hipMemcpyAsync(h_n_merges, d_n, (size_t)n_prob * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_merge_a, d_a, (size_t)n_total * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_merge_b, d_b, (size_t)n_total * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -758,7 +769,7 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
     HIPCHK(c, hipMemcpyAsync(kmin.data(), B.smin, (size_t)n_prob * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(fmax.data(), d_fmax, (size_t)n_prob * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(fmin.data(), d_fmin, (size_t)n_prob * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    st = end_call(c);
+    const spkd_status st = call.finish();
     for (int64_t p = 0; p < n_prob; ++p) {
         if (P->variant == 1) {
             h_stat_max[p] = key_to_double(kmax[(size_t)p], true);
@@ -869,28 +880,29 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
     if (!c->gw_lds_ok) return fail(c, SPKD_EHIP, "gw: the kernel's dynamic LDS size was not admitted on this device");
     std::vector<TurnDesc> turns;
     int64_t n_cand;
-    spkd_status st = build_turns(c, n_frames, hb, he, n_turns, P, h_ev_off, true, turns, n_cand);
-    if (st != SPKD_OK) return st;
+    TRY(build_turns(c, n_frames, hb, he, n_turns, P, h_ev_off, true, turns, n_cand));
     for (int64_t t = 0; check_capacity && t < n_turns; ++t)
         if (turns[(size_t)t].ev_cap < spkd_gw_event_capacity_p(turns[(size_t)t].len, P))
             return fail(c, SPKD_EINVAL, "gw: event capacity too small, see spkd_gw_event_capacity_p");
-    if ((st = begin_call(c)) != SPKD_OK) return st;
+    unsigned long long cnt2[2] = {0ull, 0ull};
+    Call call(c);
+    TRY(call.opened);
     const int64_t n_ev = h_ev_off[n_turns];
     TurnDesc* d_turns = nullptr;
     void *d_snap = nullptr, *d_cand = nullptr, *d_i32a = nullptr, *d_i32b = nullptr, *d_d0 = nullptr, *d_d1 = nullptr,
          *d_d2 = nullptr, *d_d3 = nullptr, *d_d4 = nullptr, *d_log = nullptr;
-    if ((st = upload(c, S_TURNS, turns, &d_turns)) != SPKD_OK) return st;
+    TRY(upload(c, S_TURNS, turns.data(), turns.size(), &d_turns));
     // one packed record (running moment sums at the split point) per candidate slot
-    if ((st = scratch(c, S_SNAP, (size_t)n_cand * REC * sizeof(double), &d_snap)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_CAND, (size_t)n_cand * 4 * sizeof(double), &d_cand)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_EV_I32A, (size_t)n_turns * sizeof(int32_t), &d_i32a)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_EV_I32B, (size_t)n_ev * sizeof(int32_t), &d_i32b)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_EV_D0, (size_t)n_ev * sizeof(double), &d_d0)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_EV_D1, (size_t)n_ev * sizeof(double), &d_d1)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_EV_D2, (size_t)n_ev * sizeof(double), &d_d2)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_EV_D3, (size_t)n_ev * sizeof(double), &d_d3)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_EV_D4, (size_t)n_turns * sizeof(double), &d_d4)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_LOG, (size_t)std::max<int64_t>(log_cap, 1) * sizeof(spkd_cand_log), &d_log)) != SPKD_OK) return st;
+    TRY(scratch(c, S_SNAP, (size_t)n_cand * REC * sizeof(double), &d_snap));
+    TRY(scratch(c, S_CAND, (size_t)n_cand * 4 * sizeof(double), &d_cand));
+    TRY(scratch(c, S_EV_I32A, (size_t)n_turns * sizeof(int32_t), &d_i32a));
+    TRY(scratch(c, S_EV_I32B, (size_t)n_ev * sizeof(int32_t), &d_i32b));
+    TRY(scratch(c, S_EV_D0, (size_t)n_ev * sizeof(double), &d_d0));
+    TRY(scratch(c, S_EV_D1, (size_t)n_ev * sizeof(double), &d_d1));
+    TRY(scratch(c, S_EV_D2, (size_t)n_ev * sizeof(double), &d_d2));
+    TRY(scratch(c, S_EV_D3, (size_t)n_ev * sizeof(double), &d_d3));
+    TRY(scratch(c, S_EV_D4, (size_t)n_turns * sizeof(double), &d_d4));
+    TRY(scratch(c, S_LOG, (size_t)std::max<int64_t>(log_cap, 1) * sizeof(spkd_cand_log), &d_log));
     // every pointer the kernel dereferences (a null one would be a GPU memory fault, not a status)
     if (!d_turns || !d_snap || !d_cand || !d_i32a || !d_i32b || !d_d0 || !d_d1 || !d_d2 || !d_d3 || !d_d4 ||
         !d_log || !c->d_counter || !c->d_err)
@@ -910,11 +922,13 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
                        (int32_t*)d_i32a, (double*)d_d0, (int32_t*)d_i32b, (double*)d_d1, (double*)d_d2,        \
                        (double*)d_d3, (double*)d_d4, d_seg_stats, (spkd_cand_log*)d_log, (long long)log_cap,   \
                        c->d_counter, c->d_err)
-    TIMED(c, SPKD_T_GW, if (nw == 1) SPKD_GW_LAUNCH(1); else if (nw == 2) SPKD_GW_LAUNCH(2);
-                        else if (nw == 8) SPKD_GW_LAUNCH(8); else SPKD_GW_LAUNCH(4));
+    {
+        Timer t(c, SPKD_T_GW);
+        if (nw == 1) SPKD_GW_LAUNCH(1); else if (nw == 2) SPKD_GW_LAUNCH(2);
+        else if (nw == 8) SPKD_GW_LAUNCH(8); else SPKD_GW_LAUNCH(4);
+    }
 #undef SPKD_GW_LAUNCH
     HIPCHK(c, hipGetLastError());
-    unsigned long long cnt2[2] = {0ull, 0ull};
     unsigned long long& cnt = cnt2[0];
     HIPCHK(c, hipMemcpyAsync(h_n_win, d_i32a, (size_t)n_turns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_win_maxd, d_d0, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -924,7 +938,7 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
     HIPCHK(c, hipMemcpyAsync(h_det_d, d_d3, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_final_start, d_d4, (size_t)n_turns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(cnt2, c->d_counter, sizeof cnt2, hipMemcpyDeviceToHost, c->stream));
-    st = end_call(c);
+    const spkd_status st = call.finish();
     c->last_gw_items = (int64_t)cnt2[1];
     if (h_log_count) *h_log_count = (int64_t)cnt;
     if (h_log && log_cap > 0 && cnt > 0) {
@@ -990,17 +1004,15 @@ spkd_status spkd_gather_stats(spkd_ctx* c, const double* d_src, int64_t n_src, c
         const int64_t d = h_dst_index ? h_dst_index[i] : i;
         if (d < 0 || d >= n_dst) return fail(c, SPKD_EINVAL, "gather: destination index out of range");
     }
-    spkd_status st = begin_call(c);
-    if (st != SPKD_OK) return st;
-    std::vector<int64_t> idx(h_src_index, h_src_index + n);
-    if (h_dst_index) idx.insert(idx.end(), h_dst_index, h_dst_index + n);
-    int64_t* d_idx = nullptr;
-    if ((st = upload(c, S_IDXA, idx, &d_idx)) != SPKD_OK) return st;
+    Call call(c);
+    TRY(call.opened);
+    int64_t *d_si = nullptr, *d_di = nullptr;
+    TRY(upload(c, S_IDXA, h_src_index, (size_t)n, &d_si));
+    if (h_dst_index) TRY(upload(c, S_IDXB, h_dst_index, (size_t)n, &d_di));
     hipLaunchKernelGGL(k_gather_records, dim3((unsigned)n), dim3(256), 0, c->stream, d_src,
-                       (const int64_t*)d_idx, h_dst_index ? (const int64_t*)(d_idx + n) : (const int64_t*)nullptr,
-                       n, d_dst);
+                       (const int64_t*)d_si, (const int64_t*)d_di, n, d_dst);
     HIPCHK(c, hipGetLastError());
-    return end_call(c);       // (idx must outlive the copy: end_call waits for the stream)
+    return call.finish();
 }
 
 namespace {
@@ -1047,36 +1059,29 @@ spkd_status spkd_sw(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
     }
     if (n_d == 0) return SPKD_OK;
     if (2 * n_d > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "sw: too many windows in one call");
-    spkd_status st = begin_call(c);
-    if (st != SPKD_OK) return st;
-    void *d_rec = nullptr, *d_out = nullptr;
-    if ((st = scratch(c, S_SNAP, (size_t)(2 * n_d) * REC * sizeof(double), &d_rec)) != SPKD_OK) return st;
-    if ((st = scratch(c, S_EV_D0, (size_t)n_d * sizeof(double), &d_out)) != SPKD_OK) return st;
     std::vector<Chunk> chunks;
-    std::vector<int64_t> set_off;
-    (void)hipEventRecord(c->ka[SPKD_T_SW], c->stream);
-    if ((st = set_stats_launch(c, d_frames, n_frames, rb.data(), re.data(), rs.data(), 2 * n_d, 2 * n_d, (double*)d_rec,
-                               chunks, set_off)) != SPKD_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        return st;
-    }
-    std::vector<int64_t> seg_off((size_t)n_d + 1);
-    for (int64_t w = 0; w <= n_d; ++w) seg_off[(size_t)w] = 2 * w;
-    AhcBuffers B;
-    int64_t n_total = 0;
-    std::vector<int64_t> offs;
+    std::vector<int64_t> set_off, offs;
     std::vector<int32_t> prob_of;
-    if ((st = ahc_prepare(c, (const double*)d_rec, seg_off.data(), n_d, 1, P->kind, P->lambdac, B, n_total, offs, prob_of)) != SPKD_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        return st;
+    Call call(c);
+    TRY(call.opened);
+    void *d_rec = nullptr, *d_out = nullptr;
+    TRY(scratch(c, S_SNAP, (size_t)(2 * n_d) * REC * sizeof(double), &d_rec));
+    TRY(scratch(c, S_EV_D0, (size_t)n_d * sizeof(double), &d_out));
+    {
+        Timer t(c, SPKD_T_SW);
+        TRY(set_stats_launch(c, d_frames, n_frames, rb.data(), re.data(), rs.data(), 2 * n_d, 2 * n_d, (double*)d_rec,
+                             chunks, set_off));
+        std::vector<int64_t> seg_off((size_t)n_d + 1);
+        for (int64_t w = 0; w <= n_d; ++w) seg_off[(size_t)w] = 2 * w;
+        AhcBuffers B;
+        int64_t n_total = 0;
+        TRY(ahc_prepare(c, (const double*)d_rec, seg_off.data(), n_d, 1, P->kind, P->lambdac, B, n_total, offs, prob_of));
+        hipLaunchKernelGGL(k_take_pair_distance, dim3((unsigned)((n_d + 255) / 256)), dim3(256), 0, c->stream,
+                           (const double*)B.mat, n_d, (double*)d_out);
     }
-    hipLaunchKernelGGL(k_take_pair_distance, dim3((unsigned)((n_d + 255) / 256)), dim3(256), 0, c->stream,
-                       (const double*)B.mat, n_d, (double*)d_out);
-    (void)hipEventRecord(c->kb[SPKD_T_SW], c->stream);
-    c->kused[SPKD_T_SW] = true;
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_d, d_out, (size_t)n_d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    return end_call(c);
+    return call.finish();
 }
 
 // ------------------------------------------------------------------ (6) front-end
@@ -1096,8 +1101,7 @@ spkd_status spkd_mfcc(spkd_ctx* c, const int16_t* d_pcm, int64_t n_samples, cons
         return fail(c, SPKD_EINVAL, "mfcc: unsupported mean-subtraction window or delta parameters");
     const int hop = P->sample_rate / P->frame_rate;
     if (hop < 1) return fail(c, SPKD_EINVAL, "mfcc: frame rate above the sample rate");
-    // everything that can be refused is refused BEFORE the first launch: an early return behind
-    // one would leave the stream with work that references host memory on its way out
+    // everything that can be refused is refused before the call opens: a refusal enqueues nothing
     const int span = MP_FR + 2 * MP_HALO;
     const size_t lds = (size_t)((span + P->cms_left + P->cms_right) * MF_STATIC + 2 * span * MF_STATIC +
                                 MP_FR * MF_DIM + MF_DIM * MF_DIM) * sizeof(float);
@@ -1106,8 +1110,6 @@ spkd_status spkd_mfcc(spkd_ctx* c, const int16_t* d_pcm, int64_t n_samples, cons
     *h_n_frames = T;
     if (T == 0) return SPKD_OK;
     if (!d_pcm || !d_features) return fail(c, SPKD_EINVAL, "mfcc: null device buffer");
-    spkd_status st = begin_call(c);
-    if (st != SPKD_OK) return st;
     // tables: mel filterbank | dct | mean | scale | transform
     std::vector<float> tab;
     tab.insert(tab.end(), h_melfb, h_melfb + MF_MEL * MF_BINS);
@@ -1115,13 +1117,12 @@ spkd_status spkd_mfcc(spkd_ctx* c, const int16_t* d_pcm, int64_t n_samples, cons
     tab.insert(tab.end(), h_mean, h_mean + MF_DIM);
     tab.insert(tab.end(), h_scale, h_scale + MF_DIM);
     tab.insert(tab.end(), h_transform, h_transform + MF_DIM * MF_DIM);
+    Call call(c);
+    TRY(call.opened);
     float* d_tab = nullptr;
     void* d_static = nullptr;
-    if ((st = upload(c, S_MFCC_TAB, tab, &d_tab)) != SPKD_OK ||
-        (st = scratch(c, S_MFCC_STATIC, (size_t)T * MF_STATIC * sizeof(float), &d_static)) != SPKD_OK) {
-        (void)hipStreamSynchronize(c->stream);       // (the upload of `tab` may be in flight)
-        return st;
-    }
+    TRY(upload(c, S_MFCC_TAB, tab.data(), tab.size(), &d_tab));
+    TRY(scratch(c, S_MFCC_STATIC, (size_t)T * MF_STATIC * sizeof(float), &d_static));
     const float* d_fb = d_tab;
     const float* d_dct = d_fb + MF_MEL * MF_BINS;
     const float* d_mean = d_dct + MF_CEP * MF_MEL;
@@ -1132,11 +1133,8 @@ spkd_status spkd_mfcc(spkd_ctx* c, const int16_t* d_pcm, int64_t n_samples, cons
     hipLaunchKernelGGL(k_mfcc_post, dim3((unsigned)((T + MP_FR - 1) / MP_FR)), dim3(MF_TPB), lds, c->stream,
                        (const float*)d_static, (long long)T, P->cms_left, P->cms_right, P->delta_width[0],
                        P->delta_norm[0], P->delta_width[1], P->delta_norm[1], d_mean, d_scale, d_tr, d_features);
-    if (hipGetLastError() != hipSuccess) {
-        (void)hipStreamSynchronize(c->stream);
-        return fail(c, SPKD_EHIP, "mfcc: kernel launch failed");
-    }
-    return end_call(c);        // (tab must outlive the upload: end_call waits for the stream)
+    if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "mfcc: kernel launch failed");
+    return call.finish();
 }
 
 // ------------------------------------------------------------------ (5) host helpers
