@@ -46,7 +46,26 @@ typedef enum {
     SPKD_ENOMEM = 5
 } spkd_status;
 
-typedef enum { SPKD_BIC = 0, SPKD_GLR = 1, SPKD_KL2 = 2 } spkd_kind;
+typedef enum { SPKD_BIC = 0, SPKD_GLR = 1, SPKD_KL2 = 2, SPKD_KL2_PINV = 3 } spkd_kind;
+
+/* KL2 modes.  The reference's kl2 (spk-clustering.py:124-133, spk-change-detection.py:124-133)
+ * uses only diag(scipy.linalg.pinv(S)) of each covariance.
+ *   SPKD_KL2 (the default): diag(S^-1) by an elimination without pivoting; NaN whenever S is
+ *     not positive definite (digital silence, constant stretches, any set of fewer than 40
+ *     frames), so such a distance is NaN where the reference's is finite.
+ *   SPKD_KL2_PINV (opt-in): the reference's pseudo-inverse.  Eigenvalues with
+ *     |lambda| > 39 * eps * max|lambda| are kept (strictly greater: an all-zero covariance
+ *     has a zero pseudo-inverse, as in scipy), diag_i = sum over kept k of V_ik^2 / lambda_k.
+ *     Positive definite covariances with tr(S) tr(S^-1) <= 1e-3 / (39 eps) keep every
+ *     eigenvalue and take the inverse's diagonal as in SPKD_KL2; the others go through a
+ *     one-wave Jacobi eigen-decomposition on the device, which gives NaN if it has not
+ *     converged after 40 sweeps.  Non-finite covariances behave as in SPKD_KL2 and return
+ *     SPKD_ENONFINITE where that does (scipy's pinv refuses them too).  The covariance is
+ *     formed from the sufficient statistics: a constant stretch whose frames are not all
+ *     zero gives a covariance of rounding noise instead of an exact zero, and the distance
+ *     then differs from the reference's (BIC's log det has the same limit).
+ *   The first call in this mode allocates the context's Jacobi workspace (about 26 MB of
+ *   device memory, freed by spkd_destroy). */
 
 typedef struct spkd_ctx spkd_ctx;
 
@@ -107,13 +126,14 @@ spkd_status spkd_set_stats(spkd_ctx *ctx, const float *d_frames, int64_t n_frame
  * host (merge_rec, spk_cluster_in).  For pair p the 8 doubles at h_terms[8*p]:
  *   [0] n1  [1] n2  [2] log det S1  [3] log det S2  [4] log det S(union)
  *   [5] log det((n1 S1 + n2 S2)/N)   (only with SPKD_WANT_GLR, else NaN)
- *   [6] KL2 as coded in the reference (only with SPKD_WANT_KL2, else NaN)
+ *   [6] KL2 as coded in the reference (only with SPKD_WANT_KL2 or SPKD_WANT_KL2_PINV, else NaN)
  *   [7] reserved
  * S = np.cov(rowvar=0) semantics (unbiased); log det = log of the LU
  * determinant: 0 -> -inf, negative -> NaN.
  */
 #define SPKD_WANT_GLR 1
 #define SPKD_WANT_KL2 2
+#define SPKD_WANT_KL2_PINV 4   /* term [6] is SPKD_KL2_PINV's KL2; excludes SPKD_WANT_KL2 (SPKD_EINVAL) */
 spkd_status spkd_pair_terms(spkd_ctx *ctx, const double *d_stats,
                             const int32_t *h_idx_a, const int32_t *h_idx_b,
                             int64_t n_pairs, int flags, double *h_terms);
@@ -129,7 +149,7 @@ spkd_status spkd_distance_matrix(spkd_ctx *ctx, int kind, double lambdac,
  * later record is compared with every cluster so far (the cluster is the distance's first
  * argument, the record its second; a cluster's record is the sum of its members') and joins
  * the first arg-min over the finite distances if that is <= threshold, else founds a cluster.
- * kind: SPKD_BIC, SPKD_GLR or SPKD_KL2.  h_label[n]: 0-based cluster of every record.  h_dist
+ * kind: SPKD_BIC, SPKD_GLR, SPKD_KL2 or SPKD_KL2_PINV.  h_label[n]: 0-based cluster of every record.  h_dist
  * [dist_cap]: all distances in evaluation order, those of record s at h_dist_off[s] ..
  * h_dist_off[s + 1] (h_dist_off[n + 1]) -- the caller replays the reference's prints and
  * statistics from them.  *h_n_done: records processed; < n with SPKD_ENONFINITE (a

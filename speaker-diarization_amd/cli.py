@@ -34,6 +34,11 @@ def _common(p, seg_default, out_default):
     p.add_argument('-fe', dest='feaext', type=str, default='.fea', help='feature file extension')
     p.add_argument('-se', dest='segext', type=str, default='.seg', help='alignment file extension')
     p.add_argument('-f', dest='frame_rate', type=int, default=125, help='frames per second')
+    # long option only: no short form can clash with the reference's flags
+    p.add_argument('--kl2-pinv', dest='kl2_pinv', action='store_true',
+                   help='KL2 with the pseudo-inverse of each covariance, as the reference '
+                        'computes it (default: the inverse, NaN for covariances that are not '
+                        'positive definite)')
 
 
 def build_cd_parser():
@@ -75,9 +80,15 @@ def build_cl_parser(variant):
     return p
 
 
-def _default_engine():
+def _default_engine(kl2_pinv=False):
     from .engine import HipEngine
-    return HipEngine()
+    return HipEngine(kl2_pinv=kl2_pinv)
+
+
+def _check_engine(args, engine):
+    if args.kl2_pinv and engine is not None and not getattr(engine, 'kl2_pinv', False):
+        raise ValueError('--kl2-pinv needs an engine built with kl2_pinv=True '
+                         '(e.g. HipEngine(kl2_pinv=True))')
 
 
 def _run_with_outputs(outfile, segfile, body):
@@ -96,6 +107,7 @@ def main_change_detection(argv=None, engine=None, stdout=None):
     out = stdout or sys.stdout
     say = _say_to(out)
     args = build_cd_parser().parse_args(argv)
+    _check_engine(args, engine)
     say('Reading recipe from:', args.recfile)
     with open(args.recfile, 'r') as f:
         recipe = parse_recipe(f, echo=lambda s: say(s))
@@ -140,7 +152,7 @@ def main_change_detection(argv=None, engine=None, stdout=None):
         say('Disabling LNA renaming')
 
     if engine is None:
-        engine = _default_engine()
+        engine = _default_engine(args.kl2_pinv)
     run = ChangeDetectionRun(engine, opts, args.feapath, args.feaext, say=say)
 
     def body(outf, segf):
@@ -160,6 +172,7 @@ def main_clustering(argv=None, variant=1, engine=None, stdout=None):
     out = stdout or sys.stdout
     say = _say_to(out)
     args = build_cl_parser(variant).parse_args(argv)
+    _check_engine(args, engine)
     say('Reading recipe from:', args.recfile)
     with open(args.recfile, 'r') as f:
         recipe = parse_recipe(f, echo=lambda s: say(s))
@@ -213,7 +226,7 @@ def main_clustering(argv=None, variant=1, engine=None, stdout=None):
         say('Disabling LNA renaming')
 
     if engine is None:
-        engine = _default_engine()
+        engine = _default_engine(args.kl2_pinv)
     run = ClusteringRun(engine, opts, feapath, args.feaext, say=say)
 
     def body(outf, segf):

@@ -696,7 +696,8 @@ __global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void k_gw(
         int32_t* __restrict__ n_win, double* __restrict__ win_maxd, int32_t* __restrict__ win_det,
         double* __restrict__ det_start, double* __restrict__ det_maxi, double* __restrict__ det_d,
         double* __restrict__ final_start, double* __restrict__ seg_stats, spkd_cand_log* clog,
-        long long log_cap, unsigned long long* log_count, int* err) {
+        long long log_cap, unsigned long long* log_count, int* err,
+        double* pinv_ws) {
     extern __shared__ double gw_lds[];
     double* ldsEnd = gw_lds;                         // P(c), tri record
     constexpr int GW_WAVES = NW, GW_TPB = Gw<NW>::TPB;
@@ -853,7 +854,7 @@ __global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void k_gw(
                     const double nn = t ? n2 : n1;
                     const double mean_i = a_[D] / nn;
                     cov_rows(a_, nn);
-                    kl2_lane_terms(a_, mean_i, ds[t], dp[t], mu[t]);
+                    kl2_lane_terms(a_, mean_i, ds[t], dp[t], mu[t], pinv_ws);
                 }
                 const double dist = kl2_combine(ds[0], dp[0], mu[0], ds[1], dp[1], mu[1]);
                 if (lane == 0) c_x[base + job] = dist;

@@ -94,12 +94,13 @@ __device__ __forceinline__ double kl2_from_aux(const double* __restrict__ a1,
 }
 
 // per-lane KL2 ingredients of one record held as covariance rows in a (consumed):
-// ds = S_ii, dp = pinv(S)_ii (inverse; NaN when S is not positive definite),
+// ds = S_ii, dp = pinv(S)_ii (inverse, NaN when S is not positive definite; with a
+// pinv workspace (SPKD_KL2_PINV) the reference's pseudo-inverse, spd_diag_terms_fn),
 // mu = mean_i rounded to float32.
 __device__ __forceinline__ void kl2_lane_terms(double (&a)[DA], double mean_i,
-                                               double& ds, double& dp, double& mu) {
+                                               double& ds, double& dp, double& mu, double* pinv_ws) {
     double out[2];
-    spd_diag_terms_fn(a, out);
+    spd_diag_terms_fn(a, out, pinv_ws);
     ds = out[0];
     dp = out[1];
     mu = (double)(float)mean_i;
@@ -115,9 +116,9 @@ __device__ __forceinline__ double kl2_combine(double s1, double p1, double m1,
 }
 
 __device__ __forceinline__ void kl2_aux_from_cov(double (&a)[DA], double mean_i,
-                                                 double* __restrict__ aux) {
+                                                 double* __restrict__ aux, double* pinv_ws) {
     double ds, dp, mu;
-    kl2_lane_terms(a, mean_i, ds, dp, mu);
+    kl2_lane_terms(a, mean_i, ds, dp, mu, pinv_ws);
     const int lane = lane_id();
     if (lane < D) {
         aux[lane] = ds;
@@ -374,7 +375,8 @@ __device__ __forceinline__ void quad_from_packed_lds(double* lds, const double* 
 __global__ __launch_bounds__(PT2_WAVES * WAVE) void k_pair_terms(
         const double* __restrict__ stats, const int32_t* __restrict__ ia,
         const int32_t* __restrict__ ib, int64_t n_pairs, int flags,
-        double* __restrict__ out, int* err) {
+        double* __restrict__ out, int* err,
+        double* pinv_ws) {
     __shared__ double slabs[PT2_WAVES][2][QREC];
     const int wave = threadIdx.x >> 6;
     const int lane = lane_id();
@@ -446,7 +448,7 @@ __global__ __launch_bounds__(PT2_WAVES * WAVE) void k_pair_terms(
             const double nn = t ? n2 : n1;
             const double mean_i = a[D] / nn;
             cov_rows(a, nn);
-            kl2_lane_terms(a, mean_i, ds[t], dp[t], mu[t]);
+            kl2_lane_terms(a, mean_i, ds[t], dp[t], mu[t], pinv_ws);
         }
         kl = kl2_combine(ds[0], dp[0], mu[0], ds[1], dp[1], mu[1]);
     }
@@ -462,7 +464,8 @@ __global__ __launch_bounds__(PT2_WAVES * WAVE) void k_pair_terms(
 // per-record cached terms: log det S (BIC / GLR) or the KL2 vectors
 __global__ __launch_bounds__(PT_WAVES * WAVE) void k_cluster_prep(
         const double* __restrict__ qr, int64_t n_rec, int kind,
-        double* __restrict__ ld, double* __restrict__ aux, int* err) {
+        double* __restrict__ ld, double* __restrict__ aux, int* err,
+        double* pinv_ws) {
     const int wave = threadIdx.x >> 6;
     const int64_t w = (int64_t)blockIdx.x * PT_WAVES + wave;
     if (kind == SPKD_KL2) {
@@ -473,7 +476,7 @@ __global__ __launch_bounds__(PT_WAVES * WAVE) void k_cluster_prep(
         const double n = qr_count(R);
         const double mean_i = a[D] / n;
         cov_rows(a, n);
-        kl2_aux_from_cov(a, mean_i, aux + w * AUX);
+        kl2_aux_from_cov(a, mean_i, aux + w * AUX, pinv_ws);
         if (lane_id() == 0) ld[w] = 0.0;
         return;
     }
@@ -704,7 +707,8 @@ __global__ __launch_bounds__(AHC_TPB) void k_ahc(
         double* __restrict__ rmin_all, int32_t* __restrict__ rcache_all,
         int32_t* __restrict__ out_n, int32_t* __restrict__ out_a, int32_t* __restrict__ out_b,
         double* __restrict__ out_d, unsigned long long* stat_max, unsigned long long* stat_min,
-        double* __restrict__ final_max, double* __restrict__ final_min, int* err) {
+        double* __restrict__ final_max, double* __restrict__ final_min, int* err,
+        double* pinv_ws) {
     extern __shared__ int32_t ids[];                    // alive partner slots of the merged cluster
     __shared__ double ldsA[QREC];
     __shared__ unsigned long long red3[AHC_WAVES][3];
@@ -871,7 +875,7 @@ __global__ __launch_bounds__(AHC_TPB) void k_ahc(
                 single_rows_from_qr(A, a);
                 const double mean_i = a[D] / nA;
                 cov_rows(a, nA);
-                kl2_aux_from_cov(a, mean_i, aux + (off + sa) * AUX);
+                kl2_aux_from_cov(a, mean_i, aux + (off + sa) * AUX, pinv_ws);
             }
         } else {
             // (the waves take the quads of partners from a counter, not by stride: a wave whose
@@ -1165,7 +1169,8 @@ __global__ __launch_bounds__(SW * WAVE) void k_ahc_step(
         double threshold, double* __restrict__ ld, double* __restrict__ aux,
         double* __restrict__ mat, const int64_t* __restrict__ mat_off, StepArrays Q,
         int32_t* __restrict__ out_a, int32_t* __restrict__ out_b, double* __restrict__ out_d,
-        unsigned long long* stat_max, unsigned long long* stat_min, int* err) {
+        unsigned long long* stat_max, unsigned long long* stat_min, int* err,
+        double* pinv_ws) {
     constexpr int TPB = SW * WAVE;
     extern __shared__ int32_t s_dyn[];               // [N] partner list | [N] current slot of a cluster (-1: dead)
     __shared__ double ldsA[QREC];
@@ -1456,7 +1461,7 @@ __global__ __launch_bounds__(SW * WAVE) void k_ahc_step(
         single_rows_from_qr(ldsA, a);
         const double mean_i = a[D] / nA;
         cov_rows(a, nA);
-        kl2_aux_from_cov(a, mean_i, s_auxA);
+        kl2_aux_from_cov(a, mean_i, s_auxA, pinv_ws);
         if (keeper && lane < D) {
             double* ga = aux + (off + sa) * AUX;
             ga[lane] = s_auxA[lane]; ga[DA + lane] = s_auxA[DA + lane]; ga[2 * DA + lane] = s_auxA[2 * DA + lane];
@@ -1635,7 +1640,8 @@ __global__ __launch_bounds__(CIN_TPB) void k_cluster_in(
         const double* __restrict__ seg_aux, long long n, int kind, double lambdac, double threshold,
         double* __restrict__ clu_ex, double* __restrict__ clu_pk, double* __restrict__ clu_ld, double* __restrict__ clu_aux,
         double* __restrict__ tmp, int32_t* __restrict__ label, double* __restrict__ dist, long long dist_cap,
-        long long* __restrict__ dist_off, long long* __restrict__ done, int* err) {
+        long long* __restrict__ dist_off, long long* __restrict__ done, int* err,
+        double* pinv_ws) {
     __shared__ double ldsA[QREC];
     __shared__ int s_best, s_stop;
     __shared__ double s_mind;
@@ -1717,7 +1723,7 @@ __global__ __launch_bounds__(CIN_TPB) void k_cluster_in(
                     const double nM = ldsA[QREC_COUNT_AT];
                     const double mean_i = a[D] / nM;
                     cov_rows(a, nM);
-                    kl2_aux_from_cov(a, mean_i, clu_aux + (long long)best * AUX);
+                    kl2_aux_from_cov(a, mean_i, clu_aux + (long long)best * AUX, pinv_ws);
                 }
             } else if (TWO && kind == SPKD_GLR) {
                 if (wave == 0) {

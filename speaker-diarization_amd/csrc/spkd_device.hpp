@@ -326,16 +326,194 @@ __device__ __forceinline__ double logdet_formed(double (&a)[DA], int* err, Form 
     return log(det);
 }
 
-// out[0] = S_ii, out[1] = (S^-1)_ii (NaN if S is not positive definite), for the
-// lane's row of the covariance held in rows[] (row-per-lane layout)
-__device__ __noinline__ void spd_diag_terms_fn(const double* rows, double* out) {
+// ---------------------------------------------------------------------------
+// diag(pinv(S)) of a symmetric 39x39 covariance, scipy.linalg.pinv semantics (the
+// reference's kl2, spk-clustering.py:124-133): eigenvalues |lambda| > 39 eps max|lambda|
+// are kept (strictly, so S = 0 gives 0), diag_i = sum over kept k of V_ik^2 / lambda_k.
+//
+// Parallel (round-robin) Jacobi, one wave: step t of a sweep rotates the 20 disjoint pairs
+// (t, 39) and ((t + k) mod 39, (t - k) mod 39), k = 1..19 -- index 39 is a zero dummy, so
+// every pair (p, q) of 0..38 is met once per 39 steps.  A step updates A <- J^T A J and
+// V <- V J as 20 x 20 independent 2 x 2 blocks, each read and written by one lane, so the
+// only ordering a step needs is against the step before.  A and V (2 x 40 x 40 doubles)
+// live in a slab of the context's device workspace: the calling kernels keep their LDS.
+//
+// Workspace: PINV_LOCK_BYTES of lock words, then PINV_XCC x PINV_SLABS_PER_XCC slabs.  A
+// wave takes a free slab of its own XCD's pool (L2s of different XCDs are not coherent
+// inside one launch; a slab never changes XCD within a launch) and writes every cell it
+// will read before reading it, so nothing a previous holder left behind is ever seen.
+// More waves in the fallback on one XCD than it has slabs wait for one (s_sleep between
+// attempts); a holder waits for nothing, so every waiter gets one.
+// ---------------------------------------------------------------------------
+constexpr int PINV_XCC = 8;
+constexpr int PINV_SLABS_PER_XCC = 128;
+constexpr int PINV_SLAB = 2 * DA * DA;                 // doubles: A | V
+constexpr size_t PINV_LOCK_BYTES = (size_t)PINV_XCC * PINV_SLABS_PER_XCC * sizeof(unsigned);
+constexpr size_t PINV_WS_BYTES =
+    PINV_LOCK_BYTES + (size_t)PINV_XCC * PINV_SLABS_PER_XCC * PINV_SLAB * sizeof(double);
+constexpr int PINV_MAX_SWEEPS = 40;                    // not converged by then: NaN
+constexpr int PINV_PAIRS = DA / 2;                     // rotations per step
+constexpr int PINV_BLOCKS = PINV_PAIRS * PINV_PAIRS;   // 2 x 2 blocks per step
+// Fast path: invert_spd succeeded and tr(S) tr(S^-1) <= PINV_FAST_BOUND implies
+// lambda_min / lambda_max > 39 eps (lambda_max <= tr S, lambda_min >= 1 / tr S^-1): every
+// eigenvalue is kept, pinv == inverse.  1e-3 / (39 eps).
+constexpr double PINV_FAST_BOUND = 1e-3 / (39.0 * 2.220446049250313e-16);
+
+// pair k of step t, p < q (pair 0: (t, 39), the identity)
+__device__ __forceinline__ void pinv_pair(int t, int k, int& p, int& q) {
+    int a = t + k, b = t - k;
+    a = a >= D ? a - D : a;
+    b = b < 0 ? b + D : b;
+    p = k == 0 ? t : (a < b ? a : b);
+    q = k == 0 ? D : (a < b ? b : a);
+}
+
+__device__ __forceinline__ double wave_sum64(double v) {
+#pragma unroll
+    for (int m = 1; m < WAVE; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// orders the slab accesses of one step against the next (lanes of one wave read what
+// other lanes wrote): no code motion across it, and the stores have completed
+__device__ __forceinline__ void pinv_step_fence() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __builtin_amdgcn_s_waitcnt(0);
+}
+
+__device__ __noinline__ double pinv_diag_fn(const double* rows, double* ws) {
+    const int lane = lane_id();
     double a[DA];
 #pragma unroll
     for (int j = 0; j < DA; ++j) a[j] = rows[j];
-    out[0] = diag_of(a);
+    if (!rows_finite(a)) return __builtin_nan("");   // (the reference's pinv raises; the caller flags it)
+    // a free slab of this XCD's pool (HW_REG_XCC_ID: hwreg id 20, bits [3:0])
+    unsigned* locks = (unsigned*)ws;
+    const int xcc = __builtin_amdgcn_s_getreg(20 | (3 << 11)) & (PINV_XCC - 1);
+    int slot = 0;
+    if (lane == 0) {
+        int i = (int)((blockIdx.x + blockIdx.y * 7u + (threadIdx.x >> 6) * 13u) % PINV_SLABS_PER_XCC);
+        unsigned* pool = locks + xcc * PINV_SLABS_PER_XCC;
+        while (atomicCAS(pool + i, 0u, 1u) != 0u) {
+            i = i + 1 == PINV_SLABS_PER_XCC ? 0 : i + 1;
+            if (i == 0) __builtin_amdgcn_s_sleep(8);
+        }
+        slot = xcc * PINV_SLABS_PER_XCC + i;
+    }
+    slot = __builtin_amdgcn_readfirstlane(__shfl(slot, 0));
+    double* A = (double*)((char*)ws + PINV_LOCK_BYTES) + (size_t)slot * PINV_SLAB;
+    double* V = A + DA * DA;
+    // A = S with a zero row / column 39, V = I (both symmetric: lane i writes column i,
+    // consecutive lanes consecutive doubles)
+    double fro = 0.0;
+    if (lane < DA) {
+#pragma unroll
+        for (int j = 0; j < DA; ++j) {
+            const double v = (lane < D && j < D) ? a[j] : 0.0;
+            fro = fma(v, v, fro);
+            A[j * DA + lane] = v;
+            V[j * DA + lane] = lane == j ? 1.0 : 0.0;
+        }
+    }
+    // a pair is rotated when |a_pq| > max(1e-15 sqrt|a_pp a_qq|, 1e-15 ||S||_F): the second
+    // term is the rounding floor (the rotations keep regenerating off-diagonal noise of
+    // ~eps ||S|| between the kept and the cut eigenvectors of a singular S); converged = a
+    // sweep without a rotation
+    const double floor_abs = 1e-15 * sqrt(wave_sum64(fro));
+    bool conv = false;
+#pragma unroll 1
+    for (int sweep = 0; sweep < PINV_MAX_SWEEPS && !conv; ++sweep) {
+        bool rotated = false;
+#pragma unroll 1
+        for (int t = 0; t < D; ++t) {
+            // lane k < 20: the rotation of pair k (numerical-recipes form, as oracle/spkd_oracle.c)
+            double cr = 1.0, sr = 0.0;
+            bool rot = false;
+            if (lane > 0 && lane < PINV_PAIRS) {
+                int p, q;
+                pinv_pair(t, lane, p, q);
+                const double apq = A[p * DA + q];
+                const double app = A[p * DA + p], aqq = A[q * DA + q];
+                rot = fabs(apq) > fmax(1e-15 * sqrt(fabs(app * aqq)), floor_abs);
+                if (rot) {
+                    const double th = (aqq - app) / (2.0 * apq);
+                    // (|theta| > 1e150: theta^2 would overflow, t = 1 / (2 theta) to working precision)
+                    const double tt = fabs(th) > 1e150 ? 0.5 / th
+                                    : (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
+                    cr = 1.0 / sqrt(tt * tt + 1.0);
+                    sr = tt * cr;
+                }
+            }
+            if (!__any(rot)) continue;                 // (uniform)
+            rotated = true;
+#pragma unroll
+            for (int it = 0; it < (PINV_BLOCKS + WAVE - 1) / WAVE; ++it) {
+                const int b = lane + WAVE * it;
+                const bool on = b < PINV_BLOCKS;
+                const int P = on ? b / PINV_PAIRS : 0, Q = on ? b - (b / PINV_PAIRS) * PINV_PAIRS : 0;
+                const double cP = __shfl(cr, P), sP = __shfl(sr, P);
+                const double cQ = __shfl(cr, Q), sQ = __shfl(sr, Q);
+                if (on) {
+                    int p, q, r, s;
+                    pinv_pair(t, P, p, q);
+                    pinv_pair(t, Q, r, s);
+                    const double apr = A[p * DA + r], aps = A[p * DA + s];
+                    const double aqr = A[q * DA + r], aqs = A[q * DA + s];
+                    const double vpr = V[p * DA + r], vps = V[p * DA + s];
+                    const double vqr = V[q * DA + r], vqs = V[q * DA + s];
+                    // columns (r, s) by J_Q, then rows (p, q) by J_P^T
+                    const double xpr = cQ * apr - sQ * aps, xps = sQ * apr + cQ * aps;
+                    const double xqr = cQ * aqr - sQ * aqs, xqs = sQ * aqr + cQ * aqs;
+                    A[p * DA + r] = cP * xpr - sP * xqr;
+                    A[q * DA + r] = sP * xpr + cP * xqr;
+                    A[p * DA + s] = cP * xps - sP * xqs;
+                    A[q * DA + s] = sP * xps + cP * xqs;
+                    V[p * DA + r] = cQ * vpr - sQ * vps;
+                    V[p * DA + s] = sQ * vpr + cQ * vps;
+                    V[q * DA + r] = cQ * vqr - sQ * vqs;
+                    V[q * DA + s] = sQ * vqr + cQ * vqs;
+                }
+            }
+            pinv_step_fence();
+        }
+        conv = !rotated;
+    }
+    // eigenvalues on the diagonal; the cut-off; lane i < 39: sum_k V_ik^2 / lambda_k
+    const int li = lane < D ? lane : 0;
+    const double lam = A[li * DA + li];
+    double lmax = lane < D ? fabs(lam) : 0.0;
+#pragma unroll
+    for (int m = 1; m < WAVE; m <<= 1) lmax = fmax(lmax, __shfl_xor(lmax, m));
+    const double cut = 39.0 * 2.220446049250313e-16 * lmax;
+    double acc = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < D; ++k) {
+        const double lk = readlane_d(lam, k);
+        const double v = V[li * DA + k];
+        if (fabs(lk) > cut) acc += v * v / lk;
+    }
+    pinv_step_fence();
+    if (lane == 0) atomicExch(locks + slot, 0u);
+    return conv ? acc : __builtin_nan("");
+}
+
+// out[0] = S_ii, out[1] = (S^-1)_ii (NaN if S is not positive definite), for the
+// lane's row of the covariance held in rows[] (row-per-lane layout).  pinv_ws != nullptr:
+// out[1] = pinv(S)_ii instead -- the inverse's when the fast-path bound holds, else
+// pinv_diag_fn's.
+__device__ __noinline__ void spd_diag_terms_fn(const double* rows, double* out, double* pinv_ws) {
+    double a[DA];
+#pragma unroll
+    for (int j = 0; j < DA; ++j) a[j] = rows[j];
+    const double ds = diag_of(a);
+    out[0] = ds;
     const bool ok = invert_spd(a);
     double dp = diag_of(a);
     if (!ok) dp = __builtin_nan("");
+    if (pinv_ws) {
+        const double tr = wave_sum39(ds) * wave_sum39(dp);   // (NaN when !ok)
+        if (!(ok && tr <= PINV_FAST_BOUND)) dp = pinv_diag_fn(rows, pinv_ws);
+    }
     out[1] = dp;
 }
 

@@ -45,6 +45,10 @@ struct spkd_ctx {
     float kms[SPKD_N_TIMERS] = {};
     void* slot[N_SLOTS] = {};
     size_t slot_bytes[N_SLOTS] = {};
+    // SPKD_KL2_PINV: the Jacobi slabs of spkd_device.hpp (allocated by the first call that asks
+    // for the mode) and what the current call's KL2 kernels get (nullptr: the inverse)
+    void* pinv_ws = nullptr;
+    double* pinv_cur = nullptr;
 };
 
 namespace {
@@ -130,6 +134,25 @@ struct Call {
     }
 };
 
+// The kind of a call that takes one: SPKD_KL2_PINV runs as SPKD_KL2 with the pseudo-inverse
+// workspace handed to the kernels (c->pinv_cur), every other kind with none.  Called after the
+// call's bracket is open (the first use clears the workspace's lock words on the stream).
+spkd_status use_kind(spkd_ctx* c, int kind, int* base) {
+    c->pinv_cur = nullptr;
+    *base = kind;
+    if (kind != SPKD_KL2_PINV) return SPKD_OK;
+    *base = SPKD_KL2;
+    if (!c->pinv_ws) {
+        if (hipMalloc(&c->pinv_ws, PINV_WS_BYTES) != hipSuccess) {
+            c->pinv_ws = nullptr;
+            return fail(c, SPKD_ENOMEM, "pinv workspace allocation failed");
+        }
+        HIPCHK(c, hipMemsetAsync(c->pinv_ws, 0, PINV_LOCK_BYTES, c->stream));
+    }
+    c->pinv_cur = (double*)c->pinv_ws;
+    return SPKD_OK;
+}
+
 // times the work its scope enqueues as kernel timer idx (spkd_last_kernel_ms); closes before finish()
 struct Timer {
     spkd_ctx* const c;
@@ -211,6 +234,7 @@ void spkd_destroy(spkd_ctx* c) {
     for (int i = 0; i < N_SLOTS; ++i)
         if (c->slot[i]) (void)hipFree(c->slot[i]);
     if (c->d_err) (void)hipFree(c->d_err);
+    if (c->pinv_ws) (void)hipFree(c->pinv_ws);
     if (c->d_counter) (void)hipFree(c->d_counter);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -342,8 +366,13 @@ spkd_status spkd_pair_terms(spkd_ctx* c, const double* d_stats, const int32_t* h
     if (!c || n_pairs < 0) return SPKD_EINVAL;
     if (n_pairs == 0) return SPKD_OK;
     if (!d_stats || !h_a || !h_b || !h_terms) return fail(c, SPKD_EINVAL, "null argument");
+    if ((flags & SPKD_WANT_KL2) && (flags & SPKD_WANT_KL2_PINV))
+        return fail(c, SPKD_EINVAL, "pair_terms: SPKD_WANT_KL2 and SPKD_WANT_KL2_PINV exclude each other");
     Call call(c);
     TRY(call.opened);
+    int kind_unused;
+    TRY(use_kind(c, (flags & SPKD_WANT_KL2_PINV) ? (int)SPKD_KL2_PINV : (int)SPKD_KL2, &kind_unused));
+    if (flags & SPKD_WANT_KL2_PINV) flags = (flags & ~SPKD_WANT_KL2_PINV) | SPKD_WANT_KL2;
     int32_t *d_a = nullptr, *d_b = nullptr;
     void* d_terms = nullptr;
     TRY(upload(c, S_IDXA, h_a, (size_t)n_pairs, &d_a));
@@ -353,7 +382,7 @@ spkd_status spkd_pair_terms(spkd_ctx* c, const double* d_stats, const int32_t* h
     {
         Timer t(c, SPKD_T_PAIR_TERMS);
         hipLaunchKernelGGL(k_pair_terms, dim3(blocks), dim3(PT2_WAVES * WAVE), 0, c->stream,
-                           d_stats, d_a, d_b, n_pairs, flags, (double*)d_terms, c->d_err);
+                           d_stats, d_a, d_b, n_pairs, flags, (double*)d_terms, c->d_err, c->pinv_cur);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_terms, d_terms, (size_t)n_pairs * 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -485,7 +514,7 @@ spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg
         {
             Timer t(c, SPKD_T_CLUSTER_PREP);
             hipLaunchKernelGGL(k_cluster_prep, dim3(blocks), dim3(PT_WAVES * WAVE), 0, c->stream,
-                               (const double*)B.ex, n_total, kind, B.ld, B.aux, c->d_err);
+                               (const double*)B.ex, n_total, kind, B.ld, B.aux, c->d_err, c->pinv_cur);
         }
         auto kmat = kind == SPKD_GLR ? k_matrix<true> : k_matrix<false>;   // GLR has a second rank-one term
         if (plan.d_init) {
@@ -514,7 +543,7 @@ double key_to_double(unsigned long long k, bool is_max) {
 
 spkd_status spkd_distance_matrix(spkd_ctx* c, int kind, double lambdac, const double* d_stats,
                                  int64_t n, double* d_matrix) {
-    if (!c || n < 0 || kind < 0 || kind > 2) return SPKD_EINVAL;
+    if (!c || n < 0 || kind < 0 || kind > 3) return SPKD_EINVAL;
     if (n == 0) return SPKD_OK;
     if (!d_stats || !d_matrix) return fail(c, SPKD_EINVAL, "null argument");
     const int64_t seg_off[2] = {0, n};
@@ -524,6 +553,7 @@ spkd_status spkd_distance_matrix(spkd_ctx* c, int kind, double lambdac, const do
     std::vector<int32_t> prob_of;
     Call call(c);
     TRY(call.opened);
+    TRY(use_kind(c, kind, &kind));
     TRY(ahc_prepare(c, d_stats, seg_off, 1, 1, kind, lambdac, B, n_total, offs, prob_of));
     HIPCHK(c, hipMemcpyAsync(d_matrix, B.mat, (size_t)n * n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return call.finish();
@@ -532,7 +562,7 @@ spkd_status spkd_distance_matrix(spkd_ctx* c, int kind, double lambdac, const do
 spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int kind, double lambdac, double threshold,
                             int32_t* h_label, double* h_dist, int64_t dist_cap, int64_t* h_dist_off,
                             int64_t* h_n_done, int64_t* h_n_clusters) {
-    if (!c || n < 0 || dist_cap < 0 || kind < 0 || kind > 2) return SPKD_EINVAL;
+    if (!c || n < 0 || dist_cap < 0 || kind < 0 || kind > 3) return SPKD_EINVAL;
     if (h_n_done) *h_n_done = 0;
     if (h_n_clusters) *h_n_clusters = 0;
     if (n == 0) return SPKD_OK;
@@ -541,6 +571,7 @@ spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int k
     long long done2[2] = {0, 0};
     Call call(c);
     TRY(call.opened);
+    TRY(use_kind(c, kind, &kind));
     void *p_ex = nullptr, *p_ld = nullptr, *p_aux = nullptr, *p_cex = nullptr, *p_cpk = nullptr, *p_misc = nullptr, *p_dist = nullptr;
     const size_t nn = (size_t)n;
     TRY(scratch(c, S_AHC_STATS, nn * QREC * sizeof(double), &p_ex));
@@ -569,14 +600,15 @@ spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int k
         {
             Timer t(c, SPKD_T_CLUSTER_PREP);
             hipLaunchKernelGGL(k_cluster_prep, dim3(blocks), dim3(PT_WAVES * WAVE), 0, c->stream,
-                               (const double*)p_ex, n, kind == SPKD_KL2 ? (int)SPKD_BIC : kind, (double*)p_ld, (double*)p_aux, c->d_err);
+                               (const double*)p_ex, n, kind == SPKD_KL2 ? (int)SPKD_BIC : kind, (double*)p_ld, (double*)p_aux, c->d_err,
+                               c->pinv_cur);
         }
         if (kind == SPKD_KL2) {
             void* p_ld2 = nullptr;                       // (the KL2 pass of the same kernel rewrites ld with zeros)
             TRY(scratch(c, S_AHC_OUT, nn * sizeof(double), &p_ld2));
             const unsigned blocks1 = (unsigned)((n + PT_WAVES - 1) / PT_WAVES);
             hipLaunchKernelGGL(k_cluster_prep, dim3(blocks1), dim3(PT_WAVES * WAVE), 0, c->stream,
-                               (const double*)p_ex, n, (int)SPKD_KL2, (double*)p_ld2, (double*)p_aux, c->d_err);
+                               (const double*)p_ex, n, (int)SPKD_KL2, (double*)p_ld2, (double*)p_aux, c->d_err, c->pinv_cur);
         }
     }
     auto kin = kind == SPKD_GLR ? k_cluster_in<true> : k_cluster_in<false>;
@@ -585,7 +617,7 @@ spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int k
         hipLaunchKernelGGL(kin, dim3(1), dim3(CIN_TPB), 0, c->stream,
                            (const double*)p_ex, d_stats, (const double*)p_ld, (const double*)p_aux, (long long)n, kind, lambdac, threshold,
                            (double*)p_cex, (double*)p_cpk, clu_ld, clu_aux, tmp, d_label, (double*)p_dist, (long long)dist_cap,
-                           d_off, d_done, c->d_err);
+                           d_off, d_done, c->d_err, c->pinv_cur);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(done2, d_done, sizeof done2, hipMemcpyDeviceToHost, c->stream));
@@ -602,7 +634,7 @@ spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int k
 spkd_status spkd_distance_rows(spkd_ctx* c, int variant, int kind, double lambdac, const double* d_stats,
                                int64_t n, int64_t row_begin, int64_t row_end, double* d_rows,
                                double* h_stat_max, double* h_stat_min) {
-    if (!c || n < 0 || kind < 0 || kind > 2 || (variant != 1 && variant != 2)) return SPKD_EINVAL;
+    if (!c || n < 0 || kind < 0 || kind > 3 || (variant != 1 && variant != 2)) return SPKD_EINVAL;
     if (row_begin < 0 || row_end < row_begin || row_end > n) return fail(c, SPKD_EINVAL, "distance_rows: bad row block");
     if (h_stat_max) *h_stat_max = std::nan("");
     if (h_stat_min) *h_stat_min = std::nan("");
@@ -619,6 +651,7 @@ spkd_status spkd_distance_rows(spkd_ctx* c, int variant, int kind, double lambda
     unsigned long long keys[2] = {0ull, ~0ull};
     Call call(c);
     TRY(call.opened);
+    TRY(use_kind(c, kind, &kind));
     TRY(ahc_prepare(c, d_stats, seg_off, 1, variant, kind, lambdac, B, n_total, offs, prob_of, plan));
     HIPCHK(c, hipMemcpyAsync(d_rows, B.mat + row_begin * n, (size_t)(row_end - row_begin) * n * sizeof(double),
                              hipMemcpyDeviceToDevice, c->stream));
@@ -640,7 +673,7 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
     if (!d_stats || !h_seg_off || !h_n_merges || !h_merge_a || !h_merge_b || !h_merge_d ||
         !h_stat_max || !h_stat_min)
         return fail(c, SPKD_EINVAL, "null argument");
-    if ((P->variant != 1 && P->variant != 2) || P->kind < 0 || P->kind > 2)
+    if ((P->variant != 1 && P->variant != 2) || P->kind < 0 || P->kind > 3)
         return fail(c, SPKD_EINVAL, "bad variant / kind");
     for (int64_t p = 0; p < n_prob; ++p)
         if (h_seg_off[p + 1] - h_seg_off[p] < 1) return fail(c, SPKD_EINVAL, "empty clustering problem");
@@ -664,6 +697,9 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
     std::vector<double> fmax((size_t)n_prob), fmin((size_t)n_prob);
     Call call(c);
     TRY(call.opened);
+    spkd_ahc_params Pk = *P;                         // (kind as the kernels take it)
+    TRY(use_kind(c, P->kind, &Pk.kind));
+    P = &Pk;
     // ahc_prepare expands the records into a private working copy (merged in place)
     TRY(ahc_prepare(c, d_stats, h_seg_off, n_prob, P->variant, P->kind, P->lambdac, B, n_total, offs, prob_of, plan));
     // outputs + per-slot scratch
@@ -689,7 +725,8 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
         hipLaunchKernelGGL(kahc, dim3((unsigned)n_prob), dim3(AHC_TPB), lds, c->stream,
                            B.ex, B.pk, (const int64_t*)B.seg_off, P->variant, P->kind, P->max_spk, P->lambdac,
                            P->threshold, B.ld, B.aux, B.mat, (const int64_t*)B.mat_off, d_alive, d_tmp,
-                           d_rmin, d_rcache, d_n, d_a, d_b, d_merge_d, B.smax, B.smin, d_fmax, d_fmin, c->d_err);
+                           d_rmin, d_rcache, d_n, d_a, d_b, d_merge_d, B.smax, B.smin, d_fmax, d_fmin, c->d_err,
+                           c->pinv_cur);
     } else {
         // the step chain: one launch per merge, every workgroup selects for itself (spkd_cluster.hpp)
         StepArrays Q;
@@ -754,7 +791,7 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
             hipLaunchKernelGGL(kstep, dim3(blocks, (unsigned)n_prob), dim3(step_waves * WAVE), step_lds, c->stream,
                                (int)it, (const int64_t*)B.seg_off, P->variant, P->kind, P->max_spk, P->lambdac,
                                P->threshold, B.ld, B.aux, B.mat, (const int64_t*)B.mat_off, Q, d_a, d_b, d_merge_d,
-                               B.smax, B.smin, c->d_err);
+                               B.smax, B.smin, c->d_err, c->pinv_cur);
         }
         hipLaunchKernelGGL(k_step_final, dim3((unsigned)n_prob), dim3(AHC_TPB), 0, c->stream,
                            (int)(n_max - 1), (const int64_t*)B.seg_off, (const double*)B.mat, (const int64_t*)B.mat_off,
@@ -873,7 +910,7 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
     if (!d_frames || !hb || !he || !h_ev_off || !h_n_win || !h_win_maxd || !h_win_det || !h_det_start ||
         !h_det_maxi || !h_det_d || !h_final_start)
         return fail(c, SPKD_EINVAL, "null argument");
-    if (P->kind < 0 || P->kind > 2) return fail(c, SPKD_EINVAL, "gw: bad kind");
+    if (P->kind < 0 || P->kind > 3) return fail(c, SPKD_EINVAL, "gw: bad kind");
     if (!(P->rate >= 10.0) || !(P->winsize >= 1.0) || !(P->winstep >= 1.0))
         return fail(c, SPKD_EINVAL, "gw: rate >= 10, winsize >= 1 frame and winstep >= 1 frame required");
     if (log_cap < 0 || (log_cap > 0 && !h_log)) return fail(c, SPKD_EINVAL, "gw: log capacity without a log buffer");
@@ -887,6 +924,9 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
     unsigned long long cnt2[2] = {0ull, 0ull};
     Call call(c);
     TRY(call.opened);
+    spkd_cd_params Pk = *P;                          // (kind as the kernel takes it)
+    TRY(use_kind(c, P->kind, &Pk.kind));
+    P = &Pk;
     const int64_t n_ev = h_ev_off[n_turns];
     TurnDesc* d_turns = nullptr;
     void *d_snap = nullptr, *d_cand = nullptr, *d_i32a = nullptr, *d_i32b = nullptr, *d_d0 = nullptr, *d_d1 = nullptr,
@@ -921,7 +961,7 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
                        d_frames, (const TurnDesc*)d_turns, *P, (double*)d_snap, (double*)d_cand,               \
                        (int32_t*)d_i32a, (double*)d_d0, (int32_t*)d_i32b, (double*)d_d1, (double*)d_d2,        \
                        (double*)d_d3, (double*)d_d4, d_seg_stats, (spkd_cand_log*)d_log, (long long)log_cap,   \
-                       c->d_counter, c->d_err)
+                       c->d_counter, c->d_err, c->pinv_cur)
     {
         Timer t(c, SPKD_T_GW);
         if (nw == 1) SPKD_GW_LAUNCH(1); else if (nw == 2) SPKD_GW_LAUNCH(2);
@@ -1038,7 +1078,7 @@ spkd_status spkd_sw(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
     if (!c || !P || n_turns < 0) return SPKD_EINVAL;
     if (n_turns == 0) return SPKD_OK;
     if (!d_frames || !hb || !he || !h_d_off || !h_d) return fail(c, SPKD_EINVAL, "null argument");
-    if (P->kind < 0 || P->kind > 2) return fail(c, SPKD_EINVAL, "bad kind");
+    if (P->kind < 0 || P->kind > 3) return fail(c, SPKD_EINVAL, "bad kind");
     if (!(P->winsize >= 1.0) || !(P->winstep >= 1.0)) return fail(c, SPKD_EINVAL, "sw: window and step must be >= 1 frame");
     const int64_t n_d = h_d_off[n_turns];
     std::vector<int64_t> rb, re;
@@ -1064,6 +1104,9 @@ spkd_status spkd_sw(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
     std::vector<int32_t> prob_of;
     Call call(c);
     TRY(call.opened);
+    spkd_cd_params Pk = *P;                          // (kind as the kernels take it)
+    TRY(use_kind(c, P->kind, &Pk.kind));
+    P = &Pk;
     void *d_rec = nullptr, *d_out = nullptr;
     TRY(scratch(c, S_SNAP, (size_t)(2 * n_d) * REC * sizeof(double), &d_rec));
     TRY(scratch(c, S_EV_D0, (size_t)n_d * sizeof(double), &d_out));

@@ -15,8 +15,11 @@ def _f(x):
 
 
 class HipEngine(object):
-    def __init__(self, device=0, stream=None):
+    def __init__(self, device=0, stream=None, kl2_pinv=False):
         self.ctx = hipabi.Context(device, stream)
+        # kl2_pinv: every 'KL2' request runs as the reference's pseudo-inverse KL2 (SPKD_KL2_PINV)
+        # instead of the default inverse, which is NaN off the positive definite cone
+        self._kl2_pinv = bool(kl2_pinv)
         self.d_frames = None
         self.n_frames = 0
         self._owned = []
@@ -30,6 +33,13 @@ class HipEngine(object):
         self._rec_cap = 4096
         self._rec_buf = None
         self._rec_slot = {}
+
+    @property
+    def kl2_pinv(self):
+        return self._kl2_pinv
+
+    def _kind(self, kind):
+        return 'KL2P' if self._kl2_pinv and kind == 'KL2' else kind
 
     # ------------------------------------------------------------- memory
     def _forget_records(self):
@@ -139,7 +149,8 @@ class HipEngine(object):
         for ra, rb in jobs:
             sets.append(ra); sets.append(rb)
         slots = self._record_slots(sets)
-        flags = (hipabi.WANT_GLR if want_glr else 0) | (hipabi.WANT_KL2 if want_kl2 else 0)
+        kl2_flag = hipabi.WANT_KL2_PINV if self._kl2_pinv else hipabi.WANT_KL2
+        flags = (hipabi.WANT_GLR if want_glr else 0) | (kl2_flag if want_kl2 else 0)
         out, st = self.ctx.pair_terms(self._rec_buf, slots[0::2], slots[1::2], flags)
         self._raise_nonfinite(st)
         res = []
@@ -156,14 +167,14 @@ class HipEngine(object):
         way, which raises where the reference does."""
         d = self._stats_of_sets([[s] for s in segs])
         try:
-            label, dists, done, _, _ = self.ctx.cluster_in(d, len(segs), kind, lambdac, threshold)
+            label, dists, done, _, _ = self.ctx.cluster_in(d, len(segs), self._kind(kind), lambdac, threshold)
         finally:
             self.ctx.dev_free(d)
         return label, dists, done
 
     # ------------------------------------------------------------- growing window
     def gw(self, turns, kind, lambdac, threshold, winsize, winstep, deltaws, rate, trace=False):
-        p = hipabi.CdParams(hipabi.KINDS[kind], 1 if trace else 0, lambdac, threshold, winsize,
+        p = hipabi.CdParams(hipabi.KINDS[self._kind(kind)], 1 if trace else 0, lambdac, threshold, winsize,
                             winstep, deltaws, rate)
         b = [t[0] for t in turns]
         e = [t[1] for t in turns]
@@ -203,7 +214,7 @@ class HipEngine(object):
 
     # ------------------------------------------------------------- sliding window
     def sw(self, turns, kind, lambdac, winsize, winstep):
-        p = hipabi.CdParams(hipabi.KINDS[kind], 0, lambdac, 0.0, winsize, winstep, 0.0, 125.0)
+        p = hipabi.CdParams(hipabi.KINDS[self._kind(kind)], 0, lambdac, 0.0, winsize, winstep, 0.0, 125.0)
         b = [t[0] for t in turns]
         e = [t[1] for t in turns]
         st, off, d = self.ctx.sw(self.d_frames, self.n_frames, b, e, p)
@@ -216,7 +227,7 @@ class HipEngine(object):
         d = self._stats_of_sets([[s] for s in segs])
         self.last_ms['stats'] = self.ctx.last_ms()
         try:
-            p = hipabi.AhcParams(variant, hipabi.KINDS[kind], max_spk, self.ahc_path, lambdac, threshold)
+            p = hipabi.AhcParams(variant, hipabi.KINDS[self._kind(kind)], max_spk, self.ahc_path, lambdac, threshold)
             r = self.ctx.ahc(d, [0, len(segs)], p)
             self.last_ms['ahc'] = self.ctx.last_ms()
         finally:

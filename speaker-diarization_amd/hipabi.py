@@ -10,8 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SPKD_HIP_LIBRARY') or os.path.join(HERE, 'csrc', 'libspkd_hip.so')
 
 SPKD_OK, SPKD_EINVAL, SPKD_EHIP, SPKD_ENONFINITE, SPKD_EOVERFLOW, SPKD_ENOMEM = range(6)
-KINDS = {'BIC': 0, 'GLR': 1, 'KL2': 2}
-WANT_GLR, WANT_KL2 = 1, 2
+# 'KL2P': KL2 with the reference's pseudo-inverse (SPKD_KL2_PINV); 'KL2' is the inverse
+KINDS = {'BIC': 0, 'GLR': 1, 'KL2': 2, 'KL2P': 3}
+WANT_GLR, WANT_KL2, WANT_KL2_PINV = 1, 2, 4
 TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pair_terms',
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw'])}
 REC = 820
