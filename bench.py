@@ -3,10 +3,15 @@
 BIC clustering (the exact flags spk-diarization2.py passes) over a batch of
 synthetic 1 h / 4-speaker feature files resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 --dump-outputs writes the rows of every file from the last timed step (seeded inputs: two
 builds run with the same arguments can be compared array for array).
+
+A plain run sets up, warms up, times the K steps and prints the line; the per-kernel figures
+come from the HIP events of those steps.  --full adds everything else, each with runs of its
+own: file 0 against the file-based drop-in scripts before timing, and after the timed steps
+the keys marked (--full) below.  --no-extras and --no-cpu-baseline leave parts of that out.
 
 One process per GPU (torchrun sets RANK / LOCAL_RANK / WORLD_SIZE).  Files are
 independent, so ranks share nothing on the data path: each rank owns its own
@@ -21,14 +26,19 @@ What the line carries besides the contract's keys:
                       `traffic` only from a PMC profile of THIS build (the profile's
                       kernel time must match the one measured now within 5 %), else null
   kernels             the same for every hot kernel
-  hbm_copy_GBps       device-to-device copy rate measured in this run (the achievable
-                      HBM rate next to the 8 TB/s spec)
-  verified            the batch result was compared with the file-based drop-in scripts
-                      before timing, and every timed step reproduced the same digest
-  other_configs       latency of BASELINE.json configs 2, 3 and 5 as single-file calls
-  cpu_baseline        oracle/numpy_engine.py (np.cov + det per distance, like the
+  verified            the last timed step reproduced the rows digest of the first (untimed)
+                      step; with --full, file 0 of that step was also compared with the
+                      file-based drop-in scripts before timing (file0_rows, against)
+  two_batches_in_flight  (--full) the same steps with two batches in flight
+  value_incl_h2d      (--full) the same steps with every batch uploaded from pinned host memory
+  dropin_scripts_wall_s  (--full) the two drop-in scripts as child processes on one file
+  host_driven_modes_1h   (--full) the reference's host-driven modes on one file
+  hbm_copy_GBps       (--full) device-to-device copy rate (the achievable HBM rate next to
+                      the 8 TB/s spec)
+  other_configs       (--full) latency of BASELINE.json configs 2, 3 and 5 as single-file calls
+  cpu_baseline        (--full) oracle/numpy_engine.py (np.cov + det per distance, like the
                       reference) on a bounded sample, this box's host cores
-  cpu_baseline_stats  oracle/spkd_oracle.c (fp64 sufficient statistics, the algorithmic
+  cpu_baseline_stats  (--full) oracle/spkd_oracle.c (fp64 sufficient statistics, the algorithmic
                       twin of the GPU path) on one thread and on the job's CPU share (<= 16)
 """
 import argparse
@@ -81,12 +91,19 @@ def parse():
                          'stream of its own, take the steps in turn; kernels of different batches then share '
                          'the GPU (tails overlap with the next launch) and their HIP-event durations are no '
                          'longer those of a kernel alone.  Default 1: strictly one step at a time; the '
-                         'two-in-flight rate is reported beside it as "two_batches_in_flight"')
+                         'two-in-flight rate is reported beside it as "two_batches_in_flight" (with --full)')
     ap.add_argument('--two-pass', action='store_true',
                     help='read the frames once per stage (k_chunk_stats) instead of the fused single read')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, measure and check everything else (runs of their own, before and '
+                         'after the timed steps): file 0 against the drop-in scripts, two batches in flight, the '
+                         'upload-inclusive rate, the drop-in scripts as child processes, the host-driven modes, the '
+                         'copy rate, the other-config latencies and the CPU baselines')
     ap.add_argument('--cpu-sample-seconds', type=float, default=900.0)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the other-config latencies and the copy rate')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--no-extras', action='store_true',
+                    help='with --full: skip the other GPU measurements (two in flight, uploads, drop-in scripts, '
+                         'host-driven modes, copy rate, other configs)')
     ap.add_argument('--ahc-path', type=int, default=0, help='0 auto, 1 one workgroup per file, 2 chained launches')
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend (nccl = RCCL; gloo for rehearsals)')
     ap.add_argument('--share-device', action='store_true',
@@ -290,7 +307,7 @@ def main():
     T = int(sessions[0][0].shape[0])
     frames = torch.cat([sessions[i % n_distinct][0] for i in range(args.files)])
     files = [pipeline.BatchFile(i * T, T, vad_times(sessions[i % n_distinct][1])) for i in range(args.files)]
-    first_host = (sessions[0][0].cpu().numpy(), sessions[0][1]) if rank == 0 else None
+    first_host = (sessions[0][0].cpu().numpy(), sessions[0][1]) if rank == 0 and args.full else None
     del sessions
     total = args.files * T
     torch.cuda.synchronize()
@@ -354,11 +371,11 @@ def main():
         if world > 1:
             dist.barrier()
 
-    # ---- before timing: the batch result of this rank's first file == the file-based
+    # ---- before timing (--full): the batch result of this rank's first file == the file-based
     # drop-in scripts on the same file (rank 0 only; the scripts re-read the .fea)
-    verified = None
+    verified = {} if rank == 0 else None
     out = step()
-    if rank == 0:
+    if rank == 0 and args.full:
         import re
         import tempfile
         with tempfile.TemporaryDirectory() as tmp:
@@ -373,7 +390,7 @@ def main():
         got = [(a, b, int(c)) for a, b, c in out[0].tolist()]
         if got != want:
             raise SystemExit('bench.py: the batch pipeline and the file-based scripts disagree on file 0')
-        verified = {'file0_rows': len(want), 'against': 'spk-change-detection.py + spk-clustering.py (file based, HIP engine)'}
+        verified.update(file0_rows=len(want), against='spk-change-detection.py + spk-clustering.py (file based, HIP engine)')
     digest0 = rows_digest(out) if out is not None else None
     for _ in range(max(0, args.warmup - 1)):
         out = step()
@@ -508,7 +525,7 @@ def main():
         if ranks_info:
             res['gather_ms'] = ranks_info['gather_ms']           # rank 0, per step (incl. waiting for the slowest rank)
             res['ranks'] = ranks_info
-        if world == 1 and not args.no_extras and depth == 1:
+        if world == 1 and args.full and not args.no_extras and depth == 1:
             # the same job with two batches in flight: a second context on a stream of its own, a
             # host thread per context; the kernels of consecutive batches share the GPU (the tail of
             # one launch runs beside the head of the next), so this is a throughput figure
@@ -530,14 +547,14 @@ def main():
             res['two_batches_in_flight'] = {'value': args.files * (args.seconds / 3600.0) * k2 / dt2,
                                             'unit': 'hours-audio/s', 'steps': k2,
                                             'ms_per_step': round(1e3 * dt2 / k2, 2)}
-        if world == 1 and not args.no_extras and depth == 1:
+        if world == 1 and args.full and not args.no_extras and depth == 1:
             res['value_incl_h2d'] = with_uploads(torch, dev, args, frames, total, files, pipeline, ctx, cl, fused, digest0)
             res['dropin_scripts_wall_s'] = dropin_wall(args, synth, first_host)
             res['host_driven_modes_1h'] = host_driven_modes(args, synth, first_host, local)
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             res['hbm_copy_GBps'] = round(copy_rate(torch, dev), 1)
             res['other_configs'] = other_configs(torch, dev, hipabi, pipeline, synth_device, vad_times, ctx, local)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(args, synth, cli)
             res['cpu_baseline_stats'] = cpu_baseline_stats(args, synth, cli)
         print(json.dumps(res))
