@@ -330,7 +330,8 @@ spkd_status spkd_ahc_matrix(spkd_ctx *ctx, const double *d_stats, int64_t n, con
  * (6) Feature front-end: what `feacat -c fconfig.cfg -H --raw-output x.wav` computes for the
  * reference (spk-diarization2.py:98-100; external AaltoASR C++, not in the reference tree)
  * with the module chain of fconfig.cfg:1-101: pre-emphasis, 400-sample Hamming windows at
- * 125 frames/s, magnitude spectrum, mel filterbank + log, DCT (12 cepstra) and log power,
+ * 125 frames/s (window_width 256, the VAD models' .cfg, is built too: zero-padded to the
+ * same 512-point transform), magnitude spectrum, mel filterbank + log, DCT (12 cepstra) and log power,
  * mean subtraction over +-75 frames, deltas and delta-deltas, normalization, 39x39
  * transform.  PARITY UNPINNED: feacat is not available, the semantics the configuration
  * file leaves open are documented choices (oracle/mfcc_numpy.py).
@@ -348,6 +349,36 @@ spkd_status spkd_mfcc(spkd_ctx *ctx, const int16_t *d_pcm, int64_t n_samples,
                       const spkd_mfcc_params *params, const float *h_melfb, const float *h_dct,
                       const float *h_mean, const float *h_scale, const float *h_transform,
                       float *d_features, int64_t *h_n_frames);
+
+/* ---------------------------------------------------------------------------
+ * (7) Speech / non-speech frame scoring: the per-frame state log-likelihoods that AaltoASR's
+ * `phone_probs` writes for generate_exp.py (generate_exp.py:94-97; external C++, not in the
+ * reference tree) from a diagonal-covariance Gaussian mixture model (.gk / .mc files):
+ *
+ *   score[t][s] = logsumexp_{j in s} ( log_weight[j] + log_norm[k] - 1/2 sum_d (x_td - mean[k][d])^2 inv_var[k][d] ),
+ *   k = kernel[j],  j = state_off[s] .. state_off[s+1] - 1,
+ *   log_norm[k] = -1/2 (dim ln 2pi + sum_d ln var[k][d])     (the caller forms it, and 1/var, ln w, in fp64)
+ *
+ * natural logarithms.  The log-sum-exp takes the state's maximum first; a term whose log weight
+ * is -inf (weight 0) contributes nothing; a state without a contributing term, or whose terms
+ * are all -inf, scores -inf; a NaN term makes the state NaN (non-finite features propagate).
+ * PARITY UNPINNED: phone_probs is not available, the convention is a documented choice.
+ * Limits: dim == 39, 1 <= n_kernels <= 256, 1 <= n_states <= 16, at most n_kernels entries a
+ * state, kernel indices in range, finite means and normalising constants, finite positive
+ * inverse variances, log weights finite or -inf; otherwise SPKD_EINVAL before any device work.
+ * d_features: n_frames x 39 floats in device memory (several files may be concatenated);
+ * d_scores receives n_frames x n_states floats.  The model arrays are host memory. */
+typedef struct {
+    int32_t n_kernels, n_states, dim;
+    const float *mean;        /* [n_kernels][dim] */
+    const float *inv_var;     /* [n_kernels][dim] */
+    const float *log_norm;    /* [n_kernels] */
+    const int32_t *state_off; /* [n_states + 1], CSR offsets into kernel / log_weight */
+    const int32_t *kernel;    /* [state_off[n_states]] kernel index (kernels may be shared) */
+    const float *log_weight;  /* [state_off[n_states]] ln of the mixture weight */
+} spkd_gmm_params;
+spkd_status spkd_gmm_loglik(spkd_ctx *ctx, const float *d_features, int64_t n_frames,
+                            const spkd_gmm_params *params, float *d_scores);
 
 /* ---------------------------------------------------------------------------
  * (5) Host-side helpers of the boundary (no GPU work).
@@ -391,6 +422,25 @@ spkd_status spkd_gw_lines(int64_t n_turns, const int64_t *h_off, const int32_t *
                           const int64_t *h_turn_end, double rate, int text_contract,
                           int64_t n_lines, double *h_times, int64_t *h_frame_b,
                           int64_t *h_frame_e, int64_t *h_index, int32_t *h_line_turn);
+
+/* Host-side: the speech / non-speech decoding of generate_exp.py (its AaltoASR token pass,
+ * generate_exp.py:189-239) for a loop of one-state words, as an exact Viterbi in fp64.
+ * Word j emits state h_word_state[j] of h_scores (n_frames x n_states floats, frame-major, the
+ * .lna layout); a NaN score counts as -inf, a frame whose words all score -inf counts as 0 for
+ * every word.  With the per-word constants the caller forms (stay = ts ln a_jj,
+ * exit = ts ln a_j,exit, enter = lm ln(10) log10 P(j) - ins):
+ *
+ *   d_0(j) = enter_j + obs_0(j)
+ *   d_t(j) = max( d_{t-1}(j) + stay_j , max_i(d_{t-1}(i) + exit_i) + enter_j ) + obs_t(j)
+ *
+ * i over every word, j included.  Ties: staying beats switching, the lowest i, and at the end
+ * the lowest j, win.  Out: the tokens of the best path -- the first frame and the word of every
+ * word it enters, in order (at most n_frames: the caller's arrays hold n_frames entries) -- and
+ * its score max_j d_{T-1}(j) (-inf for no frames).  Limits: 1 <= n_states, n_words <= 16. */
+spkd_status spkd_vad_viterbi(int64_t n_frames, int32_t n_states, const float *h_scores,
+                             int32_t n_words, const int32_t *h_word_state, const double *h_stay,
+                             const double *h_exit, const double *h_enter, int64_t *h_tok_frame,
+                             int32_t *h_tok_word, int64_t *h_n_tokens, double *h_score);
 
 #ifdef __cplusplus
 }

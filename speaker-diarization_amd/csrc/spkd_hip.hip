@@ -17,11 +17,12 @@
 #include "spkd_device.hpp"
 #include "spkd_stats.hpp"
 #include "spkd_mfcc.hpp"
+#include "spkd_vad.hpp"
 
 using namespace spkd;
 
 namespace {
-constexpr int N_SLOTS = 32;
+constexpr int N_SLOTS = 36;
 }
 
 struct spkd_ctx {
@@ -165,7 +166,7 @@ enum {
     S_CHUNKS = 0, S_SETOFF, S_PARTIAL, S_IDXA, S_IDXB, S_TERMS, S_TURNS, S_SNAP, S_CAND,
     S_EV_I32A, S_EV_I32B, S_EV_D0, S_EV_D1, S_EV_D2, S_EV_D3, S_EV_D4, S_LOG,
     S_AHC_STATS, S_AHC_LD, S_AHC_AUX, S_AHC_MAT, S_AHC_MISC, S_AHC_OUT, S_AHC_OFF, S_AHC_PROB, S_AHC_PACKED, S_MFCC_TAB, S_MFCC_STATIC,
-    S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_COUNT
+    S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -1135,9 +1136,9 @@ spkd_status spkd_mfcc(spkd_ctx* c, const int16_t* d_pcm, int64_t n_samples, cons
     *h_n_frames = 0;
     if (n_samples < 0 || !h_melfb || !h_dct || !h_mean || !h_scale || !h_transform)
         return fail(c, SPKD_EINVAL, "mfcc: null argument");
-    if (P->window_width != MF_WIN || P->n_fft != MF_NFFT || P->n_mel != MF_MEL || P->n_cep != MF_CEP ||
-        P->frame_rate <= 0 || P->sample_rate <= 0 || P->sample_rate % P->frame_rate != 0)
-        return fail(c, SPKD_EINVAL, "mfcc: this build does 400-sample windows, a 512-point transform, 21 mel bins, 12 cepstra");
+    if ((P->window_width != MF_WIN && P->window_width != MF_WIN_VAD) || P->n_fft != MF_NFFT || P->n_mel != MF_MEL ||
+        P->n_cep != MF_CEP || P->frame_rate <= 0 || P->sample_rate <= 0 || P->sample_rate % P->frame_rate != 0)
+        return fail(c, SPKD_EINVAL, "mfcc: this build does 400- or 256-sample windows, a 512-point transform, 21 mel bins, 12 cepstra");
     if (P->cms_left < 0 || P->cms_right < 0 || P->cms_left + P->cms_right > 1024 || P->delta_width[0] < 1 ||
         P->delta_width[0] > 2 || P->delta_width[1] < 1 || P->delta_width[1] > 2 || !(P->delta_norm[0] > 0.f) ||
         !(P->delta_norm[1] > 0.f))
@@ -1171,12 +1172,70 @@ spkd_status spkd_mfcc(spkd_ctx* c, const int16_t* d_pcm, int64_t n_samples, cons
     const float* d_mean = d_dct + MF_CEP * MF_MEL;
     const float* d_scale = d_mean + MF_DIM;
     const float* d_tr = d_scale + MF_DIM;
-    hipLaunchKernelGGL(k_mfcc_static, dim3((unsigned)((T + MF_FR - 1) / MF_FR)), dim3(MF_TPB), 0, c->stream,
-                       d_pcm, (long long)n_samples, (long long)T, hop, P->pre_emph, d_fb, d_dct, (float*)d_static);
+    if (P->window_width == MF_WIN)
+        hipLaunchKernelGGL(k_mfcc_static<MF_WIN>, dim3((unsigned)((T + MF_FR - 1) / MF_FR)), dim3(MF_TPB), 0, c->stream,
+                           d_pcm, (long long)n_samples, (long long)T, hop, P->pre_emph, d_fb, d_dct, (float*)d_static);
+    else
+        hipLaunchKernelGGL(k_mfcc_static<MF_WIN_VAD>, dim3((unsigned)((T + MF_FR - 1) / MF_FR)), dim3(MF_TPB), 0,
+                           c->stream, d_pcm, (long long)n_samples, (long long)T, hop, P->pre_emph, d_fb, d_dct,
+                           (float*)d_static);
     hipLaunchKernelGGL(k_mfcc_post, dim3((unsigned)((T + MP_FR - 1) / MP_FR)), dim3(MF_TPB), lds, c->stream,
                        (const float*)d_static, (long long)T, P->cms_left, P->cms_right, P->delta_width[0],
                        P->delta_norm[0], P->delta_width[1], P->delta_norm[1], d_mean, d_scale, d_tr, d_features);
     if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "mfcc: kernel launch failed");
+    return call.finish();
+}
+
+// ------------------------------------------------------------------ (7) speech / non-speech scoring
+spkd_status spkd_gmm_loglik(spkd_ctx* c, const float* d_features, int64_t n_frames, const spkd_gmm_params* P,
+                            float* d_scores) {
+    if (!c || !P) return SPKD_EINVAL;
+    const int K = P->n_kernels, S = P->n_states;
+    if (P->dim != GM_DIM || K < 1 || K > GM_MAX_K || S < 1 || S > GM_MAX_S || n_frames < 0)
+        return fail(c, SPKD_EINVAL, "gmm_loglik: dim must be 39, 1 <= kernels <= 256, 1 <= states <= 16");
+    if (!P->mean || !P->inv_var || !P->log_norm || !P->state_off || !P->kernel || !P->log_weight)
+        return fail(c, SPKD_EINVAL, "gmm_loglik: null model array");
+    if (P->state_off[0] != 0) return fail(c, SPKD_EINVAL, "gmm_loglik: state_off[0] must be 0");
+    for (int s = 0; s < S; ++s)
+        if (P->state_off[s + 1] < P->state_off[s] || P->state_off[s + 1] - P->state_off[s] > K)
+            return fail(c, SPKD_EINVAL, "gmm_loglik: state_off must be non-decreasing, at most 256 kernels a state");
+    const int nnz = P->state_off[S];
+    for (int j = 0; j < nnz; ++j) {
+        const float lw = P->log_weight[j];
+        if (P->kernel[j] < 0 || P->kernel[j] >= K || std::isnan(lw) || lw == INFINITY)
+            return fail(c, SPKD_EINVAL, "gmm_loglik: kernel index out of range or log weight NaN / +inf");
+    }
+    for (int64_t i = 0; i < (int64_t)K * GM_DIM; ++i)
+        if (!std::isfinite(P->mean[i]) || !std::isfinite(P->inv_var[i]) || !(P->inv_var[i] > 0.f))
+            return fail(c, SPKD_EINVAL, "gmm_loglik: means must be finite, inverse variances finite and positive");
+    for (int k = 0; k < K; ++k)
+        if (!std::isfinite(P->log_norm[k])) return fail(c, SPKD_EINVAL, "gmm_loglik: non-finite normalising constant");
+    if (n_frames == 0) return SPKD_OK;
+    if (!d_features || !d_scores) return fail(c, SPKD_EINVAL, "gmm_loglik: null device buffer");
+    const int64_t n_blocks = (n_frames + GM_TPB - 1) / GM_TPB;
+    if (n_blocks > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "gmm_loglik: too many frames in one call");
+    // tables: mean | inverse variance | normalising constant | log weight;  state_off | kernel
+    std::vector<float> tab;
+    tab.insert(tab.end(), P->mean, P->mean + (size_t)K * GM_DIM);
+    tab.insert(tab.end(), P->inv_var, P->inv_var + (size_t)K * GM_DIM);
+    tab.insert(tab.end(), P->log_norm, P->log_norm + K);
+    tab.insert(tab.end(), P->log_weight, P->log_weight + nnz);
+    std::vector<int32_t> idx(P->state_off, P->state_off + S + 1);
+    idx.insert(idx.end(), P->kernel, P->kernel + nnz);
+    Call call(c);
+    TRY(call.opened);
+    float* d_tab = nullptr;
+    int32_t* d_idx = nullptr;
+    TRY(upload(c, S_GMM_TAB, tab.data(), tab.size(), &d_tab));
+    TRY(upload(c, S_GMM_IDX, idx.data(), idx.size(), &d_idx));
+    const float* d_mean = d_tab;
+    const float* d_iv = d_mean + (size_t)K * GM_DIM;
+    const float* d_c = d_iv + (size_t)K * GM_DIM;
+    const float* d_lw = d_c + K;
+    hipLaunchKernelGGL(k_gmm_loglik, dim3((unsigned)n_blocks), dim3(GM_TPB), 0, c->stream, d_features,
+                       (long long)n_frames, d_mean, d_iv, d_c, (const int*)d_idx, (const int*)(d_idx + S + 1), d_lw,
+                       S, d_scores);
+    if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "gmm_loglik: kernel launch failed");
     return call.finish();
 }
 
@@ -1335,6 +1394,68 @@ spkd_status spkd_gw_lines(int64_t n_turns, const int64_t* h_off, const int32_t* 
     }
     if (i != n_lines) return SPKD_EINVAL;
     if (text_contract) spkd_py2_roundtrip(h_times, 2 * n_lines);
+    return SPKD_OK;
+}
+
+// Exact Viterbi over a loop of one-state words (include/spkd.h).  Sums and comparisons only, in
+// the order the header gives, so that a restatement in fp64 reproduces every bit.
+spkd_status spkd_vad_viterbi(int64_t n_frames, int32_t n_states, const float* h_scores, int32_t n_words,
+                             const int32_t* h_word_state, const double* h_stay, const double* h_exit,
+                             const double* h_enter, int64_t* h_tok_frame, int32_t* h_tok_word, int64_t* h_n_tokens,
+                             double* h_score) {
+    if (!h_n_tokens || !h_score || n_frames < 0 || n_states < 1 || n_states > GM_MAX_S || n_words < 1 ||
+        n_words > GM_MAX_S || !h_word_state || !h_stay || !h_exit || !h_enter)
+        return SPKD_EINVAL;
+    *h_n_tokens = 0;
+    *h_score = -INFINITY;
+    for (int32_t j = 0; j < n_words; ++j)
+        if (h_word_state[j] < 0 || h_word_state[j] >= n_states) return SPKD_EINVAL;
+    if (n_frames == 0) return SPKD_OK;
+    if (!h_scores || !h_tok_frame || !h_tok_word) return SPKD_EINVAL;
+    const int W = n_words;
+    std::vector<int8_t> back((size_t)n_frames * W);     // -1: stayed in the word, i: entered from word i
+    double d[GM_MAX_S], nd[GM_MAX_S], obs[GM_MAX_S];
+    for (int64_t t = 0; t < n_frames; ++t) {
+        bool all_ninf = true;
+        for (int j = 0; j < W; ++j) {
+            const double o = (double)h_scores[t * n_states + h_word_state[j]];
+            obs[j] = std::isnan(o) ? -INFINITY : o;
+            all_ninf = all_ninf && obs[j] == -INFINITY;
+        }
+        if (all_ninf)
+            for (int j = 0; j < W; ++j) obs[j] = 0.0;
+        if (t == 0) {
+            for (int j = 0; j < W; ++j) { d[j] = h_enter[j] + obs[j]; back[(size_t)j] = -1; }
+            continue;
+        }
+        double best = d[0] + h_exit[0];
+        int bi = 0;
+        for (int i = 1; i < W; ++i) {
+            const double v = d[i] + h_exit[i];
+            if (v > best) { best = v; bi = i; }
+        }
+        for (int j = 0; j < W; ++j) {
+            const double stay = d[j] + h_stay[j], sw = best + h_enter[j];
+            int8_t& b = back[(size_t)t * W + j];
+            if (stay >= sw) { nd[j] = stay + obs[j]; b = -1; }
+            else { nd[j] = sw + obs[j]; b = (int8_t)bi; }
+        }
+        for (int j = 0; j < W; ++j) d[j] = nd[j];
+    }
+    int j = 0;
+    for (int i = 1; i < W; ++i)
+        if (d[i] > d[j]) j = i;
+    *h_score = d[j];
+    // backtrack: a token at every frame where the path enters a word (and at frame 0)
+    int64_t n = 0;
+    for (int64_t t = n_frames - 1; t >= 0; --t) {
+        const int8_t b = back[(size_t)t * W + j];
+        if (t == 0 || b >= 0) { h_tok_frame[n] = t; h_tok_word[n] = j; ++n; }
+        if (t > 0 && b >= 0) j = b;
+    }
+    std::reverse(h_tok_frame, h_tok_frame + n);
+    std::reverse(h_tok_word, h_tok_word + n);
+    *h_n_tokens = n;
     return SPKD_OK;
 }
 

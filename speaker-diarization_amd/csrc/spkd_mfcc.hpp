@@ -4,7 +4,9 @@
 // PARITY UNPINNED (feacat is not available): the module semantics the configuration file
 // does not spell out are the choices listed in oracle/mfcc_numpy.py, which this restates.
 //
-//   k_mfcc_static : workgroup per 8 frames.  Pre-emphasis + Hamming window into LDS, then a
+//   k_mfcc_static : templated on the window width (400: fconfig.cfg; 256: the VAD model's
+//                   .cfg, zero-padded to the same 512-point transform).
+//                   workgroup per 8 frames.  Pre-emphasis + Hamming window into LDS, then a
 //                   direct 512-point DFT (thread k = bin k, the 8 frames share every twiddle;
 //                   205 k MAC per frame is 1.5 ms per audio-hour -- no FFT needed), magnitude,
 //                   mel filterbank, log, DCT, log power -> static [T][13]
@@ -17,7 +19,8 @@
 
 namespace spkd {
 
-constexpr int MF_WIN = 400;          // samples per window
+constexpr int MF_WIN = 400;          // samples per window (fconfig.cfg)
+constexpr int MF_WIN_VAD = 256;      // samples per window (the VAD model's .cfg)
 constexpr int MF_NFFT = 512;
 constexpr int MF_BINS = MF_NFFT / 2 + 1;
 constexpr int MF_MEL = 21;
@@ -28,11 +31,13 @@ constexpr int MF_FR = 8;             // frames per workgroup (static stage)
 constexpr int MF_TPB = 256;
 constexpr float MF_FLOOR = 1e-10f;
 
+template <int WIN>
 __global__ __launch_bounds__(MF_TPB) void k_mfcc_static(
         const int16_t* __restrict__ pcm, long long n_samples, long long n_frames, int hop, float pre_emph,
         const float* __restrict__ melfb /* [MF_MEL][MF_BINS] */, const float* __restrict__ dct /* [MF_CEP][MF_MEL] */,
         float* __restrict__ stat /* [T][13] */) {
-    __shared__ float y[MF_FR][MF_WIN];
+    static_assert(WIN <= MF_NFFT, "the window is zero-padded to the transform length");
+    __shared__ float y[MF_FR][WIN];
     __shared__ float tw_c[MF_NFFT], tw_s[MF_NFFT];
     __shared__ float mag[MF_FR][MF_BINS + 3];
     __shared__ float lmel[MF_FR][MF_MEL + 3];
@@ -45,15 +50,15 @@ __global__ __launch_bounds__(MF_TPB) void k_mfcc_static(
         tw_c[n] = (float)cos(a);
         tw_s[n] = (float)sin(a);
     }
-    for (int e = tid; e < MF_FR * MF_WIN; e += MF_TPB) {
-        const int f = e / MF_WIN, n = e - f * MF_WIN;
+    for (int e = tid; e < MF_FR * WIN; e += MF_TPB) {
+        const int f = e / WIN, n = e - f * WIN;
         const long long t = t0 + f;
         float v = 0.0f;
         if (t < n_frames) {
-            long long i = t * hop - MF_WIN / 2 + n;
+            long long i = t * hop - WIN / 2 + n;
             long long ic = i < 0 ? 0 : (i >= n_samples ? n_samples - 1 : i);
             long long ip = i - 1 < 0 ? 0 : (i - 1 >= n_samples ? n_samples - 1 : i - 1);
-            const double w = 0.54 - 0.46 * cos(two_pi * (double)n / (double)(MF_WIN - 1));
+            const double w = 0.54 - 0.46 * cos(two_pi * (double)n / (double)(WIN - 1));
             v = (float)(((double)pcm[ic] - (double)pre_emph * (double)pcm[ip]) * w);
         }
         y[f][n] = v;
@@ -65,7 +70,7 @@ __global__ __launch_bounds__(MF_TPB) void k_mfcc_static(
 #pragma unroll
         for (int f = 0; f < MF_FR; ++f) { re[f] = 0.0f; im[f] = 0.0f; }
         int ph = 0;                                   // (k * n) mod 512
-        for (int n = 0; n < MF_WIN; ++n) {
+        for (int n = 0; n < WIN; ++n) {
             const float c = tw_c[ph], s = tw_s[ph];
             ph = (ph + k) & (MF_NFFT - 1);
 #pragma unroll

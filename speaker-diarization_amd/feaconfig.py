@@ -79,6 +79,10 @@ class FeatureConfig(object):
              ('delta', ['delta']), ('merge', ['mean_subtractor', 'delta', 'delta']),
              ('normalization', ['merge']), ('lin_transform', ['normalization'])]
 
+    # window widths the device code is built for: fconfig.cfg's 400 and the VAD models' 256
+    # (both zero-padded to the one 512-point transform)
+    WINDOWS = (400, 256)
+
     def _check_supported(self, mods):
         """Raises ValueError unless the configuration is the supported chain with the supported
         switches: magnitude 1, zeroth 0, copy_borders 1, n_mel / n_fft / window as built."""
@@ -86,8 +90,9 @@ class FeatureConfig(object):
             if getattr(self, key) != want:
                 raise ValueError('feature configuration: %s %d is not supported (this build computes %s %d)'
                                  % (key, getattr(self, key), key, want))
-        if self.window_width != 400 or self.n_cep != 12:
-            raise ValueError('feature configuration: this build does 400-sample windows and 12 cepstra')
+        if self.window_width not in self.WINDOWS or self.n_cep != 12:
+            raise ValueError('feature configuration: this build does %s-sample windows and 12 cepstra'
+                             % ' or '.join(str(w) for w in self.WINDOWS))
         by_name = {m['name'][0]: m for m in mods if 'name' in m}
         got = []
         for m in mods:

@@ -48,31 +48,45 @@ def read_wav(path):
         return np.frombuffer(w.readframes(w.getnframes()), dtype='<i2'), w.getframerate()
 
 
+def extract_device(pcm, cfg, ctx):
+    """int16 samples -> (device pointer to float32 [T, 39] features, T).  The features stay on
+    the device for a later stage; the caller frees the buffer (ctx.dev_free), which is None for
+    T = 0."""
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+    T = len(pcm) // cfg.hop
+    if T == 0:
+        return None, 0
+    d_pcm = ctx.dev_alloc(max(pcm.nbytes, 16))
+    d_out = ctx.dev_alloc(T * cfg.dim * 4)
+    try:
+        ctx.h2d(d_pcm, pcm)
+        p = hipabi.MfccParams(cfg.sample_rate, cfg.frame_rate, cfg.window_width, N_FFT, N_MEL, cfg.n_cep,
+                              cfg.cms_left, cfg.cms_right, (hipabi.C.c_int32 * 2)(*cfg.delta_width),
+                              cfg.pre_emph, (hipabi.C.c_float * 2)(*cfg.delta_norm))
+        n = ctx.mfcc(d_pcm, len(pcm), p, mel_filterbank(cfg.sample_rate), dct_matrix(cfg.n_cep), cfg.mean,
+                     cfg.scale, cfg.transform, d_out)
+        assert n == T
+    except BaseException:
+        ctx.dev_free(d_out)
+        raise
+    finally:
+        ctx.dev_free(d_pcm)
+    return d_out, T
+
+
 def extract(pcm, cfg, ctx=None, device=0):
     """int16 samples -> float32 [T, 39] features (device computation, result on the host)."""
-    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
     own = ctx is None
     if own:
         ctx = hipabi.Context(device)
     try:
-        T = len(pcm) // cfg.hop
+        d_out, T = extract_device(pcm, cfg, ctx)
         out = np.zeros((T, cfg.dim), dtype=np.float32)
-        if T == 0:
-            return out
-        d_pcm = ctx.dev_alloc(max(pcm.nbytes, 16))
-        d_out = ctx.dev_alloc(max(out.nbytes, 16))
-        try:
-            ctx.h2d(d_pcm, pcm)
-            p = hipabi.MfccParams(cfg.sample_rate, cfg.frame_rate, cfg.window_width, N_FFT, N_MEL, cfg.n_cep,
-                                  cfg.cms_left, cfg.cms_right, (hipabi.C.c_int32 * 2)(*cfg.delta_width),
-                                  cfg.pre_emph, (hipabi.C.c_float * 2)(*cfg.delta_norm))
-            n = ctx.mfcc(d_pcm, len(pcm), p, mel_filterbank(cfg.sample_rate), dct_matrix(cfg.n_cep), cfg.mean,
-                         cfg.scale, cfg.transform, d_out)
-            assert n == T
-            ctx.d2h(out, d_out)
-        finally:
-            ctx.dev_free(d_pcm)
-            ctx.dev_free(d_out)
+        if T:
+            try:
+                ctx.d2h(out, d_out)
+            finally:
+                ctx.dev_free(d_out)
         return out
     finally:
         if own:

@@ -23,7 +23,8 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_set_stats', 'spkd_pair_terms',
            'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gather_stats', 'spkd_mfcc',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_py2_roundtrip',
-           'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines']
+           'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
+           'spkd_gmm_loglik', 'spkd_vad_viterbi']
 
 
 class CdParams(C.Structure):
@@ -46,6 +47,12 @@ class MfccParams(C.Structure):
                 ('n_fft', C.c_int32), ('n_mel', C.c_int32), ('n_cep', C.c_int32), ('cms_left', C.c_int32),
                 ('cms_right', C.c_int32), ('delta_width', C.c_int32 * 2), ('pre_emph', C.c_float),
                 ('delta_norm', C.c_float * 2)]
+
+
+class GmmParams(C.Structure):
+    _fields_ = [('n_kernels', C.c_int32), ('n_states', C.c_int32), ('dim', C.c_int32), ('mean', C.c_void_p),
+                ('inv_var', C.c_void_p), ('log_norm', C.c_void_p), ('state_off', C.c_void_p), ('kernel', C.c_void_p),
+                ('log_weight', C.c_void_p)]
 
 
 class AhcParams(C.Structure):
@@ -172,6 +179,8 @@ def load_library(path=None):
     lib.spkd_labels_from_merges.argtypes = [i64, i64, vp, vp, vp]
     lib.spkd_labels_from_merges_batch.argtypes = [i64, vp, vp, vp, vp, vp]
     lib.spkd_count_flags.argtypes = [vp, vp, vp, i64, vp]
+    lib.spkd_gmm_loglik.argtypes = [vp, vp, i64, P(GmmParams), vp]
+    lib.spkd_vad_viterbi.argtypes = [i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, P(i64), P(dbl)]
     lib.spkd_gw_lines.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, dbl, C.c_int, i64, vp, vp, vp, vp, vp]
     if lib.spkd_abi_version() != 2:
         raise ImportError('libspkd_hip.so ABI version mismatch')
@@ -244,6 +253,30 @@ def gw_lines(off, n_det, det_start, det_maxi, final_start, turn_start_s, turn_en
     if st != SPKD_OK:
         raise SpkdError(st, 'bad growing-window result')
     return {'times': times, 'turn': turn, 'frame_b': fb, 'frame_e': fe, 'index': ix}
+
+
+def vad_viterbi(scores, word_state, stay, exit_, enter):
+    """Exact Viterbi over a loop of one-state words (spkd_vad_viterbi): scores [T, S] float32
+    (the .lna layout), word j emitting state word_state[j], per-word fp64 constants.  Returns
+    (token first frames int64, token words int32, final score)."""
+    c = np.ascontiguousarray
+    scores = c(scores, dtype=np.float32)
+    if scores.ndim != 2:
+        raise SpkdError(SPKD_EINVAL, 'scores must be [frames, states]')
+    ws = c(word_state, dtype=np.int32)
+    consts = [c(a, dtype=np.float64) for a in (stay, exit_, enter)]
+    if any(len(a) != len(ws) for a in consts):
+        raise SpkdError(SPKD_EINVAL, 'one constant of each kind per word')
+    T, S = scores.shape
+    tf = np.zeros(max(T, 1), dtype=np.int64)
+    tw = np.zeros(max(T, 1), dtype=np.int32)
+    n = C.c_int64(0)
+    sc = C.c_double(0.0)
+    st = load_library().spkd_vad_viterbi(T, S, _ptr(scores), len(ws), _ptr(ws), *[_ptr(a) for a in consts],
+                                         _ptr(tf), _ptr(tw), C.byref(n), C.byref(sc))
+    if st != SPKD_OK:
+        raise SpkdError(st, 'bad decoder input')
+    return tf[:n.value].copy(), tw[:n.value].copy(), sc.value
 
 
 def labels_from_merges_batch(seg_off, n_merges, a, b):
@@ -476,6 +509,22 @@ class Context(object):
         self.check(self.lib.spkd_mfcc(self.h, C.c_void_p(d_pcm), n_samples, C.byref(params), *[_ptr(a) for a in arrs],
                                       C.c_void_p(d_features), C.byref(n)))
         return int(n.value)
+
+    # ---- (7)
+    def gmm_loglik(self, d_features, n_frames, gmm, d_scores):
+        """Per-frame state log-likelihoods of device features [n_frames, 39] into device
+        scores [n_frames, n_states]; gmm: a dict of host arrays (mean, inv_var, log_norm
+        float32; state_off, kernel int32; log_weight float32)."""
+        a = {k: np.ascontiguousarray(gmm[k], dtype=np.int32 if k in ('state_off', 'kernel') else np.float32)
+             for k in ('mean', 'inv_var', 'log_norm', 'state_off', 'kernel', 'log_weight')}
+        K, S = len(a['log_norm']), len(a['state_off']) - 1
+        if a['mean'].size != K * DIM or a['inv_var'].size != K * DIM or S < 1 or \
+                len(a['kernel']) != len(a['log_weight']) or int(a['state_off'][-1]) != len(a['kernel']):
+            raise SpkdError(SPKD_EINVAL, 'inconsistent model array sizes')
+        p = GmmParams(K, S, a['mean'].shape[-1] if a['mean'].ndim == 2 else DIM,
+                      *[_ptr(a[k]) for k in ('mean', 'inv_var', 'log_norm', 'state_off', 'kernel', 'log_weight')])
+        self.check(self.lib.spkd_gmm_loglik(self.h, C.c_void_p(d_features), int(n_frames), C.byref(p),
+                                            C.c_void_p(d_scores)))
 
     # ---- (4)
     def ahc(self, d_stats, seg_off, params):

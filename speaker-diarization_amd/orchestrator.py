@@ -12,9 +12,10 @@ contract of the reference script restated (paths relative to the reference tree)
   * aku2ann.py / aku2elan.py when the output is a file ..... spk-diarization2.py:130-138
 
 Every stage is addressed as ./<script> relative to the working directory and its return
-code is ignored, exactly like the reference: the stages ARE the interface.  The two the
-reference takes from AaltoASR (./generate_exp.py's decoder, feacat) stay external
-programs of those names; the other five are this repository's drop-in executables.
+code is ignored, exactly like the reference: the stages ARE the interface.  All seven have
+drop-in executables in this repository: the two the reference takes from AaltoASR are
+stand-ins (./generate_exp.py with GPU scoring and an exact Viterbi, ./feacat with the GPU
+front-end; parity unpinned), the other five restate the reference's scripts.
 """
 import argparse
 import os.path as op
