@@ -270,6 +270,50 @@ spkd_status spkd_gather_stats(spkd_ctx *ctx, const double *d_src, int64_t n_src,
                               const int64_t *h_src_index, const int64_t *h_dst_index,
                               int64_t n, int64_t n_dst, double *d_dst);
 
+/* The batch hand-off: spkd_gw_fused whose results stay on the device and come back as the
+ * recipe lines the change-detection script writes (spk-change-detection.py:254 a detection,
+ * :288 the tail), instead of as event slots for the host to walk.  Behind k_gw, in the same
+ * call bracket and only when the device error word is clean, three small kernels count every
+ * turn's detections from its window flags, scan them in the CALLER's turn order and write per
+ * line what spkd_gw_lines with frame outputs writes -- same fields, same fp64 operations in
+ * the same order: the two times, the turn, the record index h_ev_off[t] + j and the frame
+ * range that record covers.  Only these compact arrays (and n_win per turn) are copied, into
+ * pinned memory the context owns and reuses.  Then, on the host and in one pass over them:
+ * the 12-digit round trip of the times (spkd_py2_roundtrip) and, per line, the frame range the
+ * clustering script would cut from the round-tripped times (spk-clustering.py:263-292 parses
+ * the line, :46-52 slices the frames: begin = min(int(t0 * rate), file_len), end = max(begin,
+ * min(int(t1 * rate), file_len)), plus file_off) compared with the range the record covers;
+ * the lines where they differ -- the round trip moved a boundary across a frame edge -- come
+ * back as the redo list.
+ *   h_turn_start_s / h_turn_end_s   the turn's times as the VAD recipe states them
+ *   h_turn_file_off / h_turn_file_len   first frame and frame count of the turn's file
+ *   want_index   also copy the line -> record map to the host (view.index; else NULL)
+ * Every pointer of the view belongs to the context and is valid until its next spkd_gw_batch
+ * (d_index: until the next spkd_gw_batch or spkd_ahc_fused, which consumes it).  Capacities,
+ * SPKD_EOVERFLOW and d_seg_stats as for spkd_gw_fused with check_capacity = 0; no candidate
+ * log.  The view is zeroed on every status but SPKD_OK. */
+typedef struct {
+    int64_t n_lines;             /* sum over turns of detections + 1 */
+    int64_t n_redo;
+    const int32_t *n_win;        /* [n_turns] */
+    const double *times;         /* [n_lines][2] start, end in seconds, after the round trip */
+    const int32_t *turn;         /* [n_lines] */
+    const int64_t *frame_b;      /* [n_lines] range of the frame array the fused record covers */
+    const int64_t *frame_e;
+    const int64_t *index;        /* [n_lines] record of the line in d_seg_stats (want_index) */
+    const int64_t *d_index;      /* the same map, DEVICE memory */
+    const int64_t *redo_line;    /* [n_redo] ascending */
+    const int64_t *redo_begin;   /* [n_redo] the range to compute the record from instead */
+    const int64_t *redo_end;
+} spkd_gw_lines_view;
+
+spkd_status spkd_gw_batch(spkd_ctx *ctx, const float *d_frames, int64_t n_frames,
+                          const int64_t *h_turn_begin, const int64_t *h_turn_end, int64_t n_turns,
+                          const spkd_cd_params *params, const int64_t *h_ev_off,
+                          const double *h_turn_start_s, const double *h_turn_end_s,
+                          const int64_t *h_turn_file_off, const int64_t *h_turn_file_len,
+                          double *d_seg_stats, int want_index, spkd_gw_lines_view *view);
+
 /* Sliding-window distances, the per-window part of dist_sw
  * (spk-change-detection.py:304-312): window w of turn t compares
  * [int(w*step), int(w*step+size)) with [int(w*step+size), int(w*step+2*size)).
@@ -325,6 +369,28 @@ spkd_status spkd_ahc_matrix(spkd_ctx *ctx, const double *d_stats, int64_t n, con
                             const double *d_matrix, double stat_max_in, double stat_min_in,
                             int32_t *h_n_merges, int32_t *h_merge_a, int32_t *h_merge_b,
                             double *h_merge_d, double *h_stat_max, double *h_stat_min);
+
+/* spkd_ahc for the lines of a spkd_gw_batch, in ONE call bracket: problem p owns the lines
+ * [h_seg_off[p], h_seg_off[p+1]); line i's record is d_records[d_line_index[i]] (the fused
+ * detector's buffer of n_records records and the view's d_index: what spkd_gather_stats used to
+ * copy into segment order is read in place by the kernel that builds the clustering stage's
+ * working copies), except for the n_redo lines of the redo list, whose records are computed
+ * from the frames [h_redo_begin[k], h_redo_end[k]) first (the kernels of spkd_set_stats) --
+ * the same records, so the same merges, as spkd_gather_stats / spkd_set_stats / spkd_ahc in
+ * sequence (spk-clustering.py:263-292 read into 46-52, 88-94).  d_line_index is overwritten at
+ * the redo lines.  A map entry outside [0, n_records) is SPKD_EOVERFLOW.
+ * The outputs are pointers into pinned memory of the context, laid out as spkd_ahc's and
+ * valid until the next spkd_ahc_fused; labels: the final 1-based cluster of every line
+ * (spkd_labels_from_merges_batch of the merge log). */
+spkd_status spkd_ahc_fused(spkd_ctx *ctx, const float *d_frames, int64_t n_frames,
+                           const double *d_records, int64_t n_records, int64_t *d_line_index,
+                           const int64_t *h_seg_off, int64_t n_problems,
+                           const int64_t *h_redo_line, const int64_t *h_redo_begin,
+                           const int64_t *h_redo_end, int64_t n_redo,
+                           const spkd_ahc_params *params,
+                           const int32_t **h_n_merges, const int32_t **h_merge_a,
+                           const int32_t **h_merge_b, const double **h_merge_d,
+                           const int32_t **h_labels);
 
 /* ---------------------------------------------------------------------------
  * (6) Feature front-end: what `feacat -c fconfig.cfg -H --raw-output x.wav` computes for the

@@ -22,7 +22,9 @@
 using namespace spkd;
 
 namespace {
-constexpr int N_SLOTS = 36;
+constexpr int N_SLOTS = 40;
+// pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused)
+enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, N_PIN };
 }
 
 struct spkd_ctx {
@@ -50,6 +52,15 @@ struct spkd_ctx {
     // for the mode) and what the current call's KL2 kernels get (nullptr: the inverse)
     void* pinv_ws = nullptr;
     double* pinv_cur = nullptr;
+    // grow-only pinned host memory (results of the batch hand-off land here) and the redo
+    // list of the most recent spkd_gw_batch
+    void* pin[N_PIN] = {};
+    size_t pin_bytes[N_PIN] = {};
+    std::vector<int64_t> redo_line, redo_begin, redo_end;
+    // host side of the redo statistics of spkd_ahc_fused (read by copies of the call)
+    std::vector<Chunk> redo_chunks;
+    std::vector<int64_t> redo_setoff;
+    std::vector<int32_t> redo_sets;
 };
 
 namespace {
@@ -86,6 +97,25 @@ spkd_status scratch(spkd_ctx* c, int slot, size_t bytes, void** out) {
         c->slot_bytes[slot] = want;
     }
     *out = c->slot[slot];
+    return SPKD_OK;
+}
+
+// grow-only pinned host buffers, like scratch(): a copy into pinned memory is one DMA
+// transfer at link speed, and the pages are touched once in the life of the context
+spkd_status pinned(spkd_ctx* c, int which, size_t bytes, void** out) {
+    if (bytes == 0) bytes = 16;
+    if (c->pin_bytes[which] < bytes) {
+        if (c->pin[which]) HIPCHK(c, hipHostFree(c->pin[which]));
+        c->pin[which] = nullptr;
+        c->pin_bytes[which] = 0;
+        const size_t want = bytes + bytes / 4;
+        if (hipHostMalloc(&c->pin[which], want, hipHostMallocDefault) != hipSuccess) {
+            c->pin[which] = nullptr;
+            return fail(c, SPKD_ENOMEM, "pinned host allocation failed");
+        }
+        c->pin_bytes[which] = want;
+    }
+    *out = c->pin[which];
     return SPKD_OK;
 }
 
@@ -166,7 +196,8 @@ enum {
     S_CHUNKS = 0, S_SETOFF, S_PARTIAL, S_IDXA, S_IDXB, S_TERMS, S_TURNS, S_SNAP, S_CAND,
     S_EV_I32A, S_EV_I32B, S_EV_D0, S_EV_D1, S_EV_D2, S_EV_D3, S_EV_D4, S_LOG,
     S_AHC_STATS, S_AHC_LD, S_AHC_AUX, S_AHC_MAT, S_AHC_MISC, S_AHC_OUT, S_AHC_OFF, S_AHC_PROB, S_AHC_PACKED, S_MFCC_TAB, S_MFCC_STATIC,
-    S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX, S_COUNT
+    S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX,
+    S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -236,6 +267,8 @@ void spkd_destroy(spkd_ctx* c) {
         if (c->slot[i]) (void)hipFree(c->slot[i]);
     if (c->d_err) (void)hipFree(c->d_err);
     if (c->pinv_ws) (void)hipFree(c->pinv_ws);
+    for (int i = 0; i < N_PIN; ++i)
+        if (c->pin[i]) (void)hipHostFree(c->pin[i]);
     if (c->d_counter) (void)hipFree(c->d_counter);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -417,7 +450,59 @@ struct MatrixPlan {
     const double* d_init = nullptr;
     double init_max = NAN, init_min = NAN;            // variant 1: max / min over the distances behind d_init
     int64_t row_begin = -1, row_end = -1;
+    // the batch hand-off (spkd_ahc_fused): record r of the problems is d_stats[d_map[r]] of n_src
+    // records, except the redo lines, whose records are computed from the frames first
+    int64_t* d_map = nullptr;
+    int64_t n_src = 0;
+    const float* d_frames = nullptr;
+    int64_t n_frames = 0;
+    const int64_t *redo_line = nullptr, *redo_begin = nullptr, *redo_end = nullptr;
+    int64_t n_redo = 0;
 };
+
+// line -> source record of spkd_ahc_fused: -(k + 1) stands for record k of the redo buffer
+__global__ __launch_bounds__(256) void k_patch_map(const int64_t* __restrict__ line, int64_t n, int64_t* __restrict__ map) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k < n) map[line[k]] = -(k + 1);
+}
+
+// k_to_quadrec reading every record through the line -> record map, and leaving the packed
+// working copy beside the quad one: the record is fetched once, from where the detector (or
+// the redo statistics) wrote it.  A map entry outside both buffers sets the capacity bit.
+__global__ __launch_bounds__(256) void k_records_from_map(const double* __restrict__ recs, int64_t n_recs,
+                                                          const int64_t* __restrict__ map,
+                                                          const double* __restrict__ redo, int64_t n_redo,
+                                                          int64_t n_rec, double* __restrict__ qr,
+                                                          double* __restrict__ packed, int* __restrict__ err) {
+    const int64_t c = blockIdx.x;
+    if (c >= n_rec) return;
+    const int64_t m = map[c];
+    const double* g;
+    if (m >= 0 && m < n_recs) {
+        g = recs + m * REC;
+    } else if (m < 0 && -(m + 1) < n_redo) {
+        g = redo + (-(m + 1)) * REC;
+    } else {
+        if (threadIdx.x == 0) atomicOr(err, 4);
+        return;
+    }
+    double* o = qr + c * QREC;
+    for (int e = threadIdx.x; e < QREC; e += 256) {          // (k_to_quadrec's map)
+        const int t = e & 15, sj = e >> 4;
+        const int s = sj / DA, j = sj - s * DA;
+        double v = 0.0;
+        if (t < QL) {
+            const int i = QL * s + t;
+            const int r = i < j ? i : j, cc = i < j ? j : i;
+            v = g[pk(r, cc)];
+        } else if (e == QREC_COUNT_AT) {
+            v = g[REC - 1];
+        }
+        o[e] = v;
+    }
+    double* p = packed + c * REC;
+    for (int e = threadIdx.x; e < REC; e += 256) p[e] = g[e];
+}
 
 spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_off, int64_t n_prob,
                         int variant, int kind, double lambdac, AhcBuffers& B, int64_t& n_total,
@@ -507,8 +592,25 @@ spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg
     TRY(scratch(c, S_AHC_PACKED, (size_t)n_total * REC * sizeof(double), &p));
     B.pk = (double*)p;
     if (n_total > 0) {
-        hipLaunchKernelGGL(k_to_quadrec, dim3((unsigned)n_total), dim3(256), 0, c->stream, d_stats, n_total, B.ex);
-        HIPCHK(c, hipMemcpyAsync(B.pk, d_stats, (size_t)n_total * REC * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (plan.d_map) {
+            void* d_redo = nullptr;
+            if (plan.n_redo > 0) {
+                int64_t* d_rl = nullptr;
+                TRY(scratch(c, S_REDO_STATS, (size_t)plan.n_redo * REC * sizeof(double), &d_redo));
+                TRY(upload(c, S_REDO_IDX, plan.redo_line, (size_t)plan.n_redo, &d_rl));
+                c->redo_sets.resize((size_t)plan.n_redo);
+                for (int64_t k = 0; k < plan.n_redo; ++k) c->redo_sets[(size_t)k] = (int32_t)k;
+                TRY(set_stats_launch(c, plan.d_frames, plan.n_frames, plan.redo_begin, plan.redo_end, c->redo_sets.data(),
+                                     plan.n_redo, plan.n_redo, (double*)d_redo, c->redo_chunks, c->redo_setoff));
+                hipLaunchKernelGGL(k_patch_map, dim3((unsigned)((plan.n_redo + 255) / 256)), dim3(256), 0, c->stream,
+                                   (const int64_t*)d_rl, plan.n_redo, plan.d_map);
+            }
+            hipLaunchKernelGGL(k_records_from_map, dim3((unsigned)n_total), dim3(256), 0, c->stream, d_stats, plan.n_src,
+                               (const int64_t*)plan.d_map, (const double*)d_redo, plan.n_redo, n_total, B.ex, B.pk, c->d_err);
+        } else {
+            hipLaunchKernelGGL(k_to_quadrec, dim3((unsigned)n_total), dim3(256), 0, c->stream, d_stats, n_total, B.ex);
+            HIPCHK(c, hipMemcpyAsync(B.pk, d_stats, (size_t)n_total * REC * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        }
         // KL2: one wave per record; BIC / GLR: four records per wave
         const int64_t per_block = kind == SPKD_KL2 ? PT_WAVES : 4 * PT_WAVES;
         const unsigned blocks = (unsigned)((n_total + per_block - 1) / per_block);
@@ -897,6 +999,225 @@ spkd_status build_turns(spkd_ctx* c, int64_t n_frames, const int64_t* hb, const 
 }  // namespace
 
 namespace {
+// ---- the batch hand-off behind k_gw (spkd_gw_batch): event slots -> recipe lines, on the device.
+// All three kernels return at once when the error word is set (a capacity overflow leaves
+// counts that mean nothing); the host looks at the word before it uses anything.
+constexpr int CP_TPB = 256;
+constexpr int CP_SCAN_TPB = 1024;
+
+// per launch position: the turn's detections = the ones among its n_win window flags, filed
+// under the caller's turn index together with the position (k_cp_lines finds the turn by it)
+__global__ __launch_bounds__(CP_TPB) void k_cp_count(const TurnDesc* __restrict__ turns, int64_t n_turns,
+                                                     const int32_t* __restrict__ n_win,
+                                                     const int32_t* __restrict__ win_det, const int* __restrict__ err,
+                                                     int32_t* __restrict__ n_det, int32_t* __restrict__ pos) {
+    if (*err) return;
+    const int64_t p = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (p >= n_turns) return;
+    const TurnDesc T = turns[p];
+    int64_t nw = n_win[T.id];
+    nw = nw < 0 ? 0 : (nw > T.ev_cap ? T.ev_cap : nw);
+    const int32_t* f = win_det + T.ev_off;
+    int32_t cnt = 0;
+    for (int64_t i = 0; i < nw; ++i) cnt += f[i] != 0;
+    n_det[T.id] = cnt;
+    pos[T.id] = (int32_t)p;
+}
+
+// exclusive scan of (detections + 1) over the turns in the caller's order -> first line of every
+// turn, line_off[n_turns] = number of lines.  One workgroup: a run of turns per thread.
+__global__ __launch_bounds__(CP_SCAN_TPB) void k_cp_scan(const int32_t* __restrict__ n_det, int64_t n_turns,
+                                                         const int* __restrict__ err, int64_t* __restrict__ line_off) {
+    __shared__ int64_t part[CP_SCAN_TPB];
+    const int tid = threadIdx.x;
+    if (*err) {
+        if (tid == 0) line_off[n_turns] = 0;
+        return;
+    }
+    const int64_t per = (n_turns + CP_SCAN_TPB - 1) / CP_SCAN_TPB;
+    const int64_t lo = tid * per < n_turns ? tid * per : n_turns;
+    const int64_t hi = lo + per < n_turns ? lo + per : n_turns;
+    int64_t sum = 0;
+    for (int64_t t = lo; t < hi; ++t) sum += (int64_t)n_det[t] + 1;
+    part[tid] = sum;
+    __syncthreads();
+    for (int d = 1; d < CP_SCAN_TPB; d <<= 1) {
+        const int64_t v = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int64_t run = part[tid] - sum;
+    for (int64_t t = lo; t < hi; ++t) {
+        line_off[t] = run;
+        run += (int64_t)n_det[t] + 1;
+    }
+    if (tid == CP_SCAN_TPB - 1) line_off[n_turns] = part[tid];
+}
+
+// per turn (caller's order) its lines: spkd_gw_lines with frame outputs, operation for operation
+__global__ __launch_bounds__(CP_TPB) void k_cp_lines(const TurnDesc* __restrict__ turns, int64_t n_turns,
+                                                     const int32_t* __restrict__ n_det, const int32_t* __restrict__ pos,
+                                                     const int64_t* __restrict__ line_off, int64_t n_lines,
+                                                     const double* __restrict__ det_start,
+                                                     const double* __restrict__ det_maxi,
+                                                     const double* __restrict__ final_start,
+                                                     const double* __restrict__ turn_start_s,
+                                                     const double* __restrict__ turn_end_s, double rate,
+                                                     const int* __restrict__ err, double* __restrict__ times,
+                                                     int64_t* __restrict__ frame_b, int64_t* __restrict__ frame_e,
+                                                     int64_t* __restrict__ index, int32_t* __restrict__ line_turn) {
+#pragma clang fp contract(off)
+    if (*err) return;
+    const int64_t t = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
+    if (t >= n_turns) return;
+    const TurnDesc T = turns[pos[t]];
+    const int64_t nd = n_det[t];
+    const double ls = turn_start_s[t], le = turn_end_s[t];
+    int64_t i = line_off[t];
+    for (int64_t j = 0; j <= nd && i < n_lines; ++j, ++i) {
+        const bool tail = j == nd;
+        double fs, fe;
+        if (tail) {
+            fs = final_start[t];
+            times[2 * i] = fs / rate + ls;
+            times[2 * i + 1] = ((le - ls) * rate) / rate + ls;
+            fe = 0.0;
+        } else {
+            fs = det_start[T.ev_off + j];
+            fe = fs + det_maxi[T.ev_off + j];
+            times[2 * i] = fs / rate + ls;
+            times[2 * i + 1] = fe / rate + ls;
+        }
+        frame_b[i] = T.begin + (int64_t)fs;
+        frame_e[i] = tail ? T.begin + T.len : T.begin + (int64_t)fe;
+        index[i] = T.ev_off + j;
+        line_turn[i] = (int32_t)t;
+    }
+}
+
+// what spkd_gw_batch adds to the growing-window call
+struct GwBatch {
+    const double *turn_start_s, *turn_end_s;
+    const int64_t *file_off, *file_len;
+    int want_index;
+    spkd_gw_lines_view* view;
+    // device side (gw_batch_upload)
+    double *d_ls = nullptr, *d_le = nullptr;
+    int64_t* d_line_off = nullptr;
+    int32_t *d_n_det = nullptr, *d_pos = nullptr;
+    // host side, pinned
+    int64_t* h_head = nullptr;                       // [0] lines, [1] the device error word
+    int32_t* h_n_win = nullptr;
+    int64_t n_lines = 0;
+    bool have_lines = false;
+};
+
+// before k_gw is enqueued: the turn times go up while nothing waits for them
+spkd_status gw_batch_upload(spkd_ctx* c, GwBatch& G, int64_t n_turns) {
+    const size_t nt = (size_t)n_turns;
+    void *p = nullptr, *h = nullptr;
+    TRY(scratch(c, S_CP_TURNS, nt * (2 * sizeof(double) + 2 * sizeof(int32_t)) + (nt + 1) * sizeof(int64_t), &p));
+    G.d_ls = (double*)p;
+    G.d_le = G.d_ls + nt;
+    G.d_line_off = (int64_t*)(G.d_le + nt);
+    G.d_n_det = (int32_t*)(G.d_line_off + nt + 1);
+    G.d_pos = G.d_n_det + nt;
+    HIPCHK(c, hipMemcpyAsync(G.d_ls, G.turn_start_s, nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(G.d_le, G.turn_end_s, nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    TRY(pinned(c, PIN_GW_TURNS, 2 * sizeof(int64_t) + nt * sizeof(int32_t), &h));
+    G.h_head = (int64_t*)h;
+    G.h_n_win = (int32_t*)(G.h_head + 2);
+    return SPKD_OK;
+}
+
+// behind k_gw, inside its call bracket: count, scan, learn the number of lines, write and fetch them
+spkd_status gw_batch_compact(spkd_ctx* c, GwBatch& G, const TurnDesc* d_turns, int64_t n_turns,
+                             const int32_t* d_n_win, const int32_t* d_win_det, const double* d_det_start,
+                             const double* d_det_maxi, const double* d_final_start, double rate) {
+    const unsigned blocks = (unsigned)((n_turns + CP_TPB - 1) / CP_TPB);
+    hipLaunchKernelGGL(k_cp_count, dim3(blocks), dim3(CP_TPB), 0, c->stream, d_turns, n_turns, d_n_win, d_win_det,
+                       (const int*)c->d_err, G.d_n_det, G.d_pos);
+    hipLaunchKernelGGL(k_cp_scan, dim3(1), dim3(CP_SCAN_TPB), 0, c->stream, (const int32_t*)G.d_n_det, n_turns,
+                       (const int*)c->d_err, G.d_line_off);
+    HIPCHK(c, hipGetLastError());
+    G.h_head[0] = 0;
+    G.h_head[1] = 0;
+    HIPCHK(c, hipMemcpyAsync(&G.h_head[0], G.d_line_off + n_turns, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&G.h_head[1], c->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(G.h_n_win, d_n_win, (size_t)n_turns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (G.h_head[1] != 0) return SPKD_OK;            // (the call's finish() turns the word into its status)
+    const int64_t n = G.h_head[0];
+    if (n < n_turns) return fail(c, SPKD_EHIP, "internal error: fewer lines than turns");
+    const size_t nn = (size_t)n;
+    void *d_t = nullptr, *d_l = nullptr, *h = nullptr;
+    TRY(scratch(c, S_CP_TIMES, nn * 2 * sizeof(double), &d_t));
+    TRY(scratch(c, S_CP_LINES, nn * (3 * sizeof(int64_t) + sizeof(int32_t)), &d_l));
+    TRY(pinned(c, PIN_GW_LINES, nn * (2 * sizeof(double) + 3 * sizeof(int64_t) + sizeof(int32_t)), &h));
+    int64_t* d_fb = (int64_t*)d_l;                   // frame_b | frame_e | index | turn
+    int64_t* d_ix = d_fb + 2 * nn;
+    int32_t* d_tn = (int32_t*)(d_ix + nn);
+    hipLaunchKernelGGL(k_cp_lines, dim3(blocks), dim3(CP_TPB), 0, c->stream, d_turns, n_turns,
+                       (const int32_t*)G.d_n_det, (const int32_t*)G.d_pos, (const int64_t*)G.d_line_off, n, d_det_start,
+                       d_det_maxi, d_final_start, (const double*)G.d_ls, (const double*)G.d_le, rate,
+                       (const int*)c->d_err, (double*)d_t, d_fb, d_fb + nn, d_ix, d_tn);
+    HIPCHK(c, hipGetLastError());
+    double* h_times = (double*)h;
+    int64_t* h_fb = (int64_t*)(h_times + 2 * nn);
+    int64_t* h_ix = h_fb + 2 * nn;
+    int32_t* h_tn = (int32_t*)(h_ix + nn);
+    HIPCHK(c, hipMemcpyAsync(h_times, d_t, nn * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_fb, d_fb, nn * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_tn, d_tn, nn * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (G.want_index)
+        HIPCHK(c, hipMemcpyAsync(h_ix, d_ix, nn * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    spkd_gw_lines_view& V = *G.view;
+    V.n_lines = n;
+    V.n_win = G.h_n_win;
+    V.times = h_times;
+    V.turn = h_tn;
+    V.frame_b = h_fb;
+    V.frame_e = h_fb + nn;
+    V.index = G.want_index ? h_ix : nullptr;
+    V.d_index = d_ix;
+    G.n_lines = n;
+    G.have_lines = true;
+    return SPKD_OK;
+}
+
+// after the call has drained: the 12-digit round trip of the times in place, and in the same
+// pass the lines whose frame range -- as the clustering script cuts it from the round-tripped
+// times -- is not the one the fused record covers
+spkd_status gw_batch_finish(spkd_ctx* c, GwBatch& G, int64_t n_turns, double rate) {
+    spkd_gw_lines_view& V = *G.view;
+    double* times = const_cast<double*>(V.times);
+    spkd_py2_roundtrip(times, 2 * V.n_lines);
+    c->redo_line.clear();
+    c->redo_begin.clear();
+    c->redo_end.clear();
+    for (int64_t i = 0; i < V.n_lines; ++i) {
+        const int64_t t = V.turn[i];
+        if (t < 0 || t >= n_turns) return fail(c, SPKD_EHIP, "internal error: line of no turn");
+        const int64_t fn = G.file_len[t];
+        int64_t a0 = (int64_t)(times[2 * i] * rate), a1 = (int64_t)(times[2 * i + 1] * rate);
+        a0 = a0 < 0 ? 0 : (a0 > fn ? fn : a0);
+        a1 = a1 < 0 ? 0 : (a1 > fn ? fn : a1);
+        if (a1 < a0) a1 = a0;
+        const int64_t b = G.file_off[t] + a0, e = G.file_off[t] + a1;
+        if (b != V.frame_b[i] || e != V.frame_e[i]) {
+            c->redo_line.push_back(i);
+            c->redo_begin.push_back(b);
+            c->redo_end.push_back(e);
+        }
+    }
+    V.n_redo = (int64_t)c->redo_line.size();
+    V.redo_line = c->redo_line.data();
+    V.redo_begin = c->redo_begin.data();
+    V.redo_end = c->redo_end.data();
+    return SPKD_OK;
+}
+
 // from this many turns on, a wave per turn (2 048 wave slots on the chip at two waves per SIMD)
 constexpr int64_t GW_WAVE_PER_TURN_FROM = 4096;
 constexpr int64_t GW_EIGHT_WAVES_UP_TO = 256;           // a workgroup per CU: eight waves per turn
@@ -904,12 +1225,14 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
                     const int64_t* he, int64_t n_turns, const spkd_cd_params* P, const int64_t* h_ev_off,
                     int check_capacity, int32_t* h_n_win, double* h_win_maxd, int32_t* h_win_det,
                     double* h_det_start, double* h_det_maxi, double* h_det_d, double* h_final_start,
-                    double* d_seg_stats, spkd_cand_log* h_log, int64_t log_cap, int64_t* h_log_count) {
+                    double* d_seg_stats, spkd_cand_log* h_log, int64_t log_cap, int64_t* h_log_count,
+                    GwBatch* batch = nullptr) {
     if (!c || !P || n_turns < 0) return SPKD_EINVAL;
     if (h_log_count) *h_log_count = 0;
     if (n_turns == 0) return SPKD_OK;
-    if (!d_frames || !hb || !he || !h_ev_off || !h_n_win || !h_win_maxd || !h_win_det || !h_det_start ||
-        !h_det_maxi || !h_det_d || !h_final_start)
+    if (!d_frames || !hb || !he || !h_ev_off) return fail(c, SPKD_EINVAL, "null argument");
+    // (the batch form copies none of the event arrays)
+    if (!batch && (!h_n_win || !h_win_maxd || !h_win_det || !h_det_start || !h_det_maxi || !h_det_d || !h_final_start))
         return fail(c, SPKD_EINVAL, "null argument");
     if (P->kind < 0 || P->kind > 3) return fail(c, SPKD_EINVAL, "gw: bad kind");
     if (!(P->rate >= 10.0) || !(P->winsize >= 1.0) || !(P->winstep >= 1.0))
@@ -949,6 +1272,7 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
         !d_log || !c->d_counter || !c->d_err)
         return fail(c, SPKD_EHIP, "gw: a device scratch buffer is missing");
     HIPCHK(c, hipMemsetAsync(c->d_counter, 0, 2 * sizeof(unsigned long long), c->stream));   // [0] log entries, [1] determinants
+    if (batch) TRY(gw_batch_upload(c, *batch, n_turns));
     // A turn is a serial chain of scans.  With few turns a workgroup of four waves shares a
     // turn's matrices (latency); with thousands, ONE WAVE per turn keeps every wave of the
     // chip busy with its own chain (throughput): no wave waits at a barrier for the serial
@@ -971,6 +1295,16 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
 #undef SPKD_GW_LAUNCH
     HIPCHK(c, hipGetLastError());
     unsigned long long& cnt = cnt2[0];
+    if (batch) {
+        TRY(gw_batch_compact(c, *batch, d_turns, n_turns, (const int32_t*)d_i32a, (const int32_t*)d_i32b,
+                             (const double*)d_d1, (const double*)d_d2, (const double*)d_d4, P->rate));
+        HIPCHK(c, hipMemcpyAsync(cnt2, c->d_counter, sizeof cnt2, hipMemcpyDeviceToHost, c->stream));
+        const spkd_status st = call.finish();
+        c->last_gw_items = (int64_t)cnt2[1];
+        if (st != SPKD_OK) return st;
+        if (!batch->have_lines) return fail(c, SPKD_EHIP, "internal error: no lines from a clean call");
+        return gw_batch_finish(c, *batch, n_turns, P->rate);
+    }
     HIPCHK(c, hipMemcpyAsync(h_n_win, d_i32a, (size_t)n_turns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_win_maxd, d_d0, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h_win_det, d_i32b, (size_t)n_ev * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1020,6 +1354,82 @@ spkd_status spkd_gw_fused(spkd_ctx* c, const float* d_frames, int64_t n_frames, 
     return gw_impl(c, d_frames, n_frames, hb, he, n_turns, P, h_ev_off, check_capacity, h_n_win, h_win_maxd,
                    h_win_det, h_det_start, h_det_maxi, h_det_d, h_final_start, d_seg_stats, h_log, log_cap,
                    h_log_count);
+}
+
+spkd_status spkd_gw_batch(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
+                          const int64_t* he, int64_t n_turns, const spkd_cd_params* P, const int64_t* h_ev_off,
+                          const double* h_turn_start_s, const double* h_turn_end_s, const int64_t* h_turn_file_off,
+                          const int64_t* h_turn_file_len, double* d_seg_stats, int want_index,
+                          spkd_gw_lines_view* view) {
+    if (!c || !view) return SPKD_EINVAL;
+    std::memset(view, 0, sizeof *view);
+    if (!d_seg_stats) return fail(c, SPKD_EINVAL, "gw_batch: null statistics buffer");
+    if (n_turns > 0 && (!h_turn_start_s || !h_turn_end_s || !h_turn_file_off || !h_turn_file_len))
+        return fail(c, SPKD_EINVAL, "gw_batch: null turn arrays");
+    GwBatch G;
+    G.turn_start_s = h_turn_start_s;
+    G.turn_end_s = h_turn_end_s;
+    G.file_off = h_turn_file_off;
+    G.file_len = h_turn_file_len;
+    G.want_index = want_index;
+    G.view = view;
+    const spkd_status st = gw_impl(c, d_frames, n_frames, hb, he, n_turns, P, h_ev_off, 0, nullptr, nullptr, nullptr,
+                                   nullptr, nullptr, nullptr, nullptr, d_seg_stats, nullptr, 0, nullptr, &G);
+    if (st != SPKD_OK) std::memset(view, 0, sizeof *view);
+    return st;
+}
+
+spkd_status spkd_ahc_fused(spkd_ctx* c, const float* d_frames, int64_t n_frames, const double* d_records,
+                           int64_t n_records, int64_t* d_line_index, const int64_t* h_seg_off, int64_t n_prob,
+                           const int64_t* h_redo_line, const int64_t* h_redo_begin, const int64_t* h_redo_end,
+                           int64_t n_redo, const spkd_ahc_params* P, const int32_t** h_n_merges,
+                           const int32_t** h_merge_a, const int32_t** h_merge_b, const double** h_merge_d,
+                           const int32_t** h_labels) {
+    if (!c || !P || n_prob < 0 || n_redo < 0) return SPKD_EINVAL;
+    if (!h_n_merges || !h_merge_a || !h_merge_b || !h_merge_d || !h_labels)
+        return fail(c, SPKD_EINVAL, "ahc_fused: null output");
+    *h_n_merges = *h_merge_a = *h_merge_b = *h_labels = nullptr;
+    *h_merge_d = nullptr;
+    if (n_prob == 0) return SPKD_OK;
+    if (!d_records || !d_line_index || !h_seg_off || n_records < 1 || h_seg_off[0] != 0)
+        return fail(c, SPKD_EINVAL, "ahc_fused: null argument or first offset not 0");
+    for (int64_t p = 0; p < n_prob; ++p)
+        if (h_seg_off[p + 1] < h_seg_off[p]) return fail(c, SPKD_EINVAL, "seg_off must be non-decreasing");
+    const int64_t n_total = h_seg_off[n_prob];
+    if (n_redo > 0 && (!h_redo_line || !h_redo_begin || !h_redo_end || !d_frames))
+        return fail(c, SPKD_EINVAL, "ahc_fused: null redo arrays");
+    for (int64_t k = 0; k < n_redo; ++k)
+        if (h_redo_line[k] < 0 || h_redo_line[k] >= n_total || (k > 0 && h_redo_line[k] <= h_redo_line[k - 1]))
+            return fail(c, SPKD_EINVAL, "ahc_fused: redo lines must be ascending line indices");
+    // doubles first: merge_d | stat_max | stat_min, then merge_a | merge_b | labels | n_merges
+    const size_t nt = (size_t)n_total, np = (size_t)n_prob;
+    void* h = nullptr;
+    TRY(pinned(c, PIN_AHC_OUT, (nt + 2 * np) * sizeof(double) + (3 * nt + np) * sizeof(int32_t), &h));
+    double* md = (double*)h;
+    double* smax = md + nt;
+    double* smin = smax + np;
+    int32_t* ma = (int32_t*)(smin + np);
+    int32_t* mb = ma + nt;
+    int32_t* lab = mb + nt;
+    int32_t* nm = lab + nt;
+    MatrixPlan plan;
+    plan.d_map = d_line_index;
+    plan.n_src = n_records;
+    plan.d_frames = d_frames;
+    plan.n_frames = n_frames;
+    plan.redo_line = h_redo_line;
+    plan.redo_begin = h_redo_begin;
+    plan.redo_end = h_redo_end;
+    plan.n_redo = n_redo;
+    TRY(ahc_impl(c, d_records, h_seg_off, n_prob, P, plan, nm, ma, mb, md, smax, smin));
+    if (spkd_labels_from_merges_batch(n_prob, h_seg_off, nm, ma, mb, lab) != SPKD_OK)
+        return fail(c, SPKD_EHIP, "internal error: merge log does not replay");
+    *h_n_merges = nm;
+    *h_merge_a = ma;
+    *h_merge_b = mb;
+    *h_merge_d = md;
+    *h_labels = lab;
+    return SPKD_OK;
 }
 
 // records d_dst[dst[i]] = d_src[src[i]] (dst = NULL: i)

@@ -21,7 +21,7 @@ DIM = 39
 EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_destroy', 'spkd_last_error', 'spkd_sync',
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_set_stats', 'spkd_pair_terms',
-           'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gather_stats', 'spkd_mfcc',
+           'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_mfcc',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi']
@@ -37,6 +37,13 @@ class CandLog(C.Structure):
     _fields_ = [('turn', C.c_int32), ('coarse', C.c_int32), ('seq', C.c_int64),
                 ('start', C.c_double), ('i', C.c_double), ('d', C.c_double),
                 ('n1', C.c_int64), ('n2', C.c_int64)]
+
+
+class GwLinesView(C.Structure):
+    _fields_ = [('n_lines', C.c_int64), ('n_redo', C.c_int64), ('n_win', C.c_void_p), ('times', C.c_void_p),
+                ('turn', C.c_void_p), ('frame_b', C.c_void_p), ('frame_e', C.c_void_p), ('index', C.c_void_p),
+                ('d_index', C.c_void_p), ('redo_line', C.c_void_p), ('redo_begin', C.c_void_p),
+                ('redo_end', C.c_void_p)]
 
 
 AHC_AUTO, AHC_MONO, AHC_WIDE = 0, 1, 2
@@ -165,6 +172,9 @@ def load_library(path=None):
                                vp, vp, i64, P(i64)]
     lib.spkd_gw_fused.argtypes = [vp, vp, i64, vp, vp, i64, P(CdParams), vp, C.c_int, vp, vp, vp, vp, vp, vp,
                                   vp, vp, vp, i64, P(i64)]
+    lib.spkd_gw_batch.argtypes = [vp, vp, i64, vp, vp, i64, P(CdParams), vp, vp, vp, vp, vp, vp, C.c_int, P(GwLinesView)]
+    lib.spkd_ahc_fused.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, P(AhcParams),
+                                   P(vp), P(vp), P(vp), P(vp), P(vp)]
     lib.spkd_gather_stats.argtypes = [vp, vp, i64, vp, vp, i64, i64, vp]
     lib.spkd_mfcc.argtypes = [vp, vp, i64, P(MfccParams), vp, vp, vp, vp, vp, vp, P(i64)]
     lib.spkd_sw_window_count.argtypes = [i64, dbl, dbl]
@@ -191,6 +201,14 @@ def load_library(path=None):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _view(addr, n, dtype):
+    """numpy view of n items of library-owned host memory (no copy)."""
+    if not addr or n <= 0:
+        return np.zeros(0, dtype=dtype)
+    ct = {np.int32: C.c_int32, np.int64: C.c_int64, np.float64: C.c_double}[dtype]
+    return np.ctypeslib.as_array(C.cast(C.c_void_p(addr), C.POINTER(ct)), shape=(int(n),))
 
 
 def py2_roundtrip(values):
@@ -485,6 +503,77 @@ class Context(object):
         return dict(status=st, off=off, n_ev=nev, n_win=n_win, win_maxd=win_maxd, win_det=win_det,
                     det_start=det_start, det_maxi=det_maxi, det_d=det_d, final_start=final_start,
                     log=log, log_count=min(int(cnt.value), log_cap))
+
+    def gw_batch(self, d_frames, n_frames, begins, ends, params, turn_start_s, turn_end_s, file_off, file_len,
+                 seg_stats, tight=True, first_guess_scale=1.0, want_index=False):
+        """The batch hand-off (spkd_gw_batch): gw(seg_stats=...) whose results come back as recipe
+        lines -- times after the 12-digit round trip, turn, the frame range each fused record
+        covers -- plus the redo list, the lines whose range the round trip moved.  The arrays are
+        views of memory the context owns: valid until the next gw_batch on it.  Capacities as
+        in gw(): a first guess that doubles until it fits."""
+        c = np.ascontiguousarray
+        b = c(begins, dtype=np.int64)
+        e = c(ends, dtype=np.int64)
+        nt = len(b)
+        host = [c(turn_start_s, dtype=np.float64), c(turn_end_s, dtype=np.float64), c(file_off, dtype=np.int64),
+                c(file_len, dtype=np.int64)]
+        if any(len(a) != nt for a in host):
+            raise SpkdError(SPKD_EINVAL, 'one entry per turn')
+        if not (params.rate >= 10.0 and params.winstep >= 1.0):
+            raise SpkdError(SPKD_EINVAL, 'unsupported growing-window parameters (frame rate >= 10 and '
+                                         'a window step of at least one frame needed)')
+        step = min(0.2 * params.rate, 0.5 * params.rate, params.winstep)
+        full = ((e - b).astype(np.float64) / step).astype(np.int64) + 8
+        if first_guess_scale != 1.0:
+            full = np.maximum((full * float(first_guess_scale)).astype(np.int64), 2)
+        grow = 1
+        view = GwLinesView()
+        while True:
+            caps = (full // 4 + 8) if tight else full * grow
+            off = np.zeros(nt + 1, dtype=np.int64)
+            off[1:] = np.cumsum(caps)
+            nev = int(off[-1])
+            d_seg = seg_stats(nev)
+            st = self.lib.spkd_gw_batch(self.h, C.c_void_p(d_frames), n_frames, _ptr(b), _ptr(e), nt, C.byref(params),
+                                        _ptr(off), *[_ptr(a) for a in host], C.c_void_p(d_seg),
+                                        1 if want_index else 0, C.byref(view))
+            if st == SPKD_EOVERFLOW and tight:
+                tight = False
+                continue
+            if st == SPKD_EOVERFLOW and grow < 1024:
+                grow *= 2
+                continue
+            self.check(st, allow=(SPKD_ENONFINITE,))
+            break
+        n, nr = int(view.n_lines), int(view.n_redo)
+        return dict(status=st, off=off, n_ev=nev, d_seg=d_seg, n_lines=n, n_win=_view(view.n_win, nt if n else 0, np.int32),
+                    times=_view(view.times, 2 * n, np.float64).reshape(-1, 2), turn=_view(view.turn, n, np.int32),
+                    frame_b=_view(view.frame_b, n, np.int64), frame_e=_view(view.frame_e, n, np.int64),
+                    index=_view(view.index, n, np.int64) if want_index else None, d_index=view.d_index,
+                    redo_line=_view(view.redo_line, nr, np.int64), redo_begin=_view(view.redo_begin, nr, np.int64),
+                    redo_end=_view(view.redo_end, nr, np.int64))
+
+    def ahc_fused(self, d_frames, n_frames, d_records, n_records, d_line_index, seg_off, redo_line, redo_begin,
+                  redo_end, params):
+        """spkd_ahc_fused: redo statistics, working copies read through the line -> record map,
+        matrix, merge loop and label replay in one call.  The arrays are views of memory the
+        context owns: valid until the next ahc_fused on it."""
+        c = np.ascontiguousarray
+        seg_off = c(seg_off, dtype=np.int64)
+        rl, rb, re_ = c(redo_line, dtype=np.int64), c(redo_begin, dtype=np.int64), c(redo_end, dtype=np.int64)
+        if not (len(rl) == len(rb) == len(re_)):
+            raise SpkdError(SPKD_EINVAL, 'one range per redo line')
+        npb, nt = len(seg_off) - 1, int(seg_off[-1])
+        out = [C.c_void_p() for _ in range(5)]
+        st = self.lib.spkd_ahc_fused(self.h, C.c_void_p(d_frames), n_frames, C.c_void_p(d_records), n_records,
+                                     C.c_void_p(d_line_index), _ptr(seg_off), npb, _ptr(rl), _ptr(rb), _ptr(re_), len(rl),
+                                     C.byref(params), *[C.byref(o) for o in out])
+        self.check(st, allow=(SPKD_ENONFINITE,))
+        if st != SPKD_OK:
+            return dict(status=st)
+        return dict(status=st, n_merges=_view(out[0].value, npb, np.int32), a=_view(out[1].value, nt, np.int32),
+                    b=_view(out[2].value, nt, np.int32), d=_view(out[3].value, nt, np.float64),
+                    labels=_view(out[4].value, nt, np.int32))
 
     def sw(self, d_frames, n_frames, begins, ends, params):
         b = np.ascontiguousarray(begins, dtype=np.int64)

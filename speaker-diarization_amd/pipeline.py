@@ -211,14 +211,121 @@ def cluster_batch(ctx, d_frames, total_frames, files, segments, rate=125.0, cl=D
     return out
 
 
+def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl=DIA2_CL, timings=None,
+                         detail=None, first_guess_scale=1.0):
+    """diarize_batch(fused=True) with the hand-off between the two stages on the device: the
+    detector's results come back as recipe lines (spkd_gw_batch: compacted in recipe order
+    behind k_gw, round trip and redo list in one native pass), and the clustering stage reads
+    the fused records in place through the line -> record map the compaction left, in one call
+    (spkd_ahc_fused: redo statistics, working copies, matrix, merge loop, label replay).  Same
+    rows as the host hand-off: the same records go through the same kernels.
+    detail: a dict; receives the gw_batch result with its host index map ('lines') and the merge
+    log per file with segments ('merges', as cluster_batch's want_merges)."""
+    rate = float(rate)
+    _t0 = time.perf_counter()
+    nturn = [len(f.vad) for f in files]
+    if sum(nturn) == 0:
+        return [np.zeros((0, 3)) for _ in files]
+    vad = np.concatenate([f.vad_arr for f in files])
+    owner = np.repeat(np.arange(len(files)), nturn)
+    foff = np.array([f.frame_off for f in files], dtype=np.int64)[owner]
+    fn = np.array([f.n_frames for f in files], dtype=np.int64)[owner]
+    ls, le = np.ascontiguousarray(vad[:, 0]), np.ascontiguousarray(vad[:, 1])
+    f0 = np.minimum((ls * rate).astype(np.int64), fn)
+    f1 = np.maximum(f0, np.minimum((le * rate).astype(np.int64), fn))
+    tb, te = foff + f0, foff + f1
+    p = hipabi.CdParams(hipabi.KINDS[cd['kind']], 0, cd['lambdac'], cd['threshold'],
+                        float(np.floor(cd['winsize_s'] * rate)), float(np.floor(cd['winstep_s'] * rate)),
+                        float(np.floor(rate * cd['deltaws_s'])), rate)
+    _t1 = time.perf_counter()
+    r = ctx.gw_batch(d_frames, total_frames, tb, te, p, ls, le, foff, fn,
+                     lambda n_rec: ctx.dev_scratch('fused_segment_stats', max(n_rec, 1) * hipabi.REC * 8),
+                     tight=True, first_guess_scale=first_guess_scale, want_index=detail is not None)
+    _t2 = time.perf_counter()
+    if timings is not None:
+        timings.setdefault('gw', []).append(ctx.last_ms('gw'))
+        timings.setdefault('gw_stream_ms', []).append(ctx.last_ms('call'))
+        timings['gw_frames'] = int((te - tb).sum())
+        timings['gw_windows'] = int(r['n_win'].sum())
+        timings['gw_dets'] = ctx.last_gw_items()
+    if r['status'] == hipabi.SPKD_ENONFINITE:
+        raise ValueError('array must not contain infs or NaNs')
+    rt = r['times']
+    n = r['n_lines']
+    line_file = owner[r['turn']]
+    bounds = np.searchsorted(line_file, np.arange(len(files) + 1))
+    _t3 = time.perf_counter()
+    # files without a line are not clustering problems; the lines of the others stay in place
+    cnt = np.diff(bounds)
+    kept = np.nonzero(cnt)[0]
+    seg_off = np.zeros(len(kept) + 1, dtype=np.int64)
+    seg_off[1:] = np.cumsum(cnt[kept])
+    ap = hipabi.AhcParams(cl['variant'], hipabi.KINDS[cl['kind']], cl['max_spk'], cl.get('path', 0),
+                          cl['lambdac'], cl['threshold'])
+    n_redo = len(r['redo_line'])
+    _t4 = time.perf_counter()
+    a = ctx.ahc_fused(d_frames, total_frames, r['d_seg'], r['n_ev'], r['d_index'], seg_off, r['redo_line'],
+                      r['redo_begin'], r['redo_end'], ap)
+    _t5 = time.perf_counter()
+    if timings is not None:
+        if n_redo:
+            timings.setdefault('chunk_stats', []).append(ctx.last_ms('chunk_stats'))
+            timings.setdefault('reduce_sets', []).append(ctx.last_ms('reduce_sets'))
+        timings['stats_frames'] = int((r['redo_end'] - r['redo_begin']).sum())
+        timings['stats_sets'] = n
+        timings['stats_recomputed'] = n_redo
+        for k in ('cluster_prep', 'matrix', 'ahc'):
+            timings.setdefault(k, []).append(ctx.last_ms(k))
+    if a['status'] == hipabi.SPKD_ENONFINITE:
+        raise ValueError('array must not contain infs or NaNs')
+    if timings is not None:
+        npb = np.diff(seg_off)
+        nm = a['n_merges'].astype(np.int64)
+        timings['matrix_pairs'] = int((npb * (npb - 1) // 2).sum())
+        timings['ahc_pairs'] = int((nm * (npb - 2) - nm * (nm - 1) // 2).sum())
+    if detail is not None:
+        detail['lines'] = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
+        detail['merges'] = [list(zip(a['a'][o:o + m].tolist(), a['b'][o:o + m].tolist(), a['d'][o:o + m].tolist()))
+                            for o, m in zip(seg_off[:-1].tolist(), a['n_merges'].tolist())]
+    # recipe order of spk_cluster_hi's output: per file, sorted by (start*rate, end*rate, line);
+    # the detector emits a file's lines in time order, so one O(n) look almost always settles it
+    k0, k1 = rt[:, 0] * rate, rt[:, 1] * rate
+    in_order = (line_file[1:] != line_file[:-1]) | (k0[1:] > k0[:-1]) | ((k0[1:] == k0[:-1]) & (k1[1:] >= k1[:-1]))
+    rows = np.column_stack([rt, a['labels'].astype(np.float64)])       # (a copy: rt and the labels are views)
+    if not bool(in_order.all()):
+        rows = rows[np.lexsort((np.arange(n), k1, k0, line_file))]
+    out = [rows[bounds[i]:bounds[i + 1]] for i in range(len(files))]
+    if timings is not None:
+        _t6 = time.perf_counter()
+        timings.setdefault('wall_cd_prepare', []).append(1e3 * (_t1 - _t0))
+        timings.setdefault('wall_cd_call', []).append(1e3 * (_t2 - _t1))
+        timings.setdefault('wall_cd_finish', []).append(1e3 * (_t3 - _t2))
+        timings.setdefault('wall_cl_prepare', []).append(1e3 * (_t4 - _t3))
+        timings.setdefault('wall_cl_stats_call', []).append(0.0)      # (the redo statistics are part of the one call)
+        timings.setdefault('wall_cl_ahc_call', []).append(1e3 * (_t5 - _t4))
+        timings.setdefault('wall_cl_finish', []).append(1e3 * (_t6 - _t5))
+    return out
+
+
 def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl=DIA2_CL, timings=None,
-                  text_contract=True, fused=False):
+                  text_contract=True, fused=False, handoff=None):
     """CD (gw/BIC) + CL (hi/BIC) for a batch; returns per file an array of rows
     [start_s, end_s, speaker] in recipe order.
     fused=True: the frames are read once -- the change detector leaves every segment's
     statistics record for the clustering stage (segments and labels are those of the
     two-pass form; a record differs from the two-pass one only in the order of its
-    floating-point sums)."""
+    floating-point sums).
+    handoff: 'device' (the default of fused=True with the text contract: diarize_batch_device)
+    or 'host' (the event arrays come to the host, which builds the lines and gathers the
+    records: the only form of the two-pass and text_contract=False modes)."""
+    if handoff is None:
+        handoff = 'device' if fused and text_contract else 'host'
+    if handoff == 'device':
+        if not (fused and text_contract):
+            raise ValueError('the device hand-off is the fused mode with the text contract')
+        return diarize_batch_device(ctx, d_frames, total_frames, files, rate, cd, cl, timings)
+    if handoff != 'host':
+        raise ValueError('handoff: device or host')
     box = [] if fused else None
     segs = change_detect_batch(ctx, d_frames, total_frames, files, rate, cd, timings, text_contract, box)
     fs = box[0] if box else None
