@@ -132,13 +132,9 @@ constexpr int PT_WAVES = 4;
 
 // Packed -> quad records (see spkd_quad.hpp).  The packed form (6 560 B) stays the
 // ABI format; the clustering kernels keep their working set as quad records.
-__global__ __launch_bounds__(256) void k_to_quadrec(const double* __restrict__ packed, int64_t n_rec,
-                                                    double* __restrict__ qr) {
-    const int64_t c = blockIdx.x;
-    if (c >= n_rec) return;
-    const double* g = packed + c * REC;
-    double* o = qr + c * QREC;
-    for (int e = threadIdx.x; e < QREC; e += 256) {
+// One record by a workgroup of 256 threads: g the packed record, o its quad form.
+__device__ __forceinline__ void quadrec_from_packed(const double* __restrict__ g, double* __restrict__ o, int tid) {
+    for (int e = tid; e < QREC; e += 256) {
         const int t = e & 15, sj = e >> 4;
         const int s = sj / DA, j = sj - s * DA;
         double v = 0.0;
@@ -151,6 +147,13 @@ __global__ __launch_bounds__(256) void k_to_quadrec(const double* __restrict__ p
         }
         o[e] = v;
     }
+}
+
+__global__ __launch_bounds__(256) void k_to_quadrec(const double* __restrict__ packed, int64_t n_rec,
+                                                    double* __restrict__ qr) {
+    const int64_t c = blockIdx.x;
+    if (c >= n_rec) return;
+    quadrec_from_packed(packed + c * REC, qr + c * QREC, threadIdx.x);
 }
 
 // row-per-lane (single matrix) rows of a packed record, by symmetry (k_gw's cache records)

@@ -15,6 +15,7 @@
 #include "spkd_cd.hpp"
 #include "spkd_cluster.hpp"
 #include "spkd_device.hpp"
+#include "spkd_handoff.hpp"
 #include "spkd_stats.hpp"
 #include "spkd_mfcc.hpp"
 #include "spkd_vad.hpp"
@@ -459,50 +460,6 @@ struct MatrixPlan {
     const int64_t *redo_line = nullptr, *redo_begin = nullptr, *redo_end = nullptr;
     int64_t n_redo = 0;
 };
-
-// line -> source record of spkd_ahc_fused: -(k + 1) stands for record k of the redo buffer
-__global__ __launch_bounds__(256) void k_patch_map(const int64_t* __restrict__ line, int64_t n, int64_t* __restrict__ map) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k < n) map[line[k]] = -(k + 1);
-}
-
-// k_to_quadrec reading every record through the line -> record map, and leaving the packed
-// working copy beside the quad one: the record is fetched once, from where the detector (or
-// the redo statistics) wrote it.  A map entry outside both buffers sets the capacity bit.
-__global__ __launch_bounds__(256) void k_records_from_map(const double* __restrict__ recs, int64_t n_recs,
-                                                          const int64_t* __restrict__ map,
-                                                          const double* __restrict__ redo, int64_t n_redo,
-                                                          int64_t n_rec, double* __restrict__ qr,
-                                                          double* __restrict__ packed, int* __restrict__ err) {
-    const int64_t c = blockIdx.x;
-    if (c >= n_rec) return;
-    const int64_t m = map[c];
-    const double* g;
-    if (m >= 0 && m < n_recs) {
-        g = recs + m * REC;
-    } else if (m < 0 && -(m + 1) < n_redo) {
-        g = redo + (-(m + 1)) * REC;
-    } else {
-        if (threadIdx.x == 0) atomicOr(err, 4);
-        return;
-    }
-    double* o = qr + c * QREC;
-    for (int e = threadIdx.x; e < QREC; e += 256) {          // (k_to_quadrec's map)
-        const int t = e & 15, sj = e >> 4;
-        const int s = sj / DA, j = sj - s * DA;
-        double v = 0.0;
-        if (t < QL) {
-            const int i = QL * s + t;
-            const int r = i < j ? i : j, cc = i < j ? j : i;
-            v = g[pk(r, cc)];
-        } else if (e == QREC_COUNT_AT) {
-            v = g[REC - 1];
-        }
-        o[e] = v;
-    }
-    double* p = packed + c * REC;
-    for (int e = threadIdx.x; e < REC; e += 256) p[e] = g[e];
-}
 
 spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_off, int64_t n_prob,
                         int variant, int kind, double lambdac, AhcBuffers& B, int64_t& n_total,
@@ -996,105 +953,6 @@ spkd_status build_turns(spkd_ctx* c, int64_t n_frames, const int64_t* hb, const 
     if (gw) std::stable_sort(turns.begin(), turns.end(), [](const TurnDesc& a, const TurnDesc& b) { return a.len > b.len; });
     return SPKD_OK;
 }
-}  // namespace
-
-namespace {
-// ---- the batch hand-off behind k_gw (spkd_gw_batch): event slots -> recipe lines, on the device.
-// All three kernels return at once when the error word is set (a capacity overflow leaves
-// counts that mean nothing); the host looks at the word before it uses anything.
-constexpr int CP_TPB = 256;
-constexpr int CP_SCAN_TPB = 1024;
-
-// per launch position: the turn's detections = the ones among its n_win window flags, filed
-// under the caller's turn index together with the position (k_cp_lines finds the turn by it)
-__global__ __launch_bounds__(CP_TPB) void k_cp_count(const TurnDesc* __restrict__ turns, int64_t n_turns,
-                                                     const int32_t* __restrict__ n_win,
-                                                     const int32_t* __restrict__ win_det, const int* __restrict__ err,
-                                                     int32_t* __restrict__ n_det, int32_t* __restrict__ pos) {
-    if (*err) return;
-    const int64_t p = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
-    if (p >= n_turns) return;
-    const TurnDesc T = turns[p];
-    int64_t nw = n_win[T.id];
-    nw = nw < 0 ? 0 : (nw > T.ev_cap ? T.ev_cap : nw);
-    const int32_t* f = win_det + T.ev_off;
-    int32_t cnt = 0;
-    for (int64_t i = 0; i < nw; ++i) cnt += f[i] != 0;
-    n_det[T.id] = cnt;
-    pos[T.id] = (int32_t)p;
-}
-
-// exclusive scan of (detections + 1) over the turns in the caller's order -> first line of every
-// turn, line_off[n_turns] = number of lines.  One workgroup: a run of turns per thread.
-__global__ __launch_bounds__(CP_SCAN_TPB) void k_cp_scan(const int32_t* __restrict__ n_det, int64_t n_turns,
-                                                         const int* __restrict__ err, int64_t* __restrict__ line_off) {
-    __shared__ int64_t part[CP_SCAN_TPB];
-    const int tid = threadIdx.x;
-    if (*err) {
-        if (tid == 0) line_off[n_turns] = 0;
-        return;
-    }
-    const int64_t per = (n_turns + CP_SCAN_TPB - 1) / CP_SCAN_TPB;
-    const int64_t lo = tid * per < n_turns ? tid * per : n_turns;
-    const int64_t hi = lo + per < n_turns ? lo + per : n_turns;
-    int64_t sum = 0;
-    for (int64_t t = lo; t < hi; ++t) sum += (int64_t)n_det[t] + 1;
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < CP_SCAN_TPB; d <<= 1) {
-        const int64_t v = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int64_t run = part[tid] - sum;
-    for (int64_t t = lo; t < hi; ++t) {
-        line_off[t] = run;
-        run += (int64_t)n_det[t] + 1;
-    }
-    if (tid == CP_SCAN_TPB - 1) line_off[n_turns] = part[tid];
-}
-
-// per turn (caller's order) its lines: spkd_gw_lines with frame outputs, operation for operation
-__global__ __launch_bounds__(CP_TPB) void k_cp_lines(const TurnDesc* __restrict__ turns, int64_t n_turns,
-                                                     const int32_t* __restrict__ n_det, const int32_t* __restrict__ pos,
-                                                     const int64_t* __restrict__ line_off, int64_t n_lines,
-                                                     const double* __restrict__ det_start,
-                                                     const double* __restrict__ det_maxi,
-                                                     const double* __restrict__ final_start,
-                                                     const double* __restrict__ turn_start_s,
-                                                     const double* __restrict__ turn_end_s, double rate,
-                                                     const int* __restrict__ err, double* __restrict__ times,
-                                                     int64_t* __restrict__ frame_b, int64_t* __restrict__ frame_e,
-                                                     int64_t* __restrict__ index, int32_t* __restrict__ line_turn) {
-#pragma clang fp contract(off)
-    if (*err) return;
-    const int64_t t = (int64_t)blockIdx.x * CP_TPB + threadIdx.x;
-    if (t >= n_turns) return;
-    const TurnDesc T = turns[pos[t]];
-    const int64_t nd = n_det[t];
-    const double ls = turn_start_s[t], le = turn_end_s[t];
-    int64_t i = line_off[t];
-    for (int64_t j = 0; j <= nd && i < n_lines; ++j, ++i) {
-        const bool tail = j == nd;
-        double fs, fe;
-        if (tail) {
-            fs = final_start[t];
-            times[2 * i] = fs / rate + ls;
-            times[2 * i + 1] = ((le - ls) * rate) / rate + ls;
-            fe = 0.0;
-        } else {
-            fs = det_start[T.ev_off + j];
-            fe = fs + det_maxi[T.ev_off + j];
-            times[2 * i] = fs / rate + ls;
-            times[2 * i + 1] = fe / rate + ls;
-        }
-        frame_b[i] = T.begin + (int64_t)fs;
-        frame_e[i] = tail ? T.begin + T.len : T.begin + (int64_t)fe;
-        index[i] = T.ev_off + j;
-        line_turn[i] = (int32_t)t;
-    }
-}
 
 // what spkd_gw_batch adds to the growing-window call
 struct GwBatch {
@@ -1218,31 +1076,48 @@ spkd_status gw_batch_finish(spkd_ctx* c, GwBatch& G, int64_t n_turns, double rat
     return SPKD_OK;
 }
 
+// what a growing-window call reads ...
+struct GwIn {
+    const float* d_frames = nullptr;
+    int64_t n_frames = 0, n_turns = 0;
+    const int64_t *hb = nullptr, *he = nullptr, *h_ev_off = nullptr;
+    const spkd_cd_params* P = nullptr;
+    int check_capacity = 0;
+    double* d_seg_stats = nullptr;                   // the fused forms: a record per event slot
+};
+// ... and where it leaves the event arrays and the candidate log on the host (the batch form
+// copies none of them)
+struct GwOut {
+    int32_t *h_n_win = nullptr, *h_win_det = nullptr;
+    double *h_win_maxd = nullptr, *h_det_start = nullptr, *h_det_maxi = nullptr, *h_det_d = nullptr,
+           *h_final_start = nullptr;
+    spkd_cand_log* h_log = nullptr;
+    int64_t log_cap = 0;
+    int64_t* h_log_count = nullptr;
+};
+
 // from this many turns on, a wave per turn (2 048 wave slots on the chip at two waves per SIMD)
 constexpr int64_t GW_WAVE_PER_TURN_FROM = 4096;
 constexpr int64_t GW_EIGHT_WAVES_UP_TO = 256;           // a workgroup per CU: eight waves per turn
-spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
-                    const int64_t* he, int64_t n_turns, const spkd_cd_params* P, const int64_t* h_ev_off,
-                    int check_capacity, int32_t* h_n_win, double* h_win_maxd, int32_t* h_win_det,
-                    double* h_det_start, double* h_det_maxi, double* h_det_d, double* h_final_start,
-                    double* d_seg_stats, spkd_cand_log* h_log, int64_t log_cap, int64_t* h_log_count,
-                    GwBatch* batch = nullptr) {
+spkd_status gw_impl(spkd_ctx* c, const GwIn& in, const GwOut& out, GwBatch* batch = nullptr) {
+    const int64_t n_turns = in.n_turns, log_cap = out.log_cap;
+    const spkd_cd_params* P = in.P;
     if (!c || !P || n_turns < 0) return SPKD_EINVAL;
-    if (h_log_count) *h_log_count = 0;
+    if (out.h_log_count) *out.h_log_count = 0;
     if (n_turns == 0) return SPKD_OK;
-    if (!d_frames || !hb || !he || !h_ev_off) return fail(c, SPKD_EINVAL, "null argument");
-    // (the batch form copies none of the event arrays)
-    if (!batch && (!h_n_win || !h_win_maxd || !h_win_det || !h_det_start || !h_det_maxi || !h_det_d || !h_final_start))
+    if (!in.d_frames || !in.hb || !in.he || !in.h_ev_off) return fail(c, SPKD_EINVAL, "null argument");
+    if (!batch && (!out.h_n_win || !out.h_win_maxd || !out.h_win_det || !out.h_det_start || !out.h_det_maxi ||
+                   !out.h_det_d || !out.h_final_start))
         return fail(c, SPKD_EINVAL, "null argument");
     if (P->kind < 0 || P->kind > 3) return fail(c, SPKD_EINVAL, "gw: bad kind");
     if (!(P->rate >= 10.0) || !(P->winsize >= 1.0) || !(P->winstep >= 1.0))
         return fail(c, SPKD_EINVAL, "gw: rate >= 10, winsize >= 1 frame and winstep >= 1 frame required");
-    if (log_cap < 0 || (log_cap > 0 && !h_log)) return fail(c, SPKD_EINVAL, "gw: log capacity without a log buffer");
+    if (log_cap < 0 || (log_cap > 0 && !out.h_log)) return fail(c, SPKD_EINVAL, "gw: log capacity without a log buffer");
     if (!c->gw_lds_ok) return fail(c, SPKD_EHIP, "gw: the kernel's dynamic LDS size was not admitted on this device");
     std::vector<TurnDesc> turns;
     int64_t n_cand;
-    TRY(build_turns(c, n_frames, hb, he, n_turns, P, h_ev_off, true, turns, n_cand));
-    for (int64_t t = 0; check_capacity && t < n_turns; ++t)
+    TRY(build_turns(c, in.n_frames, in.hb, in.he, n_turns, P, in.h_ev_off, true, turns, n_cand));
+    for (int64_t t = 0; in.check_capacity && t < n_turns; ++t)
         if (turns[(size_t)t].ev_cap < spkd_gw_event_capacity_p(turns[(size_t)t].len, P))
             return fail(c, SPKD_EINVAL, "gw: event capacity too small, see spkd_gw_event_capacity_p");
     unsigned long long cnt2[2] = {0ull, 0ull};
@@ -1251,7 +1126,7 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
     spkd_cd_params Pk = *P;                          // (kind as the kernel takes it)
     TRY(use_kind(c, P->kind, &Pk.kind));
     P = &Pk;
-    const int64_t n_ev = h_ev_off[n_turns];
+    const int64_t n_ev = in.h_ev_off[n_turns];
     TurnDesc* d_turns = nullptr;
     void *d_snap = nullptr, *d_cand = nullptr, *d_i32a = nullptr, *d_i32b = nullptr, *d_d0 = nullptr, *d_d1 = nullptr,
          *d_d2 = nullptr, *d_d3 = nullptr, *d_d4 = nullptr, *d_log = nullptr;
@@ -1283,9 +1158,9 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
         nw = n_turns >= GW_WAVE_PER_TURN_FROM ? 1 : (n_turns <= GW_EIGHT_WAVES_UP_TO ? 8 : 4);
 #define SPKD_GW_LAUNCH(NW_)                                                                                     \
     hipLaunchKernelGGL(k_gw<NW_>, dim3((unsigned)n_turns), dim3(Gw<NW_>::TPB), Gw<NW_>::LDS_BYTES, c->stream, \
-                       d_frames, (const TurnDesc*)d_turns, *P, (double*)d_snap, (double*)d_cand,               \
+                       in.d_frames, (const TurnDesc*)d_turns, *P, (double*)d_snap, (double*)d_cand,            \
                        (int32_t*)d_i32a, (double*)d_d0, (int32_t*)d_i32b, (double*)d_d1, (double*)d_d2,        \
-                       (double*)d_d3, (double*)d_d4, d_seg_stats, (spkd_cand_log*)d_log, (long long)log_cap,   \
+                       (double*)d_d3, (double*)d_d4, in.d_seg_stats, (spkd_cand_log*)d_log, (long long)log_cap,   \
                        c->d_counter, c->d_err, c->pinv_cur)
     {
         Timer t(c, SPKD_T_GW);
@@ -1305,22 +1180,22 @@ spkd_status gw_impl(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
         if (!batch->have_lines) return fail(c, SPKD_EHIP, "internal error: no lines from a clean call");
         return gw_batch_finish(c, *batch, n_turns, P->rate);
     }
-    HIPCHK(c, hipMemcpyAsync(h_n_win, d_i32a, (size_t)n_turns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_win_maxd, d_d0, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_win_det, d_i32b, (size_t)n_ev * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_det_start, d_d1, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_det_maxi, d_d2, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_det_d, d_d3, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_final_start, d_d4, (size_t)n_turns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out.h_n_win, d_i32a, (size_t)n_turns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out.h_win_maxd, d_d0, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out.h_win_det, d_i32b, (size_t)n_ev * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out.h_det_start, d_d1, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out.h_det_maxi, d_d2, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out.h_det_d, d_d3, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out.h_final_start, d_d4, (size_t)n_turns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(cnt2, c->d_counter, sizeof cnt2, hipMemcpyDeviceToHost, c->stream));
     const spkd_status st = call.finish();
     c->last_gw_items = (int64_t)cnt2[1];
-    if (h_log_count) *h_log_count = (int64_t)cnt;
-    if (h_log && log_cap > 0 && cnt > 0) {
+    if (out.h_log_count) *out.h_log_count = (int64_t)cnt;
+    if (out.h_log && log_cap > 0 && cnt > 0) {
         const size_t ncopy = (size_t)std::min<int64_t>((int64_t)cnt, log_cap);
-        HIPCHK(c, hipMemcpy(h_log, d_log, ncopy * sizeof(spkd_cand_log), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out.h_log, d_log, ncopy * sizeof(spkd_cand_log), hipMemcpyDeviceToHost));
     }
-    if (st == SPKD_OK && (int64_t)cnt > log_cap && h_log)
+    if (st == SPKD_OK && (int64_t)cnt > log_cap && out.h_log)
         return fail(c, SPKD_EOVERFLOW, "candidate log too small");
     return st;
 }
@@ -1331,8 +1206,14 @@ spkd_status spkd_gw(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
                     int32_t* h_n_win, double* h_win_maxd, int32_t* h_win_det, double* h_det_start,
                     double* h_det_maxi, double* h_det_d, double* h_final_start, spkd_cand_log* h_log,
                     int64_t log_cap, int64_t* h_log_count) {
-    return gw_impl(c, d_frames, n_frames, hb, he, n_turns, P, h_ev_off, 1, h_n_win, h_win_maxd, h_win_det,
-                   h_det_start, h_det_maxi, h_det_d, h_final_start, nullptr, h_log, log_cap, h_log_count);
+    GwIn in;
+    in.d_frames = d_frames; in.n_frames = n_frames; in.hb = hb; in.he = he; in.n_turns = n_turns;
+    in.P = P; in.h_ev_off = h_ev_off; in.check_capacity = 1;
+    GwOut out;
+    out.h_n_win = h_n_win; out.h_win_maxd = h_win_maxd; out.h_win_det = h_win_det; out.h_det_start = h_det_start;
+    out.h_det_maxi = h_det_maxi; out.h_det_d = h_det_d; out.h_final_start = h_final_start;
+    out.h_log = h_log; out.log_cap = log_cap; out.h_log_count = h_log_count;
+    return gw_impl(c, in, out);
 }
 
 spkd_status spkd_gw_ex(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
@@ -1340,9 +1221,14 @@ spkd_status spkd_gw_ex(spkd_ctx* c, const float* d_frames, int64_t n_frames, con
                        int check_capacity, int32_t* h_n_win, double* h_win_maxd, int32_t* h_win_det,
                        double* h_det_start, double* h_det_maxi, double* h_det_d, double* h_final_start,
                        spkd_cand_log* h_log, int64_t log_cap, int64_t* h_log_count) {
-    return gw_impl(c, d_frames, n_frames, hb, he, n_turns, P, h_ev_off, check_capacity, h_n_win, h_win_maxd,
-                   h_win_det, h_det_start, h_det_maxi, h_det_d, h_final_start, nullptr, h_log, log_cap,
-                   h_log_count);
+    GwIn in;
+    in.d_frames = d_frames; in.n_frames = n_frames; in.hb = hb; in.he = he; in.n_turns = n_turns;
+    in.P = P; in.h_ev_off = h_ev_off; in.check_capacity = check_capacity;
+    GwOut out;
+    out.h_n_win = h_n_win; out.h_win_maxd = h_win_maxd; out.h_win_det = h_win_det; out.h_det_start = h_det_start;
+    out.h_det_maxi = h_det_maxi; out.h_det_d = h_det_d; out.h_final_start = h_final_start;
+    out.h_log = h_log; out.log_cap = log_cap; out.h_log_count = h_log_count;
+    return gw_impl(c, in, out);
 }
 
 spkd_status spkd_gw_fused(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
@@ -1351,9 +1237,14 @@ spkd_status spkd_gw_fused(spkd_ctx* c, const float* d_frames, int64_t n_frames, 
                           double* h_det_start, double* h_det_maxi, double* h_det_d, double* h_final_start,
                           double* d_seg_stats, spkd_cand_log* h_log, int64_t log_cap, int64_t* h_log_count) {
     if (c && !d_seg_stats) return fail(c, SPKD_EINVAL, "gw_fused: null statistics buffer");
-    return gw_impl(c, d_frames, n_frames, hb, he, n_turns, P, h_ev_off, check_capacity, h_n_win, h_win_maxd,
-                   h_win_det, h_det_start, h_det_maxi, h_det_d, h_final_start, d_seg_stats, h_log, log_cap,
-                   h_log_count);
+    GwIn in;
+    in.d_frames = d_frames; in.n_frames = n_frames; in.hb = hb; in.he = he; in.n_turns = n_turns;
+    in.P = P; in.h_ev_off = h_ev_off; in.check_capacity = check_capacity; in.d_seg_stats = d_seg_stats;
+    GwOut out;
+    out.h_n_win = h_n_win; out.h_win_maxd = h_win_maxd; out.h_win_det = h_win_det; out.h_det_start = h_det_start;
+    out.h_det_maxi = h_det_maxi; out.h_det_d = h_det_d; out.h_final_start = h_final_start;
+    out.h_log = h_log; out.log_cap = log_cap; out.h_log_count = h_log_count;
+    return gw_impl(c, in, out);
 }
 
 spkd_status spkd_gw_batch(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
@@ -1373,8 +1264,10 @@ spkd_status spkd_gw_batch(spkd_ctx* c, const float* d_frames, int64_t n_frames, 
     G.file_len = h_turn_file_len;
     G.want_index = want_index;
     G.view = view;
-    const spkd_status st = gw_impl(c, d_frames, n_frames, hb, he, n_turns, P, h_ev_off, 0, nullptr, nullptr, nullptr,
-                                   nullptr, nullptr, nullptr, nullptr, d_seg_stats, nullptr, 0, nullptr, &G);
+    GwIn in;
+    in.d_frames = d_frames; in.n_frames = n_frames; in.hb = hb; in.he = he; in.n_turns = n_turns;
+    in.P = P; in.h_ev_off = h_ev_off; in.d_seg_stats = d_seg_stats;
+    const spkd_status st = gw_impl(c, in, GwOut(), &G);
     if (st != SPKD_OK) std::memset(view, 0, sizeof *view);
     return st;
 }
@@ -1432,19 +1325,6 @@ spkd_status spkd_ahc_fused(spkd_ctx* c, const float* d_frames, int64_t n_frames,
     return SPKD_OK;
 }
 
-// records d_dst[dst[i]] = d_src[src[i]] (dst = NULL: i)
-namespace {
-__global__ __launch_bounds__(256) void k_gather_records(const double* __restrict__ src, const int64_t* __restrict__ si,
-                                                        const int64_t* __restrict__ di, int64_t n,
-                                                        double* __restrict__ dst) {
-    const int64_t i = blockIdx.x;
-    if (i >= n) return;
-    const double2* s = reinterpret_cast<const double2*>(src + si[i] * REC);
-    double2* d = reinterpret_cast<double2*>(dst + (di ? di[i] : i) * REC);
-    for (int e = threadIdx.x; e < REC / 2; e += 256) d[e] = s[e];
-}
-}  // namespace
-
 spkd_status spkd_gather_stats(spkd_ctx* c, const double* d_src, int64_t n_src, const int64_t* h_src_index,
                               const int64_t* h_dst_index, int64_t n, int64_t n_dst, double* d_dst) {
     if (!c || n < 0) return SPKD_EINVAL;
@@ -1465,14 +1345,6 @@ spkd_status spkd_gather_stats(spkd_ctx* c, const double* d_src, int64_t n_src, c
     HIPCHK(c, hipGetLastError());
     return call.finish();
 }
-
-namespace {
-// D[0][1] of every 2-record problem of a batch of matrices (4 doubles each) -> out[p]
-__global__ __launch_bounds__(256) void k_take_pair_distance(const double* __restrict__ mat, int64_t n, double* __restrict__ out) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p < n) out[p] = mat[4 * p + 1];
-}
-}  // namespace
 
 // Sliding window (dist_sw, spk-change-detection.py:304-312): window w of a turn compares the
 // frames [a, a + size) with [a + size, a + 2 size), a = int(w * step).  Every window is a pair
@@ -1759,15 +1631,11 @@ spkd_status spkd_count_flags(const int32_t* h_flags, const int64_t* h_off, const
     if (n_groups < 0 || (n_groups > 0 && (!h_flags || !h_off || !h_n || !h_out))) return SPKD_EINVAL;
     for (int64_t g = 0; g < n_groups; ++g) {
         if (h_n[g] < 0 || h_off[g] < 0) return SPKD_EINVAL;
-        const int32_t* f = h_flags + h_off[g];
-        int32_t c = 0;
-        for (int32_t i = 0; i < h_n[g]; ++i) c += f[i] != 0;
-        h_out[g] = c;
+        h_out[g] = count_detections(h_flags + h_off[g], h_n[g]);
     }
     return SPKD_OK;
 }
 
-#pragma clang fp contract(off)
 spkd_status spkd_gw_lines(int64_t n_turns, const int64_t* h_off, const int32_t* h_n_det, const double* h_det_start,
                           const double* h_det_maxi, const double* h_final_start, const double* h_turn_start_s,
                           const double* h_turn_end_s, const int64_t* h_turn_begin, const int64_t* h_turn_end,
@@ -1783,22 +1651,13 @@ spkd_status spkd_gw_lines(int64_t n_turns, const int64_t* h_off, const int32_t* 
         if (nd < 0 || i + nd + 1 > n_lines) return SPKD_EINVAL;
         const double ls = h_turn_start_s[t], le = h_turn_end_s[t];
         for (int64_t j = 0; j <= nd; ++j, ++i) {
-            const bool tail = j == nd;
-            double fs, fe;                       // the line's frame positions inside the turn
-            if (tail) {
-                fs = h_final_start[t];
-                h_times[2 * i] = fs / rate + ls;
-                h_times[2 * i + 1] = ((le - ls) * rate) / rate + ls;
-                fe = 0.0;
-            } else {
-                fs = h_det_start[h_off[t] + j];
-                fe = fs + h_det_maxi[h_off[t] + j];
-                h_times[2 * i] = fs / rate + ls;
-                h_times[2 * i + 1] = fe / rate + ls;
-            }
-            if (h_frame_b) h_frame_b[i] = h_turn_begin[t] + (int64_t)fs;
-            if (h_frame_e) h_frame_e[i] = tail ? h_turn_end[t] : h_turn_begin[t] + (int64_t)fe;
-            if (h_index) h_index[i] = h_off[t] + j;
+            const RecipeLine L = recipe_line(h_turn_begin[t], h_turn_end[t] - h_turn_begin[t], h_off[t], j, nd,
+                                             h_det_start, h_det_maxi, h_final_start + t, ls, le, rate);
+            h_times[2 * i] = L.start_s;
+            h_times[2 * i + 1] = L.end_s;
+            if (h_frame_b) h_frame_b[i] = L.frame_b;
+            if (h_frame_e) h_frame_e[i] = L.frame_e;
+            if (h_index) h_index[i] = L.index;
             if (h_line_turn) h_line_turn[i] = (int32_t)t;
         }
     }

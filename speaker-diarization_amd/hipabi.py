@@ -312,6 +312,33 @@ def labels_from_merges_batch(seg_off, n_merges, a, b):
     return out
 
 
+def _gw_capacity_ladder(turn_len, params, tight, first_guess_scale):
+    """The event capacities a growing-window call is tried with (see Context.gw), as the `off`
+    array of each try: with tight a quarter of the first guess, then the first guess, then the
+    first guess doubled, up to 1024 times.  The caller takes the next one while the call
+    answers SPKD_EOVERFLOW."""
+    if not (params.rate >= 10.0 and params.winstep >= 1.0):
+        raise SpkdError(SPKD_EINVAL, 'unsupported growing-window parameters (frame rate >= 10 and '
+                                     'a window step of at least one frame needed)')
+    # == spkd_gw_event_capacity_p(len, params), vectorised
+    step = min(0.2 * params.rate, 0.5 * params.rate, params.winstep)
+    full = (turn_len.astype(np.float64) / step).astype(np.int64) + 8
+    if first_guess_scale != 1.0:
+        full = np.maximum((full * float(first_guess_scale)).astype(np.int64), 2)
+    grow = 1
+    while True:
+        caps = (full // 4 + 8) if tight else full * grow
+        off = np.zeros(len(full) + 1, dtype=np.int64)
+        off[1:] = np.cumsum(caps)
+        yield off
+        if tight:
+            tight = False                      # an unusually busy turn: the full first guess
+        elif grow < 1024:
+            grow *= 2                          # a turn that re-scans (Context.gw): double until it fits
+        else:
+            return
+
+
 class Context(object):
     """One (device, stream) context; owns nothing but the library's scratch."""
 
@@ -452,19 +479,7 @@ class Context(object):
         b = np.ascontiguousarray(begins, dtype=np.int64)
         e = np.ascontiguousarray(ends, dtype=np.int64)
         nt = len(b)
-        if not (params.rate >= 10.0 and params.winstep >= 1.0):
-            raise SpkdError(SPKD_EINVAL, 'unsupported growing-window parameters (frame rate >= 10 and '
-                                         'a window step of at least one frame needed)')
-        # == spkd_gw_event_capacity_p(len, params), vectorised
-        step = min(0.2 * params.rate, 0.5 * params.rate, params.winstep)
-        full = ((e - b).astype(np.float64) / step).astype(np.int64) + 8
-        if first_guess_scale != 1.0:
-            full = np.maximum((full * float(first_guess_scale)).astype(np.int64), 2)
-        grow = 1
-        while True:
-            caps = (full // 4 + 8) if tight else full * grow
-            off = np.zeros(nt + 1, dtype=np.int64)
-            off[1:] = np.cumsum(caps)
+        for off in _gw_capacity_ladder(e - b, params, tight, first_guess_scale):
             nev = int(off[-1])
             mk = self._buf if reuse else (lambda name, n, dt: np.empty(n, dtype=dt))
             n_win = mk('n_win', nt, np.int32)
@@ -474,32 +489,28 @@ class Context(object):
             det_maxi = mk('det_maxi', nev, np.float64)
             det_d = mk('det_d', nev, np.float64)
             final_start = mk('final_start', nt, np.float64)
-            log = (CandLog * max(log_cap, 1))()
-            cnt = C.c_int64(0)
-            if seg_stats is None:
-                st = self.lib.spkd_gw_ex(self.h, C.c_void_p(d_frames), n_frames, _ptr(b), _ptr(e), nt,
-                                         C.byref(params), _ptr(off), 0, _ptr(n_win),
-                                         _ptr(win_maxd), _ptr(win_det), _ptr(det_start), _ptr(det_maxi),
-                                         _ptr(det_d), _ptr(final_start), C.cast(log, C.c_void_p), log_cap,
-                                         C.byref(cnt))
-            else:
-                d_seg = seg_stats(nev)
-                st = self.lib.spkd_gw_fused(self.h, C.c_void_p(d_frames), n_frames, _ptr(b), _ptr(e), nt,
-                                            C.byref(params), _ptr(off), 0, _ptr(n_win),
-                                            _ptr(win_maxd), _ptr(win_det), _ptr(det_start), _ptr(det_maxi),
-                                            _ptr(det_d), _ptr(final_start), C.c_void_p(d_seg),
-                                            C.cast(log, C.c_void_p), log_cap, C.byref(cnt))
-            if st == SPKD_EOVERFLOW and cnt.value > log_cap:
+            d_seg = None if seg_stats is None else seg_stats(nev)
+            while True:
+                log = (CandLog * max(log_cap, 1))()
+                cnt = C.c_int64(0)
+                if seg_stats is None:
+                    st = self.lib.spkd_gw_ex(self.h, C.c_void_p(d_frames), n_frames, _ptr(b), _ptr(e), nt,
+                                             C.byref(params), _ptr(off), 0, _ptr(n_win),
+                                             _ptr(win_maxd), _ptr(win_det), _ptr(det_start), _ptr(det_maxi),
+                                             _ptr(det_d), _ptr(final_start), C.cast(log, C.c_void_p), log_cap,
+                                             C.byref(cnt))
+                else:
+                    st = self.lib.spkd_gw_fused(self.h, C.c_void_p(d_frames), n_frames, _ptr(b), _ptr(e), nt,
+                                                C.byref(params), _ptr(off), 0, _ptr(n_win),
+                                                _ptr(win_maxd), _ptr(win_det), _ptr(det_start), _ptr(det_maxi),
+                                                _ptr(det_d), _ptr(final_start), C.c_void_p(d_seg),
+                                                C.cast(log, C.c_void_p), log_cap, C.byref(cnt))
+                if not (st == SPKD_EOVERFLOW and cnt.value > log_cap):
+                    break
                 log_cap = int(cnt.value) + 16      # the run is deterministic: retry with room
-                continue
-            if st == SPKD_EOVERFLOW and tight:
-                tight = False                      # an unusually busy turn: the full first guess
-                continue
-            if st == SPKD_EOVERFLOW and grow < 1024:
-                grow *= 2                          # a turn that re-scans (see above): double until it fits
-                continue
-            self.check(st, allow=(SPKD_ENONFINITE,))
-            break
+            if st != SPKD_EOVERFLOW:
+                break
+        self.check(st, allow=(SPKD_ENONFINITE,))
         return dict(status=st, off=off, n_ev=nev, n_win=n_win, win_maxd=win_maxd, win_det=win_det,
                     det_start=det_start, det_maxi=det_maxi, det_d=det_d, final_start=final_start,
                     log=log, log_count=min(int(cnt.value), log_cap))
@@ -519,32 +530,16 @@ class Context(object):
                 c(file_len, dtype=np.int64)]
         if any(len(a) != nt for a in host):
             raise SpkdError(SPKD_EINVAL, 'one entry per turn')
-        if not (params.rate >= 10.0 and params.winstep >= 1.0):
-            raise SpkdError(SPKD_EINVAL, 'unsupported growing-window parameters (frame rate >= 10 and '
-                                         'a window step of at least one frame needed)')
-        step = min(0.2 * params.rate, 0.5 * params.rate, params.winstep)
-        full = ((e - b).astype(np.float64) / step).astype(np.int64) + 8
-        if first_guess_scale != 1.0:
-            full = np.maximum((full * float(first_guess_scale)).astype(np.int64), 2)
-        grow = 1
         view = GwLinesView()
-        while True:
-            caps = (full // 4 + 8) if tight else full * grow
-            off = np.zeros(nt + 1, dtype=np.int64)
-            off[1:] = np.cumsum(caps)
+        for off in _gw_capacity_ladder(e - b, params, tight, first_guess_scale):
             nev = int(off[-1])
             d_seg = seg_stats(nev)
             st = self.lib.spkd_gw_batch(self.h, C.c_void_p(d_frames), n_frames, _ptr(b), _ptr(e), nt, C.byref(params),
                                         _ptr(off), *[_ptr(a) for a in host], C.c_void_p(d_seg),
                                         1 if want_index else 0, C.byref(view))
-            if st == SPKD_EOVERFLOW and tight:
-                tight = False
-                continue
-            if st == SPKD_EOVERFLOW and grow < 1024:
-                grow *= 2
-                continue
-            self.check(st, allow=(SPKD_ENONFINITE,))
-            break
+            if st != SPKD_EOVERFLOW:
+                break
+        self.check(st, allow=(SPKD_ENONFINITE,))
         n, nr = int(view.n_lines), int(view.n_redo)
         return dict(status=st, off=off, n_ev=nev, d_seg=d_seg, n_lines=n, n_win=_view(view.n_win, nt if n else 0, np.int32),
                     times=_view(view.times, 2 * n, np.float64).reshape(-1, 2), turn=_view(view.turn, n, np.int32),

@@ -43,6 +43,96 @@ class FusedStats(object):
         self.d_buf, self.n_buf, self.index, self.begin, self.end = d_buf, n_buf, index, begin, end
 
 
+def _turn_table(files, rate):
+    """Per VAD turn of the batch, in file order: owning file, that file's offset and length in
+    the resident array, start / end seconds (views), absolute frame range -- int() truncation
+    and the clamp of a slice (no lower clamp: spk-change-detection.py cuts feas[start:end]).
+    None when no file has a turn."""
+    nturn = [len(f.vad) for f in files]
+    if sum(nturn) == 0:
+        return None
+    vad = np.concatenate([f.vad_arr for f in files])
+    owner = np.repeat(np.arange(len(files)), nturn)
+    foff = np.array([f.frame_off for f in files], dtype=np.int64)[owner]
+    fn = np.array([f.n_frames for f in files], dtype=np.int64)[owner]
+    ls, le = vad[:, 0], vad[:, 1]
+    f0 = np.minimum((ls * rate).astype(np.int64), fn)
+    f1 = np.maximum(f0, np.minimum((le * rate).astype(np.int64), fn))
+    return owner, foff, fn, ls, le, foff + f0, foff + f1
+
+
+def _cd_params(cd, rate):
+    return hipabi.CdParams(hipabi.KINDS[cd['kind']], 0, cd['lambdac'], cd['threshold'],
+                           float(np.floor(cd['winsize_s'] * rate)), float(np.floor(cd['winstep_s'] * rate)),
+                           float(np.floor(rate * cd['deltaws_s'])), rate)
+
+
+def _ahc_params(cl):
+    return hipabi.AhcParams(cl['variant'], hipabi.KINDS[cl['kind']], cl['max_spk'], cl.get('path', 0),
+                            cl['lambdac'], cl['threshold'])
+
+
+def _detector_done(ctx, timings, tb, te, r):
+    """After a growing-window call (gw or gw_batch result r): its timings entries, and the
+    reference's error for frames that are not finite."""
+    if timings is not None:
+        timings.setdefault('gw', []).append(ctx.last_ms('gw'))
+        timings.setdefault('gw_stream_ms', []).append(ctx.last_ms('call'))     # uploads + kernel + result copies
+        timings['gw_frames'] = int((te - tb).sum())
+        timings['gw_windows'] = int(r['n_win'].sum())
+        timings['gw_dets'] = ctx.last_gw_items()
+    if r['status'] == hipabi.SPKD_ENONFINITE:
+        raise ValueError('array must not contain infs or NaNs')
+
+
+def _time_stats(ctx, timings, n, begin, end):
+    """The timings entries of the statistics kernels: n records, those of [begin, end) from the frames."""
+    if len(begin):
+        timings.setdefault('chunk_stats', []).append(ctx.last_ms('chunk_stats'))
+        timings.setdefault('reduce_sets', []).append(ctx.last_ms('reduce_sets'))
+    timings['stats_frames'] = int((end - begin).sum())
+    timings['stats_sets'] = n
+    timings['stats_recomputed'] = len(begin)
+
+
+def _clustering_done(ctx, timings, seg_off, r):
+    """After a clustering call (ahc or ahc_fused result r), as _detector_done."""
+    if timings is not None:
+        for k in ('cluster_prep', 'matrix', 'ahc'):
+            timings.setdefault(k, []).append(ctx.last_ms(k))
+    if r['status'] == hipabi.SPKD_ENONFINITE:
+        raise ValueError('array must not contain infs or NaNs')
+    if timings is not None:
+        npb = np.diff(seg_off)
+        nm = r['n_merges'].astype(np.int64)
+        timings['matrix_pairs'] = int((npb * (npb - 1) // 2).sum())
+        # merge m of a problem with N records recomputes N - 2 - m distances
+        timings['ahc_pairs'] = int((nm * (npb - 2) - nm * (nm - 1) // 2).sum())
+
+
+def _problems(cnt):
+    """A file without a line is not a clustering problem (spkd_ahc rejects empty ones): the
+    indices of the others and their seg_off; the lines of those stay in place."""
+    cnt = np.asarray(cnt, dtype=np.int64)
+    kept = np.nonzero(cnt)[0]
+    seg_off = np.zeros(len(kept) + 1, dtype=np.int64)
+    seg_off[1:] = np.cumsum(cnt[kept])
+    return kept, seg_off
+
+
+def _recipe_rows(times, line_file, labels, rate):
+    """Rows [start_s, end_s, speaker] in the recipe order of spk_cluster_hi's output: per file,
+    sorted by (start*rate, end*rate, line).  The change detector emits a file's lines in time
+    order, so the keys are almost always sorted already (a stable sort then changes nothing):
+    one O(n) look instead of the sort."""
+    k0, k1 = times[:, 0] * rate, times[:, 1] * rate
+    in_order = (line_file[1:] != line_file[:-1]) | (k0[1:] > k0[:-1]) | ((k0[1:] == k0[:-1]) & (k1[1:] >= k1[:-1]))
+    rows = np.column_stack([times, labels.astype(np.float64)])       # (a copy: the inputs may be views)
+    if not bool(in_order.all()):
+        rows = rows[np.lexsort((np.arange(len(rows)), k1, k0, line_file))]
+    return rows
+
+
 def change_detect_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, timings=None,
                         text_contract=True, fused=None):
     """Returns, per file, the list of (start_s, end_s) the change-detection recipe
@@ -56,20 +146,11 @@ def change_detect_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_
     cluster_batch does not read the frames a second time."""
     rate = float(rate)
     _t0 = time.perf_counter()
-    nturn = [len(f.vad) for f in files]
-    if sum(nturn) == 0:
+    table = _turn_table(files, rate)
+    if table is None:
         return [[] for _ in files]
-    vad = np.concatenate([f.vad_arr for f in files])
-    owner = np.repeat(np.arange(len(files)), nturn)
-    foff = np.array([f.frame_off for f in files], dtype=np.int64)[owner]
-    fn = np.array([f.n_frames for f in files], dtype=np.int64)[owner]
-    ls, le = vad[:, 0], vad[:, 1]
-    f0 = np.minimum((ls * rate).astype(np.int64), fn)            # int() truncation + slice clamp
-    f1 = np.maximum(f0, np.minimum((le * rate).astype(np.int64), fn))
-    tb, te = foff + f0, foff + f1
-    p = hipabi.CdParams(hipabi.KINDS[cd['kind']], 0, cd['lambdac'], cd['threshold'],
-                        float(np.floor(cd['winsize_s'] * rate)), float(np.floor(cd['winstep_s'] * rate)),
-                        float(np.floor(rate * cd['deltaws_s'])), rate)
+    owner, _, _, ls, le, tb, te = table
+    p = _cd_params(cd, rate)
     _t1 = time.perf_counter()
     seg_buf = {}
 
@@ -81,16 +162,8 @@ def change_detect_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_
     r = ctx.gw(d_frames, total_frames, tb, te, p, log_cap=4096, tight=True, reuse=True,
                seg_stats=seg_alloc if fused is not None else None)
     _t2 = time.perf_counter()
-    if timings is not None:
-        timings.setdefault('gw', []).append(ctx.last_ms('gw'))
-        timings.setdefault('gw_stream_ms', []).append(ctx.last_ms('call'))     # uploads + kernel + result copies
-        timings['gw_frames'] = int((te - tb).sum())
-        timings['gw_windows'] = int(r['n_win'].sum())
-        timings['gw_dets'] = ctx.last_gw_items()
-    if r['status'] == hipabi.SPKD_ENONFINITE:
-        raise ValueError('array must not contain infs or NaNs')
+    _detector_done(ctx, timings, tb, te, r)
     off = r['off']
-    nt = len(tb)
     # detections per turn = ones among the turn's n_win window flags (what lies behind them
     # in the reused buffers is not looked at)
     nd = hipabi.count_flags(r['win_det'], off[:-1], r['n_win'])
@@ -146,12 +219,7 @@ def segment_stats(ctx, d_frames, total_frames, files, segments, rate=125.0, timi
                           len(redo), d_tmp)
             ctx.gather_stats(d_tmp, len(redo), np.arange(len(redo)), d_stats, n, redo)
     if timings is not None:
-        if len(redo):
-            timings.setdefault('chunk_stats', []).append(ctx.last_ms('chunk_stats'))
-            timings.setdefault('reduce_sets', []).append(ctx.last_ms('reduce_sets'))
-        timings['stats_frames'] = int((e[redo] - b[redo]).sum())
-        timings['stats_sets'] = n
-        timings['stats_recomputed'] = int(len(redo))
+        _time_stats(ctx, timings, n, b[redo], e[redo])
     return d_stats, seg_off, n, _t1
 
 
@@ -165,34 +233,22 @@ def cluster_batch(ctx, d_frames, total_frames, files, segments, rate=125.0, cl=D
     the detector summed are gathered from its buffer; only the others -- a boundary the
     12-digit text round trip moved across a frame edge -- are computed from the frames."""
     rate = float(rate)
-    # files without any segment are not clustering problems (spkd_ahc rejects empty ones)
-    if fused is None and any(len(sg) == 0 for sg in segments):
-        keep = [i for i, sg in enumerate(segments) if len(sg) > 0]
+    cnt = [len(s) for s in segments]
+    keep = _problems(cnt)[0]
+    if len(keep) < len(files):               # (the lines of the others keep their order: fused stays valid)
         out = [(np.zeros(0, dtype=np.int32), [] if want_merges else None) for _ in files]
-        if keep:
+        if len(keep):
             sub = cluster_batch(ctx, d_frames, total_frames, [files[i] for i in keep],
-                                [segments[i] for i in keep], rate, cl, timings, want_merges)
+                                [segments[i] for i in keep], rate, cl, timings, want_merges, fused)
             for i, r in zip(keep, sub):
                 out[i] = r
         return out
     _t0 = time.perf_counter()
-    cnt = [len(s) for s in segments]
     d_stats, seg_off, n, _t1 = segment_stats(ctx, d_frames, total_frames, files, segments, rate, timings, fused)
     _t2 = time.perf_counter()
-    p = hipabi.AhcParams(cl['variant'], hipabi.KINDS[cl['kind']], cl['max_spk'], cl.get('path', 0),
-                         cl['lambdac'], cl['threshold'])
-    r = ctx.ahc(d_stats, seg_off, p)
+    r = ctx.ahc(d_stats, seg_off, _ahc_params(cl))
     _t3 = time.perf_counter()
-    if timings is not None:
-        for k in ('cluster_prep', 'matrix', 'ahc'):
-            timings.setdefault(k, []).append(ctx.last_ms(k))
-        npb = np.diff(seg_off)
-        nm = r['n_merges'].astype(np.int64)
-        timings['matrix_pairs'] = int((npb * (npb - 1) // 2).sum())
-        # merge m of a problem with N records recomputes N - 2 - m distances
-        timings['ahc_pairs'] = int((nm * (npb - 2) - nm * (nm - 1) // 2).sum())
-    if r['status'] == hipabi.SPKD_ENONFINITE:
-        raise ValueError('array must not contain infs or NaNs')
+    _clustering_done(ctx, timings, seg_off, r)
     all_labels = hipabi.labels_from_merges_batch(seg_off, r['n_merges'], r['a'], r['b'])
     out = []
     for fi in range(len(files)):
@@ -223,77 +279,35 @@ def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2
     log per file with segments ('merges', as cluster_batch's want_merges)."""
     rate = float(rate)
     _t0 = time.perf_counter()
-    nturn = [len(f.vad) for f in files]
-    if sum(nturn) == 0:
+    table = _turn_table(files, rate)
+    if table is None:
         return [np.zeros((0, 3)) for _ in files]
-    vad = np.concatenate([f.vad_arr for f in files])
-    owner = np.repeat(np.arange(len(files)), nturn)
-    foff = np.array([f.frame_off for f in files], dtype=np.int64)[owner]
-    fn = np.array([f.n_frames for f in files], dtype=np.int64)[owner]
-    ls, le = np.ascontiguousarray(vad[:, 0]), np.ascontiguousarray(vad[:, 1])
-    f0 = np.minimum((ls * rate).astype(np.int64), fn)
-    f1 = np.maximum(f0, np.minimum((le * rate).astype(np.int64), fn))
-    tb, te = foff + f0, foff + f1
-    p = hipabi.CdParams(hipabi.KINDS[cd['kind']], 0, cd['lambdac'], cd['threshold'],
-                        float(np.floor(cd['winsize_s'] * rate)), float(np.floor(cd['winstep_s'] * rate)),
-                        float(np.floor(rate * cd['deltaws_s'])), rate)
+    owner, foff, fn, ls, le, tb, te = table
+    ls, le = np.ascontiguousarray(ls), np.ascontiguousarray(le)
+    p = _cd_params(cd, rate)
     _t1 = time.perf_counter()
     r = ctx.gw_batch(d_frames, total_frames, tb, te, p, ls, le, foff, fn,
                      lambda n_rec: ctx.dev_scratch('fused_segment_stats', max(n_rec, 1) * hipabi.REC * 8),
                      tight=True, first_guess_scale=first_guess_scale, want_index=detail is not None)
     _t2 = time.perf_counter()
-    if timings is not None:
-        timings.setdefault('gw', []).append(ctx.last_ms('gw'))
-        timings.setdefault('gw_stream_ms', []).append(ctx.last_ms('call'))
-        timings['gw_frames'] = int((te - tb).sum())
-        timings['gw_windows'] = int(r['n_win'].sum())
-        timings['gw_dets'] = ctx.last_gw_items()
-    if r['status'] == hipabi.SPKD_ENONFINITE:
-        raise ValueError('array must not contain infs or NaNs')
-    rt = r['times']
-    n = r['n_lines']
+    _detector_done(ctx, timings, tb, te, r)
     line_file = owner[r['turn']]
     bounds = np.searchsorted(line_file, np.arange(len(files) + 1))
     _t3 = time.perf_counter()
-    # files without a line are not clustering problems; the lines of the others stay in place
-    cnt = np.diff(bounds)
-    kept = np.nonzero(cnt)[0]
-    seg_off = np.zeros(len(kept) + 1, dtype=np.int64)
-    seg_off[1:] = np.cumsum(cnt[kept])
-    ap = hipabi.AhcParams(cl['variant'], hipabi.KINDS[cl['kind']], cl['max_spk'], cl.get('path', 0),
-                          cl['lambdac'], cl['threshold'])
-    n_redo = len(r['redo_line'])
+    seg_off = _problems(np.diff(bounds))[1]
+    ap = _ahc_params(cl)
     _t4 = time.perf_counter()
     a = ctx.ahc_fused(d_frames, total_frames, r['d_seg'], r['n_ev'], r['d_index'], seg_off, r['redo_line'],
                       r['redo_begin'], r['redo_end'], ap)
     _t5 = time.perf_counter()
     if timings is not None:
-        if n_redo:
-            timings.setdefault('chunk_stats', []).append(ctx.last_ms('chunk_stats'))
-            timings.setdefault('reduce_sets', []).append(ctx.last_ms('reduce_sets'))
-        timings['stats_frames'] = int((r['redo_end'] - r['redo_begin']).sum())
-        timings['stats_sets'] = n
-        timings['stats_recomputed'] = n_redo
-        for k in ('cluster_prep', 'matrix', 'ahc'):
-            timings.setdefault(k, []).append(ctx.last_ms(k))
-    if a['status'] == hipabi.SPKD_ENONFINITE:
-        raise ValueError('array must not contain infs or NaNs')
-    if timings is not None:
-        npb = np.diff(seg_off)
-        nm = a['n_merges'].astype(np.int64)
-        timings['matrix_pairs'] = int((npb * (npb - 1) // 2).sum())
-        timings['ahc_pairs'] = int((nm * (npb - 2) - nm * (nm - 1) // 2).sum())
+        _time_stats(ctx, timings, r['n_lines'], r['redo_begin'], r['redo_end'])
+    _clustering_done(ctx, timings, seg_off, a)
     if detail is not None:
         detail['lines'] = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}
         detail['merges'] = [list(zip(a['a'][o:o + m].tolist(), a['b'][o:o + m].tolist(), a['d'][o:o + m].tolist()))
                             for o, m in zip(seg_off[:-1].tolist(), a['n_merges'].tolist())]
-    # recipe order of spk_cluster_hi's output: per file, sorted by (start*rate, end*rate, line);
-    # the detector emits a file's lines in time order, so one O(n) look almost always settles it
-    k0, k1 = rt[:, 0] * rate, rt[:, 1] * rate
-    in_order = (line_file[1:] != line_file[:-1]) | (k0[1:] > k0[:-1]) | ((k0[1:] == k0[:-1]) & (k1[1:] >= k1[:-1]))
-    rows = np.column_stack([rt, a['labels'].astype(np.float64)])       # (a copy: rt and the labels are views)
-    if not bool(in_order.all()):
-        rows = rows[np.lexsort((np.arange(n), k1, k0, line_file))]
+    rows = _recipe_rows(r['times'], line_file, a['labels'], rate)
     out = [rows[bounds[i]:bounds[i + 1]] for i in range(len(files))]
     if timings is not None:
         _t6 = time.perf_counter()
@@ -331,38 +345,17 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     fs = box[0] if box else None
     if fused and fs is None:                 # no turn at all in the batch
         return [np.zeros((0, 3)) for _ in files]
-    if fused and any(len(sg) == 0 for sg in segs):
-        # files without segments are not clustering problems: drop them, keep the line order
-        keep = [i for i, sg in enumerate(segs) if len(sg) > 0]
-        out = [np.zeros((0, 3)) for _ in files]
-        if keep:
-            sub = _cluster_and_order(ctx, d_frames, total_frames, [files[i] for i in keep],
-                                     [segs[i] for i in keep], rate, cl, timings, fs)
-            for i, rws in zip(keep, sub):
-                out[i] = rws
-        return out
     return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs)
 
 
 def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs):
     res = cluster_batch(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fused=fs)
-    # recipe order of spk_cluster_hi's output: per file, sorted by (start*rate, end*rate, line)
     cnt = [len(s) for s in segs]
-    n = sum(cnt)
-    if n == 0:
+    if sum(cnt) == 0:
         return [np.zeros((0, 3)) for _ in segs]
     allseg = np.concatenate([np.asarray(s, dtype=np.float64).reshape(-1, 2) for s in segs])
-    labels = np.concatenate([lab for (lab, _) in res]).astype(np.float64)
-    owner = np.repeat(np.arange(len(segs)), cnt)
-    k0, k1 = allseg[:, 0] * rate, allseg[:, 1] * rate
-    # the change detector emits a file's lines in time order, so the keys are almost always
-    # sorted already (a stable sort then changes nothing): one O(n) look instead of the sort
-    in_order = (owner[1:] != owner[:-1]) | (k0[1:] > k0[:-1]) | ((k0[1:] == k0[:-1]) & (k1[1:] >= k1[:-1]))
-    if bool(in_order.all()):
-        rows = np.column_stack([allseg, labels])
-    else:
-        order = np.lexsort((np.arange(n), k1, k0, owner))
-        rows = np.column_stack([allseg[order], labels[order]])
+    labels = np.concatenate([lab for (lab, _) in res])
+    rows = _recipe_rows(allseg, np.repeat(np.arange(len(segs)), cnt), labels, rate)
     bounds = np.zeros(len(segs) + 1, dtype=np.int64)
     bounds[1:] = np.cumsum(cnt)
     out = [rows[bounds[i]:bounds[i + 1]] for i in range(len(segs))]

@@ -250,6 +250,39 @@ def test_gw_lines_helper_matches_the_vectorised_restatement():
         assert got['index'].tolist() == ix
 
 
+@pytest.mark.parametrize('scale', [1.0, 1.0 / 64])
+def test_capacity_ladder_offers_tight_full_then_doubled(scale):
+    """The capacities gw() and gw_batch() retry with (Context.gw's docstring): a first guess of
+    turn_len / step + 8 events per turn, step = min(0.2 rate, 0.5 rate, winstep), scaled by
+    first_guess_scale (at least 2); tight starts from a quarter of it (+ 8), an overflow then
+    takes the full guess, every further one doubles it, 1024 times at the most.  The stub try
+    reports overflow k times and sees these totals, in this order."""
+    hipabi = pkg('hipabi')
+    p = hipabi.CdParams(0, 0, 1.0, 0.0, 125.0, 375.0, 12.0, 125.0)
+    lens = [0, 187, 1000, 7777, 450000]
+    guess = [int(n / 25.0) + 8 for n in lens]                       # step = 0.2 * 125
+    if scale != 1.0:
+        guess = [max(int(g * scale), 2) for g in guess]
+    want = [sum(g // 4 + 8 for g in guess)] + [sum(g << k for g in guess) for k in range(11)]
+    for tight in (True, False):
+        expect = want if tight else want[1:]
+        for k in (0, 1, 2, 5, len(expect) - 1, len(expect) + 3):
+            seen, overflows = [], [k]
+
+            def one_try(off):
+                assert off[0] == 0 and len(off) == len(lens) + 1
+                seen.append(int(off[-1]))
+                overflows[0] -= 1
+                return overflows[0] >= 0                           # "SPKD_EOVERFLOW"
+
+            for off in hipabi._gw_capacity_ladder(np.array(lens, dtype=np.int64), p, tight, scale):
+                if not one_try(off):
+                    break
+            assert seen == expect[:k + 1], (tight, k)
+    with pytest.raises(hipabi.SpkdError):
+        next(hipabi._gw_capacity_ladder(np.array(lens), hipabi.CdParams(0, 0, 1.0, 0.0, 125.0, 0.5, 12.0, 125.0), True, 1.0))
+
+
 def test_in_flight_keeps_order_and_surfaces_errors():
     """pipeline.in_flight: one job per context at a time, results in job order, a job's
     exception re-raised to the consumer (contexts faked: no GPU involved)."""
