@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -129,6 +130,48 @@ spkd_status upload(spkd_ctx* c, int slot, const T* h, size_t n, T** d) {
     return SPKD_OK;
 }
 
+// A buffer that holds several arrays.  Its parts are listed once, in a function that chains a
+// part() for each in order and returns bytes(); that function runs twice: on a Layout without
+// a base to measure, on one with the base to place the pointers.  Every part starts at a
+// multiple of its type's alignment.  With a staging area, part() also copies its source there:
+// the host image of a table that goes up in one copy.
+struct Layout {
+    char* const base;
+    char* const stage;
+    size_t at = 0;
+    explicit Layout(void* b = nullptr, void* s = nullptr) : base((char*)b), stage((char*)s) {}
+    template <class T>
+    Layout& part(T*& p, size_t count, const T* src = nullptr) {
+        at = (at + alignof(T) - 1) / alignof(T) * alignof(T);
+        p = base ? (T*)(base + at) : nullptr;
+        if (stage && src) std::memcpy(stage + at, src, count * sizeof(T));
+        at += count * sizeof(T);
+        return *this;
+    }
+    size_t bytes() const { return at; }
+};
+
+// such a buffer from scratch() or pinned(): the size is what the walk over its parts measured
+template <class Parts>
+spkd_status carve(spkd_ctx* c, spkd_status (*alloc)(spkd_ctx*, int, size_t, void**), int slot, Parts parts) {
+    void* p = nullptr;
+    TRY(alloc(c, slot, parts(Layout()), &p));
+    parts(Layout(p));
+    return SPKD_OK;
+}
+
+// a table upload: the sources of the parts staged in `image` (declared before the Call), sent in
+// one copy, the parts placed on the device
+template <class Parts>
+spkd_status upload_parts(spkd_ctx* c, int slot, std::vector<char>& image, Parts parts) {
+    image.resize(parts(Layout()));
+    parts(Layout(nullptr, image.data()));
+    char* d = nullptr;
+    TRY(upload(c, slot, image.data(), image.size(), &d));
+    parts(Layout(d));
+    return SPKD_OK;
+}
+
 // The bracket of an entry point that enqueues device work, opened after its argument checks:
 // whatever its status, the call returns with that work finished (include/spkd.h).  finish()
 // waits for the stream, the destructor whenever finish() did not get through.  Host memory that
@@ -185,6 +228,17 @@ spkd_status use_kind(spkd_ctx* c, int kind, int* base) {
     return SPKD_OK;
 }
 
+bool bad_kind(int kind) { return kind < 0 || kind > 3; }
+
+// the caller's parameters with the kind as the kernels take it: Pk is the copy, P points to it
+template <class Params>
+spkd_status kernel_params(spkd_ctx* c, const Params*& P, Params& Pk) {
+    Pk = *P;
+    TRY(use_kind(c, P->kind, &Pk.kind));
+    P = &Pk;
+    return SPKD_OK;
+}
+
 // times the work its scope enqueues as kernel timer idx (spkd_last_kernel_ms); closes before finish()
 struct Timer {
     spkd_ctx* const c;
@@ -195,7 +249,7 @@ struct Timer {
 
 enum {
     S_CHUNKS = 0, S_SETOFF, S_PARTIAL, S_IDXA, S_IDXB, S_TERMS, S_TURNS, S_SNAP, S_CAND,
-    S_EV_I32A, S_EV_I32B, S_EV_D0, S_EV_D1, S_EV_D2, S_EV_D3, S_EV_D4, S_LOG,
+    S_GW_N_WIN, S_GW_WIN_DET, S_GW_WIN_MAXD, S_GW_DET_START, S_GW_DET_MAXI, S_GW_DET_D, S_GW_FINAL_START, S_LOG,
     S_AHC_STATS, S_AHC_LD, S_AHC_AUX, S_AHC_MAT, S_AHC_MISC, S_AHC_OUT, S_AHC_OFF, S_AHC_PROB, S_AHC_PACKED, S_MFCC_TAB, S_MFCC_STATIC,
     S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX,
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_COUNT
@@ -426,7 +480,9 @@ spkd_status spkd_pair_terms(spkd_ctx* c, const double* d_stats, const int32_t* h
 
 // ------------------------------------------------------------------ clustering internals
 namespace {
-struct AhcBuffers {
+// What ahc_prepare leaves: the device buffers of the problems, and the host images of its two
+// uploads -- declared by the caller before its Call, since copies of the call read them.
+struct AhcPrep {
     double* ex;
     double* pk;          // packed working copies (the pair passes load these)
     double* ld;
@@ -436,6 +492,10 @@ struct AhcBuffers {
     int64_t* mat_off;
     unsigned long long* smax;
     unsigned long long* smin;
+    int64_t n_total = 0;
+    int64_t grid_rows = 0;           // k_matrix's grid
+    std::vector<char> offs;          // seg_off | mat_off
+    std::vector<char> prob_of;       // record -> its problem | k_matrix's launch order
 };
 
 unsigned long long host_dkey(double v) {                      // dkey() of spkd_cluster.hpp, on the host
@@ -461,32 +521,43 @@ struct MatrixPlan {
     int64_t n_redo = 0;
 };
 
+// the records in the quad layout the clustering kernels load from
+void to_quadrec(spkd_ctx* c, const double* d_stats, int64_t n, double* ex) {
+    hipLaunchKernelGGL(k_to_quadrec, dim3((unsigned)n), dim3(256), 0, c->stream, d_stats, n, ex);
+}
+
+// log dets / KL2 vectors of n records.  KL2: one wave per record; BIC / GLR: four records per wave
+void cluster_prep(spkd_ctx* c, const double* ex, int64_t n, int kind, double* ld, double* aux) {
+    const int64_t per_block = kind == SPKD_KL2 ? PT_WAVES : 4 * PT_WAVES;
+    const unsigned blocks = (unsigned)((n + per_block - 1) / per_block);
+    hipLaunchKernelGGL(k_cluster_prep, dim3(blocks), dim3(PT_WAVES * WAVE), 0, c->stream, ex, n, kind, ld, aux, c->d_err,
+                       c->pinv_cur);
+}
+
 spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_off, int64_t n_prob,
-                        int variant, int kind, double lambdac, AhcBuffers& B, int64_t& n_total,
-                        std::vector<int64_t>& offs, std::vector<int32_t>& prob_of,
-                        const MatrixPlan& plan = MatrixPlan()) {
-    n_total = h_seg_off[n_prob];
-    offs.clear();                                    // seg_off | mat_off
-    offs.insert(offs.end(), h_seg_off, h_seg_off + n_prob + 1);
+                        int variant, int kind, double lambdac, AhcPrep& B, const MatrixPlan& plan = MatrixPlan()) {
+    const int64_t n_total = B.n_total = h_seg_off[n_prob];
+    const size_t np = (size_t)n_prob;
+    std::vector<int64_t> mat_off(np + 1);
     int64_t cells = 0;
     for (int64_t p = 0; p < n_prob; ++p) {
         const int64_t n = h_seg_off[p + 1] - h_seg_off[p];
         if (n < 0) return fail(c, SPKD_EINVAL, "seg_off must be non-decreasing");
-        offs.push_back(cells);
+        mat_off[(size_t)p] = cells;
         cells += n * n;
     }
-    offs.push_back(cells);
-    prob_of.assign((size_t)n_total, 0);              // record -> its problem
+    mat_off[np] = cells;
+    std::vector<int32_t> prob((size_t)n_total, 0);   // record -> its problem
     for (int64_t p = 0; p < n_prob; ++p)
-        for (int64_t r = h_seg_off[p]; r < h_seg_off[p + 1]; ++r) prob_of[(size_t)r] = (int32_t)p;
-    // k_matrix's launch order, appended to the same upload: block b computes the matrix row
+        for (int64_t r = h_seg_off[p]; r < h_seg_off[p + 1]; ++r) prob[(size_t)r] = (int32_t)p;
+    // k_matrix's launch order, in the same upload: block b computes the matrix row
     // of record sched[b] (-1: nothing).  Workgroups go to the eight XCDs round-robin by block
     // index and every XCD has an L2 of its own, so the rows of one problem -- they all read
     // that problem's records as partners -- are given to ONE XCD: its working set is then a
     // problem or two (2.5 MB each at N = 390) instead of a slice of all of them.  Whole
     // problems are dealt to the least-loaded XCD, largest first; with fewer problems than
     // XCDs the rows are dealt round-robin instead.
-    int64_t grid_rows = 0;
+    int32_t *d_prob = nullptr, *d_sched = nullptr;
     {
         const int X = 8;
         std::vector<std::vector<int32_t>> lists(X);
@@ -512,27 +583,22 @@ spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg
         }
         size_t longest = 0;
         for (auto& l : lists) longest = std::max(longest, l.size());
-        grid_rows = (int64_t)longest * X;
-        prob_of.resize((size_t)(n_total + grid_rows), -1);
+        B.grid_rows = (int64_t)longest * X;
+        std::vector<int32_t> sched((size_t)B.grid_rows, -1);
         for (int x = 0; x < X; ++x)
-            for (size_t i = 0; i < lists[x].size(); ++i) prob_of[(size_t)n_total + i * X + x] = lists[x][i];
+            for (size_t i = 0; i < lists[x].size(); ++i) sched[i * X + x] = lists[x][i];
+        TRY(upload_parts(c, S_AHC_OFF, B.offs, [&](Layout L) {
+            return L.part(B.seg_off, np + 1, h_seg_off).part(B.mat_off, np + 1, mat_off.data()).bytes();
+        }));
+        TRY(upload_parts(c, S_AHC_PROB, B.prob_of, [&](Layout L) {
+            return L.part(d_prob, prob.size(), prob.data()).part(d_sched, sched.size(), sched.data()).bytes();
+        }));
     }
-    int64_t* d_offs = nullptr;
-    int32_t* d_prob = nullptr;
-    TRY(upload(c, S_AHC_OFF, offs.data(), offs.size(), &d_offs));
-    TRY(upload(c, S_AHC_PROB, prob_of.data(), prob_of.size(), &d_prob));
-    B.seg_off = d_offs;
-    B.mat_off = d_offs + n_prob + 1;
-    void* p = nullptr;
-    TRY(scratch(c, S_AHC_LD, (size_t)n_total * sizeof(double), &p));
-    B.ld = (double*)p;
-    TRY(scratch(c, S_AHC_AUX, (size_t)n_total * AUX * sizeof(double), &p));
-    B.aux = (double*)p;
-    TRY(scratch(c, S_AHC_MAT, (size_t)cells * sizeof(double), &p));
-    B.mat = (double*)p;
-    TRY(scratch(c, S_AHC_MISC, (size_t)n_prob * 2 * sizeof(unsigned long long), &p));
-    B.smax = (unsigned long long*)p;
-    B.smin = B.smax + n_prob;
+    const size_t nt = (size_t)n_total;
+    TRY(carve(c, scratch, S_AHC_LD, [&](Layout L) { return L.part(B.ld, nt).bytes(); }));
+    TRY(carve(c, scratch, S_AHC_AUX, [&](Layout L) { return L.part(B.aux, nt * AUX).bytes(); }));
+    TRY(carve(c, scratch, S_AHC_MAT, [&](Layout L) { return L.part(B.mat, (size_t)cells).bytes(); }));
+    TRY(carve(c, scratch, S_AHC_MISC, [&](Layout L) { return L.part(B.smax, np).part(B.smin, np).bytes(); }));
     HIPCHK(c, hipMemsetAsync(B.smax, 0x00, (size_t)n_prob * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(B.smin, 0xff, (size_t)n_prob * sizeof(unsigned long long), c->stream));
     if (plan.d_init && n_prob == 1) {
@@ -544,10 +610,8 @@ spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg
     }
     // a private working copy of the records (clusters are merged in place), expanded to the
     // quad layout the clustering kernels load from
-    TRY(scratch(c, S_AHC_STATS, (size_t)n_total * QREC * sizeof(double), &p));
-    B.ex = (double*)p;
-    TRY(scratch(c, S_AHC_PACKED, (size_t)n_total * REC * sizeof(double), &p));
-    B.pk = (double*)p;
+    TRY(carve(c, scratch, S_AHC_STATS, [&](Layout L) { return L.part(B.ex, nt * QREC).bytes(); }));
+    TRY(carve(c, scratch, S_AHC_PACKED, [&](Layout L) { return L.part(B.pk, nt * REC).bytes(); }));
     if (n_total > 0) {
         if (plan.d_map) {
             void* d_redo = nullptr;
@@ -565,25 +629,21 @@ spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg
             hipLaunchKernelGGL(k_records_from_map, dim3((unsigned)n_total), dim3(256), 0, c->stream, d_stats, plan.n_src,
                                (const int64_t*)plan.d_map, (const double*)d_redo, plan.n_redo, n_total, B.ex, B.pk, c->d_err);
         } else {
-            hipLaunchKernelGGL(k_to_quadrec, dim3((unsigned)n_total), dim3(256), 0, c->stream, d_stats, n_total, B.ex);
+            to_quadrec(c, d_stats, n_total, B.ex);
             HIPCHK(c, hipMemcpyAsync(B.pk, d_stats, (size_t)n_total * REC * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         }
-        // KL2: one wave per record; BIC / GLR: four records per wave
-        const int64_t per_block = kind == SPKD_KL2 ? PT_WAVES : 4 * PT_WAVES;
-        const unsigned blocks = (unsigned)((n_total + per_block - 1) / per_block);
         {
             Timer t(c, SPKD_T_CLUSTER_PREP);
-            hipLaunchKernelGGL(k_cluster_prep, dim3(blocks), dim3(PT_WAVES * WAVE), 0, c->stream,
-                               (const double*)B.ex, n_total, kind, B.ld, B.aux, c->d_err, c->pinv_cur);
+            cluster_prep(c, B.ex, n_total, kind, B.ld, B.aux);
         }
         auto kmat = kind == SPKD_GLR ? k_matrix<true> : k_matrix<false>;   // GLR has a second rank-one term
         if (plan.d_init) {
             HIPCHK(c, hipMemcpyAsync(B.mat, plan.d_init, (size_t)cells * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        } else if (grid_rows > 0) {
+        } else if (B.grid_rows > 0) {
             Timer t(c, SPKD_T_MATRIX);
-            hipLaunchKernelGGL(kmat, dim3((unsigned)grid_rows), dim3(MX_WAVES * WAVE), 0, c->stream,
+            hipLaunchKernelGGL(kmat, dim3((unsigned)B.grid_rows), dim3(MX_WAVES * WAVE), 0, c->stream,
                                (const double*)B.ex, (const double*)B.pk, (const int64_t*)B.seg_off, (const int32_t*)d_prob,
-                               (const int32_t*)d_prob + n_total, variant, kind, lambdac,
+                               (const int32_t*)d_sched, variant, kind, lambdac,
                                (const double*)B.ld, (const double*)B.aux, B.mat, (const int64_t*)B.mat_off,
                                B.smax, B.smin, c->d_err);
         }
@@ -603,18 +663,15 @@ double key_to_double(unsigned long long k, bool is_max) {
 
 spkd_status spkd_distance_matrix(spkd_ctx* c, int kind, double lambdac, const double* d_stats,
                                  int64_t n, double* d_matrix) {
-    if (!c || n < 0 || kind < 0 || kind > 3) return SPKD_EINVAL;
+    if (!c || n < 0 || bad_kind(kind)) return SPKD_EINVAL;
     if (n == 0) return SPKD_OK;
     if (!d_stats || !d_matrix) return fail(c, SPKD_EINVAL, "null argument");
     const int64_t seg_off[2] = {0, n};
-    AhcBuffers B;
-    int64_t n_total = 0;
-    std::vector<int64_t> offs;
-    std::vector<int32_t> prob_of;
+    AhcPrep B;
     Call call(c);
     TRY(call.opened);
     TRY(use_kind(c, kind, &kind));
-    TRY(ahc_prepare(c, d_stats, seg_off, 1, 1, kind, lambdac, B, n_total, offs, prob_of));
+    TRY(ahc_prepare(c, d_stats, seg_off, 1, 1, kind, lambdac, B));
     HIPCHK(c, hipMemcpyAsync(d_matrix, B.mat, (size_t)n * n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return call.finish();
 }
@@ -622,7 +679,7 @@ spkd_status spkd_distance_matrix(spkd_ctx* c, int kind, double lambdac, const do
 spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int kind, double lambdac, double threshold,
                             int32_t* h_label, double* h_dist, int64_t dist_cap, int64_t* h_dist_off,
                             int64_t* h_n_done, int64_t* h_n_clusters) {
-    if (!c || n < 0 || dist_cap < 0 || kind < 0 || kind > 3) return SPKD_EINVAL;
+    if (!c || n < 0 || dist_cap < 0 || bad_kind(kind)) return SPKD_EINVAL;
     if (h_n_done) *h_n_done = 0;
     if (h_n_clusters) *h_n_clusters = 0;
     if (n == 0) return SPKD_OK;
@@ -632,44 +689,34 @@ spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int k
     Call call(c);
     TRY(call.opened);
     TRY(use_kind(c, kind, &kind));
-    void *p_ex = nullptr, *p_ld = nullptr, *p_aux = nullptr, *p_cex = nullptr, *p_cpk = nullptr, *p_misc = nullptr, *p_dist = nullptr;
+    void *p_ex = nullptr, *p_ld = nullptr, *p_aux = nullptr, *p_cex = nullptr, *p_cpk = nullptr, *p_dist = nullptr;
     const size_t nn = (size_t)n;
     TRY(scratch(c, S_AHC_STATS, nn * QREC * sizeof(double), &p_ex));
     TRY(scratch(c, S_AHC_LD, nn * sizeof(double), &p_ld));
     TRY(scratch(c, S_AHC_AUX, nn * AUX * sizeof(double), &p_aux));
     TRY(scratch(c, S_STEP_EXM, nn * QREC * sizeof(double), &p_cex));
     TRY(scratch(c, S_STEP_PKM, nn * REC * sizeof(double), &p_cpk));
-    // misc: cluster log dets | determinants of a step | cluster KL2 vectors | dist_off | done | labels
-    const size_t misc_bytes = (2 + AUX) * nn * sizeof(double) + (nn + 1 + 2) * sizeof(long long) + nn * sizeof(int32_t) + 64;
-    TRY(scratch(c, S_STEP_MISC, misc_bytes, &p_misc));
+    double *clu_ld, *tmp, *clu_aux;
+    long long *d_off, *d_done;
+    int32_t* d_label;
+    // cluster log dets | determinants of a step | cluster KL2 vectors | dist_off | done | labels
+    TRY(carve(c, scratch, S_STEP_MISC, [&](Layout L) {
+        return L.part(clu_ld, nn).part(tmp, nn).part(clu_aux, nn * AUX).part(d_off, nn + 1).part(d_done, 2)
+            .part(d_label, nn).bytes();
+    }));
     TRY(scratch(c, S_AHC_MAT, (size_t)std::max<int64_t>(dist_cap, 1) * sizeof(double), &p_dist));
-    double* clu_ld = (double*)p_misc;
-    double* tmp = clu_ld + nn;
-    double* clu_aux = tmp + nn;
-    long long* d_off = (long long*)(clu_aux + nn * AUX);
-    long long* d_done = d_off + nn + 1;
-    int32_t* d_label = (int32_t*)(d_done + 2);
     HIPCHK(c, hipMemsetAsync(d_done, 0, 2 * sizeof(long long), c->stream));
-    // the records in the quad layout, their own log dets (four records per wave)
-    hipLaunchKernelGGL(k_to_quadrec, dim3((unsigned)n), dim3(256), 0, c->stream, d_stats, n, (double*)p_ex);
+    to_quadrec(c, d_stats, n, (double*)p_ex);
+    // the records' own log dets (also for KL2: they are what flags a covariance with infs or NaNs,
+    // which the reference's pinv refuses like its det)
     {
-        const int64_t per_block = 4 * PT_WAVES;
-        const unsigned blocks = (unsigned)((n + per_block - 1) / per_block);
-        // (the log dets also for KL2: they are what flags a covariance with infs or NaNs, which the
-        // reference's pinv refuses like its det)
-        {
-            Timer t(c, SPKD_T_CLUSTER_PREP);
-            hipLaunchKernelGGL(k_cluster_prep, dim3(blocks), dim3(PT_WAVES * WAVE), 0, c->stream,
-                               (const double*)p_ex, n, kind == SPKD_KL2 ? (int)SPKD_BIC : kind, (double*)p_ld, (double*)p_aux, c->d_err,
-                               c->pinv_cur);
-        }
-        if (kind == SPKD_KL2) {
-            void* p_ld2 = nullptr;                       // (the KL2 pass of the same kernel rewrites ld with zeros)
-            TRY(scratch(c, S_AHC_OUT, nn * sizeof(double), &p_ld2));
-            const unsigned blocks1 = (unsigned)((n + PT_WAVES - 1) / PT_WAVES);
-            hipLaunchKernelGGL(k_cluster_prep, dim3(blocks1), dim3(PT_WAVES * WAVE), 0, c->stream,
-                               (const double*)p_ex, n, (int)SPKD_KL2, (double*)p_ld2, (double*)p_aux, c->d_err, c->pinv_cur);
-        }
+        Timer t(c, SPKD_T_CLUSTER_PREP);
+        cluster_prep(c, (const double*)p_ex, n, kind == SPKD_KL2 ? (int)SPKD_BIC : kind, (double*)p_ld, (double*)p_aux);
+    }
+    if (kind == SPKD_KL2) {
+        void* p_ld2 = nullptr;                           // (the KL2 pass of the same kernel rewrites ld with zeros)
+        TRY(scratch(c, S_AHC_OUT, nn * sizeof(double), &p_ld2));
+        cluster_prep(c, (const double*)p_ex, n, SPKD_KL2, (double*)p_ld2, (double*)p_aux);
     }
     auto kin = kind == SPKD_GLR ? k_cluster_in<true> : k_cluster_in<false>;
     {
@@ -694,17 +741,14 @@ spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int k
 spkd_status spkd_distance_rows(spkd_ctx* c, int variant, int kind, double lambdac, const double* d_stats,
                                int64_t n, int64_t row_begin, int64_t row_end, double* d_rows,
                                double* h_stat_max, double* h_stat_min) {
-    if (!c || n < 0 || kind < 0 || kind > 3 || (variant != 1 && variant != 2)) return SPKD_EINVAL;
+    if (!c || n < 0 || bad_kind(kind) || (variant != 1 && variant != 2)) return SPKD_EINVAL;
     if (row_begin < 0 || row_end < row_begin || row_end > n) return fail(c, SPKD_EINVAL, "distance_rows: bad row block");
     if (h_stat_max) *h_stat_max = std::nan("");
     if (h_stat_min) *h_stat_min = std::nan("");
     if (n == 0 || row_end == row_begin) return SPKD_OK;
     if (!d_stats || !d_rows) return fail(c, SPKD_EINVAL, "null argument");
     const int64_t seg_off[2] = {0, n};
-    AhcBuffers B;
-    int64_t n_total = 0;
-    std::vector<int64_t> offs;
-    std::vector<int32_t> prob_of;
+    AhcPrep B;
     MatrixPlan plan;
     plan.row_begin = row_begin;
     plan.row_end = row_end;
@@ -712,7 +756,7 @@ spkd_status spkd_distance_rows(spkd_ctx* c, int variant, int kind, double lambda
     Call call(c);
     TRY(call.opened);
     TRY(use_kind(c, kind, &kind));
-    TRY(ahc_prepare(c, d_stats, seg_off, 1, variant, kind, lambdac, B, n_total, offs, prob_of, plan));
+    TRY(ahc_prepare(c, d_stats, seg_off, 1, variant, kind, lambdac, B, plan));
     HIPCHK(c, hipMemcpyAsync(d_rows, B.mat + row_begin * n, (size_t)(row_end - row_begin) * n * sizeof(double),
                              hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(&keys[0], B.smax, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -733,7 +777,7 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
     if (!d_stats || !h_seg_off || !h_n_merges || !h_merge_a || !h_merge_b || !h_merge_d ||
         !h_stat_max || !h_stat_min)
         return fail(c, SPKD_EINVAL, "null argument");
-    if ((P->variant != 1 && P->variant != 2) || P->kind < 0 || P->kind > 3)
+    if ((P->variant != 1 && P->variant != 2) || bad_kind(P->kind))
         return fail(c, SPKD_EINVAL, "bad variant / kind");
     for (int64_t p = 0; p < n_prob; ++p)
         if (h_seg_off[p + 1] - h_seg_off[p] < 1) return fail(c, SPKD_EINVAL, "empty clustering problem");
@@ -749,34 +793,24 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
     // (checked before the n x n matrix is built)
     if (path == SPKD_AHC_WIDE && n_max > STEP_MAX_N)
         return fail(c, SPKD_EINVAL, "clustering problem larger than 16384 records (wide merge loop)");
-    AhcBuffers B;
-    int64_t n_total = 0;
-    std::vector<int64_t> offs;
-    std::vector<int32_t> prob_of;
+    AhcPrep B;
     std::vector<unsigned long long> kmax((size_t)n_prob), kmin((size_t)n_prob);
     std::vector<double> fmax((size_t)n_prob), fmin((size_t)n_prob);
     Call call(c);
     TRY(call.opened);
-    spkd_ahc_params Pk = *P;                         // (kind as the kernels take it)
-    TRY(use_kind(c, P->kind, &Pk.kind));
-    P = &Pk;
+    spkd_ahc_params Pk;
+    TRY(kernel_params(c, P, Pk));
     // ahc_prepare expands the records into a private working copy (merged in place)
-    TRY(ahc_prepare(c, d_stats, h_seg_off, n_prob, P->variant, P->kind, P->lambdac, B, n_total, offs, prob_of, plan));
+    TRY(ahc_prepare(c, d_stats, h_seg_off, n_prob, P->variant, P->kind, P->lambdac, B, plan));
+    const int64_t n_total = B.n_total;
+    const size_t nt = (size_t)n_total, np = (size_t)n_prob;
     // outputs + per-slot scratch
-    void* op = nullptr;
-    const size_t out_bytes = (size_t)n_total * (6 * sizeof(int32_t) + 3 * sizeof(double)) +
-                             (size_t)n_prob * (sizeof(int32_t) + 2 * sizeof(double)) + 64;
-    TRY(scratch(c, S_AHC_OUT, out_bytes, &op));
-    double* d_merge_d = (double*)op;
-    double* d_tmp = d_merge_d + n_total;
-    double* d_rmin = d_tmp + n_total;
-    double* d_fmax = d_rmin + n_total;
-    double* d_fmin = d_fmax + n_prob;
-    int32_t* d_a = (int32_t*)(d_fmin + n_prob);
-    int32_t* d_b = d_a + n_total;
-    int32_t* d_alive = d_b + n_total;
-    int32_t* d_rcache = d_alive + n_total;           // 3 ints per record: arg col, NaN col, dirty
-    int32_t* d_n = d_rcache + 3 * n_total;
+    double *d_merge_d, *d_tmp, *d_rmin, *d_fmax, *d_fmin;
+    int32_t *d_a, *d_b, *d_alive, *d_rcache, *d_n;
+    TRY(carve(c, scratch, S_AHC_OUT, [&](Layout L) {            // (rcache: arg col, NaN col, dirty of every record)
+        return L.part(d_merge_d, nt).part(d_tmp, nt).part(d_rmin, nt).part(d_fmax, np).part(d_fmin, np)
+            .part(d_a, nt).part(d_b, nt).part(d_alive, nt).part(d_rcache, 3 * nt).part(d_n, np).bytes();
+    }));
     if (path == SPKD_AHC_MONO) {
         auto kahc = P->kind == SPKD_GLR ? k_ahc<true> : k_ahc<false>;
         if (lds > 48 * 1024)
@@ -790,19 +824,13 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
     } else {
         // the step chain: one launch per merge, every workgroup selects for itself (spkd_cluster.hpp)
         StepArrays Q;
-        void *pm = nullptr, *pe = nullptr, *pp = nullptr;
-        const size_t nt = (size_t)n_total;
-        const size_t misc_bytes = nt * 2 * sizeof(StepSel) + nt * sizeof(double) + nt * sizeof(unsigned long long) +
-                                  (size_t)2 * n_prob * sizeof(StepState) + nt * sizeof(int32_t) + 64;
-        TRY(scratch(c, S_STEP_MISC, misc_bytes, &pm));
+        void *pe = nullptr, *pp = nullptr;
+        TRY(carve(c, scratch, S_STEP_MISC, [&](Layout L) {
+            return L.part(Q.sel2, 2 * nt).part(Q.cnt, nt).part(Q.sw, nt).part(Q.state2, 2 * np).part(Q.death, nt).bytes();
+        }));
         TRY(scratch(c, S_STEP_EXM, nt * QREC * sizeof(double), &pe));
         TRY(scratch(c, S_STEP_PKM, nt * REC * sizeof(double), &pp));
         Q.ex = B.ex; Q.pk = B.pk; Q.exm = (double*)pe; Q.pkm = (double*)pp;
-        Q.sel2 = (StepSel*)pm;
-        Q.cnt = (double*)(Q.sel2 + 2 * nt);
-        Q.sw = (unsigned long long*)(Q.cnt + nt);
-        Q.state2 = (StepState*)(Q.sw + nt);
-        Q.death = (int32_t*)(Q.state2 + 2 * n_prob);
         Q.n_total = n_total;
         Q.n_prob = (int32_t)n_prob;
         // eight waves per workgroup once a thread of four would meet more than ~4 clusters in the
@@ -974,28 +1002,36 @@ struct GwBatch {
 // before k_gw is enqueued: the turn times go up while nothing waits for them
 spkd_status gw_batch_upload(spkd_ctx* c, GwBatch& G, int64_t n_turns) {
     const size_t nt = (size_t)n_turns;
-    void *p = nullptr, *h = nullptr;
-    TRY(scratch(c, S_CP_TURNS, nt * (2 * sizeof(double) + 2 * sizeof(int32_t)) + (nt + 1) * sizeof(int64_t), &p));
-    G.d_ls = (double*)p;
-    G.d_le = G.d_ls + nt;
-    G.d_line_off = (int64_t*)(G.d_le + nt);
-    G.d_n_det = (int32_t*)(G.d_line_off + nt + 1);
-    G.d_pos = G.d_n_det + nt;
+    TRY(carve(c, scratch, S_CP_TURNS, [&](Layout L) {
+        return L.part(G.d_ls, nt).part(G.d_le, nt).part(G.d_line_off, nt + 1).part(G.d_n_det, nt).part(G.d_pos, nt).bytes();
+    }));
     HIPCHK(c, hipMemcpyAsync(G.d_ls, G.turn_start_s, nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(G.d_le, G.turn_end_s, nt * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    TRY(pinned(c, PIN_GW_TURNS, 2 * sizeof(int64_t) + nt * sizeof(int32_t), &h));
-    G.h_head = (int64_t*)h;
-    G.h_n_win = (int32_t*)(G.h_head + 2);
-    return SPKD_OK;
+    return carve(c, pinned, PIN_GW_TURNS, [&](Layout L) { return L.part(G.h_head, 2).part(G.h_n_win, nt).bytes(); });
 }
 
+// the event arrays of a growing-window call on the device, by the names k_gw gives them
+struct GwEvents {
+    int32_t* n_win = nullptr;
+    double* win_maxd = nullptr;
+    int32_t* win_det = nullptr;
+    double *det_start = nullptr, *det_maxi = nullptr, *det_d = nullptr, *final_start = nullptr;
+};
+
+// the lines of a batch, on the device and in pinned host memory alike
+struct LineArrays {
+    int64_t* frame;                                  // frame_b | frame_e
+    int64_t* index;
+    int32_t* turn;
+    Layout& parts(Layout& L, size_t n) { return L.part(frame, 2 * n).part(index, n).part(turn, n); }
+};
+
 // behind k_gw, inside its call bracket: count, scan, learn the number of lines, write and fetch them
-spkd_status gw_batch_compact(spkd_ctx* c, GwBatch& G, const TurnDesc* d_turns, int64_t n_turns,
-                             const int32_t* d_n_win, const int32_t* d_win_det, const double* d_det_start,
-                             const double* d_det_maxi, const double* d_final_start, double rate) {
+spkd_status gw_batch_compact(spkd_ctx* c, GwBatch& G, const TurnDesc* d_turns, int64_t n_turns, const GwEvents& ev,
+                             double rate) {
     const unsigned blocks = (unsigned)((n_turns + CP_TPB - 1) / CP_TPB);
-    hipLaunchKernelGGL(k_cp_count, dim3(blocks), dim3(CP_TPB), 0, c->stream, d_turns, n_turns, d_n_win, d_win_det,
-                       (const int*)c->d_err, G.d_n_det, G.d_pos);
+    hipLaunchKernelGGL(k_cp_count, dim3(blocks), dim3(CP_TPB), 0, c->stream, d_turns, n_turns, (const int32_t*)ev.n_win,
+                       (const int32_t*)ev.win_det, (const int*)c->d_err, G.d_n_det, G.d_pos);
     hipLaunchKernelGGL(k_cp_scan, dim3(1), dim3(CP_SCAN_TPB), 0, c->stream, (const int32_t*)G.d_n_det, n_turns,
                        (const int*)c->d_err, G.d_line_off);
     HIPCHK(c, hipGetLastError());
@@ -1003,42 +1039,38 @@ spkd_status gw_batch_compact(spkd_ctx* c, GwBatch& G, const TurnDesc* d_turns, i
     G.h_head[1] = 0;
     HIPCHK(c, hipMemcpyAsync(&G.h_head[0], G.d_line_off + n_turns, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(&G.h_head[1], c->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(G.h_n_win, d_n_win, (size_t)n_turns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(G.h_n_win, ev.n_win, (size_t)n_turns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (G.h_head[1] != 0) return SPKD_OK;            // (the call's finish() turns the word into its status)
     const int64_t n = G.h_head[0];
     if (n < n_turns) return fail(c, SPKD_EHIP, "internal error: fewer lines than turns");
     const size_t nn = (size_t)n;
-    void *d_t = nullptr, *d_l = nullptr, *h = nullptr;
+    void* d_t = nullptr;
+    LineArrays D, H;
+    double* h_times;
     TRY(scratch(c, S_CP_TIMES, nn * 2 * sizeof(double), &d_t));
-    TRY(scratch(c, S_CP_LINES, nn * (3 * sizeof(int64_t) + sizeof(int32_t)), &d_l));
-    TRY(pinned(c, PIN_GW_LINES, nn * (2 * sizeof(double) + 3 * sizeof(int64_t) + sizeof(int32_t)), &h));
-    int64_t* d_fb = (int64_t*)d_l;                   // frame_b | frame_e | index | turn
-    int64_t* d_ix = d_fb + 2 * nn;
-    int32_t* d_tn = (int32_t*)(d_ix + nn);
+    TRY(carve(c, scratch, S_CP_LINES, [&](Layout L) { return D.parts(L, nn).bytes(); }));
+    TRY(carve(c, pinned, PIN_GW_LINES, [&](Layout L) { return H.parts(L.part(h_times, 2 * nn), nn).bytes(); }));
     hipLaunchKernelGGL(k_cp_lines, dim3(blocks), dim3(CP_TPB), 0, c->stream, d_turns, n_turns,
-                       (const int32_t*)G.d_n_det, (const int32_t*)G.d_pos, (const int64_t*)G.d_line_off, n, d_det_start,
-                       d_det_maxi, d_final_start, (const double*)G.d_ls, (const double*)G.d_le, rate,
-                       (const int*)c->d_err, (double*)d_t, d_fb, d_fb + nn, d_ix, d_tn);
+                       (const int32_t*)G.d_n_det, (const int32_t*)G.d_pos, (const int64_t*)G.d_line_off, n,
+                       (const double*)ev.det_start, (const double*)ev.det_maxi, (const double*)ev.final_start,
+                       (const double*)G.d_ls, (const double*)G.d_le, rate,
+                       (const int*)c->d_err, (double*)d_t, D.frame, D.frame + nn, D.index, D.turn);
     HIPCHK(c, hipGetLastError());
-    double* h_times = (double*)h;
-    int64_t* h_fb = (int64_t*)(h_times + 2 * nn);
-    int64_t* h_ix = h_fb + 2 * nn;
-    int32_t* h_tn = (int32_t*)(h_ix + nn);
     HIPCHK(c, hipMemcpyAsync(h_times, d_t, nn * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_fb, d_fb, nn * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_tn, d_tn, nn * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(H.frame, D.frame, nn * 2 * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(H.turn, D.turn, nn * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (G.want_index)
-        HIPCHK(c, hipMemcpyAsync(h_ix, d_ix, nn * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(H.index, D.index, nn * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
     spkd_gw_lines_view& V = *G.view;
     V.n_lines = n;
     V.n_win = G.h_n_win;
     V.times = h_times;
-    V.turn = h_tn;
-    V.frame_b = h_fb;
-    V.frame_e = h_fb + nn;
-    V.index = G.want_index ? h_ix : nullptr;
-    V.d_index = d_ix;
+    V.turn = H.turn;
+    V.frame_b = H.frame;
+    V.frame_e = H.frame + nn;
+    V.index = G.want_index ? H.index : nullptr;
+    V.d_index = D.index;
     G.n_lines = n;
     G.have_lines = true;
     return SPKD_OK;
@@ -1096,6 +1128,25 @@ struct GwOut {
     int64_t* h_log_count = nullptr;
 };
 
+// Every event array once, in the order k_gw takes them and the results are copied: its scratch
+// slot, its element size, whether it holds a value per turn or per event slot, and where its
+// pointer is in GwEvents and in GwOut.
+struct GwEventArray { int slot; size_t elem; bool per_turn; size_t dev, host; };
+#define SPKD_EV(SLOT, T, per_turn, name) {SLOT, sizeof(T), per_turn, offsetof(GwEvents, name), offsetof(GwOut, h_##name)}
+const GwEventArray GW_EVENT_ARRAYS[] = {
+    SPKD_EV(S_GW_N_WIN, int32_t, true, n_win),
+    SPKD_EV(S_GW_WIN_MAXD, double, false, win_maxd),
+    SPKD_EV(S_GW_WIN_DET, int32_t, false, win_det),
+    SPKD_EV(S_GW_DET_START, double, false, det_start),
+    SPKD_EV(S_GW_DET_MAXI, double, false, det_maxi),
+    SPKD_EV(S_GW_DET_D, double, false, det_d),
+    SPKD_EV(S_GW_FINAL_START, double, true, final_start),
+};
+#undef SPKD_EV
+// (the pointer members have different types: read and written as bytes)
+void* get_pointer(const void* s, size_t off) { void* p; std::memcpy(&p, (const char*)s + off, sizeof p); return p; }
+void set_pointer(void* s, size_t off, void* p) { std::memcpy((char*)s + off, &p, sizeof p); }
+
 // from this many turns on, a wave per turn (2 048 wave slots on the chip at two waves per SIMD)
 constexpr int64_t GW_WAVE_PER_TURN_FROM = 4096;
 constexpr int64_t GW_EIGHT_WAVES_UP_TO = 256;           // a workgroup per CU: eight waves per turn
@@ -1106,10 +1157,9 @@ spkd_status gw_impl(spkd_ctx* c, const GwIn& in, const GwOut& out, GwBatch* batc
     if (out.h_log_count) *out.h_log_count = 0;
     if (n_turns == 0) return SPKD_OK;
     if (!in.d_frames || !in.hb || !in.he || !in.h_ev_off) return fail(c, SPKD_EINVAL, "null argument");
-    if (!batch && (!out.h_n_win || !out.h_win_maxd || !out.h_win_det || !out.h_det_start || !out.h_det_maxi ||
-                   !out.h_det_d || !out.h_final_start))
-        return fail(c, SPKD_EINVAL, "null argument");
-    if (P->kind < 0 || P->kind > 3) return fail(c, SPKD_EINVAL, "gw: bad kind");
+    for (const GwEventArray& a : GW_EVENT_ARRAYS)
+        if (!batch && !get_pointer(&out, a.host)) return fail(c, SPKD_EINVAL, "null argument");
+    if (bad_kind(P->kind)) return fail(c, SPKD_EINVAL, "gw: bad kind");
     if (!(P->rate >= 10.0) || !(P->winsize >= 1.0) || !(P->winstep >= 1.0))
         return fail(c, SPKD_EINVAL, "gw: rate >= 10, winsize >= 1 frame and winstep >= 1 frame required");
     if (log_cap < 0 || (log_cap > 0 && !out.h_log)) return fail(c, SPKD_EINVAL, "gw: log capacity without a log buffer");
@@ -1123,28 +1173,27 @@ spkd_status gw_impl(spkd_ctx* c, const GwIn& in, const GwOut& out, GwBatch* batc
     unsigned long long cnt2[2] = {0ull, 0ull};
     Call call(c);
     TRY(call.opened);
-    spkd_cd_params Pk = *P;                          // (kind as the kernel takes it)
-    TRY(use_kind(c, P->kind, &Pk.kind));
-    P = &Pk;
+    spkd_cd_params Pk;
+    TRY(kernel_params(c, P, Pk));
     const int64_t n_ev = in.h_ev_off[n_turns];
     TurnDesc* d_turns = nullptr;
-    void *d_snap = nullptr, *d_cand = nullptr, *d_i32a = nullptr, *d_i32b = nullptr, *d_d0 = nullptr, *d_d1 = nullptr,
-         *d_d2 = nullptr, *d_d3 = nullptr, *d_d4 = nullptr, *d_log = nullptr;
+    void *d_snap = nullptr, *d_cand = nullptr, *d_log = nullptr;
+    GwEvents ev;
     TRY(upload(c, S_TURNS, turns.data(), turns.size(), &d_turns));
     // one packed record (running moment sums at the split point) per candidate slot
     TRY(scratch(c, S_SNAP, (size_t)n_cand * REC * sizeof(double), &d_snap));
     TRY(scratch(c, S_CAND, (size_t)n_cand * 4 * sizeof(double), &d_cand));
-    TRY(scratch(c, S_EV_I32A, (size_t)n_turns * sizeof(int32_t), &d_i32a));
-    TRY(scratch(c, S_EV_I32B, (size_t)n_ev * sizeof(int32_t), &d_i32b));
-    TRY(scratch(c, S_EV_D0, (size_t)n_ev * sizeof(double), &d_d0));
-    TRY(scratch(c, S_EV_D1, (size_t)n_ev * sizeof(double), &d_d1));
-    TRY(scratch(c, S_EV_D2, (size_t)n_ev * sizeof(double), &d_d2));
-    TRY(scratch(c, S_EV_D3, (size_t)n_ev * sizeof(double), &d_d3));
-    TRY(scratch(c, S_EV_D4, (size_t)n_turns * sizeof(double), &d_d4));
-    TRY(scratch(c, S_LOG, (size_t)std::max<int64_t>(log_cap, 1) * sizeof(spkd_cand_log), &d_log));
+    auto ev_bytes = [&](const GwEventArray& a) { return (size_t)(a.per_turn ? n_turns : n_ev) * a.elem; };
     // every pointer the kernel dereferences (a null one would be a GPU memory fault, not a status)
-    if (!d_turns || !d_snap || !d_cand || !d_i32a || !d_i32b || !d_d0 || !d_d1 || !d_d2 || !d_d3 || !d_d4 ||
-        !d_log || !c->d_counter || !c->d_err)
+    bool missing = false;
+    for (const GwEventArray& a : GW_EVENT_ARRAYS) {
+        void* p = nullptr;
+        TRY(scratch(c, a.slot, ev_bytes(a), &p));
+        set_pointer(&ev, a.dev, p);
+        missing = missing || !p;
+    }
+    TRY(scratch(c, S_LOG, (size_t)std::max<int64_t>(log_cap, 1) * sizeof(spkd_cand_log), &d_log));
+    if (missing || !d_turns || !d_snap || !d_cand || !d_log || !c->d_counter || !c->d_err)
         return fail(c, SPKD_EHIP, "gw: a device scratch buffer is missing");
     HIPCHK(c, hipMemsetAsync(c->d_counter, 0, 2 * sizeof(unsigned long long), c->stream));   // [0] log entries, [1] determinants
     if (batch) TRY(gw_batch_upload(c, *batch, n_turns));
@@ -1159,9 +1208,9 @@ spkd_status gw_impl(spkd_ctx* c, const GwIn& in, const GwOut& out, GwBatch* batc
 #define SPKD_GW_LAUNCH(NW_)                                                                                     \
     hipLaunchKernelGGL(k_gw<NW_>, dim3((unsigned)n_turns), dim3(Gw<NW_>::TPB), Gw<NW_>::LDS_BYTES, c->stream, \
                        in.d_frames, (const TurnDesc*)d_turns, *P, (double*)d_snap, (double*)d_cand,            \
-                       (int32_t*)d_i32a, (double*)d_d0, (int32_t*)d_i32b, (double*)d_d1, (double*)d_d2,        \
-                       (double*)d_d3, (double*)d_d4, in.d_seg_stats, (spkd_cand_log*)d_log, (long long)log_cap,   \
-                       c->d_counter, c->d_err, c->pinv_cur)
+                       ev.n_win, ev.win_maxd, ev.win_det, ev.det_start, ev.det_maxi, ev.det_d, ev.final_start,  \
+                       in.d_seg_stats, (spkd_cand_log*)d_log, (long long)log_cap, c->d_counter, c->d_err,      \
+                       c->pinv_cur)
     {
         Timer t(c, SPKD_T_GW);
         if (nw == 1) SPKD_GW_LAUNCH(1); else if (nw == 2) SPKD_GW_LAUNCH(2);
@@ -1171,8 +1220,7 @@ spkd_status gw_impl(spkd_ctx* c, const GwIn& in, const GwOut& out, GwBatch* batc
     HIPCHK(c, hipGetLastError());
     unsigned long long& cnt = cnt2[0];
     if (batch) {
-        TRY(gw_batch_compact(c, *batch, d_turns, n_turns, (const int32_t*)d_i32a, (const int32_t*)d_i32b,
-                             (const double*)d_d1, (const double*)d_d2, (const double*)d_d4, P->rate));
+        TRY(gw_batch_compact(c, *batch, d_turns, n_turns, ev, P->rate));
         HIPCHK(c, hipMemcpyAsync(cnt2, c->d_counter, sizeof cnt2, hipMemcpyDeviceToHost, c->stream));
         const spkd_status st = call.finish();
         c->last_gw_items = (int64_t)cnt2[1];
@@ -1180,13 +1228,9 @@ spkd_status gw_impl(spkd_ctx* c, const GwIn& in, const GwOut& out, GwBatch* batc
         if (!batch->have_lines) return fail(c, SPKD_EHIP, "internal error: no lines from a clean call");
         return gw_batch_finish(c, *batch, n_turns, P->rate);
     }
-    HIPCHK(c, hipMemcpyAsync(out.h_n_win, d_i32a, (size_t)n_turns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out.h_win_maxd, d_d0, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out.h_win_det, d_i32b, (size_t)n_ev * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out.h_det_start, d_d1, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out.h_det_maxi, d_d2, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out.h_det_d, d_d3, (size_t)n_ev * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out.h_final_start, d_d4, (size_t)n_turns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    for (const GwEventArray& a : GW_EVENT_ARRAYS)
+        HIPCHK(c, hipMemcpyAsync(get_pointer(&out, a.host), get_pointer(&ev, a.dev), ev_bytes(a), hipMemcpyDeviceToHost,
+                                 c->stream));
     HIPCHK(c, hipMemcpyAsync(cnt2, c->d_counter, sizeof cnt2, hipMemcpyDeviceToHost, c->stream));
     const spkd_status st = call.finish();
     c->last_gw_items = (int64_t)cnt2[1];
@@ -1199,44 +1243,14 @@ spkd_status gw_impl(spkd_ctx* c, const GwIn& in, const GwOut& out, GwBatch* batc
         return fail(c, SPKD_EOVERFLOW, "candidate log too small");
     return st;
 }
-}  // namespace
 
-spkd_status spkd_gw(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
-                    const int64_t* he, int64_t n_turns, const spkd_cd_params* P, const int64_t* h_ev_off,
-                    int32_t* h_n_win, double* h_win_maxd, int32_t* h_win_det, double* h_det_start,
-                    double* h_det_maxi, double* h_det_d, double* h_final_start, spkd_cand_log* h_log,
-                    int64_t log_cap, int64_t* h_log_count) {
-    GwIn in;
-    in.d_frames = d_frames; in.n_frames = n_frames; in.hb = hb; in.he = he; in.n_turns = n_turns;
-    in.P = P; in.h_ev_off = h_ev_off; in.check_capacity = 1;
-    GwOut out;
-    out.h_n_win = h_n_win; out.h_win_maxd = h_win_maxd; out.h_win_det = h_win_det; out.h_det_start = h_det_start;
-    out.h_det_maxi = h_det_maxi; out.h_det_d = h_det_d; out.h_final_start = h_final_start;
-    out.h_log = h_log; out.log_cap = log_cap; out.h_log_count = h_log_count;
-    return gw_impl(c, in, out);
-}
-
-spkd_status spkd_gw_ex(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
+// the growing-window call of the three entry points that copy the event arrays to the host
+// (d_seg_stats: nullptr unless fused)
+spkd_status gw_to_host(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
                        const int64_t* he, int64_t n_turns, const spkd_cd_params* P, const int64_t* h_ev_off,
                        int check_capacity, int32_t* h_n_win, double* h_win_maxd, int32_t* h_win_det,
                        double* h_det_start, double* h_det_maxi, double* h_det_d, double* h_final_start,
-                       spkd_cand_log* h_log, int64_t log_cap, int64_t* h_log_count) {
-    GwIn in;
-    in.d_frames = d_frames; in.n_frames = n_frames; in.hb = hb; in.he = he; in.n_turns = n_turns;
-    in.P = P; in.h_ev_off = h_ev_off; in.check_capacity = check_capacity;
-    GwOut out;
-    out.h_n_win = h_n_win; out.h_win_maxd = h_win_maxd; out.h_win_det = h_win_det; out.h_det_start = h_det_start;
-    out.h_det_maxi = h_det_maxi; out.h_det_d = h_det_d; out.h_final_start = h_final_start;
-    out.h_log = h_log; out.log_cap = log_cap; out.h_log_count = h_log_count;
-    return gw_impl(c, in, out);
-}
-
-spkd_status spkd_gw_fused(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
-                          const int64_t* he, int64_t n_turns, const spkd_cd_params* P, const int64_t* h_ev_off,
-                          int check_capacity, int32_t* h_n_win, double* h_win_maxd, int32_t* h_win_det,
-                          double* h_det_start, double* h_det_maxi, double* h_det_d, double* h_final_start,
-                          double* d_seg_stats, spkd_cand_log* h_log, int64_t log_cap, int64_t* h_log_count) {
-    if (c && !d_seg_stats) return fail(c, SPKD_EINVAL, "gw_fused: null statistics buffer");
+                       double* d_seg_stats, spkd_cand_log* h_log, int64_t log_cap, int64_t* h_log_count) {
     GwIn in;
     in.d_frames = d_frames; in.n_frames = n_frames; in.hb = hb; in.he = he; in.n_turns = n_turns;
     in.P = P; in.h_ev_off = h_ev_off; in.check_capacity = check_capacity; in.d_seg_stats = d_seg_stats;
@@ -1245,6 +1259,36 @@ spkd_status spkd_gw_fused(spkd_ctx* c, const float* d_frames, int64_t n_frames, 
     out.h_det_maxi = h_det_maxi; out.h_det_d = h_det_d; out.h_final_start = h_final_start;
     out.h_log = h_log; out.log_cap = log_cap; out.h_log_count = h_log_count;
     return gw_impl(c, in, out);
+}
+}  // namespace
+
+spkd_status spkd_gw(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
+                    const int64_t* he, int64_t n_turns, const spkd_cd_params* P, const int64_t* h_ev_off,
+                    int32_t* h_n_win, double* h_win_maxd, int32_t* h_win_det, double* h_det_start,
+                    double* h_det_maxi, double* h_det_d, double* h_final_start, spkd_cand_log* h_log,
+                    int64_t log_cap, int64_t* h_log_count) {
+    return gw_to_host(c, d_frames, n_frames, hb, he, n_turns, P, h_ev_off, 1, h_n_win, h_win_maxd, h_win_det,
+                      h_det_start, h_det_maxi, h_det_d, h_final_start, nullptr, h_log, log_cap, h_log_count);
+}
+
+spkd_status spkd_gw_ex(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
+                       const int64_t* he, int64_t n_turns, const spkd_cd_params* P, const int64_t* h_ev_off,
+                       int check_capacity, int32_t* h_n_win, double* h_win_maxd, int32_t* h_win_det,
+                       double* h_det_start, double* h_det_maxi, double* h_det_d, double* h_final_start,
+                       spkd_cand_log* h_log, int64_t log_cap, int64_t* h_log_count) {
+    return gw_to_host(c, d_frames, n_frames, hb, he, n_turns, P, h_ev_off, check_capacity, h_n_win, h_win_maxd,
+                      h_win_det, h_det_start, h_det_maxi, h_det_d, h_final_start, nullptr, h_log, log_cap, h_log_count);
+}
+
+spkd_status spkd_gw_fused(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
+                          const int64_t* he, int64_t n_turns, const spkd_cd_params* P, const int64_t* h_ev_off,
+                          int check_capacity, int32_t* h_n_win, double* h_win_maxd, int32_t* h_win_det,
+                          double* h_det_start, double* h_det_maxi, double* h_det_d, double* h_final_start,
+                          double* d_seg_stats, spkd_cand_log* h_log, int64_t log_cap, int64_t* h_log_count) {
+    if (c && !d_seg_stats) return fail(c, SPKD_EINVAL, "gw_fused: null statistics buffer");
+    return gw_to_host(c, d_frames, n_frames, hb, he, n_turns, P, h_ev_off, check_capacity, h_n_win, h_win_maxd,
+                      h_win_det, h_det_start, h_det_maxi, h_det_d, h_final_start, d_seg_stats, h_log, log_cap,
+                      h_log_count);
 }
 
 spkd_status spkd_gw_batch(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
@@ -1294,17 +1338,13 @@ spkd_status spkd_ahc_fused(spkd_ctx* c, const float* d_frames, int64_t n_frames,
     for (int64_t k = 0; k < n_redo; ++k)
         if (h_redo_line[k] < 0 || h_redo_line[k] >= n_total || (k > 0 && h_redo_line[k] <= h_redo_line[k - 1]))
             return fail(c, SPKD_EINVAL, "ahc_fused: redo lines must be ascending line indices");
-    // doubles first: merge_d | stat_max | stat_min, then merge_a | merge_b | labels | n_merges
     const size_t nt = (size_t)n_total, np = (size_t)n_prob;
-    void* h = nullptr;
-    TRY(pinned(c, PIN_AHC_OUT, (nt + 2 * np) * sizeof(double) + (3 * nt + np) * sizeof(int32_t), &h));
-    double* md = (double*)h;
-    double* smax = md + nt;
-    double* smin = smax + np;
-    int32_t* ma = (int32_t*)(smin + np);
-    int32_t* mb = ma + nt;
-    int32_t* lab = mb + nt;
-    int32_t* nm = lab + nt;
+    double *md, *smax, *smin;
+    int32_t *ma, *mb, *lab, *nm;
+    // merge_d | stat_max | stat_min | merge_a | merge_b | labels | n_merges
+    TRY(carve(c, pinned, PIN_AHC_OUT, [&](Layout L) {
+        return L.part(md, nt).part(smax, np).part(smin, np).part(ma, nt).part(mb, nt).part(lab, nt).part(nm, np).bytes();
+    }));
     MatrixPlan plan;
     plan.d_map = d_line_index;
     plan.n_src = n_records;
@@ -1361,7 +1401,7 @@ spkd_status spkd_sw(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
     if (!c || !P || n_turns < 0) return SPKD_EINVAL;
     if (n_turns == 0) return SPKD_OK;
     if (!d_frames || !hb || !he || !h_d_off || !h_d) return fail(c, SPKD_EINVAL, "null argument");
-    if (P->kind < 0 || P->kind > 3) return fail(c, SPKD_EINVAL, "bad kind");
+    if (bad_kind(P->kind)) return fail(c, SPKD_EINVAL, "bad kind");
     if (!(P->winsize >= 1.0) || !(P->winstep >= 1.0)) return fail(c, SPKD_EINVAL, "sw: window and step must be >= 1 frame");
     const int64_t n_d = h_d_off[n_turns];
     std::vector<int64_t> rb, re;
@@ -1383,25 +1423,23 @@ spkd_status spkd_sw(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
     if (n_d == 0) return SPKD_OK;
     if (2 * n_d > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "sw: too many windows in one call");
     std::vector<Chunk> chunks;
-    std::vector<int64_t> set_off, offs;
-    std::vector<int32_t> prob_of;
+    std::vector<int64_t> set_off;
+    AhcPrep B;
     Call call(c);
     TRY(call.opened);
-    spkd_cd_params Pk = *P;                          // (kind as the kernels take it)
-    TRY(use_kind(c, P->kind, &Pk.kind));
-    P = &Pk;
+    spkd_cd_params Pk;
+    TRY(kernel_params(c, P, Pk));
     void *d_rec = nullptr, *d_out = nullptr;
+    // (borrowed from the growing-window call: the two never share a call)
     TRY(scratch(c, S_SNAP, (size_t)(2 * n_d) * REC * sizeof(double), &d_rec));
-    TRY(scratch(c, S_EV_D0, (size_t)n_d * sizeof(double), &d_out));
+    TRY(scratch(c, S_GW_WIN_MAXD, (size_t)n_d * sizeof(double), &d_out));
     {
         Timer t(c, SPKD_T_SW);
         TRY(set_stats_launch(c, d_frames, n_frames, rb.data(), re.data(), rs.data(), 2 * n_d, 2 * n_d, (double*)d_rec,
                              chunks, set_off));
         std::vector<int64_t> seg_off((size_t)n_d + 1);
         for (int64_t w = 0; w <= n_d; ++w) seg_off[(size_t)w] = 2 * w;
-        AhcBuffers B;
-        int64_t n_total = 0;
-        TRY(ahc_prepare(c, (const double*)d_rec, seg_off.data(), n_d, 1, P->kind, P->lambdac, B, n_total, offs, prob_of));
+        TRY(ahc_prepare(c, (const double*)d_rec, seg_off.data(), n_d, 1, P->kind, P->lambdac, B));
         hipLaunchKernelGGL(k_take_pair_distance, dim3((unsigned)((n_d + 255) / 256)), dim3(256), 0, c->stream,
                            (const double*)B.mat, n_d, (double*)d_out);
     }
@@ -1436,24 +1474,16 @@ spkd_status spkd_mfcc(spkd_ctx* c, const int16_t* d_pcm, int64_t n_samples, cons
     *h_n_frames = T;
     if (T == 0) return SPKD_OK;
     if (!d_pcm || !d_features) return fail(c, SPKD_EINVAL, "mfcc: null device buffer");
-    // tables: mel filterbank | dct | mean | scale | transform
-    std::vector<float> tab;
-    tab.insert(tab.end(), h_melfb, h_melfb + MF_MEL * MF_BINS);
-    tab.insert(tab.end(), h_dct, h_dct + MF_CEP * MF_MEL);
-    tab.insert(tab.end(), h_mean, h_mean + MF_DIM);
-    tab.insert(tab.end(), h_scale, h_scale + MF_DIM);
-    tab.insert(tab.end(), h_transform, h_transform + MF_DIM * MF_DIM);
+    float *d_fb, *d_dct, *d_mean, *d_scale, *d_tr;
+    std::vector<char> tab;
     Call call(c);
     TRY(call.opened);
-    float* d_tab = nullptr;
     void* d_static = nullptr;
-    TRY(upload(c, S_MFCC_TAB, tab.data(), tab.size(), &d_tab));
+    TRY(upload_parts(c, S_MFCC_TAB, tab, [&](Layout L) {
+        return L.part(d_fb, MF_MEL * MF_BINS, h_melfb).part(d_dct, MF_CEP * MF_MEL, h_dct).part(d_mean, MF_DIM, h_mean)
+            .part(d_scale, MF_DIM, h_scale).part(d_tr, MF_DIM * MF_DIM, h_transform).bytes();
+    }));
     TRY(scratch(c, S_MFCC_STATIC, (size_t)T * MF_STATIC * sizeof(float), &d_static));
-    const float* d_fb = d_tab;
-    const float* d_dct = d_fb + MF_MEL * MF_BINS;
-    const float* d_mean = d_dct + MF_CEP * MF_MEL;
-    const float* d_scale = d_mean + MF_DIM;
-    const float* d_tr = d_scale + MF_DIM;
     if (P->window_width == MF_WIN)
         hipLaunchKernelGGL(k_mfcc_static<MF_WIN>, dim3((unsigned)((T + MF_FR - 1) / MF_FR)), dim3(MF_TPB), 0, c->stream,
                            d_pcm, (long long)n_samples, (long long)T, hop, P->pre_emph, d_fb, d_dct, (float*)d_static);
@@ -1496,26 +1526,20 @@ spkd_status spkd_gmm_loglik(spkd_ctx* c, const float* d_features, int64_t n_fram
     if (!d_features || !d_scores) return fail(c, SPKD_EINVAL, "gmm_loglik: null device buffer");
     const int64_t n_blocks = (n_frames + GM_TPB - 1) / GM_TPB;
     if (n_blocks > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "gmm_loglik: too many frames in one call");
-    // tables: mean | inverse variance | normalising constant | log weight;  state_off | kernel
-    std::vector<float> tab;
-    tab.insert(tab.end(), P->mean, P->mean + (size_t)K * GM_DIM);
-    tab.insert(tab.end(), P->inv_var, P->inv_var + (size_t)K * GM_DIM);
-    tab.insert(tab.end(), P->log_norm, P->log_norm + K);
-    tab.insert(tab.end(), P->log_weight, P->log_weight + nnz);
-    std::vector<int32_t> idx(P->state_off, P->state_off + S + 1);
-    idx.insert(idx.end(), P->kernel, P->kernel + nnz);
+    float *d_mean, *d_iv, *d_c, *d_lw;
+    int32_t *d_state_off, *d_kernel;
+    std::vector<char> tab, idx;
     Call call(c);
     TRY(call.opened);
-    float* d_tab = nullptr;
-    int32_t* d_idx = nullptr;
-    TRY(upload(c, S_GMM_TAB, tab.data(), tab.size(), &d_tab));
-    TRY(upload(c, S_GMM_IDX, idx.data(), idx.size(), &d_idx));
-    const float* d_mean = d_tab;
-    const float* d_iv = d_mean + (size_t)K * GM_DIM;
-    const float* d_c = d_iv + (size_t)K * GM_DIM;
-    const float* d_lw = d_c + K;
+    TRY(upload_parts(c, S_GMM_TAB, tab, [&](Layout L) {
+        return L.part(d_mean, (size_t)K * GM_DIM, P->mean).part(d_iv, (size_t)K * GM_DIM, P->inv_var)
+            .part(d_c, (size_t)K, P->log_norm).part(d_lw, (size_t)nnz, P->log_weight).bytes();
+    }));
+    TRY(upload_parts(c, S_GMM_IDX, idx, [&](Layout L) {
+        return L.part(d_state_off, (size_t)S + 1, P->state_off).part(d_kernel, (size_t)nnz, P->kernel).bytes();
+    }));
     hipLaunchKernelGGL(k_gmm_loglik, dim3((unsigned)n_blocks), dim3(GM_TPB), 0, c->stream, d_features,
-                       (long long)n_frames, d_mean, d_iv, d_c, (const int*)d_idx, (const int*)(d_idx + S + 1), d_lw,
+                       (long long)n_frames, d_mean, d_iv, d_c, (const int*)d_state_off, (const int*)d_kernel, d_lw,
                        S, d_scores);
     if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "gmm_loglik: kernel launch failed");
     return call.finish();
