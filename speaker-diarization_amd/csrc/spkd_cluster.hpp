@@ -92,6 +92,20 @@ __device__ __forceinline__ double kl2_from_aux(const double* __restrict__ a1,
     i = i >= D ? D - 1 : i;
     return kl2_combine(a1[i], a1[DA + i], a1[2 * DA + i], a2[i], a2[DA + i], a2[2 * DA + i]);
 }
+// The same distance by ONE lane, its 39-term sums in index order.  kl2_from_aux (a wave per pair,
+// wave_sum39's tree order) fills the initial matrix and the pair terms; this one serves every
+// distance to a merged or grown cluster (k_ahc, k_ahc_step, k_cluster_in: a lane per pair).  The
+// two orders round differently in the last bits: they are not interchangeable.
+__device__ __forceinline__ double kl2_from_aux_serial(const double* a1, const double* a2) {
+    double t1 = 0.0, t2 = 0.0;
+    for (int i = 0; i < D; ++i) {
+        const float dm = (float)a1[2 * DA + i] - (float)a2[2 * DA + i];
+        const double delta = (double)dm;
+        t1 += (a1[i] - a2[i]) * (a2[DA + i] - a1[DA + i]);
+        t2 += ((a1[DA + i] + a2[DA + i]) * delta) * delta;
+    }
+    return 0.5 * t1 + 0.5 * t2;
+}
 
 // per-lane KL2 ingredients of one record held as covariance rows in a (consumed):
 // ds = S_ii, dp = pinv(S)_ii (inverse, NaN when S is not positive definite; with a
@@ -113,18 +127,6 @@ __device__ __forceinline__ double kl2_combine(double s1, double p1, double m1,
     const double t1 = wave_sum39((s1 - s2) * (p2 - p1));
     const double t2 = wave_sum39(((p1 + p2) * delta) * delta);
     return 0.5 * t1 + 0.5 * t2;
-}
-
-__device__ __forceinline__ void kl2_aux_from_cov(double (&a)[DA], double mean_i,
-                                                 double* __restrict__ aux, double* pinv_ws) {
-    double ds, dp, mu;
-    kl2_lane_terms(a, mean_i, ds, dp, mu, pinv_ws);
-    const int lane = lane_id();
-    if (lane < D) {
-        aux[lane] = ds;
-        aux[DA + lane] = dp;
-        aux[2 * DA + lane] = mu;
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -172,6 +174,24 @@ __device__ __forceinline__ void single_rows_from_qr(const double* __restrict__ q
     const int base = (i / QL) * DA * 16 + (i % QL);
 #pragma unroll
     for (int j = 0; j < DA; ++j) q[j] = qr[base + j * 16];
+}
+
+// The KL2 vectors (diag S | diag pinv S | mean) of one quad record, global or LDS, by one wave:
+// what k_cluster_prep caches per record and what every merged or grown cluster gets anew.
+__device__ __forceinline__ void kl2_aux_from_qr(const double* qr, double* aux_out, double* pinv_ws) {
+    double a[DA];
+    single_rows_from_qr(qr, a);
+    const double n = qr_count(qr);
+    const double mean_i = a[D] / n;
+    cov_rows(a, n);
+    double ds, dp, mu;
+    kl2_lane_terms(a, mean_i, ds, dp, mu, pinv_ws);
+    const int lane = lane_id();
+    if (lane < D) {
+        aux_out[lane] = ds;
+        aux_out[DA + lane] = dp;
+        aux_out[2 * DA + lane] = mu;
+    }
 }
 
 // matrix whose log det a pair distance needs, row-per-lane layout
@@ -473,13 +493,7 @@ __global__ __launch_bounds__(PT_WAVES * WAVE) void k_cluster_prep(
     const int64_t w = (int64_t)blockIdx.x * PT_WAVES + wave;
     if (kind == SPKD_KL2) {
         if (w >= n_rec) return;
-        const double* R = qr + w * QREC;
-        double a[DA];
-        single_rows_from_qr(R, a);
-        const double n = qr_count(R);
-        const double mean_i = a[D] / n;
-        cov_rows(a, n);
-        kl2_aux_from_cov(a, mean_i, aux + w * AUX, pinv_ws);
+        kl2_aux_from_qr(qr + w * QREC, aux + w * AUX, pinv_ws);
         if (lane_id() == 0) ld[w] = 0.0;
         return;
     }
@@ -632,10 +646,117 @@ __device__ unsigned long long g_ahc_prof[8];      // profiling builds: rows resc
 constexpr int NO_COL = 0x7fffffff;
 constexpr int AHC_MAX_N = 65536;       // records per problem (row-flag masks live in LDS)
 
-// Row-cache refresh: every alive row flagged dirty gets its minimum, the first
-// column holding it and its first NaN column recomputed.  The flags are read 64
-// rows per load and the dirty ones taken from the ballot, so a round with few
-// dirty rows costs a few memory latencies, not one per row.
+// ---- The rules of the merge loop that k_ahc and the step chain share.  Each is stated here
+// once; the kernels differ in how they mark a cluster alive, never in these.
+
+// A row's cache entry: its minimum over the alive columns, the first column that holds it and
+// the first column that holds a NaN (NO_COL: none), with numpy's first-occurrence semantics.
+struct RowMin { double mv; int mc, nc; };
+
+// scan_row: the cache entry of one row by one wave, uniform across the wave.  alive(c) says
+// whether column c (< N) counts; sub_col >= 0 replaces that column's stored value by sub_val
+// (the caller's own fresh write).  A lane meets its columns in ascending order, four loads in
+// flight, and compares in fp64; the lanes' results meet as integers (wave_argmin_key on the
+// order-preserving key and the column, ~0 for a lane that found nothing).
+// Where the minimum of a row is a zero that occurs with both signs in different lanes, the key
+// order puts -0.0 first, where an fp64 compare would call the two equal and take the lower
+// column.  The selection over the rows (both launch shapes) orders by key as well.
+template <class Alive>
+__device__ __forceinline__ RowMin scan_row(const double* __restrict__ row, long long N, Alive alive,
+                                           long long sub_col, double sub_val, int lane) {
+    double mv = __builtin_huge_val();
+    int mc = NO_COL, nc = NO_COL;
+    for (long long c0 = 0; c0 < N; c0 += 4 * WAVE) {
+        double v[4];
+        int a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long long c = c0 + u * WAVE + lane;
+            const long long cc = c < N ? c : N - 1;
+            a[u] = (c < N) ? (alive(cc) ? 1 : 0) : 0;
+            v[u] = row[cc];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const long long cl = c0 + u * WAVE + lane;
+            const int c = (int)cl;
+            if (!a[u]) continue;
+            const double x = (cl == sub_col) ? sub_val : v[u];
+            if (x != x) { if (c < nc) nc = c; continue; }
+            if (x < mv || (x == mv && c < mc)) { mv = x; mc = c; }
+        }
+    }
+    unsigned long long okey;
+    unsigned oc;
+    wave_argmin_key(mc != NO_COL ? dkey(mv) : ~0ull, (unsigned)mc, okey, oc);
+    RowMin r;
+    r.mv = okey != ~0ull ? dkey_inv(okey) : __builtin_huge_val();
+    r.mc = okey != ~0ull ? (int)oc : NO_COL;
+    r.nc = __any(nc != NO_COL) ? (int)wave_red_u32<false>((unsigned)nc) : NO_COL;
+    return r;
+}
+
+// What the new distance d at column sa does to a partner row's cache entry (rm, ra, rn) after
+// the merge of (sa, sb): true = the entry cannot be kept, rescan the row; false = the entry, as
+// updated in place, stands.  Variant 1 rewrites column sa and drops column sb: an entry that
+// points at either (minimum or first NaN) is lost, unless its minimum sat there, its NaN did not,
+// and d is strictly smaller -- then d at sa is the row minimum whatever the rest holds.  Any
+// other row takes d like one more column: a NaN by its first column, a number by (value, then
+// lower column).  Variant 2 leaves column sa its stale value (A-9): only sb's departure matters.
+__device__ __forceinline__ bool row_cache_after_merge(int variant, double d, int sa, int sb,
+                                                      double& rm, int& ra, int& rn) {
+    if (variant != 1) return ra == sb || rn == sb;
+    const bool nan_hit = rn == sa || rn == sb;
+    if (ra == sa || ra == sb || nan_hit) {
+        if (nan_hit || !(d < rm)) return true;
+        rm = d; ra = sa;
+    } else if (d != d) {
+        if (sa < rn) rn = sa;
+    } else if (d < rm || (d == rm && sa < ra)) {
+        rm = d; ra = sa;
+    }
+    return false;
+}
+
+// distances.max() over the final alive sub-matrix (variant 2 reports it), NaN propagating, by a
+// workgroup of AHC_WAVES waves: a wave per row, a fold over the waves through s_tmax.  The
+// result is thread 0's.
+template <class Alive>
+__device__ __forceinline__ double final_matrix_max(const double* __restrict__ Dm, long long N, Alive alive,
+                                                   double* s_tmax, int tid) {
+    const int lane = tid & (WAVE - 1), wave = tid >> 6;
+    double tmax = -__builtin_huge_val();
+    bool anynan = false;
+    for (long long r = wave; r < N; r += AHC_WAVES) {
+        if (!alive(r)) continue;
+        const double* row = Dm + r * N;
+        for (long long c = lane; c < N; c += WAVE) {
+            if (!alive(c)) continue;
+            const double v = row[c];
+            if (v != v) anynan = true; else tmax = v > tmax ? v : tmax;
+        }
+    }
+#pragma unroll
+    for (int s = 1; s < WAVE; s <<= 1) {
+        const double t2 = __shfl_xor(tmax, s);
+        tmax = t2 > tmax ? t2 : tmax;
+    }
+    anynan = __any(anynan);
+    if (lane == 0) s_tmax[wave] = anynan ? __builtin_nan("") : tmax;
+    __syncthreads();
+    double mx = s_tmax[0];
+    if (tid == 0) {
+        for (int w = 1; w < AHC_WAVES; ++w) {
+            const double x = s_tmax[w];
+            if (mx == mx) mx = (x != x) ? x : (x > mx ? x : mx);
+        }
+    }
+    return mx;
+}
+
+// Row-cache refresh: every alive row flagged dirty gets its cache entry recomputed (scan_row).
+// The flags are read 64 rows per load and the dirty ones taken from the ballot, so a round
+// with few dirty rows costs a few memory latencies, not one per row.
 __device__ __forceinline__ void refresh_rows(const double* __restrict__ Dm, long long N,
                                              const int32_t* __restrict__ al, int32_t* __restrict__ dirty,
                                              double* __restrict__ rmin, int32_t* __restrict__ rarg,
@@ -662,37 +783,8 @@ __device__ __forceinline__ void refresh_rows(const double* __restrict__ Dm, long
             todo &= todo - 1;
             if ((ord++ & (AHC_WAVES - 1)) != wave) continue;
             const long long r = r0 + b;
-            const double* row = Dm + r * N;
-            double mv = __builtin_huge_val();
-            int mc = NO_COL, nc = NO_COL;
-            for (long long c0 = 0; c0 < N; c0 += 4 * WAVE) {
-                double v[4];
-                int a[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const long long c = c0 + u * WAVE + lane;
-                    const long long cc = c < N ? c : N - 1;
-                    a[u] = (c < N) ? al[cc] : 0;
-                    v[u] = row[cc];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int c = (int)(c0 + u * WAVE + lane);
-                    if (!a[u]) continue;
-                    if (v[u] != v[u]) { if (c < nc) nc = c; continue; }
-                    if (v[u] < mv || (v[u] == mv && c < mc)) { mv = v[u]; mc = c; }
-                }
-            }
-            {
-                // (the wave's minimum and its first column in integers: DPP row steps + v_readlane)
-                unsigned long long okey;
-                unsigned oc;
-                wave_argmin_key(mc != NO_COL ? dkey(mv) : ~0ull, (unsigned)mc, okey, oc);
-                mv = okey != ~0ull ? dkey_inv(okey) : __builtin_huge_val();
-                mc = okey != ~0ull ? (int)oc : NO_COL;
-                nc = __any(nc != NO_COL) ? (int)wave_red_u32<false>((unsigned)nc) : NO_COL;
-            }
-            if (lane == 0) { rmin[r] = mv; rarg[r] = mc; rnan[r] = nc; dirty[r] = 0; }
+            const RowMin e = scan_row(Dm + r * N, N, [&](long long c) { return al[c] != 0; }, -1, 0.0, lane);
+            if (lane == 0) { rmin[r] = e.mv; rarg[r] = e.mc; rnan[r] = e.nc; dirty[r] = 0; }
 #ifdef SPKD_PROFILE
             if (lane == 0) atomicAdd(&g_ahc_prof[0], 1ull);      // rows rescanned
 #endif
@@ -873,13 +965,7 @@ __global__ __launch_bounds__(AHC_TPB) void k_ahc(
         const double nA = ldsA[QREC_COUNT_AT];
         // ---- 3. the merged cluster's own term and the log dets of its unions
         if (kind == SPKD_KL2) {
-            if (wave == 0) {
-                double a[DA];
-                single_rows_from_qr(A, a);
-                const double mean_i = a[D] / nA;
-                cov_rows(a, nA);
-                kl2_aux_from_cov(a, mean_i, aux + (off + sa) * AUX, pinv_ws);
-            }
+            if (wave == 0) kl2_aux_from_qr(ldsA, aux + (off + sa) * AUX, pinv_ws);
         } else {
             // (the waves take the quads of partners from a counter, not by stride: a wave whose
             // records come late takes fewer, nobody idles at the barrier for the slowest's sixth pass)
@@ -908,38 +994,25 @@ __global__ __launch_bounds__(AHC_TPB) void k_ahc(
             if (c == sa || !al[c]) continue;
             double d;
             if (kind == SPKD_KL2) {
-                // (one lane per pair here: 39-term sums done serially)
-                const double* a1 = aux + (off + sa) * AUX;
-                const double* a2 = aux + (off + c) * AUX;
-                double t1 = 0.0, t2 = 0.0;
-                for (int i = 0; i < D; ++i) {
-                    const float dm = (float)a1[2 * DA + i] - (float)a2[2 * DA + i];
-                    const double delta = (double)dm;
-                    t1 += (a1[i] - a2[i]) * (a2[DA + i] - a1[DA + i]);
-                    t2 += ((a1[DA + i] + a2[DA + i]) * delta) * delta;
-                }
-                d = 0.5 * t1 + 0.5 * t2;
+                d = kl2_from_aux_serial(aux + (off + sa) * AUX, aux + (off + c) * AUX);
             } else {
                 const double nC = qr_count(ex + (off + c) * QREC);
                 d = finish_distance(kind, lambdac, nA, ldA, nC, ldp[c], log(tp[c]));
             }
             Dm[sa * N + c] = d;
-            const int ra = rarg[c], rn = rnan[c];
-            if (variant == 1) {
-                Dm[c * N + sa] = d;
-                if (ra == sa || ra == sb || rn == sa || rn == sb) {
-                    // a strictly smaller value at sa is the new row minimum whatever the rest holds
-                    if (rn != sa && rn != sb && d < rmin[c]) { rmin[c] = d; rarg[c] = (int)sa; }
-                    else dirty[c] = 1;
-                }
-                else if (d != d) { if ((int)sa < rn) rnan[c] = (int)sa; }
-                else if (d < rmin[c] || (d == rmin[c] && (int)sa < ra)) { rmin[c] = d; rarg[c] = (int)sa; }
-                if (stat_valid(d)) {
-                    wmax = (wmax != wmax || d > wmax) ? d : wmax;
-                    wmin = (wmin != wmin || d < wmin) ? d : wmin;
-                }
-            } else {
-                if (ra == sb || rn == sb) dirty[c] = 1;   // column sa keeps its stale value (A-9)
+            const double rm0 = rmin[c];
+            const int ra0 = rarg[c], rn0 = rnan[c];
+            double rm = rm0;
+            int ra = ra0, rn = rn0;
+            if (variant == 1) Dm[c * N + sa] = d;
+            if (row_cache_after_merge(variant, d, (int)sa, (int)sb, rm, ra, rn)) dirty[c] = 1;
+            else {                                        // (only what changed is stored)
+                if (rm != rm0 || ra != ra0) { rmin[c] = rm; rarg[c] = ra; }
+                if (rn != rn0) rnan[c] = rn;
+            }
+            if (variant == 1 && stat_valid(d)) {
+                wmax = (wmax != wmax || d > wmax) ? d : wmax;
+                wmin = (wmin != wmin || d < wmin) ? d : wmin;
             }
         }
         if (tid == 0) dirty[sa] = 1;
@@ -957,72 +1030,11 @@ __global__ __launch_bounds__(AHC_TPB) void k_ahc(
 #ifdef SPKD_PROFILE
     if (tid == 0) for (int i = 0; i < 5; ++i) atomicAdd(&g_ahc_prof[2 + i], ahc_acc[i]);
 #endif
-    // max over the final alive sub-matrix (variant 2 reports distances.max()); NaN propagates
-    double tmax = -__builtin_huge_val();
-    bool anynan = false;
-    for (long long r = wave; r < N; r += AHC_WAVES) {
-        if (!al[r]) continue;
-        const double* row = Dm + r * N;
-        for (long long c = lane; c < N; c += WAVE) {
-            if (!al[c]) continue;
-            const double v = row[c];
-            if (v != v) anynan = true; else tmax = v > tmax ? v : tmax;
-        }
-    }
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) {
-        const double t2 = __shfl_xor(tmax, s);
-        tmax = t2 > tmax ? t2 : tmax;
-    }
-    anynan = __any(anynan);
-    if (lane == 0) s_tmax[wave] = anynan ? __builtin_nan("") : tmax;
-    __syncthreads();
+    const double mx = final_matrix_max(Dm, N, [&](long long c) { return al[c] != 0; }, s_tmax, tid);
     if (tid == 0) {
-        double mx = s_tmax[0];
-        for (int w = 1; w < AHC_WAVES; ++w) {
-            const double x = s_tmax[w];
-            if (mx == mx) mx = (x != x) ? x : (x > mx ? x : mx);
-        }
         out_n[p] = n_merges;
         final_max[p] = mx;
         final_min[p] = fmin;
-    }
-}
-
-// wave-wide (min, first column, first NaN column) of one row; sub_col >= 0
-// replaces that column's stored value by sub_val (the caller's own fresh write)
-__device__ __forceinline__ void ahc_scan_row(const double* __restrict__ row, long long N,
-                                             const int32_t* __restrict__ al, bool all_alive,
-                                             long long sub_col, double sub_val, int lane,
-                                             double& mv, int& mc, int& nc) {
-    mv = __builtin_huge_val();
-    mc = NO_COL; nc = NO_COL;
-    for (long long c0 = 0; c0 < N; c0 += 4 * WAVE) {
-        double v[4];
-        int a[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const long long c = c0 + u * WAVE + lane;
-            const long long cc = c < N ? c : N - 1;
-            a[u] = (c < N) ? (all_alive ? 1 : al[cc]) : 0;
-            v[u] = row[cc];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const long long cl = c0 + u * WAVE + lane;
-            const int c = (int)cl;
-            if (!a[u]) continue;
-            const double x = (cl == sub_col) ? sub_val : v[u];
-            if (x != x) { if (c < nc) nc = c; continue; }
-            if (x < mv || (x == mv && c < mc)) { mv = x; mc = c; }
-        }
-    }
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) {
-        const double v2 = __shfl_xor(mv, s);
-        const int c2 = __shfl_xor(mc, s), n2 = __shfl_xor(nc, s);
-        if (v2 < mv || (v2 == mv && c2 < mc)) { mv = v2; mc = c2; }
-        nc = n2 < nc ? n2 : nc;
     }
 }
 
@@ -1044,7 +1056,9 @@ __device__ __forceinline__ void ahc_scan_row(const double* __restrict__ row, lon
 //     word (round | new | old) that reads correctly before and after workgroup 0 replaces it.
 // It replaced a ticket form, in which the last workgroup to arrive selected the next merge
 // alone, at 25.5 us per merge at N = 380 (this form: 14; DESIGN.md par. 3).
-// Arithmetic, tie-breaks and NaN rules are those of k_ahc; results are bit-identical.
+// Arithmetic, tie-breaks and NaN rules are k_ahc's by construction -- both call scan_row,
+// row_cache_after_merge, kl2_aux_from_qr, kl2_from_aux_serial, finish_distance and
+// final_matrix_max, with their own alive test -- so results are bit-identical.
 // ---------------------------------------------------------------------------
 constexpr int STEP_WAVES = 4;
 constexpr int STEP_WIDE_FROM = 1024;                       // problems larger than this: eight waves per workgroup
@@ -1108,54 +1122,15 @@ __global__ __launch_bounds__(AHC_TPB) void k_step_init(
     }
     const long long r = (long long)blockIdx.x * AHC_WAVES + wave;
     if (r >= N) return;
-    double mv;
-    int mc, nc;
-    ahc_scan_row(mat + mat_off[p] + r * N, N, nullptr, true, -1, 0.0, lane, mv, mc, nc);
+    const RowMin m = scan_row(mat + mat_off[p] + r * N, N, [](long long) { return true; }, -1, 0.0, lane);
     if (lane == 0) {
         StepSel e;
-        e.rmin = mv; e.newrow = 0.0; e.rarg = mc; e.rnan = nc; e.death = ALIVE_ROUND; e.pad = 0;
+        e.rmin = m.mv; e.newrow = 0.0; e.rarg = m.mc; e.rnan = m.nc; e.death = ALIVE_ROUND; e.pad = 0;
         Q.sel2[Q.n_total + off + r] = e;
         Q.sel2[off + r] = e;
         Q.death[off + r] = ALIVE_ROUND;
         Q.sw[off + r] = step_slot_word(0, (int)r, (int)r);
         Q.cnt[off + r] = Q.pk[(off + r) * REC + REC - 1];
-    }
-}
-
-// wave-wide (min, first column, first NaN column) of one row over the clusters alive AFTER
-// merge k (death > k, and not sb: its mark may not have landed yet); sub_col as in ahc_scan_row
-__device__ __forceinline__ void step_scan_row(const double* __restrict__ row, long long N,
-                                              const int32_t* __restrict__ death, int k, long long sb,
-                                              long long sub_col, double sub_val, int lane,
-                                              double& mv, int& mc, int& nc) {
-    mv = __builtin_huge_val();
-    mc = NO_COL; nc = NO_COL;
-    for (long long c0 = 0; c0 < N; c0 += 4 * WAVE) {
-        double v[4];
-        int a[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const long long c = c0 + u * WAVE + lane;
-            const long long cc = c < N ? c : N - 1;
-            a[u] = (c < N && c != sb) ? (death[cc] > k ? 1 : 0) : 0;
-            v[u] = row[cc];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const long long cl = c0 + u * WAVE + lane;
-            const int c = (int)cl;
-            if (!a[u]) continue;
-            const double x = (cl == sub_col) ? sub_val : v[u];
-            if (x != x) { if (c < nc) nc = c; continue; }
-            if (x < mv || (x == mv && c < mc)) { mv = x; mc = c; }
-        }
-    }
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) {
-        const double v2 = __shfl_xor(mv, s);
-        const int c2 = __shfl_xor(mc, s), n2 = __shfl_xor(nc, s);
-        if (v2 < mv || (v2 == mv && c2 < mc)) { mv = v2; mc = c2; }
-        nc = n2 < nc ? n2 : nc;
     }
 }
 
@@ -1181,7 +1156,6 @@ __global__ __launch_bounds__(SW * WAVE) void k_ahc_step(
     __shared__ double s_ldx[4 * STEP_WAVES];
     __shared__ double s_dfin[4 * STEP_WAVES];
     __shared__ int s_rescan[4 * STEP_WAVES];
-    struct RowRed { double mv; int mc, nc; };
     struct WaveRed { unsigned long long kb, kr, kmax, kmin; unsigned ib, inan; int mc, nc; };
     __shared__ WaveRed wred[SW];
     __shared__ int s_cnt[2];
@@ -1356,7 +1330,7 @@ __global__ __launch_bounds__(SW * WAVE) void k_ahc_step(
     }
     WaveRed f = fw[0];
     // row psa: its fresh cache (what the finish reads for r == psa), and its place in the arg-min
-    RowRed s_psa;
+    RowMin s_psa;
     s_psa.mv = f.mc != NO_COL ? dkey_inv(f.kr) : __builtin_huge_val();
     s_psa.mc = f.mc; s_psa.nc = f.nc;
     if (hp) {
@@ -1460,11 +1434,7 @@ __global__ __launch_bounds__(SW * WAVE) void k_ahc_step(
         }
     }
     if (kind == SPKD_KL2 && wave == 0) {
-        double a[DA];
-        single_rows_from_qr(ldsA, a);
-        const double mean_i = a[D] / nA;
-        cov_rows(a, nA);
-        kl2_aux_from_cov(a, mean_i, s_auxA, pinv_ws);
+        kl2_aux_from_qr(ldsA, s_auxA, pinv_ws);
         if (keeper && lane < D) {
             double* ga = aux + (off + sa) * AUX;
             ga[lane] = s_auxA[lane]; ga[DA + lane] = s_auxA[DA + lane]; ga[2 * DA + lane] = s_auxA[2 * DA + lane];
@@ -1517,39 +1487,16 @@ __global__ __launch_bounds__(SW * WAVE) void k_ahc_step(
         double d = 0.0;
         if (fin) {
             const long long r = fin_r;
-            if (kind == SPKD_KL2) {
-                const double* a2 = aux + (off + r) * AUX;
-                double t1 = 0.0, t2 = 0.0;
-                for (int i = 0; i < D; ++i) {
-                    const float dm = (float)s_auxA[2 * DA + i] - (float)a2[2 * DA + i];
-                    const double delta = (double)dm;
-                    t1 += (s_auxA[i] - a2[i]) * (a2[DA + i] - s_auxA[DA + i]);
-                    t2 += ((s_auxA[DA + i] + a2[DA + i]) * delta) * delta;
-                }
-                d = 0.5 * t1 + 0.5 * t2;
-            } else {
-                d = finish_distance(kind, lambdac, nA, ldA, fin_nC, fin_ld, s_ldx[j]);
-            }
+            if (kind == SPKD_KL2) d = kl2_from_aux_serial(s_auxA, aux + (off + r) * AUX);
+            else d = finish_distance(kind, lambdac, nA, ldA, fin_nC, fin_ld, s_ldx[j]);
             double rm;
             int ra, rn;
             if (r == psa) { rm = s_psa.mv; ra = s_psa.mc; rn = s_psa.nc; }
             else { rm = fin_sel.rmin; ra = fin_sel.rarg; rn = fin_sel.rnan; }
             Dm[sa * N + r] = d;
             sel_w[r].newrow = d;
-            if (variant == 1) {
-                Dm[r * N + sa] = d;
-                const bool nan_hit = (rn == sa || rn == sb);
-                if (ra == sa || ra == sb || nan_hit) {
-                    if (!nan_hit && d < rm) { rm = d; ra = (int)sa; }    // still (or now) the strict row minimum
-                    else rescan = true;
-                } else if (d != d) {
-                    if ((int)sa < rn) rn = (int)sa;
-                } else if (d < rm || (d == rm && (int)sa < ra)) {
-                    rm = d; ra = (int)sa;
-                }
-            } else if (ra == sb || rn == sb) {       // column sa keeps its stale value (A-9)
-                rescan = true;
-            }
+            if (variant == 1) Dm[r * N + sa] = d;
+            rescan = row_cache_after_merge(variant, d, (int)sa, (int)sb, rm, ra, rn);
             if (!rescan) { sel_w[r].rmin = rm; sel_w[r].rarg = ra; sel_w[r].rnan = rn; }
         }
         if (tid < 4 * STEP_WAVES) { s_rescan[tid] = rescan ? 1 : 0; s_dfin[tid] = d; }
@@ -1557,10 +1504,10 @@ __global__ __launch_bounds__(SW * WAVE) void k_ahc_step(
         for (int jj = 1 + wave; jj <= mine_n; jj += SW) {
             if (!s_rescan[jj]) continue;             // (wave-uniform)
             const long long r = s_ids[first + jj - 1];
-            double mv2;
-            int mc2, nc2;
-            step_scan_row(Dm + r * N, N, death, k, sb, variant == 1 ? sa : -1, s_dfin[jj], lane, mv2, mc2, nc2);
-            if (lane == 0) { sel_w[r].rmin = mv2; sel_w[r].rarg = mc2; sel_w[r].rnan = nc2; }
+            // the clusters alive AFTER merge k: death > k, and not sb (its mark may not have landed yet)
+            const RowMin e = scan_row(Dm + r * N, N, [&](long long c) { return c != sb && death[c] > k; },
+                                      variant == 1 ? sa : -1, s_dfin[jj], lane);
+            if (lane == 0) { sel_w[r].rmin = e.mv; sel_w[r].rarg = e.mc; sel_w[r].rnan = e.nc; }
         }
     }
     STEP_TICK(6);                                    // logs, distances, row caches, rescans
@@ -1580,38 +1527,14 @@ __global__ __launch_bounds__(AHC_TPB) void k_step_final(
         const int64_t* __restrict__ mat_off, StepArrays Q, int32_t* __restrict__ out_n,
         double* __restrict__ final_max, double* __restrict__ final_min) {
     __shared__ double s_tmax[AHC_WAVES];
-    const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int p = blockIdx.x;
     const int64_t off = seg_off[p];
     const long long N = seg_off[p + 1] - off;
-    const double* Dm = mat + mat_off[p];
     const int32_t* death = Q.death + off;
     const StepState S = Q.state2[(size_t)((last_round + 1) & 1) * Q.n_prob + p];
-    double tmax = -__builtin_huge_val();
-    bool anynan = false;
-    for (long long r = wave; r < N; r += AHC_WAVES) {
-        if (death[r] != ALIVE_ROUND) continue;
-        const double* row = Dm + r * N;
-        for (long long c = lane; c < N; c += WAVE) {
-            if (death[c] != ALIVE_ROUND) continue;
-            const double v = row[c];
-            if (v != v) anynan = true; else tmax = v > tmax ? v : tmax;
-        }
-    }
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) {
-        const double t2 = __shfl_xor(tmax, s);
-        tmax = t2 > tmax ? t2 : tmax;
-    }
-    anynan = __any(anynan);
-    if (lane == 0) s_tmax[wave] = anynan ? __builtin_nan("") : tmax;
-    __syncthreads();
+    const double mx = final_matrix_max(mat + mat_off[p], N, [&](long long c) { return death[c] == ALIVE_ROUND; }, s_tmax, tid);
     if (tid == 0) {
-        double mx = s_tmax[0];
-        for (int w = 1; w < AHC_WAVES; ++w) {
-            const double x = s_tmax[w];
-            if (mx == mx) mx = (x != x) ? x : (x > mx ? x : mx);
-        }
         out_n[p] = S.n_merges;
         final_max[p] = mx;
         final_min[p] = S.fmin;
@@ -1673,17 +1596,7 @@ __global__ __launch_bounds__(CIN_TPB) void k_cluster_in(
         const bool room = off + K <= dist_cap;
         for (long long k = tid; k < K && room; k += CIN_TPB) {
             if (kl2) {
-                // (one lane per pair, 39-term sums done serially: the arithmetic of k_ahc's finish)
-                const double* a1 = clu_aux + k * AUX;
-                const double* a2 = seg_aux + s * AUX;
-                double t1 = 0.0, t2 = 0.0;
-                for (int i = 0; i < D; ++i) {
-                    const float dm = (float)a1[2 * DA + i] - (float)a2[2 * DA + i];
-                    const double delta = (double)dm;
-                    t1 += (a1[i] - a2[i]) * (a2[DA + i] - a1[DA + i]);
-                    t2 += ((a1[DA + i] + a2[DA + i]) * delta) * delta;
-                }
-                dist[off + k] = 0.5 * t1 + 0.5 * t2;
+                dist[off + k] = kl2_from_aux_serial(clu_aux + k * AUX, seg_aux + s * AUX);
                 continue;
             }
             const double ldx = log(tmp[k]);
@@ -1720,14 +1633,7 @@ __global__ __launch_bounds__(CIN_TPB) void k_cluster_in(
             for (int e = tid; e < REC; e += CIN_TPB) Cp[e] = Cp[e] + Sp[e];
             __syncthreads();
             if (kl2) {
-                if (wave == 0) {                         // the grown cluster's KL2 vectors
-                    double a[DA];
-                    single_rows_from_qr(ldsA, a);
-                    const double nM = ldsA[QREC_COUNT_AT];
-                    const double mean_i = a[D] / nM;
-                    cov_rows(a, nM);
-                    kl2_aux_from_cov(a, mean_i, clu_aux + (long long)best * AUX, pinv_ws);
-                }
+                if (wave == 0) kl2_aux_from_qr(ldsA, clu_aux + (long long)best * AUX, pinv_ws);   // the grown cluster's
             } else if (TWO && kind == SPKD_GLR) {
                 if (wave == 0) {
                     const double v = quad_pair_det<TWO>(kind, ldsA, ldsA[QREC_COUNT_AT], Cx, Cx, Cp, true, L, err);

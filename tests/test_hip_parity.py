@@ -297,6 +297,102 @@ def test_ahc_launch_shapes_agree(eng, variant, kind):
                 _same_merges(b.merges, want.merges, rel=1e-5 if kind == 'KL2' else 1e-9)
 
 
+@pytest.mark.parametrize('n', [65, 257])
+@pytest.mark.parametrize('variant', [1, 2])
+def test_merge_loop_selection_on_a_planted_matrix(eng, variant, n):
+    """The merge loop on a caller's matrix (spkd_ahc_matrix) with ties and NaNs planted where the
+    row scan and the selection over the rows have their seams: n = 65 is two 64-row mask chunks,
+    the last with one row, and a tail lane in the scan; n = 257 a second trip of the scan's
+    256-column loop that holds one live column.  Both launch shapes must agree to the bit, and
+    the first merge must be numpy's M.min() / M.argmin() (first occurrence in row-major order;
+    with a NaN present the minimum is NaN and the position the first NaN: CL1:203-204)."""
+    synth = pkg('synth')
+    hipabi = pkg('hipabi')
+    feats, _, _ = synth.make_session(4242, 150, 3)
+    begins = np.arange(n, dtype=np.int64) * 60              # 60-frame slices: full-rank covariances
+    assert feats.shape[0] // 60 >= n
+    ctx = eng.ctx
+    d_fr = ctx.dev_alloc(feats.nbytes)
+    d_st = ctx.dev_alloc(n * hipabi.REC * 8)
+    d_m = ctx.dev_alloc(n * n * 8)
+    try:
+        ctx.h2d(d_fr, feats)
+        ctx.set_stats(d_fr, feats.shape[0], begins, begins + 60, np.arange(n, dtype=np.int32), n, d_st)
+        ctx.distance_rows(variant, 'BIC', 1.3, d_st, n, 0, n, d_m)
+        M = np.empty((n, n), dtype=np.float64)
+        ctx.d2h(M, d_m)
+        if variant == 1:                                    # the form spkd.h asks of the caller
+            diag = np.diag(M).copy()
+            up = np.triu(M, 1)
+            M = up + up.T
+            M[np.diag_indices(n)] = diag
+        iu = np.triu_indices(n, 1)
+        assert np.all(np.isfinite(M[iu]))
+
+        def put(r, c, v):
+            M[r, c] = v
+            if variant == 1:
+                M[c, r] = v
+
+        # (a) the global minimum at (1, 3), and its value again in a later column of that row
+        # (another lane, another of the scan's loads in flight) and in a later row (another wave
+        # of the selection): the first in row-major order has to win
+        r0, c0 = [int(x[np.argmin(M[iu])]) for x in iu]
+        g, old = M[r0, c0], M[1, 3]
+        put(r0, c0, old)
+        put(1, 3, g)
+        far = 3 + 65 if n > 3 + 65 else n - 1
+        put(1, far, g)
+        put(n - 2, n - 1, g)
+        # (b) a value below every other of row 5 (but above the global minimum) at the last column
+        row5 = np.delete(M[5], 5)
+        v = g + 0.5 * (row5.min() - g)
+        assert g < v < row5.min() and g != 0.0 and v != 0.0
+        put(5, n - 1, v)
+
+        def run(M, max_spk, threshold):
+            fin = M[iu][np.isfinite(M[iu])]
+            got = {}
+            for path in (hipabi.AHC_MONO, hipabi.AHC_WIDE):
+                ctx.h2d(d_m, np.ascontiguousarray(M))
+                p = hipabi.AhcParams(variant, hipabi.KINDS['BIC'], max_spk, path, 1.3, threshold)
+                got[path] = ctx.ahc_matrix(d_st, n, p, d_m, float(fin.max()), float(fin.min()))
+            a, b = got[hipabi.AHC_MONO], got[hipabi.AHC_WIDE]
+            nm = int(a['n_merges'][0])
+            assert int(b['n_merges'][0]) == nm
+            assert np.array_equal(a['a'][:nm], b['a'][:nm]) and np.array_equal(a['b'][:nm], b['b'][:nm])
+            for key in ('d', 'stat_max', 'stat_min'):       # equal to the bit, or both NaN
+                x, y = a[key][:nm] if key == 'd' else a[key], b[key][:nm] if key == 'd' else b[key]
+                assert np.array_equal(np.isnan(x), np.isnan(y)), key
+                assert np.array_equal(x[~np.isnan(x)].view(np.uint64), y[~np.isnan(y)].view(np.uint64)), key
+            # the first merge against numpy on the whole matrix (both variants scan every cell:
+            # variant 2's lower triangle and diagonal hold +inf, variant 1's diagonal 2^63);
+            # every cluster is alive, so the compacted indices are the cell's own
+            want_d, pos = M.min(), int(M.argmin())
+            r, c = divmod(pos, n)
+            assert (int(a['a'][0]), int(a['b'][0])) == (min(r, c), max(r, c))
+            assert (np.isnan(want_d) and np.isnan(a['d'][0])) or \
+                np.float64(want_d).view(np.uint64) == a['d'][:1].view(np.uint64)[0]
+            return nm, (min(r, c), max(r, c))
+
+        nm, first = run(M, 0, 0.0)
+        assert first == (1, 3)
+        assert nm >= 10
+        # (c) NaNs: one at the last column of row 7, one at an earlier cell of that row, and one
+        # in a later row at a column in front of both: the first in row-major order is (7, 20).
+        # The loop stops at a NaN minimum unless max_spk forces it: three forced merges, none
+        # by the threshold.
+        put(7, n - 1, float('nan'))
+        put(7, 20, float('nan'))
+        put(9, 12, float('nan'))
+        nm, first = run(M, n - 3, -1e300)
+        assert first == (7, 20)
+        assert nm == 3
+    finally:
+        for d in (d_m, d_st, d_fr):
+            ctx.dev_free(d)
+
+
 def test_sliding_window_and_merge_modes_on_a_longer_file(eng, tmp_path):
     """sw (GLR), m (BIC with the frozen c1, GLR) on 10 minutes against the C oracle."""
     import io
