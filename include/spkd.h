@@ -161,6 +161,30 @@ spkd_status spkd_cluster_in(spkd_ctx *ctx, const double *d_stats, int64_t n, int
                             double *h_dist, int64_t dist_cap, int64_t *h_dist_off,
                             int64_t *h_n_done, int64_t *h_n_clusters);
 
+/* spkd_cluster_in for n_problems independent recipes (files) in one launch, a workgroup per
+ * problem: problem p owns the records [h_seg_off[p], h_seg_off[p+1]) of d_stats (read only;
+ * h_seg_off[0] = 0, n = h_seg_off[n_problems]) and is clustered exactly as spkd_cluster_in
+ * clusters those records alone -- same kernels' arithmetic in the same order, the same labels
+ * and distances to the bit.  The distances themselves are not returned:
+ *   h_label[n]        0-based cluster of every record within its problem
+ *   h_mind[n]         the reference's `mind` of the record: the minimum over its finite
+ *                     distances, the value compared with the threshold; 2^63 (sys.maxint)
+ *                     when it has none, as for the first record of a problem
+ *   h_n_done[p], h_n_clusters[p]   records processed and clusters founded
+ *   h_stat_max[p], h_stat_min[p]   max / min over every finite distance of the records
+ *                     processed (NaN: none) -- the summary the scripts print
+ * An empty problem reports 0 records, 0 clusters, NaN; n_problems = 0 is SPKD_OK.  A covariance
+ * with infs or NaNs stops ITS problem at record h_n_done[p] < its size, like spkd_cluster_in,
+ * and leaves every other problem untouched: the call returns SPKD_ENONFINITE with all outputs
+ * valid (h_label -1 and h_mind NaN from the record that stopped a problem on).  There is no
+ * distance buffer and so no SPKD_EOVERFLOW.  A bad kind, a null pointer, an h_seg_off that
+ * decreases or a problem of more than 65 536 records: SPKD_EINVAL before any device work. */
+spkd_status spkd_cluster_in_batch(spkd_ctx *ctx, const double *d_stats, int64_t n_problems,
+                                  const int64_t *h_seg_off, int kind, double lambdac,
+                                  double threshold, int32_t *h_label, double *h_mind,
+                                  int64_t *h_n_done, int64_t *h_n_clusters,
+                                  double *h_stat_max, double *h_stat_min);
+
 /* Rows [row_begin, row_end) of that matrix, as spk_cluster_hi's variant `variant` fills them
  * (a block of the outer loop of spk-clustering.py:188-200 / spk-clustering2.py:178-184):
  * d_rows[(a - row_begin) * n + c] for c > a is the distance, c == a the diagonal value

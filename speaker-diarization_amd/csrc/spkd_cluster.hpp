@@ -484,13 +484,14 @@ __global__ __launch_bounds__(PT2_WAVES * WAVE) void k_pair_terms(
 }
 
 // ---------------------------------------------------------------------------
-// per-record cached terms: log det S (BIC / GLR) or the KL2 vectors
-__global__ __launch_bounds__(PT_WAVES * WAVE) void k_cluster_prep(
+// per-record cached terms: log det S (BIC / GLR) or the KL2 vectors; workgroup `block` of the
+// n_rec records at qr
+__device__ __forceinline__ void cluster_prep_block(
         const double* __restrict__ qr, int64_t n_rec, int kind,
         double* __restrict__ ld, double* __restrict__ aux, int* err,
-        double* pinv_ws) {
+        double* pinv_ws, int64_t block) {
     const int wave = threadIdx.x >> 6;
-    const int64_t w = (int64_t)blockIdx.x * PT_WAVES + wave;
+    const int64_t w = block * PT_WAVES + wave;
     if (kind == SPKD_KL2) {
         if (w >= n_rec) return;
         kl2_aux_from_qr(qr + w * QREC, aux + w * AUX, pinv_ws);
@@ -526,6 +527,25 @@ __global__ __launch_bounds__(PT_WAVES * WAVE) void k_cluster_prep(
     auto form_single = [&](int mi, double (&a)[DA]) { single_pair_matrix(kind, recs[mi], recs[mi], true, a); };
     const double v = tri_logdet(q, L.m, err, form_single);
     if (valid && L.t == 0) ld[c] = v;
+}
+
+__global__ __launch_bounds__(PT_WAVES * WAVE) void k_cluster_prep(
+        const double* __restrict__ qr, int64_t n_rec, int kind,
+        double* __restrict__ ld, double* __restrict__ aux, int* err,
+        double* pinv_ws) {
+    cluster_prep_block(qr, n_rec, kind, ld, aux, err, pinv_ws, blockIdx.x);
+}
+
+// The same for the records of several problems, problem blockIdx.x by its own workgroups
+// (blockIdx.y; those past its end leave): a wave's four records are one problem's, so a record
+// whose covariance is not finite raises the word of ITS problem, prob_err[p], and no other.
+__global__ __launch_bounds__(PT_WAVES * WAVE) void k_cluster_prep_batch(
+        const double* __restrict__ qr, const int64_t* __restrict__ seg_off, int kind,
+        double* __restrict__ ld, double* __restrict__ aux, int* prob_err,
+        double* pinv_ws) {
+    const int64_t off = seg_off[blockIdx.x];
+    cluster_prep_block(qr + off * QREC, seg_off[blockIdx.x + 1] - off, kind, ld + off, aux + off * AUX,
+                       prob_err + blockIdx.x, pinv_ws, blockIdx.y);
 }
 
 __device__ __forceinline__ double finish_distance(int kind, double lambdac, double nA, double ldA,
@@ -1543,30 +1563,75 @@ __global__ __launch_bounds__(AHC_TPB) void k_step_final(
 
 // ---------------------------------------------------------------------------
 // spk_cluster_in (spk-clustering.py:136-175 / spk-clustering2.py:135-170) as ONE device-resident
-// chain over the statistics records of the recipe's lines, in recipe order: record 0 founds
+// chain over the statistics records of a recipe's lines, in recipe order: record 0 founds
 // cluster 0; every later record is compared with every cluster so far -- the cluster is the
 // first argument of the distance, the new segment the second -- and joins the first arg-min
 // over the finite distances if that is <= threshold, else founds a new cluster.  A cluster's
 // record is the sum of its members' (the reference concatenates their frames); BIC's own term
 // of a grown cluster is the union determinant of the pair that grew it, GLR's takes one more
-// pass.  One workgroup: the chain is serial, a step is one wave pass for up to 16 clusters.
-// Host-driven (a library call and a synchronisation per segment and per stage) the same took
-// 345 us per segment; this takes ~10.
-// dist: all distances in evaluation order, dist_off[s] .. dist_off[s + 1] those of record s
-// (the host replays the reference's prints and statistics from them).  done[0]: records
-// processed (< n: a non-finite covariance or a full dist buffer stopped the chain at that
-// record), done[1]: clusters.
+// pass.  One workgroup per chain: the chain is serial, a step is one wave pass for up to 16
+// clusters.  Host-driven (a library call and a synchronisation per segment and per stage) the
+// same took 345 us per segment; this takes ~10.
+// cluster_in_chain is the chain; what becomes of a step's distances is its caller's (`out`):
+//   CinKeep     (k_cluster_in, one recipe): all distances in evaluation order, dist_off[s] ..
+//               dist_off[s + 1] those of record s (the host replays the reference's prints and
+//               statistics from them); a full buffer stops the chain (error bit 4).
+//   CinSummary  (k_cluster_in_batch, a recipe per workgroup): a step's distances in a row of the
+//               problem's own, per record the reference's `mind` (the minimum that decided it,
+//               MAXINT_F without a finite distance), per problem the running max / min over
+//               the finite distances of the records done (NaN: none).
+// err: the word the chain's determinants raise ERR_NONFINITE in and the chain stops on -- the
+// problem's own (one problem: the context's).  Returns the records processed (< n: stopped at
+// that record); K: the clusters.
 // ---------------------------------------------------------------------------
 constexpr int CIN_WAVES = 4;
 constexpr int CIN_TPB = CIN_WAVES * WAVE;
 
-template <bool TWO>
-__global__ __launch_bounds__(CIN_TPB) void k_cluster_in(
+struct CinKeep {
+    double* dist;
+    long long cap;
+    long long* dist_off;
+    int* status;
+    long long off = 0;
+    __device__ bool room(long long K) const { return off + K <= cap; }
+    __device__ void refuse() const { atomicOr(status, 4); }          // the host gave too small a buffer
+    __device__ double* row() const { return dist + off; }
+    __device__ void step() {}
+    __device__ void seen(double) {}
+    __device__ void decided(long long s, long long K, double, bool lead) {
+        off += K;
+        if (lead) dist_off[s + 1] = off;
+    }
+};
+
+struct CinSummary {                  // (seen, and the running values, are the leading thread's)
+    double* dists;
+    double* mind;
+    double smax = __builtin_nan(""), smin = __builtin_nan("");
+    double tmax = __builtin_nan(""), tmin = __builtin_nan("");     // of the step under way
+    __device__ bool room(long long) const { return true; }
+    __device__ void refuse() const {}
+    __device__ double* row() const { return dists; }
+    __device__ void step() { tmax = tmin = __builtin_nan(""); }
+    __device__ void seen(double d) {
+        if (!stat_valid(d)) return;
+        if (!(tmax >= d)) tmax = d;
+        if (!(tmin <= d)) tmin = d;
+    }
+    __device__ void decided(long long s, long long, double m, bool lead) {
+        if (!lead) return;
+        mind[s] = m;
+        if (tmax == tmax && !(smax >= tmax)) smax = tmax;
+        if (tmin == tmin && !(smin <= tmin)) smin = tmin;
+    }
+};
+
+template <bool TWO, class Out>
+__device__ __forceinline__ long long cluster_in_chain(
         const double* __restrict__ seg_ex, const double* __restrict__ seg_pk, const double* __restrict__ seg_ld,
         const double* __restrict__ seg_aux, long long n, int kind, double lambdac, double threshold,
         double* __restrict__ clu_ex, double* __restrict__ clu_pk, double* __restrict__ clu_ld, double* __restrict__ clu_aux,
-        double* __restrict__ tmp, int32_t* __restrict__ label, double* __restrict__ dist, long long dist_cap,
-        long long* __restrict__ dist_off, long long* __restrict__ done, int* err,
+        double* __restrict__ tmp, int32_t* __restrict__ label, Out& out, long long& K, int* err,
         double* pinv_ws) {
     __shared__ double ldsA[QREC];
     __shared__ int s_best, s_stop;
@@ -1575,10 +1640,11 @@ __global__ __launch_bounds__(CIN_TPB) void k_cluster_in(
     const QuadLane L = quad_lane();
     for (int e = tid; e < QREC; e += CIN_TPB) clu_ex[e] = seg_ex[e];
     for (int e = tid; e < REC; e += CIN_TPB) clu_pk[e] = seg_pk[e];
-    if (tid == 0) { clu_ld[0] = seg_ld[0]; label[0] = 0; dist_off[0] = 0; dist_off[1] = 0; }
+    if (tid == 0) { clu_ld[0] = seg_ld[0]; label[0] = 0; }
     const bool kl2 = kind == SPKD_KL2;               // distances from the records' KL2 vectors (k_cluster_prep), no eliminations
     if (kl2) for (int e = tid; e < AUX; e += CIN_TPB) clu_aux[e] = seg_aux[e];
-    long long K = 1, off = 0, s = 1;
+    long long s = 1;
+    K = 1;
     __syncthreads();
     for (; s < n; ++s) {
         const double* A = seg_ex + s * QREC;
@@ -1593,28 +1659,31 @@ __global__ __launch_bounds__(CIN_TPB) void k_cluster_in(
             if (valid && L.t == 0) tmp[k] = v;
         }
         __syncthreads();
-        const bool room = off + K <= dist_cap;
+        const bool room = out.room(K);
+        double* dist = out.row();
         for (long long k = tid; k < K && room; k += CIN_TPB) {
             if (kl2) {
-                dist[off + k] = kl2_from_aux_serial(clu_aux + k * AUX, seg_aux + s * AUX);
+                dist[k] = kl2_from_aux_serial(clu_aux + k * AUX, seg_aux + s * AUX);
                 continue;
             }
             const double ldx = log(tmp[k]);
             tmp[k] = ldx;
-            dist[off + k] = finish_distance(kind, lambdac, clu_pk[k * REC + REC - 1], clu_ld[k], nA, ldS, ldx);
+            dist[k] = finish_distance(kind, lambdac, clu_pk[k * REC + REC - 1], clu_ld[k], nA, ldS, ldx);
         }
         __syncthreads();
         if (tid == 0) {
             double mind = MAXINT_F;                      // sys.maxint
             int best = -1;
+            out.step();
             for (long long k = 0; k < K && room; ++k) {
-                const double d = dist[off + k];
+                const double d = dist[k];
+                out.seen(d);
                 // "if d != inf and d != -inf" (a NaN passes and then fails every comparison)
                 if (d != __builtin_huge_val() && d != -__builtin_huge_val() && d < mind) { mind = d; best = (int)k; }
             }
             s_mind = mind; s_best = best;
             int stop = room ? 0 : 1;
-            if (!room) atomicOr(err, 4);                 // the host gave too small a buffer
+            if (!room) out.refuse();
             if (*reinterpret_cast<volatile int*>(err) & ERR_NONFINITE) stop = 1;
             s_stop = stop;
         }
@@ -1652,12 +1721,66 @@ __global__ __launch_bounds__(CIN_TPB) void k_cluster_in(
             if (kl2) for (int e = tid; e < AUX; e += CIN_TPB) clu_aux[K * AUX + e] = seg_aux[s * AUX + e];
             if (tid == 0) { clu_ld[K] = ldS; label[s] = (int32_t)K; }
         }
-        off += K;
+        out.decided(s, K, s_mind, tid == 0);
         if (!(s_mind <= threshold && best >= 0)) ++K;
-        if (tid == 0) dist_off[s + 1] = off;
         __syncthreads();
     }
-    if (tid == 0) { done[0] = s; done[1] = K; }
+    return s;
+}
+
+// done[0]: records processed (< n: a non-finite covariance or a full dist buffer stopped the
+// chain at that record), done[1]: clusters.
+template <bool TWO>
+__global__ __launch_bounds__(CIN_TPB) void k_cluster_in(
+        const double* __restrict__ seg_ex, const double* __restrict__ seg_pk, const double* __restrict__ seg_ld,
+        const double* __restrict__ seg_aux, long long n, int kind, double lambdac, double threshold,
+        double* __restrict__ clu_ex, double* __restrict__ clu_pk, double* __restrict__ clu_ld, double* __restrict__ clu_aux,
+        double* __restrict__ tmp, int32_t* __restrict__ label, double* __restrict__ dist, long long dist_cap,
+        long long* __restrict__ dist_off, long long* __restrict__ done, int* err,
+        double* pinv_ws) {
+    if (threadIdx.x == 0) { dist_off[0] = 0; dist_off[1] = 0; }
+    CinKeep out{dist, dist_cap, dist_off, err};
+    long long K;
+    const long long s = cluster_in_chain<TWO>(seg_ex, seg_pk, seg_ld, seg_aux, n, kind, lambdac, threshold,
+                                              clu_ex, clu_pk, clu_ld, clu_aux, tmp, label, out, K, err, pinv_ws);
+    if (threadIdx.x == 0) { done[0] = s; done[1] = K; }
+}
+
+// P chains in one launch, a workgroup each: problem p = blockIdx.x owns the records seg_off[p] ..
+// seg_off[p + 1] of every per-record array, the input's and -- a problem never has more
+// clusters than records -- the clusters', the step's determinants (tmp) and distances (dists).
+// label: the record's cluster within its problem (-1 behind a stop), mind: see CinSummary (NaN
+// behind a stop); done[2 p], done[2 p + 1], stat_max[p], stat_min[p] as above.  prob_err[p] is
+// the problem's error word (k_cluster_prep_batch has raised it for a record of p that is not
+// finite; the chain's determinants do, and the chain stops on it): nothing a problem reports
+// depends on another problem's records.  The call's status is the OR of the words, in err.
+template <bool TWO>
+__global__ __launch_bounds__(CIN_TPB) void k_cluster_in_batch(
+        const double* __restrict__ seg_ex, const double* __restrict__ seg_pk, const double* __restrict__ seg_ld,
+        const double* __restrict__ seg_aux, const int64_t* __restrict__ seg_off, int kind, double lambdac, double threshold,
+        double* __restrict__ clu_ex, double* __restrict__ clu_pk, double* __restrict__ clu_ld, double* __restrict__ clu_aux,
+        double* __restrict__ tmp, double* __restrict__ dists, int32_t* __restrict__ label, double* __restrict__ mind,
+        long long* __restrict__ done, double* __restrict__ stat_max, double* __restrict__ stat_min,
+        int* prob_err, int* err, double* pinv_ws) {
+    const int tid = threadIdx.x;
+    const long long p = blockIdx.x, off = seg_off[p], n = seg_off[p + 1] - off;
+    CinSummary out{dists + off, mind + off};
+    long long s = 0, K = 0;
+    if (n > 0) {                                     // (block-uniform)
+        if (tid == 0) mind[off] = MAXINT_F;          // record 0 meets no cluster
+        s = cluster_in_chain<TWO>(seg_ex + off * QREC, seg_pk + off * REC, seg_ld + off, seg_aux + off * AUX, n, kind,
+                                  lambdac, threshold, clu_ex + off * QREC, clu_pk + off * REC, clu_ld + off,
+                                  clu_aux + off * AUX, tmp + off, label + off, out, K, prob_err + p, pinv_ws);
+    }
+    for (long long r = s + tid; r < n; r += CIN_TPB) { label[off + r] = -1; mind[off + r] = __builtin_nan(""); }
+    if (tid == 0) {
+        done[2 * p] = s;
+        done[2 * p + 1] = K;
+        stat_max[p] = out.smax;
+        stat_min[p] = out.smin;
+        const int e = *reinterpret_cast<volatile int*>(prob_err + p);
+        if (e) atomicOr(err, e);
+    }
 }
 
 }  // namespace spkd

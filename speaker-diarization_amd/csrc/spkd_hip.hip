@@ -738,6 +738,90 @@ spkd_status spkd_cluster_in(spkd_ctx* c, const double* d_stats, int64_t n, int k
     return st;
 }
 
+spkd_status spkd_cluster_in_batch(spkd_ctx* c, const double* d_stats, int64_t n_prob, const int64_t* h_seg_off, int kind,
+                                  double lambdac, double threshold, int32_t* h_label, double* h_mind,
+                                  int64_t* h_n_done, int64_t* h_n_clusters, double* h_stat_max, double* h_stat_min) {
+    if (!c || n_prob < 0 || bad_kind(kind)) return SPKD_EINVAL;
+    if (n_prob == 0) return SPKD_OK;
+    if (!h_seg_off || !h_n_done || !h_n_clusters || !h_stat_max || !h_stat_min) return fail(c, SPKD_EINVAL, "null argument");
+    if (h_seg_off[0] != 0) return fail(c, SPKD_EINVAL, "seg_off must start at 0");
+    int64_t longest = 0;
+    for (int64_t p = 0; p < n_prob; ++p) {
+        if (h_seg_off[p + 1] < h_seg_off[p]) return fail(c, SPKD_EINVAL, "seg_off must be non-decreasing");
+        longest = std::max(longest, h_seg_off[p + 1] - h_seg_off[p]);
+    }
+    if (longest > 65536) return fail(c, SPKD_EINVAL, "cluster_in_batch: a problem of more than 65 536 records");
+    const int64_t n = h_seg_off[n_prob];
+    if (n > 0 && (!d_stats || !h_label || !h_mind)) return fail(c, SPKD_EINVAL, "null argument");
+    const size_t nn = (size_t)n, np = (size_t)n_prob;
+    std::vector<long long> done2(2 * np, 0);
+    std::vector<char> offs;
+    Call call(c);
+    TRY(call.opened);
+    TRY(use_kind(c, kind, &kind));
+    int64_t* d_segoff = nullptr;
+    TRY(upload_parts(c, S_AHC_OFF, offs, [&](Layout L) { return L.part(d_segoff, np + 1, h_seg_off).bytes(); }));
+    double *ex, *ld, *aux, *clu_ex, *clu_pk;
+    TRY(carve(c, scratch, S_AHC_STATS, [&](Layout L) { return L.part(ex, nn * QREC).bytes(); }));
+    TRY(carve(c, scratch, S_AHC_LD, [&](Layout L) { return L.part(ld, nn).bytes(); }));
+    TRY(carve(c, scratch, S_AHC_AUX, [&](Layout L) { return L.part(aux, nn * AUX).bytes(); }));
+    TRY(carve(c, scratch, S_STEP_EXM, [&](Layout L) { return L.part(clu_ex, nn * QREC).bytes(); }));
+    TRY(carve(c, scratch, S_STEP_PKM, [&](Layout L) { return L.part(clu_pk, nn * REC).bytes(); }));
+    double *clu_ld, *tmp, *clu_aux, *dists, *d_mind, *d_smax, *d_smin;
+    long long* d_done;
+    int32_t* d_label;
+    int* d_perr;
+    // cluster log dets | determinants and distances of a step | cluster KL2 vectors | mind | per problem: done,
+    // clusters, max, min | labels | the problems' error words
+    TRY(carve(c, scratch, S_STEP_MISC, [&](Layout L) {
+        return L.part(clu_ld, nn).part(tmp, nn).part(dists, nn).part(clu_aux, nn * AUX).part(d_mind, nn)
+            .part(d_smax, np).part(d_smin, np).part(d_done, 2 * np).part(d_label, nn).part(d_perr, np).bytes();
+    }));
+    HIPCHK(c, hipMemsetAsync(d_perr, 0, np * sizeof(int), c->stream));
+    if (n > 0) {
+        to_quadrec(c, d_stats, n, ex);
+        // (the records' own log dets also for KL2, and its vectors in a second pass: see spkd_cluster_in)
+        auto prep = [&](int k, double* out_ld) {
+            const int64_t per_block = k == SPKD_KL2 ? PT_WAVES : 4 * PT_WAVES;
+            hipLaunchKernelGGL(k_cluster_prep_batch, dim3((unsigned)n_prob, (unsigned)((longest + per_block - 1) / per_block)),
+                               dim3(PT_WAVES * WAVE), 0, c->stream, (const double*)ex, (const int64_t*)d_segoff, k, out_ld, aux,
+                               d_perr, c->pinv_cur);
+        };
+        {
+            Timer t(c, SPKD_T_CLUSTER_PREP);
+            prep(kind == SPKD_KL2 ? (int)SPKD_BIC : kind, ld);
+        }
+        if (kind == SPKD_KL2) {
+            void* p_ld2 = nullptr;
+            TRY(scratch(c, S_AHC_OUT, nn * sizeof(double), &p_ld2));
+            prep(SPKD_KL2, (double*)p_ld2);
+        }
+    }
+    auto kin = kind == SPKD_GLR ? k_cluster_in_batch<true> : k_cluster_in_batch<false>;
+    {
+        Timer t(c, SPKD_T_AHC);
+        hipLaunchKernelGGL(kin, dim3((unsigned)n_prob), dim3(CIN_TPB), 0, c->stream,
+                           (const double*)ex, d_stats, (const double*)ld, (const double*)aux, (const int64_t*)d_segoff, kind,
+                           lambdac, threshold, clu_ex, clu_pk, clu_ld, clu_aux, tmp, dists, d_label, d_mind, d_done,
+                           d_smax, d_smin, d_perr, c->d_err, c->pinv_cur);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(done2.data(), d_done, 2 * np * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_stat_max, d_smax, np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_stat_min, d_smin, np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n > 0) {
+        HIPCHK(c, hipMemcpyAsync(h_label, d_label, nn * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h_mind, d_mind, nn * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    const spkd_status st = call.finish();
+    if (st != SPKD_OK && st != SPKD_ENONFINITE) return st;
+    for (size_t p = 0; p < np; ++p) {
+        h_n_done[p] = done2[2 * p];
+        h_n_clusters[p] = done2[2 * p + 1];
+    }
+    return st;
+}
+
 spkd_status spkd_distance_rows(spkd_ctx* c, int variant, int kind, double lambdac, const double* d_stats,
                                int64_t n, int64_t row_begin, int64_t row_end, double* d_rows,
                                double* h_stat_max, double* h_stat_min) {

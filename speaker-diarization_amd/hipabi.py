@@ -22,7 +22,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_set_stats', 'spkd_pair_terms',
            'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_mfcc',
-           'spkd_sw_window_count', 'spkd_sw', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_py2_roundtrip',
+           'spkd_sw_window_count', 'spkd_sw', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi']
 
@@ -184,6 +184,7 @@ def load_library(path=None):
     lib.spkd_ahc_matrix.argtypes = [vp, vp, i64, P(AhcParams), vp, dbl, dbl, vp, vp, vp, vp, vp, vp]
     lib.spkd_distance_rows.argtypes = [vp, C.c_int, C.c_int, dbl, vp, i64, i64, i64, vp, P(dbl), P(dbl)]
     lib.spkd_cluster_in.argtypes = [vp, vp, i64, C.c_int, dbl, dbl, vp, vp, i64, vp, P(i64), P(i64)]
+    lib.spkd_cluster_in_batch.argtypes = [vp, vp, i64, vp, C.c_int, dbl, dbl, vp, vp, vp, vp, vp, vp]
     lib.spkd_py2_roundtrip.argtypes = [vp, i64]
     lib.spkd_py2_roundtrip.restype = None
     lib.spkd_labels_from_merges.argtypes = [i64, i64, vp, vp, vp]
@@ -662,6 +663,30 @@ class Context(object):
         nd = int(done.value)
         dists = [dist[int(off[s]):int(off[s + 1])].copy() for s in range(nd)]
         return label[:n], dists, nd, int(nclu.value), st
+
+    def cluster_in_batch(self, d_stats, seg_off, kind, lambdac, threshold):
+        """spk_cluster_in for every problem of seg_off in one launch (spkd_cluster_in_batch), each
+        as cluster_in on its records alone -> dict: label (0-based within the problem) and mind
+        per record, n_done, n_clusters, stat_max, stat_min per problem, status.  status is
+        SPKD_ENONFINITE when a covariance with infs or NaNs stopped a problem (n_done[p] < its
+        size); the other problems are complete."""
+        seg_off = np.ascontiguousarray(seg_off, dtype=np.int64)
+        if seg_off.ndim != 1 or len(seg_off) < 1:
+            raise SpkdError(SPKD_EINVAL, 'seg_off: one entry per problem and the total')
+        npb = len(seg_off) - 1
+        nt = max(int(seg_off[-1]), 0)
+        label = np.zeros(nt, dtype=np.int32)
+        mind = np.zeros(nt, dtype=np.float64)
+        done = np.zeros(npb, dtype=np.int64)
+        nclu = np.zeros(npb, dtype=np.int64)
+        smax = np.full(npb, np.nan)
+        smin = np.full(npb, np.nan)
+        st = self.lib.spkd_cluster_in_batch(self.h, C.c_void_p(d_stats), npb, _ptr(seg_off),
+                                            KINDS[kind] if isinstance(kind, str) else int(kind), float(lambdac),
+                                            float(threshold), _ptr(label), _ptr(mind), _ptr(done), _ptr(nclu),
+                                            _ptr(smax), _ptr(smin))
+        self.check(st, allow=(SPKD_ENONFINITE,))
+        return dict(status=st, label=label, mind=mind, n_done=done, n_clusters=nclu, stat_max=smax, stat_min=smin)
 
     def ahc_matrix(self, d_stats, n, params, d_matrix, stat_max_in=float('nan'), stat_min_in=float('nan')):
         """The merge loop of one n-record problem on a caller-supplied initial matrix."""

@@ -72,6 +72,15 @@ def _ahc_params(cl):
                             cl['lambdac'], cl['threshold'])
 
 
+def _method(cl):
+    """The clustering mode of a `cl` dictionary: 'hi' (spk_cluster_hi, also when the key is
+    absent) or 'in' (spk_cluster_in)."""
+    m = cl.get('method', 'hi')
+    if m not in ('hi', 'in'):
+        raise ValueError('cl method: hi or in')
+    return m
+
+
 def _detector_done(ctx, timings, tb, te, r):
     """After a growing-window call (gw or gw_batch result r): its timings entries, and the
     reference's error for frames that are not finite."""
@@ -108,6 +117,22 @@ def _clustering_done(ctx, timings, seg_off, r):
         timings['matrix_pairs'] = int((npb * (npb - 1) // 2).sum())
         # merge m of a problem with N records recomputes N - 2 - m distances
         timings['ahc_pairs'] = int((nm * (npb - 2) - nm * (nm - 1) // 2).sum())
+
+
+def _cluster_in_done(ctx, timings, seg_off, r):
+    """After a cluster_in_batch call (result r), as _clustering_done: the chain is the 'ahc' entry."""
+    if timings is not None:
+        for k in ('cluster_prep', 'ahc'):
+            timings.setdefault(k, []).append(ctx.last_ms(k))
+    if r['status'] == hipabi.SPKD_ENONFINITE:
+        raise ValueError('array must not contain infs or NaNs')
+    if timings is not None:
+        # a record meets the clusters founded before it: one more than the largest label so far
+        pairs = 0
+        for o, e in zip(seg_off[:-1].tolist(), seg_off[1:].tolist()):
+            if e - o > 1:
+                pairs += int((np.maximum.accumulate(r['label'][o:e - 1]).astype(np.int64) + 1).sum())
+        timings['cluster_in_pairs'] = pairs
 
 
 def _problems(cnt):
@@ -228,11 +253,16 @@ def cluster_batch(ctx, d_frames, total_frames, files, segments, rate=125.0, cl=D
     """segments: per file, array [(start_s, end_s)] as the clustering script parses
     them.  Returns per file (labels[int array, 1-based, per segment in input
     order], merges[(a, b, d)]).
+    cl['method'] = 'in': spk_cluster_in instead of spk_cluster_hi, every file's chain in one
+    launch (spkd_cluster_in_batch); labels are the cluster numbers in the order the clusters
+    were founded, merges is None.
     fused: the FusedStats of change_detect_batch for exactly these segments: the records
     of the segments whose frame range (as computed here, from the times) equals the range
     the detector summed are gathered from its buffer; only the others -- a boundary the
     12-digit text round trip moved across a frame edge -- are computed from the frames."""
     rate = float(rate)
+    method = _method(cl)
+    want_merges = want_merges and method == 'hi'
     cnt = [len(s) for s in segments]
     keep = _problems(cnt)[0]
     if len(keep) < len(files):               # (the lines of the others keep their order: fused stays valid)
@@ -246,10 +276,16 @@ def cluster_batch(ctx, d_frames, total_frames, files, segments, rate=125.0, cl=D
     _t0 = time.perf_counter()
     d_stats, seg_off, n, _t1 = segment_stats(ctx, d_frames, total_frames, files, segments, rate, timings, fused)
     _t2 = time.perf_counter()
-    r = ctx.ahc(d_stats, seg_off, _ahc_params(cl))
-    _t3 = time.perf_counter()
-    _clustering_done(ctx, timings, seg_off, r)
-    all_labels = hipabi.labels_from_merges_batch(seg_off, r['n_merges'], r['a'], r['b'])
+    if method == 'in':
+        r = ctx.cluster_in_batch(d_stats, seg_off, cl['kind'], cl['lambdac'], cl['threshold'])
+        _t3 = time.perf_counter()
+        _cluster_in_done(ctx, timings, seg_off, r)
+        all_labels = r['label'] + 1
+    else:
+        r = ctx.ahc(d_stats, seg_off, _ahc_params(cl))
+        _t3 = time.perf_counter()
+        _clustering_done(ctx, timings, seg_off, r)
+        all_labels = hipabi.labels_from_merges_batch(seg_off, r['n_merges'], r['a'], r['b'])
     out = []
     for fi in range(len(files)):
         o, c = int(seg_off[fi]), cnt[fi]
@@ -325,6 +361,10 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
                   text_contract=True, fused=False, handoff=None):
     """CD (gw/BIC) + CL (hi/BIC) for a batch; returns per file an array of rows
     [start_s, end_s, speaker] in recipe order.
+    cl['method'] = 'in' clusters with spk_cluster_in (cluster_batch): host hand-off only; the
+    rows stay in input order (the script writes each line as it is decided) with the times it
+    writes -- the input's, but from a file's second line on under variant 1, which casts:
+    int(t * rate) / rate (clustering._cluster_in_chain).
     fused=True: the frames are read once -- the change detector leaves every segment's
     statistics record for the clustering stage (segments and labels are those of the
     two-pass form; a record differs from the two-pass one only in the order of its
@@ -332,9 +372,12 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     handoff: 'device' (the default of fused=True with the text contract: diarize_batch_device)
     or 'host' (the event arrays come to the host, which builds the lines and gathers the
     records: the only form of the two-pass and text_contract=False modes)."""
+    method = _method(cl)
     if handoff is None:
-        handoff = 'device' if fused and text_contract else 'host'
+        handoff = 'device' if fused and text_contract and method == 'hi' else 'host'
     if handoff == 'device':
+        if method == 'in':
+            raise ValueError('the device hand-off clusters with spk_cluster_hi: method in takes the host hand-off')
         if not (fused and text_contract):
             raise ValueError('the device hand-off is the fused mode with the text contract')
         return diarize_batch_device(ctx, d_frames, total_frames, files, rate, cd, cl, timings)
@@ -355,9 +398,16 @@ def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timin
         return [np.zeros((0, 3)) for _ in segs]
     allseg = np.concatenate([np.asarray(s, dtype=np.float64).reshape(-1, 2) for s in segs])
     labels = np.concatenate([lab for (lab, _) in res])
-    rows = _recipe_rows(allseg, np.repeat(np.arange(len(segs)), cnt), labels, rate)
     bounds = np.zeros(len(segs) + 1, dtype=np.int64)
     bounds[1:] = np.cumsum(cnt)
+    if _method(cl) == 'in':
+        rows = np.column_stack([allseg, labels.astype(np.float64)])
+        if cl['variant'] == 1:
+            later = np.ones(len(rows), dtype=bool)
+            later[bounds[:-1][np.diff(bounds) > 0]] = False
+            rows[later, :2] = (rows[later, :2] * rate).astype(np.int64) / rate
+    else:
+        rows = _recipe_rows(allseg, np.repeat(np.arange(len(segs)), cnt), labels, rate)
     out = [rows[bounds[i]:bounds[i + 1]] for i in range(len(segs))]
     return out
 
