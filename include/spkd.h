@@ -350,6 +350,51 @@ spkd_status spkd_sw(spkd_ctx *ctx, const float *d_frames, int64_t n_frames,
                     const int64_t *h_turn_begin, const int64_t *h_turn_end, int64_t n_turns,
                     const spkd_cd_params *params, const int64_t *h_d_off, double *h_d);
 
+/* The positive-run pass of dist_sw (spk-change-detection.py:299-357) on the device, over a
+ * DEVICE array of window distances: turn t owns d_dist[h_d_off[t] .. h_d_off[t+1]) (h_d_off[0]
+ * = 0), one wave per turn.  The state machine is the script's, in fp64: bestd = -1 and
+ * best_position = -1 at first; d < threshold or d = +-inf is a negative window, everything else
+ * (NaN included) a positive one; a positive d moves last_positive, only d > bestd moves bestd
+ * and best_position = start + winsize; a series is written when start - winstep ==
+ * last_positive, at a negative window and once behind the loop; writing resets bestd to 0 and
+ * leaves best_position (a series that never beat bestd writes the stale position, -1 when
+ * there never was one).  Uses params->winsize, winstep, threshold.
+ * Results in the growing-window event layout, so that spkd_gw_lines writes the script's lines:
+ * detection j of turn t at slot h_ev_off[t] + j with det_start = `end` before it, det_maxi =
+ * best_position - end, det_d = bestd; h_final_start[t] = the last `end`; h_n_det[t].  A turn
+ * needs (windows / 2 + 1) slots -- a bound: two series have a negative window between them --
+ * and less is SPKD_EINVAL.
+ * Per turn also the script's summary counters over that turn alone, each started where the
+ * script starts it (maxima at 0, minima at 2^63 = float(sys.maxint)) and moved by its
+ * comparisons (d > max, d < min): h_win_cnt / h_win_max / h_win_min over the windows whose
+ * distance is not +-inf, h_det_max / h_det_min over the detections' det_d (their count is
+ * h_n_det).  The sums are the host's: their order is. */
+spkd_status spkd_sw_runs(spkd_ctx *ctx, const double *d_dist, const int64_t *h_d_off, int64_t n_turns,
+                         const spkd_cd_params *params, const int64_t *h_ev_off,
+                         int32_t *h_n_det, double *h_det_start, double *h_det_maxi, double *h_det_d,
+                         double *h_final_start, int64_t *h_win_cnt, double *h_win_max,
+                         double *h_win_min, double *h_det_max, double *h_det_min);
+
+/* Sliding-window change detection for every turn of every file in one call: the distances of
+ * spkd_sw (bit for bit: the same sums in the same order through the same kernels) and the pass
+ * of spkd_sw_runs behind them, all on the device.  Only the per-turn arrays go up; the windows'
+ * geometry is formed on the device.  The windows, counted flat over the turns, are processed in
+ * tiles of tile_windows (0: the library's default, 4 096): device scratch is 45.8 KB per window
+ * of a TILE, plus 8 bytes per window of the call for the distances -- not the 2 x 6 560 bytes
+ * and the working copies per window of the call that spkd_sw needs.
+ * h_d_off as for spkd_sw (checked against spkd_sw_window_count), h_ev_off and the outputs as
+ * for spkd_sw_runs; only these per-turn and per-detection arrays are copied back, and the
+ * distances when h_d is not NULL.  Argument checks (SPKD_EINVAL) come before any device work.
+ * Frames with infs or NaNs inside a window: SPKD_ENONFINITE for the call, as spkd_sw.
+ * kind = SPKD_BIC is the correct two-window BIC, as spkd_sw. */
+spkd_status spkd_sw_batch(spkd_ctx *ctx, const float *d_frames, int64_t n_frames,
+                          const int64_t *h_turn_begin, const int64_t *h_turn_end, int64_t n_turns,
+                          const spkd_cd_params *params, const int64_t *h_d_off, const int64_t *h_ev_off,
+                          int64_t tile_windows,
+                          int32_t *h_n_det, double *h_det_start, double *h_det_maxi, double *h_det_d,
+                          double *h_final_start, int64_t *h_win_cnt, double *h_win_max,
+                          double *h_win_min, double *h_det_max, double *h_det_min, double *h_d);
+
 /* ---------------------------------------------------------------------------
  * (4) Agglomerative clustering, spk_cluster_hi
  * (variant 1: spk-clustering.py:178-240, variant 2: spk-clustering2.py:173-222).

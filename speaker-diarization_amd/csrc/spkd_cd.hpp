@@ -13,13 +13,16 @@
 // The growing-window decision chain (a float state machine with int() truncation,
 // SURVEY.md A-1) runs on the device with the exact operation order of the reference.
 //
-// Sliding window (dist_sw, spk-change-detection.py:291-357): no kernel of its own -- every
-// window is a pair distance between two frame sets, computed by the statistics and
-// clustering kernels (spkd_sw in spkd_hip.hip).
+// Sliding window (dist_sw, spk-change-detection.py:291-357): every window is a pair distance
+// between two frame sets, computed by the statistics and clustering kernels (spkd_sw in
+// spkd_hip.hip).  The batch form (spkd_sw_batch) has two kernels of its own, at the end of this
+// file: k_sw_window_stats forms the two records of a window from per-turn data alone, and
+// k_sw_runs walks a turn's distances through the positive-run state machine (CD:299-357).
 #pragma once
 #include <type_traits>
 #include "spkd_device.hpp"
 #include "spkd_quad.hpp"
+#include "spkd_stats.hpp"
 #include "spkd_cluster.hpp"
 #include "../../include/spkd.h"
 
@@ -1122,6 +1125,136 @@ __global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void k_gw(
     }
     if (lane == 0) atomicAdd(&g_gw_prof[6], prof_passes);
 #endif
+}
+
+// ---------------------------------------------------------------------------
+// Sliding window, batch form.
+//
+// k_sw_window_stats: one workgroup per window of the current tile (flat window index
+// w0 + blockIdx.x over all turns).  The turn is found in the per-turn window offsets, the
+// geometry formed here: a = turn_begin + (int64)((double)w * winstep), halves [a, a + size) and
+// [a + size, a + 2 size).  Each half is summed chunk by chunk with k_chunk_stats' body and the
+// chunk sums added in chunk order from 0.0, as k_reduce_sets adds them: the records are the
+// ones spkd_sw gets, bit for bit.  Record 2 b (left) and 2 b + 1 (right) of the tile's buffer.
+// A window that does not lie inside its turn raises the capacity bit and writes nothing.
+__global__ __launch_bounds__(STATS_TPB) void k_sw_window_stats(
+        const float* __restrict__ frames, const int64_t* __restrict__ turn_begin,
+        const int64_t* __restrict__ turn_end, const int64_t* __restrict__ d_off, int64_t n_turns,
+        int64_t w0, double winstep, int64_t size, double* __restrict__ rec, int* err) {
+    __shared__ double xs[STATS_TILE][DA];
+    __shared__ double part[STATS_WAVES][SBLOCKS][SB * SB];
+    const int tid = threadIdx.x;
+    const int64_t g = w0 + blockIdx.x;
+    const int t = find_problem(d_off, n_turns, g);
+    const int64_t tb = turn_begin[t];
+    const int64_t a = tb + (int64_t)((double)(g - d_off[t]) * winstep);
+    if (a < tb || a + 2 * size > turn_end[t]) {          // (workgroup-uniform)
+        if (tid == 0) atomicOr(err, 4);
+        return;
+    }
+    for (int h = 0; h < 2; ++h) {
+        double sum[STATS_ENTRIES];
+#pragma unroll
+        for (int k = 0; k < STATS_ENTRIES; ++k) sum[k] = 0.0;
+        const int64_t b = a + h * size;
+        for (int64_t c = 0; c < size; c += STATS_CHUNK) {
+            const int len = (int)(size - c < STATS_CHUNK ? size - c : STATS_CHUNK);
+            chunk_stats_accumulate(frames, b + c, len, xs, part, [&](int k, int, double v) { sum[k] += v; });
+            __syncthreads();                             // part is read out before the next chunk fills it
+        }
+        double* out = rec + (2 * (int64_t)blockIdx.x + h) * REC;
+#pragma unroll
+        for (int k = 0; k < STATS_ENTRIES; ++k) {
+            const int e = tid + k * STATS_TPB;
+            if (e < REC) out[e] = sum[k];
+        }
+    }
+}
+
+// What k_sw_runs leaves per turn beside the events: the script's summary counters over the
+// turn alone, each started where the script starts it (maxima at 0, minima at float(sys.maxint)),
+// so the host folds the turns with the same comparisons (_window_stat, _detection_stat).
+struct SwTurnStats {
+    long long* win_cnt;          // windows whose distance is not +-inf
+    double *win_max, *win_min;   // over those
+    double *det_max, *det_min;   // over the detections' distances (their count is n_det)
+};
+
+// The positive-run pass of dist_sw (CD:299-357) over the distances of a turn, one wave per
+// turn: the wave stages 64 distances at a time, lane 0 walks them.  All state fp64 with the
+// values the script has: bestd = -1 and best_position = -1 at first; a written series resets
+// bestd to 0 and leaves best_position; d < threshold or d = +-inf is negative, everything else
+// (NaN too) positive; a positive d moves last_positive, only d > bestd moves bestd and
+// best_position; a series is written when start - winstep == last_positive at a negative window
+// and once behind the loop.  Detection j of turn t goes to slot ev_off[t] + j in the
+// growing-window layout: det_start = the `end` before it, det_maxi = best_position - end,
+// det_d = bestd; final_start = the last `end`.  More detections than slots: the capacity bit.
+constexpr int SWR_STAGE = WAVE;
+__global__ __launch_bounds__(WAVE) void k_sw_runs(
+        const double* __restrict__ dist, const int64_t* __restrict__ d_off, const int64_t* __restrict__ ev_off,
+        int64_t n_turns, double winsize, double winstep, double threshold,
+        int32_t* __restrict__ n_det, double* __restrict__ det_start, double* __restrict__ det_maxi,
+        double* __restrict__ det_d, double* __restrict__ final_start, SwTurnStats st, int* err) {
+    __shared__ double stage[SWR_STAGE];
+    const int64_t t = blockIdx.x;
+    if (t >= n_turns) return;
+    const int lane = threadIdx.x;
+    const int64_t o = d_off[t], W = d_off[t + 1] - o;
+    const int64_t e0 = ev_off[t], cap = ev_off[t + 1] - e0;
+    double start = 0.0, end = 0.0, bestd = -1.0, best_position = -1.0, last_positive = -1.0;
+    long long cnt = 0;
+    double wmax = 0.0, wmin = MAXINT_F, dmax = 0.0, dmin = MAXINT_F;
+    int64_t nd = 0;
+    bool full = false;
+    auto flush = [&]() {
+        if (nd < cap) {
+            det_start[e0 + nd] = end;
+            det_maxi[e0 + nd] = best_position - end;
+            det_d[e0 + nd] = bestd;
+        } else {
+            full = true;
+        }
+        ++nd;
+        if (bestd > dmax) dmax = bestd;
+        if (bestd < dmin) dmin = bestd;
+        bestd = 0.0;
+        end = best_position;
+    };
+    for (int64_t w0 = 0; w0 < W; w0 += SWR_STAGE) {
+        const int n = (int)(W - w0 < SWR_STAGE ? W - w0 : SWR_STAGE);
+        __syncthreads();                                 // the previous stage has been walked
+        if (lane < n) stage[lane] = dist[o + w0 + lane];
+        __syncthreads();
+        if (lane == 0) {
+            for (int i = 0; i < n; ++i) {
+                const double d = stage[i];
+                const bool inf = fabs(d) == __builtin_huge_val();
+                if (!inf) {
+                    ++cnt;
+                    if (d > wmax) wmax = d;
+                    if (d < wmin) wmin = d;
+                }
+                if (d < threshold || inf) {
+                    if (start - winstep == last_positive) flush();
+                } else {
+                    if (d > bestd) { bestd = d; best_position = start + winsize; }
+                    last_positive = start;
+                }
+                start += winstep;
+            }
+        }
+    }
+    if (lane == 0) {
+        if (start - winstep == last_positive) flush();
+        if (full) atomicOr(err, 4);
+        n_det[t] = (int32_t)(full ? 0 : nd);
+        final_start[t] = end;
+        st.win_cnt[t] = cnt;
+        st.win_max[t] = wmax;
+        st.win_min[t] = wmin;
+        st.det_max[t] = dmax;
+        st.det_min[t] = dmin;
+    }
 }
 
 }  // namespace spkd

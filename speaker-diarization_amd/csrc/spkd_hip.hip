@@ -1036,6 +1036,12 @@ int64_t spkd_gw_event_capacity_p(int64_t turn_len, const spkd_cd_params* P) {
 
 int64_t spkd_sw_window_count(int64_t turn_len, double winsize, double winstep) {
     if (!(winstep >= 1.0) || !(winsize >= 1.0)) return -1;
+    // whole frames (what the scripts' floor() gives): the sums of the loop below are exact
+    if (winsize == std::floor(winsize) && winstep == std::floor(winstep) && winsize < 1e15 && winstep < 1e15 &&
+        turn_len < (int64_t)1e15) {
+        const int64_t size2 = 2 * (int64_t)winsize;
+        return turn_len < size2 ? 0 : (turn_len - size2) / (int64_t)winstep + 1;
+    }
     int64_t w = 0;
     for (double s = 0; s + 2 * winsize <= (double)turn_len; s += winstep) ++w;
     return w;
@@ -1529,6 +1535,202 @@ spkd_status spkd_sw(spkd_ctx* c, const float* d_frames, int64_t n_frames, const 
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_d, d_out, (size_t)n_d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return call.finish();
+}
+
+// ---- sliding window for a whole batch (spkd_sw_batch, spkd_sw_runs)
+namespace {
+// windows per tile when the caller leaves the choice to the library: per window the tile holds two
+// packed and two quad records, their log dets and KL2 vectors and a 2 x 2 matrix, 45.8 KB
+constexpr int64_t SW_TILE_WINDOWS = 4096;
+
+// where the positive-run pass leaves its results on the host
+struct SwRunsOut {
+    int32_t* n_det;
+    double *det_start, *det_maxi, *det_d, *final_start;
+    int64_t* win_cnt;
+    double *win_max, *win_min, *det_max, *det_min;
+    bool complete() const {
+        return n_det && det_start && det_maxi && det_d && final_start && win_cnt && win_max && win_min && det_max && det_min;
+    }
+};
+
+// the checks of the two calls on the per-turn offsets: windows from 0 and non-decreasing, event
+// slots per turn at least the bound windows / 2 + 1
+spkd_status sw_check_offsets(spkd_ctx* c, const int64_t* h_d_off, const int64_t* h_ev_off, int64_t n_turns) {
+    if (h_d_off[0] != 0 || h_ev_off[0] < 0) return fail(c, SPKD_EINVAL, "sw: offsets must start at 0");
+    for (int64_t t = 0; t < n_turns; ++t) {
+        const int64_t W = h_d_off[t + 1] - h_d_off[t];
+        if (W < 0) return fail(c, SPKD_EINVAL, "sw: offsets must be non-decreasing");
+        if (h_ev_off[t + 1] - h_ev_off[t] < W / 2 + 1)
+            return fail(c, SPKD_EINVAL, "sw: event capacity below windows / 2 + 1");
+    }
+    return SPKD_OK;
+}
+
+// the per-turn tables of the two calls on the device; begin / end only with frames
+struct SwTurns {
+    int64_t *begin = nullptr, *end = nullptr, *d_off = nullptr, *ev_off = nullptr;
+    std::vector<char> image;
+};
+
+spkd_status sw_upload_turns(spkd_ctx* c, SwTurns& T, const int64_t* hb, const int64_t* he, const int64_t* h_d_off,
+                            const int64_t* h_ev_off, int64_t n_turns) {
+    const size_t nt = (size_t)n_turns;
+    return upload_parts(c, S_TURNS, T.image, [&](Layout L) {
+        if (hb) L.part(T.begin, nt, hb).part(T.end, nt, he);
+        return L.part(T.d_off, nt + 1, h_d_off).part(T.ev_off, nt + 1, h_ev_off).bytes();
+    });
+}
+
+// k_sw_runs over d_dist and the copies of its results, inside the caller's bracket
+spkd_status sw_runs_enqueue(spkd_ctx* c, const double* d_dist, const SwTurns& T, int64_t n_turns, int64_t n_ev,
+                            const spkd_cd_params* P, const SwRunsOut& out) {
+    const size_t nt = (size_t)n_turns, ne = (size_t)n_ev;
+    int32_t* n_det;
+    double *det_start, *det_maxi, *det_d, *final_start;
+    SwTurnStats st;
+    TRY(carve(c, scratch, S_GW_DET_START, [&](Layout L) {
+        return L.part(det_start, ne).part(det_maxi, ne).part(det_d, ne).part(final_start, nt).part(st.win_max, nt)
+            .part(st.win_min, nt).part(st.det_max, nt).part(st.det_min, nt).part(st.win_cnt, nt).part(n_det, nt).bytes();
+    }));
+    hipLaunchKernelGGL(k_sw_runs, dim3((unsigned)n_turns), dim3(WAVE), 0, c->stream, d_dist, (const int64_t*)T.d_off,
+                       (const int64_t*)T.ev_off, n_turns, P->winsize, P->winstep, P->threshold, n_det, det_start,
+                       det_maxi, det_d, final_start, st, c->d_err);
+    HIPCHK(c, hipGetLastError());
+    auto back = [&](void* h, const void* d, size_t bytes) {
+        return bytes ? hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIPCHK(c, back(out.n_det, n_det, nt * sizeof(int32_t)));
+    HIPCHK(c, back(out.det_start, det_start, ne * sizeof(double)));
+    HIPCHK(c, back(out.det_maxi, det_maxi, ne * sizeof(double)));
+    HIPCHK(c, back(out.det_d, det_d, ne * sizeof(double)));
+    HIPCHK(c, back(out.final_start, final_start, nt * sizeof(double)));
+    HIPCHK(c, back(out.win_cnt, st.win_cnt, nt * sizeof(int64_t)));
+    HIPCHK(c, back(out.win_max, st.win_max, nt * sizeof(double)));
+    HIPCHK(c, back(out.win_min, st.win_min, nt * sizeof(double)));
+    HIPCHK(c, back(out.det_max, st.det_max, nt * sizeof(double)));
+    HIPCHK(c, back(out.det_min, st.det_min, nt * sizeof(double)));
+    return SPKD_OK;
+}
+}  // namespace
+
+spkd_status spkd_sw_runs(spkd_ctx* c, const double* d_dist, const int64_t* h_d_off, int64_t n_turns,
+                         const spkd_cd_params* P, const int64_t* h_ev_off, int32_t* h_n_det, double* h_det_start,
+                         double* h_det_maxi, double* h_det_d, double* h_final_start, int64_t* h_win_cnt,
+                         double* h_win_max, double* h_win_min, double* h_det_max, double* h_det_min) {
+    if (!c || !P || n_turns < 0) return SPKD_EINVAL;
+    if (n_turns == 0) return SPKD_OK;
+    const SwRunsOut out = {h_n_det, h_det_start, h_det_maxi, h_det_d, h_final_start,
+                           h_win_cnt, h_win_max, h_win_min, h_det_max, h_det_min};
+    if (!h_d_off || !h_ev_off || !out.complete()) return fail(c, SPKD_EINVAL, "null argument");
+    if (!(P->winsize >= 1.0) || !(P->winstep >= 1.0)) return fail(c, SPKD_EINVAL, "sw: window and step must be >= 1 frame");
+    TRY(sw_check_offsets(c, h_d_off, h_ev_off, n_turns));
+    if (h_d_off[n_turns] > 0 && !d_dist) return fail(c, SPKD_EINVAL, "null argument");
+    SwTurns T;
+    Call call(c);
+    TRY(call.opened);
+    TRY(sw_upload_turns(c, T, nullptr, nullptr, h_d_off, h_ev_off, n_turns));
+    {
+        Timer t(c, SPKD_T_SW);
+        TRY(sw_runs_enqueue(c, d_dist, T, n_turns, h_ev_off[n_turns], P, out));
+    }
+    return call.finish();
+}
+
+// One call for every turn of every file.  The windows, counted flat over the turns, are taken in
+// tiles of tile_windows: per tile k_sw_window_stats writes the two records of every window,
+// k_cluster_prep and k_matrix turn them into distances exactly as spkd_sw does (every window a
+// two-record problem; only the row of its left record is launched, the right one's would write
+// nothing but a diagonal cell), and the distances land in the tile's slice of d_dist.  The
+// scratch of the records and working copies is the tile's; the tables that say "window p owns
+// records 2 p, 2 p + 1 and cells 4 p .." are the same for every tile and go up once.  Then
+// k_sw_runs walks d_dist per turn.
+spkd_status spkd_sw_batch(spkd_ctx* c, const float* d_frames, int64_t n_frames, const int64_t* hb,
+                          const int64_t* he, int64_t n_turns, const spkd_cd_params* P, const int64_t* h_d_off,
+                          const int64_t* h_ev_off, int64_t tile_windows, int32_t* h_n_det, double* h_det_start,
+                          double* h_det_maxi, double* h_det_d, double* h_final_start, int64_t* h_win_cnt,
+                          double* h_win_max, double* h_win_min, double* h_det_max, double* h_det_min, double* h_d) {
+    if (!c || !P || n_turns < 0) return SPKD_EINVAL;
+    if (n_turns == 0) return SPKD_OK;
+    const SwRunsOut out = {h_n_det, h_det_start, h_det_maxi, h_det_d, h_final_start,
+                           h_win_cnt, h_win_max, h_win_min, h_det_max, h_det_min};
+    if (!d_frames || !hb || !he || !h_d_off || !h_ev_off || !out.complete()) return fail(c, SPKD_EINVAL, "null argument");
+    if (bad_kind(P->kind)) return fail(c, SPKD_EINVAL, "bad kind");
+    if (!(P->winsize >= 1.0) || !(P->winstep >= 1.0)) return fail(c, SPKD_EINVAL, "sw: window and step must be >= 1 frame");
+    if (tile_windows < 0) return fail(c, SPKD_EINVAL, "sw_batch: negative tile_windows");
+    const int64_t wsz = (int64_t)P->winsize;
+    for (int64_t t = 0; t < n_turns; ++t) {
+        if (hb[t] < 0 || he[t] < hb[t] || he[t] > n_frames) return fail(c, SPKD_EINVAL, "bad turn range");
+        const int64_t W = spkd_sw_window_count(he[t] - hb[t], P->winsize, P->winstep);
+        if (h_d_off[t + 1] - h_d_off[t] != W) return fail(c, SPKD_EINVAL, "sw: offsets do not match spkd_sw_window_count");
+        // (the count walks s += step, the geometry multiplies: the last window must still end inside the turn)
+        if (W > 0 && hb[t] + (int64_t)((double)(W - 1) * P->winstep) + 2 * wsz > he[t])
+            return fail(c, SPKD_EINVAL, "sw: a window ends behind its turn");
+    }
+    TRY(sw_check_offsets(c, h_d_off, h_ev_off, n_turns));
+    const int64_t n_d = h_d_off[n_turns];
+    const int64_t tile = std::min(tile_windows ? tile_windows : SW_TILE_WINDOWS, std::min<int64_t>(n_d, 0x3fffffff));
+    const size_t nw = (size_t)tile;
+    // the tile's tables: window p is the problem of records 2 p, 2 p + 1 with cells 4 p ..; block b computes the
+    // row of record 2 b
+    std::vector<int64_t> seg_off(nw + 1), mat_off(nw + 1);
+    std::vector<int32_t> prob(2 * nw), sched(nw);
+    for (size_t p = 0; p <= nw; ++p) { seg_off[p] = 2 * (int64_t)p; mat_off[p] = 4 * (int64_t)p; }
+    for (size_t p = 0; p < nw; ++p) { prob[2 * p] = prob[2 * p + 1] = (int32_t)p; sched[p] = (int32_t)(2 * p); }
+    std::vector<char> offs, prob_of;
+    SwTurns T;
+    Call call(c);
+    TRY(call.opened);
+    spkd_cd_params Pk;
+    TRY(kernel_params(c, P, Pk));
+    TRY(sw_upload_turns(c, T, hb, he, h_d_off, h_ev_off, n_turns));
+    void* d_dist = nullptr;
+    TRY(scratch(c, S_GW_WIN_MAXD, (size_t)n_d * sizeof(double), &d_dist));
+    {
+        Timer timer(c, SPKD_T_SW);
+        if (n_d > 0) {
+            int64_t *d_segoff, *d_matoff;
+            int32_t *d_prob, *d_sched;
+            double *rec, *ex, *ld, *aux, *mat;
+            unsigned long long *smax, *smin;
+            TRY(upload_parts(c, S_AHC_OFF, offs, [&](Layout L) {
+                return L.part(d_segoff, nw + 1, seg_off.data()).part(d_matoff, nw + 1, mat_off.data()).bytes();
+            }));
+            TRY(upload_parts(c, S_AHC_PROB, prob_of, [&](Layout L) {
+                return L.part(d_prob, 2 * nw, prob.data()).part(d_sched, nw, sched.data()).bytes();
+            }));
+            // (the records are borrowed from the growing-window call, as in spkd_sw; nothing merges
+            // here, so they serve as the packed working copies too)
+            TRY(carve(c, scratch, S_SNAP, [&](Layout L) { return L.part(rec, 2 * nw * REC).bytes(); }));
+            TRY(carve(c, scratch, S_AHC_STATS, [&](Layout L) { return L.part(ex, 2 * nw * QREC).bytes(); }));
+            TRY(carve(c, scratch, S_AHC_LD, [&](Layout L) { return L.part(ld, 2 * nw).bytes(); }));
+            TRY(carve(c, scratch, S_AHC_AUX, [&](Layout L) { return L.part(aux, 2 * nw * AUX).bytes(); }));
+            TRY(carve(c, scratch, S_AHC_MAT, [&](Layout L) { return L.part(mat, 4 * nw).bytes(); }));
+            TRY(carve(c, scratch, S_AHC_MISC, [&](Layout L) { return L.part(smax, nw).part(smin, nw).bytes(); }));
+            HIPCHK(c, hipMemsetAsync(smax, 0x00, nw * sizeof(unsigned long long), c->stream));
+            HIPCHK(c, hipMemsetAsync(smin, 0xff, nw * sizeof(unsigned long long), c->stream));
+            auto kmat = P->kind == SPKD_GLR ? k_matrix<true> : k_matrix<false>;
+            for (int64_t w0 = 0; w0 < n_d; w0 += tile) {
+                const int64_t n = std::min(tile, n_d - w0);
+                hipLaunchKernelGGL(k_sw_window_stats, dim3((unsigned)n), dim3(STATS_TPB), 0, c->stream, d_frames,
+                                   (const int64_t*)T.begin, (const int64_t*)T.end, (const int64_t*)T.d_off, n_turns, w0,
+                                   P->winstep, wsz, rec, c->d_err);
+                to_quadrec(c, rec, 2 * n, ex);
+                cluster_prep(c, ex, 2 * n, P->kind, ld, aux);
+                hipLaunchKernelGGL(kmat, dim3((unsigned)n), dim3(MX_WAVES * WAVE), 0, c->stream, (const double*)ex,
+                                   (const double*)rec, (const int64_t*)d_segoff, (const int32_t*)d_prob,
+                                   (const int32_t*)d_sched, 1, P->kind, P->lambdac, (const double*)ld, (const double*)aux,
+                                   mat, (const int64_t*)d_matoff, smax, smin, c->d_err);
+                hipLaunchKernelGGL(k_take_pair_distance, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
+                                   (const double*)mat, n, (double*)d_dist + w0);
+                HIPCHK(c, hipGetLastError());
+            }
+        }
+        TRY(sw_runs_enqueue(c, (const double*)d_dist, T, n_turns, h_ev_off[n_turns], P, out));
+    }
+    if (h_d && n_d > 0)
+        HIPCHK(c, hipMemcpyAsync(h_d, d_dist, (size_t)n_d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     return call.finish();
 }
 

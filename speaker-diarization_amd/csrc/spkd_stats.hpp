@@ -29,6 +29,7 @@ constexpr int STATS_CHUNK = 1024;     // frames per chunk (host splits ranges)
 constexpr int SB = 4;                 // register block: each lane owns a 4 x 4 block of entries
 constexpr int SNB = DA / SB;          // 10 block rows / columns
 constexpr int SBLOCKS = SNB * (SNB + 1) / 2;   // 55 upper-triangular blocks per wave
+constexpr int STATS_ENTRIES = (REC + STATS_TPB - 1) / STATS_TPB;   // record entries per thread
 
 // Register-blocked accumulation: a wave covers the whole 40 x 40 upper triangle with
 // 55 lanes, each holding a 4 x 4 block of fp64 accumulators; per frame a lane reads
@@ -37,13 +38,15 @@ constexpr int SBLOCKS = SNB * (SNB + 1) / 2;   // 55 upper-triangular blocks per
 // instead of 5 for the one-entry-per-thread form.  The four waves of the workgroup
 // take every fourth frame of the tile; their partial blocks are summed through LDS
 // in wave order at the end (deterministic).
-__global__ __launch_bounds__(STATS_TPB) void k_chunk_stats(
-        const float* __restrict__ frames, const Chunk* __restrict__ chunks,
-        double* __restrict__ partial) {
-    __shared__ double xs[STATS_TILE][DA];                       // 20 KB
-    __shared__ double part[STATS_WAVES][SBLOCKS][SB * SB];      // 28 KB
+//
+// The body, for the workgroup's STATS_TPB threads: the moment sums of the `len` >= 1 frames from
+// `begin` on; thread tid gets entry e = tid + k * STATS_TPB of the packed record as emit(k, e, v),
+// k < STATS_ENTRIES.  xs / part: the workgroup's LDS; a second call may follow behind a barrier.
+template <class Emit>
+__device__ __forceinline__ void chunk_stats_accumulate(
+        const float* __restrict__ frames, int64_t begin, int len,
+        double (&xs)[STATS_TILE][DA], double (&part)[STATS_WAVES][SBLOCKS][SB * SB], Emit emit) {
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
-    const Chunk ch = chunks[blockIdx.x];
     // lane -> block (bi <= bj)
     int bi = 0, rem = lane < SBLOCKS ? lane : 0;
     while (rem >= SNB - bi) { rem -= SNB - bi; ++bi; }
@@ -53,7 +56,7 @@ __global__ __launch_bounds__(STATS_TPB) void k_chunk_stats(
     for (int a = 0; a < SB; ++a)
 #pragma unroll
         for (int b = 0; b < SB; ++b) acc[a][b] = 0.0;
-    const float* base = frames + ch.begin * (int64_t)D;
+    const float* base = frames + begin * (int64_t)D;
     // software pipeline: the floats of tile k+1 are loaded into registers while tile k
     // is being accumulated, so the global latency is paid once per chunk, not per tile
     constexpr int PF = (STATS_TILE * D + STATS_TPB - 1) / STATS_TPB;      // 10 floats per thread
@@ -66,7 +69,7 @@ __global__ __launch_bounds__(STATS_TPB) void k_chunk_stats(
     }
     float pf[PF];
     auto issue = [&](int t0) {
-        const int tl = min(STATS_TILE, ch.len - t0);
+        const int tl = min(STATS_TILE, len - t0);
         const float* src = base + (int64_t)t0 * D;
 #pragma unroll
         for (int k = 0; k < PF; ++k) {
@@ -76,14 +79,14 @@ __global__ __launch_bounds__(STATS_TPB) void k_chunk_stats(
     };
     issue(0);
     double* xsf = &xs[0][0];
-    for (int t0 = 0; t0 < ch.len; t0 += STATS_TILE) {
-        const int tl = min(STATS_TILE, ch.len - t0);
+    for (int t0 = 0; t0 < len; t0 += STATS_TILE) {
+        const int tl = min(STATS_TILE, len - t0);
 #pragma unroll
         for (int k = 0; k < PF; ++k)
             if (tid + STATS_TPB * k < STATS_TILE * D) xsf[loff[k]] = (double)pf[k];
         if (tid < STATS_TILE) xs[tid][D] = 1.0;
         __syncthreads();
-        if (t0 + STATS_TILE < ch.len) issue(t0 + STATS_TILE);
+        if (t0 + STATS_TILE < len) issue(t0 + STATS_TILE);
         for (int f = wave; f < tl; f += STATS_WAVES) {
             double xi[SB], xj[SB];
 #pragma unroll
@@ -102,18 +105,31 @@ __global__ __launch_bounds__(STATS_TPB) void k_chunk_stats(
             for (int b = 0; b < SB; ++b) part[wave][lane][a * SB + b] = acc[a][b];
     }
     __syncthreads();
-    double* out = partial + (int64_t)blockIdx.x * REC;
-    for (int e = tid; e < REC; e += STATS_TPB) {
-        int r, c;
-        decode_entry(e, r, c);
-        const int pbi = r / SB, pbj = c / SB;
-        const int blk = pbi * SNB - (pbi * (pbi - 1)) / 2 + (pbj - pbi);
-        const int w = (r % SB) * SB + (c % SB);
-        double v = part[0][blk][w];
 #pragma unroll
-        for (int q = 1; q < STATS_WAVES; ++q) v += part[q][blk][w];
-        out[e] = v;
+    for (int k = 0; k < STATS_ENTRIES; ++k) {
+        const int e = tid + k * STATS_TPB;
+        if (e < REC) {
+            int r, c;
+            decode_entry(e, r, c);
+            const int pbi = r / SB, pbj = c / SB;
+            const int blk = pbi * SNB - (pbi * (pbi - 1)) / 2 + (pbj - pbi);
+            const int w = (r % SB) * SB + (c % SB);
+            double v = part[0][blk][w];
+#pragma unroll
+            for (int q = 1; q < STATS_WAVES; ++q) v += part[q][blk][w];
+            emit(k, e, v);
+        }
     }
+}
+
+__global__ __launch_bounds__(STATS_TPB) void k_chunk_stats(
+        const float* __restrict__ frames, const Chunk* __restrict__ chunks,
+        double* __restrict__ partial) {
+    __shared__ double xs[STATS_TILE][DA];                       // 20 KB
+    __shared__ double part[STATS_WAVES][SBLOCKS][SB * SB];      // 28 KB
+    const Chunk ch = chunks[blockIdx.x];
+    double* out = partial + (int64_t)blockIdx.x * REC;
+    chunk_stats_accumulate(frames, ch.begin, ch.len, xs, part, [&](int, int e, double v) { out[e] = v; });
 }
 
 // set s owns chunks [set_chunk_off[s], set_chunk_off[s+1])

@@ -22,7 +22,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_set_stats', 'spkd_pair_terms',
            'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_mfcc',
-           'spkd_sw_window_count', 'spkd_sw', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
+           'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi']
 
@@ -180,6 +180,8 @@ def load_library(path=None):
     lib.spkd_sw_window_count.argtypes = [i64, dbl, dbl]
     lib.spkd_sw_window_count.restype = i64
     lib.spkd_sw.argtypes = [vp, vp, i64, vp, vp, i64, P(CdParams), vp, vp]
+    lib.spkd_sw_runs.argtypes = [vp, vp, vp, i64, P(CdParams), vp] + [vp] * 10
+    lib.spkd_sw_batch.argtypes = [vp, vp, i64, vp, vp, i64, P(CdParams), vp, vp, i64] + [vp] * 11
     lib.spkd_ahc.argtypes = [vp, vp, vp, i64, P(AhcParams), vp, vp, vp, vp, vp, vp]
     lib.spkd_ahc_matrix.argtypes = [vp, vp, i64, P(AhcParams), vp, dbl, dbl, vp, vp, vp, vp, vp, vp]
     lib.spkd_distance_rows.argtypes = [vp, C.c_int, C.c_int, dbl, vp, i64, i64, i64, vp, P(dbl), P(dbl)]
@@ -586,6 +588,61 @@ class Context(object):
                               C.byref(params), _ptr(off), _ptr(d))
         self.check(st, allow=(SPKD_ENONFINITE,))
         return st, off, d
+
+    @staticmethod
+    def _sw_outputs(d_off, ev_off):
+        """ev_off (None: the bound, windows // 2 + 1 slots per turn) and the output arrays of the
+        positive-run pass, in the order the two calls take them."""
+        nt = len(d_off) - 1
+        if ev_off is None:
+            ev_off = np.zeros(nt + 1, dtype=np.int64)
+            ev_off[1:] = np.cumsum(np.diff(d_off) // 2 + 1)
+        ev_off = np.ascontiguousarray(ev_off, dtype=np.int64)
+        if len(ev_off) != nt + 1:
+            raise SpkdError(SPKD_EINVAL, 'one event offset per turn and the total')
+        nev = max(int(ev_off[-1]), 0)
+        out = dict(n_det=np.zeros(nt, dtype=np.int32), det_start=np.zeros(nev), det_maxi=np.zeros(nev),
+                   det_d=np.zeros(nev), final_start=np.zeros(nt), win_cnt=np.zeros(nt, dtype=np.int64),
+                   win_max=np.zeros(nt), win_min=np.zeros(nt), det_max=np.zeros(nt), det_min=np.zeros(nt))
+        return ev_off, out
+
+    def sw_runs(self, d_dist, d_off, params, ev_off=None):
+        """The positive-run pass of dist_sw (spkd_sw_runs) over the device array d_dist, turn t
+        owning [d_off[t], d_off[t+1]) -> dict: off (event offsets), n_det, final_start and the
+        summary counters per turn, det_start / det_maxi / det_d per event slot, status."""
+        d_off = np.ascontiguousarray(d_off, dtype=np.int64)
+        if d_off.ndim != 1 or len(d_off) < 1:
+            raise SpkdError(SPKD_EINVAL, 'd_off: one entry per turn and the total')
+        ev_off, out = self._sw_outputs(d_off, ev_off)
+        st = self.lib.spkd_sw_runs(self.h, C.c_void_p(d_dist), _ptr(d_off), len(d_off) - 1, C.byref(params),
+                                   _ptr(ev_off), *[_ptr(a) for a in out.values()])
+        self.check(st)
+        return dict(out, status=st, off=ev_off, d_off=d_off)
+
+    def sw_batch(self, d_frames, n_frames, begins, ends, params, tile_windows=0, want_d=False, d_off=None,
+                 ev_off=None):
+        """Sliding-window change detection of every turn in one call (spkd_sw_batch): the result
+        of sw_runs over the distances of sw(), which stay on the device unless want_d ('d').
+        d_off / ev_off: None for the window counts / the bound (tests pass their own)."""
+        b = np.ascontiguousarray(begins, dtype=np.int64)
+        e = np.ascontiguousarray(ends, dtype=np.int64)
+        nt = len(b)
+        if d_off is None:
+            cnt = [self.lib.spkd_sw_window_count(int(n), params.winsize, params.winstep) for n in (e - b).tolist()]
+            if any(c < 0 for c in cnt):
+                raise SpkdError(SPKD_EINVAL, 'window size and step must be at least one frame')
+            d_off = np.zeros(nt + 1, dtype=np.int64)
+            d_off[1:] = np.cumsum(cnt)
+        d_off = np.ascontiguousarray(d_off, dtype=np.int64)
+        if len(d_off) != nt + 1:
+            raise SpkdError(SPKD_EINVAL, 'one window offset per turn and the total')
+        ev_off, out = self._sw_outputs(d_off, ev_off)
+        d = np.zeros(max(int(d_off[-1]), 0), dtype=np.float64) if want_d else None
+        st = self.lib.spkd_sw_batch(self.h, C.c_void_p(d_frames), n_frames, _ptr(b), _ptr(e), nt, C.byref(params),
+                                    _ptr(d_off), _ptr(ev_off), int(tile_windows), *[_ptr(a) for a in out.values()],
+                                    None if d is None else _ptr(d))
+        self.check(st, allow=(SPKD_ENONFINITE,))
+        return dict(out, status=st, off=ev_off, d_off=d_off, d=d)
 
     # ---- (6)
     def mfcc(self, d_pcm, n_samples, params, melfb, dct, mean, scale, transform, d_features):

@@ -20,6 +20,8 @@ from .recipe import py2_float_str
 
 DIA2_CD = dict(kind='BIC', lambdac=1.0, threshold=0.0, winsize_s=1.0, winstep_s=3.0, deltaws_s=0.1)
 DIA2_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
+# the change-detection script's own defaults: -m sw -d GLR -w 5.0 -st 0.5 (spk-change-detection.py:499-532)
+SW_CD = dict(method='sw', kind='GLR', lambdac=1.3, threshold=0.0, winsize_s=5.0, winstep_s=0.5, deltaws_s=0.05)
 
 
 class BatchFile(object):
@@ -79,6 +81,25 @@ def _method(cl):
     if m not in ('hi', 'in'):
         raise ValueError('cl method: hi or in')
     return m
+
+
+def _cd_method(cd):
+    """The change-detection mode of a `cd` dictionary: 'gw' (dist_gw, also when the key is
+    absent) or 'sw' (dist_sw)."""
+    m = cd.get('method', 'gw')
+    if m not in ('gw', 'sw'):
+        raise ValueError('cd method: gw or sw')
+    return m
+
+
+def _sw_done(ctx, timings, tb, te, r):
+    """After a sliding-window call (sw_batch result r), as _detector_done."""
+    if timings is not None:
+        timings.setdefault('sw', []).append(ctx.last_ms('sw'))
+        timings['sw_frames'] = int((te - tb).sum())
+        timings['sw_windows'] = int(r['d_off'][-1])
+    if r['status'] == hipabi.SPKD_ENONFINITE:
+        raise ValueError('array must not contain infs or NaNs')
 
 
 def _detector_done(ctx, timings, tb, te, r):
@@ -168,7 +189,14 @@ def change_detect_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_
     edge can land one frame away.
     fused: a list; when given, the detector also leaves the statistics record of every
     segment on the device (spkd_gw_fused) and a FusedStats is appended to the list, so that
-    cluster_batch does not read the frames a second time."""
+    cluster_batch does not read the frames a second time.
+    cd['method'] = 'sw': the sliding double window (dist_sw) instead of the growing one, every
+    turn of every file in one call (spkd_sw_batch: distances and the positive-run pass on the
+    device); no fused records.  kind 'BIC' follows the script there: it raises on
+    the first turn that has a window, and writes every turn as one line when none has."""
+    method = _cd_method(cd)
+    if method == 'sw' and fused is not None:
+        raise ValueError('the sliding window leaves no fused records: cd method sw takes fused=None')
     rate = float(rate)
     _t0 = time.perf_counter()
     table = _turn_table(files, rate)
@@ -177,6 +205,20 @@ def change_detect_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_
     owner, _, _, ls, le, tb, te = table
     p = _cd_params(cd, rate)
     _t1 = time.perf_counter()
+    if method == 'sw':
+        if cd['kind'] == 'BIC':
+            if bool((2 * p.winsize <= (te - tb)).any()):
+                raise ValueError('array must not contain infs or NaNs')
+            nt = len(tb)
+            off = np.arange(nt + 1, dtype=np.int64)
+            nd, ds, dm, fs = np.zeros(nt, dtype=np.int32), np.zeros(nt), np.zeros(nt), np.zeros(nt)
+        else:
+            r = ctx.sw_batch(d_frames, total_frames, tb, te, p)
+            _sw_done(ctx, timings, tb, te, r)
+            off, nd, ds, dm, fs = r['off'], r['n_det'], r['det_start'], r['det_maxi'], r['final_start']
+        _t2 = time.perf_counter()
+        lines = hipabi.gw_lines(off[:-1], nd, ds, dm, fs, ls, le, tb, te, rate, text_contract=text_contract)
+        return _lines_per_file(lines, owner, len(files), timings, _t0, _t1, _t2)
     seg_buf = {}
 
     def seg_alloc(n_rec):
@@ -196,14 +238,20 @@ def change_detect_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_
     # tail line; times as the script computes them, through the 12-digit text round trip
     lines = hipabi.gw_lines(off[:-1], nd, r['det_start'], r['det_maxi'], r['final_start'], ls, le, tb, te, rate,
                             text_contract=text_contract, want_frames=fused is not None)
-    rt, line_turn = lines['times'], lines['turn']
     if fused is not None:
         # the frames each record covers: [int(start), int(start + maxi)) of the turn for a
         # detection, [int(final start), turn end) for the tail
         fused.append(FusedStats(seg_buf['p'], seg_buf['n'], lines['index'], lines['frame_b'], lines['frame_e']))
+    return _lines_per_file(lines, owner, len(files), timings, _t0, _t1, _t2)
+
+
+def _lines_per_file(lines, owner, n_files, timings, _t0, _t1, _t2):
+    """The (start_s, end_s) lists of change_detect_batch from a gw_lines result, and the wall
+    times of its three phases."""
+    rt, line_turn = lines['times'], lines['turn']
     line_file = owner[line_turn]
-    bounds = np.searchsorted(line_file, np.arange(len(files) + 1))
-    out = [rt[bounds[i]:bounds[i + 1]] for i in range(len(files))]
+    bounds = np.searchsorted(line_file, np.arange(n_files + 1))
+    out = [rt[bounds[i]:bounds[i + 1]] for i in range(n_files)]
     if timings is not None:
         _t3 = time.perf_counter()
         timings.setdefault('wall_cd_prepare', []).append(1e3 * (_t1 - _t0))
@@ -313,6 +361,8 @@ def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2
     rows as the host hand-off: the same records go through the same kernels.
     detail: a dict; receives the gw_batch result with its host index map ('lines') and the merge
     log per file with segments ('merges', as cluster_batch's want_merges)."""
+    if _cd_method(cd) != 'gw':
+        raise ValueError('the device hand-off is the growing window\'s: cd method gw')
     rate = float(rate)
     _t0 = time.perf_counter()
     table = _turn_table(files, rate)
@@ -365,6 +415,8 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     rows stay in input order (the script writes each line as it is decided) with the times it
     writes -- the input's, but from a file's second line on under variant 1, which casts:
     int(t * rate) / rate (clustering._cluster_in_chain).
+    cd['method'] = 'sw' detects with the sliding window (change_detect_batch): host hand-off
+    only, not fused; either clustering method.
     fused=True: the frames are read once -- the change detector leaves every segment's
     statistics record for the clustering stage (segments and labels are those of the
     two-pass form; a record differs from the two-pass one only in the order of its
@@ -373,6 +425,10 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     or 'host' (the event arrays come to the host, which builds the lines and gathers the
     records: the only form of the two-pass and text_contract=False modes)."""
     method = _method(cl)
+    if _cd_method(cd) == 'sw':
+        if fused or handoff == 'device':
+            raise ValueError('cd method sw takes the host hand-off and is not fused')
+        handoff = 'host'
     if handoff is None:
         handoff = 'device' if fused and text_contract and method == 'hi' else 'host'
     if handoff == 'device':
@@ -386,7 +442,7 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     box = [] if fused else None
     segs = change_detect_batch(ctx, d_frames, total_frames, files, rate, cd, timings, text_contract, box)
     fs = box[0] if box else None
-    if fused and fs is None:                 # no turn at all in the batch
+    if (fused and fs is None) or not any(len(s) for s in segs):      # no turn at all in the batch
         return [np.zeros((0, 3)) for _ in files]
     return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs)
 
