@@ -97,7 +97,7 @@ spkd_status spkd_memcpy_d2d(spkd_ctx *ctx, void *d_dst, const void *d_src, size_
  * the most recent call that used it. */
 enum {
     SPKD_T_CALL = 0, SPKD_T_CHUNK_STATS, SPKD_T_REDUCE_SETS, SPKD_T_PAIR_TERMS,
-    SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_N_TIMERS
+    SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE, SPKD_N_TIMERS
 };
 spkd_status spkd_last_kernel_ms(spkd_ctx *ctx, int which, float *ms);
 
@@ -394,6 +394,46 @@ spkd_status spkd_sw_batch(spkd_ctx *ctx, const float *d_frames, int64_t n_frames
                           int32_t *h_n_det, double *h_det_start, double *h_det_maxi, double *h_det_d,
                           double *h_final_start, int64_t *h_win_cnt, double *h_win_max,
                           double *h_win_min, double *h_det_max, double *h_det_min, double *h_d);
+
+/* Neighbour merge, merge_rec (spk-change-detection.py:136-177, driven by :375-394: `-m m`), for
+ * n_problems independent recipes (files) in one call, a device chain per problem.  Problem p owns
+ * the lines [h_line_off[p], h_line_off[p+1]) of the per-line arrays (h_line_off[0] = 0, n =
+ * h_line_off[n_problems]); line k covers the absolute frame range [h_line_begin[k],
+ * h_line_end[k]) of d_frames.  Each problem behaves as a run of the script on that recipe alone:
+ * `prev`, the run merged so far, is compared with the next line; its frames are
+ * features[start_first*rate : end_last*rate], so a run spans the gaps inside it, while the gap in
+ * front of the next line is not in the pooled array.  The records of all lines and all non-empty
+ * gaps come from one statistics pass (each frame read once); a run is the sum of its lines' and
+ * gaps' records.  That sum is only the spanning range when the lines of a problem neither overlap
+ * nor go backwards (begin[k+1] >= end[k]): other recipes are SPKD_EINVAL, and the caller takes the
+ * script's path for them (ChangeDetectionRun).
+ * Distances in fp64 in the script's order (bic with the frozen c1 of a problem's first step,
+ * SURVEY.md A-8; glr; kl2); a line joins the run before it when d < threshold and d is not +-inf.
+ *   h_merged[n]   1: the line joined the run before it; 0: it starts a run (a problem's first line: 0)
+ *   h_dist[n]     the distance of the step that decided the line (a problem's first line: NaN)
+ *   h_n_done[p]   lines decided; less than the problem's size: the chain stopped there
+ *   h_win_cnt / h_win_max / h_win_min [p]   the script's window counters over the problem's steps
+ *                 whose distance is not +-inf, h_det_cnt / h_det_max / h_det_min [p] over its
+ *                 merges -- started and moved as in spkd_sw_runs (maxima at 0, minima at 2^63)
+ * A step whose left side or line has no finite covariance (infs or NaNs in its frames, fewer than
+ * two frames) stops ITS problem at that step, as the reference's det raises there: the call
+ * returns SPKD_ENONFINITE with all outputs valid (h_merged -1 and h_dist NaN from that line on)
+ * and every other problem untouched.
+ * The terms of every step whose left side is a line as the recipe names it are computed ahead, in
+ * parallel; only the steps behind a merge are computed by the chain.  flags:
+ * SPKD_MERGE_NO_AHEAD skips the ahead pass (every step computes its own terms; the results are
+ * the same to the bit).  An empty problem reports 0 lines, a problem of one line that line as a
+ * run without a distance; n_problems = 0 is SPKD_OK.  A null pointer, a bad kind, an h_line_off
+ * that decreases, a range outside [0, n_frames] or with end < begin, overlapping lines, a problem
+ * of more than 65 536 lines: SPKD_EINVAL before any device work, outputs untouched. */
+#define SPKD_MERGE_NO_AHEAD 1
+spkd_status spkd_merge_batch(spkd_ctx *ctx, const float *d_frames, int64_t n_frames,
+                             int64_t n_problems, const int64_t *h_line_off,
+                             const int64_t *h_line_begin, const int64_t *h_line_end,
+                             int kind, double lambdac, double threshold, int flags,
+                             int32_t *h_merged, double *h_dist, int64_t *h_n_done,
+                             int64_t *h_win_cnt, double *h_win_max, double *h_win_min,
+                             int64_t *h_det_cnt, double *h_det_max, double *h_det_min);
 
 /* ---------------------------------------------------------------------------
  * (4) Agglomerative clustering, spk_cluster_hi

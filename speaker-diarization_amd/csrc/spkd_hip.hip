@@ -17,6 +17,7 @@
 #include "spkd_cluster.hpp"
 #include "spkd_device.hpp"
 #include "spkd_handoff.hpp"
+#include "spkd_merge.hpp"
 #include "spkd_stats.hpp"
 #include "spkd_mfcc.hpp"
 #include "spkd_vad.hpp"
@@ -1731,6 +1732,124 @@ spkd_status spkd_sw_batch(spkd_ctx* c, const float* d_frames, int64_t n_frames, 
     }
     if (h_d && n_d > 0)
         HIPCHK(c, hipMemcpyAsync(h_d, d_dist, (size_t)n_d * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    return call.finish();
+}
+
+// ---- neighbour merge for a whole batch (spkd_merge_batch)
+// One record per line and per non-empty gap between two lines of a problem, in one statistics
+// pass (each frame is read once); the lines' records first, so that every per-line array is
+// indexed like the caller's.  Then flags, the lines' own terms, the ahead pass and the chain
+// (spkd_merge.hpp).  The problems' error words are the chain's: k_cluster_prep_batch and the
+// ahead pass, which also touch lines no step reaches, get words of their own that nobody reads.
+spkd_status spkd_merge_batch(spkd_ctx* c, const float* d_frames, int64_t n_frames, int64_t n_prob,
+                             const int64_t* h_line_off, const int64_t* hb, const int64_t* he, int kind, double lambdac,
+                             double threshold, int flags, int32_t* h_merged, double* h_dist, int64_t* h_n_done,
+                             int64_t* h_win_cnt, double* h_win_max, double* h_win_min, int64_t* h_det_cnt,
+                             double* h_det_max, double* h_det_min) {
+    if (!c || n_prob < 0 || bad_kind(kind)) return SPKD_EINVAL;
+    if (n_prob == 0) return SPKD_OK;
+    if (!h_line_off || !h_n_done || !h_win_cnt || !h_win_max || !h_win_min || !h_det_cnt || !h_det_max || !h_det_min)
+        return fail(c, SPKD_EINVAL, "null argument");
+    if (h_line_off[0] != 0) return fail(c, SPKD_EINVAL, "line_off must start at 0");
+    int64_t longest = 0;
+    for (int64_t p = 0; p < n_prob; ++p) {
+        if (h_line_off[p + 1] < h_line_off[p]) return fail(c, SPKD_EINVAL, "line_off must be non-decreasing");
+        longest = std::max(longest, h_line_off[p + 1] - h_line_off[p]);
+    }
+    if (longest > 65536) return fail(c, SPKD_EINVAL, "merge_batch: a problem of more than 65 536 lines");
+    const int64_t n = h_line_off[n_prob];
+    if (n > 0x3fffffff) return fail(c, SPKD_EINVAL, "merge_batch: too many lines");
+    if (n > 0 && (!d_frames || !hb || !he || !h_merged || !h_dist)) return fail(c, SPKD_EINVAL, "null argument");
+    // ranges of the statistics pass: line k is set k, the gaps follow in line order
+    std::vector<int64_t> rb(hb, hb + n), re(he, he + n);
+    std::vector<int32_t> rs((size_t)n), gap_rec((size_t)n, -1);
+    for (int64_t p = 0; p < n_prob; ++p)
+        for (int64_t k = h_line_off[p]; k < h_line_off[p + 1]; ++k) {
+            if (hb[k] < 0 || he[k] < hb[k] || he[k] > n_frames) return fail(c, SPKD_EINVAL, "bad line range");
+            rs[(size_t)k] = (int32_t)k;
+            if (k == h_line_off[p]) continue;
+            if (hb[k] < he[k - 1]) return fail(c, SPKD_EINVAL, "merge_batch: lines of a problem overlap or go backwards");
+            if (hb[k] > he[k - 1]) {
+                gap_rec[(size_t)k - 1] = (int32_t)rs.size();
+                rs.push_back((int32_t)rs.size());
+                rb.push_back(he[k - 1]);
+                re.push_back(hb[k]);
+            }
+        }
+    const int64_t n_rec = (int64_t)rs.size();
+    const size_t nn = (size_t)n, nr = (size_t)n_rec, np = (size_t)n_prob;
+    std::vector<Chunk> chunks;
+    std::vector<int64_t> set_off;
+    std::vector<char> tables;
+    Call call(c);
+    TRY(call.opened);
+    TRY(use_kind(c, kind, &kind));
+    int64_t* d_lineoff = nullptr;
+    int32_t* d_gaprec = nullptr;
+    TRY(upload_parts(c, S_AHC_OFF, tables, [&](Layout L) {
+        return L.part(d_lineoff, np + 1, h_line_off).part(d_gaprec, nn, gap_rec.data()).bytes();
+    }));
+    double *pk, *ex, *ld, *aux;
+    TRY(carve(c, scratch, S_AHC_PACKED, [&](Layout L) { return L.part(pk, nr * REC).bytes(); }));
+    TRY(carve(c, scratch, S_AHC_STATS, [&](Layout L) { return L.part(ex, nr * QREC).bytes(); }));
+    TRY(carve(c, scratch, S_AHC_LD, [&](Layout L) { return L.part(ld, nn).bytes(); }));
+    TRY(carve(c, scratch, S_AHC_AUX, [&](Layout L) { return L.part(aux, nn * AUX).bytes(); }));
+    double *ahead, *d_dist;
+    MergeStats st;
+    long long* d_done;
+    int32_t *d_merged, *d_flags;
+    int *d_perr, *d_perr_unread;
+    // determinants of the ahead pass | distances | per problem: the four extremes, lines done, the two counts |
+    // merged | flags of all records | the problems' error words, and the words nobody reads
+    TRY(carve(c, scratch, S_STEP_MISC, [&](Layout L) {
+        return L.part(ahead, nn).part(d_dist, nn).part(st.win_max, np).part(st.win_min, np).part(st.det_max, np)
+            .part(st.det_min, np).part(d_done, np).part(st.win_cnt, np).part(st.det_cnt, np).part(d_merged, nn)
+            .part(d_flags, nr).part(d_perr, np).part(d_perr_unread, np).bytes();
+    }));
+    HIPCHK(c, hipMemsetAsync(d_perr, 0, 2 * np * sizeof(int), c->stream));
+    const bool want_ahead = n > 0 && kind != SPKD_KL2 && !(flags & SPKD_MERGE_NO_AHEAD);
+    if (n > 0) {
+        TRY(set_stats_launch(c, d_frames, n_frames, rb.data(), re.data(), rs.data(), n_rec, n_rec, pk, chunks, set_off));
+        to_quadrec(c, pk, n_rec, ex);
+        hipLaunchKernelGGL(k_merge_flags, dim3((unsigned)n_rec), dim3(WAVE), 0, c->stream, (const double*)pk, n_rec, n,
+                           d_flags);
+        {
+            Timer t(c, SPKD_T_CLUSTER_PREP);
+            const int64_t per_block = kind == SPKD_KL2 ? PT_WAVES : 4 * PT_WAVES;
+            hipLaunchKernelGGL(k_cluster_prep_batch, dim3((unsigned)n_prob, (unsigned)((longest + per_block - 1) / per_block)),
+                               dim3(PT_WAVES * WAVE), 0, c->stream, (const double*)ex, (const int64_t*)d_lineoff, kind, ld, aux,
+                               d_perr_unread, c->pinv_cur);
+        }
+        HIPCHK(c, hipGetLastError());
+    }
+    {
+        Timer t(c, SPKD_T_MERGE);
+        if (want_ahead) {
+            auto kahead = kind == SPKD_GLR ? k_merge_ahead<true> : k_merge_ahead<false>;
+            hipLaunchKernelGGL(kahead, dim3((unsigned)((n + MRG_AHEAD_WAVES - 1) / MRG_AHEAD_WAVES)),
+                               dim3(MRG_AHEAD_WAVES * WAVE), 0, c->stream, (const double*)ex, (const double*)pk,
+                               (const int64_t*)d_lineoff, n_prob, n, kind, ahead, d_perr_unread);
+        }
+        auto kchain = kind == SPKD_GLR ? k_merge_chain_batch<true> : k_merge_chain_batch<false>;
+        hipLaunchKernelGGL(kchain, dim3((unsigned)n_prob), dim3(WAVE), 0, c->stream, (const double*)ex, (const double*)pk,
+                           (const double*)ld, (const double*)aux, (const int64_t*)d_lineoff, (const int32_t*)d_gaprec,
+                           (const int32_t*)d_flags, want_ahead ? (const double*)ahead : (const double*)nullptr, kind, lambdac,
+                           threshold, d_merged, d_dist, d_done, st, d_perr, c->d_err, c->pinv_cur);
+    }
+    HIPCHK(c, hipGetLastError());
+    auto back = [&](void* h, const void* d, size_t bytes) {
+        return bytes ? hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    static_assert(sizeof(long long) == sizeof(int64_t), "counters are copied as they are");
+    HIPCHK(c, back(h_merged, d_merged, nn * sizeof(int32_t)));
+    HIPCHK(c, back(h_dist, d_dist, nn * sizeof(double)));
+    HIPCHK(c, back(h_n_done, d_done, np * sizeof(int64_t)));
+    HIPCHK(c, back(h_win_cnt, st.win_cnt, np * sizeof(int64_t)));
+    HIPCHK(c, back(h_win_max, st.win_max, np * sizeof(double)));
+    HIPCHK(c, back(h_win_min, st.win_min, np * sizeof(double)));
+    HIPCHK(c, back(h_det_cnt, st.det_cnt, np * sizeof(int64_t)));
+    HIPCHK(c, back(h_det_max, st.det_max, np * sizeof(double)));
+    HIPCHK(c, back(h_det_min, st.det_min, np * sizeof(double)));
     return call.finish();
 }
 

@@ -13,8 +13,9 @@ SPKD_OK, SPKD_EINVAL, SPKD_EHIP, SPKD_ENONFINITE, SPKD_EOVERFLOW, SPKD_ENOMEM = 
 # 'KL2P': KL2 with the reference's pseudo-inverse (SPKD_KL2_PINV); 'KL2' is the inverse
 KINDS = {'BIC': 0, 'GLR': 1, 'KL2': 2, 'KL2P': 3}
 WANT_GLR, WANT_KL2, WANT_KL2_PINV = 1, 2, 4
+MERGE_NO_AHEAD = 1
 TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pair_terms',
-                                        'cluster_prep', 'matrix', 'ahc', 'gw', 'sw'])}
+                                        'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge'])}
 REC = 820
 DIM = 39
 
@@ -22,7 +23,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_set_stats', 'spkd_pair_terms',
            'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_mfcc',
-           'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
+           'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi']
 
@@ -182,6 +183,7 @@ def load_library(path=None):
     lib.spkd_sw.argtypes = [vp, vp, i64, vp, vp, i64, P(CdParams), vp, vp]
     lib.spkd_sw_runs.argtypes = [vp, vp, vp, i64, P(CdParams), vp] + [vp] * 10
     lib.spkd_sw_batch.argtypes = [vp, vp, i64, vp, vp, i64, P(CdParams), vp, vp, i64] + [vp] * 11
+    lib.spkd_merge_batch.argtypes = [vp, vp, i64, i64, vp, vp, vp, C.c_int, dbl, dbl, C.c_int] + [vp] * 9
     lib.spkd_ahc.argtypes = [vp, vp, vp, i64, P(AhcParams), vp, vp, vp, vp, vp, vp]
     lib.spkd_ahc_matrix.argtypes = [vp, vp, i64, P(AhcParams), vp, dbl, dbl, vp, vp, vp, vp, vp, vp]
     lib.spkd_distance_rows.argtypes = [vp, C.c_int, C.c_int, dbl, vp, i64, i64, i64, vp, P(dbl), P(dbl)]
@@ -643,6 +645,31 @@ class Context(object):
                                     None if d is None else _ptr(d))
         self.check(st, allow=(SPKD_ENONFINITE,))
         return dict(out, status=st, off=ev_off, d_off=d_off, d=d)
+
+    def merge_batch(self, d_frames, n_frames, line_off, begins, ends, kind, lambdac, threshold, flags=0):
+        """merge_rec (`-m m`) for every problem of line_off in one call (spkd_merge_batch), each as
+        a run of the script on its lines alone -> dict: merged (1: the line joined the run before
+        it, 0: it starts one, -1 behind a stop) and dist per line, n_done and the script's counters
+        (win_cnt, win_max, win_min, det_cnt, det_max, det_min) per problem, status.  status is
+        SPKD_ENONFINITE when a covariance with infs or NaNs stopped a problem (n_done[p] < its
+        size); the other problems are complete.  flags: MERGE_NO_AHEAD."""
+        line_off = np.ascontiguousarray(line_off, dtype=np.int64)
+        if line_off.ndim != 1 or len(line_off) < 1:
+            raise SpkdError(SPKD_EINVAL, 'line_off: one entry per problem and the total')
+        b = np.ascontiguousarray(begins, dtype=np.int64)
+        e = np.ascontiguousarray(ends, dtype=np.int64)
+        npb = len(line_off) - 1
+        nt = max(int(line_off[-1]), 0)
+        if len(b) != nt or len(e) != nt:
+            raise SpkdError(SPKD_EINVAL, 'one frame range per line')
+        out = dict(merged=np.zeros(nt, dtype=np.int32), dist=np.full(nt, np.nan), n_done=np.zeros(npb, dtype=np.int64),
+                   win_cnt=np.zeros(npb, dtype=np.int64), win_max=np.zeros(npb), win_min=np.zeros(npb),
+                   det_cnt=np.zeros(npb, dtype=np.int64), det_max=np.zeros(npb), det_min=np.zeros(npb))
+        st = self.lib.spkd_merge_batch(self.h, C.c_void_p(d_frames), int(n_frames), npb, _ptr(line_off), _ptr(b), _ptr(e),
+                                       KINDS[kind] if isinstance(kind, str) else int(kind), float(lambdac),
+                                       float(threshold), int(flags), *[_ptr(a) for a in out.values()])
+        self.check(st, allow=(SPKD_ENONFINITE,))
+        return dict(out, status=st)
 
     # ---- (6)
     def mfcc(self, d_pcm, n_samples, params, melfb, dct, mean, scale, transform, d_features):

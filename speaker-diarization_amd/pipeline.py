@@ -22,6 +22,8 @@ DIA2_CD = dict(kind='BIC', lambdac=1.0, threshold=0.0, winsize_s=1.0, winstep_s=
 DIA2_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
 # the change-detection script's own defaults: -m sw -d GLR -w 5.0 -st 0.5 (spk-change-detection.py:499-532)
 SW_CD = dict(method='sw', kind='GLR', lambdac=1.3, threshold=0.0, winsize_s=5.0, winstep_s=0.5, deltaws_s=0.05)
+# the same script in merge mode, -m m: its second pass, over a detector's output (the window flags are unused there)
+MERGE_CD = dict(method='m', kind='GLR', lambdac=1.3, threshold=0.0, winsize_s=5.0, winstep_s=0.5, deltaws_s=0.05)
 
 
 class BatchFile(object):
@@ -85,11 +87,48 @@ def _method(cl):
 
 def _cd_method(cd):
     """The change-detection mode of a `cd` dictionary: 'gw' (dist_gw, also when the key is
-    absent) or 'sw' (dist_sw)."""
+    absent), 'sw' (dist_sw) or 'm' (merge_rec)."""
     m = cd.get('method', 'gw')
-    if m not in ('gw', 'sw'):
-        raise ValueError('cd method: gw or sw')
+    if m not in ('gw', 'sw', 'm'):
+        raise ValueError('cd method: gw, sw or m')
     return m
+
+
+def _merge_lines(files, rate):
+    """Per line of the batch, in file order, for merge mode: line_off per file, start / end
+    seconds, absolute frame range -- ChangeDetectionRun._merge_ranges' truncation and clamps.
+    Raises what the script's path raises for a file of one line, and ValueError for lines that
+    overlap or go backwards: a merged run is then not the sum of its lines and gaps, and the
+    caller takes ChangeDetectionRun."""
+    cnt = [len(f.vad) for f in files]
+    if 1 in cnt:
+        raise AttributeError("'function' object has no attribute 'prev'")
+    line_off = np.zeros(len(files) + 1, dtype=np.int64)
+    line_off[1:] = np.cumsum(cnt)
+    vad = np.concatenate([f.vad_arr for f in files])
+    owner = np.repeat(np.arange(len(files)), cnt)
+    foff = np.array([f.frame_off for f in files], dtype=np.int64)[owner]
+    fn = np.array([f.n_frames for f in files], dtype=np.int64)[owner]
+    ls, le = vad[:, 0], vad[:, 1]
+    f0 = np.clip((ls * rate).astype(np.int64), 0, fn)
+    f1 = np.clip((le * rate).astype(np.int64), 0, fn)
+    inside = owner[1:] == owner[:-1]
+    if bool((f1 < f0).any()) or bool((inside & (f0[1:] < f1[:-1])).any()):
+        raise ValueError('merge mode in a batch takes lines in time order that do not overlap')
+    return line_off, ls, le, foff + f0, foff + f1
+
+
+def _merge_done(ctx, timings, line_off, r):
+    """After a merge_batch call (result r), as _detector_done."""
+    if timings is not None:
+        timings.setdefault('merge', []).append(ctx.last_ms('merge'))
+        timings['merge_lines'] = len(r['merged'])
+        # a step is the chain's own work when the line before its line had joined a run
+        stepped = r['merged'] >= 0
+        stepped[line_off[:-1][np.diff(line_off) > 0]] = False          # (a file's first line is no step)
+        timings['merge_steps_behind_a_merge'] = int((stepped[1:] & (r['merged'][:-1] == 1)).sum())
+    if r['status'] == hipabi.SPKD_ENONFINITE:
+        raise ValueError('array must not contain infs or NaNs')
 
 
 def _sw_done(ctx, timings, tb, te, r):
@@ -190,6 +229,11 @@ def change_detect_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_
     fused: a list; when given, the detector also leaves the statistics record of every
     segment on the device (spkd_gw_fused) and a FusedStats is appended to the list, so that
     cluster_batch does not read the frames a second time.
+    cd['method'] = 'm' (MERGE_CD): the script's merge mode (merge_rec), its second pass over a
+    detector's output: every file's `vad` list is the recipe lines to merge, every file's chain in
+    one call (spkd_merge_batch); the result is the (start_s, end_s) of every run as the script
+    writes them.  No fused records.  A file of one line raises the script's AttributeError, a
+    file whose lines overlap or go backwards ValueError (ChangeDetectionRun takes those).
     cd['method'] = 'sw': the sliding double window (dist_sw) instead of the growing one, every
     turn of every file in one call (spkd_sw_batch: distances and the positive-run pass on the
     device); no fused records.  kind 'BIC' follows the script there: it raises on
@@ -197,8 +241,33 @@ def change_detect_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_
     method = _cd_method(cd)
     if method == 'sw' and fused is not None:
         raise ValueError('the sliding window leaves no fused records: cd method sw takes fused=None')
+    if method == 'm' and fused is not None:
+        raise ValueError('merge mode leaves no fused records: cd method m takes fused=None')
     rate = float(rate)
     _t0 = time.perf_counter()
+    if method == 'm':
+        if sum(len(f.vad) for f in files) == 0:
+            return [[] for _ in files]
+        line_off, ls, le, lb, lend = _merge_lines(files, rate)
+        _t1 = time.perf_counter()
+        r = ctx.merge_batch(d_frames, total_frames, line_off, lb, lend, cd['kind'], cd['lambdac'], cd['threshold'])
+        _t2 = time.perf_counter()
+        _merge_done(ctx, timings, line_off, r)
+        # a run: from the start of the line that founds it to the end of the last line that joined; the
+        # script writes prev[2] * rate and prev[3] * rate as frames with lna_start 0 (CD:175-176, :392-394)
+        first = np.nonzero(r['merged'] == 0)[0]
+        last = np.append(first[1:], len(ls)) - 1
+        rt = np.column_stack([(ls[first] * rate) / rate + 0.0, (le[last] * rate) / rate + 0.0])
+        if text_contract:
+            rt = hipabi.py2_roundtrip(rt.ravel()).reshape(-1, 2)
+        bounds = np.searchsorted(first, line_off)
+        out = [rt[bounds[i]:bounds[i + 1]] for i in range(len(files))]
+        if timings is not None:
+            _t3 = time.perf_counter()
+            timings.setdefault('wall_cd_prepare', []).append(1e3 * (_t1 - _t0))
+            timings.setdefault('wall_cd_call', []).append(1e3 * (_t2 - _t1))
+            timings.setdefault('wall_cd_finish', []).append(1e3 * (_t3 - _t2))
+        return out
     table = _turn_table(files, rate)
     if table is None:
         return [[] for _ in files]
@@ -416,7 +485,8 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     writes -- the input's, but from a file's second line on under variant 1, which casts:
     int(t * rate) / rate (clustering._cluster_in_chain).
     cd['method'] = 'sw' detects with the sliding window (change_detect_batch): host hand-off
-    only, not fused; either clustering method.
+    only, not fused; either clustering method.  cd['method'] = 'm' merges the files' lines
+    instead of detecting (change_detect_batch), under the same two rules.
     fused=True: the frames are read once -- the change detector leaves every segment's
     statistics record for the clustering stage (segments and labels are those of the
     two-pass form; a record differs from the two-pass one only in the order of its
@@ -425,9 +495,9 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     or 'host' (the event arrays come to the host, which builds the lines and gathers the
     records: the only form of the two-pass and text_contract=False modes)."""
     method = _method(cl)
-    if _cd_method(cd) == 'sw':
+    if _cd_method(cd) in ('sw', 'm'):
         if fused or handoff == 'device':
-            raise ValueError('cd method sw takes the host hand-off and is not fused')
+            raise ValueError('cd method %s takes the host hand-off and is not fused' % _cd_method(cd))
         handoff = 'host'
     if handoff is None:
         handoff = 'device' if fused and text_contract and method == 'hi' else 'host'
