@@ -97,7 +97,8 @@ spkd_status spkd_memcpy_d2d(spkd_ctx *ctx, void *d_dst, const void *d_src, size_
  * the most recent call that used it. */
 enum {
     SPKD_T_CALL = 0, SPKD_T_CHUNK_STATS, SPKD_T_REDUCE_SETS, SPKD_T_PAIR_TERMS,
-    SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE, SPKD_N_TIMERS
+    SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
+    SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_N_TIMERS
 };
 spkd_status spkd_last_kernel_ms(spkd_ctx *ctx, int which, float *ms);
 
@@ -554,6 +555,42 @@ typedef struct {
 } spkd_gmm_params;
 spkd_status spkd_gmm_loglik(spkd_ctx *ctx, const float *d_features, int64_t n_frames,
                             const spkd_gmm_params *params, float *d_scores);
+
+/* The decision part of generate_exp.py for a whole batch of files on the device: the scores of
+ * n_files files concatenated frame-major, [sum T][n_states] floats as spkd_gmm_loglik leaves them
+ * for concatenated features; file f owns the frames [h_frame_off[f], h_frame_off[f+1])
+ * (h_frame_off[0] = 0, non-decreasing; a file may have no frames).
+ *
+ * spkd_vad_shift_batch: shift_dec_bord (generate_exp.py:177-186) per file, with its reshape: the
+ * file's block of T * n_states floats is read as (n_states, T), row r = flat [r T, (r + 1) T), and
+ * per column, in fp64: exp of every value, row 1 times `shift`, each divided by the sum of the rows
+ * in row order, log, rounded to float32 into the same flat position of d_out.  Naive IEEE as the
+ * reference: an underflow to 0 gives -inf, 0 / 0 NaN.  d_out may be d_scores (in place).
+ * n_states == 1 has no row 1: SPKD_EINVAL.
+ *
+ * spkd_vad_viterbi_batch: spkd_vad_viterbi for every file in one launch, a group of lanes per file,
+ * the same fp64 sums and comparisons in the same order: tokens and scores equal the host
+ * function's on the file's slice to the bit.  Out, in pinned memory of the context, valid until
+ * its next spkd_vad_viterbi_batch: (*h_tok_off)[n_files + 1], file f's tokens at [tok_off[f],
+ * tok_off[f+1]) of *h_tok_frame (first frames, relative to the file) and *h_tok_word;
+ * (*h_score)[n_files] the path scores.  A file without frames has no tokens and scores -inf.  The
+ * tokens are counted on the device first and then stored at their exact offsets: token memory is
+ * 12 bytes per token, not per frame.  Device scratch held by the context: per frame one
+ * back-pointer record of 2 bytes (n_words <= 8) or 4 bytes, each file rounded up to SPKD_VAD_TILE
+ * frames, the tile in which the kernel fetches scores and stores records.
+ * Limits as spkd_vad_viterbi; a bad count, a null pointer, a word state out of range, an
+ * h_frame_off that does not start at 0 or decreases: SPKD_EINVAL before any device work.
+ * Timers: SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK (both passes). */
+#define SPKD_VAD_TILE 32
+spkd_status spkd_vad_shift_batch(spkd_ctx *ctx, const float *d_scores, int64_t n_files,
+                                 const int64_t *h_frame_off, int32_t n_states, double shift,
+                                 float *d_out);
+spkd_status spkd_vad_viterbi_batch(spkd_ctx *ctx, const float *d_scores, int64_t n_files,
+                                   const int64_t *h_frame_off, int32_t n_states, int32_t n_words,
+                                   const int32_t *h_word_state, const double *h_stay,
+                                   const double *h_exit, const double *h_enter,
+                                   const int64_t **h_tok_off, const int64_t **h_tok_frame,
+                                   const int32_t **h_tok_word, const double **h_score);
 
 /* ---------------------------------------------------------------------------
  * (5) Host-side helpers of the boundary (no GPU work).

@@ -21,13 +21,14 @@
 #include "spkd_stats.hpp"
 #include "spkd_mfcc.hpp"
 #include "spkd_vad.hpp"
+#include "spkd_vad_batch.hpp"
 
 using namespace spkd;
 
 namespace {
-constexpr int N_SLOTS = 40;
-// pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused)
-enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, N_PIN };
+constexpr int N_SLOTS = 48;
+// pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused) and of spkd_vad_viterbi_batch
+enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, N_PIN };
 }
 
 struct spkd_ctx {
@@ -253,7 +254,7 @@ enum {
     S_GW_N_WIN, S_GW_WIN_DET, S_GW_WIN_MAXD, S_GW_DET_START, S_GW_DET_MAXI, S_GW_DET_D, S_GW_FINAL_START, S_LOG,
     S_AHC_STATS, S_AHC_LD, S_AHC_AUX, S_AHC_MAT, S_AHC_MISC, S_AHC_OUT, S_AHC_OFF, S_AHC_PROB, S_AHC_PACKED, S_MFCC_TAB, S_MFCC_STATIC,
     S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX,
-    S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_COUNT
+    S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -1947,6 +1948,169 @@ spkd_status spkd_gmm_loglik(spkd_ctx* c, const float* d_features, int64_t n_fram
                        (long long)n_frames, d_mean, d_iv, d_c, (const int*)d_state_off, (const int*)d_kernel, d_lw,
                        S, d_scores);
     if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "gmm_loglik: kernel launch failed");
+    return call.finish();
+}
+
+// ------------------------------------------------------------------ (7b) the decision part for a batch
+namespace {
+static_assert(VB_TILE == SPKD_VAD_TILE, "the header states the kernels' tile");
+static_assert(VB_MAX == GM_MAX_S, "one limit for states and words");
+
+spkd_status vad_check_offsets(spkd_ctx* c, int64_t n_files, const int64_t* h_frame_off) {
+    if (n_files < 0 || !h_frame_off) return fail(c, SPKD_EINVAL, "vad batch: null frame_off or a negative file count");
+    if (h_frame_off[0] != 0) return fail(c, SPKD_EINVAL, "vad batch: frame_off must start at 0");
+    for (int64_t f = 0; f < n_files; ++f)
+        if (h_frame_off[f + 1] < h_frame_off[f]) return fail(c, SPKD_EINVAL, "vad batch: frame_off must be non-decreasing");
+    if (h_frame_off[n_files] > (int64_t)0x7fffffff * VB_SHIFT_TPB)
+        return fail(c, SPKD_EINVAL, "vad batch: too many frames in one call");
+    return SPKD_OK;
+}
+}  // namespace
+
+spkd_status spkd_vad_shift_batch(spkd_ctx* c, const float* d_scores, int64_t n_files, const int64_t* h_frame_off,
+                                 int32_t n_states, double shift, float* d_out) {
+    if (!c) return SPKD_EINVAL;
+    if (n_states < 2 || n_states > GM_MAX_S)
+        return fail(c, SPKD_EINVAL, "vad_shift_batch: 2 <= states <= 16 (the shift scales row 1)");
+    TRY(vad_check_offsets(c, n_files, h_frame_off));
+    const int64_t total = h_frame_off[n_files];
+    if (total == 0) return SPKD_OK;
+    if (!d_scores || !d_out) return fail(c, SPKD_EINVAL, "vad_shift_batch: null device buffer");
+    std::vector<char> tab;
+    Call call(c);
+    TRY(call.opened);
+    int64_t* d_off = nullptr;
+    TRY(upload_parts(c, S_VAD_TAB, tab, [&](Layout L) { return L.part(d_off, (size_t)n_files + 1, h_frame_off).bytes(); }));
+    {
+        Timer t(c, SPKD_T_VAD_SHIFT);
+        hipLaunchKernelGGL(k_vad_shift, dim3((unsigned)((total + VB_SHIFT_TPB - 1) / VB_SHIFT_TPB)), dim3(VB_SHIFT_TPB), 0,
+                           c->stream, d_scores, (const long long*)d_off, (long long)n_files, (int)n_states, shift, d_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    return call.finish();
+}
+
+namespace {
+struct VadTables {
+    int64_t *frame_off, *back_off;
+    int32_t* word_state;
+    double *stay, *exit, *enter;
+};
+struct VadFiles {                // per file, device or pinned host
+    int64_t *tok_off, *count;
+    double* score;
+    int32_t* final_word;
+};
+
+extern "C++" {
+template <int G>
+void vad_decode_launch(spkd_ctx* c, const float* d_scores, const VadTables& t, int64_t n_files, int S, int W, void* back,
+                       const VadFiles& d) {
+    typedef typename VbRecord<G>::type Rec;
+    const int64_t per_wave = WAVE / G;
+    hipLaunchKernelGGL(k_vad_viterbi<G>, dim3((unsigned)((n_files + per_wave - 1) / per_wave)), dim3(WAVE), 0, c->stream,
+                       d_scores, (const long long*)t.frame_off, (const long long*)t.back_off, (long long)n_files, S, W,
+                       (const int*)t.word_state, (const double*)t.stay, (const double*)t.exit, (const double*)t.enter,
+                       (Rec*)back, (int*)d.final_word, d.score);
+}
+
+template <class Rec, bool WRITE>
+void vad_backtrack_launch(spkd_ctx* c, const void* back, const VadTables& t, int64_t n_files, int G, const VadFiles& d,
+                          int64_t* tok_frame, int32_t* tok_word) {
+    hipLaunchKernelGGL((k_vad_backtrack<Rec, WRITE>), dim3((unsigned)((n_files + WAVE - 1) / WAVE)), dim3(WAVE), 0,
+                       c->stream, (const Rec*)back, (const long long*)t.frame_off, (const long long*)t.back_off,
+                       (long long)n_files, G, (const int*)d.final_word, (long long*)d.count, (const long long*)d.tok_off,
+                       (long long*)tok_frame, (int*)tok_word);
+}
+}  // extern "C++"
+}  // namespace
+
+spkd_status spkd_vad_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_t n_files, const int64_t* h_frame_off,
+                                   int32_t n_states, int32_t n_words, const int32_t* h_word_state, const double* h_stay,
+                                   const double* h_exit, const double* h_enter, const int64_t** h_tok_off,
+                                   const int64_t** h_tok_frame, const int32_t** h_tok_word, const double** h_score) {
+    if (!c) return SPKD_EINVAL;
+    if (!h_tok_off || !h_tok_frame || !h_tok_word || !h_score) return fail(c, SPKD_EINVAL, "vad_viterbi_batch: null output");
+    *h_tok_off = nullptr;
+    *h_tok_frame = nullptr;
+    *h_tok_word = nullptr;
+    *h_score = nullptr;
+    if (n_states < 1 || n_states > GM_MAX_S || n_words < 1 || n_words > GM_MAX_S)
+        return fail(c, SPKD_EINVAL, "vad_viterbi_batch: 1 <= states, words <= 16");
+    if (!h_word_state || !h_stay || !h_exit || !h_enter) return fail(c, SPKD_EINVAL, "vad_viterbi_batch: null argument");
+    for (int32_t j = 0; j < n_words; ++j)
+        if (h_word_state[j] < 0 || h_word_state[j] >= n_states)
+            return fail(c, SPKD_EINVAL, "vad_viterbi_batch: word state out of range");
+    TRY(vad_check_offsets(c, n_files, h_frame_off));
+    if (h_frame_off[n_files] > 0 && !d_scores) return fail(c, SPKD_EINVAL, "vad_viterbi_batch: null device buffer");
+    const size_t nf = (size_t)n_files, W = (size_t)n_words;
+    // a file's back-pointer records start at a multiple of the tile
+    std::vector<int64_t> back_off(nf + 1, 0);
+    for (size_t f = 0; f < nf; ++f)
+        back_off[f + 1] = back_off[f] + (h_frame_off[f + 1] - h_frame_off[f] + VB_TILE - 1) / VB_TILE * VB_TILE;
+    int G = 1;
+    while (G < n_words) G *= 2;
+    const size_t rec_bytes = G == 16 ? sizeof(VbRecord<16>::type) : sizeof(VbRecord<1>::type);
+    VadFiles h;                  // pinned: the results of the call
+    TRY(carve(c, pinned, PIN_VAD_FILES, [&](Layout L) {
+        return L.part(h.tok_off, nf + 1).part(h.count, nf).part(h.score, nf).part(h.final_word, nf).bytes();
+    }));
+    h.tok_off[0] = 0;
+    *h_tok_off = h.tok_off;
+    *h_score = h.score;
+    if (n_files == 0) return SPKD_OK;
+    std::vector<char> tab;
+    Call call(c);
+    TRY(call.opened);
+    VadTables t;
+    TRY(upload_parts(c, S_VAD_TAB, tab, [&](Layout L) {
+        return L.part(t.frame_off, nf + 1, h_frame_off).part(t.back_off, nf + 1, (const int64_t*)back_off.data())
+            .part(t.stay, W, h_stay).part(t.exit, W, h_exit).part(t.enter, W, h_enter).part(t.word_state, W, h_word_state)
+            .bytes();
+    }));
+    VadFiles d;
+    TRY(carve(c, scratch, S_VAD_FILES, [&](Layout L) {
+        return L.part(d.tok_off, nf + 1).part(d.count, nf).part(d.score, nf).part(d.final_word, nf).bytes();
+    }));
+    void* back = nullptr;
+    TRY(scratch(c, S_VAD_BACK, (size_t)back_off[nf] * rec_bytes, &back));
+    {
+        Timer tm(c, SPKD_T_VAD_VITERBI);
+        switch (G) {
+            case 1: vad_decode_launch<1>(c, d_scores, t, n_files, n_states, n_words, back, d); break;
+            case 2: vad_decode_launch<2>(c, d_scores, t, n_files, n_states, n_words, back, d); break;
+            case 4: vad_decode_launch<4>(c, d_scores, t, n_files, n_states, n_words, back, d); break;
+            case 8: vad_decode_launch<8>(c, d_scores, t, n_files, n_states, n_words, back, d); break;
+            default: vad_decode_launch<16>(c, d_scores, t, n_files, n_states, n_words, back, d); break;
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    int64_t *d_tok_frame = nullptr, *h_frames = nullptr;
+    int32_t *d_tok_word = nullptr, *h_words = nullptr;
+    {
+        // both passes of k_vad_backtrack and the copy of the counts between them
+        Timer tm(c, SPKD_T_VAD_BACKTRACK);
+        if (G == 16) vad_backtrack_launch<VbRecord<16>::type, false>(c, back, t, n_files, G, d, nullptr, nullptr);
+        else vad_backtrack_launch<VbRecord<1>::type, false>(c, back, t, n_files, G, d, nullptr, nullptr);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h.count, d.count, nf * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h.score, d.score, nf * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (size_t f = 0; f < nf; ++f) h.tok_off[f + 1] = h.tok_off[f] + h.count[f];
+        const size_t n_tok = (size_t)h.tok_off[nf];
+        TRY(carve(c, scratch, S_VAD_TOKENS, [&](Layout L) { return L.part(d_tok_frame, n_tok).part(d_tok_word, n_tok).bytes(); }));
+        TRY(carve(c, pinned, PIN_VAD_TOKENS, [&](Layout L) { return L.part(h_frames, n_tok).part(h_words, n_tok).bytes(); }));
+        HIPCHK(c, hipMemcpyAsync(d.tok_off, h.tok_off, (nf + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        if (G == 16) vad_backtrack_launch<VbRecord<16>::type, true>(c, back, t, n_files, G, d, d_tok_frame, d_tok_word);
+        else vad_backtrack_launch<VbRecord<1>::type, true>(c, back, t, n_files, G, d, d_tok_frame, d_tok_word);
+        HIPCHK(c, hipGetLastError());
+        if (n_tok) {
+            HIPCHK(c, hipMemcpyAsync(h_frames, d_tok_frame, n_tok * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(h_words, d_tok_word, n_tok * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    *h_tok_frame = h_frames;
+    *h_tok_word = h_words;
     return call.finish();
 }
 

@@ -128,6 +128,53 @@ def device_scores(ctx, model, pcm):
     return out
 
 
+def decode_batch(ctx, model, pcms, timings=None):
+    """The decision part of stage 1 for a batch of files, on the device: per file of int16 samples
+    the .exp token list [(first frame, word name)] and the .last_frame value.  The front-end runs
+    per file into one concatenated feature buffer (the mean-subtraction window does not cross
+    files), spkd_gmm_loglik once on the concatenation, the border shift (in place) and the decoding
+    are one call each (spkd_vad_shift_batch, spkd_vad_viterbi_batch); the scores never come to the
+    host.  Returns (tokens, last_frames)."""
+    cfg = model.cfg
+    pcms = [np.ascontiguousarray(p, dtype=np.int16) for p in pcms]
+    last_frames = [len(p) // cfg.hop for p in pcms]
+    off = np.concatenate([[0], np.cumsum(last_frames)]).astype(np.int64)
+    total = int(off[-1])
+    d_feat = ctx.dev_scratch('vad_features', max(total, 1) * cfg.dim * 4)
+    d_sc = ctx.dev_scratch('vad_scores', max(total, 1) * model.n_states * 4)
+    d_pcm = ctx.dev_scratch('vad_pcm', max([p.nbytes for p in pcms] + [16]))
+    mfcc = hipabi.MfccParams(cfg.sample_rate, cfg.frame_rate, cfg.window_width, frontend.N_FFT, frontend.N_MEL,
+                             cfg.n_cep, cfg.cms_left, cfg.cms_right, (hipabi.C.c_int32 * 2)(*cfg.delta_width),
+                             cfg.pre_emph, (hipabi.C.c_float * 2)(*cfg.delta_norm))
+    melfb, dct = frontend.mel_filterbank(cfg.sample_rate), frontend.dct_matrix(cfg.n_cep)
+    for p, o, T in zip(pcms, off, last_frames):
+        if T:
+            ctx.h2d(d_pcm, p)
+            n = ctx.mfcc(d_pcm, len(p), mfcc, melfb, dct, cfg.mean, cfg.scale, cfg.transform, d_feat + int(o) * cfg.dim * 4)
+            assert n == T
+    if total:
+        ctx.gmm_loglik(d_feat, total, model.gmm_arrays(), d_sc)
+    tokens = decode_device_scores(ctx, model, d_sc, off, timings)
+    return tokens, last_frames
+
+
+def decode_device_scores(ctx, model, d_scores, frame_off, timings=None):
+    """Border shift (in place) and decoding of concatenated device scores [sum T, S]: the .exp
+    token list [(first frame, word name)] of every file of frame_off."""
+    if int(frame_off[-1]):
+        ctx.vad_shift_batch(d_scores, frame_off, model.n_states, SHIFT_BORD)
+        if timings is not None:
+            timings.setdefault('vad_shift', []).append(ctx.last_ms('vad_shift'))
+    stay, exit_, enter = model.decoder_constants()
+    tok_off, frames, words, _ = ctx.vad_viterbi_batch(d_scores, frame_off, model.n_states, model.word_state,
+                                                      stay, exit_, enter)
+    if timings is not None and len(frame_off) > 1:
+        timings.setdefault('vad_viterbi', []).append(ctx.last_ms('vad_viterbi'))
+        timings.setdefault('vad_backtrack', []).append(ctx.last_ms('vad_backtrack'))
+    return [[(int(t), model.words[w]) for t, w in zip(frames[a:b], words[a:b])]
+            for a, b in zip(tok_off[:-1], tok_off[1:])]
+
+
 def run(recipe, lnapath, exppath, model_path, device=0):
     """Every file of the recipe: .lna (shifted), .last_frame, .exp.  Returns the lna paths."""
     lnas = get_lnas(recipe, lnapath)

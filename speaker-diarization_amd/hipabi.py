@@ -15,7 +15,9 @@ KINDS = {'BIC': 0, 'GLR': 1, 'KL2': 2, 'KL2P': 3}
 WANT_GLR, WANT_KL2, WANT_KL2_PINV = 1, 2, 4
 MERGE_NO_AHEAD = 1
 TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pair_terms',
-                                        'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge'])}
+                                        'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
+                                        'vad_shift', 'vad_viterbi', 'vad_backtrack'])}
+VAD_TILE = 32       # SPKD_VAD_TILE: frames per score / back-pointer tile of k_vad_viterbi
 REC = 820
 DIM = 39
 
@@ -25,7 +27,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_mfcc',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
-           'spkd_gmm_loglik', 'spkd_vad_viterbi']
+           'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch']
 
 
 class CdParams(C.Structure):
@@ -196,6 +198,8 @@ def load_library(path=None):
     lib.spkd_count_flags.argtypes = [vp, vp, vp, i64, vp]
     lib.spkd_gmm_loglik.argtypes = [vp, vp, i64, P(GmmParams), vp]
     lib.spkd_vad_viterbi.argtypes = [i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, P(i64), P(dbl)]
+    lib.spkd_vad_shift_batch.argtypes = [vp, vp, i64, vp, i32, dbl, vp]
+    lib.spkd_vad_viterbi_batch.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, P(vp), P(vp), P(vp), P(vp)]
     lib.spkd_gw_lines.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, dbl, C.c_int, i64, vp, vp, vp, vp, vp]
     if lib.spkd_abi_version() != 2:
         raise ImportError('libspkd_hip.so ABI version mismatch')
@@ -694,6 +698,40 @@ class Context(object):
                       *[_ptr(a[k]) for k in ('mean', 'inv_var', 'log_norm', 'state_off', 'kernel', 'log_weight')])
         self.check(self.lib.spkd_gmm_loglik(self.h, C.c_void_p(d_features), int(n_frames), C.byref(p),
                                             C.c_void_p(d_scores)))
+
+    # ---- (7b) the decision part for a batch of files
+    @staticmethod
+    def _frame_off(frame_off):
+        off = np.ascontiguousarray(frame_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1:
+            raise SpkdError(SPKD_EINVAL, 'frame_off: one entry per file and the total')
+        return off
+
+    def vad_shift_batch(self, d_scores, frame_off, n_states, shift, d_out=None):
+        """shift_dec_bord for every file of concatenated device scores [sum T, n_states]
+        (spkd_vad_shift_batch); d_out=None: in place."""
+        off = self._frame_off(frame_off)
+        self.check(self.lib.spkd_vad_shift_batch(self.h, C.c_void_p(d_scores), len(off) - 1, _ptr(off), int(n_states),
+                                                 float(shift), C.c_void_p(d_scores if d_out is None else d_out)))
+
+    def vad_viterbi_batch(self, d_scores, frame_off, n_states, word_state, stay, exit_, enter):
+        """spkd_vad_viterbi for every file of concatenated device scores in one launch
+        (spkd_vad_viterbi_batch) -> (tok_off int64 [n_files + 1], token first frames int64 (relative
+        to the file), token words int32, path scores [n_files]); copies: the library's arrays live
+        until the next call."""
+        off = self._frame_off(frame_off)
+        ws = np.ascontiguousarray(word_state, dtype=np.int32)
+        consts = [np.ascontiguousarray(a, dtype=np.float64) for a in (stay, exit_, enter)]
+        if any(len(a) != len(ws) for a in consts):
+            raise SpkdError(SPKD_EINVAL, 'one constant of each kind per word')
+        n = len(off) - 1
+        out = [C.c_void_p() for _ in range(4)]
+        self.check(self.lib.spkd_vad_viterbi_batch(self.h, C.c_void_p(d_scores), n, _ptr(off), int(n_states), len(ws),
+                                                   _ptr(ws), *[_ptr(a) for a in consts], *[C.byref(o) for o in out]))
+        tok_off = _view(out[0].value, n + 1, np.int64).copy()
+        n_tok = int(tok_off[-1])
+        return (tok_off, _view(out[1].value, n_tok, np.int64).copy(), _view(out[2].value, n_tok, np.int32).copy(),
+                _view(out[3].value, n, np.float64).copy())
 
     # ---- (4)
     def ahc(self, d_stats, seg_off, params):

@@ -47,6 +47,31 @@ class FusedStats(object):
         self.d_buf, self.n_buf, self.index, self.begin, self.end = d_buf, n_buf, index, begin, end
 
 
+def vad_batch(ctx, model, pcms, opt=None, text_contract=True, timings=None):
+    """Speech / non-speech turns of a batch of files from their int16 samples, decided on the
+    device (exp_generator.decode_batch: front-end, scores, border shift and decoding without the
+    scores leaving it), then the turn state machine of voice-detection2.py over each file's tokens.
+    One list of (start_s, end_s) per file, ready for BatchFile(..., vad=...).  With text_contract
+    the times are the ones the change detector reads back from the recipe the file path writes
+    (py2_str, 12 significant digits: spkd_py2_roundtrip)."""
+    from . import exp_generator, voice_detection
+    opt = opt or voice_detection.VadOptions()
+    _t0 = time.perf_counter()
+    tokens, last_frames = exp_generator.decode_batch(ctx, model, pcms, timings)
+    _t1 = time.perf_counter()
+    out = []
+    for toks, last in zip(tokens, last_frames):
+        turns = voice_detection.turns_from_tokens(((str(t), w) for t, w in toks), 'a', opt, lambda: str(last))
+        times = np.array([(s, e) for _, s, e in turns], dtype=np.float64).reshape(-1, 2)
+        if text_contract:
+            times = hipabi.py2_roundtrip(times.ravel()).reshape(-1, 2)
+        out.append([(float(s), float(e)) for s, e in times])
+    if timings is not None:
+        timings.setdefault('wall_vad_decode', []).append(1e3 * (_t1 - _t0))
+        timings.setdefault('wall_vad_turns', []).append(1e3 * (time.perf_counter() - _t1))
+    return out
+
+
 def _turn_table(files, rate):
     """Per VAD turn of the batch, in file order: owning file, that file's offset and length in
     the resident array, start / end seconds (views), absolute frame range -- int() truncation
