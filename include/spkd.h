@@ -98,7 +98,8 @@ spkd_status spkd_memcpy_d2d(spkd_ctx *ctx, void *d_dst, const void *d_src, size_
 enum {
     SPKD_T_CALL = 0, SPKD_T_CHUNK_STATS, SPKD_T_REDUCE_SETS, SPKD_T_PAIR_TERMS,
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
-    SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_N_TIMERS
+    SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
+    SPKD_N_TIMERS
 };
 spkd_status spkd_last_kernel_ms(spkd_ctx *ctx, int which, float *ms);
 
@@ -525,6 +526,31 @@ spkd_status spkd_mfcc(spkd_ctx *ctx, const int16_t *d_pcm, int64_t n_samples,
                       const spkd_mfcc_params *params, const float *h_melfb, const float *h_dct,
                       const float *h_mean, const float *h_scale, const float *h_transform,
                       float *d_features, int64_t *h_n_frames);
+
+/* The front-end for a whole batch of files: one table upload, one launch for the static stage of
+ * every file and one for the post stage (mean subtraction to transform), one wait at the end,
+ * whatever n_files is.  spkd_mfcc is this call with one file.
+ * Layout: file f owns the samples d_pcm[h_sample_off[f] .. h_sample_off[f+1]) (h_sample_off[0] = 0,
+ * non-decreasing; a file may be empty) and has T_f = n_f / hop frames, as spkd_mfcc counts them;
+ * h_frame_off (out, n_files + 1 entries) is the running sum of T_f, and file f's features are the
+ * rows [h_frame_off[f], h_frame_off[f+1]) of d_features, 39 floats each.  The sample offsets need
+ * not be multiples of the hop: frame t of file f is centred on sample h_sample_off[f] + t * hop.
+ * Borders: every rule of spkd_mfcc holds per file -- sample indices clamp to the file's own
+ * samples, the mean is over the file's existing frames of [t - left, t + right], delta indices
+ * clamp to [0, T_f) -- and a workgroup's tile of frames never crosses a file boundary, so nothing
+ * of a neighbouring file enters a file's features: for every file the output equals spkd_mfcc's
+ * for that file alone to the bit, for both window widths.
+ * Refusals (SPKD_EINVAL before any device work): spkd_mfcc's parameter checks, n_files < 0, a
+ * null h_sample_off / h_frame_off, offsets that do not start at 0 or decrease; null device
+ * pointers only when there is a frame.  No file, or no frame in any: SPKD_OK, h_frame_off
+ * filled, nothing launched.
+ * Device scratch held by the context: the static rows, 52 bytes per frame of the batch.
+ * Timers: SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST. */
+spkd_status spkd_mfcc_batch(spkd_ctx *ctx, const int16_t *d_pcm, int64_t n_files,
+                            const int64_t *h_sample_off /* [n_files + 1] */,
+                            const spkd_mfcc_params *params, const float *h_melfb, const float *h_dct,
+                            const float *h_mean, const float *h_scale, const float *h_transform,
+                            float *d_features, int64_t *h_frame_off /* out [n_files + 1] */);
 
 /* ---------------------------------------------------------------------------
  * (7) Speech / non-speech frame scoring: the per-frame state log-likelihoods that AaltoASR's

@@ -20,6 +20,7 @@
 #include "spkd_merge.hpp"
 #include "spkd_stats.hpp"
 #include "spkd_mfcc.hpp"
+#include "spkd_mfcc_batch.hpp"
 #include "spkd_vad.hpp"
 #include "spkd_vad_batch.hpp"
 
@@ -252,7 +253,7 @@ struct Timer {
 enum {
     S_CHUNKS = 0, S_SETOFF, S_PARTIAL, S_IDXA, S_IDXB, S_TERMS, S_TURNS, S_SNAP, S_CAND,
     S_GW_N_WIN, S_GW_WIN_DET, S_GW_WIN_MAXD, S_GW_DET_START, S_GW_DET_MAXI, S_GW_DET_D, S_GW_FINAL_START, S_LOG,
-    S_AHC_STATS, S_AHC_LD, S_AHC_AUX, S_AHC_MAT, S_AHC_MISC, S_AHC_OUT, S_AHC_OFF, S_AHC_PROB, S_AHC_PACKED, S_MFCC_TAB, S_MFCC_STATIC,
+    S_AHC_STATS, S_AHC_LD, S_AHC_AUX, S_AHC_MAT, S_AHC_MISC, S_AHC_OUT, S_AHC_OFF, S_AHC_PROB, S_AHC_PACKED, S_MFCC_TAB, S_MFCC_STATIC, S_MFCC_TW,
     S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX,
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_COUNT
 };
@@ -1855,13 +1856,11 @@ spkd_status spkd_merge_batch(spkd_ctx* c, const float* d_frames, int64_t n_frame
 }
 
 // ------------------------------------------------------------------ (6) front-end
-spkd_status spkd_mfcc(spkd_ctx* c, const int16_t* d_pcm, int64_t n_samples, const spkd_mfcc_params* P,
-                      const float* h_melfb, const float* h_dct, const float* h_mean, const float* h_scale,
-                      const float* h_transform, float* d_features, int64_t* h_n_frames) {
-    if (!c || !P || !h_n_frames) return SPKD_EINVAL;
-    *h_n_frames = 0;
-    if (n_samples < 0 || !h_melfb || !h_dct || !h_mean || !h_scale || !h_transform)
-        return fail(c, SPKD_EINVAL, "mfcc: null argument");
+namespace {
+// what spkd_mfcc and spkd_mfcc_batch refuse alike; out: the hop and k_mfcc_post's LDS bytes
+spkd_status mfcc_check(spkd_ctx* c, const spkd_mfcc_params* P, const float* h_melfb, const float* h_dct,
+                       const float* h_mean, const float* h_scale, const float* h_transform, int* hop, size_t* lds) {
+    if (!P || !h_melfb || !h_dct || !h_mean || !h_scale || !h_transform) return fail(c, SPKD_EINVAL, "mfcc: null argument");
     if ((P->window_width != MF_WIN && P->window_width != MF_WIN_VAD) || P->n_fft != MF_NFFT || P->n_mel != MF_MEL ||
         P->n_cep != MF_CEP || P->frame_rate <= 0 || P->sample_rate <= 0 || P->sample_rate % P->frame_rate != 0)
         return fail(c, SPKD_EINVAL, "mfcc: this build does 400- or 256-sample windows, a 512-point transform, 21 mel bins, 12 cepstra");
@@ -1869,39 +1868,102 @@ spkd_status spkd_mfcc(spkd_ctx* c, const int16_t* d_pcm, int64_t n_samples, cons
         P->delta_width[0] > 2 || P->delta_width[1] < 1 || P->delta_width[1] > 2 || !(P->delta_norm[0] > 0.f) ||
         !(P->delta_norm[1] > 0.f))
         return fail(c, SPKD_EINVAL, "mfcc: unsupported mean-subtraction window or delta parameters");
-    const int hop = P->sample_rate / P->frame_rate;
-    if (hop < 1) return fail(c, SPKD_EINVAL, "mfcc: frame rate above the sample rate");
-    // everything that can be refused is refused before the call opens: a refusal enqueues nothing
+    *hop = P->sample_rate / P->frame_rate;
+    if (*hop < 1) return fail(c, SPKD_EINVAL, "mfcc: frame rate above the sample rate");
     const int span = MP_FR + 2 * MP_HALO;
-    const size_t lds = (size_t)((span + P->cms_left + P->cms_right) * MF_STATIC + 2 * span * MF_STATIC +
-                                MP_FR * MF_DIM + MF_DIM * MF_DIM) * sizeof(float);
-    if (lds > 60 * 1024) return fail(c, SPKD_EINVAL, "mfcc: mean-subtraction window too wide for the LDS tile");
-    const int64_t T = n_samples / hop;
-    *h_n_frames = T;
-    if (T == 0) return SPKD_OK;
+    *lds = (size_t)((span + P->cms_left + P->cms_right) * MF_STATIC + 2 * span * MF_STATIC + MP_FR * MF_DIM +
+                    MF_DIM * MF_DIM) * sizeof(float);
+    if (*lds > 60 * 1024) return fail(c, SPKD_EINVAL, "mfcc: mean-subtraction window too wide for the LDS tile");
+    return SPKD_OK;
+}
+
+extern "C++" {
+template <int WIN>
+void mfcc_static_launch(spkd_ctx* c, unsigned tiles, const int16_t* d_pcm, const int64_t* d_soff, const int64_t* d_foff,
+                        const int64_t* d_tiles, int64_t n_files, int hop, float pre_emph, float2* d_tw, void* d_ham,
+                        const float* d_fb, const float* d_dct, float* d_static) {
+    hipLaunchKernelGGL(k_mfcc_tables<WIN>, dim3(1), dim3(MF_NFFT), 0, c->stream, d_tw, (double*)d_ham);
+    Timer t(c, SPKD_T_MFCC_STATIC);
+    hipLaunchKernelGGL(k_mfcc_static<WIN>, dim3(tiles), dim3(MF_STATIC_TPB), 0, c->stream, d_pcm, (const long long*)d_soff,
+                       (const long long*)d_foff, (const long long*)d_tiles, (long long)n_files, hop, pre_emph,
+                       (const float2*)d_tw, (const double*)d_ham, d_fb, d_dct, d_static);
+}
+}  // extern "C++"
+}  // namespace
+
+spkd_status spkd_mfcc_batch(spkd_ctx* c, const int16_t* d_pcm, int64_t n_files, const int64_t* h_sample_off,
+                            const spkd_mfcc_params* P, const float* h_melfb, const float* h_dct, const float* h_mean,
+                            const float* h_scale, const float* h_transform, float* d_features, int64_t* h_frame_off) {
+    if (!c) return SPKD_EINVAL;
+    int hop = 0;
+    size_t lds = 0;
+    TRY(mfcc_check(c, P, h_melfb, h_dct, h_mean, h_scale, h_transform, &hop, &lds));
+    if (n_files < 0 || !h_sample_off || !h_frame_off)
+        return fail(c, SPKD_EINVAL, "mfcc_batch: null sample_off / frame_off or a negative file count");
+    if (h_sample_off[0] != 0) return fail(c, SPKD_EINVAL, "mfcc_batch: sample_off must start at 0");
+    for (int64_t f = 0; f < n_files; ++f)
+        if (h_sample_off[f + 1] < h_sample_off[f]) return fail(c, SPKD_EINVAL, "mfcc_batch: sample_off must be non-decreasing");
+    // the frame layout, and per stage the running count of tiles: a tile lies in one file
+    const size_t n1 = (size_t)n_files + 1;
+    std::vector<int64_t> static_tiles(n1, 0), post_tiles(n1, 0);
+    h_frame_off[0] = 0;
+    for (int64_t f = 0; f < n_files; ++f) {
+        const int64_t T = (h_sample_off[f + 1] - h_sample_off[f]) / hop;
+        h_frame_off[f + 1] = h_frame_off[f] + T;
+        static_tiles[(size_t)f + 1] = static_tiles[(size_t)f] + (T + MF_FR - 1) / MF_FR;
+        post_tiles[(size_t)f + 1] = post_tiles[(size_t)f] + (T + MP_FR - 1) / MP_FR;
+    }
+    const int64_t total = h_frame_off[n_files];
+    if (total == 0) return SPKD_OK;
     if (!d_pcm || !d_features) return fail(c, SPKD_EINVAL, "mfcc: null device buffer");
+    if (static_tiles[(size_t)n_files] > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "mfcc_batch: too many frames in one call");
     float *d_fb, *d_dct, *d_mean, *d_scale, *d_tr;
+    int64_t *d_soff, *d_foff, *d_stiles, *d_ptiles;
+    float2* d_tw;
+    double* d_ham;                                   // (k_mfcc_tables fills these two; the table's pad entries are never used)
     std::vector<char> tab;
     Call call(c);
     TRY(call.opened);
     void* d_static = nullptr;
     TRY(upload_parts(c, S_MFCC_TAB, tab, [&](Layout L) {
         return L.part(d_fb, MF_MEL * MF_BINS, h_melfb).part(d_dct, MF_CEP * MF_MEL, h_dct).part(d_mean, MF_DIM, h_mean)
-            .part(d_scale, MF_DIM, h_scale).part(d_tr, MF_DIM * MF_DIM, h_transform).bytes();
+            .part(d_scale, MF_DIM, h_scale).part(d_tr, MF_DIM * MF_DIM, h_transform).part(d_soff, n1, h_sample_off)
+            .part(d_foff, n1, (const int64_t*)h_frame_off).part(d_stiles, n1, (const int64_t*)static_tiles.data())
+            .part(d_ptiles, n1, (const int64_t*)post_tiles.data()).bytes();
     }));
-    TRY(scratch(c, S_MFCC_STATIC, (size_t)T * MF_STATIC * sizeof(float), &d_static));
+    TRY(carve(c, scratch, S_MFCC_TW, [&](Layout L) { return L.part(d_tw, MF_TW_LEN).part(d_ham, MF_WIN).bytes(); }));
+    TRY(scratch(c, S_MFCC_STATIC, (size_t)total * MF_STATIC * sizeof(float), &d_static));
+    const unsigned tiles = (unsigned)static_tiles[(size_t)n_files];
     if (P->window_width == MF_WIN)
-        hipLaunchKernelGGL(k_mfcc_static<MF_WIN>, dim3((unsigned)((T + MF_FR - 1) / MF_FR)), dim3(MF_TPB), 0, c->stream,
-                           d_pcm, (long long)n_samples, (long long)T, hop, P->pre_emph, d_fb, d_dct, (float*)d_static);
+        mfcc_static_launch<MF_WIN>(c, tiles, d_pcm, d_soff, d_foff, d_stiles, n_files, hop, P->pre_emph, d_tw, d_ham, d_fb,
+                                   d_dct, (float*)d_static);
     else
-        hipLaunchKernelGGL(k_mfcc_static<MF_WIN_VAD>, dim3((unsigned)((T + MF_FR - 1) / MF_FR)), dim3(MF_TPB), 0,
-                           c->stream, d_pcm, (long long)n_samples, (long long)T, hop, P->pre_emph, d_fb, d_dct,
-                           (float*)d_static);
-    hipLaunchKernelGGL(k_mfcc_post, dim3((unsigned)((T + MP_FR - 1) / MP_FR)), dim3(MF_TPB), lds, c->stream,
-                       (const float*)d_static, (long long)T, P->cms_left, P->cms_right, P->delta_width[0],
-                       P->delta_norm[0], P->delta_width[1], P->delta_norm[1], d_mean, d_scale, d_tr, d_features);
+        mfcc_static_launch<MF_WIN_VAD>(c, tiles, d_pcm, d_soff, d_foff, d_stiles, n_files, hop, P->pre_emph, d_tw, d_ham,
+                                       d_fb, d_dct, (float*)d_static);
+    {
+        Timer t(c, SPKD_T_MFCC_POST);
+        hipLaunchKernelGGL(k_mfcc_post, dim3((unsigned)post_tiles[(size_t)n_files]), dim3(MF_TPB), lds, c->stream,
+                           (const float*)d_static, (const long long*)d_foff, (const long long*)d_ptiles, (long long)n_files,
+                           P->cms_left, P->cms_right, P->delta_width[0], P->delta_norm[0], P->delta_width[1],
+                           P->delta_norm[1], d_mean, d_scale, d_tr, d_features);
+    }
     if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "mfcc: kernel launch failed");
     return call.finish();
+}
+
+// the batch of one file
+spkd_status spkd_mfcc(spkd_ctx* c, const int16_t* d_pcm, int64_t n_samples, const spkd_mfcc_params* P,
+                      const float* h_melfb, const float* h_dct, const float* h_mean, const float* h_scale,
+                      const float* h_transform, float* d_features, int64_t* h_n_frames) {
+    if (!c || !P || !h_n_frames) return SPKD_EINVAL;
+    *h_n_frames = 0;
+    if (n_samples < 0) return fail(c, SPKD_EINVAL, "mfcc: null argument");
+    const int64_t sample_off[2] = {0, n_samples};
+    int64_t frame_off[2] = {0, 0};
+    const spkd_status st = spkd_mfcc_batch(c, d_pcm, 1, sample_off, P, h_melfb, h_dct, h_mean, h_scale, h_transform,
+                                           d_features, frame_off);
+    *h_n_frames = frame_off[1];
+    return st;
 }
 
 // ------------------------------------------------------------------ (7) speech / non-speech scoring

@@ -3,7 +3,7 @@ line of a recipe, speech / non-speech state scores into `<lnapath>/<base>.lna`, 
 border shift, `<exppath>/<base>.last_frame` and the decoded token stream `<exppath>/<base>.exp`.
 
   features  the model's .cfg through spkd_mfcc (frontend.extract_device; 256-sample windows
-            for the shipped VAD models), left on the device
+            for the shipped VAD models), left on the device; a batch through spkd_mfcc_batch
   scores    spkd_gmm_loglik: natural-log state likelihoods of the .gk / .mc mixtures
             (what AaltoASR's phone_probs writes, generate_exp.py:94-97)
   .lna      phone_probs's layout: 4 header bytes (the state count), one byte 4, float32
@@ -128,30 +128,21 @@ def device_scores(ctx, model, pcm):
     return out
 
 
-def decode_batch(ctx, model, pcms, timings=None):
+def decode_batch(ctx, model, pcms, timings=None, uploaded=None):
     """The decision part of stage 1 for a batch of files, on the device: per file of int16 samples
-    the .exp token list [(first frame, word name)] and the .last_frame value.  The front-end runs
-    per file into one concatenated feature buffer (the mean-subtraction window does not cross
-    files), spkd_gmm_loglik once on the concatenation, the border shift (in place) and the decoding
-    are one call each (spkd_vad_shift_batch, spkd_vad_viterbi_batch); the scores never come to the
-    host.  Returns (tokens, last_frames)."""
-    cfg = model.cfg
-    pcms = [np.ascontiguousarray(p, dtype=np.int16) for p in pcms]
-    last_frames = [len(p) // cfg.hop for p in pcms]
-    off = np.concatenate([[0], np.cumsum(last_frames)]).astype(np.int64)
+    the .exp token list [(first frame, word name)] and the .last_frame value.  One upload of the
+    samples (or `uploaded`, the (d_pcm, sample_off) pair of a frontend.upload_batch the caller
+    shares with another chain; pcms is not read then; upload_batch takes integer samples that fit
+    int16 and refuses the rest with ValueError), the front-end once for every file
+    (frontend.extract_batch: the borders are each file's own), spkd_gmm_loglik once on the
+    concatenation, the border shift (in place) and the decoding one call each
+    (spkd_vad_shift_batch, spkd_vad_viterbi_batch); the scores never come to the host.
+    Returns (tokens, last_frames)."""
+    d_pcm, sample_off = uploaded if uploaded is not None else frontend.upload_batch(ctx, pcms, timings)
+    d_feat, off = frontend.extract_batch(ctx, model.cfg, d_pcm, sample_off, timings=timings)
+    last_frames = [int(n) for n in np.diff(off)]
     total = int(off[-1])
-    d_feat = ctx.dev_scratch('vad_features', max(total, 1) * cfg.dim * 4)
     d_sc = ctx.dev_scratch('vad_scores', max(total, 1) * model.n_states * 4)
-    d_pcm = ctx.dev_scratch('vad_pcm', max([p.nbytes for p in pcms] + [16]))
-    mfcc = hipabi.MfccParams(cfg.sample_rate, cfg.frame_rate, cfg.window_width, frontend.N_FFT, frontend.N_MEL,
-                             cfg.n_cep, cfg.cms_left, cfg.cms_right, (hipabi.C.c_int32 * 2)(*cfg.delta_width),
-                             cfg.pre_emph, (hipabi.C.c_float * 2)(*cfg.delta_norm))
-    melfb, dct = frontend.mel_filterbank(cfg.sample_rate), frontend.dct_matrix(cfg.n_cep)
-    for p, o, T in zip(pcms, off, last_frames):
-        if T:
-            ctx.h2d(d_pcm, p)
-            n = ctx.mfcc(d_pcm, len(p), mfcc, melfb, dct, cfg.mean, cfg.scale, cfg.transform, d_feat + int(o) * cfg.dim * 4)
-            assert n == T
     if total:
         ctx.gmm_loglik(d_feat, total, model.gmm_arrays(), d_sc)
     tokens = decode_device_scores(ctx, model, d_sc, off, timings)

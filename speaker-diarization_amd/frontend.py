@@ -10,6 +10,7 @@ feature file (int32 dim + float32 frames, spk-change-detection.py:37-41) on stdo
 """
 import argparse
 import sys
+import time
 import wave
 
 import numpy as np
@@ -48,6 +49,13 @@ def read_wav(path):
         return np.frombuffer(w.readframes(w.getnframes()), dtype='<i2'), w.getframerate()
 
 
+def mfcc_params(cfg):
+    """The spkd_mfcc_params of a feature configuration."""
+    return hipabi.MfccParams(cfg.sample_rate, cfg.frame_rate, cfg.window_width, N_FFT, N_MEL, cfg.n_cep,
+                             cfg.cms_left, cfg.cms_right, (hipabi.C.c_int32 * 2)(*cfg.delta_width),
+                             cfg.pre_emph, (hipabi.C.c_float * 2)(*cfg.delta_norm))
+
+
 def extract_device(pcm, cfg, ctx):
     """int16 samples -> (device pointer to float32 [T, 39] features, T).  The features stay on
     the device for a later stage; the caller frees the buffer (ctx.dev_free), which is None for
@@ -60,10 +68,7 @@ def extract_device(pcm, cfg, ctx):
     d_out = ctx.dev_alloc(T * cfg.dim * 4)
     try:
         ctx.h2d(d_pcm, pcm)
-        p = hipabi.MfccParams(cfg.sample_rate, cfg.frame_rate, cfg.window_width, N_FFT, N_MEL, cfg.n_cep,
-                              cfg.cms_left, cfg.cms_right, (hipabi.C.c_int32 * 2)(*cfg.delta_width),
-                              cfg.pre_emph, (hipabi.C.c_float * 2)(*cfg.delta_norm))
-        n = ctx.mfcc(d_pcm, len(pcm), p, mel_filterbank(cfg.sample_rate), dct_matrix(cfg.n_cep), cfg.mean,
+        n = ctx.mfcc(d_pcm, len(pcm), mfcc_params(cfg), mel_filterbank(cfg.sample_rate), dct_matrix(cfg.n_cep), cfg.mean,
                      cfg.scale, cfg.transform, d_out)
         assert n == T
     except BaseException:
@@ -72,6 +77,59 @@ def extract_device(pcm, cfg, ctx):
     finally:
         ctx.dev_free(d_pcm)
     return d_out, T
+
+
+def frame_offsets(sample_off, hop):
+    """The frame layout of a batch (spkd_mfcc_batch), on the host: the file of the samples
+    [sample_off[f], sample_off[f+1]) has that many // hop frames, whatever its offset; returns
+    their running sum, int64 [n_files + 1]."""
+    off = np.asarray(sample_off, dtype=np.int64)
+    return np.concatenate([[0], np.cumsum(np.diff(off) // int(hop))]).astype(np.int64)
+
+
+def upload_batch(ctx, pcms, timings=None):
+    """The int16 samples of a batch of files, concatenated in a buffer the context keeps ->
+    (d_pcm, sample_off int64 [n_files + 1]).  Each file is copied straight to its offset on the
+    device: concatenating on the host first costs a pass over all samples that a batch of hour-long
+    files does not win back (the front-end paragraph).  Both feature chains of a batch
+    read this one upload (extract_batch).  A file is a one-dimensional array of integers that all
+    fit int16; anything else -- two dimensions, floats, a value out of range -- is a ValueError,
+    never a silent cast."""
+    _t0 = time.perf_counter()
+    files = []
+    for i, p in enumerate(pcms):
+        a = np.asarray(p)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in 'iu'):
+            raise ValueError('file %d: one-dimensional int16 samples expected, got %s %r' % (i, a.dtype, a.shape))
+        if a.size and a.dtype != np.int16 and (int(a.min()) < -32768 or int(a.max()) > 32767):
+            raise ValueError('file %d: %s samples outside the int16 range' % (i, a.dtype))
+        files.append(a.astype(np.int16, copy=False))
+    sample_off = np.concatenate([[0], np.cumsum([len(a) for a in files])]).astype(np.int64)
+    d_pcm = ctx.dev_scratch('pcm_batch', max(2 * int(sample_off[-1]), 16))
+    for a, o in zip(files, sample_off):
+        if a.size:
+            ctx.h2d(d_pcm + 2 * int(o), a)
+    if timings is not None:
+        timings.setdefault('wall_upload', []).append(1e3 * (time.perf_counter() - _t0))
+    return d_pcm, sample_off
+
+
+def extract_batch(ctx, cfg, d_pcm, sample_off, d_out=None, timings=None):
+    """Uploaded samples (upload_batch) -> (device pointer to the float32 [sum T, 39] features of
+    every file, frame_off int64 [n_files + 1]) in one call (spkd_mfcc_batch).  d_out=None: a buffer
+    the context keeps per window width, so the VAD chain and the diarization chain of one batch do
+    not share one."""
+    frame_off = frame_offsets(sample_off, cfg.hop)
+    total = int(frame_off[-1])
+    if d_out is None:
+        d_out = ctx.dev_scratch('features_w%d' % cfg.window_width, max(total, 1) * cfg.dim * 4)
+    got = ctx.mfcc_batch(d_pcm, sample_off, mfcc_params(cfg), mel_filterbank(cfg.sample_rate), dct_matrix(cfg.n_cep),
+                         cfg.mean, cfg.scale, cfg.transform, d_out)
+    assert np.array_equal(got, frame_off)
+    if timings is not None and total:
+        timings.setdefault('mfcc_static', []).append(ctx.last_ms('mfcc_static'))
+        timings.setdefault('mfcc_post', []).append(ctx.last_ms('mfcc_post'))
+    return d_out, got
 
 
 def extract(pcm, cfg, ctx=None, device=0):

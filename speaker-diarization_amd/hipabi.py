@@ -16,7 +16,7 @@ WANT_GLR, WANT_KL2, WANT_KL2_PINV = 1, 2, 4
 MERGE_NO_AHEAD = 1
 TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pair_terms',
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
-                                        'vad_shift', 'vad_viterbi', 'vad_backtrack'])}
+                                        'vad_shift', 'vad_viterbi', 'vad_backtrack', 'mfcc_static', 'mfcc_post'])}
 VAD_TILE = 32       # SPKD_VAD_TILE: frames per score / back-pointer tile of k_vad_viterbi
 REC = 820
 DIM = 39
@@ -24,7 +24,7 @@ DIM = 39
 EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_destroy', 'spkd_last_error', 'spkd_sync',
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_set_stats', 'spkd_pair_terms',
-           'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_mfcc',
+           'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_mfcc', 'spkd_mfcc_batch',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch']
@@ -180,6 +180,7 @@ def load_library(path=None):
                                    P(vp), P(vp), P(vp), P(vp), P(vp)]
     lib.spkd_gather_stats.argtypes = [vp, vp, i64, vp, vp, i64, i64, vp]
     lib.spkd_mfcc.argtypes = [vp, vp, i64, P(MfccParams), vp, vp, vp, vp, vp, vp, P(i64)]
+    lib.spkd_mfcc_batch.argtypes = [vp, vp, i64, vp, P(MfccParams), vp, vp, vp, vp, vp, vp, vp]
     lib.spkd_sw_window_count.argtypes = [i64, dbl, dbl]
     lib.spkd_sw_window_count.restype = i64
     lib.spkd_sw.argtypes = [vp, vp, i64, vp, vp, i64, P(CdParams), vp, vp]
@@ -682,6 +683,19 @@ class Context(object):
         self.check(self.lib.spkd_mfcc(self.h, C.c_void_p(d_pcm), n_samples, C.byref(params), *[_ptr(a) for a in arrs],
                                       C.c_void_p(d_features), C.byref(n)))
         return int(n.value)
+
+    def mfcc_batch(self, d_pcm, sample_off, params, melfb, dct, mean, scale, transform, d_features):
+        """The front-end for every file of concatenated device samples (spkd_mfcc_batch): file f owns
+        the samples [sample_off[f], sample_off[f+1]); its features land at the rows [frame_off[f],
+        frame_off[f+1]) of d_features.  Returns frame_off (int64, one entry per file and the total)."""
+        off = np.ascontiguousarray(sample_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1:
+            raise SpkdError(SPKD_EINVAL, 'sample_off: one entry per file and the total')
+        arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (melfb, dct, mean, scale, transform)]
+        frame_off = np.zeros(len(off), dtype=np.int64)
+        self.check(self.lib.spkd_mfcc_batch(self.h, C.c_void_p(d_pcm), len(off) - 1, _ptr(off), C.byref(params),
+                                            *[_ptr(a) for a in arrs], C.c_void_p(d_features), _ptr(frame_off)))
+        return frame_off
 
     # ---- (7)
     def gmm_loglik(self, d_features, n_frames, gmm, d_scores):

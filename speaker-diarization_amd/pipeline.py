@@ -47,17 +47,18 @@ class FusedStats(object):
         self.d_buf, self.n_buf, self.index, self.begin, self.end = d_buf, n_buf, index, begin, end
 
 
-def vad_batch(ctx, model, pcms, opt=None, text_contract=True, timings=None):
+def vad_batch(ctx, model, pcms, opt=None, text_contract=True, timings=None, uploaded=None):
     """Speech / non-speech turns of a batch of files from their int16 samples, decided on the
     device (exp_generator.decode_batch: front-end, scores, border shift and decoding without the
     scores leaving it), then the turn state machine of voice-detection2.py over each file's tokens.
     One list of (start_s, end_s) per file, ready for BatchFile(..., vad=...).  With text_contract
     the times are the ones the change detector reads back from the recipe the file path writes
-    (py2_str, 12 significant digits: spkd_py2_roundtrip)."""
+    (py2_str, 12 significant digits: spkd_py2_roundtrip).  uploaded: the samples already on the
+    device (frontend.upload_batch), as decode_batch takes them."""
     from . import exp_generator, voice_detection
     opt = opt or voice_detection.VadOptions()
     _t0 = time.perf_counter()
-    tokens, last_frames = exp_generator.decode_batch(ctx, model, pcms, timings)
+    tokens, last_frames = exp_generator.decode_batch(ctx, model, pcms, timings, uploaded)
     _t1 = time.perf_counter()
     out = []
     for toks, last in zip(tokens, last_frames):
@@ -70,6 +71,37 @@ def vad_batch(ctx, model, pcms, opt=None, text_contract=True, timings=None):
         timings.setdefault('wall_vad_decode', []).append(1e3 * (_t1 - _t0))
         timings.setdefault('wall_vad_turns', []).append(1e3 * (time.perf_counter() - _t1))
     return out
+
+
+def features_batch(ctx, cfg, pcms=None, uploaded=None, timings=None):
+    """The resident frame array of a batch from its files' int16 samples (or from `uploaded`, the
+    pair of a frontend.upload_batch): (d_frames, total_frames, frame_off), file f at the frames
+    [frame_off[f], frame_off[f+1]).  The buffer is the context's and lives until its next batch of
+    this window width."""
+    from . import frontend
+    if uploaded is None:
+        uploaded = frontend.upload_batch(ctx, pcms, timings)
+    d_frames, frame_off = frontend.extract_batch(ctx, cfg, uploaded[0], uploaded[1], timings=timings)
+    return d_frames, int(frame_off[-1]), frame_off
+
+
+def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=None, **kw):
+    """From samples to speakers for a batch of files: one upload of the int16 samples, the VAD
+    chain (vad_batch with the model's own feature configuration) and the diarization features
+    (features_batch with cfg, the fconfig.cfg chain) both from it, then diarize_batch with the
+    turns and the frames as they lie on the device.  kw: diarize_batch's text_contract, fused,
+    handoff.  Returns its rows."""
+    from . import frontend
+    if model.cfg.sample_rate != cfg.sample_rate:
+        raise ValueError('the VAD model wants %d Hz, the feature configuration %d Hz' % (model.cfg.sample_rate, cfg.sample_rate))
+    if model.cfg.hop != cfg.hop:
+        raise ValueError('the VAD model steps %d samples a frame, the feature configuration %d: one frame '
+                         'clock for the turns and the features' % (model.cfg.hop, cfg.hop))
+    uploaded = frontend.upload_batch(ctx, pcms, timings)
+    vad = vad_batch(ctx, model, None, text_contract=kw.get('text_contract', True), timings=timings, uploaded=uploaded)
+    d_frames, total, frame_off = features_batch(ctx, cfg, uploaded=uploaded, timings=timings)
+    files = [BatchFile(frame_off[f], frame_off[f + 1] - frame_off[f], vad[f]) for f in range(len(vad))]
+    return diarize_batch(ctx, d_frames, total, files, rate=float(cfg.frame_rate), cd=cd, cl=cl, timings=timings, **kw)
 
 
 def _turn_table(files, rate):
