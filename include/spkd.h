@@ -296,6 +296,24 @@ spkd_status spkd_gather_stats(spkd_ctx *ctx, const double *d_src, int64_t n_src,
                               const int64_t *h_src_index, const int64_t *h_dst_index,
                               int64_t n, int64_t n_dst, double *d_dst);
 
+/* Sums of whole records: set s owns the members h_member[h_set_off[s] .. h_set_off[s+1]), each
+ * the index of a record of d_src (n_src records), and d_dst[s] is their entry-wise fp64 sum IN
+ * MEMBER ORDER: the first member copied, every later one added to it, one chain of additions
+ * per entry -- no atomics, no tree, no reordering, so the result is bit-reproducible and equals
+ * a host loop that adds the same records in the same order (a set of one member is a copy).
+ * A record is a raw moment sum, so this is the record of the union of the members' frame sets
+ * without reading a frame: the speakers of a batch from its segments' records (the order of a
+ * set's members is the caller's, and a record may be a member of several sets).
+ * d_dst holds n_sets records and must not overlap d_src; both are 16-byte aligned.  The two
+ * index arrays go up in one copy through pinned memory the context owns.  n_sets = 0 is SPKD_OK
+ * without a launch.  A null pointer, h_set_off[0] != 0, an h_set_off that decreases, an empty
+ * set, a member outside [0, n_src), overlapping or misaligned buffers: SPKD_EINVAL before any
+ * device work, d_dst untouched.
+ * Timer: SPKD_T_REDUCE_SETS (the kernel; like k_reduce_sets it sums records into sets). */
+spkd_status spkd_sum_stats(spkd_ctx *ctx, const double *d_src, int64_t n_src,
+                           const int64_t *h_member, const int64_t *h_set_off,
+                           int64_t n_sets, double *d_dst);
+
 /* The batch hand-off: spkd_gw_fused whose results stay on the device and come back as the
  * recipe lines the change-detection script writes (spk-change-detection.py:254 a detection,
  * :288 the tail), instead of as event slots for the host to walk.  Behind k_gw, in the same

@@ -28,8 +28,9 @@ using namespace spkd;
 
 namespace {
 constexpr int N_SLOTS = 48;
-// pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused) and of spkd_vad_viterbi_batch
-enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, N_PIN };
+// pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused), of spkd_vad_viterbi_batch and of
+// spkd_sum_stats (its index arrays on their way up)
+enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, N_PIN };
 }
 
 struct spkd_ctx {
@@ -255,7 +256,7 @@ enum {
     S_GW_N_WIN, S_GW_WIN_DET, S_GW_WIN_MAXD, S_GW_DET_START, S_GW_DET_MAXI, S_GW_DET_D, S_GW_FINAL_START, S_LOG,
     S_AHC_STATS, S_AHC_LD, S_AHC_AUX, S_AHC_MAT, S_AHC_MISC, S_AHC_OUT, S_AHC_OFF, S_AHC_PROB, S_AHC_PACKED, S_MFCC_TAB, S_MFCC_STATIC, S_MFCC_TW,
     S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX,
-    S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_COUNT
+    S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -1475,6 +1476,43 @@ spkd_status spkd_gather_stats(spkd_ctx* c, const double* d_src, int64_t n_src, c
     if (h_dst_index) TRY(upload(c, S_IDXB, h_dst_index, (size_t)n, &d_di));
     hipLaunchKernelGGL(k_gather_records, dim3((unsigned)n), dim3(256), 0, c->stream, d_src,
                        (const int64_t*)d_si, (const int64_t*)d_di, n, d_dst);
+    HIPCHK(c, hipGetLastError());
+    return call.finish();
+}
+
+spkd_status spkd_sum_stats(spkd_ctx* c, const double* d_src, int64_t n_src, const int64_t* h_member,
+                           const int64_t* h_set_off, int64_t n_sets, double* d_dst) {
+    if (!c || n_sets < 0) return SPKD_EINVAL;
+    if (n_sets == 0) return SPKD_OK;
+    if (!d_src || !h_member || !h_set_off || !d_dst) return fail(c, SPKD_EINVAL, "null argument");
+    if (n_sets > 0x7fffffff) return fail(c, SPKD_EINVAL, "sum_stats: too many sets");
+    if (h_set_off[0] != 0) return fail(c, SPKD_EINVAL, "set_off must start at 0");
+    for (int64_t s = 0; s < n_sets; ++s)
+        if (h_set_off[s + 1] <= h_set_off[s])
+            return fail(c, SPKD_EINVAL, h_set_off[s + 1] < h_set_off[s] ? "set_off must be non-decreasing" : "sum_stats: an empty set");
+    const int64_t n_mem = h_set_off[n_sets];
+    for (int64_t i = 0; i < n_mem; ++i)
+        if (h_member[i] < 0 || h_member[i] >= n_src) return fail(c, SPKD_EINVAL, "sum_stats: member out of range");
+    const uintptr_t s0 = (uintptr_t)d_src, s1 = s0 + (uintptr_t)n_src * REC * sizeof(double);
+    const uintptr_t t0 = (uintptr_t)d_dst, t1 = t0 + (uintptr_t)n_sets * REC * sizeof(double);
+    if (s0 % 16 || t0 % 16) return fail(c, SPKD_EINVAL, "sum_stats: record buffers must be 16-byte aligned");
+    if (s0 < t1 && t0 < s1) return fail(c, SPKD_EINVAL, "sum_stats: the destination overlaps the source");
+    const size_t ns = (size_t)n_sets, nm = (size_t)n_mem;
+    // the two arrays as one image in pinned memory: one copy up
+    int64_t *h_off = nullptr, *h_mem = nullptr, *d_off = nullptr, *d_mem = nullptr;
+    auto parts = [&](Layout L, int64_t*& off, int64_t*& mem) { return L.part(off, ns + 1).part(mem, nm).bytes(); };
+    TRY(carve(c, pinned, PIN_SUM_IDX, [&](Layout L) { return parts(L, h_off, h_mem); }));
+    std::memcpy(h_off, h_set_off, (ns + 1) * sizeof(int64_t));
+    std::memcpy(h_mem, h_member, nm * sizeof(int64_t));
+    Call call(c);
+    TRY(call.opened);
+    TRY(carve(c, scratch, S_SUM_IDX, [&](Layout L) { return parts(L, d_off, d_mem); }));
+    HIPCHK(c, hipMemcpyAsync(d_off, h_off, (ns + 1 + nm) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    {
+        Timer t(c, SPKD_T_REDUCE_SETS);
+        hipLaunchKernelGGL(k_sum_records, dim3((unsigned)n_sets), dim3(SUM_TPB), 0, c->stream, d_src,
+                           (const int64_t*)d_mem, (const int64_t*)d_off, d_dst);
+    }
     HIPCHK(c, hipGetLastError());
     return call.finish();
 }

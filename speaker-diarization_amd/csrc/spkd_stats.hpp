@@ -145,4 +145,81 @@ __global__ __launch_bounds__(STATS_TPB) void k_reduce_sets(
     }
 }
 
+// K_sum: records -> sums of records (spkd_sum_stats).  A record is a raw moment sum, so the
+// record of a union of frame sets is the sum of their records: set s owns the members
+// member[set_off[s] .. set_off[s+1]), indices into src, and dst[s] is their entry-wise sum in
+// member order -- the first member copied, every later one added to it, one chain of fp64
+// additions per entry (no atomics, no tree: the bits are those of a host loop in that order).
+// One workgroup per set; a record is 410 double2, and thread t < 205 owns the two at t and
+// t + 205 of every record (a wave reads 1 KiB of a record at a stretch; the other 51 threads of
+// the workgroup leave at once: there is no barrier).  The members go by in batches of SUM_DEPTH
+// in two register sets that take turns: the loads of a batch are all issued before the batch
+// ahead of it is added, so the waits are counted ones and 8 to 16 loads a thread are in flight.
+// A streaming kernel: members x 6 560 B read, sets x 6 560 B written.
+constexpr int SUM_TPB = 256;
+constexpr int SUM_OWN = 2;                                        // double2 per active thread
+constexpr int SUM_LANES = REC / 2 / SUM_OWN;                      // 205 active threads
+constexpr int SUM_DEPTH = 4;                                      // members per batch
+static_assert(SUM_LANES * SUM_OWN * 2 == REC && SUM_LANES <= SUM_TPB, "a record is 205 x 2 double2");
+
+__global__ __launch_bounds__(SUM_TPB) void k_sum_records(
+        const double* __restrict__ src, const int64_t* __restrict__ member,
+        const int64_t* __restrict__ set_off, double* __restrict__ dst) {
+    const int tid = threadIdx.x;
+    if (tid >= SUM_LANES) return;
+    const int64_t s = blockIdx.x;
+    const int64_t m0 = set_off[s], m1 = set_off[s + 1];
+    auto load = [&](int64_t m, double2 (&v)[SUM_OWN]) {
+        const double2* r = reinterpret_cast<const double2*>(src + member[m] * REC);
+#pragma unroll
+        for (int k = 0; k < SUM_OWN; ++k) v[k] = r[tid + k * SUM_LANES];
+    };
+    auto fetch = [&](int64_t m, double2 (&buf)[SUM_DEPTH][SUM_OWN]) {
+#pragma unroll
+        for (int j = 0; j < SUM_DEPTH; ++j) load(m + j, buf[j]);
+    };
+    double2 acc[SUM_OWN];
+    auto add = [&](const double2 (&v)[SUM_OWN]) {
+#pragma unroll
+        for (int k = 0; k < SUM_OWN; ++k) {
+            acc[k].x += v[k].x;
+            acc[k].y += v[k].y;
+        }
+    };
+    auto add_batch = [&](const double2 (&buf)[SUM_DEPTH][SUM_OWN]) {
+#pragma unroll
+        for (int j = 0; j < SUM_DEPTH; ++j) add(buf[j]);
+    };
+    load(m0, acc);
+    int64_t m = m0 + 1;
+    const int64_t full = (m1 - m) / SUM_DEPTH;                   // whole batches behind the first member
+    if (full > 0) {
+        double2 a[SUM_DEPTH][SUM_OWN], b[SUM_DEPTH][SUM_OWN];
+        fetch(m, a);
+        int64_t k = 1;
+        for (; k + 1 < full; k += 2) {
+            fetch(m + k * SUM_DEPTH, b);
+            add_batch(a);
+            fetch(m + (k + 1) * SUM_DEPTH, a);
+            add_batch(b);
+        }
+        if (k < full) {
+            fetch(m + k * SUM_DEPTH, b);
+            add_batch(a);
+            add_batch(b);
+        } else {
+            add_batch(a);
+        }
+        m += full * SUM_DEPTH;
+    }
+    for (; m < m1; ++m) {                                        // fewer than SUM_DEPTH are left
+        double2 v[SUM_OWN];
+        load(m, v);
+        add(v);
+    }
+    double2* d = reinterpret_cast<double2*>(dst + s * REC);
+#pragma unroll
+    for (int k = 0; k < SUM_OWN; ++k) d[tid + k * SUM_LANES] = acc[k];
+}
+
 }  // namespace spkd

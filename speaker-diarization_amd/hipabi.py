@@ -24,7 +24,7 @@ DIM = 39
 EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_destroy', 'spkd_last_error', 'spkd_sync',
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_set_stats', 'spkd_pair_terms',
-           'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_mfcc', 'spkd_mfcc_batch',
+           'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_sum_stats', 'spkd_mfcc', 'spkd_mfcc_batch',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch']
@@ -179,6 +179,7 @@ def load_library(path=None):
     lib.spkd_ahc_fused.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, P(AhcParams),
                                    P(vp), P(vp), P(vp), P(vp), P(vp)]
     lib.spkd_gather_stats.argtypes = [vp, vp, i64, vp, vp, i64, i64, vp]
+    lib.spkd_sum_stats.argtypes = [vp, vp, i64, vp, vp, i64, vp]
     lib.spkd_mfcc.argtypes = [vp, vp, i64, P(MfccParams), vp, vp, vp, vp, vp, vp, P(i64)]
     lib.spkd_mfcc_batch.argtypes = [vp, vp, i64, vp, P(MfccParams), vp, vp, vp, vp, vp, vp, vp]
     lib.spkd_sw_window_count.argtypes = [i64, dbl, dbl]
@@ -468,6 +469,19 @@ class Context(object):
         self.check(self.lib.spkd_gather_stats(self.h, C.c_void_p(d_src), n_src, _ptr(si),
                                               None if di is None else _ptr(di), len(si), n_dst,
                                               C.c_void_p(d_dst)))
+
+    def sum_stats(self, d_src, n_src, member, set_off, d_dst):
+        """d_dst[s] = the sum of the records d_src[member[set_off[s] : set_off[s + 1]]], added in
+        that order (spkd_sum_stats): the record of a union of frame sets from the sets' records.
+        The kernel's time is last_ms('reduce_sets')."""
+        m = np.ascontiguousarray(member, dtype=np.int64)
+        off = np.ascontiguousarray(set_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1 or m.ndim != 1:
+            raise SpkdError(SPKD_EINVAL, 'set_off: one entry per set and the total')
+        if len(m) != int(off[-1]):
+            raise SpkdError(SPKD_EINVAL, 'one member per entry of the sets')
+        self.check(self.lib.spkd_sum_stats(self.h, C.c_void_p(d_src), int(n_src), _ptr(m), _ptr(off), len(off) - 1,
+                                           C.c_void_p(d_dst)))
 
     def gw(self, d_frames, n_frames, begins, ends, params, log_cap=4096, tight=False, reuse=False,
            seg_stats=None, first_guess_scale=1.0):

@@ -24,6 +24,8 @@ DIA2_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
 SW_CD = dict(method='sw', kind='GLR', lambdac=1.3, threshold=0.0, winsize_s=5.0, winstep_s=0.5, deltaws_s=0.05)
 # the same script in merge mode, -m m: its second pass, over a detector's output (the window flags are unused there)
 MERGE_CD = dict(method='m', kind='GLR', lambdac=1.3, threshold=0.0, winsize_s=5.0, winstep_s=0.5, deltaws_s=0.05)
+# linking the speakers of a batch's files (link_batch): the clustering script's own defaults
+LINK_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
 
 
 class BatchFile(object):
@@ -90,7 +92,7 @@ def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=Non
     chain (vad_batch with the model's own feature configuration) and the diarization features
     (features_batch with cfg, the fconfig.cfg chain) both from it, then diarize_batch with the
     turns and the frames as they lie on the device.  kw: diarize_batch's text_contract, fused,
-    handoff.  Returns its rows."""
+    handoff, link, detail.  Returns its rows."""
     from . import frontend
     if model.cfg.sample_rate != cfg.sample_rate:
         raise ValueError('the VAD model wants %d Hz, the feature configuration %d Hz' % (model.cfg.sample_rate, cfg.sample_rate))
@@ -423,7 +425,7 @@ def segment_stats(ctx, d_frames, total_frames, files, segments, rate=125.0, timi
 
 
 def cluster_batch(ctx, d_frames, total_frames, files, segments, rate=125.0, cl=DIA2_CL, timings=None,
-                  want_merges=False, fused=None):
+                  want_merges=False, fused=None, stats_out=None):
     """segments: per file, array [(start_s, end_s)] as the clustering script parses
     them.  Returns per file (labels[int array, 1-based, per segment in input
     order], merges[(a, b, d)]).
@@ -433,7 +435,10 @@ def cluster_batch(ctx, d_frames, total_frames, files, segments, rate=125.0, cl=D
     fused: the FusedStats of change_detect_batch for exactly these segments: the records
     of the segments whose frame range (as computed here, from the times) equals the range
     the detector summed are gathered from its buffer; only the others -- a boundary the
-    12-digit text round trip moved across a frame edge -- are computed from the frames."""
+    12-digit text round trip moved across a frame edge -- are computed from the frames.
+    stats_out: a list; receives (d_stats, seg_off), the segment records as they stay on the device
+    (the context's until its next cluster_batch) and their offsets per file of `files`: what
+    link_batch takes.  Nothing is appended when no file has a segment."""
     rate = float(rate)
     method = _method(cl)
     want_merges = want_merges and method == 'hi'
@@ -442,13 +447,18 @@ def cluster_batch(ctx, d_frames, total_frames, files, segments, rate=125.0, cl=D
     if len(keep) < len(files):               # (the lines of the others keep their order: fused stays valid)
         out = [(np.zeros(0, dtype=np.int32), [] if want_merges else None) for _ in files]
         if len(keep):
+            box = None if stats_out is None else []
             sub = cluster_batch(ctx, d_frames, total_frames, [files[i] for i in keep],
-                                [segments[i] for i in keep], rate, cl, timings, want_merges, fused)
+                                [segments[i] for i in keep], rate, cl, timings, want_merges, fused, box)
             for i, r in zip(keep, sub):
                 out[i] = r
+            if box:                              # (the records are in file order: the files left out own none)
+                stats_out.append((box[0][0], np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)))
         return out
     _t0 = time.perf_counter()
     d_stats, seg_off, n, _t1 = segment_stats(ctx, d_frames, total_frames, files, segments, rate, timings, fused)
+    if stats_out is not None:
+        stats_out.append((d_stats, seg_off))
     _t2 = time.perf_counter()
     if method == 'in':
         r = ctx.cluster_in_batch(d_stats, seg_off, cl['kind'], cl['lambdac'], cl['threshold'])
@@ -475,6 +485,77 @@ def cluster_batch(ctx, d_frames, total_frames, files, segments, rate=125.0, cl=D
         timings.setdefault('wall_cl_ahc_call', []).append(1e3 * (_t3 - _t2))
         timings.setdefault('wall_cl_finish', []).append(1e3 * (_t4 - _t3))
     return out
+
+
+def link_speakers(seg_off, labels):
+    """The initial speakers of a batch's linking problem: the clusters of its files, file by file
+    and within a file by ascending label -- the list the reference would hold had every file's
+    final `speakers` been concatenated.  A label no segment carries is no speaker.  labels: per
+    file the 1-based label of each of its segments (seg_off: the files' offsets among all
+    segments).  Returns (member, set_off, spk_file, spk_label): speaker s owns the segments
+    member[set_off[s]:set_off[s + 1]], in segment order, and is label spk_label[s] of file
+    spk_file[s]."""
+    seg_off = np.asarray(seg_off, dtype=np.int64)
+    if len(labels) != len(seg_off) - 1:
+        raise ValueError('one label array per file')
+    labs = [np.asarray(l, dtype=np.int64).reshape(-1) for l in labels]
+    if [len(l) for l in labs] != np.diff(seg_off).tolist():
+        raise ValueError('one label per segment')
+    lab = np.concatenate(labs) if labs else np.zeros(0, dtype=np.int64)
+    if len(lab) == 0:
+        z = np.zeros(0, dtype=np.int64)
+        return z, np.zeros(1, dtype=np.int64), z, z
+    if int(lab.min()) < 1:
+        raise ValueError('labels are 1-based')
+    owner = np.repeat(np.arange(len(labs), dtype=np.int64), [len(l) for l in labs])
+    width = int(lab.max()) + 1
+    keys, spk = np.unique(owner * width + lab, return_inverse=True)
+    member = np.argsort(spk, kind='stable').astype(np.int64)
+    set_off = np.zeros(len(keys) + 1, dtype=np.int64)
+    set_off[1:] = np.cumsum(np.bincount(spk, minlength=len(keys)))
+    return member, set_off, keys // width, keys % width
+
+
+def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None):
+    """Which speaker of one file is which speaker of another: spk_cluster_hi over the speakers of
+    all files of a batch (spk-clustering.py:178-240 takes `speakers` of any length per entry; the
+    command line never gets there, :289).  d_stats, seg_off: the segment records and the files'
+    offsets as segment_stats leaves them (cluster_batch's stats_out); labels: per file the labels
+    cluster_batch returned.  The speakers (link_speakers) get their records as the sums of their
+    segments' records, in segment order (spkd_sum_stats: no frame is read again), and are one
+    clustering problem of `link` (the keys of DIA2_CL).
+    Returns (maps, merges, stat_max, stat_min): maps[f][l] is the global 1-based speaker of label
+    l of file f (0 for a label no segment carries; length 0 for a file without segments), merges
+    the log [(a, b, d)] over the speaker list, stat_max / stat_min as spkd_ahc states them.
+    More than 16 384 speakers: ValueError.  timings: link_sum (the sum kernel, ms), link_ahc (the
+    clustering call, ms), link_speakers, link_merges."""
+    member, set_off, spk_file, spk_label = link_speakers(seg_off, labels)
+    n_spk = len(spk_file)
+    maps = [np.zeros(int(np.max(l)) + 1 if len(l) else 0, dtype=np.int32) for l in labels]
+    if n_spk == 0:
+        return maps, [], float('nan'), float('nan')
+    d_spk = ctx.dev_scratch('link_speaker_stats', n_spk * hipabi.REC * 8)
+    ctx.sum_stats(d_stats, int(seg_off[-1]), member, set_off, d_spk)
+    if timings is not None:
+        timings.setdefault('link_sum', []).append(ctx.last_ms('reduce_sets'))
+    try:
+        r = ctx.ahc(d_spk, np.array([0, n_spk], dtype=np.int64), _ahc_params(link))
+    except hipabi.SpkdError as e:
+        if e.status == hipabi.SPKD_EINVAL:
+            raise ValueError(str(e))
+        raise
+    nm = int(r['n_merges'][0])
+    if timings is not None:
+        timings.setdefault('link_ahc', []).append(ctx.last_ms('call'))
+        timings['link_speakers'] = n_spk
+        timings['link_merges'] = nm
+    if r['status'] == hipabi.SPKD_ENONFINITE:
+        raise ValueError('array must not contain infs or NaNs')
+    glob = hipabi.labels_from_merges(n_spk, r['a'][:nm], r['b'][:nm])
+    for f, l, g in zip(spk_file.tolist(), spk_label.tolist(), glob.tolist()):
+        maps[f][l] = g
+    merges = list(zip(r['a'][:nm].tolist(), r['b'][:nm].tolist(), r['d'][:nm].tolist()))
+    return maps, merges, float(r['stat_max'][0]), float(r['stat_min'][0])
 
 
 def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl=DIA2_CL, timings=None,
@@ -534,7 +615,7 @@ def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2
 
 
 def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl=DIA2_CL, timings=None,
-                  text_contract=True, fused=False, handoff=None):
+                  text_contract=True, fused=False, handoff=None, link=None, detail=None):
     """CD (gw/BIC) + CL (hi/BIC) for a batch; returns per file an array of rows
     [start_s, end_s, speaker] in recipe order.
     cl['method'] = 'in' clusters with spk_cluster_in (cluster_batch): host hand-off only; the
@@ -550,12 +631,18 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     floating-point sums).
     handoff: 'device' (the default of fused=True with the text contract: diarize_batch_device)
     or 'host' (the event arrays come to the host, which builds the lines and gathers the
-    records: the only form of the two-pass and text_contract=False modes)."""
+    records: the only form of the two-pass and text_contract=False modes).
+    link: a dictionary like LINK_CL; the speakers of the files are then linked across the batch
+    (link_batch) and the rows' third column holds the global speakers -- segments, times and
+    order are those of link=None.  Host hand-off only.  detail: a dict; receives link_batch's
+    result as detail['link'] = dict(maps, merges, stat_max, stat_min)."""
     method = _method(cl)
     if _cd_method(cd) in ('sw', 'm'):
         if fused or handoff == 'device':
             raise ValueError('cd method %s takes the host hand-off and is not fused' % _cd_method(cd))
         handoff = 'host'
+    if link is not None and (handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi')):
+        raise ValueError('link takes the host hand-off')
     if handoff is None:
         handoff = 'device' if fused and text_contract and method == 'hi' else 'host'
     if handoff == 'device':
@@ -570,17 +657,27 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     segs = change_detect_batch(ctx, d_frames, total_frames, files, rate, cd, timings, text_contract, box)
     fs = box[0] if box else None
     if (fused and fs is None) or not any(len(s) for s in segs):      # no turn at all in the batch
+        if link is not None and detail is not None:
+            detail['link'] = dict(maps=[np.zeros(0, dtype=np.int32) for _ in files], merges=[],
+                                  stat_max=float('nan'), stat_min=float('nan'))
         return [np.zeros((0, 3)) for _ in files]
-    return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs)
+    return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail)
 
 
-def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs):
-    res = cluster_batch(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fused=fs)
+def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link=None, detail=None):
+    box = None if link is None else []
+    res = cluster_batch(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fused=fs, stats_out=box)
     cnt = [len(s) for s in segs]
     if sum(cnt) == 0:
         return [np.zeros((0, 3)) for _ in segs]
     allseg = np.concatenate([np.asarray(s, dtype=np.float64).reshape(-1, 2) for s in segs])
-    labels = np.concatenate([lab for (lab, _) in res])
+    if link is None:
+        labels = np.concatenate([lab for (lab, _) in res])
+    else:
+        maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], [lab for (lab, _) in res], link, timings)
+        labels = np.concatenate([m[lab] for m, (lab, _) in zip(maps, res)])
+        if detail is not None:
+            detail['link'] = dict(maps=maps, merges=merges, stat_max=smax, stat_min=smin)
     bounds = np.zeros(len(segs) + 1, dtype=np.int64)
     bounds[1:] = np.cumsum(cnt)
     if _method(cl) == 'in':

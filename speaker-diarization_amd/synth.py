@@ -128,12 +128,14 @@ def plan_session(seed, seconds, n_speakers=4, min_turn=3.0, max_turn=15.0,
 
 
 def make_session(seed, seconds, n_speakers=4, min_turn=3.0, max_turn=15.0,
-                 sil_seconds=2.0, group=(2, 6), lead_silence=1.0):
+                 sil_seconds=2.0, group=(2, 6), lead_silence=1.0, models=None):
     """Returns (features float32 [T, 39], vad_turns, truth) where
-    vad_turns = [(start_frame, end_frame)] and truth = [(start, end, speaker)]."""
+    vad_turns = [(start_frame, end_frame)] and truth = [(start, end, speaker)].
+    models: the speakers' (mu, A) instead of the seed's own (make_series)."""
     total, pieces, vad, truth = plan_session(seed, seconds, n_speakers, min_turn, max_turn,
                                              sil_seconds, group, lead_silence)
-    models = [_speaker_model(seed, k) for k in range(n_speakers)]
+    if models is None:
+        models = [_speaker_model(seed, k) for k in range(n_speakers)]
     feats = np.empty((total, DIM), dtype=np.float32)
     for (pos, n, stream, k) in pieces:
         if k < 0:
@@ -143,6 +145,17 @@ def make_session(seed, seconds, n_speakers=4, min_turn=3.0, max_turn=15.0,
             mu, a = models[k]
             feats[pos:pos + n] = _emit(seed, stream, n, mu, a)
     return feats, vad, truth
+
+
+def make_series(seeds, seconds, shared_seed, n_shared=2, n_speakers=3, **kw):
+    """The files of one meeting series: file i is make_session(seeds[i], seconds, n_speakers) in
+    layout and noise, but its speakers 0 .. n_shared - 1 are the same people in every file (the
+    mean and mixing of shared_seed's speakers); the others are the file's own.  Returns one
+    (features, vad_turns, truth) per seed."""
+    shared = [_speaker_model(shared_seed, k) for k in range(n_shared)]
+    return [make_session(seed, seconds, n_speakers, models=shared + [_speaker_model(seed, k) for k in
+                                                                     range(n_shared, n_speakers)], **kw)
+            for seed in seeds]
 
 
 def write_fea(path, feats):

@@ -1,0 +1,118 @@
+#!/usr/bin/env python
+"""Times the linking of a batch's speakers (pipeline.link_batch) on bench.py's synthetic batch
+(--files x --seconds): the segments are the generator's truth turns and a file's labels its
+truth speakers, so the batch has --files x --speakers initial speakers.  Reported:
+  (a) link_sum: the records of all speakers as sums of their segments' records (spkd_sum_stats,
+      kernel time) and the GB/s of its members x 6 560 B read + sets x 6 560 B written,
+  (b) the only route to the same records without it: spkd_set_stats with one multi-range set per
+      speaker from the resident frames (kernel times of its two passes), every frame read again,
+  (c) link_ahc: the one clustering problem over all speakers (the whole call), with its speakers
+      and merges.
+Medians and spreads over --runs after a warm-up of each; (a) and (b) must give the same records
+(1e-12 relative: the order of the sums differs) before they are compared.  Wall times are around
+calls that return with their device work finished.  Prints one JSON line.  Run it under
+`timeout`."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = 'speaker-diarization_amd'
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--files', type=int, default=256)
+    ap.add_argument('--seconds', type=float, default=3600.0)
+    ap.add_argument('--speakers', type=int, default=4)
+    ap.add_argument('--runs', type=int, default=7)
+    ap.add_argument('--ahc-runs', type=int, default=3)
+    args = ap.parse_args()
+    import torch
+    hipabi = importlib.import_module(PKG + '.hipabi')
+    pipeline = importlib.import_module(PKG + '.pipeline')
+    synth_device = importlib.import_module(PKG + '.synth_device')
+    dev = torch.device('cuda', 0)
+    parts, begins, ends, labels, off = [], [], [], [], 0
+    for i in range(args.files):
+        feats, _, truth = synth_device.make_session_device(1000003 + i, args.seconds, args.speakers, device=dev)
+        begins += [off + a for a, _, _ in truth]
+        ends += [off + b for _, b, _ in truth]
+        labels.append(np.array([k + 1 for _, _, k in truth], dtype=np.int32))
+        parts.append(feats)
+        off += int(feats.shape[0])
+    frames = torch.cat(parts)
+    del parts
+    torch.cuda.synchronize()
+    ctx = hipabi.Context(0, torch.cuda.current_stream().cuda_stream)
+    ptr, total = frames.data_ptr(), int(frames.shape[0])
+    b, e = np.array(begins, dtype=np.int64), np.array(ends, dtype=np.int64)
+    n_seg = len(b)
+    seg_off = np.concatenate([[0], np.cumsum([len(l) for l in labels])]).astype(np.int64)
+    # what cluster_batch leaves: one record per segment, in segment order
+    d_stats = ctx.dev_alloc(n_seg * hipabi.REC * 8)
+    ctx.set_stats(ptr, total, b, e, np.arange(n_seg, dtype=np.int32), n_seg, d_stats)
+    member, set_off, _, _ = pipeline.link_speakers(seg_off, labels)
+    n_spk = len(set_off) - 1
+    d_a = ctx.dev_alloc(n_spk * hipabi.REC * 8)
+    d_b = ctx.dev_alloc(n_spk * hipabi.REC * 8)
+    owner = np.repeat(np.arange(n_spk, dtype=np.int32), np.diff(set_off))
+
+    def sum_records():
+        t0 = time.perf_counter()
+        ctx.sum_stats(d_stats, n_seg, member, set_off, d_a)
+        return time.perf_counter() - t0, ctx.last_ms('reduce_sets')
+
+    def from_frames():
+        t0 = time.perf_counter()
+        ctx.set_stats(ptr, total, b[member], e[member], owner, n_spk, d_b)
+        return time.perf_counter() - t0, ctx.last_ms('chunk_stats') + ctx.last_ms('reduce_sets')
+
+    sum_records()
+    from_frames()
+    ra, rb = np.empty((n_spk, hipabi.REC)), np.empty((n_spk, hipabi.REC))
+    ctx.d2h(ra, d_a)
+    ctx.d2h(rb, d_b)
+    worst = float(np.max(np.abs(ra - rb) / np.maximum(1.0, np.abs(rb))))
+    assert worst < 1e-12, worst
+    sa, sb = [], []
+    for _ in range(args.runs):
+        sa.append(sum_records())
+        sb.append(from_frames())
+    ahc = []
+    for i in range(args.ahc_runs + 1):
+        tm = {}
+        t0 = time.perf_counter()
+        maps, merges, _, _ = pipeline.link_batch(ctx, d_stats, seg_off, labels, timings=tm)
+        if i:
+            ahc.append((time.perf_counter() - t0, tm['link_ahc'][0], tm['link_sum'][0]))
+    med = lambda xs: round(float(np.median(xs)), 3)
+    spread = lambda xs: [round(float(min(xs)), 3), round(float(max(xs)), 3)]
+    nbytes = (len(member) + n_spk) * hipabi.REC * 8
+    out = {
+        'files': args.files, 'seconds': args.seconds, 'segments': n_seg, 'speakers': n_spk, 'members': int(len(member)),
+        'frames_of_members': int((e - b).sum()), 'runs': args.runs, 'ahc_runs': args.ahc_runs,
+        'link_sum_kernel_ms': med([x[1] for x in sa]), 'link_sum_kernel_min_max_ms': spread([x[1] for x in sa]),
+        'link_sum_call_ms': med([1e3 * x[0] for x in sa]), 'link_sum_bytes': nbytes,
+        'set_stats_kernels_ms': med([x[1] for x in sb]), 'set_stats_kernels_min_max_ms': spread([x[1] for x in sb]),
+        'set_stats_call_ms': med([1e3 * x[0] for x in sb]), 'records_worst_rel_diff': worst,
+        'link_ahc_call_ms': med([x[1] for x in ahc]), 'link_ahc_min_max_ms': spread([x[1] for x in ahc]),
+        'link_batch_wall_ms': med([1e3 * x[0] for x in ahc]), 'link_merges': len(merges),
+        'global_speakers': int(max(int(m.max()) for m in maps)), 'device': torch.cuda.get_device_name(0),
+    }
+    out['link_sum_gb_s'] = round(nbytes / (out['link_sum_kernel_ms'] * 1e-3) / 1e9, 1)
+    out['set_stats_over_link_sum'] = round(out['set_stats_kernels_ms'] / out['link_sum_kernel_ms'], 2)
+    print(json.dumps(out))
+    for p in (d_stats, d_a, d_b):
+        ctx.dev_free(p)
+    ctx.close()
+
+
+if __name__ == '__main__':
+    main()
