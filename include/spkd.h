@@ -98,7 +98,8 @@ spkd_status spkd_memcpy_d2d(spkd_ctx *ctx, void *d_dst, const void *d_src, size_
 enum {
     SPKD_T_CALL = 0, SPKD_T_CHUNK_STATS, SPKD_T_REDUCE_SETS, SPKD_T_PAIR_TERMS,
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
-    SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
+    SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
+    SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
     SPKD_N_TIMERS
 };
 spkd_status spkd_last_kernel_ms(spkd_ctx *ctx, int which, float *ms);
@@ -635,6 +636,59 @@ spkd_status spkd_vad_viterbi_batch(spkd_ctx *ctx, const float *d_scores, int64_t
                                    const double *h_exit, const double *h_enter,
                                    const int64_t **h_tok_off, const int64_t **h_tok_frame,
                                    const int32_t **h_tok_word, const double **h_score);
+
+/* ---------------------------------------------------------------------------
+ * (8) Resegmentation: full-covariance Gaussian speaker models from statistics records and the
+ * log-likelihood of every frame of a set of sequences (VAD turns) under the speakers of its file.
+ * With spkd_sum_stats in front (speaker records from segment records) and spkd_vad_viterbi_batch
+ * behind (sequences = turns, n_states = n_words = n_cols, word_state = identity, stay = exit = 0,
+ * enter = -penalty: a speaker loop with a switch penalty; with penalty >= 0 its tie rule, staying
+ * beats switching, means a path never re-enters the word it is in) this is the Viterbi
+ * resegmentation pass that BIC segmentation + agglomerative clustering systems end with.
+ * PARITY: no reference counterpart (the reference stops at clustering); tests/reseg_numpy.py
+ * restates both calls in numpy.
+ *
+ * spkd_gauss_models: one model per record, in fp64.  n = the record's frame count, mu = sum x / n,
+ * S = the unbiased covariance (np.cov(rowvar=0), from the moments: (M_ij - (s_i / n) s_j) / (n - 1)),
+ * S = L L^T by Cholesky.  A model is SPKD_GAUSS_MODEL = 820 doubles:
+ *   [0, 39)    mu
+ *   [39, 819)  W = L^-1, packed lower triangle, row-major: W_ij (j <= i) at 39 + i (i + 1) / 2 + j
+ *   [819]      c = -1/2 * 39 * ln(2 pi) - sum_i ln L_ii
+ * h_ok[i] = 1 when n >= 2 and every pivot is a positive finite number, else 0.  "Positive" is
+ * above rounding noise: pivot j must exceed 2^-40 * M_jj / (n - 1), the diagonal entry it started
+ * from before the mean was taken out, and a record of fewer than 40 frames, whose covariance has
+ * no full rank whatever rounding leaves in its last pivots, is not ok.  So digital silence,
+ * constant stretches, fewer than 40 frames and records that are not finite all give 0.  This is
+ * no error status: a speaker that cannot be modelled is simply never chosen.  A model that is
+ * not ok may hold anything.  One wave per record.
+ * n = 0: SPKD_OK without a launch.  A null pointer, buffers that are not 16-byte aligned:
+ * SPKD_EINVAL before any device work.  Timer: SPKD_T_GAUSS_MODELS.
+ *
+ * spkd_gauss_loglik: sequence q covers the absolute frames [h_seq_begin[q], h_seq_end[q]) of
+ * d_frames (n_frames x 39 floats); sequences may be empty, need not be contiguous and need not
+ * ascend.  It is scored under the models h_seq_model[q] .. + h_seq_n_models[q] - 1 of d_models
+ * (n_models models as spkd_gauss_models leaves them, h_model_ok its h_ok).  d_scores is compact:
+ * [sum len][n_cols] floats, frame-major, sequence q from row sum_{p < q} len[p] on -- the layout
+ * spkd_vad_viterbi_batch reads with h_frame_off set to that running sum.  Column k < n_models(q):
+ *   c - 1/2 sum_i y_i^2,   y_i = sum_{j <= i} W_ij (x_j - mu_j)
+ * all in fp64 from the float32 frame, rounded once to float32 on the store (as spkd_vad_shift_batch).
+ * A model that is not ok gives -inf in its column, and so do the columns n_models(q) .. n_cols - 1.
+ * Frames that are not finite propagate NaN.  A workgroup takes a tile of SPKD_GAUSS_TILE frames of
+ * one sequence, a lane per frame.
+ * Limits: 1 <= n_cols <= 16, 0 <= n_models(q) <= n_cols.  A range outside [0, n_frames] or with
+ * end < begin, a model index out of range, a null pointer, d_models not 16-byte aligned:
+ * SPKD_EINVAL before any device work, d_scores untouched.  n_seq = 0 or no frame in any sequence:
+ * SPKD_OK without a launch.  The index arrays go up in one copy through pinned memory the context
+ * owns.  Timer: SPKD_T_GAUSS_LOGLIK. */
+#define SPKD_GAUSS_MODEL 820
+#define SPKD_GAUSS_TILE 64
+spkd_status spkd_gauss_models(spkd_ctx *ctx, const double *d_stats, int64_t n, double *d_models,
+                              int32_t *h_ok);
+spkd_status spkd_gauss_loglik(spkd_ctx *ctx, const float *d_frames, int64_t n_frames,
+                              const double *d_models, int64_t n_models, const int32_t *h_model_ok,
+                              int64_t n_seq, const int64_t *h_seq_begin, const int64_t *h_seq_end,
+                              const int32_t *h_seq_model, const int32_t *h_seq_n_models,
+                              int32_t n_cols, float *d_scores);
 
 /* ---------------------------------------------------------------------------
  * (5) Host-side helpers of the boundary (no GPU work).

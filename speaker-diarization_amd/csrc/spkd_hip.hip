@@ -23,14 +23,15 @@
 #include "spkd_mfcc_batch.hpp"
 #include "spkd_vad.hpp"
 #include "spkd_vad_batch.hpp"
+#include "spkd_gauss.hpp"
 
 using namespace spkd;
 
 namespace {
 constexpr int N_SLOTS = 48;
 // pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused), of spkd_vad_viterbi_batch and of
-// spkd_sum_stats (its index arrays on their way up)
-enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, N_PIN };
+// spkd_sum_stats and spkd_gauss_loglik (their index arrays on their way up)
+enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX, N_PIN };
 }
 
 struct spkd_ctx {
@@ -256,7 +257,7 @@ enum {
     S_GW_N_WIN, S_GW_WIN_DET, S_GW_WIN_MAXD, S_GW_DET_START, S_GW_DET_MAXI, S_GW_DET_D, S_GW_FINAL_START, S_LOG,
     S_AHC_STATS, S_AHC_LD, S_AHC_AUX, S_AHC_MAT, S_AHC_MISC, S_AHC_OUT, S_AHC_OFF, S_AHC_PROB, S_AHC_PACKED, S_MFCC_TAB, S_MFCC_STATIC, S_MFCC_TW,
     S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX,
-    S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_COUNT
+    S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -2211,6 +2212,92 @@ spkd_status spkd_vad_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_t n
     }
     *h_tok_frame = h_frames;
     *h_tok_word = h_words;
+    return call.finish();
+}
+
+// ------------------------------------------------------------------ (8) speaker models and their scores
+static_assert(GS_TILE == SPKD_GAUSS_TILE && GS_MODEL == SPKD_GAUSS_MODEL, "the header states the kernels' tile and model");
+
+spkd_status spkd_gauss_models(spkd_ctx* c, const double* d_stats, int64_t n, double* d_models, int32_t* h_ok) {
+    if (!c || n < 0) return SPKD_EINVAL;
+    if (n == 0) return SPKD_OK;
+    if (!d_stats || !d_models || !h_ok) return fail(c, SPKD_EINVAL, "null argument");
+    if (n > 0x7fffffff) return fail(c, SPKD_EINVAL, "gauss_models: too many records");
+    if ((uintptr_t)d_stats % 16 || (uintptr_t)d_models % 16)
+        return fail(c, SPKD_EINVAL, "gauss_models: record and model buffers must be 16-byte aligned");
+    Call call(c);
+    TRY(call.opened);
+    void* d_ok = nullptr;
+    TRY(scratch(c, S_GAUSS_OK, (size_t)n * sizeof(int32_t), &d_ok));
+    {
+        Timer t(c, SPKD_T_GAUSS_MODELS);
+        hipLaunchKernelGGL(k_gauss_models, dim3((unsigned)n), dim3(WAVE), 0, c->stream, d_stats, d_models, (int*)d_ok);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_ok, d_ok, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    return call.finish();
+}
+
+spkd_status spkd_gauss_loglik(spkd_ctx* c, const float* d_frames, int64_t n_frames, const double* d_models,
+                              int64_t n_models, const int32_t* h_model_ok, int64_t n_seq, const int64_t* h_seq_begin,
+                              const int64_t* h_seq_end, const int32_t* h_seq_model, const int32_t* h_seq_n_models,
+                              int32_t n_cols, float* d_scores) {
+    if (!c || n_seq < 0) return SPKD_EINVAL;
+    if (n_seq == 0) return SPKD_OK;
+    if (!d_frames || !d_models || !h_model_ok || !h_seq_begin || !h_seq_end || !h_seq_model || !h_seq_n_models || !d_scores)
+        return fail(c, SPKD_EINVAL, "null argument");
+    if (n_cols < 1 || n_cols > GS_MAX_COLS) return fail(c, SPKD_EINVAL, "gauss_loglik: 1 <= n_cols <= 16");
+    if (n_frames < 0 || n_models < 0 || n_models > 0x7fffffff || n_seq > 0x7fffffff)
+        return fail(c, SPKD_EINVAL, "gauss_loglik: bad count");
+    if ((uintptr_t)d_models % 16 || (uintptr_t)d_frames % 4 || (uintptr_t)d_scores % 4)
+        return fail(c, SPKD_EINVAL, "gauss_loglik: misaligned buffer (models: 16 bytes)");
+    int64_t total = 0, n_tiles = 0;
+    for (int64_t q = 0; q < n_seq; ++q) {
+        const int64_t b = h_seq_begin[q], e = h_seq_end[q];
+        if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, "gauss_loglik: sequence outside [0, n_frames]");
+        const int64_t m = h_seq_model[q], k = h_seq_n_models[q];
+        if (k < 0 || k > n_cols) return fail(c, SPKD_EINVAL, "gauss_loglik: 0 <= models of a sequence <= n_cols");
+        if (m < 0 || m + k > n_models) return fail(c, SPKD_EINVAL, "gauss_loglik: model index out of range");
+        total += e - b;
+        n_tiles += (e - b + GS_TILE - 1) / GS_TILE;
+    }
+    if (total == 0) return SPKD_OK;
+    if (n_tiles > 0x7fffffff) return fail(c, SPKD_EINVAL, "gauss_loglik: too many frames in one call");
+    const size_t ns = (size_t)n_seq, nm = (size_t)n_models, nt = (size_t)n_tiles;
+    // every index array as one image in pinned memory: one copy up
+    struct Tab { int64_t *begin, *end, *row, *tile; int32_t *model, *n_models, *ok, *tile_seq; } h, d;
+    auto parts = [&](Layout L, Tab& t) {
+        return L.part(t.begin, ns).part(t.end, ns).part(t.row, ns).part(t.tile, ns).part(t.model, ns).part(t.n_models, ns)
+            .part(t.ok, nm).part(t.tile_seq, nt).bytes();
+    };
+    size_t image = 0;
+    TRY(carve(c, pinned, PIN_GAUSS_IDX, [&](Layout L) { return image = parts(L, h); }));
+    std::memcpy(h.begin, h_seq_begin, ns * sizeof(int64_t));
+    std::memcpy(h.end, h_seq_end, ns * sizeof(int64_t));
+    std::memcpy(h.model, h_seq_model, ns * sizeof(int32_t));
+    std::memcpy(h.n_models, h_seq_n_models, ns * sizeof(int32_t));
+    std::memcpy(h.ok, h_model_ok, nm * sizeof(int32_t));
+    int64_t row = 0, tile = 0;
+    for (size_t q = 0; q < ns; ++q) {
+        h.row[q] = row;
+        h.tile[q] = tile;
+        const int64_t len = h.end[q] - h.begin[q], k = (len + GS_TILE - 1) / GS_TILE;
+        for (int64_t i = 0; i < k; ++i) h.tile_seq[tile + i] = (int32_t)q;
+        row += len;
+        tile += k;
+    }
+    Call call(c);
+    TRY(call.opened);
+    TRY(carve(c, scratch, S_GAUSS_IDX, [&](Layout L) { return parts(L, d); }));
+    HIPCHK(c, hipMemcpyAsync(d.begin, h.begin, image, hipMemcpyHostToDevice, c->stream));
+    {
+        Timer t(c, SPKD_T_GAUSS_LOGLIK);
+        hipLaunchKernelGGL(k_gauss_loglik, dim3((unsigned)n_tiles), dim3(WAVE), 0, c->stream, d_frames, d_models,
+                           (const int*)d.ok, (const long long*)d.begin, (const long long*)d.end, (const long long*)d.row,
+                           (const long long*)d.tile, (const int*)d.model, (const int*)d.n_models, (const int*)d.tile_seq,
+                           (int)n_cols, d_scores);
+    }
+    HIPCHK(c, hipGetLastError());
     return call.finish();
 }
 

@@ -16,8 +16,11 @@ WANT_GLR, WANT_KL2, WANT_KL2_PINV = 1, 2, 4
 MERGE_NO_AHEAD = 1
 TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pair_terms',
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
-                                        'vad_shift', 'vad_viterbi', 'vad_backtrack', 'mfcc_static', 'mfcc_post'])}
+                                        'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
+                                        'mfcc_static', 'mfcc_post'])}
 VAD_TILE = 32       # SPKD_VAD_TILE: frames per score / back-pointer tile of k_vad_viterbi
+GAUSS_TILE = 64     # SPKD_GAUSS_TILE: frames per workgroup of k_gauss_loglik
+GAUSS_MODEL = 820   # SPKD_GAUSS_MODEL: doubles per model (mu[39], W = L^-1 packed lower [780], c)
 REC = 820
 DIM = 39
 
@@ -27,7 +30,8 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_sum_stats', 'spkd_mfcc', 'spkd_mfcc_batch',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
-           'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch']
+           'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
+           'spkd_gauss_models', 'spkd_gauss_loglik']
 
 
 class CdParams(C.Structure):
@@ -202,6 +206,8 @@ def load_library(path=None):
     lib.spkd_vad_viterbi.argtypes = [i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, P(i64), P(dbl)]
     lib.spkd_vad_shift_batch.argtypes = [vp, vp, i64, vp, i32, dbl, vp]
     lib.spkd_vad_viterbi_batch.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, P(vp), P(vp), P(vp), P(vp)]
+    lib.spkd_gauss_models.argtypes = [vp, vp, i64, vp, vp]
+    lib.spkd_gauss_loglik.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp]
     lib.spkd_gw_lines.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, dbl, C.c_int, i64, vp, vp, vp, vp, vp]
     if lib.spkd_abi_version() != 2:
         raise ImportError('libspkd_hip.so ABI version mismatch')
@@ -760,6 +766,36 @@ class Context(object):
         n_tok = int(tok_off[-1])
         return (tok_off, _view(out[1].value, n_tok, np.int64).copy(), _view(out[2].value, n_tok, np.int32).copy(),
                 _view(out[3].value, n, np.float64).copy())
+
+    # ---- (8) resegmentation
+    def gauss_models(self, d_stats, n, d_models):
+        """One full-covariance Gaussian model (GAUSS_MODEL doubles: mu, W = L^-1 packed, c) per
+        statistics record of d_stats into d_models (spkd_gauss_models).  Returns ok (int32 [n]):
+        0 for a record that cannot be modelled (fewer than 40 frames, no positive pivot, not
+        finite), whose model may hold anything.  The kernel's time is last_ms('gauss_models')."""
+        ok = np.zeros(int(n), dtype=np.int32)
+        self.check(self.lib.spkd_gauss_models(self.h, C.c_void_p(d_stats), int(n), C.c_void_p(d_models), _ptr(ok)))
+        return ok
+
+    def gauss_loglik(self, d_frames, n_frames, d_models, model_ok, seq_begin, seq_end, seq_model, seq_n_models,
+                     n_cols, d_scores):
+        """The log-likelihood of every frame of the sequences [seq_begin[q], seq_end[q]) under the
+        models seq_model[q] .. + seq_n_models[q] - 1 (spkd_gauss_loglik) into the compact device
+        array d_scores [sum len, n_cols] float32; -inf in the columns of models that are not ok and
+        from seq_n_models[q] on.  Returns frame_off, the running sum of the lengths: what
+        vad_viterbi_batch takes with these scores.  The kernel's time is last_ms('gauss_loglik')."""
+        c = np.ascontiguousarray
+        ok = c(model_ok, dtype=np.int32)
+        b, e = c(seq_begin, dtype=np.int64), c(seq_end, dtype=np.int64)
+        m, k = c(seq_model, dtype=np.int32), c(seq_n_models, dtype=np.int32)
+        if any(a.ndim != 1 for a in (ok, b, e, m, k)) or not (len(b) == len(e) == len(m) == len(k)):
+            raise SpkdError(SPKD_EINVAL, 'one begin, end, first model and model count per sequence')
+        self.check(self.lib.spkd_gauss_loglik(self.h, C.c_void_p(d_frames), int(n_frames), C.c_void_p(d_models), len(ok),
+                                              _ptr(ok), len(b), _ptr(b), _ptr(e), _ptr(m), _ptr(k), int(n_cols),
+                                              C.c_void_p(d_scores)))
+        frame_off = np.zeros(len(b) + 1, dtype=np.int64)
+        frame_off[1:] = np.cumsum(e - b)
+        return frame_off
 
     # ---- (4)
     def ahc(self, d_stats, seg_off, params):

@@ -26,6 +26,11 @@ SW_CD = dict(method='sw', kind='GLR', lambdac=1.3, threshold=0.0, winsize_s=5.0,
 MERGE_CD = dict(method='m', kind='GLR', lambdac=1.3, threshold=0.0, winsize_s=5.0, winstep_s=0.5, deltaws_s=0.05)
 # linking the speakers of a batch's files (link_batch): the clustering script's own defaults
 LINK_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
+# Viterbi resegmentation (resegment_batch): the cost of a speaker switch inside a turn, in natural-log
+# units.  On the synthetic generator every value from 10 to 200 decodes the same paths; real audio,
+# whose frames are correlated in time, will want it tuned.
+RESEG = dict(penalty=50.0)
+RESEG_MAX_SPEAKERS = 16          # of one file: the decoder's word limit (spkd_vad_viterbi_batch)
 
 
 class BatchFile(object):
@@ -92,7 +97,7 @@ def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=Non
     chain (vad_batch with the model's own feature configuration) and the diarization features
     (features_batch with cfg, the fconfig.cfg chain) both from it, then diarize_batch with the
     turns and the frames as they lie on the device.  kw: diarize_batch's text_contract, fused,
-    handoff, link, detail.  Returns its rows."""
+    handoff, link, reseg, detail.  Returns its rows."""
     from . import frontend
     if model.cfg.sample_rate != cfg.sample_rate:
         raise ValueError('the VAD model wants %d Hz, the feature configuration %d Hz' % (model.cfg.sample_rate, cfg.sample_rate))
@@ -558,6 +563,105 @@ def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None):
     return maps, merges, float(r['stat_max'][0]), float(r['stat_min'][0])
 
 
+def _reseg_penalty(reseg):
+    p = float(reseg['penalty'])
+    if not np.isfinite(p) or p < 0.0:
+        raise ValueError('reseg penalty: a finite number >= 0 (natural-log units)')
+    return p
+
+
+def _reseg_rows(tok_off, tok_frame, tok_word, turn_start_s, turn_end_s, turn_labels, rate, text_contract):
+    """The rows of a decoded batch of turns, in turn order: token k of a turn, opening at the
+    relative frame f_k, is [turn_start_s + f_k / rate, turn_start_s + f_{k+1} / rate, label]; a turn's
+    first row starts at the turn's own start (f_0 = 0) and its last row ends at the turn's own end
+    as the VAD states it (the convention of spkd_gw_lines' tail line).  turn_labels[q][w]: the label
+    of word w in turn q.  Returns (rows [n_tokens, 3], the turn of every row)."""
+    n_tok = int(tok_off[-1])
+    turn = np.repeat(np.arange(len(tok_off) - 1), np.diff(tok_off))
+    t0 = turn_start_s[turn] + tok_frame / rate
+    t1 = np.empty(n_tok)
+    t1[:-1] = t0[1:]
+    last = tok_off[1:][np.diff(tok_off) > 0] - 1
+    t1[last] = turn_end_s[turn[last]]
+    times = np.column_stack([t0, t1])
+    if text_contract:
+        times = hipabi.py2_roundtrip(times.ravel()).reshape(-1, 2)
+    return np.column_stack([times, turn_labels[turn, tok_word].astype(np.float64)]), turn
+
+
+def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels, rate=125.0, reseg=RESEG,
+                    text_contract=True, timings=None, detail=None):
+    """Viterbi resegmentation of a clustered batch on the device: the closing pass of a BIC
+    segmentation + agglomerative clustering system (the reference has none).  d_stats, seg_off,
+    labels: the segment records, the files' offsets and the per-file labels of a cluster_batch
+    (its stats_out and results).  The speakers are link_speakers' -- file by file, by ascending
+    label -- their records the sums of their segments' (spkd_sum_stats), their models one
+    full-covariance Gaussian each (spkd_gauss_models).  Every VAD turn (_turn_table) of a file with
+    speakers is one sequence: one spkd_gauss_loglik scores all its frames under the file's speakers,
+    one spkd_vad_viterbi_batch decodes the best speaker sequence with reseg['penalty'] taken off at
+    every switch (stay = exit = 0, enter = -penalty; staying wins ties, so consecutive rows of a
+    turn differ in speaker).  Returns per file the rows [start_s, end_s, label] that tile its turns
+    (_reseg_rows; times through the 12-digit round trip with text_contract), label the file's own
+    cluster label; a file with no segments or no turns gives np.zeros((0, 3)), a turn with no
+    frames no rows.
+    A speaker whose record cannot be modelled (fewer than 40 frames, a covariance without positive
+    pivots) scores -inf and is never chosen; when that is every speaker of a turn the decoder's
+    all--inf rule applies and the file's lowest label takes the turn.  detail: a dict; receives
+    dropped = [(file, label)] of those speakers.  More than 16 speakers in one file, a negative or
+    non-finite penalty: ValueError before any device work.  timings: reseg_models, reseg_loglik,
+    reseg_viterbi, reseg_backtrack (kernel ms)."""
+    rate = float(rate)
+    penalty = _reseg_penalty(reseg)
+    member, set_off, spk_file, spk_label = link_speakers(seg_off, labels)
+    n_files = len(files)
+    if len(labels) != n_files:
+        raise ValueError('one label array per file')
+    n_spk_file = np.bincount(spk_file, minlength=n_files).astype(np.int64)
+    if n_files and int(n_spk_file.max()) > RESEG_MAX_SPEAKERS:
+        raise ValueError('resegmentation decodes at most %d speakers a file: file %d has %d'
+                         % (RESEG_MAX_SPEAKERS, int(n_spk_file.argmax()), int(n_spk_file.max())))
+    out = [np.zeros((0, 3)) for _ in files]
+    if detail is not None:
+        detail['dropped'] = []
+    table = _turn_table(files, rate)
+    if table is None or len(spk_file) == 0:
+        return out
+    owner, _, _, ls, le, tb, te = table
+    keep = n_spk_file[owner] > 0
+    owner, ls, le, tb, te = owner[keep], ls[keep], le[keep], tb[keep], te[keep]
+    if len(owner) == 0:
+        return out
+    n_spk, n_cols = len(spk_file), int(n_spk_file.max())
+    spk_base = np.zeros(n_files + 1, dtype=np.int64)
+    spk_base[1:] = np.cumsum(n_spk_file)
+    d_spk = ctx.dev_scratch('reseg_speaker_stats', n_spk * hipabi.REC * 8)
+    ctx.sum_stats(d_stats, int(seg_off[-1]), member, set_off, d_spk)
+    d_models = ctx.dev_scratch('reseg_models', n_spk * hipabi.GAUSS_MODEL * 8)
+    ok = ctx.gauss_models(d_spk, n_spk, d_models)
+    if timings is not None:
+        timings.setdefault('reseg_models', []).append(ctx.last_ms('gauss_models'))
+    if detail is not None:
+        detail['dropped'] = [(int(spk_file[s]), int(spk_label[s])) for s in np.nonzero(ok == 0)[0]]
+    d_scores = ctx.dev_scratch('reseg_scores', max(int((te - tb).sum()), 1) * n_cols * 4)
+    frame_off = ctx.gauss_loglik(d_frames, total_frames, d_models, ok, tb, te, spk_base[owner], n_spk_file[owner],
+                                 n_cols, d_scores)
+    if timings is not None:
+        timings.setdefault('reseg_loglik', []).append(ctx.last_ms('gauss_loglik'))
+    zero = np.zeros(n_cols)
+    tok_off, tok_frame, tok_word, _ = ctx.vad_viterbi_batch(d_scores, frame_off, n_cols, np.arange(n_cols), zero, zero,
+                                                            zero - penalty)
+    if timings is not None:
+        timings.setdefault('reseg_viterbi', []).append(ctx.last_ms('vad_viterbi'))
+        timings.setdefault('reseg_backtrack', []).append(ctx.last_ms('vad_backtrack'))
+    # label of word w in a turn of file f: the file's w-th speaker (a word past the file's speakers
+    # is never decoded: its column is -inf beside column 0, which wins every tie)
+    file_labels = np.zeros((n_files, n_cols), dtype=np.int64)
+    file_labels[spk_file, np.arange(n_spk) - spk_base[spk_file]] = spk_label
+    rows, turn = _reseg_rows(tok_off, tok_frame, tok_word, ls, le, file_labels[owner], rate, text_contract)
+    bounds = np.searchsorted(owner[turn], np.arange(n_files + 1))
+    return [rows[bounds[i]:bounds[i + 1]] for i in range(n_files)]
+
+
 def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl=DIA2_CL, timings=None,
                          detail=None, first_guess_scale=1.0):
     """diarize_batch(fused=True) with the hand-off between the two stages on the device: the
@@ -615,7 +719,7 @@ def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2
 
 
 def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl=DIA2_CL, timings=None,
-                  text_contract=True, fused=False, handoff=None, link=None, detail=None):
+                  text_contract=True, fused=False, handoff=None, link=None, detail=None, reseg=None):
     """CD (gw/BIC) + CL (hi/BIC) for a batch; returns per file an array of rows
     [start_s, end_s, speaker] in recipe order.
     cl['method'] = 'in' clusters with spk_cluster_in (cluster_batch): host hand-off only; the
@@ -635,8 +739,18 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     link: a dictionary like LINK_CL; the speakers of the files are then linked across the batch
     (link_batch) and the rows' third column holds the global speakers -- segments, times and
     order are those of link=None.  Host hand-off only.  detail: a dict; receives link_batch's
-    result as detail['link'] = dict(maps, merges, stat_max, stat_min)."""
+    result as detail['link'] = dict(maps, merges, stat_max, stat_min).
+    reseg: a dictionary like RESEG; the rows are then those of resegment_batch on the records and
+    labels clustering left: every turn decoded frame by frame under the file's speaker models, so
+    the boundaries sit where the evidence changes instead of on the detector's candidate grid.
+    Either clustering method, any detector; host hand-off only.  With link as well, linking runs
+    on the clustering segments as without reseg and the resegmented rows' third column is mapped
+    through its maps.  detail['dropped'] as resegment_batch.  reseg=None: today's rows."""
     method = _method(cl)
+    if reseg is not None:
+        _reseg_penalty(reseg)
+        if handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi'):
+            raise ValueError('reseg takes the host hand-off')
     if _cd_method(cd) in ('sw', 'm'):
         if fused or handoff == 'device':
             raise ValueError('cd method %s takes the host hand-off and is not fused' % _cd_method(cd))
@@ -660,16 +774,31 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
         if link is not None and detail is not None:
             detail['link'] = dict(maps=[np.zeros(0, dtype=np.int32) for _ in files], merges=[],
                                   stat_max=float('nan'), stat_min=float('nan'))
+        if reseg is not None and detail is not None:
+            detail['dropped'] = []
         return [np.zeros((0, 3)) for _ in files]
-    return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail)
+    return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail, reseg,
+                              text_contract)
 
 
-def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link=None, detail=None):
-    box = None if link is None else []
+def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link=None, detail=None,
+                       reseg=None, text_contract=True):
+    box = None if link is None and reseg is None else []
     res = cluster_batch(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fused=fs, stats_out=box)
     cnt = [len(s) for s in segs]
     if sum(cnt) == 0:
         return [np.zeros((0, 3)) for _ in segs]
+    if reseg is not None:
+        own = [lab for (lab, _) in res]
+        rows = resegment_batch(ctx, d_frames, total_frames, files, box[0][0], box[0][1], own, rate, reseg,
+                               text_contract, timings, detail)
+        if link is not None:
+            maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], own, link, timings)
+            for r, m in zip(rows, maps):
+                r[:, 2] = m[r[:, 2].astype(np.int64)] if len(r) else r[:, 2]
+            if detail is not None:
+                detail['link'] = dict(maps=maps, merges=merges, stat_max=smax, stat_min=smin)
+        return rows
     allseg = np.concatenate([np.asarray(s, dtype=np.float64).reshape(-1, 2) for s in segs])
     if link is None:
         labels = np.concatenate([lab for (lab, _) in res])
