@@ -99,7 +99,7 @@ enum {
     SPKD_T_CALL = 0, SPKD_T_CHUNK_STATS, SPKD_T_REDUCE_SETS, SPKD_T_PAIR_TERMS,
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
-    SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
+    SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
     SPKD_N_TIMERS
 };
 spkd_status spkd_last_kernel_ms(spkd_ctx *ctx, int which, float *ms);
@@ -689,6 +689,78 @@ spkd_status spkd_gauss_loglik(spkd_ctx *ctx, const float *d_frames, int64_t n_fr
                               int64_t n_seq, const int64_t *h_seq_begin, const int64_t *h_seq_end,
                               const int32_t *h_seq_model, const int32_t *h_seq_n_models,
                               int32_t n_cols, float *d_scores);
+
+/* ---------------------------------------------------------------------------
+ * (9) Resegmentation with mixture models: a diagonal-covariance Gaussian mixture per speaker,
+ * trained by EM on the device from the speaker's own frames, and the log-likelihood of every frame
+ * of a set of sequences under the mixtures of its file's speakers.  These two calls stand where
+ * spkd_sum_stats + spkd_gauss_models and spkd_gauss_loglik stand in (8); the decoder behind them is
+ * the same spkd_vad_viterbi_batch call.  One full-covariance Gaussian suits a comparison of whole
+ * segments; a frame-level decoder on speech, whose frames fall into several phonetic modes, is
+ * better served by a small mixture.
+ * PARITY: no reference counterpart; tests/reseg_gmm_numpy.py restates both calls in numpy.
+ *
+ * A speaker model is n_comp = K components of SPKD_GMM_COMP = 80 doubles, speaker s at
+ * d_gmm + s * K * 80:
+ *   [0]        ln w
+ *   [1, 40)    mean
+ *   [40, 79)   1 / var
+ *   [79]       log_norm = -1/2 (39 ln 2pi + sum_d ln var_d)
+ *
+ * spkd_gmm_train: speaker s owns the absolute frame ranges [h_range_begin[r], h_range_end[r]) for r
+ * in h_set_off[s] .. h_set_off[s + 1], in that order; its frames are numbered 0 .. N - 1 in that
+ * order.  All arithmetic is fp64 on the float32 frames.
+ *   V_d, the ML (biased) variance of all N frames, sets the floor var_floor * V_d of every variance.
+ *   Initial model (from_model = 0), "segmental": component k takes the frames with the ordinals
+ *     [floor(k N / K), floor((k + 1) N / K)): w = count / N, their mean and ML variance, floored.
+ *   from_model != 0: the start is what d_gmm holds.
+ *   An iteration: with l_k = ln w_k + log_norm_k - 1/2 sum_d (x_d - mean_kd)^2 / var_kd,
+ *     m = max_k l_k and g_k = exp(l_k - m) / sum_j exp(l_j - m) per frame (a component whose ln w
+ *     is -inf takes no part), G_k = sum g_k, A_kd = sum g_k x_d, B_kd = sum g_k x_d^2 and
+ *     L = sum (m + ln sum_j exp(l_j - m)) over the frames; h_loglik[s * n_iter + i] = L of the model
+ *     that entered iteration i.  Then w_k = G_k / N (ln w = -inf for G_k = 0) and, when G_k >= 2,
+ *     mean = A / G, var = max(B / G - mean^2, var_floor * V_d); otherwise the component keeps its
+ *     mean and variance.
+ *   h_ok[s] = 0, without an error status, when N < 40 K, when a V_d is not a finite number > 0
+ *   (constant frames, frames that are not finite), when an accumulator or L of any step is not
+ *   finite, or when a model value written is not finite (a variance of 0 under var_floor = 0): the
+ *   rule of spkd_gauss_models -- a speaker that cannot be modelled is never chosen.  Its model may
+ *   hold anything.
+ *   n_iter = 0 is the initial model alone.  The whole loop is enqueued on the context's stream
+ *   inside the one call, with no host trip between iterations; h_ok and h_loglik come back once,
+ *   through pinned memory the context owns, as the index arrays go up in one copy.
+ *   Determinism: a speaker's ordinals are cut into tiles of SPKD_GMM_TILE = 64 and chunks of
+ *   SPKD_GMM_CHUNK_TILES = 16 tiles; every sum runs in ordinal order inside a chunk and in chunk
+ *   order across them, without atomics.  The bits of a speaker's model depend neither on the run
+ *   nor on the grid nor on the other speakers of the call, and n_iter = n in one call equals n
+ *   calls of n_iter = 1 with from_model = 1.
+ *   SPKD_EINVAL before any device work, outputs untouched: a null pointer (h_loglik may be NULL
+ *   when n_iter = 0), K outside [1, SPKD_GMM_MAX_COMP = 8], n_iter < 0, var_floor not finite or < 0,
+ *   h_set_off not starting at 0, a set without a range, a range outside [0, n_frames] or with
+ *   end < begin, d_gmm not 16-byte aligned.  n_speakers = 0: SPKD_OK without a launch.
+ *   Timer: SPKD_T_GMM_TRAIN (all launches of the call).
+ *
+ * spkd_gmm_loglik_seq: spkd_gauss_loglik with mixtures: column k < n_models(q) of a frame is
+ *   m + ln sum_j exp(l_j - m) under the sequence's k-th speaker (n_models models of n_comp components
+ *   in d_gmm, h_model_ok spkd_gmm_train's h_ok), in fp64, rounded once to float32 on the store.  A
+ *   model that is not ok and the columns past the sequence's models give -inf; frames that are not
+ *   finite propagate NaN.  Compact scores, limits (1 <= n_cols <= 16), refusals (and n_comp outside
+ *   [1, 8]), the one upload of the index arrays and the tile (SPKD_GMM_TILE) are spkd_gauss_loglik's.
+ *   Timer: SPKD_T_GMM_SEQ_LOGLIK. */
+#define SPKD_GMM_COMP 80
+#define SPKD_GMM_MAX_COMP 8
+#define SPKD_GMM_TILE 64
+#define SPKD_GMM_CHUNK_TILES 16
+spkd_status spkd_gmm_train(spkd_ctx *ctx, const float *d_frames, int64_t n_frames, int64_t n_speakers,
+                           const int64_t *h_set_off, const int64_t *h_range_begin,
+                           const int64_t *h_range_end, int32_t n_comp, int32_t n_iter,
+                           int32_t from_model, double var_floor, double *d_gmm, int32_t *h_ok,
+                           double *h_loglik);
+spkd_status spkd_gmm_loglik_seq(spkd_ctx *ctx, const float *d_frames, int64_t n_frames,
+                                const double *d_gmm, int32_t n_comp, int64_t n_models,
+                                const int32_t *h_model_ok, int64_t n_seq, const int64_t *h_seq_begin,
+                                const int64_t *h_seq_end, const int32_t *h_seq_model,
+                                const int32_t *h_seq_n_models, int32_t n_cols, float *d_scores);
 
 /* ---------------------------------------------------------------------------
  * (5) Host-side helpers of the boundary (no GPU work).

@@ -24,14 +24,17 @@
 #include "spkd_vad.hpp"
 #include "spkd_vad_batch.hpp"
 #include "spkd_gauss.hpp"
+#include "spkd_gmm_train.hpp"
 
 using namespace spkd;
 
 namespace {
-constexpr int N_SLOTS = 48;
+constexpr int N_SLOTS = 56;
 // pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused), of spkd_vad_viterbi_batch and of
-// spkd_sum_stats and spkd_gauss_loglik (their index arrays on their way up)
-enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX, N_PIN };
+// spkd_sum_stats, spkd_gauss_loglik, spkd_gmm_train and spkd_gmm_loglik_seq (their index arrays on their way up;
+// spkd_gmm_train's ok flags and log-likelihoods on their way down)
+enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
+       PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, N_PIN };
 }
 
 struct spkd_ctx {
@@ -257,7 +260,8 @@ enum {
     S_GW_N_WIN, S_GW_WIN_DET, S_GW_WIN_MAXD, S_GW_DET_START, S_GW_DET_MAXI, S_GW_DET_D, S_GW_FINAL_START, S_LOG,
     S_AHC_STATS, S_AHC_LD, S_AHC_AUX, S_AHC_MAT, S_AHC_MISC, S_AHC_OUT, S_AHC_OFF, S_AHC_PROB, S_AHC_PACKED, S_MFCC_TAB, S_MFCC_STATIC, S_MFCC_TW,
     S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX,
-    S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX, S_COUNT
+    S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
+    S_GT_TAB, S_GT_WORK, S_GT_IDX, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -2293,6 +2297,181 @@ spkd_status spkd_gauss_loglik(spkd_ctx* c, const float* d_frames, int64_t n_fram
     {
         Timer t(c, SPKD_T_GAUSS_LOGLIK);
         hipLaunchKernelGGL(k_gauss_loglik, dim3((unsigned)n_tiles), dim3(WAVE), 0, c->stream, d_frames, d_models,
+                           (const int*)d.ok, (const long long*)d.begin, (const long long*)d.end, (const long long*)d.row,
+                           (const long long*)d.tile, (const int*)d.model, (const int*)d.n_models, (const int*)d.tile_seq,
+                           (int)n_cols, d_scores);
+    }
+    HIPCHK(c, hipGetLastError());
+    return call.finish();
+}
+
+// ------------------------------------------------------------------ (9) mixture speaker models and their scores
+static_assert(GT_COMP == SPKD_GMM_COMP && GT_MAX_COMP == SPKD_GMM_MAX_COMP && GT_TILE == SPKD_GMM_TILE &&
+              GT_CHUNK_TILES == SPKD_GMM_CHUNK_TILES, "the header states the kernels' layout and partition");
+
+spkd_status spkd_gmm_train(spkd_ctx* c, const float* d_frames, int64_t n_frames, int64_t n_speakers,
+                           const int64_t* h_set_off, const int64_t* h_range_begin, const int64_t* h_range_end,
+                           int32_t n_comp, int32_t n_iter, int32_t from_model, double var_floor, double* d_gmm,
+                           int32_t* h_ok, double* h_loglik) {
+    if (!c || n_speakers < 0) return SPKD_EINVAL;
+    if (n_speakers == 0) return SPKD_OK;
+    if (!d_frames || !h_set_off || !h_range_begin || !h_range_end || !d_gmm || !h_ok || (n_iter > 0 && !h_loglik))
+        return fail(c, SPKD_EINVAL, "null argument");
+    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "gmm_train: 1 <= n_comp <= 8");
+    if (n_iter < 0) return fail(c, SPKD_EINVAL, "gmm_train: n_iter >= 0");
+    if (!(var_floor >= 0.0) || !std::isfinite(var_floor)) return fail(c, SPKD_EINVAL, "gmm_train: var_floor must be finite and >= 0");
+    if (n_frames < 0 || n_speakers > 0x7fffffff) return fail(c, SPKD_EINVAL, "gmm_train: bad count");
+    if ((uintptr_t)d_gmm % 16 || (uintptr_t)d_frames % 4) return fail(c, SPKD_EINVAL, "gmm_train: misaligned buffer (models: 16 bytes)");
+    if (h_set_off[0] != 0) return fail(c, SPKD_EINVAL, "gmm_train: set_off[0] must be 0");
+    for (int64_t s = 0; s < n_speakers; ++s)
+        if (h_set_off[s + 1] <= h_set_off[s]) return fail(c, SPKD_EINVAL, "gmm_train: set_off must ascend: no empty set");
+    const int64_t n_ranges = h_set_off[n_speakers];
+    const size_t ns = (size_t)n_speakers, nr = (size_t)n_ranges;
+    int64_t n_chunks = 0;
+    for (int64_t s = 0; s < n_speakers; ++s) {
+        int64_t n = 0;
+        for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
+            const int64_t b = h_range_begin[r], e = h_range_end[r];
+            if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, "gmm_train: range outside [0, n_frames]");
+            n += e - b;
+        }
+        n_chunks += (n + GT_CHUNK - 1) / GT_CHUNK;
+    }
+    if (n_chunks > 0x7fffffff) return fail(c, SPKD_EINVAL, "gmm_train: too many frames in one call");
+    const size_t nc = (size_t)n_chunks, nl = ns * (size_t)n_iter;
+    // every index array as one image in pinned memory: one copy up
+    struct Tab { int64_t *begin, *ord, *set_off, *n, *chunk_off; int32_t *chunk_spk, *chunk_idx; } h, d;
+    auto parts = [&](Layout L, Tab& t) {
+        return L.part(t.begin, nr).part(t.ord, nr).part(t.set_off, ns + 1).part(t.n, ns).part(t.chunk_off, ns + 1)
+            .part(t.chunk_spk, nc).part(t.chunk_idx, nc).bytes();
+    };
+    size_t image = 0;
+    TRY(carve(c, pinned, PIN_GT_TAB, [&](Layout L) { return image = parts(L, h); }));
+    std::memcpy(h.begin, h_range_begin, nr * sizeof(int64_t));
+    std::memcpy(h.set_off, h_set_off, (ns + 1) * sizeof(int64_t));
+    int64_t chunk = 0;
+    for (size_t s = 0; s < ns; ++s) {
+        int64_t n = 0;
+        for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
+            h.ord[r] = n;
+            n += h_range_end[r] - h_range_begin[r];
+        }
+        h.n[s] = n;
+        h.chunk_off[s] = chunk;
+        for (int64_t i = 0; i < (n + GT_CHUNK - 1) / GT_CHUNK; ++i, ++chunk) {
+            h.chunk_spk[chunk] = (int32_t)s;
+            h.chunk_idx[chunk] = (int32_t)i;
+        }
+    }
+    h.chunk_off[ns] = chunk;
+    // what comes back: the ok flags and the log-likelihoods, through pinned memory as well
+    struct Out { double* loglik; int32_t* ok; } ho, dout;
+    double *d_part = nullptr, *d_part_ll = nullptr, *d_floor = nullptr;
+    auto outs = [&](Layout L, Out& o) { return L.part(o.loglik, nl).part(o.ok, ns).bytes(); };
+    size_t out_bytes = 0;
+    TRY(carve(c, pinned, PIN_GT_OUT, [&](Layout L) { return out_bytes = outs(L, ho); }));
+    Call call(c);
+    TRY(call.opened);
+    TRY(carve(c, scratch, S_GT_TAB, [&](Layout L) { return parts(L, d); }));
+    TRY(carve(c, scratch, S_GT_WORK, [&](Layout L) {
+        outs(L, dout);                                                   // (first: one copy down)
+        L.at = out_bytes;
+        return L.part(d_part, nc * (size_t)n_comp * GT_COMP).part(d_part_ll, nc).part(d_floor, ns * WAVE).bytes();
+    }));
+    HIPCHK(c, hipMemcpyAsync(d.begin, h.begin, image, hipMemcpyHostToDevice, c->stream));
+    {
+        Timer t(c, SPKD_T_GMM_TRAIN);
+        auto estep = [&](bool hard) {
+            if (!nc) return;
+            if (hard)
+                hipLaunchKernelGGL(k_gmm_estep<true>, dim3((unsigned)nc), dim3(WAVE), 0, c->stream, d_frames,
+                                   (const long long*)d.begin, (const long long*)d.ord, (const long long*)d.set_off,
+                                   (const long long*)d.n, (const int*)d.chunk_spk, (const int*)d.chunk_idx,
+                                   (const double*)d_gmm, (int)n_comp, d_part, d_part_ll);
+            else
+                hipLaunchKernelGGL(k_gmm_estep<false>, dim3((unsigned)nc), dim3(WAVE), 0, c->stream, d_frames,
+                                   (const long long*)d.begin, (const long long*)d.ord, (const long long*)d.set_off,
+                                   (const long long*)d.n, (const int*)d.chunk_spk, (const int*)d.chunk_idx,
+                                   (const double*)d_gmm, (int)n_comp, d_part, d_part_ll);
+        };
+        auto mstep = [&](int init, int iter) {
+            hipLaunchKernelGGL(k_gmm_mstep, dim3((unsigned)ns), dim3(WAVE), 0, c->stream, (const double*)d_part,
+                               (const double*)d_part_ll, (const long long*)d.chunk_off, (const long long*)d.n, (int)n_comp,
+                               init, from_model ? 0 : 1, var_floor, iter, (int)n_iter, d_gmm, d_floor, (int*)dout.ok,
+                               dout.loglik);
+        };
+        // the whole loop in one go: the hard pass (floor, first ok, initial model), then n_iter EM steps
+        estep(true);
+        mstep(1, 0);
+        for (int i = 0; i < n_iter; ++i) {
+            estep(false);
+            mstep(0, i);
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(ho.loglik, dout.loglik, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    TRY(call.finish());
+    std::memcpy(h_ok, ho.ok, ns * sizeof(int32_t));
+    if (nl) std::memcpy(h_loglik, ho.loglik, nl * sizeof(double));
+    return SPKD_OK;
+}
+
+spkd_status spkd_gmm_loglik_seq(spkd_ctx* c, const float* d_frames, int64_t n_frames, const double* d_gmm,
+                                int32_t n_comp, int64_t n_models, const int32_t* h_model_ok, int64_t n_seq,
+                                const int64_t* h_seq_begin, const int64_t* h_seq_end, const int32_t* h_seq_model,
+                                const int32_t* h_seq_n_models, int32_t n_cols, float* d_scores) {
+    if (!c || n_seq < 0) return SPKD_EINVAL;
+    if (n_seq == 0) return SPKD_OK;
+    if (!d_frames || !d_gmm || !h_model_ok || !h_seq_begin || !h_seq_end || !h_seq_model || !h_seq_n_models || !d_scores)
+        return fail(c, SPKD_EINVAL, "null argument");
+    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: 1 <= n_comp <= 8");
+    if (n_cols < 1 || n_cols > GS_MAX_COLS) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: 1 <= n_cols <= 16");
+    if (n_frames < 0 || n_models < 0 || n_models > 0x7fffffff || n_seq > 0x7fffffff)
+        return fail(c, SPKD_EINVAL, "gmm_loglik_seq: bad count");
+    if ((uintptr_t)d_gmm % 16 || (uintptr_t)d_frames % 4 || (uintptr_t)d_scores % 4)
+        return fail(c, SPKD_EINVAL, "gmm_loglik_seq: misaligned buffer (models: 16 bytes)");
+    int64_t total = 0, n_tiles = 0;
+    for (int64_t q = 0; q < n_seq; ++q) {
+        const int64_t b = h_seq_begin[q], e = h_seq_end[q];
+        if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: sequence outside [0, n_frames]");
+        const int64_t m = h_seq_model[q], k = h_seq_n_models[q];
+        if (k < 0 || k > n_cols) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: 0 <= models of a sequence <= n_cols");
+        if (m < 0 || m + k > n_models) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: model index out of range");
+        total += e - b;
+        n_tiles += (e - b + GT_TILE - 1) / GT_TILE;
+    }
+    if (total == 0) return SPKD_OK;
+    if (n_tiles > 0x7fffffff) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: too many frames in one call");
+    const size_t ns = (size_t)n_seq, nm = (size_t)n_models, nt = (size_t)n_tiles;
+    // every index array as one image in pinned memory: one copy up
+    struct Tab { int64_t *begin, *end, *row, *tile; int32_t *model, *n_models, *ok, *tile_seq; } h, d;
+    auto parts = [&](Layout L, Tab& t) {
+        return L.part(t.begin, ns).part(t.end, ns).part(t.row, ns).part(t.tile, ns).part(t.model, ns).part(t.n_models, ns)
+            .part(t.ok, nm).part(t.tile_seq, nt).bytes();
+    };
+    size_t image = 0;
+    TRY(carve(c, pinned, PIN_GT_IDX, [&](Layout L) { return image = parts(L, h); }));
+    std::memcpy(h.begin, h_seq_begin, ns * sizeof(int64_t));
+    std::memcpy(h.end, h_seq_end, ns * sizeof(int64_t));
+    std::memcpy(h.model, h_seq_model, ns * sizeof(int32_t));
+    std::memcpy(h.n_models, h_seq_n_models, ns * sizeof(int32_t));
+    std::memcpy(h.ok, h_model_ok, nm * sizeof(int32_t));
+    int64_t row = 0, tile = 0;
+    for (size_t q = 0; q < ns; ++q) {
+        h.row[q] = row;
+        h.tile[q] = tile;
+        const int64_t len = h.end[q] - h.begin[q], k = (len + GT_TILE - 1) / GT_TILE;
+        for (int64_t i = 0; i < k; ++i) h.tile_seq[tile + i] = (int32_t)q;
+        row += len;
+        tile += k;
+    }
+    Call call(c);
+    TRY(call.opened);
+    TRY(carve(c, scratch, S_GT_IDX, [&](Layout L) { return parts(L, d); }));
+    HIPCHK(c, hipMemcpyAsync(d.begin, h.begin, image, hipMemcpyHostToDevice, c->stream));
+    {
+        Timer t(c, SPKD_T_GMM_SEQ_LOGLIK);
+        hipLaunchKernelGGL(k_gmm_loglik_seq, dim3((unsigned)n_tiles), dim3(WAVE), 0, c->stream, d_frames, d_gmm, (int)n_comp,
                            (const int*)d.ok, (const long long*)d.begin, (const long long*)d.end, (const long long*)d.row,
                            (const long long*)d.tile, (const int*)d.model, (const int*)d.n_models, (const int*)d.tile_seq,
                            (int)n_cols, d_scores);

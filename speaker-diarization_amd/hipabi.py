@@ -17,10 +17,14 @@ MERGE_NO_AHEAD = 1
 TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pair_terms',
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
-                                        'mfcc_static', 'mfcc_post'])}
+                                        'gmm_train', 'gmm_seq_loglik', 'mfcc_static', 'mfcc_post'])}
 VAD_TILE = 32       # SPKD_VAD_TILE: frames per score / back-pointer tile of k_vad_viterbi
 GAUSS_TILE = 64     # SPKD_GAUSS_TILE: frames per workgroup of k_gauss_loglik
 GAUSS_MODEL = 820   # SPKD_GAUSS_MODEL: doubles per model (mu[39], W = L^-1 packed lower [780], c)
+GMM_COMP = 80       # SPKD_GMM_COMP: doubles per mixture component (ln w, mean[39], 1 / var[39], log_norm)
+GMM_MAX_COMP = 8    # SPKD_GMM_MAX_COMP: components per speaker
+GMM_TILE = 64       # SPKD_GMM_TILE: frame ordinals per tile of k_gmm_estep, frames per workgroup of k_gmm_loglik_seq
+GMM_CHUNK_TILES = 16    # SPKD_GMM_CHUNK_TILES: tiles per chunk, the unit of a partial sum of k_gmm_estep
 REC = 820
 DIM = 39
 
@@ -31,7 +35,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
-           'spkd_gauss_models', 'spkd_gauss_loglik']
+           'spkd_gauss_models', 'spkd_gauss_loglik', 'spkd_gmm_train', 'spkd_gmm_loglik_seq']
 
 
 class CdParams(C.Structure):
@@ -208,6 +212,8 @@ def load_library(path=None):
     lib.spkd_vad_viterbi_batch.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, P(vp), P(vp), P(vp), P(vp)]
     lib.spkd_gauss_models.argtypes = [vp, vp, i64, vp, vp]
     lib.spkd_gauss_loglik.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp]
+    lib.spkd_gmm_train.argtypes = [vp, vp, i64, i64, vp, vp, vp, i32, i32, i32, dbl, vp, vp, vp]
+    lib.spkd_gmm_loglik_seq.argtypes = [vp, vp, i64, vp, i32, i64, vp, i64, vp, vp, vp, vp, i32, vp]
     lib.spkd_gw_lines.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, dbl, C.c_int, i64, vp, vp, vp, vp, vp]
     if lib.spkd_abi_version() != 2:
         raise ImportError('libspkd_hip.so ABI version mismatch')
@@ -793,6 +799,49 @@ class Context(object):
         self.check(self.lib.spkd_gauss_loglik(self.h, C.c_void_p(d_frames), int(n_frames), C.c_void_p(d_models), len(ok),
                                               _ptr(ok), len(b), _ptr(b), _ptr(e), _ptr(m), _ptr(k), int(n_cols),
                                               C.c_void_p(d_scores)))
+        frame_off = np.zeros(len(b) + 1, dtype=np.int64)
+        frame_off[1:] = np.cumsum(e - b)
+        return frame_off
+
+    # ---- (9) resegmentation with mixture models
+    def gmm_train(self, d_frames, n_frames, set_off, range_begin, range_end, n_comp, n_iter, var_floor, d_gmm,
+                  from_model=False):
+        """One diagonal-covariance mixture of n_comp components (GMM_COMP doubles each: ln w, mean,
+        1 / var, log_norm) per speaker into d_gmm, trained by n_iter EM steps on the device
+        (spkd_gmm_train): speaker s owns the frame ranges set_off[s] .. set_off[s + 1] of range_begin /
+        range_end, in that order.  from_model: start from what d_gmm holds instead of the segmental
+        initial model.  Returns (ok int32 [n_speakers], loglik [n_speakers, n_iter]): ok 0 for a
+        speaker that cannot be modelled (fewer than 40 n_comp frames, constant or non-finite frames),
+        loglik[s, i] the total log-likelihood of speaker s's frames under the model that entered
+        iteration i.  The time of all its kernels is last_ms('gmm_train')."""
+        c = np.ascontiguousarray
+        off, b, e = c(set_off, dtype=np.int64), c(range_begin, dtype=np.int64), c(range_end, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1 or b.ndim != 1 or e.ndim != 1:
+            raise SpkdError(SPKD_EINVAL, 'set_off: one entry per speaker and the total')
+        if not (len(b) == len(e) == int(off[-1])):
+            raise SpkdError(SPKD_EINVAL, 'one begin and end per range of the sets')
+        n = len(off) - 1
+        ok = np.zeros(n, dtype=np.int32)
+        ll = np.zeros((n, max(int(n_iter), 0)), dtype=np.float64)
+        self.check(self.lib.spkd_gmm_train(self.h, C.c_void_p(d_frames), int(n_frames), n, _ptr(off), _ptr(b), _ptr(e),
+                                           int(n_comp), int(n_iter), 1 if from_model else 0, float(var_floor),
+                                           C.c_void_p(d_gmm), _ptr(ok), _ptr(ll) if ll.size else None))
+        return ok, ll
+
+    def gmm_loglik_seq(self, d_frames, n_frames, d_gmm, n_comp, model_ok, seq_begin, seq_end, seq_model, seq_n_models,
+                       n_cols, d_scores):
+        """gauss_loglik under mixtures (spkd_gmm_loglik_seq): d_gmm holds len(model_ok) models of n_comp
+        components as gmm_train leaves them, model_ok its ok.  Returns frame_off.  The kernel's time
+        is last_ms('gmm_seq_loglik')."""
+        c = np.ascontiguousarray
+        ok = c(model_ok, dtype=np.int32)
+        b, e = c(seq_begin, dtype=np.int64), c(seq_end, dtype=np.int64)
+        m, k = c(seq_model, dtype=np.int32), c(seq_n_models, dtype=np.int32)
+        if any(a.ndim != 1 for a in (ok, b, e, m, k)) or not (len(b) == len(e) == len(m) == len(k)):
+            raise SpkdError(SPKD_EINVAL, 'one begin, end, first model and model count per sequence')
+        self.check(self.lib.spkd_gmm_loglik_seq(self.h, C.c_void_p(d_frames), int(n_frames), C.c_void_p(d_gmm), int(n_comp),
+                                                len(ok), _ptr(ok), len(b), _ptr(b), _ptr(e), _ptr(m), _ptr(k), int(n_cols),
+                                                C.c_void_p(d_scores)))
         frame_off = np.zeros(len(b) + 1, dtype=np.int64)
         frame_off[1:] = np.cumsum(e - b)
         return frame_off

@@ -31,6 +31,11 @@ LINK_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
 # whose frames are correlated in time, will want it tuned.
 RESEG = dict(penalty=50.0)
 RESEG_MAX_SPEAKERS = 16          # of one file: the decoder's word limit (spkd_vad_viterbi_batch)
+# the same stage under mixture models: a diagonal-covariance GMM per speaker, trained on the device
+# (spkd_gmm_train) from the frames of the speaker's segments.  Settings, not measurements: four
+# components and five EM steps are what small per-speaker mixtures usually get; the floor is a share
+# of the variance of all the speaker's frames.
+RESEG_GMM = dict(penalty=50.0, model='gmm', components=4, iterations=5, var_floor=0.01)
 
 
 class BatchFile(object):
@@ -393,11 +398,10 @@ def _lines_per_file(lines, owner, n_files, timings, _t0, _t1, _t2):
     return out
 
 
-def segment_stats(ctx, d_frames, total_frames, files, segments, rate=125.0, timings=None, fused=None,
-                  scratch_name='segment_stats'):
-    """The statistics record of every segment (get_spk_features + the np.cov inputs,
-    spk-clustering.py:46-52, 88-94) -> (device pointer to n records in segment order,
-    seg_off per file, n, time stamp after the host preparation).  fused: see cluster_batch."""
+def _segment_ranges(files, segments, rate):
+    """The absolute frame range of every segment of a batch, in segment order (get_spk_features,
+    spk-clustering.py:46-52: int() truncation, the clamps of a slice) -> (seg_off per file, n,
+    begin, end)."""
     cnt = [len(s) for s in segments]
     seg_off = np.zeros(len(files) + 1, dtype=np.int64)
     seg_off[1:] = np.cumsum(cnt)
@@ -408,7 +412,15 @@ def segment_stats(ctx, d_frames, total_frames, files, segments, rate=125.0, timi
     fn = np.array([f.n_frames for f in files], dtype=np.int64)[owner]
     a0 = np.clip((allseg[:, 0] * rate).astype(np.int64), 0, fn)
     a1 = np.maximum(a0, np.clip((allseg[:, 1] * rate).astype(np.int64), 0, fn))
-    b, e = foff + a0, foff + a1
+    return seg_off, n, foff + a0, foff + a1
+
+
+def segment_stats(ctx, d_frames, total_frames, files, segments, rate=125.0, timings=None, fused=None,
+                  scratch_name='segment_stats'):
+    """The statistics record of every segment (get_spk_features + the np.cov inputs,
+    spk-clustering.py:46-52, 88-94) -> (device pointer to n records in segment order,
+    seg_off per file, n, time stamp after the host preparation).  fused: see cluster_batch."""
+    seg_off, n, b, e = _segment_ranges(files, segments, rate)
     d_stats = ctx.dev_scratch(scratch_name, max(n, 1) * hipabi.REC * 8)
     _t1 = time.perf_counter()
     if fused is None:
@@ -570,6 +582,27 @@ def _reseg_penalty(reseg):
     return p
 
 
+def _reseg_model(reseg):
+    """The speaker model of a `reseg` dictionary: ('gauss',) -- also when the key is absent -- or
+    ('gmm', components, iterations, var_floor), the keys RESEG_GMM names (its values where one is
+    absent)."""
+    m = reseg.get('model', 'gauss')
+    if m == 'gauss':
+        return ('gauss',)
+    if m != 'gmm':
+        raise ValueError('reseg model: gauss or gmm')
+    k = reseg.get('components', RESEG_GMM['components'])
+    it = reseg.get('iterations', RESEG_GMM['iterations'])
+    fl = float(reseg.get('var_floor', RESEG_GMM['var_floor']))
+    if int(k) != k or not 1 <= k <= hipabi.GMM_MAX_COMP:
+        raise ValueError('reseg components: 1 .. %d' % hipabi.GMM_MAX_COMP)
+    if int(it) != it or it < 0:
+        raise ValueError('reseg iterations: an integer >= 0')
+    if not np.isfinite(fl) or fl < 0.0:
+        raise ValueError('reseg var_floor: a finite number >= 0 (a share of the variance of all the speaker\'s frames)')
+    return ('gmm', int(k), int(it), fl)
+
+
 def _reseg_rows(tok_off, tok_frame, tok_word, turn_start_s, turn_end_s, turn_labels, rate, text_contract):
     """The rows of a decoded batch of turns, in turn order: token k of a turn, opening at the
     relative frame f_k, is [turn_start_s + f_k / rate, turn_start_s + f_{k+1} / rate, label]; a turn's
@@ -590,7 +623,7 @@ def _reseg_rows(tok_off, tok_frame, tok_word, turn_start_s, turn_end_s, turn_lab
 
 
 def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels, rate=125.0, reseg=RESEG,
-                    text_contract=True, timings=None, detail=None):
+                    text_contract=True, timings=None, detail=None, segments=None):
     """Viterbi resegmentation of a clustered batch on the device: the closing pass of a BIC
     segmentation + agglomerative clustering system (the reference has none).  d_stats, seg_off,
     labels: the segment records, the files' offsets and the per-file labels of a cluster_batch
@@ -609,9 +642,30 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     all--inf rule applies and the file's lowest label takes the turn.  detail: a dict; receives
     dropped = [(file, label)] of those speakers.  More than 16 speakers in one file, a negative or
     non-finite penalty: ValueError before any device work.  timings: reseg_models, reseg_loglik,
-    reseg_viterbi, reseg_backtrack (kernel ms)."""
+    reseg_viterbi, reseg_backtrack (kernel ms).
+    reseg['model'] = 'gmm' (RESEG_GMM): every speaker is a diagonal-covariance mixture of
+    reseg['components'] Gaussians instead, trained on the device by reseg['iterations'] EM steps from
+    a segmental start (spkd_gmm_train; variances floored at reseg['var_floor'] times the variance of
+    all the speaker's frames) on the frame ranges of its segments, in segment order.  segments: per
+    file the (start_s, end_s) arrays cluster_batch took -- the ranges are the ones segment_stats
+    summed (_segment_ranges); d_stats is not read.  The turns are scored by spkd_gmm_loglik_seq and
+    decoded by the same call.  A speaker of fewer than 40 frames a component, or of constant or
+    non-finite frames, is dropped as above.  detail['loglik']: per speaker (link_speakers' order) the
+    log-likelihood of its frames under the model entering each iteration.  timings: reseg_gmm_train
+    instead of reseg_models; reseg_loglik is the mixture scorer's.  An unknown model, components
+    outside 1 .. 8, negative iterations, a negative or non-finite floor, no segments: ValueError
+    before any device work."""
     rate = float(rate)
     penalty = _reseg_penalty(reseg)
+    model = _reseg_model(reseg)
+    if model[0] == 'gmm':
+        if segments is None:
+            raise ValueError('reseg model gmm trains on the frames: it takes segments, the arrays cluster_batch took')
+        if len(segments) != len(files):
+            raise ValueError('one segment array per file')
+        seg_off_s, _, seg_b, seg_e = _segment_ranges(files, segments, rate)
+        if seg_off_s.tolist() != np.asarray(seg_off, dtype=np.int64).tolist():
+            raise ValueError('segments: one per label, file by file')
     member, set_off, spk_file, spk_label = link_speakers(seg_off, labels)
     n_files = len(files)
     if len(labels) != n_files:
@@ -634,19 +688,33 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     n_spk, n_cols = len(spk_file), int(n_spk_file.max())
     spk_base = np.zeros(n_files + 1, dtype=np.int64)
     spk_base[1:] = np.cumsum(n_spk_file)
-    d_spk = ctx.dev_scratch('reseg_speaker_stats', n_spk * hipabi.REC * 8)
-    ctx.sum_stats(d_stats, int(seg_off[-1]), member, set_off, d_spk)
-    d_models = ctx.dev_scratch('reseg_models', n_spk * hipabi.GAUSS_MODEL * 8)
-    ok = ctx.gauss_models(d_spk, n_spk, d_models)
-    if timings is not None:
-        timings.setdefault('reseg_models', []).append(ctx.last_ms('gauss_models'))
+    if model[0] == 'gmm':
+        _, n_comp, n_iter, var_floor = model
+        d_models = ctx.dev_scratch('reseg_gmm', n_spk * n_comp * hipabi.GMM_COMP * 8)
+        ok, loglik = ctx.gmm_train(d_frames, total_frames, set_off, seg_b[member], seg_e[member], n_comp, n_iter,
+                                   var_floor, d_models)
+        if timings is not None:
+            timings.setdefault('reseg_gmm_train', []).append(ctx.last_ms('gmm_train'))
+        if detail is not None:
+            detail['loglik'] = loglik
+    else:
+        d_spk = ctx.dev_scratch('reseg_speaker_stats', n_spk * hipabi.REC * 8)
+        ctx.sum_stats(d_stats, int(seg_off[-1]), member, set_off, d_spk)
+        d_models = ctx.dev_scratch('reseg_models', n_spk * hipabi.GAUSS_MODEL * 8)
+        ok = ctx.gauss_models(d_spk, n_spk, d_models)
+        if timings is not None:
+            timings.setdefault('reseg_models', []).append(ctx.last_ms('gauss_models'))
     if detail is not None:
         detail['dropped'] = [(int(spk_file[s]), int(spk_label[s])) for s in np.nonzero(ok == 0)[0]]
     d_scores = ctx.dev_scratch('reseg_scores', max(int((te - tb).sum()), 1) * n_cols * 4)
-    frame_off = ctx.gauss_loglik(d_frames, total_frames, d_models, ok, tb, te, spk_base[owner], n_spk_file[owner],
-                                 n_cols, d_scores)
+    if model[0] == 'gmm':
+        frame_off = ctx.gmm_loglik_seq(d_frames, total_frames, d_models, n_comp, ok, tb, te, spk_base[owner],
+                                       n_spk_file[owner], n_cols, d_scores)
+    else:
+        frame_off = ctx.gauss_loglik(d_frames, total_frames, d_models, ok, tb, te, spk_base[owner], n_spk_file[owner],
+                                     n_cols, d_scores)
     if timings is not None:
-        timings.setdefault('reseg_loglik', []).append(ctx.last_ms('gauss_loglik'))
+        timings.setdefault('reseg_loglik', []).append(ctx.last_ms('gmm_seq_loglik' if model[0] == 'gmm' else 'gauss_loglik'))
     zero = np.zeros(n_cols)
     tok_off, tok_frame, tok_word, _ = ctx.vad_viterbi_batch(d_scores, frame_off, n_cols, np.arange(n_cols), zero, zero,
                                                             zero - penalty)
@@ -745,10 +813,13 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     the boundaries sit where the evidence changes instead of on the detector's candidate grid.
     Either clustering method, any detector; host hand-off only.  With link as well, linking runs
     on the clustering segments as without reseg and the resegmented rows' third column is mapped
-    through its maps.  detail['dropped'] as resegment_batch.  reseg=None: today's rows."""
+    through its maps.  detail['dropped'] as resegment_batch.  reseg=None: today's rows.  A dictionary
+    like RESEG_GMM decodes under mixture models trained on the clustering segments' frames
+    (resegment_batch, model 'gmm'; detail['loglik'] as there)."""
     method = _method(cl)
     if reseg is not None:
         _reseg_penalty(reseg)
+        _reseg_model(reseg)
         if handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi'):
             raise ValueError('reseg takes the host hand-off')
     if _cd_method(cd) in ('sw', 'm'):
@@ -791,7 +862,7 @@ def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timin
     if reseg is not None:
         own = [lab for (lab, _) in res]
         rows = resegment_batch(ctx, d_frames, total_frames, files, box[0][0], box[0][1], own, rate, reseg,
-                               text_contract, timings, detail)
+                               text_contract, timings, detail, segs)
         if link is not None:
             maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], own, link, timings)
             for r, m in zip(rows, maps):
