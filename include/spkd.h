@@ -99,7 +99,8 @@ enum {
     SPKD_T_CALL = 0, SPKD_T_CHUNK_STATS, SPKD_T_REDUCE_SETS, SPKD_T_PAIR_TERMS,
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
-    SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
+    SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
+    SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
     SPKD_N_TIMERS
 };
 spkd_status spkd_last_kernel_ms(spkd_ctx *ctx, int which, float *ms);
@@ -761,6 +762,67 @@ spkd_status spkd_gmm_loglik_seq(spkd_ctx *ctx, const float *d_frames, int64_t n_
                                 const int32_t *h_model_ok, int64_t n_seq, const int64_t *h_seq_begin,
                                 const int64_t *h_seq_end, const int32_t *h_seq_model,
                                 const int32_t *h_seq_n_models, int32_t n_cols, float *d_scores);
+
+/* ---------------------------------------------------------------------------
+ * (10) Linking speakers across files by cross-likelihood ratio: every speaker's zeroth- and
+ * first-order statistics under one universal background model (UBM), and agglomerative clustering of
+ * those records under MAP-adapted means.  One full-covariance Gaussian (spkd_sum_stats + spkd_ahc
+ * with BIC) suits a segment; a whole speaker's frames fall into several modes whose shares differ
+ * from recording to recording, and over 10^3 .. 10^5 frames no BIC penalty bridges the two Gaussians
+ * that gives.  The records add under a merge, so the frames are read once.
+ * PARITY: no reference counterpart; tests/link_clr_numpy.py restates both calls in numpy.
+ *
+ * The UBM is ONE model of n_comp = C components in spkd_gmm_train's layout (SPKD_GMM_COMP doubles a
+ * component), e.g. spkd_gmm_train's model of one speaker that owns the ranges of all speakers.  A
+ * speaker record is C components of SPKD_BW_COMP = 40 doubles, speaker s at d_bw + s * C * 40:
+ *   [0]        n_c = sum g_c(x)
+ *   [1, 40)    f_c = sum g_c(x) x
+ * over the speaker's frames, g_c exactly the g_k of spkd_gmm_train's iteration under the UBM (a
+ * component whose ln w is -inf takes no part: its n and f are 0).  All arithmetic is fp64 on the
+ * float32 frames.
+ *
+ * spkd_ubm_stats: the speakers and their frames are given as to spkd_gmm_train (h_set_off,
+ *   h_range_begin, h_range_end; a range may be empty).  Determinism is spkd_gmm_train's: tiles of
+ *   SPKD_GMM_TILE ordinals, chunks of SPKD_GMM_CHUNK_TILES tiles, ordinal order inside a chunk and
+ *   chunk order across chunks, no atomics; the bits of a record depend neither on the run nor on the
+ *   grid nor on the other speakers of the call.  Every frame is read once (156 bytes); the index
+ *   arrays go up in one copy through pinned memory the context owns, h_ok comes back once.
+ *   h_ok[s] = 0, without an error status, when the speaker has no frame or when a sum is not finite.
+ *   SPKD_EINVAL before any device work, outputs untouched: spkd_gmm_train's rules for the pointers,
+ *   the sets and the ranges, C outside [1, SPKD_GMM_MAX_COMP], d_ubm or d_bw not 16-byte aligned.
+ *   n_speakers = 0: SPKD_OK without a launch.  Timer: SPKD_T_UBM_STATS (both launches).
+ *
+ * spkd_clr_link: the whole agglomerative chain over n records in one call, no host trip per merge.
+ *   With the UBM's means mu and variances, the relevance r and N = sum_c n_c (component order):
+ *     m_c = (f_c + r mu_c) / (n_c + r)                                   (MAP, means only)
+ *     H(a|b) = (1 / N_a) sum_c sum_d [(m^b_cd - mu_cd) f^a_cd - 1/2 n^a_c ((m^b_cd)^2 - mu_cd^2)] / var_cd
+ *     CLR(a, b) = H(a|b) + H(b|a)                                        (higher: more alike)
+ *   H(a|b) is the log-likelihood ratio per frame of a's frames under b's adapted model against the
+ *   UBM at the UBM's alignment.  A step: over the clusters whose h_ok is set, the pair a < b of the
+ *   highest CLR, the first in row-major order on a tie.  It is merged when CLR > threshold, or when
+ *   max_spk > 0 and more than max_spk clusters are in the list (those whose h_ok is 0 included);
+ *   otherwise, and when fewer than two ok clusters are left, the chain stops.  A merge is
+ *   record[a] += record[b] and speakers.pop(b): later indices shift down, the convention of spkd_ahc's
+ *   log, replayable by spkd_labels_from_merges.  Only row and column a are computed again.  A speaker
+ *   whose h_ok is 0 is never chosen and keeps its own label (the rule of spkd_gauss_models).
+ *   h_merge_a / h_merge_b / h_merge_d take up to n - 1 entries; h_stat_max / h_stat_min are the
+ *   extremes of the initial matrix (NaN when it has no pair).  d_bw is not modified.
+ *   A CLR among ok speakers that is not finite: SPKD_ENONFINITE, with the log so far.
+ *   Limits: n <= SPKD_CLR_MAX_N = 4096 (the chain is one workgroup whose per-row state waits in LDS;
+ *   the matrix is n^2 doubles of device scratch).  SPKD_EINVAL before any device work, outputs
+ *   untouched: a null pointer, n above the limit, C outside [1, SPKD_GMM_MAX_COMP], r not finite or
+ *   <= 0, threshold NaN, max_spk < 0, d_bw or d_ubm not 16-byte aligned.  n = 0: SPKD_OK without a
+ *   launch; n = 1: no merge.  Timer: SPKD_T_CLR_LINK (all launches of the call). */
+#define SPKD_BW_COMP 40
+#define SPKD_CLR_MAX_N 4096
+spkd_status spkd_ubm_stats(spkd_ctx *ctx, const float *d_frames, int64_t n_frames, const double *d_ubm,
+                           int32_t n_comp, int64_t n_speakers, const int64_t *h_set_off,
+                           const int64_t *h_range_begin, const int64_t *h_range_end, double *d_bw,
+                           int32_t *h_ok);
+spkd_status spkd_clr_link(spkd_ctx *ctx, const double *d_bw, int64_t n, const int32_t *h_ok,
+                          const double *d_ubm, int32_t n_comp, double relevance, double threshold,
+                          int32_t max_spk, int32_t *h_merge_a, int32_t *h_merge_b, double *h_merge_d,
+                          int32_t *h_n_merges, double *h_stat_max, double *h_stat_min);
 
 /* ---------------------------------------------------------------------------
  * (5) Host-side helpers of the boundary (no GPU work).

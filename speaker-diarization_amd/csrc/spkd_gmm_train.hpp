@@ -64,6 +64,67 @@ __device__ inline long long gt_frame(const long long* __restrict__ ord, const lo
     return begin[lo] + (o - ord[lo]);
 }
 
+// the frames of the tile of ordinals [o0, o0 + len) of the speaker that owns the ranges [r0, r1), staged
+// in xs (fr: the tile's absolute frames): a lane per frame finds it, then coalesced loads
+__device__ inline void gt_stage_tile(const float* __restrict__ frames, const long long* __restrict__ range_ord,
+                                     const long long* __restrict__ range_begin, long long r0, long long r1,
+                                     long long o0, int len, int lane, long long* fr, float* xs) {
+    if (lane < len) fr[lane] = gt_frame(range_ord, range_begin, r0, r1, o0 + lane);
+    __syncthreads();
+    constexpr int PF = (GT_TILE * D + WAVE - 1) / WAVE;              // 39 floats a lane
+#pragma unroll 13
+    for (int k = 0; k < PF; ++k) {
+        const int idx = lane + WAVE * k;
+        if (idx < len * D) {
+            const int j = idx / D;
+            xs[idx] = frames[fr[j] * D + (idx - j * D)];
+        }
+    }
+    __syncthreads();
+}
+
+// phase 1 of a soft pass, the lane's frame of the staged tile under the K components of M (a
+// wave-uniform address): its responsibilities g_k to gl[k * GT_TILE + lane] (0 for a component whose
+// ln w is -inf: it takes no part), its log-likelihood to lls[lane]
+__device__ inline void gt_responsibilities(const float* xs, const double* __restrict__ M, int K, int lane,
+                                           double* gl, double* lls) {
+    float x[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) x[j] = xs[lane * D + j];
+#pragma unroll 1
+    for (int k = 0; k < K; ++k) {
+        const double* __restrict__ Mk = M + k * GT_COMP;
+        if (Mk[0] == -INFINITY) continue;                   // (wave-uniform) contributes nothing
+        double q = 0.0;
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            const double d = (double)x[j] - Mk[GT_MEAN + j];
+            q = fma(d * d, Mk[GT_IVAR + j], q);
+        }
+        gl[k * GT_TILE + lane] = fma(-0.5, q, Mk[0] + Mk[GT_NORM]);
+    }
+    double m = -INFINITY;
+#pragma unroll 1
+    for (int k = 0; k < K; ++k)
+        if (M[k * GT_COMP] != -INFINITY) {
+            const double l = gl[k * GT_TILE + lane];
+            if (l > m) m = l;
+        }
+    double sum = 0.0;
+#pragma unroll 1
+    for (int k = 0; k < K; ++k) {
+        double e = 0.0;
+        if (M[k * GT_COMP] != -INFINITY) {
+            e = exp(gl[k * GT_TILE + lane] - m);
+            sum += e;
+        }
+        gl[k * GT_TILE + lane] = e;
+    }
+#pragma unroll 1
+    for (int k = 0; k < K; ++k) gl[k * GT_TILE + lane] /= sum;
+    lls[lane] = m + log(sum);
+}
+
 template <bool HARD>
 __global__ __launch_bounds__(WAVE) void k_gmm_estep(
         const float* __restrict__ frames, const long long* __restrict__ range_begin,
@@ -88,18 +149,7 @@ __global__ __launch_bounds__(WAVE) void k_gmm_estep(
         const long long o0 = c0 + (long long)t * GT_TILE;
         if (o0 >= N) break;                                             // (wave-uniform)
         const int len = N - o0 < GT_TILE ? (int)(N - o0) : GT_TILE;
-        if (lane < len) fr[lane] = gt_frame(range_ord, range_begin, r0, r1, o0 + lane);
-        __syncthreads();
-        constexpr int PF = (GT_TILE * D + WAVE - 1) / WAVE;              // 39 floats a lane
-#pragma unroll 13
-        for (int k = 0; k < PF; ++k) {
-            const int idx = lane + WAVE * k;
-            if (idx < len * D) {
-                const int j = idx / D;
-                xs[idx] = frames[fr[j] * D + (idx - j * D)];
-            }
-        }
-        __syncthreads();
+        gt_stage_tile(frames, range_ord, range_begin, r0, r1, o0, len, lane, fr, xs);
         if (lane < len) {
             if (HARD) {
                 const long long o = o0 + lane;
@@ -107,41 +157,7 @@ __global__ __launch_bounds__(WAVE) void k_gmm_estep(
                     gl[k * GT_TILE + lane] = (o >= k * N / K && o < (k + 1) * N / K) ? 1.0 : 0.0;
                 lls[lane] = 0.0;
             } else {
-                float x[D];
-#pragma unroll
-                for (int j = 0; j < D; ++j) x[j] = xs[lane * D + j];
-#pragma unroll 1
-                for (int k = 0; k < K; ++k) {
-                    const double* __restrict__ Mk = M + k * GT_COMP;
-                    if (Mk[0] == -INFINITY) continue;                   // (wave-uniform) contributes nothing
-                    double q = 0.0;
-#pragma unroll
-                    for (int j = 0; j < D; ++j) {
-                        const double d = (double)x[j] - Mk[GT_MEAN + j];
-                        q = fma(d * d, Mk[GT_IVAR + j], q);
-                    }
-                    gl[k * GT_TILE + lane] = fma(-0.5, q, Mk[0] + Mk[GT_NORM]);
-                }
-                double m = -INFINITY;
-#pragma unroll 1
-                for (int k = 0; k < K; ++k)
-                    if (M[k * GT_COMP] != -INFINITY) {
-                        const double l = gl[k * GT_TILE + lane];
-                        if (l > m) m = l;
-                    }
-                double sum = 0.0;
-#pragma unroll 1
-                for (int k = 0; k < K; ++k) {
-                    double e = 0.0;
-                    if (M[k * GT_COMP] != -INFINITY) {
-                        e = exp(gl[k * GT_TILE + lane] - m);
-                        sum += e;
-                    }
-                    gl[k * GT_TILE + lane] = e;
-                }
-#pragma unroll 1
-                for (int k = 0; k < K; ++k) gl[k * GT_TILE + lane] /= sum;
-                lls[lane] = m + log(sum);
+                gt_responsibilities(xs, M, K, lane, gl, lls);
             }
         }
         __syncthreads();

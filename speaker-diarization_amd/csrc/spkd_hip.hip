@@ -25,16 +25,19 @@
 #include "spkd_vad_batch.hpp"
 #include "spkd_gauss.hpp"
 #include "spkd_gmm_train.hpp"
+#include "spkd_ubm_stats.hpp"
+#include "spkd_clr.hpp"
 
 using namespace spkd;
 
 namespace {
-constexpr int N_SLOTS = 56;
+constexpr int N_SLOTS = 64;
 // pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused), of spkd_vad_viterbi_batch and of
 // spkd_sum_stats, spkd_gauss_loglik, spkd_gmm_train and spkd_gmm_loglik_seq (their index arrays on their way up;
-// spkd_gmm_train's ok flags and log-likelihoods on their way down)
+// spkd_gmm_train's ok flags and log-likelihoods on their way down), and of spkd_ubm_stats and spkd_clr_link
+// (index arrays and ok flags up; ok flags, the merge log and its statistics down)
 enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
-       PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, N_PIN };
+       PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, N_PIN };
 }
 
 struct spkd_ctx {
@@ -261,7 +264,7 @@ enum {
     S_AHC_STATS, S_AHC_LD, S_AHC_AUX, S_AHC_MAT, S_AHC_MISC, S_AHC_OUT, S_AHC_OFF, S_AHC_PROB, S_AHC_PACKED, S_MFCC_TAB, S_MFCC_STATIC, S_MFCC_TW,
     S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX,
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
-    S_GT_TAB, S_GT_WORK, S_GT_IDX, S_COUNT
+    S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -2478,6 +2481,156 @@ spkd_status spkd_gmm_loglik_seq(spkd_ctx* c, const float* d_frames, int64_t n_fr
     }
     HIPCHK(c, hipGetLastError());
     return call.finish();
+}
+
+// ------------------------------------------------------------------ (10) linking by cross-likelihood ratio
+static_assert(BW_COMP == SPKD_BW_COMP && CL_MAX_N == SPKD_CLR_MAX_N, "the header states the record and the limit");
+
+spkd_status spkd_ubm_stats(spkd_ctx* c, const float* d_frames, int64_t n_frames, const double* d_ubm, int32_t n_comp,
+                           int64_t n_speakers, const int64_t* h_set_off, const int64_t* h_range_begin,
+                           const int64_t* h_range_end, double* d_bw, int32_t* h_ok) {
+    if (!c || n_speakers < 0) return SPKD_EINVAL;
+    if (n_speakers == 0) return SPKD_OK;
+    if (!d_frames || !d_ubm || !h_set_off || !h_range_begin || !h_range_end || !d_bw || !h_ok)
+        return fail(c, SPKD_EINVAL, "null argument");
+    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "ubm_stats: 1 <= n_comp <= 8");
+    if (n_frames < 0 || n_speakers > 0x7fffffff) return fail(c, SPKD_EINVAL, "ubm_stats: bad count");
+    if ((uintptr_t)d_ubm % 16 || (uintptr_t)d_bw % 16 || (uintptr_t)d_frames % 4)
+        return fail(c, SPKD_EINVAL, "ubm_stats: misaligned buffer (model and records: 16 bytes)");
+    if (h_set_off[0] != 0) return fail(c, SPKD_EINVAL, "ubm_stats: set_off[0] must be 0");
+    for (int64_t s = 0; s < n_speakers; ++s)
+        if (h_set_off[s + 1] <= h_set_off[s]) return fail(c, SPKD_EINVAL, "ubm_stats: set_off must ascend: no empty set");
+    const int64_t n_ranges = h_set_off[n_speakers];
+    const size_t ns = (size_t)n_speakers, nr = (size_t)n_ranges;
+    int64_t n_chunks = 0;
+    for (int64_t s = 0; s < n_speakers; ++s) {
+        int64_t n = 0;
+        for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
+            const int64_t b = h_range_begin[r], e = h_range_end[r];
+            if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, "ubm_stats: range outside [0, n_frames]");
+            n += e - b;
+        }
+        n_chunks += (n + GT_CHUNK - 1) / GT_CHUNK;
+    }
+    if (n_chunks > 0x7fffffff) return fail(c, SPKD_EINVAL, "ubm_stats: too many frames in one call");
+    const size_t nc = (size_t)n_chunks;
+    // every index array as one image in pinned memory: one copy up (spkd_gmm_train's table)
+    struct Tab { int64_t *begin, *ord, *set_off, *n, *chunk_off; int32_t *chunk_spk, *chunk_idx; } h, d;
+    auto parts = [&](Layout L, Tab& t) {
+        return L.part(t.begin, nr).part(t.ord, nr).part(t.set_off, ns + 1).part(t.n, ns).part(t.chunk_off, ns + 1)
+            .part(t.chunk_spk, nc).part(t.chunk_idx, nc).bytes();
+    };
+    size_t image = 0;
+    TRY(carve(c, pinned, PIN_UBM_TAB, [&](Layout L) { return image = parts(L, h); }));
+    std::memcpy(h.begin, h_range_begin, nr * sizeof(int64_t));
+    std::memcpy(h.set_off, h_set_off, (ns + 1) * sizeof(int64_t));
+    int64_t chunk = 0;
+    for (size_t s = 0; s < ns; ++s) {
+        int64_t n = 0;
+        for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
+            h.ord[r] = n;
+            n += h_range_end[r] - h_range_begin[r];
+        }
+        h.n[s] = n;
+        h.chunk_off[s] = chunk;
+        for (int64_t i = 0; i < (n + GT_CHUNK - 1) / GT_CHUNK; ++i, ++chunk) {
+            h.chunk_spk[chunk] = (int32_t)s;
+            h.chunk_idx[chunk] = (int32_t)i;
+        }
+    }
+    h.chunk_off[ns] = chunk;
+    void* h_out = nullptr;
+    TRY(pinned(c, PIN_UBM_OUT, ns * sizeof(int32_t), &h_out));
+    Call call(c);
+    TRY(call.opened);
+    TRY(carve(c, scratch, S_UBM_TAB, [&](Layout L) { return parts(L, d); }));
+    double* d_part = nullptr;
+    int32_t* d_ok = nullptr;
+    TRY(carve(c, scratch, S_UBM_WORK, [&](Layout L) {
+        return L.part(d_part, nc * (size_t)n_comp * BW_COMP).part(d_ok, ns).bytes();
+    }));
+    HIPCHK(c, hipMemcpyAsync(d.begin, h.begin, image, hipMemcpyHostToDevice, c->stream));
+    {
+        Timer t(c, SPKD_T_UBM_STATS);
+        if (nc)
+            hipLaunchKernelGGL(k_ubm_estep, dim3((unsigned)nc), dim3(WAVE), 0, c->stream, d_frames,
+                               (const long long*)d.begin, (const long long*)d.ord, (const long long*)d.set_off,
+                               (const long long*)d.n, (const int*)d.chunk_spk, (const int*)d.chunk_idx, d_ubm, (int)n_comp,
+                               d_part);
+        hipLaunchKernelGGL(k_ubm_reduce, dim3((unsigned)ns), dim3(WAVE), 0, c->stream, (const double*)d_part,
+                           (const long long*)d.chunk_off, (const long long*)d.n, (int)n_comp, d_bw, (int*)d_ok);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_out, d_ok, ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TRY(call.finish());
+    std::memcpy(h_ok, h_out, ns * sizeof(int32_t));
+    return SPKD_OK;
+}
+
+spkd_status spkd_clr_link(spkd_ctx* c, const double* d_bw, int64_t n, const int32_t* h_ok, const double* d_ubm,
+                          int32_t n_comp, double relevance, double threshold, int32_t max_spk, int32_t* h_merge_a,
+                          int32_t* h_merge_b, double* h_merge_d, int32_t* h_n_merges, double* h_stat_max,
+                          double* h_stat_min) {
+    if (!c || n < 0) return SPKD_EINVAL;
+    if (n == 0) return SPKD_OK;
+    if (!d_bw || !h_ok || !d_ubm || !h_merge_a || !h_merge_b || !h_merge_d || !h_n_merges || !h_stat_max || !h_stat_min)
+        return fail(c, SPKD_EINVAL, "null argument");
+    if (n > CL_MAX_N) return fail(c, SPKD_EINVAL, "clr_link: at most 4096 speakers");
+    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "clr_link: 1 <= n_comp <= 8");
+    if (!(relevance > 0.0) || !std::isfinite(relevance)) return fail(c, SPKD_EINVAL, "clr_link: relevance must be finite and > 0");
+    if (std::isnan(threshold)) return fail(c, SPKD_EINVAL, "clr_link: threshold is NaN");
+    if (max_spk < 0) return fail(c, SPKD_EINVAL, "clr_link: max_spk >= 0");
+    if ((uintptr_t)d_bw % 16 || (uintptr_t)d_ubm % 16)
+        return fail(c, SPKD_EINVAL, "clr_link: misaligned buffer (model and records: 16 bytes)");
+    const double nan = std::nan("");
+    if (n == 1) {                                                        // nothing to compare
+        *h_n_merges = 0;
+        *h_stat_max = *h_stat_min = nan;
+        return SPKD_OK;
+    }
+    const size_t ns = (size_t)n, ne = ns * (size_t)n_comp * BW_COMP;
+    struct Out { double *d, *stat; int32_t *a, *b, *nm; } ho, dout;
+    auto outs = [&](Layout L, Out& o) { return L.part(o.d, ns).part(o.stat, 2).part(o.a, ns).part(o.b, ns).part(o.nm, 1).bytes(); };
+    size_t out_bytes = 0;
+    TRY(carve(c, pinned, PIN_CLR_OUT, [&](Layout L) { return out_bytes = outs(L, ho); }));
+    void* h_in = nullptr;
+    TRY(pinned(c, PIN_CLR_IN, ns * sizeof(int32_t), &h_in));
+    std::memcpy(h_in, h_ok, ns * sizeof(int32_t));
+    Call call(c);
+    TRY(call.opened);
+    double *d_w = nullptr, *d_t = nullptr, *d_n = nullptr;
+    int32_t* d_ok = nullptr;
+    void* d_mat = nullptr;
+    TRY(carve(c, scratch, S_CLR_WORK, [&](Layout L) {
+        outs(L, dout);                                                   // (first: one copy down)
+        L.at = out_bytes;
+        return L.part(d_w, ne).part(d_t, ne).part(d_n, ns).part(d_ok, ns).bytes();
+    }));
+    TRY(scratch(c, S_CLR_MAT, ns * ns * sizeof(double), &d_mat));
+    HIPCHK(c, hipMemcpyAsync(d_ok, h_in, ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    {
+        Timer t(c, SPKD_T_CLR_LINK);
+        hipLaunchKernelGGL(k_clr_prep, dim3((unsigned)ns), dim3(WAVE), 0, c->stream, d_bw, d_ubm, (int)n_comp, relevance,
+                           d_w, d_t, d_n);
+        hipLaunchKernelGGL(k_clr_matrix, dim3((unsigned)ns), dim3(CL_MAT_TPB), 0, c->stream, (const double*)d_w,
+                           (const double*)d_t, (const double*)d_n, (const int*)d_ok, (int)n, (int)n_comp, (double*)d_mat,
+                           c->d_err);
+        hipLaunchKernelGGL(k_clr_chain, dim3(1), dim3(CL_TPB), 0, c->stream, d_w, d_t, d_n, (double*)d_mat,
+                           (const int*)d_ok, (int)n, (int)n_comp, d_ubm, relevance, threshold, (int)max_spk, (int*)dout.a,
+                           (int*)dout.b, dout.d, (int*)dout.nm, dout.stat, c->d_err);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(ho.d, dout.d, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    const spkd_status st = call.finish();
+    if (st != SPKD_OK && st != SPKD_ENONFINITE) return st;
+    const int32_t nm = *ho.nm;                                           // (the log so far when a CLR was not finite)
+    *h_n_merges = nm;
+    std::memcpy(h_merge_a, ho.a, (size_t)nm * sizeof(int32_t));
+    std::memcpy(h_merge_b, ho.b, (size_t)nm * sizeof(int32_t));
+    std::memcpy(h_merge_d, ho.d, (size_t)nm * sizeof(double));
+    *h_stat_max = ho.stat[0];
+    *h_stat_min = ho.stat[1];
+    return st;
 }
 
 // ------------------------------------------------------------------ (5) host helpers

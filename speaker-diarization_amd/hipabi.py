@@ -17,7 +17,8 @@ MERGE_NO_AHEAD = 1
 TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pair_terms',
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
-                                        'gmm_train', 'gmm_seq_loglik', 'mfcc_static', 'mfcc_post'])}
+                                        'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
+                                        'mfcc_static', 'mfcc_post'])}
 VAD_TILE = 32       # SPKD_VAD_TILE: frames per score / back-pointer tile of k_vad_viterbi
 GAUSS_TILE = 64     # SPKD_GAUSS_TILE: frames per workgroup of k_gauss_loglik
 GAUSS_MODEL = 820   # SPKD_GAUSS_MODEL: doubles per model (mu[39], W = L^-1 packed lower [780], c)
@@ -25,6 +26,8 @@ GMM_COMP = 80       # SPKD_GMM_COMP: doubles per mixture component (ln w, mean[3
 GMM_MAX_COMP = 8    # SPKD_GMM_MAX_COMP: components per speaker
 GMM_TILE = 64       # SPKD_GMM_TILE: frame ordinals per tile of k_gmm_estep, frames per workgroup of k_gmm_loglik_seq
 GMM_CHUNK_TILES = 16    # SPKD_GMM_CHUNK_TILES: tiles per chunk, the unit of a partial sum of k_gmm_estep
+BW_COMP = 40        # SPKD_BW_COMP: doubles per component of a speaker record under a UBM (n_c, f_c[39])
+CLR_MAX_N = 4096    # SPKD_CLR_MAX_N: speakers of one spkd_clr_link
 REC = 820
 DIM = 39
 
@@ -35,7 +38,8 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
-           'spkd_gauss_models', 'spkd_gauss_loglik', 'spkd_gmm_train', 'spkd_gmm_loglik_seq']
+           'spkd_gauss_models', 'spkd_gauss_loglik', 'spkd_gmm_train', 'spkd_gmm_loglik_seq',
+           'spkd_ubm_stats', 'spkd_clr_link']
 
 
 class CdParams(C.Structure):
@@ -214,6 +218,8 @@ def load_library(path=None):
     lib.spkd_gauss_loglik.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp]
     lib.spkd_gmm_train.argtypes = [vp, vp, i64, i64, vp, vp, vp, i32, i32, i32, dbl, vp, vp, vp]
     lib.spkd_gmm_loglik_seq.argtypes = [vp, vp, i64, vp, i32, i64, vp, i64, vp, vp, vp, vp, i32, vp]
+    lib.spkd_ubm_stats.argtypes = [vp, vp, i64, vp, i32, i64, vp, vp, vp, vp, vp]
+    lib.spkd_clr_link.argtypes = [vp, vp, i64, vp, vp, i32, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]
     lib.spkd_gw_lines.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, dbl, C.c_int, i64, vp, vp, vp, vp, vp]
     if lib.spkd_abi_version() != 2:
         raise ImportError('libspkd_hip.so ABI version mismatch')
@@ -845,6 +851,45 @@ class Context(object):
         frame_off = np.zeros(len(b) + 1, dtype=np.int64)
         frame_off[1:] = np.cumsum(e - b)
         return frame_off
+
+    # ---- (10) linking by cross-likelihood ratio
+    def ubm_stats(self, d_frames, n_frames, d_ubm, n_comp, set_off, range_begin, range_end, d_bw):
+        """The record of every speaker under the one UBM at d_ubm (n_comp components as gmm_train leaves
+        them) into d_bw: BW_COMP doubles a component, n_c = sum g_c and f_c = sum g_c x over the
+        speaker's frames (spkd_ubm_stats).  The speakers own their ranges as in gmm_train.  Returns ok
+        int32 [n_speakers]: 0 for a speaker without a frame or with a sum that is not finite.  The
+        kernels' time is last_ms('ubm_stats')."""
+        c = np.ascontiguousarray
+        off, b, e = c(set_off, dtype=np.int64), c(range_begin, dtype=np.int64), c(range_end, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1 or b.ndim != 1 or e.ndim != 1:
+            raise SpkdError(SPKD_EINVAL, 'set_off: one entry per speaker and the total')
+        if not (len(b) == len(e) == int(off[-1])):
+            raise SpkdError(SPKD_EINVAL, 'one begin and end per range of the sets')
+        n = len(off) - 1
+        ok = np.zeros(n, dtype=np.int32)
+        self.check(self.lib.spkd_ubm_stats(self.h, C.c_void_p(d_frames), int(n_frames), C.c_void_p(d_ubm), int(n_comp), n,
+                                           _ptr(off), _ptr(b), _ptr(e), C.c_void_p(d_bw), _ptr(ok)))
+        return ok
+
+    def clr_link(self, d_bw, ok, d_ubm, n_comp, relevance, threshold, max_spk=0):
+        """The agglomerative chain over the len(ok) records at d_bw by cross-likelihood ratio under
+        means MAP-adapted from the UBM (spkd_clr_link), in one call.  Returns dict(status, n_merges, a,
+        b, d, stat_max, stat_min): the merge log in spkd_ahc's convention (labels_from_merges replays
+        it); status is SPKD_ENONFINITE, with the log so far, when a ratio among ok speakers was not
+        finite.  The kernels' time is last_ms('clr_link')."""
+        ok = np.ascontiguousarray(ok, dtype=np.int32)
+        if ok.ndim != 1:
+            raise SpkdError(SPKD_EINVAL, 'ok: one flag per record')
+        n = len(ok)
+        ma, mb, md = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float64)
+        nm = np.zeros(1, dtype=np.int32)
+        smax, smin = np.full(1, np.nan), np.full(1, np.nan)
+        st = self.lib.spkd_clr_link(self.h, C.c_void_p(d_bw), n, _ptr(ok), C.c_void_p(d_ubm), int(n_comp), float(relevance),
+                                    float(threshold), int(max_spk), _ptr(ma), _ptr(mb), _ptr(md), _ptr(nm), _ptr(smax),
+                                    _ptr(smin))
+        self.check(st, allow=(SPKD_ENONFINITE,))
+        k = int(nm[0])
+        return dict(status=st, n_merges=k, a=ma[:k], b=mb[:k], d=md[:k], stat_max=float(smax[0]), stat_min=float(smin[0]))
 
     # ---- (4)
     def ahc(self, d_stats, seg_off, params):

@@ -26,6 +26,14 @@ SW_CD = dict(method='sw', kind='GLR', lambdac=1.3, threshold=0.0, winsize_s=5.0,
 MERGE_CD = dict(method='m', kind='GLR', lambdac=1.3, threshold=0.0, winsize_s=5.0, winstep_s=0.5, deltaws_s=0.05)
 # linking the speakers of a batch's files (link_batch): the clustering script's own defaults
 LINK_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
+# linking by cross-likelihood ratio instead (link_batch, model 'clr'): a universal background model of
+# `components` diagonal Gaussians trained on the speakers' own frames (spkd_gmm_train: `iterations` EM
+# steps, `var_floor`; at most `ubm_max_frames` frames go in), every speaker's statistics under it
+# (spkd_ubm_stats), means MAP-adapted with `relevance`, and the agglomerative chain of spkd_clr_link:
+# merged while the ratio is above `threshold` (higher is more alike; max_spk as in LINK_CL).  The
+# threshold rests on ONE synthetic fixture (tests/test_link_clr.py), not on speech: tune it on real audio.
+LINK_CLR = dict(model='clr', components=8, iterations=5, var_floor=0.01, relevance=16.0,
+                threshold=-0.5, max_spk=0, ubm_max_frames=2_000_000)
 # Viterbi resegmentation (resegment_batch): the cost of a speaker switch inside a turn, in natural-log
 # units.  On the synthetic generator every value from 10 to 200 decodes the same paths; real audio,
 # whose frames are correlated in time, will want it tuned.
@@ -533,7 +541,81 @@ def link_speakers(seg_off, labels):
     return member, set_off, keys // width, keys % width
 
 
-def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None):
+def _link_model(link):
+    """The model of a `link` dictionary: ('bic',) when the key is absent -- the clustering keys of
+    LINK_CL -- or ('clr', components, iterations, var_floor, relevance, threshold, max_spk,
+    ubm_max_frames), the keys LINK_CLR names (its values where one is absent)."""
+    if 'model' not in link:
+        return ('bic',)
+    if link['model'] != 'clr':
+        raise ValueError('link model: clr (or no model: the clustering keys of LINK_CL)')
+    get = lambda k: link.get(k, LINK_CLR[k])
+    k, it, cap, ms = get('components'), get('iterations'), get('ubm_max_frames'), get('max_spk')
+    fl, r, th = float(get('var_floor')), float(get('relevance')), float(get('threshold'))
+    if int(k) != k or not 1 <= k <= hipabi.GMM_MAX_COMP:
+        raise ValueError('link components: 1 .. %d' % hipabi.GMM_MAX_COMP)
+    if int(it) != it or it < 0:
+        raise ValueError('link iterations: an integer >= 0')
+    if not np.isfinite(fl) or fl < 0.0:
+        raise ValueError('link var_floor: a finite number >= 0 (a share of the variance of all the frames)')
+    if not np.isfinite(r) or r <= 0.0:
+        raise ValueError('link relevance: a finite number > 0')
+    if not np.isfinite(th):
+        raise ValueError('link threshold: a finite number (a ratio above it merges)')
+    if int(ms) != ms or ms < 0:
+        raise ValueError('link max_spk: an integer >= 0')
+    if int(cap) != cap or cap < (hipabi.DIM + 1) * k:
+        raise ValueError('link ubm_max_frames: an integer >= 40 per component')
+    return ('clr', int(k), int(it), fl, r, th, int(ms), int(cap))
+
+
+def ubm_ranges(set_off, begin, end, cap):
+    """What the speakers give to the training of the background model: the ends of their ranges, cut.
+    Speaker s owns the ranges set_off[s] .. set_off[s + 1] of begin / end, its frames numbered in that
+    order.  While the speakers hold at most `cap` frames every range stays whole; beyond that speaker s
+    gives its first floor(cap N_s / N_total) frames -- a range past them is left empty."""
+    set_off, begin, end = (np.asarray(a, dtype=np.int64) for a in (set_off, begin, end))
+    length = end - begin
+    owner = np.repeat(np.arange(len(set_off) - 1), np.diff(set_off))
+    n = np.zeros(len(set_off) - 1, dtype=np.int64)
+    np.add.at(n, owner, length)
+    total = int(n.sum())
+    if total <= cap:
+        return end.copy()
+    share = np.array([int(cap) * int(k) // total for k in n], dtype=np.int64)
+    before = np.concatenate([[0], np.cumsum(length)])[:-1]              # frames in the ranges before this one
+    ord0 = before - before[set_off[:-1]][owner]                         # the ordinal of the range's first frame
+    return begin + np.clip(share[owner] - ord0, 0, length)
+
+
+def _link_clr(ctx, model, set_off, rng_b, rng_e, d_frames, total_frames, timings):
+    """The calls of link_batch under model 'clr' -> (n_merges, a, b, d, stat_max, stat_min), or None
+    when no background model could be trained."""
+    _, n_comp, n_iter, var_floor, relevance, threshold, max_spk, cap = model
+    n_spk = len(set_off) - 1
+    if n_spk > hipabi.CLR_MAX_N:
+        raise ValueError('clr_link: at most %d speakers' % hipabi.CLR_MAX_N)
+    d_ubm = ctx.dev_scratch('link_ubm', n_comp * hipabi.GMM_COMP * 8)
+    ok, _ = ctx.gmm_train(d_frames, total_frames, [0, len(rng_b)], rng_b, ubm_ranges(set_off, rng_b, rng_e, cap),
+                          n_comp, n_iter, var_floor, d_ubm)
+    if timings is not None:
+        timings.setdefault('link_ubm_train', []).append(ctx.last_ms('gmm_train'))
+    if not ok[0]:
+        return None
+    d_bw = ctx.dev_scratch('link_speaker_bw', n_spk * n_comp * hipabi.BW_COMP * 8)
+    spk_ok = ctx.ubm_stats(d_frames, total_frames, d_ubm, n_comp, set_off, rng_b, rng_e, d_bw)
+    if timings is not None:
+        timings.setdefault('link_ubm_stats', []).append(ctx.last_ms('ubm_stats'))
+    r = ctx.clr_link(d_bw, spk_ok, d_ubm, n_comp, relevance, threshold, max_spk)
+    if timings is not None:
+        timings.setdefault('link_clr', []).append(ctx.last_ms('clr_link'))
+    if r['status'] == hipabi.SPKD_ENONFINITE:
+        raise ValueError('array must not contain infs or NaNs')
+    return r['n_merges'], r['a'], r['b'], r['d'], r['stat_max'], r['stat_min']
+
+
+def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None, d_frames=None, total_frames=None,
+               files=None, segments=None, rate=125.0):
     """Which speaker of one file is which speaker of another: spk_cluster_hi over the speakers of
     all files of a batch (spk-clustering.py:178-240 takes `speakers` of any length per entry; the
     command line never gets there, :289).  d_stats, seg_off: the segment records and the files'
@@ -545,12 +627,50 @@ def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None):
     l of file f (0 for a label no segment carries; length 0 for a file without segments), merges
     the log [(a, b, d)] over the speaker list, stat_max / stat_min as spkd_ahc states them.
     More than 16 384 speakers: ValueError.  timings: link_sum (the sum kernel, ms), link_ahc (the
-    clustering call, ms), link_speakers, link_merges."""
+    clustering call, ms), link_speakers, link_merges.
+    link['model'] = 'clr' (LINK_CLR): the speakers are compared by cross-likelihood ratio under a
+    universal background model instead -- one Gaussian is the wrong model of a whole speaker, whose
+    frames fall into several modes in shares that differ from file to file.  This mode trains and
+    scores on frames: it takes d_frames, total_frames, files, segments (the arrays cluster_batch took;
+    the ranges are the ones segment_stats summed) and rate; d_stats is not read.  A speaker's frames
+    are those of its segments in member order.  The background model is spkd_gmm_train's model of ONE
+    speaker that owns the ranges of all speakers in speaker order (cut by ubm_ranges beyond
+    link['ubm_max_frames'] frames); spkd_ubm_stats gives every speaker's record under it from all its
+    frames, spkd_clr_link walks the chain.  Same return; stat_max / stat_min are the extremes of the
+    initial ratios.  When no background model can be trained (too few frames, constant or non-finite
+    frames) every speaker keeps a global label of its own and merges = [].  More than 4 096 speakers,
+    a key out of range, a missing array: ValueError.  timings: link_ubm_train, link_ubm_stats,
+    link_clr (kernel ms), link_speakers, link_merges."""
+    model = _link_model(link)
+    if model[0] == 'clr':
+        if d_frames is None or total_frames is None or files is None or segments is None:
+            raise ValueError('link model clr trains on the frames: it takes d_frames, total_frames, files and '
+                             'segments, the arrays cluster_batch took')
+        if len(segments) != len(files):
+            raise ValueError('one segment array per file')
+        seg_off_s, _, seg_b, seg_e = _segment_ranges(files, segments, float(rate))
+        if seg_off_s.tolist() != np.asarray(seg_off, dtype=np.int64).tolist():
+            raise ValueError('segments: one per label, file by file')
     member, set_off, spk_file, spk_label = link_speakers(seg_off, labels)
     n_spk = len(spk_file)
     maps = [np.zeros(int(np.max(l)) + 1 if len(l) else 0, dtype=np.int32) for l in labels]
     if n_spk == 0:
         return maps, [], float('nan'), float('nan')
+    if model[0] == 'clr':
+        try:
+            r = _link_clr(ctx, model, set_off, seg_b[member], seg_e[member], d_frames, total_frames, timings)
+        except hipabi.SpkdError as e:
+            if e.status == hipabi.SPKD_EINVAL:
+                raise ValueError(str(e))
+            raise
+        nm, a, b, d, smax, smin = r if r is not None else (0, [], [], [], float('nan'), float('nan'))
+        if timings is not None:
+            timings['link_speakers'] = n_spk
+            timings['link_merges'] = nm
+        glob = hipabi.labels_from_merges(n_spk, a, b)
+        for f, l, g in zip(spk_file.tolist(), spk_label.tolist(), glob.tolist()):
+            maps[f][l] = g
+        return maps, list(zip(np.asarray(a).tolist(), np.asarray(b).tolist(), np.asarray(d).tolist())), smax, smin
     d_spk = ctx.dev_scratch('link_speaker_stats', n_spk * hipabi.REC * 8)
     ctx.sum_stats(d_stats, int(seg_off[-1]), member, set_off, d_spk)
     if timings is not None:
@@ -807,7 +927,9 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     link: a dictionary like LINK_CL; the speakers of the files are then linked across the batch
     (link_batch) and the rows' third column holds the global speakers -- segments, times and
     order are those of link=None.  Host hand-off only.  detail: a dict; receives link_batch's
-    result as detail['link'] = dict(maps, merges, stat_max, stat_min).
+    result as detail['link'] = dict(maps, merges, stat_max, stat_min).  A dictionary like LINK_CLR
+    links by cross-likelihood ratio (link_batch, model 'clr'): the frames and the clustering segments
+    are passed through to it.
     reseg: a dictionary like RESEG; the rows are then those of resegment_batch on the records and
     labels clustering left: every turn decoded frame by frame under the file's speaker models, so
     the boundaries sit where the evidence changes instead of on the detector's candidate grid.
@@ -826,6 +948,8 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
         if fused or handoff == 'device':
             raise ValueError('cd method %s takes the host hand-off and is not fused' % _cd_method(cd))
         handoff = 'host'
+    if link is not None:
+        _link_model(link)
     if link is not None and (handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi')):
         raise ValueError('link takes the host hand-off')
     if handoff is None:
@@ -864,7 +988,8 @@ def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timin
         rows = resegment_batch(ctx, d_frames, total_frames, files, box[0][0], box[0][1], own, rate, reseg,
                                text_contract, timings, detail, segs)
         if link is not None:
-            maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], own, link, timings)
+            maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], own, link, timings, d_frames, total_frames,
+                                                  files, segs, rate)
             for r, m in zip(rows, maps):
                 r[:, 2] = m[r[:, 2].astype(np.int64)] if len(r) else r[:, 2]
             if detail is not None:
@@ -874,7 +999,8 @@ def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timin
     if link is None:
         labels = np.concatenate([lab for (lab, _) in res])
     else:
-        maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], [lab for (lab, _) in res], link, timings)
+        maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], [lab for (lab, _) in res], link, timings,
+                                              d_frames, total_frames, files, segs, rate)
         labels = np.concatenate([m[lab] for m, (lab, _) in zip(maps, res)])
         if detail is not None:
             detail['link'] = dict(maps=maps, merges=merges, stat_max=smax, stat_min=smin)

@@ -11,11 +11,17 @@ truth speakers, so the batch has --files x --speakers initial speakers.  Reporte
 Medians and spreads over --runs after a warm-up of each; (a) and (b) must give the same records
 (1e-12 relative: the order of the sums differs) before they are compared.  Wall times are around
 calls that return with their device work finished.  Prints one JSON line.  Run it under
-`timeout`."""
+`timeout`.
+--clr times linking by cross-likelihood ratio instead (pipeline.link_batch with LINK_CLR) on the same
+batch: the kernel times of its three calls -- link_ubm_train (spkd_gmm_train on at most ubm_max_frames
+frames), link_ubm_stats (spkd_ubm_stats over every frame of every speaker, with the GB/s of 156 B a
+frame) and link_clr (spkd_clr_link) -- and the wall time of the whole link_batch, and writes the JSON
+line into DESIGN.md in place of the "Numbers:" line of its section on the mode."""
 import argparse
 import importlib
 import json
 import os
+import re
 import sys
 import time
 
@@ -26,6 +32,45 @@ sys.path.insert(0, ROOT)
 PKG = 'speaker-diarization_amd'
 
 
+NUMBERS = re.compile(r'^Numbers \(link by CLR\):.*$', flags=re.M)
+
+
+def clr_mode(args, ctx, pipeline, ptr, total, file_frames, b, e, seg_off, labels, device):
+    rate = 125.0
+    files = [pipeline.BatchFile(o, n, []) for o, n in file_frames]
+    # a quarter of a frame past each bound: the frame ranges link_batch cuts are the truth's
+    segments = [np.column_stack([(b[lo:hi] - o + 0.25) / rate, (e[lo:hi] - o + 0.25) / rate])
+                for (o, _), lo, hi in zip(file_frames, seg_off[:-1], seg_off[1:])]
+    runs = []
+    for i in range(args.runs + 1):
+        tm = {}
+        t0 = time.perf_counter()
+        maps, merges, smax, smin = pipeline.link_batch(ctx, 0, seg_off, labels, pipeline.LINK_CLR, tm, ptr, total, files,
+                                                       segments, rate)
+        if i:
+            runs.append((1e3 * (time.perf_counter() - t0), tm['link_ubm_train'][0], tm['link_ubm_stats'][0], tm['link_clr'][0]))
+    med = lambda k: round(float(np.median([r[k] for r in runs])), 3)
+    spread = lambda k: [round(float(min(r[k] for r in runs)), 3), round(float(max(r[k] for r in runs)), 3)]
+    frames = int((e - b).sum())
+    out = {
+        'mode': 'clr', 'files': args.files, 'seconds': args.seconds, 'speakers': tm['link_speakers'], 'merges': len(merges),
+        'frames_of_speakers': frames, 'runs': args.runs, 'link': pipeline.LINK_CLR,
+        'link_ubm_train_ms': med(1), 'link_ubm_train_min_max_ms': spread(1),
+        'link_ubm_stats_ms': med(2), 'link_ubm_stats_min_max_ms': spread(2),
+        'link_clr_ms': med(3), 'link_clr_min_max_ms': spread(3),
+        'link_batch_wall_ms': med(0), 'initial_ratio_max': smax, 'initial_ratio_min': smin,
+        'global_speakers': int(max(int(m.max()) for m in maps)), 'device': device,
+    }
+    out['link_ubm_stats_gb_s'] = round(frames * 156 / (out['link_ubm_stats_ms'] * 1e-3) / 1e9, 1)
+    line = json.dumps(out)
+    print(line)
+    path = os.path.join(ROOT, 'DESIGN.md')
+    text = open(path).read()
+    if NUMBERS.search(text):
+        open(path, 'w').write(NUMBERS.sub(lambda m: 'Numbers (link by CLR): tools/link_time.py --clr measured ' + line, text, count=1))
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--files', type=int, default=256)
@@ -33,19 +78,21 @@ def main():
     ap.add_argument('--speakers', type=int, default=4)
     ap.add_argument('--runs', type=int, default=7)
     ap.add_argument('--ahc-runs', type=int, default=3)
+    ap.add_argument('--clr', action='store_true')
     args = ap.parse_args()
     import torch
     hipabi = importlib.import_module(PKG + '.hipabi')
     pipeline = importlib.import_module(PKG + '.pipeline')
     synth_device = importlib.import_module(PKG + '.synth_device')
     dev = torch.device('cuda', 0)
-    parts, begins, ends, labels, off = [], [], [], [], 0
+    parts, begins, ends, labels, off, file_frames = [], [], [], [], 0, []
     for i in range(args.files):
         feats, _, truth = synth_device.make_session_device(1000003 + i, args.seconds, args.speakers, device=dev)
         begins += [off + a for a, _, _ in truth]
         ends += [off + b for _, b, _ in truth]
         labels.append(np.array([k + 1 for _, _, k in truth], dtype=np.int32))
         parts.append(feats)
+        file_frames.append((off, int(feats.shape[0])))
         off += int(feats.shape[0])
     frames = torch.cat(parts)
     del parts
@@ -55,6 +102,9 @@ def main():
     b, e = np.array(begins, dtype=np.int64), np.array(ends, dtype=np.int64)
     n_seg = len(b)
     seg_off = np.concatenate([[0], np.cumsum([len(l) for l in labels])]).astype(np.int64)
+    if args.clr:
+        return clr_mode(args, ctx, pipeline, ptr, total, file_frames, b, e, seg_off, labels,
+                        torch.cuda.get_device_name(0))
     # what cluster_batch leaves: one record per segment, in segment order
     d_stats = ctx.dev_alloc(n_seg * hipabi.REC * 8)
     ctx.set_stats(ptr, total, b, e, np.arange(n_seg, dtype=np.int32), n_seg, d_stats)
