@@ -100,6 +100,7 @@ enum {
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
     SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
+    SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK,
     SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
     SPKD_N_TIMERS
 };
@@ -690,6 +691,51 @@ spkd_status spkd_gauss_loglik(spkd_ctx *ctx, const float *d_frames, int64_t n_fr
                               int64_t n_seq, const int64_t *h_seq_begin, const int64_t *h_seq_end,
                               const int32_t *h_seq_model, const int32_t *h_seq_n_models,
                               int32_t n_cols, float *d_scores);
+
+/* spkd_mindur_viterbi_batch: the speaker loop of (8) with a minimum duration.  The shape of
+ * spkd_vad_viterbi_batch restricted to that loop: d_scores [sum T][n_cols] floats, sequence q owns
+ * the frames [h_frame_off[q], h_frame_off[q+1]) (h_frame_off[0] = 0, non-decreasing; a sequence may
+ * be empty), word k is column k (1 <= n_cols <= 16), entering a word costs `penalty` (finite, >= 0),
+ * staying and leaving nothing -- and every stretch of a decoded path lasts at least D = min_frames
+ * (>= 1) frames.  The one exception is a sequence shorter than D frames, which is a single stretch:
+ * every token covers at least D frames or a whole sequence.  A switch penalty cannot promise that:
+ * on frames that are correlated in time a short burst beats any penalty that still lets real
+ * changes through.  PARITY: no reference counterpart; tests/reseg_mindur_numpy.py restates the
+ * recurrence and checks it against a brute-force decoder over the expanded states.
+ *
+ * The arithmetic, in fp64; the order of the operations is part of the contract:
+ *   o_t(k)  the cleaned score, as spkd_vad_viterbi: NaN counts as -inf; a frame whose words are all
+ *           -inf counts as 0 for every word.
+ *   P_t(k)  the sum of the finite o_u(k), u <= t, added in frame order starting from 0.0;
+ *           C_t(k) the number of -inf among them;  P_-1 = C_-1 = 0.
+ *   w_t(k)  -inf if C_t(k) - C_{t-D}(k) > 0, otherwise P_t(k) - P_{t-D}(k).
+ *   T == 0: no token, score -inf.  T < D: one token (0, k*), k* the lowest k that maximises
+ *           (C_{T-1}(k) > 0 ? -inf : P_{T-1}(k)); the score is (-penalty) + that value.
+ *   d_t(k)  -inf for t < D - 1;  d_{D-1}(k) = (-penalty) + w_{D-1}(k);  for t >= D, with g and b the
+ *           maximum and the lowest arg-max over k of d_{t-D}(k) (for t - D < D - 1: -inf, word 0):
+ *             stay = d_{t-1}(k) + o_t(k),  fresh = (g - penalty) + w_t(k),
+ *             d_t(k) = stay if stay >= fresh, otherwise fresh with entered_t(k) set.
+ *           Staying wins ties.  No NaN can arise: the P are finite.
+ *   end     k* the lowest arg-max of d_{T-1}(k); the score is that value.
+ *   path    from (T - 1, k*), at (t, j): on t <= D - 1 the token (0, j), and stop; if entered_t(j)
+ *           the token (t - D + 1, j), then j = b_{t-D} and t = t - D; otherwise t = t - 1.
+ * A sequence whose words all hold a -inf somewhere in every window is what the recurrence makes of
+ * it: d stays -inf, and it comes out as the one token (0, 0) with score -inf.  With D = 1 and sums
+ * that are exact the tokens and scores are those of spkd_vad_viterbi_batch with stay = exit = 0,
+ * enter = -penalty.
+ * Out, in pinned memory of the context, valid until its next spkd_mindur_viterbi_batch, laid out as
+ * spkd_vad_viterbi_batch's: (*h_tok_off)[n_seq + 1], *h_tok_frame (first frames, relative to the
+ * sequence), *h_tok_word, (*h_score)[n_seq].  Device scratch held by the context, per frame, each
+ * sequence rounded up to SPKD_MINDUR_TILE frames: the `entered` flags (2 bytes), g (8) and b (4).
+ * A bad count, a null pointer, a penalty that is negative or not finite, min_frames < 1, an
+ * h_frame_off that does not start at 0 or decreases: SPKD_EINVAL before any device work.
+ * Timers: SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK (both passes). */
+#define SPKD_MINDUR_TILE 32
+spkd_status spkd_mindur_viterbi_batch(spkd_ctx *ctx, const float *d_scores, int64_t n_seq,
+                                      const int64_t *h_frame_off, int32_t n_cols, double penalty,
+                                      int32_t min_frames,
+                                      const int64_t **h_tok_off, const int64_t **h_tok_frame,
+                                      const int32_t **h_tok_word, const double **h_score);
 
 /* ---------------------------------------------------------------------------
  * (9) Resegmentation with mixture models: a diagonal-covariance Gaussian mixture per speaker,

@@ -23,6 +23,7 @@
 #include "spkd_mfcc_batch.hpp"
 #include "spkd_vad.hpp"
 #include "spkd_vad_batch.hpp"
+#include "spkd_mindur.hpp"
 #include "spkd_gauss.hpp"
 #include "spkd_gmm_train.hpp"
 #include "spkd_ubm_stats.hpp"
@@ -32,12 +33,14 @@ using namespace spkd;
 
 namespace {
 constexpr int N_SLOTS = 64;
-// pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused), of spkd_vad_viterbi_batch and of
+// pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused), of spkd_vad_viterbi_batch, of
+// spkd_mindur_viterbi_batch (its results, like the VAD call's, but its own: neither call ends the other's) and of
 // spkd_sum_stats, spkd_gauss_loglik, spkd_gmm_train and spkd_gmm_loglik_seq (their index arrays on their way up;
 // spkd_gmm_train's ok flags and log-likelihoods on their way down), and of spkd_ubm_stats and spkd_clr_link
 // (index arrays and ok flags up; ok flags, the merge log and its statistics down)
 enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
-       PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, N_PIN };
+       PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, PIN_MD_SEQS, PIN_MD_TOKENS,
+       N_PIN };
 }
 
 struct spkd_ctx {
@@ -264,7 +267,8 @@ enum {
     S_AHC_STATS, S_AHC_LD, S_AHC_AUX, S_AHC_MAT, S_AHC_MISC, S_AHC_OUT, S_AHC_OFF, S_AHC_PROB, S_AHC_PACKED, S_MFCC_TAB, S_MFCC_STATIC, S_MFCC_TW,
     S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX,
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
-    S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT, S_COUNT
+    S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT,
+    S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -2211,6 +2215,131 @@ spkd_status spkd_vad_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_t n
         HIPCHK(c, hipMemcpyAsync(d.tok_off, h.tok_off, (nf + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
         if (G == 16) vad_backtrack_launch<VbRecord<16>::type, true>(c, back, t, n_files, G, d, d_tok_frame, d_tok_word);
         else vad_backtrack_launch<VbRecord<1>::type, true>(c, back, t, n_files, G, d, d_tok_frame, d_tok_word);
+        HIPCHK(c, hipGetLastError());
+        if (n_tok) {
+            HIPCHK(c, hipMemcpyAsync(h_frames, d_tok_frame, n_tok * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(h_words, d_tok_word, n_tok * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    *h_tok_frame = h_frames;
+    *h_tok_word = h_words;
+    return call.finish();
+}
+
+// ------------------------------------------------------------------ (8) the speaker loop with a minimum duration
+static_assert(MD_TILE == SPKD_MINDUR_TILE, "the header states the kernels' tile");
+static_assert(MD_MAX == GM_MAX_S, "one limit for states and words");
+
+namespace {
+struct MdTables { int64_t *frame_off, *rec_off; };
+struct MdWork {                  // per frame, each sequence from a multiple of MD_TILE on
+    uint16_t* rec;
+    double* g;
+    int32_t* b;
+};
+
+extern "C++" {
+template <int G>
+void mindur_decode_launch(spkd_ctx* c, const float* d_scores, const MdTables& t, int64_t n_seq, int W, double penalty,
+                          int64_t D, const MdWork& w, const VadFiles& d) {
+    const int64_t per_wave = WAVE / G;
+    const dim3 grid((unsigned)((n_seq + per_wave - 1) / per_wave));
+    if (D < MD_RING)
+        hipLaunchKernelGGL((k_mindur_viterbi<G, true>), grid, dim3(WAVE), 0, c->stream, d_scores, (const long long*)t.frame_off,
+                           (const long long*)t.rec_off, (long long)n_seq, W, W, penalty, (long long)D, w.rec, w.g, (int*)w.b,
+                           (int*)d.final_word, d.score);
+    else
+        hipLaunchKernelGGL((k_mindur_viterbi<G, false>), grid, dim3(WAVE), 0, c->stream, d_scores, (const long long*)t.frame_off,
+                           (const long long*)t.rec_off, (long long)n_seq, W, W, penalty, (long long)D, w.rec, w.g, (int*)w.b,
+                           (int*)d.final_word, d.score);
+}
+
+template <bool WRITE>
+void mindur_backtrack_launch(spkd_ctx* c, const MdTables& t, int64_t n_seq, int64_t D, const MdWork& w, const VadFiles& d,
+                             int64_t* tok_frame, int32_t* tok_word) {
+    hipLaunchKernelGGL((k_mindur_backtrack<WRITE>), dim3((unsigned)((n_seq + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->stream,
+                       (const uint16_t*)w.rec, (const int*)w.b, (const long long*)t.frame_off, (const long long*)t.rec_off,
+                       (long long)n_seq, (long long)D, (const int*)d.final_word, (long long*)d.count, (const long long*)d.tok_off,
+                       (long long*)tok_frame, (int*)tok_word);
+}
+}  // extern "C++"
+}  // namespace
+
+spkd_status spkd_mindur_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_t n_seq, const int64_t* h_frame_off,
+                                      int32_t n_cols, double penalty, int32_t min_frames, const int64_t** h_tok_off,
+                                      const int64_t** h_tok_frame, const int32_t** h_tok_word, const double** h_score) {
+    if (!c) return SPKD_EINVAL;
+    if (!h_tok_off || !h_tok_frame || !h_tok_word || !h_score) return fail(c, SPKD_EINVAL, "mindur_viterbi_batch: null output");
+    *h_tok_off = nullptr;
+    *h_tok_frame = nullptr;
+    *h_tok_word = nullptr;
+    *h_score = nullptr;
+    if (n_cols < 1 || n_cols > GM_MAX_S) return fail(c, SPKD_EINVAL, "mindur_viterbi_batch: 1 <= n_cols <= 16");
+    if (!std::isfinite(penalty) || penalty < 0.0) return fail(c, SPKD_EINVAL, "mindur_viterbi_batch: a finite penalty >= 0");
+    if (min_frames < 1) return fail(c, SPKD_EINVAL, "mindur_viterbi_batch: min_frames >= 1");
+    TRY(vad_check_offsets(c, n_seq, h_frame_off));
+    if (h_frame_off[n_seq] > 0 && !d_scores) return fail(c, SPKD_EINVAL, "mindur_viterbi_batch: null device buffer");
+    const size_t nf = (size_t)n_seq;
+    std::vector<int64_t> rec_off(nf + 1, 0);
+    for (size_t f = 0; f < nf; ++f)
+        rec_off[f + 1] = rec_off[f] + (h_frame_off[f + 1] - h_frame_off[f] + MD_TILE - 1) / MD_TILE * MD_TILE;
+    int G = 1;
+    while (G < n_cols) G *= 2;
+    VadFiles h;                  // pinned: the results of the call
+    TRY(carve(c, pinned, PIN_MD_SEQS, [&](Layout L) {
+        return L.part(h.tok_off, nf + 1).part(h.count, nf).part(h.score, nf).part(h.final_word, nf).bytes();
+    }));
+    h.tok_off[0] = 0;
+    *h_tok_off = h.tok_off;
+    *h_score = h.score;
+    if (n_seq == 0) return SPKD_OK;
+    std::vector<char> tab;
+    Call call(c);
+    TRY(call.opened);
+    MdTables t;
+    TRY(upload_parts(c, S_MD_TAB, tab, [&](Layout L) {
+        return L.part(t.frame_off, nf + 1, h_frame_off).part(t.rec_off, nf + 1, (const int64_t*)rec_off.data()).bytes();
+    }));
+    VadFiles d;
+    TRY(carve(c, scratch, S_MD_SEQS, [&](Layout L) {
+        return L.part(d.tok_off, nf + 1).part(d.count, nf).part(d.score, nf).part(d.final_word, nf).bytes();
+    }));
+    MdWork w;
+    void* p = nullptr;
+    const size_t n_rec = (size_t)rec_off[nf];
+    TRY(scratch(c, S_MD_BACK, n_rec * sizeof(uint16_t), &p));
+    w.rec = (uint16_t*)p;
+    TRY(scratch(c, S_MD_G, n_rec * sizeof(double), &p));
+    w.g = (double*)p;
+    TRY(scratch(c, S_MD_B, n_rec * sizeof(int32_t), &p));
+    w.b = (int32_t*)p;
+    {
+        Timer tm(c, SPKD_T_MINDUR_VITERBI);
+        switch (G) {
+            case 1: mindur_decode_launch<1>(c, d_scores, t, n_seq, n_cols, penalty, min_frames, w, d); break;
+            case 2: mindur_decode_launch<2>(c, d_scores, t, n_seq, n_cols, penalty, min_frames, w, d); break;
+            case 4: mindur_decode_launch<4>(c, d_scores, t, n_seq, n_cols, penalty, min_frames, w, d); break;
+            case 8: mindur_decode_launch<8>(c, d_scores, t, n_seq, n_cols, penalty, min_frames, w, d); break;
+            default: mindur_decode_launch<16>(c, d_scores, t, n_seq, n_cols, penalty, min_frames, w, d); break;
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    int64_t *d_tok_frame = nullptr, *h_frames = nullptr;
+    int32_t *d_tok_word = nullptr, *h_words = nullptr;
+    {
+        // both passes of k_mindur_backtrack and the copy of the counts between them
+        Timer tm(c, SPKD_T_MINDUR_BACKTRACK);
+        mindur_backtrack_launch<false>(c, t, n_seq, min_frames, w, d, nullptr, nullptr);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h.count, d.count, nf * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(h.score, d.score, nf * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (size_t f = 0; f < nf; ++f) h.tok_off[f + 1] = h.tok_off[f] + h.count[f];
+        const size_t n_tok = (size_t)h.tok_off[nf];
+        TRY(carve(c, scratch, S_MD_TOKENS, [&](Layout L) { return L.part(d_tok_frame, n_tok).part(d_tok_word, n_tok).bytes(); }));
+        TRY(carve(c, pinned, PIN_MD_TOKENS, [&](Layout L) { return L.part(h_frames, n_tok).part(h_words, n_tok).bytes(); }));
+        HIPCHK(c, hipMemcpyAsync(d.tok_off, h.tok_off, (nf + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+        mindur_backtrack_launch<true>(c, t, n_seq, min_frames, w, d, d_tok_frame, d_tok_word);
         HIPCHK(c, hipGetLastError());
         if (n_tok) {
             HIPCHK(c, hipMemcpyAsync(h_frames, d_tok_frame, n_tok * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));

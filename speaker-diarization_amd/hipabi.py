@@ -18,8 +18,10 @@ TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pai
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
                                         'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
+                                        'mindur_viterbi', 'mindur_backtrack',
                                         'mfcc_static', 'mfcc_post'])}
 VAD_TILE = 32       # SPKD_VAD_TILE: frames per score / back-pointer tile of k_vad_viterbi
+MINDUR_TILE = 32    # SPKD_MINDUR_TILE: frames per score / record tile of k_mindur_viterbi
 GAUSS_TILE = 64     # SPKD_GAUSS_TILE: frames per workgroup of k_gauss_loglik
 GAUSS_MODEL = 820   # SPKD_GAUSS_MODEL: doubles per model (mu[39], W = L^-1 packed lower [780], c)
 GMM_COMP = 80       # SPKD_GMM_COMP: doubles per mixture component (ln w, mean[39], 1 / var[39], log_norm)
@@ -39,7 +41,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
            'spkd_gauss_models', 'spkd_gauss_loglik', 'spkd_gmm_train', 'spkd_gmm_loglik_seq',
-           'spkd_ubm_stats', 'spkd_clr_link']
+           'spkd_ubm_stats', 'spkd_clr_link', 'spkd_mindur_viterbi_batch']
 
 
 class CdParams(C.Structure):
@@ -214,6 +216,7 @@ def load_library(path=None):
     lib.spkd_vad_viterbi.argtypes = [i64, i32, vp, i32, vp, vp, vp, vp, vp, vp, P(i64), P(dbl)]
     lib.spkd_vad_shift_batch.argtypes = [vp, vp, i64, vp, i32, dbl, vp]
     lib.spkd_vad_viterbi_batch.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, P(vp), P(vp), P(vp), P(vp)]
+    lib.spkd_mindur_viterbi_batch.argtypes = [vp, vp, i64, vp, i32, dbl, i32, P(vp), P(vp), P(vp), P(vp)]
     lib.spkd_gauss_models.argtypes = [vp, vp, i64, vp, vp]
     lib.spkd_gauss_loglik.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp]
     lib.spkd_gmm_train.argtypes = [vp, vp, i64, i64, vp, vp, vp, i32, i32, i32, dbl, vp, vp, vp]
@@ -808,6 +811,22 @@ class Context(object):
         frame_off = np.zeros(len(b) + 1, dtype=np.int64)
         frame_off[1:] = np.cumsum(e - b)
         return frame_off
+
+    def mindur_viterbi_batch(self, d_scores, frame_off, n_cols, penalty, min_frames):
+        """The speaker loop with a minimum duration for every sequence of concatenated device scores
+        [sum T, n_cols] in one launch (spkd_mindur_viterbi_batch): word k is column k, entering a word
+        costs `penalty`, no stretch is shorter than min_frames frames unless it is a whole sequence.
+        Returns what vad_viterbi_batch returns: (tok_off, token first frames, token words, path
+        scores); copies.  The kernels' times are last_ms('mindur_viterbi') and last_ms('mindur_backtrack')."""
+        off = self._frame_off(frame_off)
+        n = len(off) - 1
+        out = [C.c_void_p() for _ in range(4)]
+        self.check(self.lib.spkd_mindur_viterbi_batch(self.h, C.c_void_p(d_scores), n, _ptr(off), int(n_cols), float(penalty),
+                                                      int(min_frames), *[C.byref(o) for o in out]))
+        tok_off = _view(out[0].value, n + 1, np.int64).copy()
+        n_tok = int(tok_off[-1])
+        return (tok_off, _view(out[1].value, n_tok, np.int64).copy(), _view(out[2].value, n_tok, np.int32).copy(),
+                _view(out[3].value, n, np.float64).copy())
 
     # ---- (9) resegmentation with mixture models
     def gmm_train(self, d_frames, n_frames, set_off, range_begin, range_end, n_comp, n_iter, var_floor, d_gmm,

@@ -44,6 +44,12 @@ RESEG_MAX_SPEAKERS = 16          # of one file: the decoder's word limit (spkd_v
 # components and five EM steps are what small per-speaker mixtures usually get; the floor is a share
 # of the variance of all the speaker's frames.
 RESEG_GMM = dict(penalty=50.0, model='gmm', components=4, iterations=5, var_floor=0.01)
+# the same stage with a minimum speaker duration in the decoder (spkd_mindur_viterbi_batch): no row shorter
+# than min_dur_s unless it is a whole turn.  A setting, not a measurement: 1.0 s is the detector's own
+# smallest window (DIA2_CD['winsize_s']), and neither it nor the penalty beside it has been tuned on anything
+# but the synthetic generator.  Any reseg dictionary may also carry passes=N (default 1): the speakers are
+# retrained on the decoded rows and the turns decoded again, up to N decodes.
+RESEG_MD = dict(penalty=50.0, min_dur_s=1.0)
 
 
 class BatchFile(object):
@@ -723,6 +729,42 @@ def _reseg_model(reseg):
     return ('gmm', int(k), int(it), fl)
 
 
+def _reseg_min_frames(reseg, rate):
+    """D of a `reseg` dictionary, in frames: 0 when min_dur_s is absent or 0 -- the plain decoder --
+    otherwise max(1, floor(min_dur_s * rate))."""
+    try:
+        s = float(reseg.get('min_dur_s', 0.0))
+    except (TypeError, ValueError):
+        s = float('nan')
+    if not np.isfinite(s) or s < 0.0:
+        raise ValueError('reseg min_dur_s: a finite number >= 0 (seconds; 0: no minimum duration)')
+    return max(1, int(np.floor(s * float(rate)))) if s > 0.0 else 0
+
+
+def _reseg_passes(reseg):
+    n = reseg.get('passes', 1)
+    try:
+        whole = not isinstance(n, bool) and int(n) == n
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or n < 1:
+        raise ValueError('reseg passes: an integer >= 1')
+    return int(n)
+
+
+def _token_ranges(tok_off, tok_frame, tok_word, tb, te, first_speaker):
+    """The decoded tokens as absolute frame ranges with their speakers, in turn order: token k of turn q
+    is [tb[q] + f_k, tb[q] + f_{k+1}), a turn's last token ends at te[q]; its speaker is
+    first_speaker[q] + word.  -> (begin, end, speaker)."""
+    turn = np.repeat(np.arange(len(tok_off) - 1), np.diff(tok_off))
+    b = tb[turn] + tok_frame
+    e = np.empty_like(b)
+    e[:-1] = b[1:]
+    last = tok_off[1:][np.diff(tok_off) > 0] - 1
+    e[last] = te[turn[last]]
+    return b, e, first_speaker[turn] + tok_word
+
+
 def _reseg_rows(tok_off, tok_frame, tok_word, turn_start_s, turn_end_s, turn_labels, rate, text_contract):
     """The rows of a decoded batch of turns, in turn order: token k of a turn, opening at the
     relative frame f_k, is [turn_start_s + f_k / rate, turn_start_s + f_{k+1} / rate, label]; a turn's
@@ -774,10 +816,29 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     log-likelihood of its frames under the model entering each iteration.  timings: reseg_gmm_train
     instead of reseg_models; reseg_loglik is the mixture scorer's.  An unknown model, components
     outside 1 .. 8, negative iterations, a negative or non-finite floor, no segments: ValueError
+    before any device work.
+    reseg['min_dur_s'] > 0 (RESEG_MD): the turns are decoded by spkd_mindur_viterbi_batch instead, on the
+    same scores, with D = max(1, floor(min_dur_s * rate)) frames: every row lasts at least D frames or
+    is a whole turn.  Absent or 0: the call above, unchanged.  timings: reseg_viterbi and
+    reseg_backtrack are then that decoder's kernels.
+    reseg['passes'] = N (an integer >= 1, default 1; either model, with or without min_dur_s): after
+    every decode but the last the speakers are trained again, on the decoded tokens -- token k of turn
+    q is the absolute range [tb_q + f_k, tb_q + f_{k+1}), a turn's last token ends with the turn, its
+    speaker is the file's word-th; the ranges go in turn order, grouped by speaker by a stable sort.
+    'gauss': the records straight from those frames (spkd_set_stats), then spkd_gauss_models; 'gmm':
+    spkd_gmm_train on them with the same components, iterations and floor, from a fresh segmental
+    start (`segments` serves pass 1 only).  Then the turns are scored and decoded as in pass 1.  A
+    speaker that holds no frame any more, or whose new model is not ok, scores -inf from then on;
+    detail['dropped'] (and detail['loglik']) are those of the last pass run.  The loop stops early
+    when a pass decodes exactly the tokens of the pass before it; detail['passes_run'] is the number
+    of decodes done (0 when there was nothing to decode).  timings: the reseg lists get one entry per
+    pass.  A min_dur_s that is negative or not finite, passes that is not an integer >= 1: ValueError
     before any device work."""
     rate = float(rate)
     penalty = _reseg_penalty(reseg)
     model = _reseg_model(reseg)
+    min_frames = _reseg_min_frames(reseg, rate)
+    passes = _reseg_passes(reseg)
     if model[0] == 'gmm':
         if segments is None:
             raise ValueError('reseg model gmm trains on the frames: it takes segments, the arrays cluster_batch took')
@@ -797,6 +858,7 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     out = [np.zeros((0, 3)) for _ in files]
     if detail is not None:
         detail['dropped'] = []
+        detail['passes_run'] = 0
     table = _turn_table(files, rate)
     if table is None or len(spk_file) == 0:
         return out
@@ -808,39 +870,67 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     n_spk, n_cols = len(spk_file), int(n_spk_file.max())
     spk_base = np.zeros(n_files + 1, dtype=np.int64)
     spk_base[1:] = np.cumsum(n_spk_file)
-    if model[0] == 'gmm':
-        _, n_comp, n_iter, var_floor = model
-        d_models = ctx.dev_scratch('reseg_gmm', n_spk * n_comp * hipabi.GMM_COMP * 8)
-        ok, loglik = ctx.gmm_train(d_frames, total_frames, set_off, seg_b[member], seg_e[member], n_comp, n_iter,
-                                   var_floor, d_models)
-        if timings is not None:
-            timings.setdefault('reseg_gmm_train', []).append(ctx.last_ms('gmm_train'))
+    tokens = None
+    for p in range(passes):
+        if model[0] == 'gmm':
+            _, n_comp, n_iter, var_floor = model
+            if p == 0:
+                d_models = ctx.dev_scratch('reseg_gmm', n_spk * n_comp * hipabi.GMM_COMP * 8)
+                off, rb, re_ = set_off, seg_b[member], seg_e[member]
+            else:
+                # (spkd_gmm_train takes no empty set: a speaker without a token gets one empty range)
+                rb, re_, spk = _token_ranges(tokens[0], tokens[1], tokens[2], tb, te, spk_base[owner])
+                idle = np.nonzero(np.bincount(spk, minlength=n_spk) == 0)[0]
+                rb, re_ = np.concatenate([rb, np.zeros(len(idle), np.int64)]), np.concatenate([re_, np.zeros(len(idle), np.int64)])
+                spk = np.concatenate([spk, idle])
+                order = np.argsort(spk, kind='stable')
+                off = np.concatenate([[0], np.cumsum(np.bincount(spk, minlength=n_spk))]).astype(np.int64)
+                rb, re_ = rb[order], re_[order]
+            ok, loglik = ctx.gmm_train(d_frames, total_frames, off, rb, re_, n_comp, n_iter, var_floor, d_models)
+            if timings is not None:
+                timings.setdefault('reseg_gmm_train', []).append(ctx.last_ms('gmm_train'))
+            if detail is not None:
+                detail['loglik'] = loglik
+        else:
+            if p == 0:
+                d_spk = ctx.dev_scratch('reseg_speaker_stats', n_spk * hipabi.REC * 8)
+                ctx.sum_stats(d_stats, int(seg_off[-1]), member, set_off, d_spk)
+                d_models = ctx.dev_scratch('reseg_models', n_spk * hipabi.GAUSS_MODEL * 8)
+            else:
+                rb, re_, spk = _token_ranges(tokens[0], tokens[1], tokens[2], tb, te, spk_base[owner])
+                order = np.argsort(spk, kind='stable')                     # (spkd_set_stats takes ascending sets)
+                ctx.set_stats(d_frames, total_frames, rb[order], re_[order], sets=spk[order].astype(np.int32), n_sets=n_spk,
+                              d_stats=d_spk)
+            ok = ctx.gauss_models(d_spk, n_spk, d_models)
+            if timings is not None:
+                timings.setdefault('reseg_models', []).append(ctx.last_ms('gauss_models'))
         if detail is not None:
-            detail['loglik'] = loglik
-    else:
-        d_spk = ctx.dev_scratch('reseg_speaker_stats', n_spk * hipabi.REC * 8)
-        ctx.sum_stats(d_stats, int(seg_off[-1]), member, set_off, d_spk)
-        d_models = ctx.dev_scratch('reseg_models', n_spk * hipabi.GAUSS_MODEL * 8)
-        ok = ctx.gauss_models(d_spk, n_spk, d_models)
+            detail['dropped'] = [(int(spk_file[s]), int(spk_label[s])) for s in np.nonzero(ok == 0)[0]]
+        if p == 0:
+            d_scores = ctx.dev_scratch('reseg_scores', max(int((te - tb).sum()), 1) * n_cols * 4)
+        if model[0] == 'gmm':
+            frame_off = ctx.gmm_loglik_seq(d_frames, total_frames, d_models, n_comp, ok, tb, te, spk_base[owner],
+                                           n_spk_file[owner], n_cols, d_scores)
+        else:
+            frame_off = ctx.gauss_loglik(d_frames, total_frames, d_models, ok, tb, te, spk_base[owner], n_spk_file[owner],
+                                         n_cols, d_scores)
         if timings is not None:
-            timings.setdefault('reseg_models', []).append(ctx.last_ms('gauss_models'))
-    if detail is not None:
-        detail['dropped'] = [(int(spk_file[s]), int(spk_label[s])) for s in np.nonzero(ok == 0)[0]]
-    d_scores = ctx.dev_scratch('reseg_scores', max(int((te - tb).sum()), 1) * n_cols * 4)
-    if model[0] == 'gmm':
-        frame_off = ctx.gmm_loglik_seq(d_frames, total_frames, d_models, n_comp, ok, tb, te, spk_base[owner],
-                                       n_spk_file[owner], n_cols, d_scores)
-    else:
-        frame_off = ctx.gauss_loglik(d_frames, total_frames, d_models, ok, tb, te, spk_base[owner], n_spk_file[owner],
-                                     n_cols, d_scores)
-    if timings is not None:
-        timings.setdefault('reseg_loglik', []).append(ctx.last_ms('gmm_seq_loglik' if model[0] == 'gmm' else 'gauss_loglik'))
-    zero = np.zeros(n_cols)
-    tok_off, tok_frame, tok_word, _ = ctx.vad_viterbi_batch(d_scores, frame_off, n_cols, np.arange(n_cols), zero, zero,
-                                                            zero - penalty)
-    if timings is not None:
-        timings.setdefault('reseg_viterbi', []).append(ctx.last_ms('vad_viterbi'))
-        timings.setdefault('reseg_backtrack', []).append(ctx.last_ms('vad_backtrack'))
+            timings.setdefault('reseg_loglik', []).append(ctx.last_ms('gmm_seq_loglik' if model[0] == 'gmm' else 'gauss_loglik'))
+        if min_frames:
+            tok_off, tok_frame, tok_word, _ = ctx.mindur_viterbi_batch(d_scores, frame_off, n_cols, penalty, min_frames)
+        else:
+            zero = np.zeros(n_cols)
+            tok_off, tok_frame, tok_word, _ = ctx.vad_viterbi_batch(d_scores, frame_off, n_cols, np.arange(n_cols), zero, zero,
+                                                                    zero - penalty)
+        if timings is not None:
+            timings.setdefault('reseg_viterbi', []).append(ctx.last_ms('mindur_viterbi' if min_frames else 'vad_viterbi'))
+            timings.setdefault('reseg_backtrack', []).append(ctx.last_ms('mindur_backtrack' if min_frames else 'vad_backtrack'))
+        if detail is not None:
+            detail['passes_run'] = p + 1
+        same = tokens is not None and all(np.array_equal(a, b) for a, b in zip(tokens, (tok_off, tok_frame, tok_word)))
+        tokens = (tok_off, tok_frame, tok_word)
+        if same or len(tok_frame) == 0:
+            break
     # label of word w in a turn of file f: the file's w-th speaker (a word past the file's speakers
     # is never decoded: its column is -inf beside column 0, which wins every tie)
     file_labels = np.zeros((n_files, n_cols), dtype=np.int64)
@@ -937,11 +1027,16 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     on the clustering segments as without reseg and the resegmented rows' third column is mapped
     through its maps.  detail['dropped'] as resegment_batch.  reseg=None: today's rows.  A dictionary
     like RESEG_GMM decodes under mixture models trained on the clustering segments' frames
-    (resegment_batch, model 'gmm'; detail['loglik'] as there)."""
+    (resegment_batch, model 'gmm'; detail['loglik'] as there).  A dictionary like RESEG_MD decodes with
+    a minimum speaker duration (reseg['min_dur_s']), and reseg['passes'] retrains the speakers on the
+    decoded rows and decodes again; both keys go to resegment_batch as they are
+    (detail['passes_run'] as there)."""
     method = _method(cl)
     if reseg is not None:
         _reseg_penalty(reseg)
         _reseg_model(reseg)
+        _reseg_min_frames(reseg, rate)
+        _reseg_passes(reseg)
         if handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi'):
             raise ValueError('reseg takes the host hand-off')
     if _cd_method(cd) in ('sw', 'm'):
@@ -971,6 +1066,7 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
                                   stat_max=float('nan'), stat_min=float('nan'))
         if reseg is not None and detail is not None:
             detail['dropped'] = []
+            detail['passes_run'] = 0
         return [np.zeros((0, 3)) for _ in files]
     return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail, reseg,
                               text_contract)
