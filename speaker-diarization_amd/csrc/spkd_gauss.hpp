@@ -98,6 +98,48 @@ __global__ __launch_bounds__(WAVE) void k_gauss_models(
     }
 }
 
+// The tile of a workgroup of the scoring kernels (k_gauss_loglik, k_gmm_loglik_seq; the table is the host's
+// SeqTable): its frames, the first of its rows of the scores, its sequence's first model and model count.
+// All of it comes from blockIdx and the table, so it is wave-uniform, and so is a model's address formed from it.
+struct SeqTile {
+    int len;                              // >= 1: the host counts the tiles
+    long long row0;
+    int m0, nm;
+};
+
+// finds the workgroup's tile, stages its len * D floats in xs and leaves the lane's frame in x (zeros past len)
+__device__ inline SeqTile gs_stage_tile(
+        const float* __restrict__ frames, const long long* __restrict__ seq_begin, const long long* __restrict__ seq_end,
+        const long long* __restrict__ seq_row, const long long* __restrict__ seq_tile,
+        const int* __restrict__ seq_model, const int* __restrict__ seq_n_models,
+        const int* __restrict__ tile_seq, int lane, float* xs, float (&x)[D]) {
+    const long long tile = blockIdx.x;
+    const int q = tile_seq[tile];
+    const long long t0 = (tile - seq_tile[q]) * GS_TILE;
+    const long long b = seq_begin[q] + t0;
+    const long long left = seq_end[q] - b;
+    const SeqTile t = {left < GS_TILE ? (int)left : GS_TILE, seq_row[q] + t0, seq_model[q], seq_n_models[q]};
+    const float* src = frames + b * D;
+    constexpr int PF = (GS_TILE * D + WAVE - 1) / WAVE;              // 39 floats a lane
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+        const int idx = lane + WAVE * k;
+        if (idx < t.len * D) xs[idx] = src[idx];
+    }
+    __syncthreads();
+    const bool has = lane < t.len;
+#pragma unroll
+    for (int j = 0; j < D; ++j) x[j] = has ? xs[lane * D + j] : 0.0f;
+    return t;
+}
+
+// the tile's len * n_cols scores from so (row `lane`, column m at so[lane * n_cols + m]) in one coalesced store
+__device__ inline void gs_store_tile(const SeqTile& t, const float* so, int n_cols, int lane, float* __restrict__ scores) {
+    __syncthreads();
+    float* dst = scores + t.row0 * n_cols;
+    for (int idx = lane; idx < t.len * n_cols; idx += WAVE) dst[idx] = so[idx];
+}
+
 __global__ __launch_bounds__(WAVE) void k_gauss_loglik(
         const float* __restrict__ frames, const double* __restrict__ models, const int* __restrict__ model_ok,
         const long long* __restrict__ seq_begin, const long long* __restrict__ seq_end,
@@ -107,31 +149,13 @@ __global__ __launch_bounds__(WAVE) void k_gauss_loglik(
     __shared__ float xs[GS_TILE * D];
     __shared__ float so[GS_TILE * GS_MAX_COLS];
     const int lane = threadIdx.x;
-    const long long tile = blockIdx.x;
-    const int q = tile_seq[tile];
-    const long long t0 = (tile - seq_tile[q]) * GS_TILE;
-    const long long b = seq_begin[q] + t0;
-    const long long left = seq_end[q] - b;
-    const int len = left < GS_TILE ? (int)left : GS_TILE;           // >= 1: the host counts the tiles
-    const long long row0 = seq_row[q] + t0;
-    const int m0 = seq_model[q], nm = seq_n_models[q];
-    const float* src = frames + b * D;
-    constexpr int PF = (GS_TILE * D + WAVE - 1) / WAVE;              // 39 floats a lane
-#pragma unroll
-    for (int k = 0; k < PF; ++k) {
-        const int idx = lane + WAVE * k;
-        if (idx < len * D) xs[idx] = src[idx];
-    }
-    __syncthreads();
-    const bool has = lane < len;
     float x[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) x[j] = has ? xs[lane * D + j] : 0.0f;
+    const SeqTile t = gs_stage_tile(frames, seq_begin, seq_end, seq_row, seq_tile, seq_model, seq_n_models, tile_seq, lane, xs, x);
 #pragma unroll 1
     for (int m = 0; m < n_cols; ++m) {
         float s = -INFINITY;
-        if (m < nm && model_ok[m0 + m]) {                          // (wave-uniform)
-            const double* __restrict__ M = models + (long long)(m0 + m) * GS_MODEL;
+        if (m < t.nm && model_ok[t.m0 + m]) {                      // (wave-uniform)
+            const double* __restrict__ M = models + (long long)(t.m0 + m) * GS_MODEL;
             double d[D];
 #pragma unroll
             for (int j = 0; j < D; ++j) d[j] = (double)x[j] - M[j];
@@ -147,9 +171,7 @@ __global__ __launch_bounds__(WAVE) void k_gauss_loglik(
         }
         so[lane * n_cols + m] = s;
     }
-    __syncthreads();
-    float* dst = scores + row0 * n_cols;
-    for (int idx = lane; idx < len * n_cols; idx += WAVE) dst[idx] = so[idx];
+    gs_store_tile(t, so, n_cols, lane, scores);
 }
 
 }  // namespace spkd

@@ -46,7 +46,7 @@ constexpr int GT_MEAN = 1, GT_IVAR = 1 + D, GT_NORM = GT_COMP - 1;
 constexpr int GT_MIN_PER_COMP = D + 1;      // a speaker of fewer than 40 K frames is not modelled
 constexpr int GT_B = D + 1;           // a chunk's partials of one component: A[39], G, B[39], G again
 constexpr double GT_LN_2PI = 1.8378770664093453;
-static_assert(GT_TILE == WAVE, "a lane per frame of the tile");
+static_assert(GT_TILE == GS_TILE, "one tile for both models: spkd_gauss.hpp's, a lane per frame");
 static_assert(2 + 2 * D == GT_COMP && 2 * GT_B == GT_COMP, "ln w, mean, 1 / var, log_norm");
 
 __device__ inline bool gt_finite(double v) { return fabs(v) < INFINITY; }
@@ -83,14 +83,11 @@ __device__ inline void gt_stage_tile(const float* __restrict__ frames, const lon
     __syncthreads();
 }
 
-// phase 1 of a soft pass, the lane's frame of the staged tile under the K components of M (a
-// wave-uniform address): its responsibilities g_k to gl[k * GT_TILE + lane] (0 for a component whose
-// ln w is -inf: it takes no part), its log-likelihood to lls[lane]
-__device__ inline void gt_responsibilities(const float* xs, const double* __restrict__ M, int K, int lane,
-                                           double* gl, double* lls) {
-    float x[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) x[j] = xs[lane * D + j];
+// the lane's frame x under the K components of M (a wave-uniform address): the log-likelihood of every
+// live component (one whose ln w is not -inf; the others take no part) to lk[k * GT_TILE + lane]; returns
+// their maximum
+__device__ inline double gt_component_logliks(const float (&x)[D], const double* __restrict__ M, int K, int lane,
+                                              double* lk) {
 #pragma unroll 1
     for (int k = 0; k < K; ++k) {
         const double* __restrict__ Mk = M + k * GT_COMP;
@@ -101,15 +98,27 @@ __device__ inline void gt_responsibilities(const float* xs, const double* __rest
             const double d = (double)x[j] - Mk[GT_MEAN + j];
             q = fma(d * d, Mk[GT_IVAR + j], q);
         }
-        gl[k * GT_TILE + lane] = fma(-0.5, q, Mk[0] + Mk[GT_NORM]);
+        lk[k * GT_TILE + lane] = fma(-0.5, q, Mk[0] + Mk[GT_NORM]);
     }
     double m = -INFINITY;
 #pragma unroll 1
     for (int k = 0; k < K; ++k)
         if (M[k * GT_COMP] != -INFINITY) {
-            const double l = gl[k * GT_TILE + lane];
+            const double l = lk[k * GT_TILE + lane];
             if (l > m) m = l;
         }
+    return m;
+}
+
+// phase 1 of a soft pass, the lane's frame of the staged tile under the K components of M: its
+// responsibilities g_k to gl[k * GT_TILE + lane] (0 for a component that is not live), its log-likelihood
+// to lls[lane]
+__device__ inline void gt_responsibilities(const float* xs, const double* __restrict__ M, int K, int lane,
+                                           double* gl, double* lls) {
+    float x[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) x[j] = xs[lane * D + j];
+    const double m = gt_component_logliks(x, M, K, lane, gl);
     double sum = 0.0;
 #pragma unroll 1
     for (int k = 0; k < K; ++k) {
@@ -281,50 +290,14 @@ __global__ __launch_bounds__(WAVE) void k_gmm_loglik_seq(
     __shared__ float so[GT_TILE * GS_MAX_COLS];
     __shared__ double lk[GT_MAX_COMP * GT_TILE];
     const int lane = threadIdx.x;
-    const long long tile = blockIdx.x;
-    const int q = tile_seq[tile];
-    const long long t0 = (tile - seq_tile[q]) * GT_TILE;
-    const long long b = seq_begin[q] + t0;
-    const long long left = seq_end[q] - b;
-    const int len = left < GT_TILE ? (int)left : GT_TILE;           // >= 1: the host counts the tiles
-    const long long row0 = seq_row[q] + t0;
-    const int m0 = seq_model[q], nm = seq_n_models[q];
-    const float* src = frames + b * D;
-    constexpr int PF = (GT_TILE * D + WAVE - 1) / WAVE;
-#pragma unroll
-    for (int k = 0; k < PF; ++k) {
-        const int idx = lane + WAVE * k;
-        if (idx < len * D) xs[idx] = src[idx];
-    }
-    __syncthreads();
-    const bool has = lane < len;
     float x[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) x[j] = has ? xs[lane * D + j] : 0.0f;
+    const SeqTile t = gs_stage_tile(frames, seq_begin, seq_end, seq_row, seq_tile, seq_model, seq_n_models, tile_seq, lane, xs, x);
 #pragma unroll 1
     for (int m = 0; m < n_cols; ++m) {
         float sc = -INFINITY;
-        if (m < nm && model_ok[m0 + m]) {                          // (wave-uniform)
-            const double* __restrict__ M = gmm + (long long)(m0 + m) * K * GT_COMP;
-#pragma unroll 1
-            for (int k = 0; k < K; ++k) {
-                const double* __restrict__ Mk = M + k * GT_COMP;
-                if (Mk[0] == -INFINITY) continue;
-                double acc = 0.0;
-#pragma unroll
-                for (int j = 0; j < D; ++j) {
-                    const double d = (double)x[j] - Mk[GT_MEAN + j];
-                    acc = fma(d * d, Mk[GT_IVAR + j], acc);
-                }
-                lk[k * GT_TILE + lane] = fma(-0.5, acc, Mk[0] + Mk[GT_NORM]);
-            }
-            double mx = -INFINITY;
-#pragma unroll 1
-            for (int k = 0; k < K; ++k)
-                if (M[k * GT_COMP] != -INFINITY) {
-                    const double l = lk[k * GT_TILE + lane];
-                    if (l > mx) mx = l;
-                }
+        if (m < t.nm && model_ok[t.m0 + m]) {                      // (wave-uniform)
+            const double* __restrict__ M = gmm + (long long)(t.m0 + m) * K * GT_COMP;
+            const double mx = gt_component_logliks(x, M, K, lane, lk);
             double sum = 0.0;
 #pragma unroll 1
             for (int k = 0; k < K; ++k)
@@ -333,9 +306,7 @@ __global__ __launch_bounds__(WAVE) void k_gmm_loglik_seq(
         }
         so[lane * n_cols + m] = sc;
     }
-    __syncthreads();
-    float* dst = scores + row0 * n_cols;
-    for (int idx = lane; idx < len * n_cols; idx += WAVE) dst[idx] = so[idx];
+    gs_store_tile(t, so, n_cols, lane, scores);
 }
 
 }  // namespace spkd

@@ -33,11 +33,13 @@ using namespace spkd;
 
 namespace {
 constexpr int N_SLOTS = 64;
-// pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused), of spkd_vad_viterbi_batch, of
-// spkd_mindur_viterbi_batch (its results, like the VAD call's, but its own: neither call ends the other's) and of
-// spkd_sum_stats, spkd_gauss_loglik, spkd_gmm_train and spkd_gmm_loglik_seq (their index arrays on their way up;
-// spkd_gmm_train's ok flags and log-likelihoods on their way down), and of spkd_ubm_stats and spkd_clr_link
-// (index arrays and ok flags up; ok flags, the merge log and its statistics down)
+// pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused); of the two decoders' results
+// (TokenHandBack: PIN_VAD_FILES / PIN_VAD_TOKENS of spkd_vad_viterbi_batch, PIN_MD_SEQS / PIN_MD_TOKENS of
+// spkd_mindur_viterbi_batch, so that neither call ends the other's); of the index arrays on their way up: spkd_sum_stats'
+// (PIN_SUM_IDX), the SeqTable of spkd_gauss_loglik (PIN_GAUSS_IDX) and of spkd_gmm_loglik_seq (PIN_GT_IDX), the
+// RangeTable of spkd_gmm_train (PIN_GT_TAB) and of spkd_ubm_stats (PIN_UBM_TAB), spkd_clr_link's ok flags (PIN_CLR_IN);
+// and of what comes down: spkd_gmm_train's ok flags and log-likelihoods (PIN_GT_OUT), spkd_ubm_stats' ok flags
+// (PIN_UBM_OUT), spkd_clr_link's merge log and statistics (PIN_CLR_OUT)
 enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
        PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, PIN_MD_SEQS, PIN_MD_TOKENS,
        N_PIN };
@@ -2115,6 +2117,91 @@ struct VadFiles {                // per file, device or pinned host
 };
 
 extern "C++" {
+// f(std::integral_constant<int, G>()) for the power of two G >= n_words (1 .. 16): the lanes that share a file
+template <class F>
+void with_group(int n_words, F f) {
+    if (n_words <= 1) f(std::integral_constant<int, 1>());
+    else if (n_words <= 2) f(std::integral_constant<int, 2>());
+    else if (n_words <= 4) f(std::integral_constant<int, 4>());
+    else if (n_words <= 8) f(std::integral_constant<int, 8>());
+    else f(std::integral_constant<int, 16>());
+}
+
+// How a decoder (spkd_vad_viterbi_batch, spkd_mindur_viterbi_batch) hands its tokens back: per file the
+// count, the score and the final word on the device and in pinned memory, the tokens compact behind
+// them.  Each call has pinned and scratch slots of its own, so neither ends the other's results.
+struct TokenHandBack {
+    const int64_t **const tok_off, **const tok_frame;
+    const int32_t** const tok_word;
+    const double** const score;
+    const int pin_files, pin_tokens, s_files, s_tokens;
+    size_t nf = 0;
+    VadFiles h{}, d{};           // pinned: the results of the call; the device's
+
+    size_t parts(Layout L, VadFiles& f) const {
+        return L.part(f.tok_off, nf + 1).part(f.count, nf).part(f.score, nf).part(f.final_word, nf).bytes();
+    }
+    // before any other check: false for a null output, else the four outputs nulled
+    bool clear() const {
+        if (!tok_off || !tok_frame || !tok_word || !score) return false;
+        *tok_off = nullptr;
+        *tok_frame = nullptr;
+        *tok_word = nullptr;
+        *score = nullptr;
+        return true;
+    }
+    // after the argument checks, before the Call: what a call without files returns as well
+    spkd_status open(spkd_ctx* c, int64_t n_files) {
+        nf = (size_t)n_files;
+        TRY(carve(c, pinned, pin_files, [&](Layout L) { return parts(L, h); }));
+        h.tok_off[0] = 0;
+        *tok_off = h.tok_off;
+        *score = h.score;
+        return SPKD_OK;
+    }
+    // inside the Call, before the decoder's kernel: where it leaves each file's final word and score
+    spkd_status place(spkd_ctx* c) {
+        return carve(c, scratch, s_files, [&](Layout L) { return parts(L, d); });
+    }
+    // Both passes of the backtrack as kernel timer `timer`: count(d) leaves every file's token count,
+    // which the host needs to place the tokens (hence the wait inside the call); write(d, tok_frame,
+    // tok_word) writes them from tok_off on.
+    template <class Count, class Write>
+    spkd_status hand_back(spkd_ctx* c, int timer, Count count, Write write) {
+        int64_t *d_tok_frame = nullptr, *h_frames = nullptr;
+        int32_t *d_tok_word = nullptr, *h_words = nullptr;
+        {
+            Timer tm(c, timer);
+            count(d);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(h.count, d.count, nf * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(h.score, d.score, nf * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            for (size_t f = 0; f < nf; ++f) h.tok_off[f + 1] = h.tok_off[f] + h.count[f];
+            const size_t n_tok = (size_t)h.tok_off[nf];
+            TRY(carve(c, scratch, s_tokens, [&](Layout L) { return L.part(d_tok_frame, n_tok).part(d_tok_word, n_tok).bytes(); }));
+            TRY(carve(c, pinned, pin_tokens, [&](Layout L) { return L.part(h_frames, n_tok).part(h_words, n_tok).bytes(); }));
+            HIPCHK(c, hipMemcpyAsync(d.tok_off, h.tok_off, (nf + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+            write(d, d_tok_frame, d_tok_word);
+            HIPCHK(c, hipGetLastError());
+            if (n_tok) {
+                HIPCHK(c, hipMemcpyAsync(h_frames, d_tok_frame, n_tok * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipMemcpyAsync(h_words, d_tok_word, n_tok * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            }
+        }
+        *tok_frame = h_frames;
+        *tok_word = h_words;
+        return SPKD_OK;
+    }
+};
+
+// where each file's per-frame records start: every file from a multiple of the tile on
+std::vector<int64_t> tiled_offsets(const int64_t* h_frame_off, size_t nf, int64_t tile) {
+    std::vector<int64_t> off(nf + 1, 0);
+    for (size_t f = 0; f < nf; ++f) off[f + 1] = off[f] + (h_frame_off[f + 1] - h_frame_off[f] + tile - 1) / tile * tile;
+    return off;
+}
+
 template <int G>
 void vad_decode_launch(spkd_ctx* c, const float* d_scores, const VadTables& t, int64_t n_files, int S, int W, void* back,
                        const VadFiles& d) {
@@ -2142,11 +2229,8 @@ spkd_status spkd_vad_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_t n
                                    const double* h_exit, const double* h_enter, const int64_t** h_tok_off,
                                    const int64_t** h_tok_frame, const int32_t** h_tok_word, const double** h_score) {
     if (!c) return SPKD_EINVAL;
-    if (!h_tok_off || !h_tok_frame || !h_tok_word || !h_score) return fail(c, SPKD_EINVAL, "vad_viterbi_batch: null output");
-    *h_tok_off = nullptr;
-    *h_tok_frame = nullptr;
-    *h_tok_word = nullptr;
-    *h_score = nullptr;
+    TokenHandBack r{h_tok_off, h_tok_frame, h_tok_word, h_score, PIN_VAD_FILES, PIN_VAD_TOKENS, S_VAD_FILES, S_VAD_TOKENS};
+    if (!r.clear()) return fail(c, SPKD_EINVAL, "vad_viterbi_batch: null output");
     if (n_states < 1 || n_states > GM_MAX_S || n_words < 1 || n_words > GM_MAX_S)
         return fail(c, SPKD_EINVAL, "vad_viterbi_batch: 1 <= states, words <= 16");
     if (!h_word_state || !h_stay || !h_exit || !h_enter) return fail(c, SPKD_EINVAL, "vad_viterbi_batch: null argument");
@@ -2156,73 +2240,40 @@ spkd_status spkd_vad_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_t n
     TRY(vad_check_offsets(c, n_files, h_frame_off));
     if (h_frame_off[n_files] > 0 && !d_scores) return fail(c, SPKD_EINVAL, "vad_viterbi_batch: null device buffer");
     const size_t nf = (size_t)n_files, W = (size_t)n_words;
-    // a file's back-pointer records start at a multiple of the tile
-    std::vector<int64_t> back_off(nf + 1, 0);
-    for (size_t f = 0; f < nf; ++f)
-        back_off[f + 1] = back_off[f] + (h_frame_off[f + 1] - h_frame_off[f] + VB_TILE - 1) / VB_TILE * VB_TILE;
+    const std::vector<int64_t> back_off = tiled_offsets(h_frame_off, nf, VB_TILE);
     int G = 1;
     while (G < n_words) G *= 2;
     const size_t rec_bytes = G == 16 ? sizeof(VbRecord<16>::type) : sizeof(VbRecord<1>::type);
-    VadFiles h;                  // pinned: the results of the call
-    TRY(carve(c, pinned, PIN_VAD_FILES, [&](Layout L) {
-        return L.part(h.tok_off, nf + 1).part(h.count, nf).part(h.score, nf).part(h.final_word, nf).bytes();
-    }));
-    h.tok_off[0] = 0;
-    *h_tok_off = h.tok_off;
-    *h_score = h.score;
+    TRY(r.open(c, n_files));
     if (n_files == 0) return SPKD_OK;
     std::vector<char> tab;
     Call call(c);
     TRY(call.opened);
     VadTables t;
     TRY(upload_parts(c, S_VAD_TAB, tab, [&](Layout L) {
-        return L.part(t.frame_off, nf + 1, h_frame_off).part(t.back_off, nf + 1, (const int64_t*)back_off.data())
+        return L.part(t.frame_off, nf + 1, h_frame_off).part(t.back_off, nf + 1, back_off.data())
             .part(t.stay, W, h_stay).part(t.exit, W, h_exit).part(t.enter, W, h_enter).part(t.word_state, W, h_word_state)
             .bytes();
     }));
-    VadFiles d;
-    TRY(carve(c, scratch, S_VAD_FILES, [&](Layout L) {
-        return L.part(d.tok_off, nf + 1).part(d.count, nf).part(d.score, nf).part(d.final_word, nf).bytes();
-    }));
+    TRY(r.place(c));
     void* back = nullptr;
     TRY(scratch(c, S_VAD_BACK, (size_t)back_off[nf] * rec_bytes, &back));
     {
         Timer tm(c, SPKD_T_VAD_VITERBI);
-        switch (G) {
-            case 1: vad_decode_launch<1>(c, d_scores, t, n_files, n_states, n_words, back, d); break;
-            case 2: vad_decode_launch<2>(c, d_scores, t, n_files, n_states, n_words, back, d); break;
-            case 4: vad_decode_launch<4>(c, d_scores, t, n_files, n_states, n_words, back, d); break;
-            case 8: vad_decode_launch<8>(c, d_scores, t, n_files, n_states, n_words, back, d); break;
-            default: vad_decode_launch<16>(c, d_scores, t, n_files, n_states, n_words, back, d); break;
-        }
+        with_group(n_words, [&](auto g) {
+            vad_decode_launch<decltype(g)::value>(c, d_scores, t, n_files, n_states, n_words, back, r.d);
+        });
     }
     HIPCHK(c, hipGetLastError());
-    int64_t *d_tok_frame = nullptr, *h_frames = nullptr;
-    int32_t *d_tok_word = nullptr, *h_words = nullptr;
-    {
-        // both passes of k_vad_backtrack and the copy of the counts between them
-        Timer tm(c, SPKD_T_VAD_BACKTRACK);
-        if (G == 16) vad_backtrack_launch<VbRecord<16>::type, false>(c, back, t, n_files, G, d, nullptr, nullptr);
-        else vad_backtrack_launch<VbRecord<1>::type, false>(c, back, t, n_files, G, d, nullptr, nullptr);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h.count, d.count, nf * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(h.score, d.score, nf * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (size_t f = 0; f < nf; ++f) h.tok_off[f + 1] = h.tok_off[f] + h.count[f];
-        const size_t n_tok = (size_t)h.tok_off[nf];
-        TRY(carve(c, scratch, S_VAD_TOKENS, [&](Layout L) { return L.part(d_tok_frame, n_tok).part(d_tok_word, n_tok).bytes(); }));
-        TRY(carve(c, pinned, PIN_VAD_TOKENS, [&](Layout L) { return L.part(h_frames, n_tok).part(h_words, n_tok).bytes(); }));
-        HIPCHK(c, hipMemcpyAsync(d.tok_off, h.tok_off, (nf + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        if (G == 16) vad_backtrack_launch<VbRecord<16>::type, true>(c, back, t, n_files, G, d, d_tok_frame, d_tok_word);
-        else vad_backtrack_launch<VbRecord<1>::type, true>(c, back, t, n_files, G, d, d_tok_frame, d_tok_word);
-        HIPCHK(c, hipGetLastError());
-        if (n_tok) {
-            HIPCHK(c, hipMemcpyAsync(h_frames, d_tok_frame, n_tok * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(h_words, d_tok_word, n_tok * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        }
-    }
-    *h_tok_frame = h_frames;
-    *h_tok_word = h_words;
+    TRY(r.hand_back(c, SPKD_T_VAD_BACKTRACK,
+        [&](const VadFiles& d) {
+            if (G == 16) vad_backtrack_launch<VbRecord<16>::type, false>(c, back, t, n_files, G, d, nullptr, nullptr);
+            else vad_backtrack_launch<VbRecord<1>::type, false>(c, back, t, n_files, G, d, nullptr, nullptr);
+        },
+        [&](const VadFiles& d, int64_t* tok_frame, int32_t* tok_word) {
+            if (G == 16) vad_backtrack_launch<VbRecord<16>::type, true>(c, back, t, n_files, G, d, tok_frame, tok_word);
+            else vad_backtrack_launch<VbRecord<1>::type, true>(c, back, t, n_files, G, d, tok_frame, tok_word);
+        }));
     return call.finish();
 }
 
@@ -2269,41 +2320,25 @@ spkd_status spkd_mindur_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_
                                       int32_t n_cols, double penalty, int32_t min_frames, const int64_t** h_tok_off,
                                       const int64_t** h_tok_frame, const int32_t** h_tok_word, const double** h_score) {
     if (!c) return SPKD_EINVAL;
-    if (!h_tok_off || !h_tok_frame || !h_tok_word || !h_score) return fail(c, SPKD_EINVAL, "mindur_viterbi_batch: null output");
-    *h_tok_off = nullptr;
-    *h_tok_frame = nullptr;
-    *h_tok_word = nullptr;
-    *h_score = nullptr;
+    TokenHandBack r{h_tok_off, h_tok_frame, h_tok_word, h_score, PIN_MD_SEQS, PIN_MD_TOKENS, S_MD_SEQS, S_MD_TOKENS};
+    if (!r.clear()) return fail(c, SPKD_EINVAL, "mindur_viterbi_batch: null output");
     if (n_cols < 1 || n_cols > GM_MAX_S) return fail(c, SPKD_EINVAL, "mindur_viterbi_batch: 1 <= n_cols <= 16");
     if (!std::isfinite(penalty) || penalty < 0.0) return fail(c, SPKD_EINVAL, "mindur_viterbi_batch: a finite penalty >= 0");
     if (min_frames < 1) return fail(c, SPKD_EINVAL, "mindur_viterbi_batch: min_frames >= 1");
     TRY(vad_check_offsets(c, n_seq, h_frame_off));
     if (h_frame_off[n_seq] > 0 && !d_scores) return fail(c, SPKD_EINVAL, "mindur_viterbi_batch: null device buffer");
     const size_t nf = (size_t)n_seq;
-    std::vector<int64_t> rec_off(nf + 1, 0);
-    for (size_t f = 0; f < nf; ++f)
-        rec_off[f + 1] = rec_off[f] + (h_frame_off[f + 1] - h_frame_off[f] + MD_TILE - 1) / MD_TILE * MD_TILE;
-    int G = 1;
-    while (G < n_cols) G *= 2;
-    VadFiles h;                  // pinned: the results of the call
-    TRY(carve(c, pinned, PIN_MD_SEQS, [&](Layout L) {
-        return L.part(h.tok_off, nf + 1).part(h.count, nf).part(h.score, nf).part(h.final_word, nf).bytes();
-    }));
-    h.tok_off[0] = 0;
-    *h_tok_off = h.tok_off;
-    *h_score = h.score;
+    const std::vector<int64_t> rec_off = tiled_offsets(h_frame_off, nf, MD_TILE);
+    TRY(r.open(c, n_seq));
     if (n_seq == 0) return SPKD_OK;
     std::vector<char> tab;
     Call call(c);
     TRY(call.opened);
     MdTables t;
     TRY(upload_parts(c, S_MD_TAB, tab, [&](Layout L) {
-        return L.part(t.frame_off, nf + 1, h_frame_off).part(t.rec_off, nf + 1, (const int64_t*)rec_off.data()).bytes();
+        return L.part(t.frame_off, nf + 1, h_frame_off).part(t.rec_off, nf + 1, rec_off.data()).bytes();
     }));
-    VadFiles d;
-    TRY(carve(c, scratch, S_MD_SEQS, [&](Layout L) {
-        return L.part(d.tok_off, nf + 1).part(d.count, nf).part(d.score, nf).part(d.final_word, nf).bytes();
-    }));
+    TRY(r.place(c));
     MdWork w;
     void* p = nullptr;
     const size_t n_rec = (size_t)rec_off[nf];
@@ -2315,39 +2350,16 @@ spkd_status spkd_mindur_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_
     w.b = (int32_t*)p;
     {
         Timer tm(c, SPKD_T_MINDUR_VITERBI);
-        switch (G) {
-            case 1: mindur_decode_launch<1>(c, d_scores, t, n_seq, n_cols, penalty, min_frames, w, d); break;
-            case 2: mindur_decode_launch<2>(c, d_scores, t, n_seq, n_cols, penalty, min_frames, w, d); break;
-            case 4: mindur_decode_launch<4>(c, d_scores, t, n_seq, n_cols, penalty, min_frames, w, d); break;
-            case 8: mindur_decode_launch<8>(c, d_scores, t, n_seq, n_cols, penalty, min_frames, w, d); break;
-            default: mindur_decode_launch<16>(c, d_scores, t, n_seq, n_cols, penalty, min_frames, w, d); break;
-        }
+        with_group(n_cols, [&](auto g) {
+            mindur_decode_launch<decltype(g)::value>(c, d_scores, t, n_seq, n_cols, penalty, min_frames, w, r.d);
+        });
     }
     HIPCHK(c, hipGetLastError());
-    int64_t *d_tok_frame = nullptr, *h_frames = nullptr;
-    int32_t *d_tok_word = nullptr, *h_words = nullptr;
-    {
-        // both passes of k_mindur_backtrack and the copy of the counts between them
-        Timer tm(c, SPKD_T_MINDUR_BACKTRACK);
-        mindur_backtrack_launch<false>(c, t, n_seq, min_frames, w, d, nullptr, nullptr);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h.count, d.count, nf * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(h.score, d.score, nf * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        for (size_t f = 0; f < nf; ++f) h.tok_off[f + 1] = h.tok_off[f] + h.count[f];
-        const size_t n_tok = (size_t)h.tok_off[nf];
-        TRY(carve(c, scratch, S_MD_TOKENS, [&](Layout L) { return L.part(d_tok_frame, n_tok).part(d_tok_word, n_tok).bytes(); }));
-        TRY(carve(c, pinned, PIN_MD_TOKENS, [&](Layout L) { return L.part(h_frames, n_tok).part(h_words, n_tok).bytes(); }));
-        HIPCHK(c, hipMemcpyAsync(d.tok_off, h.tok_off, (nf + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-        mindur_backtrack_launch<true>(c, t, n_seq, min_frames, w, d, d_tok_frame, d_tok_word);
-        HIPCHK(c, hipGetLastError());
-        if (n_tok) {
-            HIPCHK(c, hipMemcpyAsync(h_frames, d_tok_frame, n_tok * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(h_words, d_tok_word, n_tok * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        }
-    }
-    *h_tok_frame = h_frames;
-    *h_tok_word = h_words;
+    TRY(r.hand_back(c, SPKD_T_MINDUR_BACKTRACK,
+        [&](const VadFiles& d) { mindur_backtrack_launch<false>(c, t, n_seq, min_frames, w, d, nullptr, nullptr); },
+        [&](const VadFiles& d, int64_t* tok_frame, int32_t* tok_word) {
+            mindur_backtrack_launch<true>(c, t, n_seq, min_frames, w, d, tok_frame, tok_word);
+        }));
     return call.finish();
 }
 
@@ -2374,6 +2386,73 @@ spkd_status spkd_gauss_models(spkd_ctx* c, const double* d_stats, int64_t n, dou
     return call.finish();
 }
 
+namespace {
+extern "C++" {
+// An index table (SeqTable, RangeTable) goes up in one copy.  Its parts() are listed once and placed twice:
+// by build(), before the Call, as the image h in pinned memory that the checked arguments fill; by this,
+// inside the Call, as d on the device, with the copy enqueued.
+template <class Table>
+spkd_status send_table(spkd_ctx* c, int slot, Table& t) {
+    TRY(carve(c, scratch, slot, [&](Layout L) { return t.parts(L, t.d); }));
+    HIPCHK(c, hipMemcpyAsync(t.d.begin, t.h.begin, t.image, hipMemcpyHostToDevice, c->stream));
+    return SPKD_OK;
+}
+}  // extern "C++"
+
+// The sequence table of spkd_gauss_loglik and spkd_gmm_loglik_seq, as the kernels take it: per sequence its
+// frames [begin, end), its first row of the scores, its first tile, its first model and its model count;
+// per model ok; per tile its sequence.
+struct SeqTable {
+    struct Tab { long long *begin, *end, *row, *tile; int *model, *n_models, *ok, *tile_seq; } h{}, d{};
+    size_t ns = 0, nm = 0, nt = 0, image = 0;  // sequences, models, tiles (0: no frame, nothing to do), bytes
+
+    size_t parts(Layout L, Tab& t) const {
+        return L.part(t.begin, ns).part(t.end, ns).part(t.row, ns).part(t.tile, ns).part(t.model, ns).part(t.n_models, ns)
+            .part(t.ok, nm).part(t.tile_seq, nt).bytes();
+    }
+    // the checks that the two calls share (`name` opens their messages), the tiles counted, the image filled
+    spkd_status build(spkd_ctx* c, const std::string& name, int64_t tile_frames, int pin_slot, const float* d_frames,
+                      int64_t n_frames, const double* d_models, int64_t n_models, const int32_t* h_model_ok, int64_t n_seq,
+                      const int64_t* h_seq_begin, const int64_t* h_seq_end, const int32_t* h_seq_model,
+                      const int32_t* h_seq_n_models, int32_t n_cols, const float* d_scores) {
+        if (n_cols < 1 || n_cols > GS_MAX_COLS) return fail(c, SPKD_EINVAL, name + ": 1 <= n_cols <= 16");
+        if (n_frames < 0 || n_models < 0 || n_models > 0x7fffffff || n_seq > 0x7fffffff)
+            return fail(c, SPKD_EINVAL, name + ": bad count");
+        if ((uintptr_t)d_models % 16 || (uintptr_t)d_frames % 4 || (uintptr_t)d_scores % 4)
+            return fail(c, SPKD_EINVAL, name + ": misaligned buffer (models: 16 bytes)");
+        int64_t n_tiles = 0;
+        for (int64_t q = 0; q < n_seq; ++q) {
+            const int64_t b = h_seq_begin[q], e = h_seq_end[q];
+            if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, name + ": sequence outside [0, n_frames]");
+            const int64_t m = h_seq_model[q], k = h_seq_n_models[q];
+            if (k < 0 || k > n_cols) return fail(c, SPKD_EINVAL, name + ": 0 <= models of a sequence <= n_cols");
+            if (m < 0 || m + k > n_models) return fail(c, SPKD_EINVAL, name + ": model index out of range");
+            n_tiles += (e - b + tile_frames - 1) / tile_frames;
+        }
+        if (n_tiles == 0) return SPKD_OK;
+        if (n_tiles > 0x7fffffff) return fail(c, SPKD_EINVAL, name + ": too many frames in one call");
+        ns = (size_t)n_seq, nm = (size_t)n_models, nt = (size_t)n_tiles;
+        TRY(carve(c, pinned, pin_slot, [&](Layout L) { return image = parts(L, h); }));
+        std::memcpy(h.begin, h_seq_begin, ns * sizeof(int64_t));
+        std::memcpy(h.end, h_seq_end, ns * sizeof(int64_t));
+        std::memcpy(h.model, h_seq_model, ns * sizeof(int32_t));
+        std::memcpy(h.n_models, h_seq_n_models, ns * sizeof(int32_t));
+        std::memcpy(h.ok, h_model_ok, nm * sizeof(int32_t));
+        long long row = 0, tile = 0;
+        for (size_t q = 0; q < ns; ++q) {
+            h.row[q] = row;
+            h.tile[q] = tile;
+            const long long len = h.end[q] - h.begin[q], k = (len + tile_frames - 1) / tile_frames;
+            for (long long i = 0; i < k; ++i) h.tile_seq[tile + i] = (int)q;
+            row += len;
+            tile += k;
+        }
+        return SPKD_OK;
+    }
+};
+static_assert(sizeof(long long) == sizeof(int64_t) && sizeof(int) == sizeof(int32_t), "the tables take the caller's arrays as they are");
+}  // namespace
+
 spkd_status spkd_gauss_loglik(spkd_ctx* c, const float* d_frames, int64_t n_frames, const double* d_models,
                               int64_t n_models, const int32_t* h_model_ok, int64_t n_seq, const int64_t* h_seq_begin,
                               const int64_t* h_seq_end, const int32_t* h_seq_model, const int32_t* h_seq_n_models,
@@ -2382,56 +2461,18 @@ spkd_status spkd_gauss_loglik(spkd_ctx* c, const float* d_frames, int64_t n_fram
     if (n_seq == 0) return SPKD_OK;
     if (!d_frames || !d_models || !h_model_ok || !h_seq_begin || !h_seq_end || !h_seq_model || !h_seq_n_models || !d_scores)
         return fail(c, SPKD_EINVAL, "null argument");
-    if (n_cols < 1 || n_cols > GS_MAX_COLS) return fail(c, SPKD_EINVAL, "gauss_loglik: 1 <= n_cols <= 16");
-    if (n_frames < 0 || n_models < 0 || n_models > 0x7fffffff || n_seq > 0x7fffffff)
-        return fail(c, SPKD_EINVAL, "gauss_loglik: bad count");
-    if ((uintptr_t)d_models % 16 || (uintptr_t)d_frames % 4 || (uintptr_t)d_scores % 4)
-        return fail(c, SPKD_EINVAL, "gauss_loglik: misaligned buffer (models: 16 bytes)");
-    int64_t total = 0, n_tiles = 0;
-    for (int64_t q = 0; q < n_seq; ++q) {
-        const int64_t b = h_seq_begin[q], e = h_seq_end[q];
-        if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, "gauss_loglik: sequence outside [0, n_frames]");
-        const int64_t m = h_seq_model[q], k = h_seq_n_models[q];
-        if (k < 0 || k > n_cols) return fail(c, SPKD_EINVAL, "gauss_loglik: 0 <= models of a sequence <= n_cols");
-        if (m < 0 || m + k > n_models) return fail(c, SPKD_EINVAL, "gauss_loglik: model index out of range");
-        total += e - b;
-        n_tiles += (e - b + GS_TILE - 1) / GS_TILE;
-    }
-    if (total == 0) return SPKD_OK;
-    if (n_tiles > 0x7fffffff) return fail(c, SPKD_EINVAL, "gauss_loglik: too many frames in one call");
-    const size_t ns = (size_t)n_seq, nm = (size_t)n_models, nt = (size_t)n_tiles;
-    // every index array as one image in pinned memory: one copy up
-    struct Tab { int64_t *begin, *end, *row, *tile; int32_t *model, *n_models, *ok, *tile_seq; } h, d;
-    auto parts = [&](Layout L, Tab& t) {
-        return L.part(t.begin, ns).part(t.end, ns).part(t.row, ns).part(t.tile, ns).part(t.model, ns).part(t.n_models, ns)
-            .part(t.ok, nm).part(t.tile_seq, nt).bytes();
-    };
-    size_t image = 0;
-    TRY(carve(c, pinned, PIN_GAUSS_IDX, [&](Layout L) { return image = parts(L, h); }));
-    std::memcpy(h.begin, h_seq_begin, ns * sizeof(int64_t));
-    std::memcpy(h.end, h_seq_end, ns * sizeof(int64_t));
-    std::memcpy(h.model, h_seq_model, ns * sizeof(int32_t));
-    std::memcpy(h.n_models, h_seq_n_models, ns * sizeof(int32_t));
-    std::memcpy(h.ok, h_model_ok, nm * sizeof(int32_t));
-    int64_t row = 0, tile = 0;
-    for (size_t q = 0; q < ns; ++q) {
-        h.row[q] = row;
-        h.tile[q] = tile;
-        const int64_t len = h.end[q] - h.begin[q], k = (len + GS_TILE - 1) / GS_TILE;
-        for (int64_t i = 0; i < k; ++i) h.tile_seq[tile + i] = (int32_t)q;
-        row += len;
-        tile += k;
-    }
+    SeqTable t;
+    TRY(t.build(c, "gauss_loglik", GS_TILE, PIN_GAUSS_IDX, d_frames, n_frames, d_models, n_models, h_model_ok, n_seq,
+                h_seq_begin, h_seq_end, h_seq_model, h_seq_n_models, n_cols, d_scores));
+    if (!t.nt) return SPKD_OK;
     Call call(c);
     TRY(call.opened);
-    TRY(carve(c, scratch, S_GAUSS_IDX, [&](Layout L) { return parts(L, d); }));
-    HIPCHK(c, hipMemcpyAsync(d.begin, h.begin, image, hipMemcpyHostToDevice, c->stream));
+    TRY(send_table(c, S_GAUSS_IDX, t));
     {
-        Timer t(c, SPKD_T_GAUSS_LOGLIK);
-        hipLaunchKernelGGL(k_gauss_loglik, dim3((unsigned)n_tiles), dim3(WAVE), 0, c->stream, d_frames, d_models,
-                           (const int*)d.ok, (const long long*)d.begin, (const long long*)d.end, (const long long*)d.row,
-                           (const long long*)d.tile, (const int*)d.model, (const int*)d.n_models, (const int*)d.tile_seq,
-                           (int)n_cols, d_scores);
+        Timer tm(c, SPKD_T_GAUSS_LOGLIK);
+        hipLaunchKernelGGL(k_gauss_loglik, dim3((unsigned)t.nt), dim3(WAVE), 0, c->stream, d_frames, d_models, t.d.ok,
+                           t.d.begin, t.d.end, t.d.row, t.d.tile, t.d.model, t.d.n_models, t.d.tile_seq, (int)n_cols,
+                           d_scores);
     }
     HIPCHK(c, hipGetLastError());
     return call.finish();
@@ -2440,6 +2481,59 @@ spkd_status spkd_gauss_loglik(spkd_ctx* c, const float* d_frames, int64_t n_fram
 // ------------------------------------------------------------------ (9) mixture speaker models and their scores
 static_assert(GT_COMP == SPKD_GMM_COMP && GT_MAX_COMP == SPKD_GMM_MAX_COMP && GT_TILE == SPKD_GMM_TILE &&
               GT_CHUNK_TILES == SPKD_GMM_CHUNK_TILES, "the header states the kernels' layout and partition");
+
+namespace {
+// The range-set table of spkd_gmm_train and spkd_ubm_stats, as the kernels take it: per range its first
+// frame and the ordinal of that frame among its speaker's; per speaker its ranges [set_off], its frame
+// count n and its chunks [chunk_off]; per chunk its speaker and its index within the speaker.
+struct RangeTable {
+    struct Tab { long long *begin, *ord, *set_off, *n, *chunk_off; int *chunk_spk, *chunk_idx; } h{}, d{};
+    size_t ns = 0, nr = 0, nc = 0, image = 0;  // speakers, ranges, chunks, bytes
+
+    size_t parts(Layout L, Tab& t) const {
+        return L.part(t.begin, nr).part(t.ord, nr).part(t.set_off, ns + 1).part(t.n, ns).part(t.chunk_off, ns + 1)
+            .part(t.chunk_spk, nc).part(t.chunk_idx, nc).bytes();
+    }
+    // the checks that the two calls share (`name` opens their messages), the chunks counted, the image filled
+    spkd_status build(spkd_ctx* c, const std::string& name, int pin_slot, int64_t n_frames, int64_t n_speakers,
+                      const int64_t* h_set_off, const int64_t* h_range_begin, const int64_t* h_range_end) {
+        if (h_set_off[0] != 0) return fail(c, SPKD_EINVAL, name + ": set_off[0] must be 0");
+        for (int64_t s = 0; s < n_speakers; ++s)
+            if (h_set_off[s + 1] <= h_set_off[s]) return fail(c, SPKD_EINVAL, name + ": set_off must ascend: no empty set");
+        int64_t n_chunks = 0;
+        for (int64_t s = 0; s < n_speakers; ++s) {
+            int64_t n = 0;
+            for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
+                const int64_t b = h_range_begin[r], e = h_range_end[r];
+                if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, name + ": range outside [0, n_frames]");
+                n += e - b;
+            }
+            n_chunks += (n + GT_CHUNK - 1) / GT_CHUNK;
+        }
+        if (n_chunks > 0x7fffffff) return fail(c, SPKD_EINVAL, name + ": too many frames in one call");
+        ns = (size_t)n_speakers, nr = (size_t)h_set_off[n_speakers], nc = (size_t)n_chunks;
+        TRY(carve(c, pinned, pin_slot, [&](Layout L) { return image = parts(L, h); }));
+        std::memcpy(h.begin, h_range_begin, nr * sizeof(int64_t));
+        std::memcpy(h.set_off, h_set_off, (ns + 1) * sizeof(int64_t));
+        long long chunk = 0;
+        for (size_t s = 0; s < ns; ++s) {
+            long long n = 0;
+            for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
+                h.ord[r] = n;
+                n += h_range_end[r] - h_range_begin[r];
+            }
+            h.n[s] = n;
+            h.chunk_off[s] = chunk;
+            for (long long i = 0; i < (n + GT_CHUNK - 1) / GT_CHUNK; ++i, ++chunk) {
+                h.chunk_spk[chunk] = (int)s;
+                h.chunk_idx[chunk] = (int)i;
+            }
+        }
+        h.chunk_off[ns] = chunk;
+        return SPKD_OK;
+    }
+};
+}  // namespace
 
 spkd_status spkd_gmm_train(spkd_ctx* c, const float* d_frames, int64_t n_frames, int64_t n_speakers,
                            const int64_t* h_set_off, const int64_t* h_range_begin, const int64_t* h_range_end,
@@ -2454,48 +2548,9 @@ spkd_status spkd_gmm_train(spkd_ctx* c, const float* d_frames, int64_t n_frames,
     if (!(var_floor >= 0.0) || !std::isfinite(var_floor)) return fail(c, SPKD_EINVAL, "gmm_train: var_floor must be finite and >= 0");
     if (n_frames < 0 || n_speakers > 0x7fffffff) return fail(c, SPKD_EINVAL, "gmm_train: bad count");
     if ((uintptr_t)d_gmm % 16 || (uintptr_t)d_frames % 4) return fail(c, SPKD_EINVAL, "gmm_train: misaligned buffer (models: 16 bytes)");
-    if (h_set_off[0] != 0) return fail(c, SPKD_EINVAL, "gmm_train: set_off[0] must be 0");
-    for (int64_t s = 0; s < n_speakers; ++s)
-        if (h_set_off[s + 1] <= h_set_off[s]) return fail(c, SPKD_EINVAL, "gmm_train: set_off must ascend: no empty set");
-    const int64_t n_ranges = h_set_off[n_speakers];
-    const size_t ns = (size_t)n_speakers, nr = (size_t)n_ranges;
-    int64_t n_chunks = 0;
-    for (int64_t s = 0; s < n_speakers; ++s) {
-        int64_t n = 0;
-        for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
-            const int64_t b = h_range_begin[r], e = h_range_end[r];
-            if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, "gmm_train: range outside [0, n_frames]");
-            n += e - b;
-        }
-        n_chunks += (n + GT_CHUNK - 1) / GT_CHUNK;
-    }
-    if (n_chunks > 0x7fffffff) return fail(c, SPKD_EINVAL, "gmm_train: too many frames in one call");
-    const size_t nc = (size_t)n_chunks, nl = ns * (size_t)n_iter;
-    // every index array as one image in pinned memory: one copy up
-    struct Tab { int64_t *begin, *ord, *set_off, *n, *chunk_off; int32_t *chunk_spk, *chunk_idx; } h, d;
-    auto parts = [&](Layout L, Tab& t) {
-        return L.part(t.begin, nr).part(t.ord, nr).part(t.set_off, ns + 1).part(t.n, ns).part(t.chunk_off, ns + 1)
-            .part(t.chunk_spk, nc).part(t.chunk_idx, nc).bytes();
-    };
-    size_t image = 0;
-    TRY(carve(c, pinned, PIN_GT_TAB, [&](Layout L) { return image = parts(L, h); }));
-    std::memcpy(h.begin, h_range_begin, nr * sizeof(int64_t));
-    std::memcpy(h.set_off, h_set_off, (ns + 1) * sizeof(int64_t));
-    int64_t chunk = 0;
-    for (size_t s = 0; s < ns; ++s) {
-        int64_t n = 0;
-        for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
-            h.ord[r] = n;
-            n += h_range_end[r] - h_range_begin[r];
-        }
-        h.n[s] = n;
-        h.chunk_off[s] = chunk;
-        for (int64_t i = 0; i < (n + GT_CHUNK - 1) / GT_CHUNK; ++i, ++chunk) {
-            h.chunk_spk[chunk] = (int32_t)s;
-            h.chunk_idx[chunk] = (int32_t)i;
-        }
-    }
-    h.chunk_off[ns] = chunk;
+    RangeTable t;
+    TRY(t.build(c, "gmm_train", PIN_GT_TAB, n_frames, n_speakers, h_set_off, h_range_begin, h_range_end));
+    const size_t ns = t.ns, nc = t.nc, nl = ns * (size_t)n_iter;
     // what comes back: the ok flags and the log-likelihoods, through pinned memory as well
     struct Out { double* loglik; int32_t* ok; } ho, dout;
     double *d_part = nullptr, *d_part_ll = nullptr, *d_floor = nullptr;
@@ -2504,39 +2559,30 @@ spkd_status spkd_gmm_train(spkd_ctx* c, const float* d_frames, int64_t n_frames,
     TRY(carve(c, pinned, PIN_GT_OUT, [&](Layout L) { return out_bytes = outs(L, ho); }));
     Call call(c);
     TRY(call.opened);
-    TRY(carve(c, scratch, S_GT_TAB, [&](Layout L) { return parts(L, d); }));
+    TRY(send_table(c, S_GT_TAB, t));
     TRY(carve(c, scratch, S_GT_WORK, [&](Layout L) {
         outs(L, dout);                                                   // (first: one copy down)
         L.at = out_bytes;
         return L.part(d_part, nc * (size_t)n_comp * GT_COMP).part(d_part_ll, nc).part(d_floor, ns * WAVE).bytes();
     }));
-    HIPCHK(c, hipMemcpyAsync(d.begin, h.begin, image, hipMemcpyHostToDevice, c->stream));
     {
-        Timer t(c, SPKD_T_GMM_TRAIN);
-        auto estep = [&](bool hard) {
-            if (!nc) return;
-            if (hard)
-                hipLaunchKernelGGL(k_gmm_estep<true>, dim3((unsigned)nc), dim3(WAVE), 0, c->stream, d_frames,
-                                   (const long long*)d.begin, (const long long*)d.ord, (const long long*)d.set_off,
-                                   (const long long*)d.n, (const int*)d.chunk_spk, (const int*)d.chunk_idx,
-                                   (const double*)d_gmm, (int)n_comp, d_part, d_part_ll);
-            else
-                hipLaunchKernelGGL(k_gmm_estep<false>, dim3((unsigned)nc), dim3(WAVE), 0, c->stream, d_frames,
-                                   (const long long*)d.begin, (const long long*)d.ord, (const long long*)d.set_off,
-                                   (const long long*)d.n, (const int*)d.chunk_spk, (const int*)d.chunk_idx,
-                                   (const double*)d_gmm, (int)n_comp, d_part, d_part_ll);
+        Timer tm(c, SPKD_T_GMM_TRAIN);
+        auto estep = [&](auto hard) {
+            if (nc)
+                hipLaunchKernelGGL(k_gmm_estep<decltype(hard)::value>, dim3((unsigned)nc), dim3(WAVE), 0, c->stream, d_frames,
+                                   t.d.begin, t.d.ord, t.d.set_off, t.d.n, t.d.chunk_spk, t.d.chunk_idx, d_gmm,
+                                   (int)n_comp, d_part, d_part_ll);
         };
         auto mstep = [&](int init, int iter) {
-            hipLaunchKernelGGL(k_gmm_mstep, dim3((unsigned)ns), dim3(WAVE), 0, c->stream, (const double*)d_part,
-                               (const double*)d_part_ll, (const long long*)d.chunk_off, (const long long*)d.n, (int)n_comp,
-                               init, from_model ? 0 : 1, var_floor, iter, (int)n_iter, d_gmm, d_floor, (int*)dout.ok,
-                               dout.loglik);
+            hipLaunchKernelGGL(k_gmm_mstep, dim3((unsigned)ns), dim3(WAVE), 0, c->stream, d_part, d_part_ll, t.d.chunk_off,
+                               t.d.n, (int)n_comp, init, from_model ? 0 : 1, var_floor, iter, (int)n_iter, d_gmm, d_floor,
+                               dout.ok, dout.loglik);
         };
         // the whole loop in one go: the hard pass (floor, first ok, initial model), then n_iter EM steps
-        estep(true);
+        estep(std::true_type());
         mstep(1, 0);
         for (int i = 0; i < n_iter; ++i) {
-            estep(false);
+            estep(std::false_type());
             mstep(0, i);
         }
     }
@@ -2557,55 +2603,17 @@ spkd_status spkd_gmm_loglik_seq(spkd_ctx* c, const float* d_frames, int64_t n_fr
     if (!d_frames || !d_gmm || !h_model_ok || !h_seq_begin || !h_seq_end || !h_seq_model || !h_seq_n_models || !d_scores)
         return fail(c, SPKD_EINVAL, "null argument");
     if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: 1 <= n_comp <= 8");
-    if (n_cols < 1 || n_cols > GS_MAX_COLS) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: 1 <= n_cols <= 16");
-    if (n_frames < 0 || n_models < 0 || n_models > 0x7fffffff || n_seq > 0x7fffffff)
-        return fail(c, SPKD_EINVAL, "gmm_loglik_seq: bad count");
-    if ((uintptr_t)d_gmm % 16 || (uintptr_t)d_frames % 4 || (uintptr_t)d_scores % 4)
-        return fail(c, SPKD_EINVAL, "gmm_loglik_seq: misaligned buffer (models: 16 bytes)");
-    int64_t total = 0, n_tiles = 0;
-    for (int64_t q = 0; q < n_seq; ++q) {
-        const int64_t b = h_seq_begin[q], e = h_seq_end[q];
-        if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: sequence outside [0, n_frames]");
-        const int64_t m = h_seq_model[q], k = h_seq_n_models[q];
-        if (k < 0 || k > n_cols) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: 0 <= models of a sequence <= n_cols");
-        if (m < 0 || m + k > n_models) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: model index out of range");
-        total += e - b;
-        n_tiles += (e - b + GT_TILE - 1) / GT_TILE;
-    }
-    if (total == 0) return SPKD_OK;
-    if (n_tiles > 0x7fffffff) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: too many frames in one call");
-    const size_t ns = (size_t)n_seq, nm = (size_t)n_models, nt = (size_t)n_tiles;
-    // every index array as one image in pinned memory: one copy up
-    struct Tab { int64_t *begin, *end, *row, *tile; int32_t *model, *n_models, *ok, *tile_seq; } h, d;
-    auto parts = [&](Layout L, Tab& t) {
-        return L.part(t.begin, ns).part(t.end, ns).part(t.row, ns).part(t.tile, ns).part(t.model, ns).part(t.n_models, ns)
-            .part(t.ok, nm).part(t.tile_seq, nt).bytes();
-    };
-    size_t image = 0;
-    TRY(carve(c, pinned, PIN_GT_IDX, [&](Layout L) { return image = parts(L, h); }));
-    std::memcpy(h.begin, h_seq_begin, ns * sizeof(int64_t));
-    std::memcpy(h.end, h_seq_end, ns * sizeof(int64_t));
-    std::memcpy(h.model, h_seq_model, ns * sizeof(int32_t));
-    std::memcpy(h.n_models, h_seq_n_models, ns * sizeof(int32_t));
-    std::memcpy(h.ok, h_model_ok, nm * sizeof(int32_t));
-    int64_t row = 0, tile = 0;
-    for (size_t q = 0; q < ns; ++q) {
-        h.row[q] = row;
-        h.tile[q] = tile;
-        const int64_t len = h.end[q] - h.begin[q], k = (len + GT_TILE - 1) / GT_TILE;
-        for (int64_t i = 0; i < k; ++i) h.tile_seq[tile + i] = (int32_t)q;
-        row += len;
-        tile += k;
-    }
+    SeqTable t;
+    TRY(t.build(c, "gmm_loglik_seq", GT_TILE, PIN_GT_IDX, d_frames, n_frames, d_gmm, n_models, h_model_ok, n_seq,
+                h_seq_begin, h_seq_end, h_seq_model, h_seq_n_models, n_cols, d_scores));
+    if (!t.nt) return SPKD_OK;
     Call call(c);
     TRY(call.opened);
-    TRY(carve(c, scratch, S_GT_IDX, [&](Layout L) { return parts(L, d); }));
-    HIPCHK(c, hipMemcpyAsync(d.begin, h.begin, image, hipMemcpyHostToDevice, c->stream));
+    TRY(send_table(c, S_GT_IDX, t));
     {
-        Timer t(c, SPKD_T_GMM_SEQ_LOGLIK);
-        hipLaunchKernelGGL(k_gmm_loglik_seq, dim3((unsigned)n_tiles), dim3(WAVE), 0, c->stream, d_frames, d_gmm, (int)n_comp,
-                           (const int*)d.ok, (const long long*)d.begin, (const long long*)d.end, (const long long*)d.row,
-                           (const long long*)d.tile, (const int*)d.model, (const int*)d.n_models, (const int*)d.tile_seq,
+        Timer tm(c, SPKD_T_GMM_SEQ_LOGLIK);
+        hipLaunchKernelGGL(k_gmm_loglik_seq, dim3((unsigned)t.nt), dim3(WAVE), 0, c->stream, d_frames, d_gmm, (int)n_comp,
+                           t.d.ok, t.d.begin, t.d.end, t.d.row, t.d.tile, t.d.model, t.d.n_models, t.d.tile_seq,
                            (int)n_cols, d_scores);
     }
     HIPCHK(c, hipGetLastError());
@@ -2626,68 +2634,26 @@ spkd_status spkd_ubm_stats(spkd_ctx* c, const float* d_frames, int64_t n_frames,
     if (n_frames < 0 || n_speakers > 0x7fffffff) return fail(c, SPKD_EINVAL, "ubm_stats: bad count");
     if ((uintptr_t)d_ubm % 16 || (uintptr_t)d_bw % 16 || (uintptr_t)d_frames % 4)
         return fail(c, SPKD_EINVAL, "ubm_stats: misaligned buffer (model and records: 16 bytes)");
-    if (h_set_off[0] != 0) return fail(c, SPKD_EINVAL, "ubm_stats: set_off[0] must be 0");
-    for (int64_t s = 0; s < n_speakers; ++s)
-        if (h_set_off[s + 1] <= h_set_off[s]) return fail(c, SPKD_EINVAL, "ubm_stats: set_off must ascend: no empty set");
-    const int64_t n_ranges = h_set_off[n_speakers];
-    const size_t ns = (size_t)n_speakers, nr = (size_t)n_ranges;
-    int64_t n_chunks = 0;
-    for (int64_t s = 0; s < n_speakers; ++s) {
-        int64_t n = 0;
-        for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
-            const int64_t b = h_range_begin[r], e = h_range_end[r];
-            if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, "ubm_stats: range outside [0, n_frames]");
-            n += e - b;
-        }
-        n_chunks += (n + GT_CHUNK - 1) / GT_CHUNK;
-    }
-    if (n_chunks > 0x7fffffff) return fail(c, SPKD_EINVAL, "ubm_stats: too many frames in one call");
-    const size_t nc = (size_t)n_chunks;
-    // every index array as one image in pinned memory: one copy up (spkd_gmm_train's table)
-    struct Tab { int64_t *begin, *ord, *set_off, *n, *chunk_off; int32_t *chunk_spk, *chunk_idx; } h, d;
-    auto parts = [&](Layout L, Tab& t) {
-        return L.part(t.begin, nr).part(t.ord, nr).part(t.set_off, ns + 1).part(t.n, ns).part(t.chunk_off, ns + 1)
-            .part(t.chunk_spk, nc).part(t.chunk_idx, nc).bytes();
-    };
-    size_t image = 0;
-    TRY(carve(c, pinned, PIN_UBM_TAB, [&](Layout L) { return image = parts(L, h); }));
-    std::memcpy(h.begin, h_range_begin, nr * sizeof(int64_t));
-    std::memcpy(h.set_off, h_set_off, (ns + 1) * sizeof(int64_t));
-    int64_t chunk = 0;
-    for (size_t s = 0; s < ns; ++s) {
-        int64_t n = 0;
-        for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
-            h.ord[r] = n;
-            n += h_range_end[r] - h_range_begin[r];
-        }
-        h.n[s] = n;
-        h.chunk_off[s] = chunk;
-        for (int64_t i = 0; i < (n + GT_CHUNK - 1) / GT_CHUNK; ++i, ++chunk) {
-            h.chunk_spk[chunk] = (int32_t)s;
-            h.chunk_idx[chunk] = (int32_t)i;
-        }
-    }
-    h.chunk_off[ns] = chunk;
+    RangeTable t;
+    TRY(t.build(c, "ubm_stats", PIN_UBM_TAB, n_frames, n_speakers, h_set_off, h_range_begin, h_range_end));
+    const size_t ns = t.ns, nc = t.nc;
     void* h_out = nullptr;
     TRY(pinned(c, PIN_UBM_OUT, ns * sizeof(int32_t), &h_out));
     Call call(c);
     TRY(call.opened);
-    TRY(carve(c, scratch, S_UBM_TAB, [&](Layout L) { return parts(L, d); }));
+    TRY(send_table(c, S_UBM_TAB, t));
     double* d_part = nullptr;
     int32_t* d_ok = nullptr;
     TRY(carve(c, scratch, S_UBM_WORK, [&](Layout L) {
         return L.part(d_part, nc * (size_t)n_comp * BW_COMP).part(d_ok, ns).bytes();
     }));
-    HIPCHK(c, hipMemcpyAsync(d.begin, h.begin, image, hipMemcpyHostToDevice, c->stream));
     {
-        Timer t(c, SPKD_T_UBM_STATS);
+        Timer tm(c, SPKD_T_UBM_STATS);
         if (nc)
-            hipLaunchKernelGGL(k_ubm_estep, dim3((unsigned)nc), dim3(WAVE), 0, c->stream, d_frames,
-                               (const long long*)d.begin, (const long long*)d.ord, (const long long*)d.set_off,
-                               (const long long*)d.n, (const int*)d.chunk_spk, (const int*)d.chunk_idx, d_ubm, (int)n_comp,
-                               d_part);
-        hipLaunchKernelGGL(k_ubm_reduce, dim3((unsigned)ns), dim3(WAVE), 0, c->stream, (const double*)d_part,
-                           (const long long*)d.chunk_off, (const long long*)d.n, (int)n_comp, d_bw, (int*)d_ok);
+            hipLaunchKernelGGL(k_ubm_estep, dim3((unsigned)nc), dim3(WAVE), 0, c->stream, d_frames, t.d.begin, t.d.ord,
+                               t.d.set_off, t.d.n, t.d.chunk_spk, t.d.chunk_idx, d_ubm, (int)n_comp, d_part);
+        hipLaunchKernelGGL(k_ubm_reduce, dim3((unsigned)ns), dim3(WAVE), 0, c->stream, d_part, t.d.chunk_off, t.d.n,
+                           (int)n_comp, d_bw, d_ok);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_out, d_ok, ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));

@@ -756,6 +756,38 @@ class Context(object):
             raise SpkdError(SPKD_EINVAL, 'frame_off: one entry per file and the total')
         return off
 
+    @staticmethod
+    def _tokens(out, n):
+        """Copies of the four arrays that a decoder handed back for n files."""
+        tok_off = _view(out[0].value, n + 1, np.int64).copy()
+        n_tok = int(tok_off[-1])
+        return (tok_off, _view(out[1].value, n_tok, np.int64).copy(), _view(out[2].value, n_tok, np.int32).copy(),
+                _view(out[3].value, n, np.float64).copy())
+
+    @staticmethod
+    def _seq_args(model_ok, seq_begin, seq_end, seq_model, seq_n_models):
+        """-> (the arguments of spkd_gauss_loglik from n_models to h_seq_n_models, frame_off); a pointer keeps its array."""
+        c = np.ascontiguousarray
+        ok = c(model_ok, dtype=np.int32)
+        b, e = c(seq_begin, dtype=np.int64), c(seq_end, dtype=np.int64)
+        m, k = c(seq_model, dtype=np.int32), c(seq_n_models, dtype=np.int32)
+        if any(a.ndim != 1 for a in (ok, b, e, m, k)) or not (len(b) == len(e) == len(m) == len(k)):
+            raise SpkdError(SPKD_EINVAL, 'one begin, end, first model and model count per sequence')
+        frame_off = np.zeros(len(b) + 1, dtype=np.int64)
+        frame_off[1:] = np.cumsum(e - b)
+        return (len(ok), _ptr(ok), len(b), _ptr(b), _ptr(e), _ptr(m), _ptr(k)), frame_off
+
+    @staticmethod
+    def _range_sets(set_off, range_begin, range_end):
+        """-> the arguments of spkd_gmm_train from n_speakers to h_range_end; a pointer keeps its array."""
+        c = np.ascontiguousarray
+        off, b, e = c(set_off, dtype=np.int64), c(range_begin, dtype=np.int64), c(range_end, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1 or b.ndim != 1 or e.ndim != 1:
+            raise SpkdError(SPKD_EINVAL, 'set_off: one entry per speaker and the total')
+        if not (len(b) == len(e) == int(off[-1])):
+            raise SpkdError(SPKD_EINVAL, 'one begin and end per range of the sets')
+        return len(off) - 1, _ptr(off), _ptr(b), _ptr(e)
+
     def vad_shift_batch(self, d_scores, frame_off, n_states, shift, d_out=None):
         """shift_dec_bord for every file of concatenated device scores [sum T, n_states]
         (spkd_vad_shift_batch); d_out=None: in place."""
@@ -777,10 +809,7 @@ class Context(object):
         out = [C.c_void_p() for _ in range(4)]
         self.check(self.lib.spkd_vad_viterbi_batch(self.h, C.c_void_p(d_scores), n, _ptr(off), int(n_states), len(ws),
                                                    _ptr(ws), *[_ptr(a) for a in consts], *[C.byref(o) for o in out]))
-        tok_off = _view(out[0].value, n + 1, np.int64).copy()
-        n_tok = int(tok_off[-1])
-        return (tok_off, _view(out[1].value, n_tok, np.int64).copy(), _view(out[2].value, n_tok, np.int32).copy(),
-                _view(out[3].value, n, np.float64).copy())
+        return self._tokens(out, n)
 
     # ---- (8) resegmentation
     def gauss_models(self, d_stats, n, d_models):
@@ -799,17 +828,9 @@ class Context(object):
         array d_scores [sum len, n_cols] float32; -inf in the columns of models that are not ok and
         from seq_n_models[q] on.  Returns frame_off, the running sum of the lengths: what
         vad_viterbi_batch takes with these scores.  The kernel's time is last_ms('gauss_loglik')."""
-        c = np.ascontiguousarray
-        ok = c(model_ok, dtype=np.int32)
-        b, e = c(seq_begin, dtype=np.int64), c(seq_end, dtype=np.int64)
-        m, k = c(seq_model, dtype=np.int32), c(seq_n_models, dtype=np.int32)
-        if any(a.ndim != 1 for a in (ok, b, e, m, k)) or not (len(b) == len(e) == len(m) == len(k)):
-            raise SpkdError(SPKD_EINVAL, 'one begin, end, first model and model count per sequence')
-        self.check(self.lib.spkd_gauss_loglik(self.h, C.c_void_p(d_frames), int(n_frames), C.c_void_p(d_models), len(ok),
-                                              _ptr(ok), len(b), _ptr(b), _ptr(e), _ptr(m), _ptr(k), int(n_cols),
-                                              C.c_void_p(d_scores)))
-        frame_off = np.zeros(len(b) + 1, dtype=np.int64)
-        frame_off[1:] = np.cumsum(e - b)
+        seqs, frame_off = self._seq_args(model_ok, seq_begin, seq_end, seq_model, seq_n_models)
+        self.check(self.lib.spkd_gauss_loglik(self.h, C.c_void_p(d_frames), int(n_frames), C.c_void_p(d_models), *seqs,
+                                              int(n_cols), C.c_void_p(d_scores)))
         return frame_off
 
     def mindur_viterbi_batch(self, d_scores, frame_off, n_cols, penalty, min_frames):
@@ -823,10 +844,7 @@ class Context(object):
         out = [C.c_void_p() for _ in range(4)]
         self.check(self.lib.spkd_mindur_viterbi_batch(self.h, C.c_void_p(d_scores), n, _ptr(off), int(n_cols), float(penalty),
                                                       int(min_frames), *[C.byref(o) for o in out]))
-        tok_off = _view(out[0].value, n + 1, np.int64).copy()
-        n_tok = int(tok_off[-1])
-        return (tok_off, _view(out[1].value, n_tok, np.int64).copy(), _view(out[2].value, n_tok, np.int32).copy(),
-                _view(out[3].value, n, np.float64).copy())
+        return self._tokens(out, n)
 
     # ---- (9) resegmentation with mixture models
     def gmm_train(self, d_frames, n_frames, set_off, range_begin, range_end, n_comp, n_iter, var_floor, d_gmm,
@@ -839,18 +857,12 @@ class Context(object):
         speaker that cannot be modelled (fewer than 40 n_comp frames, constant or non-finite frames),
         loglik[s, i] the total log-likelihood of speaker s's frames under the model that entered
         iteration i.  The time of all its kernels is last_ms('gmm_train')."""
-        c = np.ascontiguousarray
-        off, b, e = c(set_off, dtype=np.int64), c(range_begin, dtype=np.int64), c(range_end, dtype=np.int64)
-        if off.ndim != 1 or len(off) < 1 or b.ndim != 1 or e.ndim != 1:
-            raise SpkdError(SPKD_EINVAL, 'set_off: one entry per speaker and the total')
-        if not (len(b) == len(e) == int(off[-1])):
-            raise SpkdError(SPKD_EINVAL, 'one begin and end per range of the sets')
-        n = len(off) - 1
-        ok = np.zeros(n, dtype=np.int32)
-        ll = np.zeros((n, max(int(n_iter), 0)), dtype=np.float64)
-        self.check(self.lib.spkd_gmm_train(self.h, C.c_void_p(d_frames), int(n_frames), n, _ptr(off), _ptr(b), _ptr(e),
-                                           int(n_comp), int(n_iter), 1 if from_model else 0, float(var_floor),
-                                           C.c_void_p(d_gmm), _ptr(ok), _ptr(ll) if ll.size else None))
+        sets = self._range_sets(set_off, range_begin, range_end)
+        ok = np.zeros(sets[0], dtype=np.int32)
+        ll = np.zeros((sets[0], max(int(n_iter), 0)), dtype=np.float64)
+        self.check(self.lib.spkd_gmm_train(self.h, C.c_void_p(d_frames), int(n_frames), *sets, int(n_comp), int(n_iter),
+                                           1 if from_model else 0, float(var_floor), C.c_void_p(d_gmm), _ptr(ok),
+                                           _ptr(ll) if ll.size else None))
         return ok, ll
 
     def gmm_loglik_seq(self, d_frames, n_frames, d_gmm, n_comp, model_ok, seq_begin, seq_end, seq_model, seq_n_models,
@@ -858,17 +870,9 @@ class Context(object):
         """gauss_loglik under mixtures (spkd_gmm_loglik_seq): d_gmm holds len(model_ok) models of n_comp
         components as gmm_train leaves them, model_ok its ok.  Returns frame_off.  The kernel's time
         is last_ms('gmm_seq_loglik')."""
-        c = np.ascontiguousarray
-        ok = c(model_ok, dtype=np.int32)
-        b, e = c(seq_begin, dtype=np.int64), c(seq_end, dtype=np.int64)
-        m, k = c(seq_model, dtype=np.int32), c(seq_n_models, dtype=np.int32)
-        if any(a.ndim != 1 for a in (ok, b, e, m, k)) or not (len(b) == len(e) == len(m) == len(k)):
-            raise SpkdError(SPKD_EINVAL, 'one begin, end, first model and model count per sequence')
+        seqs, frame_off = self._seq_args(model_ok, seq_begin, seq_end, seq_model, seq_n_models)
         self.check(self.lib.spkd_gmm_loglik_seq(self.h, C.c_void_p(d_frames), int(n_frames), C.c_void_p(d_gmm), int(n_comp),
-                                                len(ok), _ptr(ok), len(b), _ptr(b), _ptr(e), _ptr(m), _ptr(k), int(n_cols),
-                                                C.c_void_p(d_scores)))
-        frame_off = np.zeros(len(b) + 1, dtype=np.int64)
-        frame_off[1:] = np.cumsum(e - b)
+                                                *seqs, int(n_cols), C.c_void_p(d_scores)))
         return frame_off
 
     # ---- (10) linking by cross-likelihood ratio
@@ -878,16 +882,10 @@ class Context(object):
         speaker's frames (spkd_ubm_stats).  The speakers own their ranges as in gmm_train.  Returns ok
         int32 [n_speakers]: 0 for a speaker without a frame or with a sum that is not finite.  The
         kernels' time is last_ms('ubm_stats')."""
-        c = np.ascontiguousarray
-        off, b, e = c(set_off, dtype=np.int64), c(range_begin, dtype=np.int64), c(range_end, dtype=np.int64)
-        if off.ndim != 1 or len(off) < 1 or b.ndim != 1 or e.ndim != 1:
-            raise SpkdError(SPKD_EINVAL, 'set_off: one entry per speaker and the total')
-        if not (len(b) == len(e) == int(off[-1])):
-            raise SpkdError(SPKD_EINVAL, 'one begin and end per range of the sets')
-        n = len(off) - 1
-        ok = np.zeros(n, dtype=np.int32)
-        self.check(self.lib.spkd_ubm_stats(self.h, C.c_void_p(d_frames), int(n_frames), C.c_void_p(d_ubm), int(n_comp), n,
-                                           _ptr(off), _ptr(b), _ptr(e), C.c_void_p(d_bw), _ptr(ok)))
+        sets = self._range_sets(set_off, range_begin, range_end)
+        ok = np.zeros(sets[0], dtype=np.int32)
+        self.check(self.lib.spkd_ubm_stats(self.h, C.c_void_p(d_frames), int(n_frames), C.c_void_p(d_ubm), int(n_comp),
+                                           *sets, C.c_void_p(d_bw), _ptr(ok)))
         return ok
 
     def clr_link(self, d_bw, ok, d_ubm, n_comp, relevance, threshold, max_spk=0):

@@ -752,16 +752,24 @@ def _reseg_passes(reseg):
     return int(n)
 
 
+def _token_spans(tok_off, offset, turn_begin, turn_end):
+    """Token k of turn q opens at turn_begin[q] + offset[k] and ends where the next one opens, a turn's
+    last token at turn_end[q].  -> (the turn of every token, begin, end)."""
+    n = np.diff(tok_off)
+    turn = np.repeat(np.arange(len(n)), n)
+    begin = turn_begin[turn] + offset
+    end = np.empty_like(begin)
+    end[:-1] = begin[1:]
+    last = tok_off[1:][n > 0] - 1
+    end[last] = turn_end[turn[last]]
+    return turn, begin, end
+
+
 def _token_ranges(tok_off, tok_frame, tok_word, tb, te, first_speaker):
     """The decoded tokens as absolute frame ranges with their speakers, in turn order: token k of turn q
     is [tb[q] + f_k, tb[q] + f_{k+1}), a turn's last token ends at te[q]; its speaker is
     first_speaker[q] + word.  -> (begin, end, speaker)."""
-    turn = np.repeat(np.arange(len(tok_off) - 1), np.diff(tok_off))
-    b = tb[turn] + tok_frame
-    e = np.empty_like(b)
-    e[:-1] = b[1:]
-    last = tok_off[1:][np.diff(tok_off) > 0] - 1
-    e[last] = te[turn[last]]
+    turn, b, e = _token_spans(tok_off, tok_frame, tb, te)
     return b, e, first_speaker[turn] + tok_word
 
 
@@ -771,13 +779,7 @@ def _reseg_rows(tok_off, tok_frame, tok_word, turn_start_s, turn_end_s, turn_lab
     first row starts at the turn's own start (f_0 = 0) and its last row ends at the turn's own end
     as the VAD states it (the convention of spkd_gw_lines' tail line).  turn_labels[q][w]: the label
     of word w in turn q.  Returns (rows [n_tokens, 3], the turn of every row)."""
-    n_tok = int(tok_off[-1])
-    turn = np.repeat(np.arange(len(tok_off) - 1), np.diff(tok_off))
-    t0 = turn_start_s[turn] + tok_frame / rate
-    t1 = np.empty(n_tok)
-    t1[:-1] = t0[1:]
-    last = tok_off[1:][np.diff(tok_off) > 0] - 1
-    t1[last] = turn_end_s[turn[last]]
+    turn, t0, t1 = _token_spans(tok_off, tok_frame / rate, turn_start_s, turn_end_s)
     times = np.column_stack([t0, t1])
     if text_contract:
         times = hipabi.py2_roundtrip(times.ravel()).reshape(-1, 2)
@@ -870,16 +872,26 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     n_spk, n_cols = len(spk_file), int(n_spk_file.max())
     spk_base = np.zeros(n_files + 1, dtype=np.int64)
     spk_base[1:] = np.cumsum(n_spk_file)
-    tokens = None
-    for p in range(passes):
-        if model[0] == 'gmm':
-            _, n_comp, n_iter, var_floor = model
-            if p == 0:
+    spk_first, spk_count = spk_base[owner], n_spk_file[owner]
+    d_spk = d_models = d_scores = None      # device buffers: pass 1 allocates each where it first needs it
+
+    def clock(key, which):
+        if timings is not None:
+            timings.setdefault(key, []).append(ctx.last_ms(which))
+
+    # the speaker model: train(tokens) -> ok, from the segments in pass 1 (tokens is None) and from the
+    # tokens of the pass before afterwards; score(ok) -> frame_off, the turns' scores in d_scores
+    if model[0] == 'gmm':
+        _, n_comp, n_iter, var_floor = model
+
+        def train(tokens):
+            nonlocal d_models
+            if tokens is None:
                 d_models = ctx.dev_scratch('reseg_gmm', n_spk * n_comp * hipabi.GMM_COMP * 8)
                 off, rb, re_ = set_off, seg_b[member], seg_e[member]
             else:
                 # (spkd_gmm_train takes no empty set: a speaker without a token gets one empty range)
-                rb, re_, spk = _token_ranges(tokens[0], tokens[1], tokens[2], tb, te, spk_base[owner])
+                rb, re_, spk = _token_ranges(*tokens, tb, te, spk_first)
                 idle = np.nonzero(np.bincount(spk, minlength=n_spk) == 0)[0]
                 rb, re_ = np.concatenate([rb, np.zeros(len(idle), np.int64)]), np.concatenate([re_, np.zeros(len(idle), np.int64)])
                 spk = np.concatenate([spk, idle])
@@ -887,50 +899,62 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
                 off = np.concatenate([[0], np.cumsum(np.bincount(spk, minlength=n_spk))]).astype(np.int64)
                 rb, re_ = rb[order], re_[order]
             ok, loglik = ctx.gmm_train(d_frames, total_frames, off, rb, re_, n_comp, n_iter, var_floor, d_models)
-            if timings is not None:
-                timings.setdefault('reseg_gmm_train', []).append(ctx.last_ms('gmm_train'))
+            clock('reseg_gmm_train', 'gmm_train')
             if detail is not None:
                 detail['loglik'] = loglik
-        else:
-            if p == 0:
+            return ok
+
+        def score(ok):
+            frame_off = ctx.gmm_loglik_seq(d_frames, total_frames, d_models, n_comp, ok, tb, te, spk_first, spk_count,
+                                           n_cols, d_scores)
+            clock('reseg_loglik', 'gmm_seq_loglik')
+            return frame_off
+    else:
+        def train(tokens):
+            nonlocal d_spk, d_models
+            if tokens is None:
                 d_spk = ctx.dev_scratch('reseg_speaker_stats', n_spk * hipabi.REC * 8)
                 ctx.sum_stats(d_stats, int(seg_off[-1]), member, set_off, d_spk)
                 d_models = ctx.dev_scratch('reseg_models', n_spk * hipabi.GAUSS_MODEL * 8)
             else:
-                rb, re_, spk = _token_ranges(tokens[0], tokens[1], tokens[2], tb, te, spk_base[owner])
+                rb, re_, spk = _token_ranges(*tokens, tb, te, spk_first)
                 order = np.argsort(spk, kind='stable')                     # (spkd_set_stats takes ascending sets)
                 ctx.set_stats(d_frames, total_frames, rb[order], re_[order], sets=spk[order].astype(np.int32), n_sets=n_spk,
                               d_stats=d_spk)
             ok = ctx.gauss_models(d_spk, n_spk, d_models)
-            if timings is not None:
-                timings.setdefault('reseg_models', []).append(ctx.last_ms('gauss_models'))
+            clock('reseg_models', 'gauss_models')
+            return ok
+
+        def score(ok):
+            frame_off = ctx.gauss_loglik(d_frames, total_frames, d_models, ok, tb, te, spk_first, spk_count, n_cols, d_scores)
+            clock('reseg_loglik', 'gauss_loglik')
+            return frame_off
+
+    def decode(frame_off):
+        if min_frames:
+            decoded = ctx.mindur_viterbi_batch(d_scores, frame_off, n_cols, penalty, min_frames)
+        else:
+            zero = np.zeros(n_cols)
+            decoded = ctx.vad_viterbi_batch(d_scores, frame_off, n_cols, np.arange(n_cols), zero, zero, zero - penalty)
+        clock('reseg_viterbi', 'mindur_viterbi' if min_frames else 'vad_viterbi')
+        clock('reseg_backtrack', 'mindur_backtrack' if min_frames else 'vad_backtrack')
+        return decoded[:3]                                                 # (tok_off, tok_frame, tok_word)
+
+    tokens = None
+    for p in range(passes):
+        ok = train(tokens)
         if detail is not None:
             detail['dropped'] = [(int(spk_file[s]), int(spk_label[s])) for s in np.nonzero(ok == 0)[0]]
         if p == 0:
             d_scores = ctx.dev_scratch('reseg_scores', max(int((te - tb).sum()), 1) * n_cols * 4)
-        if model[0] == 'gmm':
-            frame_off = ctx.gmm_loglik_seq(d_frames, total_frames, d_models, n_comp, ok, tb, te, spk_base[owner],
-                                           n_spk_file[owner], n_cols, d_scores)
-        else:
-            frame_off = ctx.gauss_loglik(d_frames, total_frames, d_models, ok, tb, te, spk_base[owner], n_spk_file[owner],
-                                         n_cols, d_scores)
-        if timings is not None:
-            timings.setdefault('reseg_loglik', []).append(ctx.last_ms('gmm_seq_loglik' if model[0] == 'gmm' else 'gauss_loglik'))
-        if min_frames:
-            tok_off, tok_frame, tok_word, _ = ctx.mindur_viterbi_batch(d_scores, frame_off, n_cols, penalty, min_frames)
-        else:
-            zero = np.zeros(n_cols)
-            tok_off, tok_frame, tok_word, _ = ctx.vad_viterbi_batch(d_scores, frame_off, n_cols, np.arange(n_cols), zero, zero,
-                                                                    zero - penalty)
-        if timings is not None:
-            timings.setdefault('reseg_viterbi', []).append(ctx.last_ms('mindur_viterbi' if min_frames else 'vad_viterbi'))
-            timings.setdefault('reseg_backtrack', []).append(ctx.last_ms('mindur_backtrack' if min_frames else 'vad_backtrack'))
+        decoded = decode(score(ok))
         if detail is not None:
             detail['passes_run'] = p + 1
-        same = tokens is not None and all(np.array_equal(a, b) for a, b in zip(tokens, (tok_off, tok_frame, tok_word)))
-        tokens = (tok_off, tok_frame, tok_word)
-        if same or len(tok_frame) == 0:
+        same = tokens is not None and all(np.array_equal(a, b) for a, b in zip(tokens, decoded))
+        tokens = decoded
+        if same or len(tokens[1]) == 0:
             break
+    tok_off, tok_frame, tok_word = tokens
     # label of word w in a turn of file f: the file's w-th speaker (a word past the file's speakers
     # is never decoded: its column is -inf beside column 0, which wins every tie)
     file_labels = np.zeros((n_files, n_cols), dtype=np.int64)

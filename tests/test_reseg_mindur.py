@@ -297,6 +297,49 @@ def test_refusals_and_empty_calls_with_a_context(ctx):
     assert tok_off.tolist() == [0, 0, 0] and len(tok_frame) == 0 and score.tolist() == [-np.inf, -np.inf]
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize('mindur_first', [False, True])
+def test_neither_decoder_ends_the_results_of_the_other(ctx, mindur_first):
+    """include/spkd.h: the arrays a decoder hands back live until the same call is made again.  The
+    four arrays of one decoder, read through the pointers it returned, are what they were after the
+    other decoder has run on other scores (3 sequences of 0, 40 and 100 frames, 3 words, D = 16)."""
+    rng = np.random.default_rng(16)
+    off = np.array([0, 0, 40, 140], dtype=np.int64)
+    sc = [rng.normal(-60.0, 4.0, (140, 3)).astype(np.float32) for _ in range(2)]
+    zero, enter, ws = np.zeros(3), np.full(3, -2.5), np.arange(3, dtype=np.int32)
+
+    def raw(which, d):
+        out = [C.c_void_p() for _ in range(4)]
+        byref = [C.byref(o) for o in out]
+        if which:
+            st = ctx.lib.spkd_mindur_viterbi_batch(ctx.h, C.c_void_p(d), 3, _ptr(off), 3, 2.5, 16, *byref)
+        else:
+            st = ctx.lib.spkd_vad_viterbi_batch(ctx.h, C.c_void_p(d), 3, _ptr(off), 3, 3, _ptr(ws), _ptr(zero), _ptr(zero),
+                                                _ptr(enter), *byref)
+        assert st == 0
+        return out
+
+    def read(out):
+        n_tok = int(np.ctypeslib.as_array(C.cast(out[0], C.POINTER(C.c_int64)), shape=(4,))[3])
+        return [np.ctypeslib.as_array(C.cast(o, C.POINTER(t)), shape=(n,)).copy()
+                for o, t, n in zip(out, (C.c_int64, C.c_int64, C.c_int32, C.c_double), (4, n_tok, n_tok, 3))]
+
+    d = [ctx.dev_alloc(a.nbytes) for a in sc]
+    try:
+        for p, a in zip(d, sc):
+            ctx.h2d(p, a)
+        kept = raw(mindur_first, d[0])
+        first = read(kept)
+        assert first[0][0] == 0 and first[0][3] >= 2 and first[3][0] == -np.inf and np.isfinite(first[3][1:]).all()
+        other = read(raw(not mindur_first, d[1]))
+        again = read(kept)
+    finally:
+        for p in d:
+            ctx.dev_free(p)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(first, again))
+    assert other[3].tolist() != first[3].tolist()                          # (it was another decode)
+
+
 def _close_session(seed, seconds, n_speakers, eps=0.2):
     """A session of the generator whose speakers differ by a fifth of their usual distance in the mean
     only: single frames are then often closer to the wrong speaker."""
