@@ -100,7 +100,7 @@ enum {
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
     SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
-    SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK,
+    SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK, SPKD_T_FB_POSTERIOR,
     SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
     SPKD_N_TIMERS
 };
@@ -736,6 +736,58 @@ spkd_status spkd_mindur_viterbi_batch(spkd_ctx *ctx, const float *d_scores, int6
                                       int32_t min_frames,
                                       const int64_t **h_tok_off, const int64_t **h_tok_frame,
                                       const int32_t **h_tok_word, const double **h_score);
+
+/* spkd_fb_posterior_batch: how sure the speaker loop of (8) is of what it decodes.  A forward-backward
+ * pass over the scores the decoders search, with their loop (staying costs nothing, a switch `penalty`):
+ * the posterior probability of every speaker at every frame of every sequence, per decoded token the
+ * mean posterior of its word over its frames (the confidence of the row it becomes), and the
+ * log-evidence of each sequence.  The decoded path of spkd_vad_viterbi_batch is the mode of this
+ * distribution; the confidence says how much of the mass sits near it.  Under a minimum duration
+ * (spkd_mindur_viterbi_batch) the posterior is still that of the plain switch-penalty loop.  PARITY: no
+ * reference counterpart; tests/reseg_fb_numpy.py restates the recursion and checks it against an
+ * enumeration of all paths.
+ *
+ * In: d_scores, h_frame_off, n_cols (1 .. 16) and penalty (finite, >= 0) as spkd_mindur_viterbi_batch
+ * takes them.  scale: finite, > 0, scale * penalty <= 600 -- an acoustic scale on the whole path
+ * log-weight (the decoded path is the mode for every scale).  h_seq_n_cols[n_seq]: sequence q uses the
+ * columns 0 .. n(q) - 1, 1 <= n(q) <= n_cols; NULL: n_cols for every sequence.  The tokens as the
+ * decoders hand them back: h_tok_off[n_seq + 1], h_tok_frame (first frames, relative to the sequence),
+ * h_tok_word; all three NULL: no confidences.  d_post: NULL or [sum T][n_cols] floats.  h_conf[n_tok]
+ * (with tokens) and h_logz[n_seq]: doubles, the caller's.
+ *
+ * The values, all in fp64; n = n(q), k < n.  This fixes values, not the order of the operations:
+ *   o_t(k)   the cleaned score, as spkd_vad_viterbi: NaN counts as -inf; a frame whose n words are all
+ *            -inf counts as 0 for every word.  m_t = max_k o_t(k), b_t(k) = exp(scale (o_t(k) - m_t)).
+ *            The columns >= n take no part; their posterior is 0.
+ *   q, r     q = exp(-scale penalty), r = 1 - q.
+ *   forward  u_0(k) = b_0(k), u_t(k) = b_t(k) (r a_{t-1}(k) + q), s_t = sum_k u_t(k),
+ *            a_t(k) = u_t(k) / s_t, logz = -scale penalty + sum_t (scale m_t + ln s_t).  At scale 1 logz
+ *            is on the scale of the decoders' path scores and never below the plain decoder's.
+ *   backward beta_{T-1}(k) = 1, h(k) = b_{t+1}(k) beta_{t+1}(k), H = sum_k h(k), w(k) = r h(k) + q H,
+ *            beta_t(k) = w(k) / sum_k w(k).
+ *   gamma    gamma_t(k) = a_t(k) beta_t(k) / sum_j a_t(j) beta_t(j).
+ * Every divisor is positive: s_t >= q, beta >= q / 16, the last sum >= q / 256 -- hence the cap on
+ * scale * penalty.  A b that underflows to 0 is a posterior of 0.
+ * Out: d_post receives gamma rounded once to float32, 0 in the columns >= n(q).  h_conf[i], for the token
+ * (f_i, word) of sequence q, is the mean of gamma_t(word) over [f_i, f_{i+1}); a sequence's last token
+ * runs to T.  T == 0: logz = -inf.  A +inf score makes that sequence's outputs NaN and nothing else.
+ * One launch: a group of lanes per sequence runs forward, keeping only the forward vector that enters
+ * each tile of SPKD_FB_TILE frames (fp64: device scratch of 8 G bytes a tile, G the power of two >=
+ * n_cols), then backward tile by tile, rebuilding the tile's forward vectors from the stored one.
+ * A bad count or a null required pointer; an h_frame_off that does not start at 0 or decreases; an n(q)
+ * outside 1 .. n_cols; a bad penalty or scale, scale * penalty > 600; a token table given in part; an
+ * h_tok_off that does not start at 0 or decreases; a sequence with frames whose tokens do not start at
+ * frame 0, do not ascend strictly or reach T; tokens on a sequence without frames; a word outside
+ * 0 .. n_cols - 1: SPKD_EINVAL before any device work.  n_seq = 0: SPKD_OK; no frames anywhere: every
+ * logz -inf and SPKD_OK; both without a launch.  The index and token arrays go up in one copy through
+ * pinned memory the context owns.  Timer: SPKD_T_FB_POSTERIOR. */
+#define SPKD_FB_TILE 32
+spkd_status spkd_fb_posterior_batch(spkd_ctx *ctx, const float *d_scores, int64_t n_seq,
+                                    const int64_t *h_frame_off, int32_t n_cols, double penalty,
+                                    double scale, const int32_t *h_seq_n_cols,
+                                    const int64_t *h_tok_off, const int64_t *h_tok_frame,
+                                    const int32_t *h_tok_word, float *d_post, double *h_conf,
+                                    double *h_logz);
 
 /* ---------------------------------------------------------------------------
  * (9) Resegmentation with mixture models: a diagonal-covariance Gaussian mixture per speaker,

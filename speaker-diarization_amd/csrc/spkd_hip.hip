@@ -24,6 +24,7 @@
 #include "spkd_vad.hpp"
 #include "spkd_vad_batch.hpp"
 #include "spkd_mindur.hpp"
+#include "spkd_fb.hpp"
 #include "spkd_gauss.hpp"
 #include "spkd_gmm_train.hpp"
 #include "spkd_ubm_stats.hpp"
@@ -37,12 +38,13 @@ constexpr int N_SLOTS = 64;
 // (TokenHandBack: PIN_VAD_FILES / PIN_VAD_TOKENS of spkd_vad_viterbi_batch, PIN_MD_SEQS / PIN_MD_TOKENS of
 // spkd_mindur_viterbi_batch, so that neither call ends the other's); of the index arrays on their way up: spkd_sum_stats'
 // (PIN_SUM_IDX), the SeqTable of spkd_gauss_loglik (PIN_GAUSS_IDX) and of spkd_gmm_loglik_seq (PIN_GT_IDX), the
-// RangeTable of spkd_gmm_train (PIN_GT_TAB) and of spkd_ubm_stats (PIN_UBM_TAB), spkd_clr_link's ok flags (PIN_CLR_IN);
+// RangeTable of spkd_gmm_train (PIN_GT_TAB) and of spkd_ubm_stats (PIN_UBM_TAB), spkd_clr_link's ok flags (PIN_CLR_IN),
+// the FbTable of spkd_fb_posterior_batch (PIN_FB_TAB);
 // and of what comes down: spkd_gmm_train's ok flags and log-likelihoods (PIN_GT_OUT), spkd_ubm_stats' ok flags
 // (PIN_UBM_OUT), spkd_clr_link's merge log and statistics (PIN_CLR_OUT)
 enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
        PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, PIN_MD_SEQS, PIN_MD_TOKENS,
-       N_PIN };
+       PIN_FB_TAB, N_PIN };
 }
 
 struct spkd_ctx {
@@ -270,7 +272,7 @@ enum {
     S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX,
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
     S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT,
-    S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_COUNT
+    S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_FB_TAB, S_FB_FWD, S_FB_OUT, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -2360,6 +2362,120 @@ spkd_status spkd_mindur_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_
         [&](const VadFiles& d, int64_t* tok_frame, int32_t* tok_word) {
             mindur_backtrack_launch<true>(c, t, n_seq, min_frames, w, d, tok_frame, tok_word);
         }));
+    return call.finish();
+}
+
+// ------------------------------------------------------------------ (8) the speaker loop's posteriors
+static_assert(FB_TILE == SPKD_FB_TILE, "the header states the kernel's tile");
+static_assert(FB_MAX == GM_MAX_S, "one limit for states and words");
+
+namespace {
+// The index and token table of spkd_fb_posterior_batch, as the kernel takes it: per sequence its first
+// frame, its first tile of stored forward vectors, its first token and its word count; per token its
+// first frame and word.  parts() is listed once and placed twice, as SeqTable's.
+struct FbTable {
+    struct Tab { long long *begin, *tile_off, *tok_off, *tok_frame; int *seq_n, *tok_word; } h{}, d{};
+    size_t ns = 0, ntok = 0, image = 0;
+    bool tokens = false;
+
+    size_t parts(Layout L, Tab& t) const {
+        return L.part(t.begin, ns + 1).part(t.tile_off, ns + 1).part(t.tok_off, ns + 1).part(t.tok_frame, ntok)
+            .part(t.seq_n, ns).part(t.tok_word, ntok).bytes();
+    }
+};
+
+extern "C++" {
+template <int G>
+void fb_launch(spkd_ctx* c, const float* d_scores, const FbTable& t, int64_t n_seq, int S, double penalty, double scale,
+               double* fwd, float* d_post, double* d_conf, double* d_logz) {
+    const int64_t per_wave = WAVE / G;
+    hipLaunchKernelGGL(k_fb_posterior<G>, dim3((unsigned)((n_seq + per_wave - 1) / per_wave)), dim3(WAVE), 0, c->stream,
+                       d_scores, (const long long*)t.d.begin, (const long long*)t.d.tile_off, (const int*)t.d.seq_n,
+                       (long long)n_seq, S, penalty, scale, t.tokens ? (const long long*)t.d.tok_off : nullptr,
+                       (const long long*)t.d.tok_frame, (const int*)t.d.tok_word, fwd, d_post, d_conf, d_logz);
+}
+}  // extern "C++"
+}  // namespace
+
+spkd_status spkd_fb_posterior_batch(spkd_ctx* c, const float* d_scores, int64_t n_seq, const int64_t* h_frame_off,
+                                    int32_t n_cols, double penalty, double scale, const int32_t* h_seq_n_cols,
+                                    const int64_t* h_tok_off, const int64_t* h_tok_frame, const int32_t* h_tok_word,
+                                    float* d_post, double* h_conf, double* h_logz) {
+    if (n_cols < 1 || n_cols > GM_MAX_S) return fail(c, SPKD_EINVAL, "fb_posterior_batch: 1 <= n_cols <= 16");
+    if (!std::isfinite(penalty) || penalty < 0.0) return fail(c, SPKD_EINVAL, "fb_posterior_batch: a finite penalty >= 0");
+    if (!std::isfinite(scale) || scale <= 0.0 || !(scale * penalty <= 600.0))
+        return fail(c, SPKD_EINVAL, "fb_posterior_batch: a finite scale > 0 with scale * penalty <= 600");
+    TRY(vad_check_offsets(c, n_seq, h_frame_off));
+    const bool tokens = h_tok_off || h_tok_frame || h_tok_word;
+    if (tokens && !(h_tok_off && h_tok_frame && h_tok_word))
+        return fail(c, SPKD_EINVAL, "fb_posterior_batch: the token table takes all three arrays");
+    if (n_seq > 0 && !h_logz) return fail(c, SPKD_EINVAL, "fb_posterior_batch: null output");
+    for (int64_t q = 0; q < n_seq && h_seq_n_cols; ++q)
+        if (h_seq_n_cols[q] < 1 || h_seq_n_cols[q] > n_cols)
+            return fail(c, SPKD_EINVAL, "fb_posterior_batch: 1 <= columns of a sequence <= n_cols");
+    int64_t n_tok = 0;
+    if (tokens) {
+        if (h_tok_off[0] != 0) return fail(c, SPKD_EINVAL, "fb_posterior_batch: tok_off must start at 0");
+        for (int64_t q = 0; q < n_seq; ++q) {
+            const int64_t lo = h_tok_off[q], hi = h_tok_off[q + 1], T = h_frame_off[q + 1] - h_frame_off[q];
+            if (hi < lo) return fail(c, SPKD_EINVAL, "fb_posterior_batch: tok_off must be non-decreasing");
+            if (T == 0 && hi > lo) return fail(c, SPKD_EINVAL, "fb_posterior_batch: tokens on a sequence without frames");
+            if (T > 0 && (hi == lo || h_tok_frame[lo] != 0))
+                return fail(c, SPKD_EINVAL, "fb_posterior_batch: a sequence's tokens start at frame 0");
+            for (int64_t i = lo; i < hi; ++i) {
+                if (i > lo && h_tok_frame[i] <= h_tok_frame[i - 1])
+                    return fail(c, SPKD_EINVAL, "fb_posterior_batch: a sequence's tokens ascend strictly");
+                if (h_tok_frame[i] >= T) return fail(c, SPKD_EINVAL, "fb_posterior_batch: a token at or behind the last frame");
+                if (h_tok_word[i] < 0 || h_tok_word[i] >= n_cols)
+                    return fail(c, SPKD_EINVAL, "fb_posterior_batch: word out of range");
+            }
+        }
+        n_tok = h_tok_off[n_seq];
+        if (n_tok > 0 && !h_conf) return fail(c, SPKD_EINVAL, "fb_posterior_batch: null output");
+    }
+    if (!c) return SPKD_EINVAL;
+    if (n_seq == 0) return SPKD_OK;
+    if (h_frame_off[n_seq] == 0) {
+        for (int64_t q = 0; q < n_seq; ++q) h_logz[q] = -INFINITY;
+        return SPKD_OK;
+    }
+    if (!d_scores) return fail(c, SPKD_EINVAL, "fb_posterior_batch: null device buffer");
+    if (n_seq > 0x7fffffff) return fail(c, SPKD_EINVAL, "fb_posterior_batch: too many sequences in one call");
+    FbTable t;
+    t.ns = (size_t)n_seq, t.ntok = (size_t)n_tok, t.tokens = tokens;
+    TRY(carve(c, pinned, PIN_FB_TAB, [&](Layout L) { return t.image = t.parts(L, t.h); }));
+    std::memcpy(t.h.begin, h_frame_off, (t.ns + 1) * sizeof(int64_t));
+    t.h.tile_off[0] = 0;
+    for (size_t q = 0; q < t.ns; ++q) {
+        t.h.tile_off[q + 1] = t.h.tile_off[q] + (h_frame_off[q + 1] - h_frame_off[q] + FB_TILE - 1) / FB_TILE;
+        t.h.seq_n[q] = h_seq_n_cols ? h_seq_n_cols[q] : n_cols;
+        t.h.tok_off[q + 1] = tokens ? h_tok_off[q + 1] : 0;
+    }
+    t.h.tok_off[0] = 0;
+    if (n_tok) {
+        std::memcpy(t.h.tok_frame, h_tok_frame, t.ntok * sizeof(int64_t));
+        std::memcpy(t.h.tok_word, h_tok_word, t.ntok * sizeof(int32_t));
+    }
+    int G = 1;
+    while (G < n_cols) G *= 2;
+    Call call(c);
+    TRY(call.opened);
+    TRY(carve(c, scratch, S_FB_TAB, [&](Layout L) { return t.parts(L, t.d); }));
+    HIPCHK(c, hipMemcpyAsync(t.d.begin, t.h.begin, t.image, hipMemcpyHostToDevice, c->stream));
+    void* p = nullptr;
+    TRY(scratch(c, S_FB_FWD, (size_t)t.h.tile_off[t.ns] * (size_t)G * sizeof(double), &p));
+    double* fwd = (double*)p;
+    double *d_conf = nullptr, *d_logz = nullptr;
+    TRY(carve(c, scratch, S_FB_OUT, [&](Layout L) { return L.part(d_logz, t.ns).part(d_conf, t.ntok).bytes(); }));
+    {
+        Timer tm(c, SPKD_T_FB_POSTERIOR);
+        with_group(n_cols, [&](auto g) {
+            fb_launch<decltype(g)::value>(c, d_scores, t, n_seq, n_cols, penalty, scale, fwd, d_post, d_conf, d_logz);
+        });
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_logz, d_logz, t.ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n_tok) HIPCHK(c, hipMemcpyAsync(h_conf, d_conf, t.ntok * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     return call.finish();
 }
 

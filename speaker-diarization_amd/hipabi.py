@@ -18,10 +18,11 @@ TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pai
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
                                         'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
-                                        'mindur_viterbi', 'mindur_backtrack',
+                                        'mindur_viterbi', 'mindur_backtrack', 'fb_posterior',
                                         'mfcc_static', 'mfcc_post'])}
 VAD_TILE = 32       # SPKD_VAD_TILE: frames per score / back-pointer tile of k_vad_viterbi
 MINDUR_TILE = 32    # SPKD_MINDUR_TILE: frames per score / record tile of k_mindur_viterbi
+FB_TILE = 32        # SPKD_FB_TILE: frames per score tile and per stored forward vector of k_fb_posterior
 GAUSS_TILE = 64     # SPKD_GAUSS_TILE: frames per workgroup of k_gauss_loglik
 GAUSS_MODEL = 820   # SPKD_GAUSS_MODEL: doubles per model (mu[39], W = L^-1 packed lower [780], c)
 GMM_COMP = 80       # SPKD_GMM_COMP: doubles per mixture component (ln w, mean[39], 1 / var[39], log_norm)
@@ -41,7 +42,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
            'spkd_gauss_models', 'spkd_gauss_loglik', 'spkd_gmm_train', 'spkd_gmm_loglik_seq',
-           'spkd_ubm_stats', 'spkd_clr_link', 'spkd_mindur_viterbi_batch']
+           'spkd_ubm_stats', 'spkd_clr_link', 'spkd_mindur_viterbi_batch', 'spkd_fb_posterior_batch']
 
 
 class CdParams(C.Structure):
@@ -217,6 +218,7 @@ def load_library(path=None):
     lib.spkd_vad_shift_batch.argtypes = [vp, vp, i64, vp, i32, dbl, vp]
     lib.spkd_vad_viterbi_batch.argtypes = [vp, vp, i64, vp, i32, i32, vp, vp, vp, vp, P(vp), P(vp), P(vp), P(vp)]
     lib.spkd_mindur_viterbi_batch.argtypes = [vp, vp, i64, vp, i32, dbl, i32, P(vp), P(vp), P(vp), P(vp)]
+    lib.spkd_fb_posterior_batch.argtypes = [vp, vp, i64, vp, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp]
     lib.spkd_gauss_models.argtypes = [vp, vp, i64, vp, vp]
     lib.spkd_gauss_loglik.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp]
     lib.spkd_gmm_train.argtypes = [vp, vp, i64, i64, vp, vp, vp, i32, i32, i32, dbl, vp, vp, vp]
@@ -845,6 +847,37 @@ class Context(object):
         self.check(self.lib.spkd_mindur_viterbi_batch(self.h, C.c_void_p(d_scores), n, _ptr(off), int(n_cols), float(penalty),
                                                       int(min_frames), *[C.byref(o) for o in out]))
         return self._tokens(out, n)
+
+    def fb_posterior_batch(self, d_scores, frame_off, n_cols, penalty, tokens=None, seq_n_cols=None, scale=1.0, d_post=0):
+        """The posteriors of the speaker loop (stay 0, switch -penalty) on every sequence of concatenated
+        device scores [sum T, n_cols] in one launch (spkd_fb_posterior_batch).  tokens: (tok_off, token
+        first frames, token words) as a decoder returns them, or None; seq_n_cols: the columns each
+        sequence uses (None: n_cols); scale: the acoustic scale, scale * penalty <= 600; d_post: 0 or a
+        device array [sum T, n_cols] float32 that receives every frame's posteriors.  Returns (conf,
+        logz): per token the mean posterior of its word over its frames (None without tokens) and per
+        sequence the log-evidence.  The kernel's time is last_ms('fb_posterior')."""
+        off = self._frame_off(frame_off)
+        n = len(off) - 1
+        c = np.ascontiguousarray
+        ncol = None
+        if seq_n_cols is not None:
+            ncol = c(seq_n_cols, dtype=np.int32)
+            if ncol.ndim != 1 or len(ncol) != n:
+                raise SpkdError(SPKD_EINVAL, 'seq_n_cols: one entry per sequence')
+        tok = [None, None, None]
+        conf = None
+        if tokens is not None:
+            tok = [c(tokens[0], dtype=np.int64), c(tokens[1], dtype=np.int64), c(tokens[2], dtype=np.int32)]
+            if any(a.ndim != 1 for a in tok) or len(tok[0]) != n + 1 or len(tok[1]) != len(tok[2]) or \
+                    int(tok[0].min()) < 0 or int(tok[0].max()) > len(tok[1]):
+                raise SpkdError(SPKD_EINVAL, 'tokens: tok_off with one entry per sequence and the total, a frame and a word per token')
+            conf = np.zeros(len(tok[1]), dtype=np.float64)
+        logz = np.zeros(n, dtype=np.float64)
+        p = lambda a: None if a is None else _ptr(a)
+        self.check(self.lib.spkd_fb_posterior_batch(self.h, C.c_void_p(d_scores), n, _ptr(off), int(n_cols), float(penalty),
+                                                    float(scale), p(ncol), p(tok[0]), p(tok[1]), p(tok[2]),
+                                                    C.c_void_p(d_post) if d_post else None, p(conf), _ptr(logz)))
+        return conf, logz
 
     # ---- (9) resegmentation with mixture models
     def gmm_train(self, d_frames, n_frames, set_off, range_begin, range_end, n_comp, n_iter, var_floor, d_gmm,

@@ -50,6 +50,13 @@ RESEG_GMM = dict(penalty=50.0, model='gmm', components=4, iterations=5, var_floo
 # but the synthetic generator.  Any reseg dictionary may also carry passes=N (default 1): the speakers are
 # retrained on the decoded rows and the turns decoded again, up to N decodes.
 RESEG_MD = dict(penalty=50.0, min_dur_s=1.0)
+# the same stage with a confidence for every row (spkd_fb_posterior_batch): the mean posterior of the row's
+# speaker over its frames, under the switch-penalty loop at the acoustic scale conf_scale (default 1.0).  Any
+# reseg dictionary may carry confidence=True.  On the generator's independent frames scale 1 is roughly
+# calibrated; speech, whose frames are correlated in time, will want a scale below 1 -- none exists here, so the
+# default is unmeasured.
+RESEG_CONF = dict(penalty=50.0, confidence=True)
+FB_MAX_SCALED_PENALTY = 600.0    # conf_scale * penalty: the limit of spkd_fb_posterior_batch
 
 
 class BatchFile(object):
@@ -752,6 +759,29 @@ def _reseg_passes(reseg):
     return int(n)
 
 
+def _reseg_confidence(reseg, detail):
+    """(confidence asked for, conf_scale) of a `reseg` dictionary; `detail` is where the confidences go."""
+    on = reseg.get('confidence', False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError('reseg confidence: True or False')
+    try:
+        scale = float(reseg.get('conf_scale', 1.0))
+    except (TypeError, ValueError):
+        scale = float('nan')
+    if not np.isfinite(scale) or scale <= 0.0:
+        raise ValueError('reseg conf_scale: a finite number > 0 (an acoustic scale on the path log-weights)')
+    if on and not scale * float(reseg['penalty']) <= FB_MAX_SCALED_PENALTY:
+        raise ValueError('reseg conf_scale * penalty: at most %g' % FB_MAX_SCALED_PENALTY)
+    if on and detail is None:
+        raise ValueError('reseg confidence: the confidences come back in detail, which takes a dictionary')
+    return bool(on), scale
+
+
+def _no_confidence(detail, n_files):
+    detail['confidence'] = [np.zeros(0) for _ in range(n_files)]
+    detail['log_evidence'] = [np.zeros(0) for _ in range(n_files)]
+
+
 def _token_spans(tok_off, offset, turn_begin, turn_end):
     """Token k of turn q opens at turn_begin[q] + offset[k] and ends where the next one opens, a turn's
     last token at turn_end[q].  -> (the turn of every token, begin, end)."""
@@ -835,12 +865,24 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     when a pass decodes exactly the tokens of the pass before it; detail['passes_run'] is the number
     of decodes done (0 when there was nothing to decode).  timings: the reseg lists get one entry per
     pass.  A min_dur_s that is negative or not finite, passes that is not an integer >= 1: ValueError
-    before any device work."""
+    before any device work.
+    reseg['confidence'] = True (RESEG_CONF; either model, either decoder, any passes): after the last
+    decode one spkd_fb_posterior_batch runs on the last pass's scores with the final tokens, every
+    turn's speaker count and the penalty, at the acoustic scale reseg['conf_scale'] (default 1.0).  The
+    rows are those of the call without it, to the byte.  detail['confidence']: per file a float64
+    array aligned with the file's rows, the mean posterior of the row's speaker over the row's frames;
+    detail['log_evidence']: per file the log-evidence of each of its decoded turns, in turn order (-inf
+    for a turn without frames).  Both are lists of empty arrays when there is nothing to decode.  The
+    posterior is that of the plain switch-penalty loop also under min_dur_s: the minimum duration
+    shapes the rows, not the distribution they are weighed in.  timings: reseg_posterior.  A
+    confidence that is not a bool, a conf_scale that is not a finite number > 0, conf_scale * penalty
+    above 600, confidence without a detail dictionary: ValueError before any device work."""
     rate = float(rate)
     penalty = _reseg_penalty(reseg)
     model = _reseg_model(reseg)
     min_frames = _reseg_min_frames(reseg, rate)
     passes = _reseg_passes(reseg)
+    want_conf, conf_scale = _reseg_confidence(reseg, detail)
     if model[0] == 'gmm':
         if segments is None:
             raise ValueError('reseg model gmm trains on the frames: it takes segments, the arrays cluster_batch took')
@@ -861,6 +903,8 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     if detail is not None:
         detail['dropped'] = []
         detail['passes_run'] = 0
+        if want_conf:
+            _no_confidence(detail, n_files)
     table = _turn_table(files, rate)
     if table is None or len(spk_file) == 0:
         return out
@@ -947,7 +991,8 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
             detail['dropped'] = [(int(spk_file[s]), int(spk_label[s])) for s in np.nonzero(ok == 0)[0]]
         if p == 0:
             d_scores = ctx.dev_scratch('reseg_scores', max(int((te - tb).sum()), 1) * n_cols * 4)
-        decoded = decode(score(ok))
+        frame_off = score(ok)
+        decoded = decode(frame_off)
         if detail is not None:
             detail['passes_run'] = p + 1
         same = tokens is not None and all(np.array_equal(a, b) for a, b in zip(tokens, decoded))
@@ -961,6 +1006,14 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     file_labels[spk_file, np.arange(n_spk) - spk_base[spk_file]] = spk_label
     rows, turn = _reseg_rows(tok_off, tok_frame, tok_word, ls, le, file_labels[owner], rate, text_contract)
     bounds = np.searchsorted(owner[turn], np.arange(n_files + 1))
+    if want_conf:
+        # (a row is a token: the confidences come back in row order)
+        conf, logz = ctx.fb_posterior_batch(d_scores, frame_off, n_cols, penalty, tokens=(tok_off, tok_frame, tok_word),
+                                            seq_n_cols=spk_count, scale=conf_scale)
+        clock('reseg_posterior', 'fb_posterior')
+        turns = np.searchsorted(owner, np.arange(n_files + 1))
+        detail['confidence'] = [conf[bounds[i]:bounds[i + 1]] for i in range(n_files)]
+        detail['log_evidence'] = [logz[turns[i]:turns[i + 1]] for i in range(n_files)]
     return [rows[bounds[i]:bounds[i + 1]] for i in range(n_files)]
 
 
@@ -1054,13 +1107,16 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     (resegment_batch, model 'gmm'; detail['loglik'] as there).  A dictionary like RESEG_MD decodes with
     a minimum speaker duration (reseg['min_dur_s']), and reseg['passes'] retrains the speakers on the
     decoded rows and decodes again; both keys go to resegment_batch as they are
-    (detail['passes_run'] as there)."""
+    (detail['passes_run'] as there).  A dictionary like RESEG_CONF adds a confidence to every row
+    (reseg['confidence'], reseg['conf_scale']; detail['confidence'] and detail['log_evidence'] as there):
+    it takes a detail dictionary.  With link the confidences stay those of the file's own speakers."""
     method = _method(cl)
     if reseg is not None:
         _reseg_penalty(reseg)
         _reseg_model(reseg)
         _reseg_min_frames(reseg, rate)
         _reseg_passes(reseg)
+        _reseg_confidence(reseg, detail)
         if handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi'):
             raise ValueError('reseg takes the host hand-off')
     if _cd_method(cd) in ('sw', 'm'):
@@ -1091,6 +1147,8 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
         if reseg is not None and detail is not None:
             detail['dropped'] = []
             detail['passes_run'] = 0
+            if reseg.get('confidence', False):
+                _no_confidence(detail, len(files))
         return [np.zeros((0, 3)) for _ in files]
     return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail, reseg,
                               text_contract)
