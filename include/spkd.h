@@ -101,6 +101,7 @@ enum {
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
     SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
     SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK, SPKD_T_FB_POSTERIOR,
+    SPKD_T_IDENT_SCORES, SPKD_T_IDENT_ASSIGN, SPKD_T_BW_ACCUMULATE,
     SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
     SPKD_N_TIMERS
 };
@@ -921,6 +922,73 @@ spkd_status spkd_clr_link(spkd_ctx *ctx, const double *d_bw, int64_t n, const in
                           const double *d_ubm, int32_t n_comp, double relevance, double threshold,
                           int32_t max_spk, int32_t *h_merge_a, int32_t *h_merge_b, double *h_merge_d,
                           int32_t *h_n_merges, double *h_stat_max, double *h_stat_min);
+
+/* ---------------------------------------------------------------------------
+ * (11) A gallery of enrolled speakers: the records of section 10, kept from one batch to the next,
+ * and the identification of a batch's speakers against them.  The global labels of spkd_clr_link are
+ * positions in the list of ONE call; an identity of a gallery means the same person in every call.
+ * The records of a gallery and of its probes are comparable only under the UBM they were collected
+ * under (spkd_ubm_stats takes the model as an argument: the owner of the gallery keeps it).
+ * PARITY: no reference counterpart (spk-clustering.py:289 is a TODO for more than one wav);
+ * tests/gallery_numpy.py restates both calls in numpy.
+ *
+ * spkd_clr_identify: n_probe records at d_probe_bw against n_gallery records at d_gallery_bw, both in
+ *   the layout of section 10 under the UBM at d_ubm.
+ *     score[s][g] = CLR(probe s, identity g)          (section 10; the bits are those spkd_clr_link's
+ *                                                      initial matrix holds for the same two records)
+ *   for every probe and identity whose ok flag is set, NaN elsewhere.  All arithmetic is fp64, no
+ *   atomics on values: the bits depend neither on the run nor on the tiling.  T and N of the gallery
+ *   are derived once per call.
+ *   The probes come in n_groups groups, group k the probes h_group_off[k] .. h_group_off[k + 1] (a
+ *   group may be empty): the probes of a group must receive distinct identities -- the speakers of one
+ *   file, the clusters of one batch.  exclusive = 1: a greedy chain per group.  Among the group's
+ *   undecided ok probes and the ok identities not yet taken IN THIS GROUP, the pair of the highest
+ *   score, the first in row-major order on a tie (spkd_clr_link's rule); while that score is above
+ *   `threshold` the pair is assigned, the probe and the identity are closed, and the chain goes on;
+ *   otherwise it stops and the probes left over are unknown.  exclusive = 0: every ok probe takes the
+ *   identity of its highest score (the lowest index on a tie) when that is above the threshold; no
+ *   identity is closed.
+ *   h_ident[s]: the identity, or -1 (unknown).  h_score[s]: the assigned pair's score; of an unknown
+ *   probe its highest score over all ok identities.  h_second[s]: the probe's highest score over the ok
+ *   identities other than the reported one -- of an unknown probe: other than the first that reaches
+ *   h_score -- or NaN when there is none.  Neither depends on the order of the chain beyond the
+ *   identity itself.  A probe that is not ok: ident -1, score and second NaN.  An identity that is not
+ *   ok is never chosen.  d_scores: NULL, or n_probe * n_gallery doubles that receive the matrix (row s
+ *   at d_scores + s * n_gallery).
+ *   A score between an ok probe and an ok identity that is not finite: SPKD_ENONFINITE, every ident -1,
+ *   score and second NaN.
+ *   Limits: n_probe <= SPKD_CLR_MAX_N and n_groups <= SPKD_CLR_MAX_N (a group is one workgroup whose
+ *   per-row state waits in LDS), n_gallery <= SPKD_GALLERY_MAX_N = 16384 (one bit a column there).  The
+ *   matrix is n_probe * n_gallery doubles of device scratch unless d_scores is given, at most 512 MB;
+ *   the derived records take n_gallery * C * 40 doubles more.
+ *   SPKD_EINVAL before any device work, outputs untouched: a null pointer other than d_scores (the
+ *   gallery's two may be null when n_gallery = 0), a negative count or one above its limit, group
+ *   offsets that do not start at 0, go back or do not end at n_probe, C outside
+ *   [1, SPKD_GMM_MAX_COMP], r not finite or <= 0, threshold NaN, exclusive other than 0 or 1, a device
+ *   pointer that is not 16-byte aligned.  n_probe = 0: SPKD_OK without a launch.  n_gallery = 0:
+ *   SPKD_OK without a launch, every probe unknown, score and second NaN.
+ *   Timers: SPKD_T_IDENT_SCORES (the derived records and the matrix), SPKD_T_IDENT_ASSIGN.
+ *
+ * spkd_bw_accumulate: ordered sums of records, what a merge of section 10 does to a record:
+ *     dst[h_dst[k]] = (h_keep[k] ? dst[h_dst[k]] : 0) + src[m_0] + src[m_1] + ...
+ *   over the members m_i = h_member[h_set_off[k] ..  h_set_off[k + 1]) of set k, in that order, by plain
+ *   fp64 additions, one element a lane: the bits are those of the sum written down in that order.  A
+ *   set may be empty.  The records of d_src_bw (n_src of them) and d_dst_bw (n_dst) must not overlap.
+ *   SPKD_EINVAL before any device work, d_dst_bw untouched: a null pointer, a negative count, more sets
+ *   than slots, offsets that do not start at 0 or go back, a member outside [0, n_src), a slot outside
+ *   [0, n_dst) or named twice, C outside [1, SPKD_GMM_MAX_COMP], a buffer that is not 16-byte aligned.
+ *   n_sets = 0: SPKD_OK without a launch.  Timer: SPKD_T_BW_ACCUMULATE. */
+#define SPKD_GALLERY_MAX_N 16384
+spkd_status spkd_clr_identify(spkd_ctx *ctx, const double *d_probe_bw, int64_t n_probe,
+                              const int32_t *h_probe_ok, int64_t n_groups, const int64_t *h_group_off,
+                              const double *d_gallery_bw, int64_t n_gallery, const int32_t *h_gallery_ok,
+                              const double *d_ubm, int32_t n_comp, double relevance, double threshold,
+                              int32_t exclusive, int32_t *h_ident, double *h_score, double *h_second,
+                              double *d_scores);
+spkd_status spkd_bw_accumulate(spkd_ctx *ctx, const double *d_src_bw, int64_t n_src, int32_t n_comp,
+                               int64_t n_sets, const int64_t *h_set_off, const int32_t *h_member,
+                               const int32_t *h_dst, const int32_t *h_keep, double *d_dst_bw,
+                               int64_t n_dst);
 
 /* ---------------------------------------------------------------------------
  * (5) Host-side helpers of the boundary (no GPU work).

@@ -29,11 +29,12 @@
 #include "spkd_gmm_train.hpp"
 #include "spkd_ubm_stats.hpp"
 #include "spkd_clr.hpp"
+#include "spkd_ident.hpp"
 
 using namespace spkd;
 
 namespace {
-constexpr int N_SLOTS = 64;
+constexpr int N_SLOTS = 72;
 // pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused); of the two decoders' results
 // (TokenHandBack: PIN_VAD_FILES / PIN_VAD_TOKENS of spkd_vad_viterbi_batch, PIN_MD_SEQS / PIN_MD_TOKENS of
 // spkd_mindur_viterbi_batch, so that neither call ends the other's); of the index arrays on their way up: spkd_sum_stats'
@@ -41,10 +42,11 @@ constexpr int N_SLOTS = 64;
 // RangeTable of spkd_gmm_train (PIN_GT_TAB) and of spkd_ubm_stats (PIN_UBM_TAB), spkd_clr_link's ok flags (PIN_CLR_IN),
 // the FbTable of spkd_fb_posterior_batch (PIN_FB_TAB);
 // and of what comes down: spkd_gmm_train's ok flags and log-likelihoods (PIN_GT_OUT), spkd_ubm_stats' ok flags
-// (PIN_UBM_OUT), spkd_clr_link's merge log and statistics (PIN_CLR_OUT)
+// (PIN_UBM_OUT), spkd_clr_link's merge log and statistics (PIN_CLR_OUT); spkd_clr_identify's flags and offsets on their
+// way up (PIN_ID_IN) and its decisions on their way down (PIN_ID_OUT), spkd_bw_accumulate's table (PIN_ACC_TAB)
 enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
        PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, PIN_MD_SEQS, PIN_MD_TOKENS,
-       PIN_FB_TAB, N_PIN };
+       PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, N_PIN };
 }
 
 struct spkd_ctx {
@@ -272,7 +274,8 @@ enum {
     S_STEP_EXM, S_STEP_PKM, S_STEP_MISC, S_GMM_TAB, S_GMM_IDX,
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
     S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT,
-    S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_FB_TAB, S_FB_FWD, S_FB_OUT, S_COUNT
+    S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_FB_TAB, S_FB_FWD, S_FB_OUT,
+    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -2842,6 +2845,144 @@ spkd_status spkd_clr_link(spkd_ctx* c, const double* d_bw, int64_t n, const int3
     *h_stat_max = ho.stat[0];
     *h_stat_min = ho.stat[1];
     return st;
+}
+
+// ------------------------------------------------------------------ (11) a gallery of enrolled speakers
+static_assert(ID_MAX_G == SPKD_GALLERY_MAX_N, "the header states the limit");
+
+spkd_status spkd_clr_identify(spkd_ctx* c, const double* d_probe_bw, int64_t n_probe, const int32_t* h_probe_ok,
+                              int64_t n_groups, const int64_t* h_group_off, const double* d_gallery_bw,
+                              int64_t n_gallery, const int32_t* h_gallery_ok, const double* d_ubm, int32_t n_comp,
+                              double relevance, double threshold, int32_t exclusive, int32_t* h_ident, double* h_score,
+                              double* h_second, double* d_scores) {
+    if (!c || n_probe < 0) return SPKD_EINVAL;
+    if (n_probe == 0) return SPKD_OK;
+    if (!d_probe_bw || !h_probe_ok || !h_group_off || !d_ubm || !h_ident || !h_score || !h_second ||
+        (n_gallery > 0 && (!d_gallery_bw || !h_gallery_ok)))
+        return fail(c, SPKD_EINVAL, "null argument");
+    if (n_probe > CL_MAX_N) return fail(c, SPKD_EINVAL, "clr_identify: at most 4096 probes");
+    if (n_gallery < 0 || n_gallery > ID_MAX_G) return fail(c, SPKD_EINVAL, "clr_identify: 0 <= n_gallery <= 16384");
+    if (n_groups < 1 || n_groups > CL_MAX_N) return fail(c, SPKD_EINVAL, "clr_identify: 1 <= n_groups <= 4096");
+    if (h_group_off[0] != 0 || h_group_off[n_groups] != n_probe)
+        return fail(c, SPKD_EINVAL, "clr_identify: group_off runs from 0 to n_probe");
+    for (int64_t g = 0; g < n_groups; ++g)
+        if (h_group_off[g + 1] < h_group_off[g]) return fail(c, SPKD_EINVAL, "clr_identify: group_off must not go back");
+    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "clr_identify: 1 <= n_comp <= 8");
+    if (!(relevance > 0.0) || !std::isfinite(relevance)) return fail(c, SPKD_EINVAL, "clr_identify: relevance must be finite and > 0");
+    if (std::isnan(threshold)) return fail(c, SPKD_EINVAL, "clr_identify: threshold is NaN");
+    if (exclusive != 0 && exclusive != 1) return fail(c, SPKD_EINVAL, "clr_identify: exclusive is 0 or 1");
+    if ((uintptr_t)d_probe_bw % 16 || (uintptr_t)d_gallery_bw % 16 || (uintptr_t)d_ubm % 16 || (uintptr_t)d_scores % 16)
+        return fail(c, SPKD_EINVAL, "clr_identify: misaligned buffer (model, records and scores: 16 bytes)");
+    const double nan = std::nan("");
+    const size_t S = (size_t)n_probe, G = (size_t)n_gallery, ng = (size_t)n_groups, E = (size_t)n_comp * BW_COMP;
+    if (G == 0) {                                                        // nobody is enrolled: every probe is unknown
+        for (size_t s = 0; s < S; ++s) {
+            h_ident[s] = -1;
+            h_score[s] = h_second[s] = nan;
+        }
+        return SPKD_OK;
+    }
+    struct In { int32_t *okp, *okg, *off; } hi, din;
+    struct Out { double *score, *second; int32_t* ident; } ho, dout;
+    auto ins = [&](Layout L, In& t) { return L.part(t.okp, S).part(t.okg, G).part(t.off, ng + 1).bytes(); };
+    auto outs = [&](Layout L, Out& o) { return L.part(o.score, S).part(o.second, S).part(o.ident, S).bytes(); };
+    size_t in_bytes = 0, out_bytes = 0;
+    TRY(carve(c, pinned, PIN_ID_IN, [&](Layout L) { return in_bytes = ins(L, hi); }));
+    TRY(carve(c, pinned, PIN_ID_OUT, [&](Layout L) { return out_bytes = outs(L, ho); }));
+    std::memcpy(hi.okp, h_probe_ok, S * sizeof(int32_t));
+    std::memcpy(hi.okg, h_gallery_ok, G * sizeof(int32_t));
+    for (size_t g = 0; g <= ng; ++g) hi.off[g] = (int32_t)h_group_off[g];
+    Call call(c);
+    TRY(call.opened);
+    double *d_tp = nullptr, *d_np = nullptr, *d_tg = nullptr, *d_ng = nullptr;
+    char* d_in = nullptr;
+    TRY(carve(c, scratch, S_ID_WORK, [&](Layout L) {
+        outs(L, dout);                                                   // (first: one copy down)
+        L.at = (out_bytes + 15) / 16 * 16;
+        L.part(d_in, in_bytes);                                          // (one copy up)
+        ins(Layout(d_in), din);
+        return L.part(d_tp, S * E).part(d_np, S).part(d_tg, G * E).part(d_ng, G).bytes();
+    }));
+    double* d_mat = d_scores;
+    if (!d_mat) {
+        void* p = nullptr;
+        TRY(scratch(c, S_ID_MAT, S * G * sizeof(double), &p));
+        d_mat = (double*)p;
+    }
+    HIPCHK(c, hipMemcpyAsync(d_in, hi.okp, in_bytes, hipMemcpyHostToDevice, c->stream));
+    {
+        Timer t(c, SPKD_T_IDENT_SCORES);
+        hipLaunchKernelGGL(k_ident_derive, dim3((unsigned)S), dim3(WAVE), 0, c->stream, d_probe_bw, d_ubm, (int)n_comp,
+                           relevance, d_tp, d_np);
+        hipLaunchKernelGGL(k_ident_derive, dim3((unsigned)G), dim3(WAVE), 0, c->stream, d_gallery_bw, d_ubm, (int)n_comp,
+                           relevance, d_tg, d_ng);
+        hipLaunchKernelGGL(k_ident_scores, dim3((unsigned)((S + ID_ROWS - 1) / ID_ROWS), (unsigned)((G + ID_COLS - 1) / ID_COLS)),
+                           dim3(ID_TPB), 0, c->stream, d_probe_bw, (const double*)d_tp, (const double*)d_np,
+                           (const int*)din.okp, (int)S, d_gallery_bw, (const double*)d_tg, (const double*)d_ng,
+                           (const int*)din.okg, (int)G, (int)n_comp, d_mat, c->d_err);
+    }
+    {
+        Timer t(c, SPKD_T_IDENT_ASSIGN);
+        hipLaunchKernelGGL(k_ident_assign, dim3((unsigned)ng), dim3(CL_TPB), 0, c->stream, (const double*)d_mat,
+                           (const int*)din.okp, (const int*)din.okg, (const int*)din.off, (int)G, threshold, (int)exclusive,
+                           (int*)dout.ident, dout.score, dout.second, (const int*)c->d_err);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(ho.score, dout.score, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    const spkd_status st = call.finish();
+    if (st != SPKD_OK && st != SPKD_ENONFINITE) return st;
+    std::memcpy(h_ident, ho.ident, S * sizeof(int32_t));                 // (every ident -1 when a score was not finite)
+    std::memcpy(h_score, ho.score, S * sizeof(double));
+    std::memcpy(h_second, ho.second, S * sizeof(double));
+    return st;
+}
+
+spkd_status spkd_bw_accumulate(spkd_ctx* c, const double* d_src_bw, int64_t n_src, int32_t n_comp, int64_t n_sets,
+                               const int64_t* h_set_off, const int32_t* h_member, const int32_t* h_dst,
+                               const int32_t* h_keep, double* d_dst_bw, int64_t n_dst) {
+    if (!c || n_sets < 0) return SPKD_EINVAL;
+    if (n_sets == 0) return SPKD_OK;
+    if (!d_src_bw || !h_set_off || !h_member || !h_dst || !h_keep || !d_dst_bw) return fail(c, SPKD_EINVAL, "null argument");
+    if (n_src < 0 || n_dst < 0 || n_src > 0x7fffffff || n_dst > 0x7fffffff || n_sets > n_dst)
+        return fail(c, SPKD_EINVAL, "bw_accumulate: bad count (a set per slot at most)");
+    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "bw_accumulate: 1 <= n_comp <= 8");
+    if (h_set_off[0] != 0) return fail(c, SPKD_EINVAL, "bw_accumulate: set_off[0] must be 0");
+    for (int64_t k = 0; k < n_sets; ++k)
+        if (h_set_off[k + 1] < h_set_off[k]) return fail(c, SPKD_EINVAL, "bw_accumulate: set_off must not go back");
+    const int64_t n_mem = h_set_off[n_sets];
+    if (n_mem > 0x7fffffff) return fail(c, SPKD_EINVAL, "bw_accumulate: too many members");
+    for (int64_t m = 0; m < n_mem; ++m)
+        if (h_member[m] < 0 || h_member[m] >= n_src) return fail(c, SPKD_EINVAL, "bw_accumulate: member outside [0, n_src)");
+    {
+        std::vector<char> named((size_t)n_dst, 0);
+        for (int64_t k = 0; k < n_sets; ++k) {
+            if (h_dst[k] < 0 || h_dst[k] >= n_dst) return fail(c, SPKD_EINVAL, "bw_accumulate: slot outside [0, n_dst)");
+            if (named[(size_t)h_dst[k]]++) return fail(c, SPKD_EINVAL, "bw_accumulate: a slot is named twice");
+        }
+    }
+    if ((uintptr_t)d_src_bw % 16 || (uintptr_t)d_dst_bw % 16)
+        return fail(c, SPKD_EINVAL, "bw_accumulate: misaligned buffer (records: 16 bytes)");
+    const size_t ns = (size_t)n_sets, nm = (size_t)n_mem;
+    struct Tab { long long* off; int32_t *member, *slot, *keep; } ht, dt;
+    auto parts = [&](Layout L, Tab& t) { return L.part(t.off, ns + 1).part(t.member, nm).part(t.slot, ns).part(t.keep, ns).bytes(); };
+    size_t bytes = 0;
+    TRY(carve(c, pinned, PIN_ACC_TAB, [&](Layout L) { return bytes = parts(L, ht); }));
+    for (size_t k = 0; k <= ns; ++k) ht.off[k] = h_set_off[k];
+    std::memcpy(ht.member, h_member, nm * sizeof(int32_t));
+    std::memcpy(ht.slot, h_dst, ns * sizeof(int32_t));
+    std::memcpy(ht.keep, h_keep, ns * sizeof(int32_t));
+    Call call(c);
+    TRY(call.opened);
+    TRY(carve(c, scratch, S_ACC_TAB, [&](Layout L) { return parts(L, dt); }));
+    HIPCHK(c, hipMemcpyAsync(dt.off, ht.off, bytes, hipMemcpyHostToDevice, c->stream));
+    {
+        Timer t(c, SPKD_T_BW_ACCUMULATE);
+        hipLaunchKernelGGL(k_bw_accumulate, dim3((unsigned)ns), dim3(ID_ACC_TPB), 0, c->stream, d_src_bw,
+                           (const long long*)dt.off, (const int*)dt.member, (const int*)dt.slot, (const int*)dt.keep,
+                           (int)(n_comp * BW_COMP), d_dst_bw);
+    }
+    HIPCHK(c, hipGetLastError());
+    return call.finish();
 }
 
 // ------------------------------------------------------------------ (5) host helpers

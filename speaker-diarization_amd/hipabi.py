@@ -19,6 +19,7 @@ TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pai
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
                                         'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
                                         'mindur_viterbi', 'mindur_backtrack', 'fb_posterior',
+                                        'ident_scores', 'ident_assign', 'bw_accumulate',
                                         'mfcc_static', 'mfcc_post'])}
 VAD_TILE = 32       # SPKD_VAD_TILE: frames per score / back-pointer tile of k_vad_viterbi
 MINDUR_TILE = 32    # SPKD_MINDUR_TILE: frames per score / record tile of k_mindur_viterbi
@@ -31,6 +32,7 @@ GMM_TILE = 64       # SPKD_GMM_TILE: frame ordinals per tile of k_gmm_estep, fra
 GMM_CHUNK_TILES = 16    # SPKD_GMM_CHUNK_TILES: tiles per chunk, the unit of a partial sum of k_gmm_estep
 BW_COMP = 40        # SPKD_BW_COMP: doubles per component of a speaker record under a UBM (n_c, f_c[39])
 CLR_MAX_N = 4096    # SPKD_CLR_MAX_N: speakers of one spkd_clr_link
+GALLERY_MAX_N = 16384   # SPKD_GALLERY_MAX_N: identities of one spkd_clr_identify
 REC = 820
 DIM = 39
 
@@ -42,7 +44,8 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
            'spkd_gauss_models', 'spkd_gauss_loglik', 'spkd_gmm_train', 'spkd_gmm_loglik_seq',
-           'spkd_ubm_stats', 'spkd_clr_link', 'spkd_mindur_viterbi_batch', 'spkd_fb_posterior_batch']
+           'spkd_ubm_stats', 'spkd_clr_link', 'spkd_mindur_viterbi_batch', 'spkd_fb_posterior_batch',
+           'spkd_clr_identify', 'spkd_bw_accumulate']
 
 
 class CdParams(C.Structure):
@@ -225,6 +228,8 @@ def load_library(path=None):
     lib.spkd_gmm_loglik_seq.argtypes = [vp, vp, i64, vp, i32, i64, vp, i64, vp, vp, vp, vp, i32, vp]
     lib.spkd_ubm_stats.argtypes = [vp, vp, i64, vp, i32, i64, vp, vp, vp, vp, vp]
     lib.spkd_clr_link.argtypes = [vp, vp, i64, vp, vp, i32, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]
+    lib.spkd_clr_identify.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, dbl, dbl, i32, vp, vp, vp, vp]
+    lib.spkd_bw_accumulate.argtypes = [vp, vp, i64, i32, i64, vp, vp, vp, vp, vp, i64]
     lib.spkd_gw_lines.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, dbl, C.c_int, i64, vp, vp, vp, vp, vp]
     if lib.spkd_abi_version() != 2:
         raise ImportError('libspkd_hip.so ABI version mismatch')
@@ -940,6 +945,46 @@ class Context(object):
         self.check(st, allow=(SPKD_ENONFINITE,))
         k = int(nm[0])
         return dict(status=st, n_merges=k, a=ma[:k], b=mb[:k], d=md[:k], stat_max=float(smax[0]), stat_min=float(smin[0]))
+
+    # ---- (11) a gallery of enrolled speakers
+    def clr_identify(self, d_probe_bw, probe_ok, group_off, d_gallery_bw, gallery_ok, d_ubm, n_comp, relevance,
+                     threshold, exclusive=True, d_scores=None):
+        """The len(probe_ok) records at d_probe_bw against the len(gallery_ok) records at d_gallery_bw by
+        cross-likelihood ratio under the UBM at d_ubm (spkd_clr_identify).  group_off: the probes of
+        group k are group_off[k] .. group_off[k + 1]; under `exclusive` the probes of a group get
+        distinct identities, by a greedy chain over the scores above `threshold`.  Returns dict(status,
+        ident, score, second): ident int32 (-1: unknown), score the assigned pair's or an unknown
+        probe's highest, second the highest over the other identities (NaN: none).  status is
+        SPKD_ENONFINITE, with every ident -1, when a score among ok records was not finite.  d_scores:
+        a device buffer of len(probe_ok) * len(gallery_ok) doubles that receives the matrix.  The
+        kernels' times are last_ms('ident_scores') and last_ms('ident_assign')."""
+        pok = np.ascontiguousarray(probe_ok, dtype=np.int32)
+        gok = np.ascontiguousarray(gallery_ok, dtype=np.int32)
+        off = np.ascontiguousarray(group_off, dtype=np.int64)
+        if pok.ndim != 1 or gok.ndim != 1 or off.ndim != 1 or len(off) < 1:
+            raise SpkdError(SPKD_EINVAL, 'ok: one flag per record; group_off: one offset per group and the end')
+        n = len(pok)
+        ident = np.full(n, -1, dtype=np.int32)
+        score, second = np.full(n, np.nan), np.full(n, np.nan)
+        st = self.lib.spkd_clr_identify(self.h, C.c_void_p(d_probe_bw), n, _ptr(pok), len(off) - 1, _ptr(off),
+                                        C.c_void_p(d_gallery_bw), len(gok), _ptr(gok), C.c_void_p(d_ubm), int(n_comp),
+                                        float(relevance), float(threshold), 1 if exclusive else 0, _ptr(ident),
+                                        _ptr(score), _ptr(second), C.c_void_p(d_scores) if d_scores else None)
+        self.check(st, allow=(SPKD_ENONFINITE,))
+        return dict(status=st, ident=ident, score=score, second=second)
+
+    def bw_accumulate(self, d_src_bw, n_src, n_comp, set_off, member, dst, keep, d_dst_bw, n_dst):
+        """dst[dst[k]] = (keep[k] ? dst[dst[k]] : 0) + the records member[set_off[k]:set_off[k + 1]] of
+        d_src_bw, in that order (spkd_bw_accumulate): the sum of a cluster's records, or a record added
+        to its identity.  The kernel's time is last_ms('bw_accumulate')."""
+        off = np.ascontiguousarray(set_off, dtype=np.int64)
+        mem = np.ascontiguousarray(member, dtype=np.int32)
+        slot = np.ascontiguousarray(dst, dtype=np.int32)
+        kp = np.ascontiguousarray(keep, dtype=np.int32)
+        if off.ndim != 1 or len(off) < 1 or len(slot) != len(off) - 1 or len(kp) != len(slot) or len(mem) != int(off[-1]):
+            raise SpkdError(SPKD_EINVAL, 'bw_accumulate: one slot and one keep flag per set, set_off[-1] members')
+        self.check(self.lib.spkd_bw_accumulate(self.h, C.c_void_p(d_src_bw), int(n_src), int(n_comp), len(slot), _ptr(off),
+                                               _ptr(mem), _ptr(slot), _ptr(kp), C.c_void_p(d_dst_bw), int(n_dst)))
 
     # ---- (4)
     def ahc(self, d_stats, seg_off, params):

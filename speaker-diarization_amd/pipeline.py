@@ -15,6 +15,7 @@ import time
 
 import numpy as np
 
+from . import gallery as _gallery
 from . import hipabi
 from .recipe import py2_float_str
 
@@ -601,24 +602,37 @@ def ubm_ranges(set_off, begin, end, cap):
     return begin + np.clip(share[owner] - ord0, 0, length)
 
 
-def _link_clr(ctx, model, set_off, rng_b, rng_e, d_frames, total_frames, timings):
+def _link_clr(ctx, model, set_off, rng_b, rng_e, d_frames, total_frames, timings, gallery=None, kept=None):
     """The calls of link_batch under model 'clr' -> (n_merges, a, b, d, stat_max, stat_min), or None
-    when no background model could be trained."""
+    when no background model could be trained.  gallery: its model is the background model -- trained
+    here, as without a gallery, when it has none yet.  kept: a dict that receives the speakers' records
+    (d_bw) and their flags (ok)."""
     _, n_comp, n_iter, var_floor, relevance, threshold, max_spk, cap = model
     n_spk = len(set_off) - 1
     if n_spk > hipabi.CLR_MAX_N:
         raise ValueError('clr_link: at most %d speakers' % hipabi.CLR_MAX_N)
-    d_ubm = ctx.dev_scratch('link_ubm', n_comp * hipabi.GMM_COMP * 8)
-    ok, _ = ctx.gmm_train(d_frames, total_frames, [0, len(rng_b)], rng_b, ubm_ranges(set_off, rng_b, rng_e, cap),
-                          n_comp, n_iter, var_floor, d_ubm)
-    if timings is not None:
-        timings.setdefault('link_ubm_train', []).append(ctx.last_ms('gmm_train'))
-    if not ok[0]:
-        return None
+    if gallery is None:
+        d_ubm = ctx.dev_scratch('link_ubm', n_comp * hipabi.GMM_COMP * 8)
+        ok, _ = ctx.gmm_train(d_frames, total_frames, [0, len(rng_b)], rng_b, ubm_ranges(set_off, rng_b, rng_e, cap),
+                              n_comp, n_iter, var_floor, d_ubm)
+        if timings is not None:
+            timings.setdefault('link_ubm_train', []).append(ctx.last_ms('gmm_train'))
+        if not ok[0]:
+            return None
+    else:
+        if gallery.ubm is None:
+            trained = gallery.train_ubm(d_frames, total_frames, set_off, rng_b, rng_e, n_iter, var_floor, cap)
+            if timings is not None:
+                timings.setdefault('link_ubm_train', []).append(ctx.last_ms('gmm_train'))
+            if not trained:
+                return None
+        d_ubm = gallery.d_ubm
     d_bw = ctx.dev_scratch('link_speaker_bw', n_spk * n_comp * hipabi.BW_COMP * 8)
     spk_ok = ctx.ubm_stats(d_frames, total_frames, d_ubm, n_comp, set_off, rng_b, rng_e, d_bw)
     if timings is not None:
         timings.setdefault('link_ubm_stats', []).append(ctx.last_ms('ubm_stats'))
+    if kept is not None:
+        kept.update(d_bw=d_bw, ok=spk_ok)
     r = ctx.clr_link(d_bw, spk_ok, d_ubm, n_comp, relevance, threshold, max_spk)
     if timings is not None:
         timings.setdefault('link_clr', []).append(ctx.last_ms('clr_link'))
@@ -627,8 +641,63 @@ def _link_clr(ctx, model, set_off, rng_b, rng_e, d_frames, total_frames, timings
     return r['n_merges'], r['a'], r['b'], r['d'], r['stat_max'], r['stat_min']
 
 
+def _link_gallery(link, model):
+    """The gallery keys of a `link` dictionary of model 'clr': (gallery or None, enrol, exclusive)."""
+    gal = link.get('gallery')
+    if model[0] != 'clr':
+        if gal is not None:
+            raise ValueError('link gallery: a gallery holds the records of link model clr')
+        return None, False, False
+    if gal is None:
+        return None, False, False
+    if not isinstance(gal, _gallery.Gallery):
+        raise ValueError('link gallery: a gallery.Gallery')
+    if gal.components != model[1]:
+        raise ValueError('link components: the gallery has %d' % gal.components)
+    if gal.relevance != model[4]:
+        raise ValueError('link relevance: the gallery has %r' % gal.relevance)
+    return gal, bool(link.get('enrol', True)), bool(link.get('exclusive', True))
+
+
+def _identify_clusters(ctx, gallery, enrol, exclusive, kept, glob, timings, detail):
+    """The gallery step of link_batch: the batch clusters of the chain (glob: the 1-based cluster of each
+    speaker) get their records, are identified against the gallery as ONE group and are labelled by
+    identity -> the global label of each speaker."""
+    n_spk, n_cl = len(glob), int(glob.max())
+    member = np.argsort(glob, kind='stable')                             # a cluster's speakers in ascending order
+    set_off = np.concatenate([[0], np.cumsum(np.bincount(glob - 1, minlength=n_cl))])
+    cl_ok = np.minimum.reduceat(np.asarray(kept['ok'], dtype=np.int32)[member], set_off[:-1]).astype(np.int32)
+    d_cl = ctx.dev_scratch('link_cluster_bw', n_cl * gallery.record_doubles * 8)
+    ctx.bw_accumulate(kept['d_bw'], n_spk, gallery.components, set_off, member, np.arange(n_cl), np.zeros(n_cl), d_cl, n_cl)
+    if timings is not None:
+        timings.setdefault('link_cluster_sum', []).append(ctx.last_ms('bw_accumulate'))
+    r = gallery.identify(d_cl, cl_ok, [0, n_cl], exclusive)
+    if timings is not None:
+        timings.setdefault('link_ident', []).append(
+            ctx.last_ms('ident_scores') + ctx.last_ms('ident_assign') if gallery.n else 0.0)
+    n_before = gallery.n
+    ident = r['ident'].astype(np.int64)
+    unknown = np.nonzero((cl_ok != 0) & (ident < 0))[0]
+    label = ident + 1
+    label[unknown] = n_before + 1 + np.arange(len(unknown))
+    bad = np.nonzero(cl_ok == 0)[0]                                      # (no record: a label that stands for nobody)
+    label[bad] = n_before + len(unknown) + 1 + np.arange(len(bad))
+    enrolled = []
+    if enrol:
+        after = gallery.update(d_cl, cl_ok, ident)
+        if timings is not None:
+            timings.setdefault('link_update', []).append(ctx.last_ms('bw_accumulate') if (cl_ok != 0).any() else 0.0)
+        enrolled = after[unknown].tolist()
+        ident = after.astype(np.int64)
+    elif timings is not None:
+        timings.setdefault('link_update', []).append(0.0)
+    if detail is not None:
+        detail.update(identity=ident.astype(np.int32), score=r['score'], second=r['second'], enrolled=enrolled)
+    return label[glob - 1].astype(np.int32)
+
+
 def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None, d_frames=None, total_frames=None,
-               files=None, segments=None, rate=125.0):
+               files=None, segments=None, rate=125.0, detail=None):
     """Which speaker of one file is which speaker of another: spk_cluster_hi over the speakers of
     all files of a batch (spk-clustering.py:178-240 takes `speakers` of any length per entry; the
     command line never gets there, :289).  d_stats, seg_off: the segment records and the files'
@@ -653,8 +722,28 @@ def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None, d_fram
     initial ratios.  When no background model can be trained (too few frames, constant or non-finite
     frames) every speaker keeps a global label of its own and merges = [].  More than 4 096 speakers,
     a key out of range, a missing array: ValueError.  timings: link_ubm_train, link_ubm_stats,
-    link_clr (kernel ms), link_speakers, link_merges."""
+    link_clr (kernel ms), link_speakers, link_merges.
+    A link dictionary of model 'clr' may carry gallery=<gallery.Gallery>, enrol (default True) and
+    exclusive (default True); the global labels then mean the same person in every batch.  The
+    gallery's model is the background model: it is trained on this batch, as above, only when the
+    gallery has none yet, and link['components'] and link['relevance'] must equal the gallery's
+    (ValueError).  The statistics and the chain run within the batch as above.  The records of the
+    resulting batch clusters are the sums of their speakers' records in ascending speaker order
+    (spkd_bw_accumulate); the clusters are identified against the gallery as ONE group
+    (Gallery.identify with the gallery's threshold: the chain declined to merge them, so they are
+    distinct people, and under `exclusive` they get distinct identities).  The global label of a
+    cluster is its identity's index + 1.  With enrol the unknown clusters are appended to the gallery
+    in cluster order and the matched identities take the cluster's record (Gallery.update); without it
+    the gallery is left untouched and the k-th unknown cluster is labelled gallery.n + 1 + k -- the
+    label it would have got.  (A cluster without a usable record is labelled behind those; its label
+    stands for nobody.)  maps, merges, stat_max and stat_min as above; detail: a dict that receives
+    identity, score and second per batch cluster (Gallery.identify's, identity after enrolment) and
+    enrolled, the new identities.  timings gain link_cluster_sum, link_ident (both identify kernels,
+    ms) and link_update.  When no background model can be trained the fallback is the one above and
+    the gallery is unchanged.  The identification threshold, like LINK_CLR's, rests on a synthetic
+    fixture and not on speech."""
     model = _link_model(link)
+    gal, enrol, exclusive = _link_gallery(link, model)
     if model[0] == 'clr':
         if d_frames is None or total_frames is None or files is None or segments is None:
             raise ValueError('link model clr trains on the frames: it takes d_frames, total_frames, files and '
@@ -671,7 +760,8 @@ def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None, d_fram
         return maps, [], float('nan'), float('nan')
     if model[0] == 'clr':
         try:
-            r = _link_clr(ctx, model, set_off, seg_b[member], seg_e[member], d_frames, total_frames, timings)
+            kept = None if gal is None else {}
+            r = _link_clr(ctx, model, set_off, seg_b[member], seg_e[member], d_frames, total_frames, timings, gal, kept)
         except hipabi.SpkdError as e:
             if e.status == hipabi.SPKD_EINVAL:
                 raise ValueError(str(e))
@@ -681,6 +771,13 @@ def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None, d_fram
             timings['link_speakers'] = n_spk
             timings['link_merges'] = nm
         glob = hipabi.labels_from_merges(n_spk, a, b)
+        if gal is not None and r is not None:
+            try:
+                glob = _identify_clusters(ctx, gal, enrol, exclusive, kept, glob, timings, detail)
+            except hipabi.SpkdError as e:
+                if e.status == hipabi.SPKD_EINVAL:
+                    raise ValueError(str(e))
+                raise
         for f, l, g in zip(spk_file.tolist(), spk_label.tolist(), glob.tolist()):
             maps[f][l] = g
         return maps, list(zip(np.asarray(a).tolist(), np.asarray(b).tolist(), np.asarray(d).tolist())), smax, smin
@@ -1096,7 +1193,9 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     order are those of link=None.  Host hand-off only.  detail: a dict; receives link_batch's
     result as detail['link'] = dict(maps, merges, stat_max, stat_min).  A dictionary like LINK_CLR
     links by cross-likelihood ratio (link_batch, model 'clr'): the frames and the clustering segments
-    are passed through to it.
+    are passed through to it.  Such a dictionary may carry gallery=<gallery.Gallery>, enrol and
+    exclusive (link_batch): the third column then holds identities of the gallery + 1, the same
+    person in every batch, and detail['link'] gains identity, score, second and enrolled.
     reseg: a dictionary like RESEG; the rows are then those of resegment_batch on the records and
     labels clustering left: every turn decoded frame by frame under the file's speaker models, so
     the boundaries sit where the evidence changes instead of on the detector's candidate grid.
@@ -1124,7 +1223,7 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
             raise ValueError('cd method %s takes the host hand-off and is not fused' % _cd_method(cd))
         handoff = 'host'
     if link is not None:
-        _link_model(link)
+        _link_gallery(link, _link_model(link))
     if link is not None and (handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi')):
         raise ValueError('link takes the host hand-off')
     if handoff is None:
@@ -1166,22 +1265,24 @@ def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timin
         rows = resegment_batch(ctx, d_frames, total_frames, files, box[0][0], box[0][1], own, rate, reseg,
                                text_contract, timings, detail, segs)
         if link is not None:
+            more = {}
             maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], own, link, timings, d_frames, total_frames,
-                                                  files, segs, rate)
+                                                  files, segs, rate, more)
             for r, m in zip(rows, maps):
                 r[:, 2] = m[r[:, 2].astype(np.int64)] if len(r) else r[:, 2]
             if detail is not None:
-                detail['link'] = dict(maps=maps, merges=merges, stat_max=smax, stat_min=smin)
+                detail['link'] = dict(maps=maps, merges=merges, stat_max=smax, stat_min=smin, **more)
         return rows
     allseg = np.concatenate([np.asarray(s, dtype=np.float64).reshape(-1, 2) for s in segs])
     if link is None:
         labels = np.concatenate([lab for (lab, _) in res])
     else:
+        more = {}
         maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], [lab for (lab, _) in res], link, timings,
-                                              d_frames, total_frames, files, segs, rate)
+                                              d_frames, total_frames, files, segs, rate, more)
         labels = np.concatenate([m[lab] for m, (lab, _) in zip(maps, res)])
         if detail is not None:
-            detail['link'] = dict(maps=maps, merges=merges, stat_max=smax, stat_min=smin)
+            detail['link'] = dict(maps=maps, merges=merges, stat_max=smax, stat_min=smin, **more)
     bounds = np.zeros(len(segs) + 1, dtype=np.int64)
     bounds[1:] = np.cumsum(cnt)
     if _method(cl) == 'in':
