@@ -63,19 +63,19 @@ enum { PASS_RIGHT = 0, PASS_LEFT = 1, PASS_GLR = 2, PASS_POOLED = 3 };
 // ---------------------------------------------------------------------------
 // Records of running moment sums.
 //
-// In LDS (P(c), the sums at the window end) the "tri" layout: line (tri_off(s) + j)
-// holds M(13 s + t, j) for t = 0..12 in its first 13 doubles, j < 13 (s + 1); lines
-// 78..80 hold the sums column of slot s; the frame count sits in lane 15 of line 78.
-// 81 lines of 128 B, conflict-free for the formation's reads.
+// In LDS (P(c), the sums at the window end) the "tri" layout of spkd_quad.hpp: line
+// (tri_off(s) + j) holds M(quad_row(s, t), j) for t < quad_rows(s), j < tri_cols(s); lines
+// 69..71 hold the sums column of slot s; the frame count sits in lane 15 of line 69.
+// 72 lines of 128 B, conflict-free for the formation's reads.
 //
 // In global memory (the per-candidate cache, and the per-segment output of the fused
 // mode) the ABI's packed record itself, SPKD_REC = 820 doubles.  Read by symmetry it
 // is the lower triangle column by column: column j holds rows j .. 39 contiguously
-// from pk_off(j), so the quad load of (slot s, column j) is 13 consecutive doubles at
-// pk_off(j) + 13 s - j + t.  For the lanes of a diagonal block that sit above the
-// diagonal (13 s + t < j) that address lies in the tail of the previous column --
+// from pk_off(j), so the quad load of (slot s, column j) is 16 consecutive doubles at
+// quad_pk_at(s, j) + t.  For the lanes of a diagonal block that sit above the
+// diagonal (quad_row(s, t) < j) that address lies in the tail of the previous column --
 // inside the record, and the value lands in a register nobody reads (spkd_tri.hpp).
-// 6 560 B per candidate instead of the 10 368 B of a padded tri record.
+// 6 560 B per candidate instead of the 9 216 B of a padded tri record.
 // ---------------------------------------------------------------------------
 // row-per-lane (single matrix) rows of a tri record / a packed record, by symmetry
 __device__ __forceinline__ void single_rows_from_tri(const double* rec, double (&q)[DA]) {
@@ -107,7 +107,7 @@ template <> struct GwShape<8> { static constexpr int BR = 2, BC = 2, TILE = 128;
 template <> struct GwShape<4> { static constexpr int BR = 2, BC = 2, TILE = 128; };
 template <> struct GwShape<2> { static constexpr int BR = 4, BC = 2, TILE = 64; };
 #ifndef SPKD_GW1_TILE
-#define SPKD_GW1_TILE 48        // frames per LDS tile with a wave per turn (32: 15.5 KB of LDS a wave, 48: 17.6)
+#define SPKD_GW1_TILE 48        // frames per LDS tile with a wave per turn (32: 14 352 B of LDS a wave, 48: 16 912)
 #endif
 template <> struct GwShape<1> { static constexpr int BR = 4, BC = 4, TILE = SPKD_GW1_TILE; };
 
@@ -565,10 +565,10 @@ __device__ __forceinline__ double quad_split_det(int pass, bool two, const doubl
     int ta = L.t;
     asm volatile("" : "+v"(ta));          // keep the LDS reads out of the callers' loops
     {
-        // 81 loads in flight, one latency.  One base pointer per 4 KB (the immediate
+        // 72 loads in flight, one latency.  One base pointer per 4 KB (the immediate
         // offset of a global load spans 4 KB; left to itself the compiler builds a
         // separate address for every load, spills them and serialises the loads)
-        const int t12 = ta < QL ? ta : QL - 1;          // idle lanes 13..15 ride with lane 12
+        const int t12 = quad_load_lane(ta);
         const double* rt[2];
         long long o1 = 512;                 // opaque, so that the bases stay separate registers
         asm volatile("" : "+v"(o1));
@@ -578,10 +578,10 @@ __device__ __forceinline__ double quad_split_det(int pass, bool two, const doubl
         for (int s = 0; s < QS; ++s) {
 #pragma unroll
             for (int j = 0; j < tri_cols(s); ++j) {
-                const int e = pk_off(j) + QL * s - j;   // + t12 (in the base)
+                const int e = quad_pk_at(s, j);         // + t12 (in the base)
                 q.r[s][j] = rt[e / 512][e % 512];
             }
-            const int c = QL * s + t12;                 // this lane's row of slot s
+            const int c = quad_row(s, t12);             // this lane's row of slot s (idle lanes: a row all the same)
             svb[s] = rec_b[pk_off(c) + D - c];          // (39, c): the sums entry of column c
         }
     }

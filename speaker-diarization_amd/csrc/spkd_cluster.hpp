@@ -140,8 +140,8 @@ __device__ __forceinline__ void quadrec_from_packed(const double* __restrict__ g
         const int t = e & 15, sj = e >> 4;
         const int s = sj / DA, j = sj - s * DA;
         double v = 0.0;
-        if (t < QL) {
-            const int i = QL * s + t;
+        if (t < quad_rows(s)) {
+            const int i = quad_row(s, t);
             const int r = i < j ? i : j, cc = i < j ? j : i;
             v = g[pk(r, cc)];
         } else if (e == QREC_COUNT_AT) {
@@ -171,7 +171,7 @@ __device__ __forceinline__ void single_rows_from_packed(const double* __restrict
 __device__ __forceinline__ void single_rows_from_qr(const double* __restrict__ qr, double (&q)[DA]) {
     int i = lane_id();
     i = i >= D ? D - 1 : i;           // lanes >= 39 mirror row 38 (ignored)
-    const int base = (i / QL) * DA * 16 + (i % QL);
+    const int base = qr_index(i, 0);
 #pragma unroll
     for (int j = 0; j < DA; ++j) q[j] = qr[base + j * 16];
 }
@@ -234,9 +234,8 @@ __device__ __forceinline__ void single_pair_matrix(int kind, const double* __res
 // gA: the same record in global memory (fallback path only).
 // pkC: the same partner record in the packed ABI layout (6 560 B) -- the hot loads read
 // that copy: by symmetry a packed record is the lower triangle column by column, so the
-// load of (slot s, column j) is 13 consecutive doubles at pk_off(j) + 13 s - j + t (lanes of
-// a diagonal block above the diagonal read the previous column's tail: inside the record,
-// into registers nobody reads).  A pass of the merge loop streams its partners from HBM
+// load of (slot s, column j) is 16 consecutive doubles at quad_pk_at(s, j) + t (spkd_quad.hpp:
+// lanes without a row read inside the record, into registers nobody reads).  A pass of the merge loop streams its partners from HBM
 // (a problem's records exceed its share of L2): tools/pair_bench.hip, partners streaming,
 // 559 M pairs/s from quad records, 686 M pairs/s from packed ones.  The quad copy (qrC)
 // serves the rare pivoting fallback and the in-place merges' LDS staging.
@@ -262,7 +261,7 @@ __device__ __forceinline__ double quad_pair_det(int kind, const double* ldsA, do
                                                    const QuadLane& L, int* err, double nC_known = -1.0) {
     // (nC_known >= 0: the caller has the partner's frame count already -- the step chain keeps
     // the counts in an array of their own, so that a pass does not wait for the count before it
-    // can issue its 81 record loads: two memory round trips in a row on the chain's critical path)
+    // can issue its 72 record loads: two memory round trips in a row on the chain's critical path)
     const double nC = self ? 0.0 : (nC_known >= 0.0 ? nC_known : pkC[REC - 1]);
     const double n = nA + nC;
     const bool glr = TWO && (kind == SPKD_GLR && !self);
@@ -285,9 +284,9 @@ __device__ __forceinline__ double quad_pair_det(int kind, const double* ldsA, do
     double sc[QS];
     PASS_T0();
     {
-        // 81 loads in flight, one latency; one base pointer per 4 KB of the record (the
+        // 72 loads in flight, one latency; one base pointer per 4 KB of the record (the
         // immediate offset of a global load spans 4 KB)
-        const int t12 = ta < QL ? ta : QL - 1;          // idle lanes 13..15 ride with lane 12
+        const int t12 = quad_load_lane(ta);
         const double* rt[2];
         long long o1 = 512;                 // opaque, so that the bases stay separate registers
         asm volatile("" : "+v"(o1));
@@ -297,10 +296,10 @@ __device__ __forceinline__ double quad_pair_det(int kind, const double* ldsA, do
         for (int s = 0; s < QS; ++s) {
 #pragma unroll
             for (int j = 0; j < tri_cols(s); ++j) {
-                const int e = pk_off(j) + QL * s - j;   // + t12 (in the base)
+                const int e = quad_pk_at(s, j);         // + t12 (in the base)
                 q.r[s][j] = rt[e / 512][e % 512];
             }
-            const int c = QL * s + t12;                 // this lane's row of slot s
+            const int c = quad_row(s, t12);             // this lane's row of slot s (idle lanes: a row all the same)
             sc[s] = pkC[pk_off(c) + D - c];             // (39, c): the sums entry of column c
         }
     }
@@ -358,10 +357,10 @@ __device__ __forceinline__ void stage_record(double* lds, const double* __restri
 // ---------------------------------------------------------------------------
 constexpr int PT2_WAVES = 2;
 
-// the 81 loads of a partner record (packed layout) into the elimination's registers, as
+// the 72 loads of a partner record (packed layout) into the elimination's registers, as
 // quad_pair_det issues them (one base pointer per 4 KB of the record)
 __device__ __forceinline__ void quad_load_packed(const double* __restrict__ pkC, int ta, QuadRows& q, double (&sc)[QS]) {
-    const int t12 = ta < QL ? ta : QL - 1;          // idle lanes 13..15 ride with lane 12
+    const int t12 = quad_load_lane(ta);
     const double* rt[2];
     long long o1 = 512;                 // opaque, so that the bases stay separate registers
     asm volatile("" : "+v"(o1));
@@ -371,10 +370,10 @@ __device__ __forceinline__ void quad_load_packed(const double* __restrict__ pkC,
     for (int s = 0; s < QS; ++s) {
 #pragma unroll
         for (int j = 0; j < tri_cols(s); ++j) {
-            const int e = pk_off(j) + QL * s - j;   // + t12 (in the base)
+            const int e = quad_pk_at(s, j);         // + t12 (in the base)
             q.r[s][j] = rt[e / 512][e % 512];
         }
-        const int c = QL * s + t12;                 // this lane's row of slot s
+        const int c = quad_row(s, t12);             // this lane's row of slot s (idle lanes: a row all the same)
         sc[s] = pkC[pk_off(c) + D - c];             // (39, c): the sums entry of column c
     }
 }
@@ -384,8 +383,8 @@ __device__ __forceinline__ void quad_from_packed_lds(double* lds, const double* 
         const int t = e & 15, sj = e >> 4;
         const int s = sj / DA, j = sj - s * DA;
         double v = 0.0;
-        if (t < QL) {
-            const int i = QL * s + t;
+        if (t < quad_rows(s)) {
+            const int i = quad_row(s, t);
             const int r = i < j ? i : j, cc = i < j ? j : i;
             v = g[pk(r, cc)];
         } else if (e == QREC_COUNT_AT) {
@@ -1158,7 +1157,7 @@ __global__ __launch_bounds__(AHC_TPB) void k_step_init(
 // grid (max(1, ceil((n_max - k - 1) / SP)) + 1, n_prob); dynamic LDS: 2 N_max ints + the chunk masks.
 // SP partners of the merge per workgroup (3, 7 or 15: the host picks per round).
 // SW waves per workgroup: the first STEP_WAVES of them eliminate (one wave per SIMD, the pass needs
-// 156 VGPRs); with SW = 8 four more share the selection, the partner list and the rescans, which
+// 138 VGPRs); with SW = 8 four more share the selection, the partner list and the rescans, which
 // are issue-bound per wave (15 clusters per thread at N = 3 860 with four waves) and idle at the
 // barriers through the pass.
 template <bool TWO, int SW, int SP>

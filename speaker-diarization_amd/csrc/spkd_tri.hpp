@@ -1,22 +1,21 @@
 // Symmetric ("triangular") quad elimination: the quad layout of spkd_quad.hpp
-// (four 39x39 matrices per wave64, lane t of a DPP row holds rows t, 13 + t, 26 + t)
-// keeping only the LOWER triangle: slot s needs columns 0 .. 13 (s + 1) - 1, i.e.
-// 13 + 26 + 39 = 78 doubles per lane instead of 117.  Step k updates
+// (four 39x39 matrices per wave64, lane t of a DPP row holds rows t < 7, 7 + t, 23 + t)
+// keeping only the LOWER triangle: slot s needs columns 0 .. tri_cols(s) - 1, i.e.
+// 7 + 23 + 39 = 69 doubles per lane instead of 117.  Step k updates
 //     a[i][j] -= (a[i][k] / a[k][k]) * a[j][k]        for k < j <= i
 // where a[j][k] (row j, column k: lower triangle, not yet touched by step k) is
-// broadcast from its owner lane j % 13 / slot j / 13 with one row_newbcast DPP
-// move -- the symmetric counterpart of broadcasting the pivot row.  Lanes whose
+// broadcast from its owner lane quad_lane_of(j) / slot quad_slot(j) with one row_newbcast
+// DPP move -- the symmetric counterpart of broadcasting the pivot row.  Lanes whose
 // rows lie above column j compute into registers nobody reads.  The broadcast is the
-// DPP operand of the FMA itself (v_fmac_f64_dpp): 1 144 instructions per four
-// determinants (full square form: 1 820 FMAs + 741 DPP moves), and 156 VGPRs of
-// matrix instead of 234: two waves per SIMD without column blocking.
+// DPP operand of the FMA itself (v_fmac_f64_dpp): column J of a step costs one
+// instruction per slot that holds a row >= J, 3 * 21 + 2 * 232 + 1 * 488 = 1 015 per four
+// determinants with the 7/16/16 split (the even split 13/13/13: 1 144; full square form:
+// 1 820 FMAs + 741 DPP moves), and 138 VGPRs of matrix instead of 234: two waves per SIMD
+// without column blocking.
 #pragma once
 #include "spkd_quad.hpp"
 
 namespace spkd {
-
-// columns held by slot s: 0 .. tri_cols(s) - 1
-__host__ __device__ constexpr int tri_cols(int s) { return QL * (s + 1); }
 
 // acc += bcast(src, lane T of the DPP row) * m as ONE instruction: gfx950 has the DPP
 // form of v_fmac_f64 for row_newbcast, which the compiler never selects (it emits a
@@ -64,7 +63,7 @@ template <int K, int J>
 struct TriCol {
     static __device__ __forceinline__ void run(QuadRows& q, const double (&l)[QS]) {
         if constexpr (J < D) {
-            constexpr int SJ = J / QL, TJ = J % QL;
+            constexpr int SJ = quad_slot(J), TJ = quad_lane_of(J);
             fmac_bcast16<TJ, SPKD_TRI_COLNOP != 0>(q.r[SJ][J], q.r[SJ][K], l[SJ]);
 #pragma unroll
             for (int s = SJ + 1; s < QS; ++s) fmac_bcast16<TJ, false>(q.r[s][J], q.r[SJ][K], l[s]);
@@ -117,7 +116,7 @@ struct DetAcc {
 
 template <int P, int OP>
 __device__ __forceinline__ void chain_op(QuadRows& q, PivotChain& ch, double (&ln)[QS], DetAcc& da, double piv_cur) {
-    constexpr int S = P / QL, T = P % QL;
+    constexpr int S = quad_slot(P), T = quad_lane_of(P);
     if constexpr (OP == 0) {
         // DPP read of a[P][P], written by the first FMA of column P of the running step: two
         // wait states are needed in between.  QS - 1 - S further FMAs of that column follow
@@ -163,7 +162,7 @@ struct TriColAhead {
     static __device__ __forceinline__ void run(QuadRows& q, const double (&l)[QS], PivotChain& ch, double (&ln)[QS],
                                                DetAcc& da, double piv_k) {
         if constexpr (J < D) {
-            constexpr int SJ = J / QL, TJ = J % QL;
+            constexpr int SJ = quad_slot(J), TJ = quad_lane_of(J);
             fmac_bcast16<TJ, false>(q.r[SJ][J], q.r[SJ][K], l[SJ]);
 #pragma unroll
             for (int s = SJ + 1; s < QS; ++s) fmac_bcast16<TJ, false>(q.r[s][J], q.r[SJ][K], l[s]);
@@ -184,7 +183,7 @@ struct TriColAhead {
 };
 
 // A hook runs between the steps of an elimination: after_step<K>() is called when step K is
-// complete, i.e. when column K of the matrix (13, 26 or 39 rows of it, by slot) is dead and
+// complete, i.e. when column K of the matrix (its rows in every slot) is dead and
 // its registers are free.  The library's kernels pass NoHook; tools/pair_bench.hip passes
 // PackedColumns (tools/packed_columns.hpp), which loads column K of the NEXT pass's record
 // into exactly those registers: a wave then never waits for a pass's record loads, they are
@@ -239,7 +238,7 @@ template <int J>
 struct TriRank1 {
     static __device__ __forceinline__ void run(QuadRows& q, const double (&c)[QS], const double (&v)[QS]) {
         if constexpr (J < D) {
-            constexpr int SJ = J / QL, TJ = J % QL;
+            constexpr int SJ = quad_slot(J), TJ = quad_lane_of(J);
             fmac_bcast16<TJ, true>(q.r[SJ][J], v[SJ], c[SJ]);
 #pragma unroll
             for (int s = SJ + 1; s < QS; ++s) fmac_bcast16<TJ, false>(q.r[s][J], v[SJ], c[s]);
@@ -270,7 +269,7 @@ __device__ __forceinline__ double tri_det(QuadRows& q, int m, int* err, FormSing
             if (m == mi) det = v;
         }
         // what the hook has loaded is loaded again: nothing of it has to survive the calls
-        // above (156 registers would, in scratch, with the stores on the fast path)
+        // above (138 registers would, in scratch, with the stores on the fast path)
         hook.redo();
     }
     return det;

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "quad_even.hpp"     // (archived prototype: the even 13/13/13 row split)
 #include "spkd_cluster.hpp"
 #include "spkd_blocked.hpp"
 #include "spkd_tri.hpp"

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "quad_even.hpp"     // (archived prototype: the even 13/13/13 row split)
 #include "spkd_device.hpp"
 #include "quad_square.hpp"
 using namespace spkd;

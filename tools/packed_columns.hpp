@@ -8,15 +8,14 @@ namespace spkd {
 
 // A hook for tri_det / tri_det_nopivot: the lower-triangle columns of a PACKED record (SPKD_REC doubles:
 // column j holds rows j .. 39 contiguously from pk_off(j), so the quad load of (slot s,
-// column j) is 13 consecutive doubles at pk_off(j) + 13 s - j + t; lanes of a diagonal block
-// that sit above the diagonal read the previous column's tail, inside the record, into
-// registers nobody reads) -> `dst`, column K after step K; the sums column (three more
+// column j) is 16 consecutive doubles at quad_pk_at(s, j) + t; lanes without a row read
+// inside the record, into registers nobody reads: spkd_quad.hpp) -> `dst`, column K after step K; the sums column (three more
 // doubles per lane) comes with column SUMS_AT, late enough to cost no register while the
 // matrix is still large and early enough to have landed when the elimination ends.
-// rt0 = record + t (t = min(lane in the DPP row, 12)), rt1 = rt0 + 512: the immediate offset
+// rt0 = record + t (t = quad_load_lane(lane in the DPP row)), rt1 = rt0 + 512: the immediate offset
 // of a global load spans 4 KB, so two bases reach the whole record.
 struct PackedColumns {
-    static constexpr int SUMS_AT = 2 * QL;
+    static constexpr int SUMS_AT = quad_base(2);
     const SPKD_GLOBAL double* rt0;
     const SPKD_GLOBAL double* rt1;
     QuadRows* dst;
@@ -31,18 +30,18 @@ struct PackedColumns {
     template <int J>
     __device__ __forceinline__ void column() {
 #pragma unroll
-        for (int s = J / QL; s < QS; ++s) {
-            const int e = pk_off(J) + QL * s - J;       // + t (in the base)
+        for (int s = quad_slot(J); s < QS; ++s) {
+            const int e = quad_pk_at(s, J);             // + t (in the base)
             dst->r[s][J] = e < 512 ? rt0[e] : rt1[e - 512];
         }
     }
-    // (39, c) for this lane's row c = 13 s + t of slot s: record[pk_off(c) + 39 - c]
+    // (39, c) for this lane's row c = quad_row(s, t) of slot s: record[pk_off(c) + 39 - c]
     __device__ __forceinline__ void sums_column() {
         int t = lane_id() & 15;
-        t = t < QL ? t : QL - 1;
+        t = quad_load_lane(t);
 #pragma unroll
         for (int s = 0; s < QS; ++s) {
-            const int c = QL * s + t;
+            const int c = quad_row(s, t);
             sums[s] = rt0[pk_off(c) + D - c - t];
         }
     }

@@ -6,6 +6,7 @@
 // each with the partner records L2-resident (n_rec = 387) and streaming from HBM
 // (n_rec = 40 000, every block a different window of 387 partners).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../speaker-diarization_amd/csrc -o pair_bench pair_bench.hip
+// The row split follows spkd_quad.hpp; the even split for comparison: add -DSPKD_QUAD_BASES=0,13,26
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -35,7 +36,7 @@ __global__ __launch_bounds__(512) void k_pairs(const double* __restrict__ qr, in
         // bare elimination, packed records, software-pipelined in registers: column K of the
         // NEXT record is loaded into the registers step K of this elimination has just freed
         int ta = L.t; asm volatile("" : "+v"(ta));
-        const int t12 = ta < QL ? ta : QL - 1;
+        const int t12 = quad_load_lane(ta);
         auto rec_of = [&](int base) -> const double* {
             int w = base + L.m;
             w = w < WINDOW ? w : WINDOW - 1;
@@ -87,15 +88,15 @@ __global__ __launch_bounds__(512) void k_pairs(const double* __restrict__ qr, in
             int ta = L.t; asm volatile("" : "+v"(ta));
             const double n = nA + P[REC - 1];
             const double f = 1.0 / (n - 1.0);
-            const int t12 = ta < QL ? ta : QL - 1;
+            const int t12 = quad_load_lane(ta);
             const double* rt[2];
             long long o1 = 512; asm volatile("" : "+v"(o1));
             rt[0] = P + t12; rt[1] = rt[0] + o1;
 #pragma unroll
             for (int s2 = 0; s2 < QS; ++s2) {
 #pragma unroll
-                for (int j = 0; j < tri_cols(s2); ++j) { const int e = pk_off(j) + QL * s2 - j; q.r[s2][j] = rt[e / 512][e % 512]; }
-                const int c = QL * s2 + t12;
+                for (int j = 0; j < tri_cols(s2); ++j) { const int e = quad_pk_at(s2, j); q.r[s2][j] = rt[e / 512][e % 512]; }
+                const int c = quad_row(s2, t12);
                 sv[s2] = P[pk_off(c) + D - c];
             }
             __builtin_amdgcn_sched_barrier(0);

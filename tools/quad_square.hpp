@@ -2,7 +2,7 @@
 // tools/lu_bench.hip and tools/blocked_bench.hip, which measure it against the
 // column-blocked and the symmetric forms.
 #pragma once
-#include "spkd_quad.hpp"
+#include "quad_even.hpp"
 
 namespace spkd {
 

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
+#include "quad_even.hpp"     // (archived prototype: the even 13/13/13 row split)
 #include "spkd_cluster.hpp"
 #include "spkd_tri.hpp"
 using namespace spkd;
