@@ -99,6 +99,7 @@ enum {
     SPKD_T_CALL = 0, SPKD_T_CHUNK_STATS, SPKD_T_REDUCE_SETS, SPKD_T_PAIR_TERMS,
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
+    SPKD_T_POST_STATS,
     SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
     SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK, SPKD_T_FB_POSTERIOR,
     SPKD_T_IDENT_SCORES, SPKD_T_IDENT_ASSIGN, SPKD_T_BW_ACCUMULATE,
@@ -789,6 +790,47 @@ spkd_status spkd_fb_posterior_batch(spkd_ctx *ctx, const float *d_scores, int64_
                                     const int64_t *h_tok_off, const int64_t *h_tok_frame,
                                     const int32_t *h_tok_word, float *d_post, double *h_conf,
                                     double *h_logz);
+
+/* spkd_post_stats: statistics records from frames weighted by their posteriors -- what turns the
+ * posteriors of spkd_fb_posterior_batch into speakers again (Baum-Welch retraining: every speaker of a
+ * file is trained on all frames of the file's turns, each weighted by the speaker's posterior there,
+ * instead of on the frames a decoded path gave it wholly).  PARITY: no reference counterpart;
+ * tests/reseg_soft_numpy.py restates it.
+ *
+ * In: the sequences, h_seq_model, h_seq_n_models and n_cols exactly as spkd_gauss_loglik takes them.
+ * d_post: the compact [sum len][n_cols] float32 array in that call's score layout, which is the layout
+ * spkd_fb_posterior_batch writes its d_post in.  Out: d_stats receives n_models records in the layout
+ * of spkd_set_stats: the packed upper triangle of the 40 x 40 augmented moment matrix, 820 doubles,
+ * the count at pk(39, 39), the last entry.
+ *
+ * The values, all in fp64.  For model m take every sequence q with
+ * h_seq_model[q] <= m < h_seq_model[q] + h_seq_n_models[q]; for every frame t of q let
+ * w = (double) d_post[row(q, t)][m - h_seq_model[q]]; the record adds w * x~ x~^T, x~ = (x, 1), x the
+ * float32 frame converted once.
+ *   A weight that is exactly 0 contributes nothing, whatever the frame holds: a frame that is not
+ *   finite under weight 0 leaves the record finite (the kernel passes such frames over).
+ *   Any other weight or frame that is not finite propagates; spkd_gauss_models then answers ok = 0
+ *   for that record.
+ *   Every record 0 .. n_models - 1 is written; a model no sequence covers gets zeros.
+ *   The model ranges of two sequences with models are either identical (the turns of one file) or
+ *   disjoint (different files); anything else is SPKD_EINVAL.
+ * This fixes values, not the order of the operations.  There are no float atomics: the bits of a
+ * record depend neither on the run nor on the grid nor on the other files of the call -- they are a
+ * function of the model's own sequences in the order the call lists them.
+ * Two launches: one workgroup per (chunk of SPKD_POST_CHUNK frames of a sequence, column) sums its
+ * frames, 820 FMAs a frame and column; then every model adds its workgroups' partial records in
+ * (sequence, chunk) order.  Device scratch held by the context: 6 560 bytes a workgroup.
+ * Limits and refusals are those of spkd_gauss_loglik: 1 <= n_cols <= 16, 0 <= n_models(q) <= n_cols;
+ * a range outside [0, n_frames] or with end < begin, a model index outside [0, n_models], a null
+ * pointer, a d_stats that is not 16-byte aligned: SPKD_EINVAL before any device work, d_stats
+ * untouched.  n_models = 0: SPKD_OK without a launch.  The index arrays go up in one copy through
+ * pinned memory the context owns.  Timer: SPKD_T_POST_STATS (all launches of the call). */
+#define SPKD_POST_CHUNK 1024
+spkd_status spkd_post_stats(spkd_ctx *ctx, const float *d_frames, int64_t n_frames,
+                            const float *d_post, int64_t n_seq,
+                            const int64_t *h_seq_begin, const int64_t *h_seq_end,
+                            const int32_t *h_seq_model, const int32_t *h_seq_n_models,
+                            int32_t n_cols, int64_t n_models, double *d_stats);
 
 /* ---------------------------------------------------------------------------
  * (9) Resegmentation with mixture models: a diagonal-covariance Gaussian mixture per speaker,

@@ -19,6 +19,7 @@
 #include "spkd_handoff.hpp"
 #include "spkd_merge.hpp"
 #include "spkd_stats.hpp"
+#include "spkd_post_stats.hpp"
 #include "spkd_mfcc.hpp"
 #include "spkd_mfcc_batch.hpp"
 #include "spkd_vad.hpp"
@@ -40,13 +41,13 @@ constexpr int N_SLOTS = 72;
 // spkd_mindur_viterbi_batch, so that neither call ends the other's); of the index arrays on their way up: spkd_sum_stats'
 // (PIN_SUM_IDX), the SeqTable of spkd_gauss_loglik (PIN_GAUSS_IDX) and of spkd_gmm_loglik_seq (PIN_GT_IDX), the
 // RangeTable of spkd_gmm_train (PIN_GT_TAB) and of spkd_ubm_stats (PIN_UBM_TAB), spkd_clr_link's ok flags (PIN_CLR_IN),
-// the FbTable of spkd_fb_posterior_batch (PIN_FB_TAB);
+// the FbTable of spkd_fb_posterior_batch (PIN_FB_TAB), the PostTable of spkd_post_stats (PIN_POST_TAB);
 // and of what comes down: spkd_gmm_train's ok flags and log-likelihoods (PIN_GT_OUT), spkd_ubm_stats' ok flags
 // (PIN_UBM_OUT), spkd_clr_link's merge log and statistics (PIN_CLR_OUT); spkd_clr_identify's flags and offsets on their
 // way up (PIN_ID_IN) and its decisions on their way down (PIN_ID_OUT), spkd_bw_accumulate's table (PIN_ACC_TAB)
 enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
        PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, PIN_MD_SEQS, PIN_MD_TOKENS,
-       PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, N_PIN };
+       PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, PIN_POST_TAB, N_PIN };
 }
 
 struct spkd_ctx {
@@ -275,7 +276,7 @@ enum {
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
     S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT,
     S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_FB_TAB, S_FB_FWD, S_FB_OUT,
-    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_COUNT
+    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -2592,6 +2593,93 @@ spkd_status spkd_gauss_loglik(spkd_ctx* c, const float* d_frames, int64_t n_fram
         hipLaunchKernelGGL(k_gauss_loglik, dim3((unsigned)t.nt), dim3(WAVE), 0, c->stream, d_frames, d_models, t.d.ok,
                            t.d.begin, t.d.end, t.d.row, t.d.tile, t.d.model, t.d.n_models, t.d.tile_seq, (int)n_cols,
                            d_scores);
+    }
+    HIPCHK(c, hipGetLastError());
+    return call.finish();
+}
+
+// ------------------------------------------------------------------ (8) speakers from posteriors
+static_assert(STATS_CHUNK == SPKD_POST_CHUNK, "the header states the kernel's chunk");
+
+namespace {
+// The work table of spkd_post_stats, as the kernels take it: per workgroup of k_post_chunk_stats its
+// chunk, column and partial record; per model the first of its partial records (k_reduce_sets' sets).
+// parts() is listed once and placed twice, as SeqTable's.
+struct PostTable {
+    struct Tab { PostItem* begin; long long* model_off; } h{}, d{};
+    size_t ni = 0, nm = 0, image = 0;
+
+    size_t parts(Layout L, Tab& t) const { return L.part(t.begin, ni).part(t.model_off, nm + 1).bytes(); }
+};
+}  // namespace
+
+spkd_status spkd_post_stats(spkd_ctx* c, const float* d_frames, int64_t n_frames, const float* d_post, int64_t n_seq,
+                            const int64_t* h_seq_begin, const int64_t* h_seq_end, const int32_t* h_seq_model,
+                            const int32_t* h_seq_n_models, int32_t n_cols, int64_t n_models, double* d_stats) {
+    if (!c) return SPKD_EINVAL;
+    if (n_cols < 1 || n_cols > GS_MAX_COLS) return fail(c, SPKD_EINVAL, "post_stats: 1 <= n_cols <= 16");
+    if (n_frames < 0 || n_seq < 0 || n_models < 0 || n_models > 0x7fffffff || n_seq > 0x7fffffff)
+        return fail(c, SPKD_EINVAL, "post_stats: bad count");
+    if (!d_stats || (n_seq > 0 && (!d_frames || !d_post || !h_seq_begin || !h_seq_end || !h_seq_model || !h_seq_n_models)))
+        return fail(c, SPKD_EINVAL, "post_stats: null argument");
+    if ((uintptr_t)d_stats % 16 || (uintptr_t)d_frames % 4 || (uintptr_t)d_post % 4)
+        return fail(c, SPKD_EINVAL, "post_stats: misaligned buffer (records: 16 bytes)");
+    // per model the range that covers it (first model, count; count 0: none yet) and its workgroups
+    std::vector<int32_t> cover((size_t)n_models * 2, 0);
+    std::vector<int64_t> count((size_t)n_models, 0);
+    int64_t n_items = 0;
+    for (int64_t q = 0; q < n_seq; ++q) {
+        const int64_t b = h_seq_begin[q], e = h_seq_end[q];
+        if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, "post_stats: sequence outside [0, n_frames]");
+        const int64_t m = h_seq_model[q], k = h_seq_n_models[q];
+        if (k < 0 || k > n_cols) return fail(c, SPKD_EINVAL, "post_stats: 0 <= models of a sequence <= n_cols");
+        if (m < 0 || m + k > n_models) return fail(c, SPKD_EINVAL, "post_stats: model index out of range");
+        const int64_t chunks = (e - b + STATS_CHUNK - 1) / STATS_CHUNK;
+        for (int64_t j = m; j < m + k; ++j) {
+            int32_t* cv = &cover[(size_t)j * 2];
+            if (cv[1] == 0) cv[0] = (int32_t)m, cv[1] = (int32_t)k;
+            else if (cv[0] != m || cv[1] != k)
+                return fail(c, SPKD_EINVAL, "post_stats: the model ranges of two sequences are identical or disjoint");
+            count[(size_t)j] += chunks;
+        }
+        n_items += chunks * k;
+    }
+    if (n_items > 0x7fffffff) return fail(c, SPKD_EINVAL, "post_stats: too many frames in one call");
+    if (n_models == 0) return SPKD_OK;
+    PostTable t;
+    t.ni = (size_t)n_items, t.nm = (size_t)n_models;
+    TRY(carve(c, pinned, PIN_POST_TAB, [&](Layout L) { return t.image = t.parts(L, t.h); }));
+    t.h.model_off[0] = 0;
+    for (size_t j = 0; j < t.nm; ++j) t.h.model_off[j + 1] = t.h.model_off[j] + count[j];
+    // a model's partial records: consecutive, in the order (sequence of the call, chunk); `count` turns cursor
+    for (size_t j = 0; j < t.nm; ++j) count[j] = t.h.model_off[j];
+    PostItem* it = t.h.begin;
+    int64_t row = 0;
+    for (int64_t q = 0; q < n_seq; ++q) {
+        const int64_t b = h_seq_begin[q], e = h_seq_end[q];
+        const int32_t m = h_seq_model[q], k = h_seq_n_models[q];
+        for (int64_t f = b; f < e; f += STATS_CHUNK)
+            for (int32_t col = 0; col < k; ++col, ++it) {
+                it->begin = f;
+                it->row = row + (f - b);
+                it->slot = count[(size_t)(m + col)]++;
+                it->len = (int32_t)std::min<int64_t>(STATS_CHUNK, e - f);
+                it->col = col;
+            }
+        row += e - b;
+    }
+    Call call(c);
+    TRY(call.opened);
+    TRY(send_table(c, S_POST_TAB, t));
+    void* d_partial = nullptr;
+    TRY(scratch(c, S_POST_PARTIAL, t.ni * REC * sizeof(double), &d_partial));
+    {
+        Timer tm(c, SPKD_T_POST_STATS);
+        if (t.ni)
+            hipLaunchKernelGGL(k_post_chunk_stats, dim3((unsigned)t.ni), dim3(STATS_TPB), 0, c->stream, d_frames, d_post,
+                               (const PostItem*)t.d.begin, (int)n_cols, (double*)d_partial);
+        hipLaunchKernelGGL(k_reduce_sets, dim3((unsigned)n_models), dim3(STATS_TPB), 0, c->stream,
+                           (const double*)d_partial, (const int64_t*)t.d.model_off, d_stats);
     }
     HIPCHK(c, hipGetLastError());
     return call.finish();

@@ -42,10 +42,23 @@ constexpr int STATS_ENTRIES = (REC + STATS_TPB - 1) / STATS_TPB;   // record ent
 // The body, for the workgroup's STATS_TPB threads: the moment sums of the `len` >= 1 frames from
 // `begin` on; thread tid gets entry e = tid + k * STATS_TPB of the packed record as emit(k, e, v),
 // k < STATS_ENTRIES.  xs / part: the workgroup's LDS; a second call may follow behind a barrier.
-template <class Emit>
+//
+// wt weighs the frames (spkd_post_stats.hpp); UnitWeight, an empty object, is weight 1 for all:
+//   wt.issue(t0, tl)   with the tile's global loads: fetch the weights of the tl frames from t0 on;
+//   wt.stage()         with the tile's LDS stores, ahead of the barrier: hand them to the workgroup;
+//   wt.skip(f)         frame f of the staged tile takes no part (asked before its values are read);
+//   wt.scale(f, xi)    xi *= w_f, ahead of the 16 FMAs.
+struct UnitWeight {
+    __device__ __forceinline__ void issue(int, int) {}
+    __device__ __forceinline__ void stage() {}
+    __device__ __forceinline__ bool skip(int) const { return false; }
+    __device__ __forceinline__ void scale(int, double (&)[SB]) const {}
+};
+
+template <class Emit, class Weight = UnitWeight>
 __device__ __forceinline__ void chunk_stats_accumulate(
         const float* __restrict__ frames, int64_t begin, int len,
-        double (&xs)[STATS_TILE][DA], double (&part)[STATS_WAVES][SBLOCKS][SB * SB], Emit emit) {
+        double (&xs)[STATS_TILE][DA], double (&part)[STATS_WAVES][SBLOCKS][SB * SB], Emit emit, Weight wt = Weight()) {
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid >> 6;
     // lane -> block (bi <= bj)
     int bi = 0, rem = lane < SBLOCKS ? lane : 0;
@@ -76,6 +89,7 @@ __device__ __forceinline__ void chunk_stats_accumulate(
             const int idx = tid + STATS_TPB * k;
             pf[k] = idx < tl * D ? src[idx] : 0.0f;
         }
+        wt.issue(t0, tl);
     };
     issue(0);
     double* xsf = &xs[0][0];
@@ -85,12 +99,15 @@ __device__ __forceinline__ void chunk_stats_accumulate(
         for (int k = 0; k < PF; ++k)
             if (tid + STATS_TPB * k < STATS_TILE * D) xsf[loff[k]] = (double)pf[k];
         if (tid < STATS_TILE) xs[tid][D] = 1.0;
+        wt.stage();
         __syncthreads();
         if (t0 + STATS_TILE < len) issue(t0 + STATS_TILE);
         for (int f = wave; f < tl; f += STATS_WAVES) {
+            if (wt.skip(f)) continue;
             double xi[SB], xj[SB];
 #pragma unroll
             for (int a = 0; a < SB; ++a) { xi[a] = xs[f][SB * bi + a]; xj[a] = xs[f][SB * bj + a]; }
+            wt.scale(f, xi);
 #pragma unroll
             for (int a = 0; a < SB; ++a)
 #pragma unroll

@@ -17,6 +17,7 @@ MERGE_NO_AHEAD = 1
 TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pair_terms',
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
+                                        'post_stats',
                                         'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
                                         'mindur_viterbi', 'mindur_backtrack', 'fb_posterior',
                                         'ident_scores', 'ident_assign', 'bw_accumulate',
@@ -24,6 +25,7 @@ TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pai
 VAD_TILE = 32       # SPKD_VAD_TILE: frames per score / back-pointer tile of k_vad_viterbi
 MINDUR_TILE = 32    # SPKD_MINDUR_TILE: frames per score / record tile of k_mindur_viterbi
 FB_TILE = 32        # SPKD_FB_TILE: frames per score tile and per stored forward vector of k_fb_posterior
+POST_CHUNK = 1024   # SPKD_POST_CHUNK: frames per workgroup of k_post_chunk_stats
 GAUSS_TILE = 64     # SPKD_GAUSS_TILE: frames per workgroup of k_gauss_loglik
 GAUSS_MODEL = 820   # SPKD_GAUSS_MODEL: doubles per model (mu[39], W = L^-1 packed lower [780], c)
 GMM_COMP = 80       # SPKD_GMM_COMP: doubles per mixture component (ln w, mean[39], 1 / var[39], log_norm)
@@ -45,7 +47,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
            'spkd_gauss_models', 'spkd_gauss_loglik', 'spkd_gmm_train', 'spkd_gmm_loglik_seq',
            'spkd_ubm_stats', 'spkd_clr_link', 'spkd_mindur_viterbi_batch', 'spkd_fb_posterior_batch',
-           'spkd_clr_identify', 'spkd_bw_accumulate']
+           'spkd_clr_identify', 'spkd_bw_accumulate', 'spkd_post_stats']
 
 
 class CdParams(C.Structure):
@@ -224,6 +226,7 @@ def load_library(path=None):
     lib.spkd_fb_posterior_batch.argtypes = [vp, vp, i64, vp, i32, dbl, dbl, vp, vp, vp, vp, vp, vp, vp]
     lib.spkd_gauss_models.argtypes = [vp, vp, i64, vp, vp]
     lib.spkd_gauss_loglik.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i32, vp]
+    lib.spkd_post_stats.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, i32, i64, vp]
     lib.spkd_gmm_train.argtypes = [vp, vp, i64, i64, vp, vp, vp, i32, i32, i32, dbl, vp, vp, vp]
     lib.spkd_gmm_loglik_seq.argtypes = [vp, vp, i64, vp, i32, i64, vp, i64, vp, vp, vp, vp, i32, vp]
     lib.spkd_ubm_stats.argtypes = [vp, vp, i64, vp, i32, i64, vp, vp, vp, vp, vp]
@@ -883,6 +886,30 @@ class Context(object):
                                                     float(scale), p(ncol), p(tok[0]), p(tok[1]), p(tok[2]),
                                                     C.c_void_p(d_post) if d_post else None, p(conf), _ptr(logz)))
         return conf, logz
+
+    def post_stats(self, d_frames, n_frames, d_post, seq_begin, seq_end, seq_model, seq_n_models, n_cols, n_models, d_stats,
+                   masses=True):
+        """Posterior-weighted statistics records (spkd_post_stats): record m of d_stats (n_models records
+        as set_stats leaves them) is the sum, over every frame of the sequences whose models
+        seq_model[q] .. + seq_n_models[q] - 1 include m, of d_post[row, m - seq_model[q]] * [x; 1] [x; 1]^T.
+        The sequences and n_cols are gauss_loglik's; d_post is the compact device array [sum len, n_cols]
+        float32 in that call's score layout, as fb_posterior_batch writes it.  A weight of exactly 0 adds
+        nothing whatever the frame holds; a model no sequence covers gets zeros.  Returns the records'
+        count entries, float64 [n_models]: each model's expected number of frames (the records come down
+        for it, 6 560 bytes each; masses=False: no copy, None).  The kernels' time is last_ms('post_stats')."""
+        c = np.ascontiguousarray
+        b, e = c(seq_begin, dtype=np.int64), c(seq_end, dtype=np.int64)
+        m, k = c(seq_model, dtype=np.int32), c(seq_n_models, dtype=np.int32)
+        if any(a.ndim != 1 for a in (b, e, m, k)) or not (len(b) == len(e) == len(m) == len(k)):
+            raise SpkdError(SPKD_EINVAL, 'one begin, end, first model and model count per sequence')
+        self.check(self.lib.spkd_post_stats(self.h, C.c_void_p(d_frames), int(n_frames), C.c_void_p(d_post), len(b), _ptr(b),
+                                            _ptr(e), _ptr(m), _ptr(k), int(n_cols), int(n_models), C.c_void_p(d_stats)))
+        if not masses:
+            return None
+        rec = np.empty((int(n_models), REC), dtype=np.float64)
+        if rec.size:
+            self.d2h(rec, d_stats)
+        return rec[:, REC - 1].copy()
 
     # ---- (9) resegmentation with mixture models
     def gmm_train(self, d_frames, n_frames, set_off, range_begin, range_end, n_comp, n_iter, var_floor, d_gmm,

@@ -57,7 +57,16 @@ RESEG_MD = dict(penalty=50.0, min_dur_s=1.0)
 # calibrated; speech, whose frames are correlated in time, will want a scale below 1 -- none exists here, so the
 # default is unmeasured.
 RESEG_CONF = dict(penalty=50.0, confidence=True)
-FB_MAX_SCALED_PENALTY = 600.0    # conf_scale * penalty: the limit of spkd_fb_posterior_batch
+FB_MAX_SCALED_PENALTY = 600.0    # conf_scale * penalty, soft_scale * penalty: the limit of spkd_fb_posterior_batch
+# the same stage with soft retraining between the passes (spkd_post_stats): every speaker is trained again on
+# all frames of its file's turns, each weighted by the speaker's posterior there at the acoustic scale
+# soft_scale, instead of on the frames the decoded path gave it wholly.  Any reseg dictionary with Gaussian
+# speakers may carry soft=True.  The default soft_scale of 0.1 rests on the synthetic generator and nothing
+# else: there soft at 0.1 was never worse than hard and often much better, at 1 it equals hard (the posteriors
+# of 39-dimensional Gaussians are almost one-hot), and at 0.05 a speaker bleeds its mass away and the file
+# collapses (DESIGN.md has the table).  On speech it is unmeasured, like conf_scale and the linking thresholds.
+RESEG_SOFT = dict(penalty=50.0, passes=5, soft=True)
+RESEG_SOFT_SCALE = 0.1
 
 
 class BatchFile(object):
@@ -874,6 +883,24 @@ def _reseg_confidence(reseg, detail):
     return bool(on), scale
 
 
+def _reseg_soft(reseg, model):
+    """(soft retraining asked for, soft_scale) of a `reseg` dictionary whose model is `model` (_reseg_model)."""
+    on = reseg.get('soft', False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError('reseg soft: True or False')
+    try:
+        scale = float(reseg.get('soft_scale', RESEG_SOFT_SCALE))
+    except (TypeError, ValueError):
+        scale = float('nan')
+    if not np.isfinite(scale) or scale <= 0.0:
+        raise ValueError('reseg soft_scale: a finite number > 0 (an acoustic scale on the path log-weights)')
+    if on and not scale * float(reseg['penalty']) <= FB_MAX_SCALED_PENALTY:
+        raise ValueError('reseg soft_scale * penalty: at most %g' % FB_MAX_SCALED_PENALTY)
+    if on and model[0] == 'gmm':
+        raise ValueError('reseg soft: the Gaussian speakers only (weighted mixture training is not there), not model gmm')
+    return bool(on), scale
+
+
 def _no_confidence(detail, n_files):
     detail['confidence'] = [np.zeros(0) for _ in range(n_files)]
     detail['log_evidence'] = [np.zeros(0) for _ in range(n_files)]
@@ -973,13 +1000,31 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     posterior is that of the plain switch-penalty loop also under min_dur_s: the minimum duration
     shapes the rows, not the distribution they are weighed in.  timings: reseg_posterior.  A
     confidence that is not a bool, a conf_scale that is not a finite number > 0, conf_scale * penalty
-    above 600, confidence without a detail dictionary: ValueError before any device work."""
+    above 600, confidence without a detail dictionary: ValueError before any device work.
+    reseg['soft'] = True (RESEG_SOFT; Gaussian speakers, either decoder, any passes): Baum-Welch
+    retraining.  Pass 1 is unchanged.  After every decode that is neither the last nor a repeat of the
+    one before, the next speakers are trained on posteriors instead of tokens: one
+    spkd_fb_posterior_batch on that pass's scores (no tokens, every turn's speaker count, the penalty,
+    the acoustic scale reseg['soft_scale'], default 0.1) writes every frame's posteriors, one
+    spkd_post_stats turns them and the frames into the speakers' records -- every speaker takes every
+    frame of its file's turns, weighted by its posterior there -- and spkd_gauss_models follows as
+    above.  The early stop and passes_run keep their meaning.  Under min_dur_s the posterior is that of
+    the plain loop, as for the confidences; confidence=True still runs its own final call at
+    conf_scale.  detail['soft_mass']: per retraining the float64 array [speakers] (link_speakers'
+    order) of the records' count entries, each speaker's expected number of frames: a speaker that is
+    bleeding away shows there.  timings: reseg_soft_posterior and reseg_soft_stats, one entry per
+    retraining.  The default scale comes from the synthetic generator only and is unmeasured on speech;
+    a scale that is too small lets a speaker lose its mass and the file collapse (RESEG_SOFT above).
+    Without soft, or with soft=False, the calls and the rows are those described above, to the byte.
+    A soft that is not a bool, a soft_scale that is not a finite number > 0, soft_scale * penalty above
+    600, soft with model gmm: ValueError before any device work."""
     rate = float(rate)
     penalty = _reseg_penalty(reseg)
     model = _reseg_model(reseg)
     min_frames = _reseg_min_frames(reseg, rate)
     passes = _reseg_passes(reseg)
     want_conf, conf_scale = _reseg_confidence(reseg, detail)
+    soft, soft_scale = _reseg_soft(reseg, model)
     if model[0] == 'gmm':
         if segments is None:
             raise ValueError('reseg model gmm trains on the frames: it takes segments, the arrays cluster_batch took')
@@ -1002,6 +1047,8 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
         detail['passes_run'] = 0
         if want_conf:
             _no_confidence(detail, n_files)
+        if soft:
+            detail['soft_mass'] = []
     table = _turn_table(files, rate)
     if table is None or len(spk_file) == 0:
         return out
@@ -1015,6 +1062,7 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     spk_base[1:] = np.cumsum(n_spk_file)
     spk_first, spk_count = spk_base[owner], n_spk_file[owner]
     d_spk = d_models = d_scores = None      # device buffers: pass 1 allocates each where it first needs it
+    frame_off = None                        # of the scores in d_scores: the pass before, while the next trains
 
     def clock(key, which):
         if timings is not None:
@@ -1057,6 +1105,17 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
                 d_spk = ctx.dev_scratch('reseg_speaker_stats', n_spk * hipabi.REC * 8)
                 ctx.sum_stats(d_stats, int(seg_off[-1]), member, set_off, d_spk)
                 d_models = ctx.dev_scratch('reseg_models', n_spk * hipabi.GAUSS_MODEL * 8)
+            elif soft:
+                # (d_scores and frame_off are still those of the decode that gave `tokens`)
+                d_post = ctx.dev_scratch('reseg_post', max(int(frame_off[-1]), 1) * n_cols * 4)
+                ctx.fb_posterior_batch(d_scores, frame_off, n_cols, penalty, seq_n_cols=spk_count, scale=soft_scale,
+                                       d_post=d_post)
+                clock('reseg_soft_posterior', 'fb_posterior')
+                mass = ctx.post_stats(d_frames, total_frames, d_post, tb, te, spk_first, spk_count, n_cols, n_spk, d_spk,
+                                      masses=detail is not None)
+                clock('reseg_soft_stats', 'post_stats')
+                if detail is not None:
+                    detail['soft_mass'].append(np.asarray(mass, dtype=np.float64))
             else:
                 rb, re_, spk = _token_ranges(*tokens, tb, te, spk_first)
                 order = np.argsort(spk, kind='stable')                     # (spkd_set_stats takes ascending sets)
@@ -1208,7 +1267,9 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     decoded rows and decodes again; both keys go to resegment_batch as they are
     (detail['passes_run'] as there).  A dictionary like RESEG_CONF adds a confidence to every row
     (reseg['confidence'], reseg['conf_scale']; detail['confidence'] and detail['log_evidence'] as there):
-    it takes a detail dictionary.  With link the confidences stay those of the file's own speakers."""
+    it takes a detail dictionary.  With link the confidences stay those of the file's own speakers.
+    A dictionary like RESEG_SOFT retrains the speakers between the passes on frame posteriors instead of
+    decoded rows (reseg['soft'], reseg['soft_scale']; detail['soft_mass'] as there)."""
     method = _method(cl)
     if reseg is not None:
         _reseg_penalty(reseg)
@@ -1216,6 +1277,7 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
         _reseg_min_frames(reseg, rate)
         _reseg_passes(reseg)
         _reseg_confidence(reseg, detail)
+        _reseg_soft(reseg, _reseg_model(reseg))
         if handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi'):
             raise ValueError('reseg takes the host hand-off')
     if _cd_method(cd) in ('sw', 'm'):
@@ -1248,6 +1310,8 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
             detail['passes_run'] = 0
             if reseg.get('confidence', False):
                 _no_confidence(detail, len(files))
+            if reseg.get('soft', False):
+                detail['soft_mass'] = []
         return [np.zeros((0, 3)) for _ in files]
     return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail, reseg,
                               text_contract)
