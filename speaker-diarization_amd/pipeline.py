@@ -17,7 +17,11 @@ import numpy as np
 
 from . import gallery as _gallery
 from . import hipabi
+from . import resegmentation as _resegmentation
 from .recipe import py2_float_str
+# the resegmentation stage (resegmentation.py): its settings and its entry point under their names here
+from .resegmentation import (FB_MAX_SCALED_PENALTY, RESEG, RESEG_CONF, RESEG_GMM, RESEG_MAX_SPEAKERS, RESEG_MD,
+                             RESEG_SOFT, RESEG_SOFT_SCALE, resegment_batch)
 
 DIA2_CD = dict(kind='BIC', lambdac=1.0, threshold=0.0, winsize_s=1.0, winstep_s=3.0, deltaws_s=0.1)
 DIA2_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
@@ -35,38 +39,6 @@ LINK_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
 # threshold rests on ONE synthetic fixture (tests/test_link_clr.py), not on speech: tune it on real audio.
 LINK_CLR = dict(model='clr', components=8, iterations=5, var_floor=0.01, relevance=16.0,
                 threshold=-0.5, max_spk=0, ubm_max_frames=2_000_000)
-# Viterbi resegmentation (resegment_batch): the cost of a speaker switch inside a turn, in natural-log
-# units.  On the synthetic generator every value from 10 to 200 decodes the same paths; real audio,
-# whose frames are correlated in time, will want it tuned.
-RESEG = dict(penalty=50.0)
-RESEG_MAX_SPEAKERS = 16          # of one file: the decoder's word limit (spkd_vad_viterbi_batch)
-# the same stage under mixture models: a diagonal-covariance GMM per speaker, trained on the device
-# (spkd_gmm_train) from the frames of the speaker's segments.  Settings, not measurements: four
-# components and five EM steps are what small per-speaker mixtures usually get; the floor is a share
-# of the variance of all the speaker's frames.
-RESEG_GMM = dict(penalty=50.0, model='gmm', components=4, iterations=5, var_floor=0.01)
-# the same stage with a minimum speaker duration in the decoder (spkd_mindur_viterbi_batch): no row shorter
-# than min_dur_s unless it is a whole turn.  A setting, not a measurement: 1.0 s is the detector's own
-# smallest window (DIA2_CD['winsize_s']), and neither it nor the penalty beside it has been tuned on anything
-# but the synthetic generator.  Any reseg dictionary may also carry passes=N (default 1): the speakers are
-# retrained on the decoded rows and the turns decoded again, up to N decodes.
-RESEG_MD = dict(penalty=50.0, min_dur_s=1.0)
-# the same stage with a confidence for every row (spkd_fb_posterior_batch): the mean posterior of the row's
-# speaker over its frames, under the switch-penalty loop at the acoustic scale conf_scale (default 1.0).  Any
-# reseg dictionary may carry confidence=True.  On the generator's independent frames scale 1 is roughly
-# calibrated; speech, whose frames are correlated in time, will want a scale below 1 -- none exists here, so the
-# default is unmeasured.
-RESEG_CONF = dict(penalty=50.0, confidence=True)
-FB_MAX_SCALED_PENALTY = 600.0    # conf_scale * penalty, soft_scale * penalty: the limit of spkd_fb_posterior_batch
-# the same stage with soft retraining between the passes (spkd_post_stats): every speaker is trained again on
-# all frames of its file's turns, each weighted by the speaker's posterior there at the acoustic scale
-# soft_scale, instead of on the frames the decoded path gave it wholly.  Any reseg dictionary with Gaussian
-# speakers may carry soft=True.  The default soft_scale of 0.1 rests on the synthetic generator and nothing
-# else: there soft at 0.1 was never worse than hard and often much better, at 1 it equals hard (the posteriors
-# of 39-dimensional Gaussians are almost one-hot), and at 0.05 a speaker bleeds its mass away and the file
-# collapses (DESIGN.md has the table).  On speech it is unmeasured, like conf_scale and the linking thresholds.
-RESEG_SOFT = dict(penalty=50.0, passes=5, soft=True)
-RESEG_SOFT_SCALE = 0.1
 
 
 class BatchFile(object):
@@ -814,365 +786,6 @@ def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None, d_fram
     return maps, merges, float(r['stat_max'][0]), float(r['stat_min'][0])
 
 
-def _reseg_penalty(reseg):
-    p = float(reseg['penalty'])
-    if not np.isfinite(p) or p < 0.0:
-        raise ValueError('reseg penalty: a finite number >= 0 (natural-log units)')
-    return p
-
-
-def _reseg_model(reseg):
-    """The speaker model of a `reseg` dictionary: ('gauss',) -- also when the key is absent -- or
-    ('gmm', components, iterations, var_floor), the keys RESEG_GMM names (its values where one is
-    absent)."""
-    m = reseg.get('model', 'gauss')
-    if m == 'gauss':
-        return ('gauss',)
-    if m != 'gmm':
-        raise ValueError('reseg model: gauss or gmm')
-    k = reseg.get('components', RESEG_GMM['components'])
-    it = reseg.get('iterations', RESEG_GMM['iterations'])
-    fl = float(reseg.get('var_floor', RESEG_GMM['var_floor']))
-    if int(k) != k or not 1 <= k <= hipabi.GMM_MAX_COMP:
-        raise ValueError('reseg components: 1 .. %d' % hipabi.GMM_MAX_COMP)
-    if int(it) != it or it < 0:
-        raise ValueError('reseg iterations: an integer >= 0')
-    if not np.isfinite(fl) or fl < 0.0:
-        raise ValueError('reseg var_floor: a finite number >= 0 (a share of the variance of all the speaker\'s frames)')
-    return ('gmm', int(k), int(it), fl)
-
-
-def _reseg_min_frames(reseg, rate):
-    """D of a `reseg` dictionary, in frames: 0 when min_dur_s is absent or 0 -- the plain decoder --
-    otherwise max(1, floor(min_dur_s * rate))."""
-    try:
-        s = float(reseg.get('min_dur_s', 0.0))
-    except (TypeError, ValueError):
-        s = float('nan')
-    if not np.isfinite(s) or s < 0.0:
-        raise ValueError('reseg min_dur_s: a finite number >= 0 (seconds; 0: no minimum duration)')
-    return max(1, int(np.floor(s * float(rate)))) if s > 0.0 else 0
-
-
-def _reseg_passes(reseg):
-    n = reseg.get('passes', 1)
-    try:
-        whole = not isinstance(n, bool) and int(n) == n
-    except (TypeError, ValueError, OverflowError):
-        whole = False
-    if not whole or n < 1:
-        raise ValueError('reseg passes: an integer >= 1')
-    return int(n)
-
-
-def _reseg_confidence(reseg, detail):
-    """(confidence asked for, conf_scale) of a `reseg` dictionary; `detail` is where the confidences go."""
-    on = reseg.get('confidence', False)
-    if not isinstance(on, (bool, np.bool_)):
-        raise ValueError('reseg confidence: True or False')
-    try:
-        scale = float(reseg.get('conf_scale', 1.0))
-    except (TypeError, ValueError):
-        scale = float('nan')
-    if not np.isfinite(scale) or scale <= 0.0:
-        raise ValueError('reseg conf_scale: a finite number > 0 (an acoustic scale on the path log-weights)')
-    if on and not scale * float(reseg['penalty']) <= FB_MAX_SCALED_PENALTY:
-        raise ValueError('reseg conf_scale * penalty: at most %g' % FB_MAX_SCALED_PENALTY)
-    if on and detail is None:
-        raise ValueError('reseg confidence: the confidences come back in detail, which takes a dictionary')
-    return bool(on), scale
-
-
-def _reseg_soft(reseg, model):
-    """(soft retraining asked for, soft_scale) of a `reseg` dictionary whose model is `model` (_reseg_model)."""
-    on = reseg.get('soft', False)
-    if not isinstance(on, (bool, np.bool_)):
-        raise ValueError('reseg soft: True or False')
-    try:
-        scale = float(reseg.get('soft_scale', RESEG_SOFT_SCALE))
-    except (TypeError, ValueError):
-        scale = float('nan')
-    if not np.isfinite(scale) or scale <= 0.0:
-        raise ValueError('reseg soft_scale: a finite number > 0 (an acoustic scale on the path log-weights)')
-    if on and not scale * float(reseg['penalty']) <= FB_MAX_SCALED_PENALTY:
-        raise ValueError('reseg soft_scale * penalty: at most %g' % FB_MAX_SCALED_PENALTY)
-    if on and model[0] == 'gmm':
-        raise ValueError('reseg soft: the Gaussian speakers only (weighted mixture training is not there), not model gmm')
-    return bool(on), scale
-
-
-def _no_confidence(detail, n_files):
-    detail['confidence'] = [np.zeros(0) for _ in range(n_files)]
-    detail['log_evidence'] = [np.zeros(0) for _ in range(n_files)]
-
-
-def _token_spans(tok_off, offset, turn_begin, turn_end):
-    """Token k of turn q opens at turn_begin[q] + offset[k] and ends where the next one opens, a turn's
-    last token at turn_end[q].  -> (the turn of every token, begin, end)."""
-    n = np.diff(tok_off)
-    turn = np.repeat(np.arange(len(n)), n)
-    begin = turn_begin[turn] + offset
-    end = np.empty_like(begin)
-    end[:-1] = begin[1:]
-    last = tok_off[1:][n > 0] - 1
-    end[last] = turn_end[turn[last]]
-    return turn, begin, end
-
-
-def _token_ranges(tok_off, tok_frame, tok_word, tb, te, first_speaker):
-    """The decoded tokens as absolute frame ranges with their speakers, in turn order: token k of turn q
-    is [tb[q] + f_k, tb[q] + f_{k+1}), a turn's last token ends at te[q]; its speaker is
-    first_speaker[q] + word.  -> (begin, end, speaker)."""
-    turn, b, e = _token_spans(tok_off, tok_frame, tb, te)
-    return b, e, first_speaker[turn] + tok_word
-
-
-def _reseg_rows(tok_off, tok_frame, tok_word, turn_start_s, turn_end_s, turn_labels, rate, text_contract):
-    """The rows of a decoded batch of turns, in turn order: token k of a turn, opening at the
-    relative frame f_k, is [turn_start_s + f_k / rate, turn_start_s + f_{k+1} / rate, label]; a turn's
-    first row starts at the turn's own start (f_0 = 0) and its last row ends at the turn's own end
-    as the VAD states it (the convention of spkd_gw_lines' tail line).  turn_labels[q][w]: the label
-    of word w in turn q.  Returns (rows [n_tokens, 3], the turn of every row)."""
-    turn, t0, t1 = _token_spans(tok_off, tok_frame / rate, turn_start_s, turn_end_s)
-    times = np.column_stack([t0, t1])
-    if text_contract:
-        times = hipabi.py2_roundtrip(times.ravel()).reshape(-1, 2)
-    return np.column_stack([times, turn_labels[turn, tok_word].astype(np.float64)]), turn
-
-
-def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels, rate=125.0, reseg=RESEG,
-                    text_contract=True, timings=None, detail=None, segments=None):
-    """Viterbi resegmentation of a clustered batch on the device: the closing pass of a BIC
-    segmentation + agglomerative clustering system (the reference has none).  d_stats, seg_off,
-    labels: the segment records, the files' offsets and the per-file labels of a cluster_batch
-    (its stats_out and results).  The speakers are link_speakers' -- file by file, by ascending
-    label -- their records the sums of their segments' (spkd_sum_stats), their models one
-    full-covariance Gaussian each (spkd_gauss_models).  Every VAD turn (_turn_table) of a file with
-    speakers is one sequence: one spkd_gauss_loglik scores all its frames under the file's speakers,
-    one spkd_vad_viterbi_batch decodes the best speaker sequence with reseg['penalty'] taken off at
-    every switch (stay = exit = 0, enter = -penalty; staying wins ties, so consecutive rows of a
-    turn differ in speaker).  Returns per file the rows [start_s, end_s, label] that tile its turns
-    (_reseg_rows; times through the 12-digit round trip with text_contract), label the file's own
-    cluster label; a file with no segments or no turns gives np.zeros((0, 3)), a turn with no
-    frames no rows.
-    A speaker whose record cannot be modelled (fewer than 40 frames, a covariance without positive
-    pivots) scores -inf and is never chosen; when that is every speaker of a turn the decoder's
-    all--inf rule applies and the file's lowest label takes the turn.  detail: a dict; receives
-    dropped = [(file, label)] of those speakers.  More than 16 speakers in one file, a negative or
-    non-finite penalty: ValueError before any device work.  timings: reseg_models, reseg_loglik,
-    reseg_viterbi, reseg_backtrack (kernel ms).
-    reseg['model'] = 'gmm' (RESEG_GMM): every speaker is a diagonal-covariance mixture of
-    reseg['components'] Gaussians instead, trained on the device by reseg['iterations'] EM steps from
-    a segmental start (spkd_gmm_train; variances floored at reseg['var_floor'] times the variance of
-    all the speaker's frames) on the frame ranges of its segments, in segment order.  segments: per
-    file the (start_s, end_s) arrays cluster_batch took -- the ranges are the ones segment_stats
-    summed (_segment_ranges); d_stats is not read.  The turns are scored by spkd_gmm_loglik_seq and
-    decoded by the same call.  A speaker of fewer than 40 frames a component, or of constant or
-    non-finite frames, is dropped as above.  detail['loglik']: per speaker (link_speakers' order) the
-    log-likelihood of its frames under the model entering each iteration.  timings: reseg_gmm_train
-    instead of reseg_models; reseg_loglik is the mixture scorer's.  An unknown model, components
-    outside 1 .. 8, negative iterations, a negative or non-finite floor, no segments: ValueError
-    before any device work.
-    reseg['min_dur_s'] > 0 (RESEG_MD): the turns are decoded by spkd_mindur_viterbi_batch instead, on the
-    same scores, with D = max(1, floor(min_dur_s * rate)) frames: every row lasts at least D frames or
-    is a whole turn.  Absent or 0: the call above, unchanged.  timings: reseg_viterbi and
-    reseg_backtrack are then that decoder's kernels.
-    reseg['passes'] = N (an integer >= 1, default 1; either model, with or without min_dur_s): after
-    every decode but the last the speakers are trained again, on the decoded tokens -- token k of turn
-    q is the absolute range [tb_q + f_k, tb_q + f_{k+1}), a turn's last token ends with the turn, its
-    speaker is the file's word-th; the ranges go in turn order, grouped by speaker by a stable sort.
-    'gauss': the records straight from those frames (spkd_set_stats), then spkd_gauss_models; 'gmm':
-    spkd_gmm_train on them with the same components, iterations and floor, from a fresh segmental
-    start (`segments` serves pass 1 only).  Then the turns are scored and decoded as in pass 1.  A
-    speaker that holds no frame any more, or whose new model is not ok, scores -inf from then on;
-    detail['dropped'] (and detail['loglik']) are those of the last pass run.  The loop stops early
-    when a pass decodes exactly the tokens of the pass before it; detail['passes_run'] is the number
-    of decodes done (0 when there was nothing to decode).  timings: the reseg lists get one entry per
-    pass.  A min_dur_s that is negative or not finite, passes that is not an integer >= 1: ValueError
-    before any device work.
-    reseg['confidence'] = True (RESEG_CONF; either model, either decoder, any passes): after the last
-    decode one spkd_fb_posterior_batch runs on the last pass's scores with the final tokens, every
-    turn's speaker count and the penalty, at the acoustic scale reseg['conf_scale'] (default 1.0).  The
-    rows are those of the call without it, to the byte.  detail['confidence']: per file a float64
-    array aligned with the file's rows, the mean posterior of the row's speaker over the row's frames;
-    detail['log_evidence']: per file the log-evidence of each of its decoded turns, in turn order (-inf
-    for a turn without frames).  Both are lists of empty arrays when there is nothing to decode.  The
-    posterior is that of the plain switch-penalty loop also under min_dur_s: the minimum duration
-    shapes the rows, not the distribution they are weighed in.  timings: reseg_posterior.  A
-    confidence that is not a bool, a conf_scale that is not a finite number > 0, conf_scale * penalty
-    above 600, confidence without a detail dictionary: ValueError before any device work.
-    reseg['soft'] = True (RESEG_SOFT; Gaussian speakers, either decoder, any passes): Baum-Welch
-    retraining.  Pass 1 is unchanged.  After every decode that is neither the last nor a repeat of the
-    one before, the next speakers are trained on posteriors instead of tokens: one
-    spkd_fb_posterior_batch on that pass's scores (no tokens, every turn's speaker count, the penalty,
-    the acoustic scale reseg['soft_scale'], default 0.1) writes every frame's posteriors, one
-    spkd_post_stats turns them and the frames into the speakers' records -- every speaker takes every
-    frame of its file's turns, weighted by its posterior there -- and spkd_gauss_models follows as
-    above.  The early stop and passes_run keep their meaning.  Under min_dur_s the posterior is that of
-    the plain loop, as for the confidences; confidence=True still runs its own final call at
-    conf_scale.  detail['soft_mass']: per retraining the float64 array [speakers] (link_speakers'
-    order) of the records' count entries, each speaker's expected number of frames: a speaker that is
-    bleeding away shows there.  timings: reseg_soft_posterior and reseg_soft_stats, one entry per
-    retraining.  The default scale comes from the synthetic generator only and is unmeasured on speech;
-    a scale that is too small lets a speaker lose its mass and the file collapse (RESEG_SOFT above).
-    Without soft, or with soft=False, the calls and the rows are those described above, to the byte.
-    A soft that is not a bool, a soft_scale that is not a finite number > 0, soft_scale * penalty above
-    600, soft with model gmm: ValueError before any device work."""
-    rate = float(rate)
-    penalty = _reseg_penalty(reseg)
-    model = _reseg_model(reseg)
-    min_frames = _reseg_min_frames(reseg, rate)
-    passes = _reseg_passes(reseg)
-    want_conf, conf_scale = _reseg_confidence(reseg, detail)
-    soft, soft_scale = _reseg_soft(reseg, model)
-    if model[0] == 'gmm':
-        if segments is None:
-            raise ValueError('reseg model gmm trains on the frames: it takes segments, the arrays cluster_batch took')
-        if len(segments) != len(files):
-            raise ValueError('one segment array per file')
-        seg_off_s, _, seg_b, seg_e = _segment_ranges(files, segments, rate)
-        if seg_off_s.tolist() != np.asarray(seg_off, dtype=np.int64).tolist():
-            raise ValueError('segments: one per label, file by file')
-    member, set_off, spk_file, spk_label = link_speakers(seg_off, labels)
-    n_files = len(files)
-    if len(labels) != n_files:
-        raise ValueError('one label array per file')
-    n_spk_file = np.bincount(spk_file, minlength=n_files).astype(np.int64)
-    if n_files and int(n_spk_file.max()) > RESEG_MAX_SPEAKERS:
-        raise ValueError('resegmentation decodes at most %d speakers a file: file %d has %d'
-                         % (RESEG_MAX_SPEAKERS, int(n_spk_file.argmax()), int(n_spk_file.max())))
-    out = [np.zeros((0, 3)) for _ in files]
-    if detail is not None:
-        detail['dropped'] = []
-        detail['passes_run'] = 0
-        if want_conf:
-            _no_confidence(detail, n_files)
-        if soft:
-            detail['soft_mass'] = []
-    table = _turn_table(files, rate)
-    if table is None or len(spk_file) == 0:
-        return out
-    owner, _, _, ls, le, tb, te = table
-    keep = n_spk_file[owner] > 0
-    owner, ls, le, tb, te = owner[keep], ls[keep], le[keep], tb[keep], te[keep]
-    if len(owner) == 0:
-        return out
-    n_spk, n_cols = len(spk_file), int(n_spk_file.max())
-    spk_base = np.zeros(n_files + 1, dtype=np.int64)
-    spk_base[1:] = np.cumsum(n_spk_file)
-    spk_first, spk_count = spk_base[owner], n_spk_file[owner]
-    d_spk = d_models = d_scores = None      # device buffers: pass 1 allocates each where it first needs it
-    frame_off = None                        # of the scores in d_scores: the pass before, while the next trains
-
-    def clock(key, which):
-        if timings is not None:
-            timings.setdefault(key, []).append(ctx.last_ms(which))
-
-    # the speaker model: train(tokens) -> ok, from the segments in pass 1 (tokens is None) and from the
-    # tokens of the pass before afterwards; score(ok) -> frame_off, the turns' scores in d_scores
-    if model[0] == 'gmm':
-        _, n_comp, n_iter, var_floor = model
-
-        def train(tokens):
-            nonlocal d_models
-            if tokens is None:
-                d_models = ctx.dev_scratch('reseg_gmm', n_spk * n_comp * hipabi.GMM_COMP * 8)
-                off, rb, re_ = set_off, seg_b[member], seg_e[member]
-            else:
-                # (spkd_gmm_train takes no empty set: a speaker without a token gets one empty range)
-                rb, re_, spk = _token_ranges(*tokens, tb, te, spk_first)
-                idle = np.nonzero(np.bincount(spk, minlength=n_spk) == 0)[0]
-                rb, re_ = np.concatenate([rb, np.zeros(len(idle), np.int64)]), np.concatenate([re_, np.zeros(len(idle), np.int64)])
-                spk = np.concatenate([spk, idle])
-                order = np.argsort(spk, kind='stable')
-                off = np.concatenate([[0], np.cumsum(np.bincount(spk, minlength=n_spk))]).astype(np.int64)
-                rb, re_ = rb[order], re_[order]
-            ok, loglik = ctx.gmm_train(d_frames, total_frames, off, rb, re_, n_comp, n_iter, var_floor, d_models)
-            clock('reseg_gmm_train', 'gmm_train')
-            if detail is not None:
-                detail['loglik'] = loglik
-            return ok
-
-        def score(ok):
-            frame_off = ctx.gmm_loglik_seq(d_frames, total_frames, d_models, n_comp, ok, tb, te, spk_first, spk_count,
-                                           n_cols, d_scores)
-            clock('reseg_loglik', 'gmm_seq_loglik')
-            return frame_off
-    else:
-        def train(tokens):
-            nonlocal d_spk, d_models
-            if tokens is None:
-                d_spk = ctx.dev_scratch('reseg_speaker_stats', n_spk * hipabi.REC * 8)
-                ctx.sum_stats(d_stats, int(seg_off[-1]), member, set_off, d_spk)
-                d_models = ctx.dev_scratch('reseg_models', n_spk * hipabi.GAUSS_MODEL * 8)
-            elif soft:
-                # (d_scores and frame_off are still those of the decode that gave `tokens`)
-                d_post = ctx.dev_scratch('reseg_post', max(int(frame_off[-1]), 1) * n_cols * 4)
-                ctx.fb_posterior_batch(d_scores, frame_off, n_cols, penalty, seq_n_cols=spk_count, scale=soft_scale,
-                                       d_post=d_post)
-                clock('reseg_soft_posterior', 'fb_posterior')
-                mass = ctx.post_stats(d_frames, total_frames, d_post, tb, te, spk_first, spk_count, n_cols, n_spk, d_spk,
-                                      masses=detail is not None)
-                clock('reseg_soft_stats', 'post_stats')
-                if detail is not None:
-                    detail['soft_mass'].append(np.asarray(mass, dtype=np.float64))
-            else:
-                rb, re_, spk = _token_ranges(*tokens, tb, te, spk_first)
-                order = np.argsort(spk, kind='stable')                     # (spkd_set_stats takes ascending sets)
-                ctx.set_stats(d_frames, total_frames, rb[order], re_[order], sets=spk[order].astype(np.int32), n_sets=n_spk,
-                              d_stats=d_spk)
-            ok = ctx.gauss_models(d_spk, n_spk, d_models)
-            clock('reseg_models', 'gauss_models')
-            return ok
-
-        def score(ok):
-            frame_off = ctx.gauss_loglik(d_frames, total_frames, d_models, ok, tb, te, spk_first, spk_count, n_cols, d_scores)
-            clock('reseg_loglik', 'gauss_loglik')
-            return frame_off
-
-    def decode(frame_off):
-        if min_frames:
-            decoded = ctx.mindur_viterbi_batch(d_scores, frame_off, n_cols, penalty, min_frames)
-        else:
-            zero = np.zeros(n_cols)
-            decoded = ctx.vad_viterbi_batch(d_scores, frame_off, n_cols, np.arange(n_cols), zero, zero, zero - penalty)
-        clock('reseg_viterbi', 'mindur_viterbi' if min_frames else 'vad_viterbi')
-        clock('reseg_backtrack', 'mindur_backtrack' if min_frames else 'vad_backtrack')
-        return decoded[:3]                                                 # (tok_off, tok_frame, tok_word)
-
-    tokens = None
-    for p in range(passes):
-        ok = train(tokens)
-        if detail is not None:
-            detail['dropped'] = [(int(spk_file[s]), int(spk_label[s])) for s in np.nonzero(ok == 0)[0]]
-        if p == 0:
-            d_scores = ctx.dev_scratch('reseg_scores', max(int((te - tb).sum()), 1) * n_cols * 4)
-        frame_off = score(ok)
-        decoded = decode(frame_off)
-        if detail is not None:
-            detail['passes_run'] = p + 1
-        same = tokens is not None and all(np.array_equal(a, b) for a, b in zip(tokens, decoded))
-        tokens = decoded
-        if same or len(tokens[1]) == 0:
-            break
-    tok_off, tok_frame, tok_word = tokens
-    # label of word w in a turn of file f: the file's w-th speaker (a word past the file's speakers
-    # is never decoded: its column is -inf beside column 0, which wins every tie)
-    file_labels = np.zeros((n_files, n_cols), dtype=np.int64)
-    file_labels[spk_file, np.arange(n_spk) - spk_base[spk_file]] = spk_label
-    rows, turn = _reseg_rows(tok_off, tok_frame, tok_word, ls, le, file_labels[owner], rate, text_contract)
-    bounds = np.searchsorted(owner[turn], np.arange(n_files + 1))
-    if want_conf:
-        # (a row is a token: the confidences come back in row order)
-        conf, logz = ctx.fb_posterior_batch(d_scores, frame_off, n_cols, penalty, tokens=(tok_off, tok_frame, tok_word),
-                                            seq_n_cols=spk_count, scale=conf_scale)
-        clock('reseg_posterior', 'fb_posterior')
-        turns = np.searchsorted(owner, np.arange(n_files + 1))
-        detail['confidence'] = [conf[bounds[i]:bounds[i + 1]] for i in range(n_files)]
-        detail['log_evidence'] = [logz[turns[i]:turns[i + 1]] for i in range(n_files)]
-    return [rows[bounds[i]:bounds[i + 1]] for i in range(n_files)]
-
-
 def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl=DIA2_CL, timings=None,
                          detail=None, first_guess_scale=1.0):
     """diarize_batch(fused=True) with the hand-off between the two stages on the device: the
@@ -1272,12 +885,7 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     decoded rows (reseg['soft'], reseg['soft_scale']; detail['soft_mass'] as there)."""
     method = _method(cl)
     if reseg is not None:
-        _reseg_penalty(reseg)
-        _reseg_model(reseg)
-        _reseg_min_frames(reseg, rate)
-        _reseg_passes(reseg)
-        _reseg_confidence(reseg, detail)
-        _reseg_soft(reseg, _reseg_model(reseg))
+        reseg_opts = _resegmentation._reseg_options(reseg, rate, detail)
         if handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi'):
             raise ValueError('reseg takes the host hand-off')
     if _cd_method(cd) in ('sw', 'm'):
@@ -1305,13 +913,8 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
         if link is not None and detail is not None:
             detail['link'] = dict(maps=[np.zeros(0, dtype=np.int32) for _ in files], merges=[],
                                   stat_max=float('nan'), stat_min=float('nan'))
-        if reseg is not None and detail is not None:
-            detail['dropped'] = []
-            detail['passes_run'] = 0
-            if reseg.get('confidence', False):
-                _no_confidence(detail, len(files))
-            if reseg.get('soft', False):
-                detail['soft_mass'] = []
+        if reseg is not None:
+            _resegmentation._empty_detail(detail, reseg_opts, len(files))
         return [np.zeros((0, 3)) for _ in files]
     return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail, reseg,
                               text_contract)

@@ -12,29 +12,16 @@ import pytest
 import reseg_numpy as R
 from helpers import ROOT
 from conftest import pkg
+from reseg_helpers import Batch, Dev as _Dev, StubContext, displaced as _displaced, ptr as _ptr
 
 RATE = 125.0
 TILE = 64
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _close(got, want, rel=1e-9):
     """The bar test_oracle_golden.py holds the numpy oracle to: 1e-9 relative, floored at 1."""
     got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
     return bool((np.abs(got - want) <= rel * np.maximum(1.0, np.maximum(np.abs(got), np.abs(want)))).all())
-
-
-def _displaced(truth, vad, shift=100):
-    """The truth's segments with every boundary inside a VAD turn moved by `shift` frames."""
-    segs = []
-    for a, b in vad:
-        inside = [t for t in truth if a <= t[0] and t[1] <= b]
-        for k, (s, e, spk) in enumerate(inside):
-            segs.append((s if k == 0 else s + shift, e if k == len(inside) - 1 else e + shift, spk))
-    return segs
 
 
 # ------------------------------------------------------------------ not GPU
@@ -164,39 +151,30 @@ def test_rows_of_a_turn():
     assert R.rows_of_turn([], [], 0.0, 1.0, [1], 125.0, True).shape == (0, 3)
 
 
-class _StubContext(object):
-    """Records what resegment_batch asks of a context and answers a canned decoding."""
+class _StubContext(StubContext):
+    """One canned decoding; every call with all its arguments, the scratch requests among them."""
 
     def __init__(self, ok, tokens):
-        self.ok, self.tokens, self.calls = np.array(ok, dtype=np.int32), tokens, []
+        StubContext.__init__(self, [tokens], [ok])
+        self.tokens = tokens
 
     def dev_scratch(self, name, nbytes):
         self.calls.append(('dev_scratch', name, nbytes))
-        return {'reseg_speaker_stats': 4096, 'reseg_models': 8192, 'reseg_scores': 12288}[name]
+        return self.SCRATCH[name]
 
     def sum_stats(self, d_src, n_src, member, set_off, d_dst):
         self.calls.append(('sum_stats', d_src, n_src, np.array(member).tolist(), np.array(set_off).tolist(), d_dst))
 
-    def gauss_models(self, d_stats, n, d_models):
-        self.calls.append(('gauss_models', d_stats, n, d_models))
-        return self.ok
-
     def gauss_loglik(self, d_frames, n_frames, d_models, ok, b, e, m, k, n_cols, d_scores):
         self.calls.append(('gauss_loglik', d_frames, n_frames, d_models, np.array(ok).tolist(), np.array(b).tolist(),
                            np.array(e).tolist(), np.array(m).tolist(), np.array(k).tolist(), n_cols, d_scores))
-        return np.concatenate([[0], np.cumsum(np.array(e) - np.array(b))]).astype(np.int64)
+        return self._frame_off(b, e)
 
     def vad_viterbi_batch(self, d_scores, frame_off, n_states, word_state, stay, exit_, enter):
         self.calls.append(('vad_viterbi_batch', d_scores, np.array(frame_off).tolist(), n_states,
                            np.array(word_state).tolist(), np.array(stay).tolist(), np.array(exit_).tolist(),
                            np.array(enter).tolist()))
-        off = np.concatenate([[0], np.cumsum([len(t) for t in self.tokens])]).astype(np.int64)
-        flat = [x for t in self.tokens for x in t]
-        return (off, np.array([f for f, _ in flat], dtype=np.int64), np.array([w for _, w in flat], dtype=np.int32),
-                np.zeros(len(self.tokens)))
-
-    def last_ms(self, which='call'):
-        return 0.5
+        return self._answer()
 
 
 def test_stages_and_rows_on_the_host():
@@ -257,31 +235,6 @@ def test_refusals_of_the_pipeline_need_no_device():
 
 
 # ------------------------------------------------------------------ GPU
-class _Dev(object):
-    """A frame array resident on the device and the records of frame sets of it."""
-
-    def __init__(self, frames):
-        self.engine, self.pipeline, self.hipabi = pkg('engine'), pkg('pipeline'), pkg('hipabi')
-        self.frames = np.ascontiguousarray(frames, dtype=np.float32)
-        self.eng = self.engine.HipEngine(0)
-        self.eng.set_features(self.frames)
-        self.ctx, self.bufs = self.eng.ctx, []
-
-    def records(self, ranges):
-        d = self.eng._stats_of_sets([[r] for r in ranges])
-        self.bufs.append(d)
-        return d
-
-    def alloc(self, nbytes):
-        self.bufs.append(self.ctx.dev_alloc(nbytes))
-        return self.bufs[-1]
-
-    def close(self):
-        for p in self.bufs:
-            self.ctx.dev_free(p)
-        self.eng.close()
-
-
 @pytest.fixture(scope='module')
 def one():
     """One 60 s session of two speakers and 64 constant frames behind it."""
@@ -393,14 +346,7 @@ def test_scores_match_the_restatement_to_an_ulp(one):
 def three():
     """Three 60 s files of 2, 3 and 4 speakers as one batch, their truth segments' records."""
     synth = pkg('synth')
-    sess = [synth.make_session(4100 + k, 60.0, k) for k in (2, 3, 4)]
-    d = _Dev(np.concatenate([s[0] for s in sess]))
-    foff = np.concatenate([[0], np.cumsum([len(s[0]) for s in sess])])
-    d.sess, d.foff = sess, foff
-    d.files = [d.pipeline.BatchFile(foff[i], len(s[0]), [(a / RATE, b / RATE) for a, b in s[1]]) for i, s in enumerate(sess)]
-    d.seg_off = np.concatenate([[0], np.cumsum([len(s[2]) for s in sess])]).astype(np.int64)
-    d.labels = [np.array([k + 1 for _, _, k in s[2]], dtype=np.int32) for s in sess]
-    d.d_stats = d.records([(int(foff[i] + a), int(foff[i] + b)) for i, s in enumerate(sess) for a, b, _ in s[2]])
+    d = Batch([synth.make_session(4100 + k, 60.0, k) for k in (2, 3, 4)])
     yield d
     d.close()
 

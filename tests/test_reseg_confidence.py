@@ -12,15 +12,13 @@ import reseg_fb_numpy as F
 import reseg_numpy as R
 from helpers import ROOT
 from conftest import pkg
+from reseg_helpers import (Batch, StubContext, close_session as _close_session, normal_scores as _normal_scores,
+                           ptr as _ptr)
 
 RATE = 125.0
 L = np.longdouble
 EPS = 2.0 ** -52
 MARGIN = 64.0        # device against the np.longdouble restatement, in units of max(CPU fp64 error, 2^-52)
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 # ------------------------------------------------------------------ not GPU
@@ -169,9 +167,10 @@ def test_value_errors_come_before_any_device_work():
         both(dict(penalty=50.0, conf_scale=bad), 'reseg conf_scale', {})
     both(dict(penalty=50.0, confidence=True, conf_scale=12.5), 'conf_scale \\* penalty', {})
     both(dict(penalty=601.0, confidence=True), 'conf_scale \\* penalty', {})
-    assert pipeline._reseg_confidence(dict(penalty=50.0), None) == (False, 1.0)
-    assert pipeline._reseg_confidence(dict(penalty=601.0), None) == (False, 1.0)        # (the limit is the posterior's)
-    assert pipeline._reseg_confidence(dict(penalty=50.0, confidence=True, conf_scale=12), {}) == (True, 12.0)
+    stage = pkg('resegmentation')
+    assert stage._reseg_confidence(dict(penalty=50.0), None) == (False, 1.0)
+    assert stage._reseg_confidence(dict(penalty=601.0), None) == (False, 1.0)           # (the limit is the posterior's)
+    assert stage._reseg_confidence(dict(penalty=50.0, confidence=True, conf_scale=12), {}) == (True, 12.0)
     # an empty batch, and a batch without speakers: empty arrays
     det = {}
     assert pipeline.diarize_batch(None, 0, 0, [], reseg=pipeline.RESEG_CONF, detail=det) == []
@@ -186,53 +185,16 @@ def test_value_errors_come_before_any_device_work():
     assert 'confidence' not in det and 'log_evidence' not in det
 
 
-class _StubContext(object):
-    """Answers one canned decoding per pass and records the calls resegment_batch makes."""
-
-    def __init__(self, answers):
-        self.answers, self.calls, self.n = answers, [], 0
-
-    def dev_scratch(self, name, nbytes):
-        return {'reseg_speaker_stats': 4096, 'reseg_models': 8192, 'reseg_scores': 12288}[name]
-
-    def sum_stats(self, *a):
-        self.calls.append(('sum_stats',))
-
-    def set_stats(self, *a, **kw):
-        self.calls.append(('set_stats',))
-
-    def gauss_models(self, d_stats, n, d_models):
-        self.calls.append(('gauss_models',))
-        return np.ones(n, dtype=np.int32)
-
-    def gauss_loglik(self, d_frames, n_frames, d_models, ok, b, e, m, k, n_cols, d_scores):
-        self.calls.append(('loglik',))
-        return np.concatenate([[0], np.cumsum(np.array(e) - np.array(b))]).astype(np.int64)
-
-    def _answer(self):
-        tokens = self.answers[min(self.n, len(self.answers) - 1)]
-        self.n += 1
-        off = np.concatenate([[0], np.cumsum([len(t) for t in tokens])]).astype(np.int64)
-        flat = [x for t in tokens for x in t]
-        return (off, np.array([f for f, _ in flat], dtype=np.int64), np.array([w for _, w in flat], dtype=np.int32),
-                np.zeros(len(tokens)))
-
-    def vad_viterbi_batch(self, d_scores, frame_off, n_states, word_state, stay, exit_, enter):
-        self.calls.append(('decode',))
-        return self._answer()
-
-    def mindur_viterbi_batch(self, d_scores, frame_off, n_cols, penalty, min_frames):
-        self.calls.append(('decode_md',))
-        return self._answer()
+class _StubContext(StubContext):
+    """The final posterior call with all its arguments; a confidence and a log-evidence that tell the rows and
+    the turns apart."""
+    MS = {'fb_posterior': 0.75}
 
     def fb_posterior_batch(self, d_scores, frame_off, n_cols, penalty, tokens=None, seq_n_cols=None, scale=1.0, d_post=0):
         self.calls.append(('fb', d_scores, np.array(frame_off).tolist(), n_cols, penalty, [np.array(t).tolist() for t in tokens],
                            np.array(seq_n_cols).tolist(), scale, d_post))
         n_tok = len(tokens[1])
         return 0.5 + np.arange(n_tok) / 16.0, -100.0 - np.arange(len(frame_off) - 1)
-
-    def last_ms(self, which='call'):
-        return {'fb_posterior': 0.75}.get(which, 0.5)
 
 
 def test_the_pipeline_calls_the_posterior_once_behind_the_last_decode():
@@ -271,24 +233,6 @@ def test_the_pipeline_calls_the_posterior_once_behind_the_last_decode():
 
 
 # ------------------------------------------------------------------ GPU
-def _normal_scores(rng, T, W):
-    """test_reseg_mindur._normal_scores: float32 normals around -100 rounded to halves (exact ties), with a
-    NaN, a -inf column and frames nobody can score planted."""
-    sc = (np.round(rng.normal(-100.0, 3.0, (T, W)) * 2.0) / 2.0).astype(np.float32)
-    if T >= 9:
-        sc[5:9] = sc[4]
-    if W > 2 and rng.integers(0, 2) == 0:
-        sc[:, 1] = -np.inf
-    if T >= 8 and rng.integers(0, 2) == 0:
-        t = int(rng.integers(0, T - 4))
-        sc[t:t + int(rng.integers(1, 5))] = -np.inf
-    if T >= 2 and rng.integers(0, 2) == 0:
-        sc[int(rng.integers(0, T)), int(rng.integers(0, W))] = np.nan
-    if W > 1 and T >= 3 and rng.integers(0, 4) == 0:
-        sc[int(rng.integers(0, T)), 0] = -np.inf
-    return sc
-
-
 def _host_tokens(hipabi, seqs, ncol, penalty):
     """The tokens of the host decoder on every sequence's first n(q) columns, as a decoder hands them back."""
     tok_off, frames, words = [0], [], []
@@ -429,43 +373,11 @@ def test_consistency_empty_calls_and_refusals_with_a_context(ctx):
     assert np.isfinite(post[off[q + 1]:-1]).all()
 
 
-def _close_session(seed, seconds, n_speakers, eps=0.2):
-    """test_reseg_mindur._close_session: a session of the generator whose speakers differ by a fifth of
-    their usual distance in the mean only: single frames are then often closer to the wrong speaker."""
-    synth = pkg('synth')
-    base = [synth._speaker_model(seed, k) for k in range(n_speakers)]
-    models = [(base[0][0] + eps * (m[0] - base[0][0]), base[0][1]) for m in base]
-    return synth.make_session(seed, seconds, n_speakers, models=models)
-
-
-class _Batch(object):
-    """Two 40 s files of 2 and 3 close speakers resident on the device, their truth segments' records,
-    labels and segments."""
-
-    def __init__(self):
-        self.engine, self.pipeline, self.hipabi = pkg('engine'), pkg('pipeline'), pkg('hipabi')
-        self.sess = [_close_session(7000, 40.0, 2), _close_session(7001, 40.0, 3)]
-        self.frames = np.ascontiguousarray(np.concatenate([s[0] for s in self.sess]), dtype=np.float32)
-        self.eng = self.engine.HipEngine(0)
-        self.eng.set_features(self.frames)
-        self.ctx = self.eng.ctx
-        foff = np.concatenate([[0], np.cumsum([len(s[0]) for s in self.sess])])
-        self.files = [self.pipeline.BatchFile(foff[i], len(s[0]), [(a / RATE, b / RATE) for a, b in s[1]])
-                      for i, s in enumerate(self.sess)]
-        self.seg_off = np.concatenate([[0], np.cumsum([len(s[2]) for s in self.sess])]).astype(np.int64)
-        self.labels = [np.array([k + 1 for _, _, k in s[2]], dtype=np.int32) for s in self.sess]
-        self.segments = [np.array([(a / RATE, b / RATE) for a, b, _ in s[2]]) for s in self.sess]
-        self.d_stats = self.eng._stats_of_sets([[(int(foff[i] + a), int(foff[i] + b))] for i, s in enumerate(self.sess)
-                                                for a, b, _ in s[2]])
-
-    def close(self):
-        self.ctx.dev_free(self.d_stats)
-        self.eng.close()
-
-
 @pytest.fixture(scope='module')
 def batch():
-    b = _Batch()
+    """Two 40 s files of 2 and 3 close speakers resident on the device, their truth segments' records,
+    labels and segments."""
+    b = Batch([_close_session(7000, 40.0, 2), _close_session(7001, 40.0, 3)])
     yield b
     b.close()
 

@@ -13,13 +13,10 @@ import reseg_numpy as R
 import reseg_gmm_numpy as G
 from helpers import ROOT
 from conftest import pkg
-from test_reseg_batch import _Dev, _close, _displaced
+from reseg_helpers import Batch, Dev as _Dev, StubContext, displaced as _displaced, ptr as _ptr
+from test_reseg_batch import _close
 
 RATE = 125.0
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _same(got, want):
@@ -211,38 +208,40 @@ def test_restatement_beats_the_displaced_input():
         assert before < 1.0 and after > before, name
 
 
-class _StubContext(object):
-    """Records what resegment_batch asks of a context under model 'gmm' and answers a canned decoding."""
+class _StubContext(StubContext):
+    """One canned decoding under model 'gmm'; every call with all its arguments, the scratch requests among
+    them.  A context without the Gaussian path: asking it for sum_stats is an AttributeError."""
+    MS = {'gmm_train': 0.25, 'gmm_seq_loglik': 0.75}
 
     def __init__(self, ok, tokens):
-        self.ok, self.tokens, self.calls = np.array(ok, dtype=np.int32), tokens, []
+        StubContext.__init__(self, [tokens], [ok])
+        self.tokens = tokens
+
+    @property
+    def sum_stats(self):
+        raise AttributeError('sum_stats')
 
     def dev_scratch(self, name, nbytes):
         self.calls.append(('dev_scratch', name, nbytes))
-        return {'reseg_gmm': 8192, 'reseg_scores': 12288}.get(name, 4096)
+        return self.SCRATCH[name]
 
     def gmm_train(self, d_frames, n_frames, set_off, b, e, n_comp, n_iter, var_floor, d_gmm, from_model=False):
         self.calls.append(('gmm_train', d_frames, n_frames, np.array(set_off).tolist(), np.array(b).tolist(),
                            np.array(e).tolist(), n_comp, n_iter, var_floor, d_gmm, from_model))
-        return self.ok, np.arange(len(self.ok) * n_iter, dtype=np.float64).reshape(len(self.ok), n_iter)
+        ok = self._ok(len(set_off) - 1)
+        return ok, np.arange(len(ok) * n_iter, dtype=np.float64).reshape(len(ok), n_iter)
 
     def gmm_loglik_seq(self, d_frames, n_frames, d_gmm, n_comp, ok, b, e, m, k, n_cols, d_scores):
         self.calls.append(('gmm_loglik_seq', d_frames, n_frames, d_gmm, n_comp, np.array(ok).tolist(),
                            np.array(b).tolist(), np.array(e).tolist(), np.array(m).tolist(), np.array(k).tolist(),
                            n_cols, d_scores))
-        return np.concatenate([[0], np.cumsum(np.array(e) - np.array(b))]).astype(np.int64)
+        return self._frame_off(b, e)
 
     def vad_viterbi_batch(self, d_scores, frame_off, n_states, word_state, stay, exit_, enter):
         self.calls.append(('vad_viterbi_batch', d_scores, np.array(frame_off).tolist(), n_states,
                            np.array(word_state).tolist(), np.array(stay).tolist(), np.array(exit_).tolist(),
                            np.array(enter).tolist()))
-        off = np.concatenate([[0], np.cumsum([len(t) for t in self.tokens])]).astype(np.int64)
-        flat = [x for t in self.tokens for x in t]
-        return (off, np.array([f for f, _ in flat], dtype=np.int64), np.array([w for _, w in flat], dtype=np.int32),
-                np.zeros(len(self.tokens)))
-
-    def last_ms(self, which='call'):
-        return {'gmm_train': 0.25, 'gmm_seq_loglik': 0.75}.get(which, 0.5)
+        return self._answer()
 
 
 def test_stages_and_rows_on_the_host():
@@ -497,15 +496,7 @@ def test_scores_match_the_restatement_to_an_ulp(one):
 def three():
     """Three 60 s files of 2, 3 and 4 speakers as one batch, their truth segments and those segments' records."""
     synth = pkg('synth')
-    sess = [synth.make_session(4100 + k, 60.0, k) for k in (2, 3, 4)]
-    d = _Dev(np.concatenate([s[0] for s in sess]))
-    foff = np.concatenate([[0], np.cumsum([len(s[0]) for s in sess])])
-    d.sess, d.foff = sess, foff
-    d.files = [d.pipeline.BatchFile(foff[i], len(s[0]), [(a / RATE, b / RATE) for a, b in s[1]]) for i, s in enumerate(sess)]
-    d.seg_off = np.concatenate([[0], np.cumsum([len(s[2]) for s in sess])]).astype(np.int64)
-    d.labels = [np.array([k + 1 for _, _, k in s[2]], dtype=np.int32) for s in sess]
-    d.segments = [np.array([(a / RATE, b / RATE) for a, b, _ in s[2]]) for s in sess]
-    d.d_stats = d.records([(int(foff[i] + a), int(foff[i] + b)) for i, s in enumerate(sess) for a, b, _ in s[2]])
+    d = Batch([synth.make_session(4100 + k, 60.0, k) for k in (2, 3, 4)])
     yield d
     d.close()
 

@@ -12,12 +12,10 @@ import reseg_mindur_numpy as M
 import reseg_numpy as R
 from helpers import ROOT
 from conftest import pkg
+from reseg_helpers import (Batch, StubContext, close_session as _close_session, normal_scores as _normal_scores,
+                           ptr as _ptr)
 
 RATE = 125.0
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
 
 
 def _lengths(D):
@@ -162,41 +160,30 @@ def test_value_errors_come_before_any_device_work():
             pipeline.resegment_batch(None, 0, 1000, files, 0, [0, 2], labels, reseg=dict(penalty=50.0, min_dur_s=bad))
         with pytest.raises(ValueError, match='reseg min_dur_s'):
             pipeline.diarize_batch(None, 0, 0, [], reseg=dict(penalty=50.0, min_dur_s=bad))
-    assert pipeline._reseg_min_frames(dict(penalty=1.0), RATE) == 0
-    assert pipeline._reseg_min_frames(dict(penalty=1.0, min_dur_s=0), RATE) == 0
-    assert pipeline._reseg_min_frames(pipeline.RESEG_MD, RATE) == 125
-    assert pipeline._reseg_min_frames(dict(min_dur_s=0.001), RATE) == 1             # never below one frame
-    assert pipeline._reseg_min_frames(dict(min_dur_s=0.29), 100.0) == 28            # floor(0.29 * 100.0 = 28.999...)
+    stage = pkg('resegmentation')
+    assert stage._reseg_min_frames(dict(penalty=1.0), RATE) == 0
+    assert stage._reseg_min_frames(dict(penalty=1.0, min_dur_s=0), RATE) == 0
+    assert stage._reseg_min_frames(pipeline.RESEG_MD, RATE) == 125
+    assert stage._reseg_min_frames(dict(min_dur_s=0.001), RATE) == 1                # never below one frame
+    assert stage._reseg_min_frames(dict(min_dur_s=0.29), 100.0) == 28               # floor(0.29 * 100.0 = 28.999...)
     det = {}
     assert pipeline.diarize_batch(None, 0, 0, [], reseg=pipeline.RESEG_MD, detail=det) == []
     assert det['dropped'] == [] and det['passes_run'] == 0
 
 
-class _StubContext(object):
-    """Records which decoder resegment_batch asks a context for and answers a canned decoding."""
+class _StubContext(StubContext):
+    """One canned decoding; records which decoder resegment_batch asks a context for, on which scores."""
+    MS = {'mindur_viterbi': 0.25, 'mindur_backtrack': 0.125}
 
     def __init__(self, tokens):
-        self.tokens, self.calls = tokens, []
+        StubContext.__init__(self, [tokens])
 
     def dev_scratch(self, name, nbytes):
         return 4096
 
-    def sum_stats(self, *a):
-        self.calls.append(('sum_stats',))
-
-    def gauss_models(self, d_stats, n, d_models):
-        self.calls.append(('gauss_models',))
-        return np.ones(n, dtype=np.int32)
-
     def gauss_loglik(self, d_frames, n_frames, d_models, ok, b, e, m, k, n_cols, d_scores):
         self.calls.append(('gauss_loglik',))
-        return np.concatenate([[0], np.cumsum(np.array(e) - np.array(b))]).astype(np.int64)
-
-    def _answer(self):
-        off = np.concatenate([[0], np.cumsum([len(t) for t in self.tokens])]).astype(np.int64)
-        flat = [x for t in self.tokens for x in t]
-        return (off, np.array([f for f, _ in flat], dtype=np.int64), np.array([w for _, w in flat], dtype=np.int32),
-                np.zeros(len(self.tokens)))
+        return self._frame_off(b, e)
 
     def vad_viterbi_batch(self, d_scores, frame_off, n_states, word_state, stay, exit_, enter):
         self.calls.append(('vad_viterbi_batch', d_scores, np.array(frame_off).tolist(), n_states, np.array(enter).tolist()))
@@ -205,9 +192,6 @@ class _StubContext(object):
     def mindur_viterbi_batch(self, d_scores, frame_off, n_cols, penalty, min_frames):
         self.calls.append(('mindur_viterbi_batch', d_scores, np.array(frame_off).tolist(), n_cols, penalty, min_frames))
         return self._answer()
-
-    def last_ms(self, which='call'):
-        return {'mindur_viterbi': 0.25, 'mindur_backtrack': 0.125}.get(which, 0.5)
 
 
 def test_defaults_keep_the_plain_decoder_and_min_dur_takes_the_new_one():
@@ -232,24 +216,6 @@ def test_defaults_keep_the_plain_decoder_and_min_dur_takes_the_new_one():
 
 
 # ------------------------------------------------------------------ GPU
-def _normal_scores(rng, T, W):
-    """Float32 normals around -100 rounded to halves (exact ties), as test_reseg_batch's decoder test,
-    with a NaN, a -inf column and frames nobody can score planted."""
-    sc = (np.round(rng.normal(-100.0, 3.0, (T, W)) * 2.0) / 2.0).astype(np.float32)
-    if T >= 9:
-        sc[5:9] = sc[4]
-    if W > 2 and rng.integers(0, 2) == 0:
-        sc[:, 1] = -np.inf
-    if T >= 8 and rng.integers(0, 2) == 0:
-        t = int(rng.integers(0, T - 4))
-        sc[t:t + int(rng.integers(1, 5))] = -np.inf
-    if T >= 2 and rng.integers(0, 2) == 0:
-        sc[int(rng.integers(0, T)), int(rng.integers(0, W))] = np.nan
-    if W > 1 and T >= 3 and rng.integers(0, 4) == 0:
-        sc[int(rng.integers(0, T)), 0] = -np.inf
-    return sc
-
-
 @pytest.fixture(scope='module')
 def ctx():
     c = pkg('hipabi').Context(0)
@@ -340,43 +306,11 @@ def test_neither_decoder_ends_the_results_of_the_other(ctx, mindur_first):
     assert other[3].tolist() != first[3].tolist()                          # (it was another decode)
 
 
-def _close_session(seed, seconds, n_speakers, eps=0.2):
-    """A session of the generator whose speakers differ by a fifth of their usual distance in the mean
-    only: single frames are then often closer to the wrong speaker."""
-    synth = pkg('synth')
-    base = [synth._speaker_model(seed, k) for k in range(n_speakers)]
-    models = [(base[0][0] + eps * (m[0] - base[0][0]), base[0][1]) for m in base]
-    return synth.make_session(seed, seconds, n_speakers, models=models)
-
-
-class _Batch(object):
-    """Two 40 s files of 2 and 3 close speakers (turns >= 3 s) resident on the device, their truth
-    segments' records and labels."""
-
-    def __init__(self):
-        self.engine, self.pipeline, self.hipabi = pkg('engine'), pkg('pipeline'), pkg('hipabi')
-        self.sess = [_close_session(7000, 40.0, 2), _close_session(7001, 40.0, 3)]
-        self.frames = np.ascontiguousarray(np.concatenate([s[0] for s in self.sess]), dtype=np.float32)
-        self.eng = self.engine.HipEngine(0)
-        self.eng.set_features(self.frames)
-        self.ctx = self.eng.ctx
-        foff = np.concatenate([[0], np.cumsum([len(s[0]) for s in self.sess])])
-        self.foff = foff
-        self.files = [self.pipeline.BatchFile(foff[i], len(s[0]), [(a / RATE, b / RATE) for a, b in s[1]])
-                      for i, s in enumerate(self.sess)]
-        self.seg_off = np.concatenate([[0], np.cumsum([len(s[2]) for s in self.sess])]).astype(np.int64)
-        self.labels = [np.array([k + 1 for _, _, k in s[2]], dtype=np.int32) for s in self.sess]
-        self.d_stats = self.eng._stats_of_sets([[(int(foff[i] + a), int(foff[i] + b))] for i, s in enumerate(self.sess)
-                                                for a, b, _ in s[2]])
-
-    def close(self):
-        self.ctx.dev_free(self.d_stats)
-        self.eng.close()
-
-
 @pytest.fixture(scope='module')
 def batch():
-    b = _Batch()
+    """Two 40 s files of 2 and 3 close speakers (turns >= 3 s) resident on the device, their truth
+    segments' records and labels."""
+    b = Batch([_close_session(7000, 40.0, 2), _close_session(7001, 40.0, 3)])
     yield b
     b.close()
 
@@ -403,7 +337,7 @@ def _rows_of_the_restated_decoder(batch, reseg):
     sc = np.empty((int((te - tb).sum()), n_cols), dtype=np.float32)
     ctx.d2h(sc, ctx.dev_scratch('reseg_scores', 0))
     off = np.concatenate([[0], np.cumsum(te - tb)])
-    D = p._reseg_min_frames(reseg, RATE)
+    D = pkg('resegmentation')._reseg_min_frames(reseg, RATE)
     want = [[] for _ in batch.files]
     for q in range(len(owner)):
         f = int(owner[q])

@@ -7,18 +7,9 @@ import pytest
 import reseg_mindur_numpy as M
 import reseg_numpy as R
 from conftest import pkg
+from reseg_helpers import Dev as _Dev, StubContext as _StubContext, displaced as _displaced
 
 RATE = 125.0
-
-
-def _displaced(truth, vad, shift=100):
-    """test_reseg_batch's case: the truth's segments with every boundary inside a VAD turn `shift` frames late."""
-    segs = []
-    for a, b in vad:
-        inside = [t for t in truth if a <= t[0] and t[1] <= b]
-        for k, (s, e, spk) in enumerate(inside):
-            segs.append((s if k == 0 else s + shift, e if k == len(inside) - 1 else e + shift, spk))
-    return segs
 
 
 def _rows_of(vad, spk, decoded, text_contract=False):
@@ -37,65 +28,20 @@ def test_passes_must_be_an_integer_from_one_on():
             pipeline.resegment_batch(None, 0, 1000, files, 0, [0, 2], labels, reseg=dict(penalty=50.0, passes=bad))
         with pytest.raises(ValueError, match='reseg passes'):
             pipeline.diarize_batch(None, 0, 0, [], reseg=dict(penalty=50.0, passes=bad))
-    assert pipeline._reseg_passes(dict(penalty=1.0)) == 1 and pipeline._reseg_passes(dict(passes=3.0)) == 3
+    stage = pkg('resegmentation')
+    assert stage._reseg_passes(dict(penalty=1.0)) == 1 and stage._reseg_passes(dict(passes=3.0)) == 3
     # model gmm with passes still wants the segments, for pass 1
     with pytest.raises(ValueError, match='it takes segments'):
         pipeline.resegment_batch(None, 0, 1000, files, 0, [0, 2], labels, reseg=dict(pipeline.RESEG_GMM, passes=2))
 
 
 def test_token_ranges_are_absolute_and_end_with_the_turn():
-    pipeline = pkg('pipeline')
     tok_off = np.array([0, 2, 2, 5])
-    b, e, spk = pipeline._token_ranges(tok_off, np.array([0, 100, 0, 7, 300]), np.array([1, 0, 2, 0, 2]),
-                                       np.array([125, 1000, 1562]), np.array([375, 1000, 2250]), np.array([0, 0, 2]))
+    b, e, spk = pkg('resegmentation')._token_ranges(tok_off, np.array([0, 100, 0, 7, 300]), np.array([1, 0, 2, 0, 2]),
+                                                    np.array([125, 1000, 1562]), np.array([375, 1000, 2250]),
+                                                    np.array([0, 0, 2]))
     assert b.tolist() == [125, 225, 1562, 1569, 1862] and e.tolist() == [225, 375, 1569, 1862, 2250]
     assert spk.tolist() == [1, 0, 4, 2, 4]
-
-
-class _StubContext(object):
-    """Answers one canned decoding per pass and records the training calls in between."""
-
-    def __init__(self, answers, ok):
-        self.answers, self.ok, self.calls, self.n = answers, ok, [], 0
-
-    def dev_scratch(self, name, nbytes):
-        return {'reseg_speaker_stats': 4096, 'reseg_models': 8192, 'reseg_scores': 12288, 'reseg_gmm': 8192}[name]
-
-    def sum_stats(self, *a):
-        self.calls.append(('sum_stats',))
-
-    def set_stats(self, d_frames, n_frames, begins, ends, sets, n_sets, d_stats):
-        self.calls.append(('set_stats', d_frames, n_frames, np.array(begins).tolist(), np.array(ends).tolist(),
-                           np.array(sets).tolist(), n_sets, d_stats))
-
-    def gauss_models(self, d_stats, n, d_models):
-        self.calls.append(('gauss_models', d_stats, n, d_models))
-        return np.array(self.ok[min(self.n, len(self.ok) - 1)], dtype=np.int32)
-
-    def gmm_train(self, d_frames, n_frames, set_off, b, e, n_comp, n_iter, var_floor, d_gmm, from_model=False):
-        self.calls.append(('gmm_train', np.array(set_off).tolist(), np.array(b).tolist(), np.array(e).tolist(), n_comp,
-                           n_iter, var_floor, d_gmm, from_model))
-        return np.array(self.ok[min(self.n, len(self.ok) - 1)], dtype=np.int32), np.zeros((3, n_iter))
-
-    def gauss_loglik(self, d_frames, n_frames, d_models, ok, b, e, m, k, n_cols, d_scores):
-        self.calls.append(('loglik', np.array(ok).tolist()))
-        return np.concatenate([[0], np.cumsum(np.array(e) - np.array(b))]).astype(np.int64)
-
-    def gmm_loglik_seq(self, d_frames, n_frames, d_gmm, n_comp, ok, b, e, m, k, n_cols, d_scores):
-        self.calls.append(('loglik', np.array(ok).tolist()))
-        return np.concatenate([[0], np.cumsum(np.array(e) - np.array(b))]).astype(np.int64)
-
-    def vad_viterbi_batch(self, d_scores, frame_off, n_states, word_state, stay, exit_, enter):
-        self.calls.append(('decode',))
-        tokens = self.answers[min(self.n, len(self.answers) - 1)]
-        self.n += 1
-        off = np.concatenate([[0], np.cumsum([len(t) for t in tokens])]).astype(np.int64)
-        flat = [x for t in tokens for x in t]
-        return (off, np.array([f for f, _ in flat], dtype=np.int64), np.array([w for _, w in flat], dtype=np.int32),
-                np.zeros(len(tokens)))
-
-    def last_ms(self, which='call'):
-        return 0.5
 
 
 def test_the_loop_on_the_host():
@@ -157,25 +103,6 @@ def test_restated_loop_converges_on_the_displaced_input():
 
 
 # ------------------------------------------------------------------ GPU
-class _Dev(object):
-    def __init__(self, frames):
-        self.engine, self.pipeline = pkg('engine'), pkg('pipeline')
-        self.frames = np.ascontiguousarray(frames, dtype=np.float32)
-        self.eng = self.engine.HipEngine(0)
-        self.eng.set_features(self.frames)
-        self.ctx, self.bufs = self.eng.ctx, []
-
-    def records(self, ranges):
-        d = self.eng._stats_of_sets([[r] for r in ranges])
-        self.bufs.append(d)
-        return d
-
-    def close(self):
-        for p in self.bufs:
-            self.ctx.dev_free(p)
-        self.eng.close()
-
-
 @pytest.fixture(scope='module')
 def displaced():
     synth = pkg('synth')

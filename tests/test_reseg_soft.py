@@ -14,6 +14,7 @@ import reseg_numpy as R
 import reseg_soft_numpy as S
 from helpers import ROOT
 from conftest import pkg
+from reseg_helpers import Batch, StubContext, close_session as _close_session, displaced as _displaced, ptr as _ptr
 
 RATE = 125.0
 L = np.longdouble
@@ -25,28 +26,6 @@ FIXTURES = [(7002, 0.10, 2, 300), (7006, 0.15, 3, 300)]
 HARD_WRONG = [370, 300]
 GAIN = 50
 SOFT8 = dict(penalty=50.0, passes=8, soft=True, soft_scale=0.1)
-
-
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _close_session(seed, seconds, n_speakers, eps):
-    """test_reseg_confidence._close_session: the generator's speakers moved to eps of their usual distance."""
-    synth = pkg('synth')
-    base = [synth._speaker_model(seed, k) for k in range(n_speakers)]
-    models = [(base[0][0] + eps * (m[0] - base[0][0]), base[0][1]) for m in base]
-    return synth.make_session(seed, seconds, n_speakers, models=models)
-
-
-def _displaced(truth, vad, shift):
-    """test_reseg_passes._displaced: the truth with every boundary inside a VAD turn `shift` frames late."""
-    segs = []
-    for a, b in vad:
-        inside = [t for t in truth if a <= t[0] and t[1] <= b]
-        for k, (s, e, spk) in enumerate(inside):
-            segs.append((s if k == 0 else s + shift, e if k == len(inside) - 1 else e + shift, spk))
-    return segs
 
 
 @functools.lru_cache(maxsize=None)
@@ -149,49 +128,20 @@ def test_value_errors_come_before_any_device_work():
         pipeline.resegment_batch(None, 0, 1000, files, 0, [0, 2], labels, reseg=gmm, segments=segments)
     with pytest.raises(ValueError, match='reseg soft: the Gaussian speakers only'):
         pipeline.diarize_batch(None, 0, 0, [], reseg=gmm)
-    assert pipeline._reseg_soft(dict(penalty=50.0), ('gauss',)) == (False, 0.1)
-    assert pipeline._reseg_soft(dict(penalty=50.0, soft=True, soft_scale=12.0), ('gauss',)) == (True, 12.0)
-    assert pipeline._reseg_soft(dict(penalty=7000.0), ('gauss',)) == (False, 0.1)      # (the product binds soft only)
-    assert pipeline._reseg_soft(dict(pipeline.RESEG_GMM, soft=False), ('gmm', 4, 5, 0.01)) == (False, 0.1)
+    stage = pkg('resegmentation')
+    assert stage._reseg_soft(dict(penalty=50.0), ('gauss',)) == (False, 0.1)
+    assert stage._reseg_soft(dict(penalty=50.0, soft=True, soft_scale=12.0), ('gauss',)) == (True, 12.0)
+    assert stage._reseg_soft(dict(penalty=7000.0), ('gauss',)) == (False, 0.1)         # (the product binds soft only)
+    assert stage._reseg_soft(dict(pipeline.RESEG_GMM, soft=False), ('gmm', 4, 5, 0.01)) == (False, 0.1)
 
 
-class _StubContext(object):
-    """Answers one canned decoding per pass and records the calls resegment_batch makes."""
-    SCRATCH = {'reseg_speaker_stats': 4096, 'reseg_models': 8192, 'reseg_scores': 12288, 'reseg_post': 16384}
+class _StubContext(StubContext):
+    """Both posterior calls and spkd_post_stats with all their arguments; either decoder is 'decode'."""
+    MS = {'fb_posterior': 0.75, 'post_stats': 0.25}
 
     def __init__(self, answers, ok):
-        self.answers, self.ok, self.calls, self.n, self.scratch, self.masses = answers, ok, [], 0, [], []
-
-    def dev_scratch(self, name, nbytes):
-        self.scratch.append((name, nbytes))
-        return self.SCRATCH[name]
-
-    def sum_stats(self, *a):
-        self.calls.append(('sum_stats',))
-
-    def set_stats(self, d_frames, n_frames, begins, ends, sets, n_sets, d_stats):
-        self.calls.append(('set_stats', d_frames, n_frames, np.array(begins).tolist(), np.array(ends).tolist(),
-                           np.array(sets).tolist(), n_sets, d_stats))
-
-    def gauss_models(self, d_stats, n, d_models):
-        self.calls.append(('gauss_models', d_stats, n, d_models))
-        return np.array(self.ok[min(self.n, len(self.ok) - 1)], dtype=np.int32)
-
-    def gauss_loglik(self, d_frames, n_frames, d_models, ok, b, e, m, k, n_cols, d_scores):
-        self.calls.append(('loglik', np.array(ok).tolist()))
-        return np.concatenate([[0], np.cumsum(np.array(e) - np.array(b))]).astype(np.int64)
-
-    def _answer(self):
-        tokens = self.answers[min(self.n, len(self.answers) - 1)]
-        self.n += 1
-        off = np.concatenate([[0], np.cumsum([len(t) for t in tokens])]).astype(np.int64)
-        flat = [x for t in tokens for x in t]
-        return (off, np.array([f for f, _ in flat], dtype=np.int64), np.array([w for _, w in flat], dtype=np.int32),
-                np.zeros(len(tokens)))
-
-    def vad_viterbi_batch(self, d_scores, frame_off, n_states, word_state, stay, exit_, enter):
-        self.calls.append(('decode',))
-        return self._answer()
+        StubContext.__init__(self, answers, ok)
+        self.masses = []
 
     def mindur_viterbi_batch(self, d_scores, frame_off, n_cols, penalty, min_frames):
         self.calls.append(('decode',))
@@ -209,9 +159,6 @@ class _StubContext(object):
                            np.array(m).tolist(), np.array(k).tolist(), n_cols, n_models, d_stats))
         self.masses.append(masses)
         return np.arange(n_models) + 100.0 * self.n if masses else None
-
-    def last_ms(self, which='call'):
-        return {'fb_posterior': 0.75, 'post_stats': 0.25}.get(which, 0.5)
 
 
 def test_the_soft_loop_on_the_host():
@@ -531,37 +478,13 @@ def test_refusals_and_empty_calls_with_a_context(ctx):
         assert (out[:2] == 0.0).all() and (out[2] == -7.0).all() and mass.tolist() == [0.0, 0.0]
 
 
-class _Batch(object):
-    """The two fixtures as one two-file batch resident on the device, with the records, labels and
-    segments of their displaced input."""
-
-    def __init__(self):
-        self.engine, self.pipeline = pkg('engine'), pkg('pipeline')
-        self.fix = [_fixture(i) for i in range(len(FIXTURES))]
-        self.frames = np.ascontiguousarray(np.concatenate([f[0] for f in self.fix]), dtype=np.float32)
-        self.eng = self.engine.HipEngine(0)
-        self.eng.set_features(self.frames)
-        self.ctx = self.eng.ctx
-        self.foff = np.concatenate([[0], np.cumsum([len(f[0]) for f in self.fix])])
-        self.files = [self.pipeline.BatchFile(self.foff[i], len(f[0]), [(a / RATE, b / RATE) for a, b in f[1]])
-                      for i, f in enumerate(self.fix)]
-        self.seg_off = np.concatenate([[0], np.cumsum([len(f[3]) for f in self.fix])]).astype(np.int64)
-        self.labels = [np.array([k + 1 for _, _, k in f[3]], dtype=np.int32) for f in self.fix]
-        self.d_stats = self.eng._stats_of_sets([[(int(self.foff[i] + a), int(self.foff[i] + b))] for i, f in enumerate(self.fix)
-                                                for a, b, _ in f[3]])
-
-    def run(self, reseg, detail=None, timings=None):
-        return self.pipeline.resegment_batch(self.ctx, self.eng.d_frames, len(self.frames), self.files, self.d_stats,
-                                             self.seg_off, self.labels, RATE, reseg, False, timings, detail)
-
-    def close(self):
-        self.ctx.dev_free(self.d_stats)
-        self.eng.close()
-
-
 @pytest.fixture(scope='module')
 def batch():
-    b = _Batch()
+    """The two fixtures as one two-file batch resident on the device, with the records, labels and
+    segments of their displaced input."""
+    fix = [_fixture(i) for i in range(len(FIXTURES))]
+    b = Batch([(feats, vad, segs) for feats, vad, _, segs, _, _ in fix])
+    b.fix = fix
     yield b
     b.close()
 
