@@ -537,7 +537,25 @@ spkd_status spkd_ahc_fused(spkd_ctx *ctx, const float *d_frames, int64_t n_frame
  * file leaves open are documented choices (oracle/mfcc_numpy.py).
  * d_pcm: n_samples 16-bit mono samples in device memory; the caller passes the tables
  * (host): mel filterbank [21][257], DCT [12][21], mean[39], scale[39], transform[39][39].
- * d_features receives floor(n_samples / hop) frames of 39 floats (*h_n_frames). */
+ * d_features receives floor(n_samples / hop) frames of 39 floats (*h_n_frames).
+ * Accepted parameters (anything else is SPKD_EINVAL before any device work):
+ *   window_width 400 or 256, n_fft 512, n_mel 21, n_cep 12; frame_rate > 0 dividing sample_rate;
+ *   cms_left >= 0, cms_right >= 0 (0, 0: every frame is its own mean, the mean-subtracted block
+ *     is 0), cms_left + cms_right <= SPKD_MFCC_CMS_MAX: the post stage keeps the static rows of a
+ *     tile of SPKD_MFCC_POST_TILE frames, its halo of SPKD_MFCC_POST_HALO to either side and the
+ *     mean window in LDS, and
+ *       4 * (13 * (3 * (TILE + 2 * HALO) + cms_left + cms_right) + 39 * TILE + 39 * 39)
+ *     bytes must not exceed SPKD_MFCC_POST_LDS;
+ *   delta_width[0], delta_width[1] each 1 or 2; delta_norm[0], delta_norm[1] > 0 (a NaN is refused).
+ * Borders, for a file of T frames, T >= 1 (there is no lower limit; T = 0 writes nothing):
+ *   a sample index outside [0, n_samples) is the nearest sample of the file, the predecessor of
+ *     sample 0 is sample 0; a file shorter than a window has both ends of every window clamped;
+ *   the mean of frame t is over the frames max(t - cms_left, 0) .. min(t + cms_right, T - 1) and
+ *     divides by their count;
+ *   d[t] = sum_{k=1..width} k (x[min(t + k, T - 1)] - x[max(t - k, 0)]) / norm, in both delta
+ *     stages, the second over the first's d[0 .. T): for T below the reach of the deltas
+ *     (T <= delta_width[0] + delta_width[1]) both clamps act on every frame, and T = 1 gives
+ *     deltas and delta-deltas of exactly 0. */
 typedef struct {
     int32_t sample_rate, frame_rate, window_width, n_fft, n_mel, n_cep;
     int32_t cms_left, cms_right;
@@ -545,6 +563,10 @@ typedef struct {
     float pre_emph;
     float delta_norm[2];
 } spkd_mfcc_params;
+#define SPKD_MFCC_POST_TILE 128
+#define SPKD_MFCC_POST_HALO 4
+#define SPKD_MFCC_POST_LDS 61440
+#define SPKD_MFCC_CMS_MAX 272
 spkd_status spkd_mfcc(spkd_ctx *ctx, const int16_t *d_pcm, int64_t n_samples,
                       const spkd_mfcc_params *params, const float *h_melfb, const float *h_dct,
                       const float *h_mean, const float *h_scale, const float *h_transform,

@@ -51,8 +51,12 @@ def dct_matrix(n_cep, n_mel=N_MEL):
     return np.sqrt(2.0 / n_mel) * np.cos(np.pi * k * (m + 0.5) / n_mel)
 
 
-def static_features(pcm, cfg):
-    """int16 / float samples -> [T, n_cep + 1] (cepstra 1..n_cep, log power), float64."""
+def static_features(pcm, cfg, melfb=None, dct=None):
+    """int16 / float samples -> [T, n_cep + 1] (cepstra 1..n_cep, log power), float64.
+    melfb [N_MEL, 257] and dct [n_cep, N_MEL] stand for the two tables the caller of the device
+    code passes (None: this module's own)."""
+    melfb = mel_filterbank(cfg.sample_rate) if melfb is None else np.asarray(melfb, dtype=np.float64)
+    dct = dct_matrix(cfg.n_cep) if dct is None else np.asarray(dct, dtype=np.float64)
     x = np.asarray(pcm, dtype=np.float64)
     n_frames = len(x) // cfg.hop
     half = cfg.window_width // 2
@@ -61,8 +65,8 @@ def static_features(pcm, cfg):
     prev = x[np.clip(idx - 1, 0, len(x) - 1)]
     y = (cur - cfg.pre_emph * prev) * np.hamming(cfg.window_width)[None, :]
     mag = np.abs(np.fft.rfft(y, n=N_FFT, axis=1))
-    logmel = np.log(np.maximum(mag @ mel_filterbank(cfg.sample_rate).T, 1e-10))
-    cep = logmel @ dct_matrix(cfg.n_cep).T
+    logmel = np.log(np.maximum(mag @ melfb.T, 1e-10))
+    cep = logmel @ dct.T
     power = np.log(np.maximum((mag ** 2).sum(axis=1), 1e-10))
     return np.concatenate([cep, power[:, None]], axis=1)
 
@@ -76,17 +80,26 @@ def _delta(x, width, norm):
     return out / norm
 
 
-def features(pcm, cfg):
-    """The whole chain: float32 [T, 39]."""
-    s = static_features(pcm, cfg)
+def stage_features(pcm, cfg, melfb=None, dct=None):
+    """The chain up to the merge, before normalization and transform: float64 [T, 39], the
+    mean-subtracted statics, the deltas and the delta-deltas (melfb, dct: as static_features)."""
+    s = static_features(pcm, cfg, melfb, dct)
     T = s.shape[0]
     if T == 0:
-        return np.zeros((0, cfg.dim), dtype=np.float32)
+        return np.zeros((0, 3 * s.shape[1]))
     c = np.concatenate([np.zeros((1, s.shape[1])), np.cumsum(s, axis=0)])
     lo = np.maximum(np.arange(T) - cfg.cms_left, 0)
     hi = np.minimum(np.arange(T) + cfg.cms_right + 1, T)
     cms = s - (c[hi] - c[lo]) / (hi - lo)[:, None]
     d1 = _delta(cms, cfg.delta_width[0], cfg.delta_norm[0])
     d2 = _delta(d1, cfg.delta_width[1], cfg.delta_norm[1])
-    z = (np.concatenate([cms, d1, d2], axis=1) - cfg.mean[None, :]) * cfg.scale[None, :]
+    return np.concatenate([cms, d1, d2], axis=1)
+
+
+def features(pcm, cfg, melfb=None, dct=None):
+    """The whole chain: float32 [T, 39] (melfb, dct: as static_features)."""
+    x = stage_features(pcm, cfg, melfb, dct)
+    if x.shape[0] == 0:
+        return np.zeros((0, cfg.dim), dtype=np.float32)
+    z = (x - cfg.mean[None, :]) * cfg.scale[None, :]
     return (z @ cfg.transform.astype(np.float64).T).astype(np.float32)

@@ -1922,18 +1922,19 @@ spkd_status mfcc_check(spkd_ctx* c, const spkd_mfcc_params* P, const float* h_me
     if ((P->window_width != MF_WIN && P->window_width != MF_WIN_VAD) || P->n_fft != MF_NFFT || P->n_mel != MF_MEL ||
         P->n_cep != MF_CEP || P->frame_rate <= 0 || P->sample_rate <= 0 || P->sample_rate % P->frame_rate != 0)
         return fail(c, SPKD_EINVAL, "mfcc: this build does 400- or 256-sample windows, a 512-point transform, 21 mel bins, 12 cepstra");
-    if (P->cms_left < 0 || P->cms_right < 0 || P->cms_left + P->cms_right > 1024 || P->delta_width[0] < 1 ||
-        P->delta_width[0] > 2 || P->delta_width[1] < 1 || P->delta_width[1] > 2 || !(P->delta_norm[0] > 0.f) ||
-        !(P->delta_norm[1] > 0.f))
+    if (P->cms_left < 0 || P->cms_right < 0 || P->delta_width[0] < 1 || P->delta_width[0] > 2 || P->delta_width[1] < 1 ||
+        P->delta_width[1] > 2 || !(P->delta_norm[0] > 0.f) || !(P->delta_norm[1] > 0.f))
         return fail(c, SPKD_EINVAL, "mfcc: unsupported mean-subtraction window or delta parameters");
     *hop = P->sample_rate / P->frame_rate;
     if (*hop < 1) return fail(c, SPKD_EINVAL, "mfcc: frame rate above the sample rate");
-    const int span = MP_FR + 2 * MP_HALO;
-    *lds = (size_t)((span + P->cms_left + P->cms_right) * MF_STATIC + 2 * span * MF_STATIC + MP_FR * MF_DIM +
-                    MF_DIM * MF_DIM) * sizeof(float);
-    if (*lds > 60 * 1024) return fail(c, SPKD_EINVAL, "mfcc: mean-subtraction window too wide for the LDS tile");
+    // left + right <= MP_CMS_MAX is what mp_lds_floats fits into MP_LDS_MAX (compared so that no sum overflows)
+    if (P->cms_left > MP_CMS_MAX || P->cms_right > MP_CMS_MAX - P->cms_left)
+        return fail(c, SPKD_EINVAL, "mfcc: mean-subtraction window too wide for the LDS tile");
+    *lds = (size_t)mp_lds_floats(P->cms_left + P->cms_right) * sizeof(float);
     return SPKD_OK;
 }
+static_assert(MP_FR == SPKD_MFCC_POST_TILE && MP_HALO == SPKD_MFCC_POST_HALO && MP_LDS_MAX == SPKD_MFCC_POST_LDS &&
+              MP_CMS_MAX == SPKD_MFCC_CMS_MAX && MF_STATIC == 13, "the header states the post stage's tile and limit");
 
 extern "C++" {
 template <int WIN>

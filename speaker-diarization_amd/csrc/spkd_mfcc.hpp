@@ -25,6 +25,19 @@ constexpr int MF_TPB = 256;
 constexpr float MF_FLOOR = 1e-10f;
 constexpr int MP_FR = 128;           // frames per workgroup (post stage)
 constexpr int MP_HALO = 4;           // two delta stages of width 2
+constexpr int MP_SPAN = MP_FR + 2 * MP_HALO;   // frames whose cms / first deltas a post tile forms
+constexpr int MP_LDS_MAX = 60 * 1024;          // bytes of LDS a post tile may take (SPKD_MFCC_POST_LDS)
+
+// floats of LDS of a post tile whose mean window is left + right = cms frames wide: the staged
+// static rows, cms and d1 over the span, the normalized rows, the transform (k_mfcc_post carves
+// them in this order)
+__host__ __device__ constexpr int mp_lds_floats(int cms) {
+    return (MP_SPAN + cms) * MF_STATIC + 2 * MP_SPAN * MF_STATIC + MP_FR * MF_DIM + MF_DIM * MF_DIM;
+}
+// the widest mean window, left + right, that fits (SPKD_MFCC_CMS_MAX)
+constexpr int MP_CMS_MAX = (MP_LDS_MAX / (int)sizeof(float) - mp_lds_floats(0)) / MF_STATIC;
+static_assert(mp_lds_floats(MP_CMS_MAX) * sizeof(float) <= MP_LDS_MAX &&
+              mp_lds_floats(MP_CMS_MAX + 1) * sizeof(float) > MP_LDS_MAX, "MP_CMS_MAX is the last width that fits");
 
 // The twiddle table is padded by one entry per 32: a lane of bin k reads entry k n mod 512, and
 // for n a multiple of 16 a plain table has the 32 lanes of a group on one LDS bank.

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(MF_TPB) void k_mfcc_post(
         const float* __restrict__ mean, const float* __restrict__ scale, const float* __restrict__ transform,
         float* __restrict__ out /* [sum T][39] */) {
     extern __shared__ float mp_lds[];
-    const int span = MP_FR + 2 * MP_HALO;                  // frames whose cms / deltas are formed here
+    const int span = MP_SPAN;                              // frames whose cms / deltas are formed here
     const int raw_n = span + cms_left + cms_right;         // static rows staged
     float* raw = mp_lds;                                   // [raw_n][13]
     float* cms = raw + raw_n * MF_STATIC;                  // [span][13]

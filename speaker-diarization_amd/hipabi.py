@@ -35,6 +35,10 @@ GMM_CHUNK_TILES = 16    # SPKD_GMM_CHUNK_TILES: tiles per chunk, the unit of a p
 BW_COMP = 40        # SPKD_BW_COMP: doubles per component of a speaker record under a UBM (n_c, f_c[39])
 CLR_MAX_N = 4096    # SPKD_CLR_MAX_N: speakers of one spkd_clr_link
 GALLERY_MAX_N = 16384   # SPKD_GALLERY_MAX_N: identities of one spkd_clr_identify
+MFCC_POST_TILE = 128    # SPKD_MFCC_POST_TILE: frames per workgroup of k_mfcc_post
+MFCC_POST_HALO = 4      # SPKD_MFCC_POST_HALO: frames to either side of a tile whose first deltas it forms
+MFCC_POST_LDS = 61440   # SPKD_MFCC_POST_LDS: bytes of LDS a tile of k_mfcc_post may take
+MFCC_CMS_MAX = 272      # SPKD_MFCC_CMS_MAX: the widest mean window, cms_left + cms_right, that fits them
 REC = 820
 DIM = 39
 

@@ -19,6 +19,7 @@ import pytest
 import vad_numpy as vn
 from conftest import pkg
 from helpers import ROOT
+from mfcc_compare import full_chain_bound, full_chain_ratios
 from test_frontend import GOLD as FEA_GOLD, _cfg_text
 
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
@@ -400,8 +401,11 @@ def test_hip_front_end_does_256_sample_windows():
         want = m.features(pcm, cfg)
         got = fe.extract(pcm, cfg)
         assert got.shape == want.shape and np.all(np.isfinite(got))
-        scale = max(1.0, float(np.abs(want).max()))
-        assert float(np.max(np.abs(got - want))) < 2e-3 * scale, (seconds, float(np.max(np.abs(got - want))))
+        # test_mfcc_reference's bound on this signal (never above the former 2e-3 of the feature scale)
+        r = full_chain_ratios(got, pcm, cfg)
+        print('%.1f s: device error / bound at most %.3f (column %d)' % (seconds, r.max(), r.argmax()))
+        assert np.all(r <= 1.0), (seconds, int(r.argmax()), float(r.max()))
+        assert full_chain_bound(pcm, cfg).max() < 2e-3 * max(1.0, float(np.abs(want).max()))
 
 
 @pytest.mark.gpu
