@@ -99,7 +99,7 @@ enum {
     SPKD_T_CALL = 0, SPKD_T_CHUNK_STATS, SPKD_T_REDUCE_SETS, SPKD_T_PAIR_TERMS,
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
-    SPKD_T_POST_STATS,
+    SPKD_T_POST_STATS, SPKD_T_RESAMPLE,
     SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
     SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK, SPKD_T_FB_POSTERIOR,
     SPKD_T_IDENT_SCORES, SPKD_T_IDENT_ASSIGN, SPKD_T_BW_ACCUMULATE,
@@ -596,6 +596,66 @@ spkd_status spkd_mfcc_batch(spkd_ctx *ctx, const int16_t *d_pcm, int64_t n_files
                             const spkd_mfcc_params *params, const float *h_melfb, const float *h_dct,
                             const float *h_mean, const float *h_scale, const float *h_transform,
                             float *d_features, int64_t *h_frame_off /* out [n_files + 1] */);
+
+/* ---------------------------------------------------------------------------
+ * (6b) Sample-rate conversion and downmix of a batch's audio: what `ffmpeg -i x -ar 16000 -ac 1`
+ * does for the reference in front of everything else (spk-diarization2.py:83; an external program,
+ * not in the reference tree).  One launch (k_resample) serves every file of the batch, whatever
+ * mixture of rates and channel counts it holds, with one wait at the end; the output lies exactly
+ * as spkd_mfcc_batch reads it.  PARITY UNPINNED: ffmpeg is not available, its resampler's filter
+ * is not restated; the filter below is a documented choice (tests/resample_numpy.py restates it).
+ *
+ * The filter is designed on the host and handed over as a table, as the mel and DCT tables of
+ * spkd_mfcc are.  For a conversion rate_in -> rate_out with g = gcd: up = L = rate_out / g,
+ * down = M = rate_in / g, r = min(1, L / M), half_taps = ceil(16 / r), fc = 0.92 r, and for
+ * phase p in [0, L), tap k in [-half + 1, half]:  t = k - p / L,
+ *   h[p][k] = fc sinc(fc t) I0(9 sqrt(1 - (t / half)^2)) / I0(9)     (sinc(x) = sin(pi x) / (pi x)),
+ * every row divided by its own sum (DC gain 1 at every phase): a Kaiser window (beta = 9) over 16
+ * zero crossings to either side, half-amplitude point at 0.92 of the lower Nyquist frequency.  The
+ * table is float32 [L][2 half_taps], row p at h_taps[taps_off + p * 2 * half_taps], tap k at
+ * column k + half_taps - 1.  The call takes any table of that shape: it checks the shape, not the
+ * design.
+ *
+ * Layout: file f owns the interleaved int16 elements d_in[h_in_off[f] .. h_in_off[f+1]) (h_in_off[0]
+ * = 0, non-decreasing; a file may be empty; offsets of any parity), has h_channels[f] channels
+ * (the span is a multiple of it), n_in = span / channels sample frames, and the conversion
+ * h_convs[h_conv[f]].  s[j] is the exact integer sum of the channels of frame j, 0 for j outside
+ * [0, n_in): zero padding per file, nothing of a neighbouring file enters (a workgroup's tile of
+ * SPKD_RESAMPLE_TILE output samples never crosses a file).
+ *   identity (up == down == 1, half_taps == 0):  n_out = n_in,  y[n] = rint((double)s[n] / channels);
+ *   filtered:  n_out = ceil(n_in up / down) (every output instant inside the input's span); for
+ *     output n:  i = n down div up,  p = n down mod up,
+ *     acc = sum_k (double)h[p][k] s[i + k]   in fp64, k ascending,    y[n] = rint(acc / channels);
+ * rint rounds half to even, the division is one correctly rounded fp64 division; y is saturated
+ * to [-32768, 32767] (upsampled full-scale noise does overshoot) and stored as int16.  fp64
+ * accumulation keeps any two evaluations within about 2 half 2^-53 sum |h||s| ~ 2e-8 of each other,
+ * so the int16 result is the same almost everywhere whoever computes it.
+ * h_out_off (out, n_files + 1 entries) is the running sum of n_out; file f's mono samples are
+ * d_out[h_out_off[f] .. h_out_off[f+1]).
+ * Refusals (SPKD_EINVAL before any device work): n_files < 0 or n_conv < 0; a null host array;
+ * offsets that do not start at 0 or decrease; a span that is no multiple of the file's channel
+ * count; a channel count outside [1, SPKD_RESAMPLE_MAX_CH]; a conversion index out of range; up or
+ * down outside [1, SPKD_RESAMPLE_MAX_TERM]; gcd(up, down) != 1; half_taps outside [0,
+ * SPKD_RESAMPLE_MAX_HALF]; half_taps == 0 unless up == down == 1, and the converse; taps_off < 0;
+ * a table of more than SPKD_RESAMPLE_MAX_TAPS floats; a tile whose input span,
+ * ceil(SPKD_RESAMPLE_TILE down / up) + 2 half_taps frames, exceeds SPKD_RESAMPLE_MAX_SPAN (the
+ * span is kept in LDS; a designed filter of at most SPKD_RESAMPLE_MAX_HALF never does); null tables
+ * with a filtered conversion; null device pointers only when there is a sample.  No file, or no
+ * sample in any: SPKD_OK, h_out_off filled, nothing launched.
+ * Timer: SPKD_T_RESAMPLE. */
+typedef struct { int32_t up, down, half_taps; int64_t taps_off; } spkd_resample_conv;
+#define SPKD_RESAMPLE_TILE 2048
+#define SPKD_RESAMPLE_MAX_CH 8
+#define SPKD_RESAMPLE_MAX_HALF 256
+#define SPKD_RESAMPLE_MAX_TERM 1048576
+#define SPKD_RESAMPLE_MAX_TAPS 4194304
+#define SPKD_RESAMPLE_MAX_SPAN 33281
+spkd_status spkd_resample_batch(spkd_ctx *ctx, const int16_t *d_in, int64_t n_files,
+                                const int64_t *h_in_off /* [n_files + 1], int16 elements */,
+                                const int32_t *h_channels /* [n_files] */,
+                                const int32_t *h_conv /* [n_files] -> h_convs */, int32_t n_conv,
+                                const spkd_resample_conv *h_convs, const float *h_taps /* all tables, concatenated */,
+                                int16_t *d_out, int64_t *h_out_off /* out [n_files + 1] */);
 
 /* ---------------------------------------------------------------------------
  * (7) Speech / non-speech frame scoring: the per-frame state log-likelihoods that AaltoASR's

@@ -22,6 +22,7 @@
 #include "spkd_post_stats.hpp"
 #include "spkd_mfcc.hpp"
 #include "spkd_mfcc_batch.hpp"
+#include "spkd_resample.hpp"
 #include "spkd_vad.hpp"
 #include "spkd_vad_batch.hpp"
 #include "spkd_mindur.hpp"
@@ -55,6 +56,7 @@ struct spkd_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     bool gw_lds_ok = false;
+    int rs_lds_cap = 0;          // dynamic LDS bytes admitted for k_resample
     int gw_waves = 0;
     unsigned long long init_keys[2] = {0ull, ~0ull};
     int step_waves = 0;          // step chain: waves per workgroup (0 = by problem size, 4, 8)
@@ -276,7 +278,7 @@ enum {
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
     S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT,
     S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_FB_TAB, S_FB_FWD, S_FB_OUT,
-    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_COUNT
+    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -322,6 +324,13 @@ static spkd_status create_ctx(int device, void* stream, bool borrow, spkd_ctx** 
                    hipFuncSetAttribute((const void*)k_gw<4>, hipFuncAttributeMaxDynamicSharedMemorySize, Gw<4>::LDS_BYTES) == hipSuccess &&
                    hipFuncSetAttribute((const void*)k_gw<2>, hipFuncAttributeMaxDynamicSharedMemorySize, Gw<2>::LDS_BYTES) == hipSuccess &&
                    hipFuncSetAttribute((const void*)k_gw<1>, hipFuncAttributeMaxDynamicSharedMemorySize, Gw<1>::LDS_BYTES) == hipSuccess;
+    // k_resample carves a tile's span and table dynamically, up to the whole LDS where the device admits it
+    c->rs_lds_cap = 64 * 1024;
+    if (lds_max > c->rs_lds_cap) {
+        const int want = lds_max < RS_LDS_MAX ? lds_max : RS_LDS_MAX;
+        if (hipFuncSetAttribute((const void*)k_resample, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess)
+            c->rs_lds_cap = want;
+    }
     // waves per turn of the growing-window kernel: 0 = by the number of turns (gw_impl)
     if (const char* e = getenv("SPKD_GW_WAVES")) c->gw_waves = atoi(e);
     if (const char* e = getenv("SPKD_STEP_WAVES")) { const int v = atoi(e); c->step_waves = (v == 4 || v == 8) ? v : 0; }
@@ -2023,6 +2032,93 @@ spkd_status spkd_mfcc(spkd_ctx* c, const int16_t* d_pcm, int64_t n_samples, cons
                                            d_features, frame_off);
     *h_n_frames = frame_off[1];
     return st;
+}
+
+// ------------------------------------------------------------------ (6b) sample-rate conversion and downmix
+static_assert(RS_TILE == SPKD_RESAMPLE_TILE && RS_MAX_CH == SPKD_RESAMPLE_MAX_CH && RS_MAX_HALF == SPKD_RESAMPLE_MAX_HALF &&
+              RS_MAX_TAPS == SPKD_RESAMPLE_MAX_TAPS && RS_MAX_TERM == SPKD_RESAMPLE_MAX_TERM && RS_MAX_SPAN == SPKD_RESAMPLE_MAX_SPAN,
+              "the header states the resampler's tile and limits");
+
+spkd_status spkd_resample_batch(spkd_ctx* c, const int16_t* d_in, int64_t n_files, const int64_t* h_in_off,
+                                const int32_t* h_channels, const int32_t* h_conv, int32_t n_conv,
+                                const spkd_resample_conv* h_convs, const float* h_taps, int16_t* d_out, int64_t* h_out_off) {
+    if (!c) return SPKD_EINVAL;
+    if (n_files < 0 || n_conv < 0) return fail(c, SPKD_EINVAL, "resample_batch: negative file or conversion count");
+    if (!h_in_off || !h_out_off || (n_files > 0 && (!h_channels || !h_conv)) || (n_conv > 0 && !h_convs))
+        return fail(c, SPKD_EINVAL, "resample_batch: null host array");
+    if (h_in_off[0] != 0) return fail(c, SPKD_EINVAL, "resample_batch: in_off must start at 0");
+    for (int64_t f = 0; f < n_files; ++f)
+        if (h_in_off[f + 1] < h_in_off[f]) return fail(c, SPKD_EINVAL, "resample_batch: in_off must be non-decreasing");
+    for (int64_t f = 0; f < n_files; ++f) {
+        if (h_channels[f] < 1 || h_channels[f] > RS_MAX_CH)
+            return fail(c, SPKD_EINVAL, "resample_batch: channel count outside [1, 8]");
+        if ((h_in_off[f + 1] - h_in_off[f]) % h_channels[f] != 0)
+            return fail(c, SPKD_EINVAL, "resample_batch: a file's span is not a multiple of its channel count");
+        if (h_conv[f] < 0 || h_conv[f] >= n_conv) return fail(c, SPKD_EINVAL, "resample_batch: conversion index out of range");
+    }
+    std::vector<RsConv> convs((size_t)n_conv);
+    int64_t n_taps = 0;                              // floats of h_taps the conversions reach
+    for (int32_t k = 0; k < n_conv; ++k) {
+        const spkd_resample_conv& v = h_convs[k];
+        if (v.up < 1 || v.down < 1 || v.up > RS_MAX_TERM || v.down > RS_MAX_TERM)
+            return fail(c, SPKD_EINVAL, "resample_batch: up and down must lie in [1, 2^20]");
+        int a = v.up, b = v.down;
+        while (b) { const int t = a % b; a = b; b = t; }
+        if (a != 1) return fail(c, SPKD_EINVAL, "resample_batch: up and down must be coprime");
+        if (v.half_taps < 0 || v.half_taps > RS_MAX_HALF) return fail(c, SPKD_EINVAL, "resample_batch: half_taps outside [0, 256]");
+        if ((v.half_taps == 0) != (v.up == 1 && v.down == 1))
+            return fail(c, SPKD_EINVAL, "resample_batch: half_taps is 0 for the identity conversion (up == down == 1) and for no other");
+        if (v.taps_off < 0) return fail(c, SPKD_EINVAL, "resample_batch: negative taps_off");
+        const int64_t table = (int64_t)v.up * 2 * v.half_taps;
+        if (table > RS_MAX_TAPS) return fail(c, SPKD_EINVAL, "resample_batch: a table of more than 2^22 taps");
+        if (rs_span(v.up, v.down, v.half_taps) > RS_MAX_SPAN)
+            return fail(c, SPKD_EINVAL, "resample_batch: a tile's input span exceeds the LDS (down / up too large for half_taps)");
+        if (v.half_taps > 0 && !h_taps) return fail(c, SPKD_EINVAL, "resample_batch: null tables with a filtered conversion");
+        if (v.half_taps > 0) n_taps = std::max(n_taps, v.taps_off + table);
+        convs[(size_t)k] = RsConv{v.up, v.down, v.half_taps, 0, (long long)v.taps_off};
+    }
+    // the output layout, and the running count of tiles: a tile lies in one file
+    const size_t n1 = (size_t)n_files + 1;
+    std::vector<int64_t> tiles(n1, 0);
+    h_out_off[0] = 0;
+    size_t lds = 0;
+    for (int64_t f = 0; f < n_files; ++f) {
+        RsConv& v = convs[(size_t)h_conv[f]];
+        const int64_t n_in = (h_in_off[f + 1] - h_in_off[f]) / h_channels[f];
+        const int64_t n_out = (n_in * v.up + v.down - 1) / v.down;
+        h_out_off[f + 1] = h_out_off[f] + n_out;
+        tiles[(size_t)f + 1] = tiles[(size_t)f] + (n_out + RS_TILE - 1) / RS_TILE;
+        if (n_out == 0 || v.half == 0) continue;
+        // the table goes to LDS beside the span where the device admits both
+        const size_t span = (size_t)rs_span_bytes(v.up, v.down, v.half), both = span + (size_t)rs_table_bytes(v.up, v.half);
+        v.in_lds = both <= (size_t)c->rs_lds_cap;
+        lds = std::max(lds, v.in_lds ? both : span);
+    }
+    if (h_out_off[n_files] == 0) return SPKD_OK;
+    if (!d_in || !d_out) return fail(c, SPKD_EINVAL, "resample_batch: null device buffer");
+    if (tiles[(size_t)n_files] > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "resample_batch: too many samples in one call");
+    if (lds > (size_t)c->rs_lds_cap)
+        return fail(c, SPKD_EHIP, "resample_batch: the kernel's dynamic LDS size was not admitted on this device");
+    int64_t *d_ioff, *d_ooff, *d_tiles;
+    int32_t *d_ch, *d_conv;
+    RsConv* d_convs;
+    float* d_taps;
+    std::vector<char> tab;
+    Call call(c);
+    TRY(call.opened);
+    TRY(upload_parts(c, S_RS_TAB, tab, [&](Layout L) {
+        return L.part(d_ioff, n1, h_in_off).part(d_ooff, n1, (const int64_t*)h_out_off).part(d_tiles, n1, (const int64_t*)tiles.data())
+            .part(d_ch, (size_t)n_files, h_channels).part(d_conv, (size_t)n_files, h_conv)
+            .part(d_convs, (size_t)n_conv, (const RsConv*)convs.data()).part(d_taps, (size_t)n_taps, h_taps).bytes();
+    }));
+    {
+        Timer t(c, SPKD_T_RESAMPLE);
+        hipLaunchKernelGGL(k_resample, dim3((unsigned)tiles[(size_t)n_files]), dim3(RS_TPB), lds, c->stream, d_in,
+                           (const long long*)d_ioff, (const long long*)d_ooff, (const long long*)d_tiles, (long long)n_files,
+                           (const int*)d_ch, (const int*)d_conv, (const RsConv*)d_convs, (const float*)d_taps, d_out);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "resample_batch: kernel launch failed");
+    return call.finish();
 }
 
 // ------------------------------------------------------------------ (7) speech / non-speech scoring

@@ -9,6 +9,8 @@ choice the configuration file leaves open is listed in the test suite's numpy re
 feature file (int32 dim + float32 frames, spk-change-detection.py:37-41) on stdout.
 """
 import argparse
+import math
+import os
 import sys
 import time
 import wave
@@ -114,6 +116,144 @@ def upload_batch(ctx, pcms, timings=None):
     return d_pcm, sample_off
 
 
+def read_audio(path):
+    """Every channel of a 16-bit PCM .wav file, int16 [n, channels], and its sample rate: the input
+    of resample_batch (read_wav is the file `ffmpeg -ar 16000 -ac 1` left: mono only)."""
+    with wave.open(path, 'rb') as w:
+        if w.getsampwidth() != 2:
+            raise ValueError('%s: 16-bit PCM expected, the file has %d-bit samples' % (path, 8 * w.getsampwidth()))
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype='<i2')
+        return pcm.reshape(-1, w.getnchannels()), w.getframerate()
+
+
+RESAMPLE_ZERO_CROSSINGS, RESAMPLE_BETA, RESAMPLE_CUTOFF = 16, 9.0, 0.92
+
+
+def resample_ratio(rate_in, rate_out):
+    """(L, M, half) of the conversion rate_in -> rate_out: output n lies at input instant n M / L, and
+    half taps to either side of it enter (0: the identity conversion)."""
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    if rate_in < 1 or rate_out < 1:
+        raise ValueError('sample rates must be positive, got %d -> %d Hz' % (rate_in, rate_out))
+    g = math.gcd(rate_in, rate_out)
+    L, M = rate_out // g, rate_in // g
+    half = 0 if L == M else -((-RESAMPLE_ZERO_CROSSINGS * max(L, M)) // L)      # ceil(16 / min(1, L / M))
+    return L, M, half
+
+
+def resample_taps(rate_in, rate_out):
+    """The polyphase filter of spkd_resample_batch for rate_in -> rate_out (include/spkd.h has the
+    definition): (float32 [L, 2 half] table, (L, M, half)); the identity conversion has an empty
+    one.  A Kaiser-windowed sinc, beta 9, 16 zero crossings to either side, half-amplitude point at
+    0.92 of the lower Nyquist frequency, every phase normalised to DC gain 1; formed in float64.
+    PARITY UNPINNED: ffmpeg's resampler is not available and not restated."""
+    L, M, half = resample_ratio(rate_in, rate_out)
+    if half == 0:
+        return np.zeros((L, 0), dtype=np.float32), (L, M, half)
+    if half > hipabi.RESAMPLE_MAX_HALF or max(L, M) > hipabi.RESAMPLE_MAX_TERM or 2 * half * L > hipabi.RESAMPLE_MAX_TAPS:
+        raise ValueError('%d Hz -> %d Hz: a filter of %d phases x %d taps is beyond this build (at most %d taps to '
+                         'either side, %d in a table)' % (rate_in, rate_out, L, 2 * half, hipabi.RESAMPLE_MAX_HALF,
+                                                          hipabi.RESAMPLE_MAX_TAPS))
+    fc = RESAMPLE_CUTOFF * min(1.0, L / M)
+    t = np.arange(-half + 1, half + 1, dtype=np.float64)[None, :] - np.arange(L, dtype=np.float64)[:, None] / L
+    w = np.i0(RESAMPLE_BETA * np.sqrt(np.maximum(0.0, 1.0 - (t / half) ** 2))) / np.i0(RESAMPLE_BETA)
+    h = fc * np.sinc(fc * t) * np.where(np.abs(t) > half, 0.0, w)
+    h /= np.array([math.fsum(row) for row in h])[:, None]
+    return h.astype(np.float32), (L, M, half)
+
+
+def output_offsets(lengths, rates, rate_out):
+    """The output layout of spkd_resample_batch, on the host: a file of lengths[f] sample frames at
+    rates[f] Hz has ceil(n L / M) samples at rate_out (every output instant inside the input's
+    span; the identity conversion keeps n); returns their running sum, int64 [n_files + 1]."""
+    out = [0]
+    for n, rate in zip(lengths, rates):
+        L, M, _ = resample_ratio(rate, rate_out)
+        out.append(out[-1] + -((-int(n) * L) // M))
+    return np.array(out, dtype=np.int64)
+
+
+RESAMPLE_GROUP_BYTES = 256 << 20
+
+
+def _audio_files(audios):
+    """resample_batch's input, checked: [(int16 [n, channels], rate)]."""
+    files = []
+    for i, item in enumerate(audios):
+        try:
+            samples, rate = item
+        except (TypeError, ValueError):
+            raise ValueError('file %d: a (samples, rate) pair expected' % i)
+        a = np.asarray(samples)
+        if a.ndim not in (1, 2) or (a.size and a.dtype.kind not in 'iu'):
+            raise ValueError('file %d: int16 samples [n] or [n, channels] expected, got %s %r' % (i, a.dtype, a.shape))
+        if a.ndim == 1:
+            a = a.reshape(-1, 1)
+        if not 1 <= a.shape[1] <= hipabi.RESAMPLE_MAX_CH:
+            raise ValueError('file %d: 1 to %d channels expected, got %d' % (i, hipabi.RESAMPLE_MAX_CH, a.shape[1]))
+        if a.size and a.dtype != np.int16 and (int(a.min()) < -32768 or int(a.max()) > 32767):
+            raise ValueError('file %d: %s samples outside the int16 range' % (i, a.dtype))
+        if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)) or rate < 1:
+            raise ValueError('file %d: a positive integer sample rate expected, got %r' % (i, rate))
+        files.append((np.ascontiguousarray(a, dtype=np.int16), int(rate)))
+    return files
+
+
+def resample_batch(ctx, audios, rate_out, group_bytes=RESAMPLE_GROUP_BYTES, timings=None):
+    """The audio of a batch of files, audios = [(samples, rate)] with int16 samples [n] or
+    [n, channels], converted to mono at rate_out on the device (spkd_resample_batch) -> (d_pcm,
+    sample_off), exactly what upload_batch returns for the converted files: vad_batch(uploaded=...)
+    and features_batch(uploaded=...) take it unchanged.  The raw audio goes up in groups of whole
+    files of at most group_bytes (a larger file is a group of its own) into a scratch the context
+    keeps, and each group is converted into its place of the 'pcm_batch' buffer, whose offsets are
+    known beforehand (output_offsets): the raw scratch stays bounded, an hour of 48 kHz stereo being
+    six times its 16 kHz mono.  Anything but integer samples that fit int16, one to eight channels
+    and a positive integer rate is a ValueError before the context is touched."""
+    files = _audio_files(audios)
+    rate_out = int(rate_out)
+    if group_bytes < 1:
+        raise ValueError('group_bytes must be positive')
+    rates = sorted(set(rate for _, rate in files))
+    convs, tables, at = [], [], 0
+    for rate in rates:
+        h, (L, M, half) = resample_taps(rate, rate_out)
+        convs.append(hipabi.ResampleConv(L, M, half, at))
+        tables.append(h.ravel())
+        at += h.size
+    taps = np.concatenate(tables) if tables else np.zeros(0, dtype=np.float32)
+    conv = np.array([rates.index(rate) for _, rate in files], dtype=np.int32)
+    channels = np.array([a.shape[1] for a, _ in files], dtype=np.int32)
+    sample_off = output_offsets([len(a) for a, _ in files], [rate for _, rate in files], rate_out)
+    # groups of consecutive files
+    groups, first, size = [], 0, 0
+    for f, (a, _) in enumerate(files):
+        if f > first and size + a.nbytes > group_bytes:
+            groups.append((first, f))
+            first, size = f, 0
+        size += a.nbytes
+    if len(files) > first:
+        groups.append((first, len(files)))
+    biggest = max([sum(files[f][0].nbytes for f in range(lo, hi)) for lo, hi in groups] + [0])
+    d_pcm = ctx.dev_scratch('pcm_batch', max(2 * int(sample_off[-1]), 16))
+    d_raw = ctx.dev_scratch('audio_batch', max(biggest, 16))
+    wall, ms = 0.0, 0.0
+    for lo, hi in groups:
+        in_off = np.concatenate([[0], np.cumsum([files[f][0].size for f in range(lo, hi)])]).astype(np.int64)
+        _t0 = time.perf_counter()
+        for f, o in zip(range(lo, hi), in_off):
+            if files[f][0].size:
+                ctx.h2d(d_raw + 2 * int(o), files[f][0])
+        wall += time.perf_counter() - _t0
+        got = ctx.resample_batch(d_raw, in_off, channels[lo:hi], conv[lo:hi], convs, taps, d_pcm + 2 * int(sample_off[lo]))
+        assert np.array_equal(got, sample_off[lo:hi + 1] - sample_off[lo])
+        if got[-1]:
+            ms += ctx.last_ms('resample')
+    if timings is not None:
+        timings.setdefault('wall_upload', []).append(1e3 * wall)
+        timings.setdefault('resample', []).append(ms)
+    return d_pcm, sample_off
+
+
 def extract_batch(ctx, cfg, d_pcm, sample_off, d_out=None, timings=None):
     """Uploaded samples (upload_batch) -> (device pointer to the float32 [sum T, 39] features of
     every file, frame_off int64 [n_files + 1]) in one call (spkd_mfcc_batch).  d_out=None: a buffer
@@ -167,4 +307,32 @@ def main(argv=None, stdout=None):
     if args.header:
         out.write(np.array([feats.shape[1]], dtype='<i4').tobytes())
     out.write(np.ascontiguousarray(feats, dtype='<f4').tobytes())
+    return 0
+
+
+def to16k_main(argv=None):
+    """./to16k.py IN.wav [-o OUT.wav] [-r 16000]: one 16-bit PCM .wav of any rate and channel count
+    -> 16-bit mono at the rate the pipeline wants, converted on the device (resample_batch).  What a
+    user without ffmpeg runs in front of spk-diarization2.py for .wav input."""
+    ap = argparse.ArgumentParser(description='Resample and downmix a 16-bit PCM .wav on the device (the step '
+                                             '`ffmpeg -ar 16000 -ac 1` is for .wav input).')
+    ap.add_argument('wav')
+    ap.add_argument('-o', dest='out', default=None, help='output file (default: IN.16k.wav beside the input)')
+    ap.add_argument('-r', dest='rate', type=int, default=16000, help='output sample rate')
+    args = ap.parse_args(argv)
+    out = args.out or os.path.splitext(args.wav)[0] + '.16k.wav'
+    samples, rate = read_audio(args.wav)
+    ctx = hipabi.Context(0)
+    try:
+        d_pcm, sample_off = resample_batch(ctx, [(samples, rate)], args.rate)
+        pcm = np.zeros(int(sample_off[-1]), dtype=np.int16)
+        if pcm.size:
+            ctx.d2h(pcm, d_pcm)
+    finally:
+        ctx.close()
+    with wave.open(out, 'wb') as w:
+        w.setnchannels(1)
+        w.setsampwidth(2)
+        w.setframerate(args.rate)
+        w.writeframes(pcm.astype('<i2').tobytes())
     return 0

@@ -17,7 +17,7 @@ MERGE_NO_AHEAD = 1
 TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pair_terms',
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
-                                        'post_stats',
+                                        'post_stats', 'resample',
                                         'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
                                         'mindur_viterbi', 'mindur_backtrack', 'fb_posterior',
                                         'ident_scores', 'ident_assign', 'bw_accumulate',
@@ -39,13 +39,19 @@ MFCC_POST_TILE = 128    # SPKD_MFCC_POST_TILE: frames per workgroup of k_mfcc_po
 MFCC_POST_HALO = 4      # SPKD_MFCC_POST_HALO: frames to either side of a tile whose first deltas it forms
 MFCC_POST_LDS = 61440   # SPKD_MFCC_POST_LDS: bytes of LDS a tile of k_mfcc_post may take
 MFCC_CMS_MAX = 272      # SPKD_MFCC_CMS_MAX: the widest mean window, cms_left + cms_right, that fits them
+RESAMPLE_TILE = 2048        # SPKD_RESAMPLE_TILE: output samples per workgroup of k_resample
+RESAMPLE_MAX_CH = 8         # SPKD_RESAMPLE_MAX_CH: channels of a file
+RESAMPLE_MAX_HALF = 256     # SPKD_RESAMPLE_MAX_HALF: taps to either side of an output instant
+RESAMPLE_MAX_TERM = 1 << 20     # SPKD_RESAMPLE_MAX_TERM: up and down of a conversion
+RESAMPLE_MAX_TAPS = 1 << 22     # SPKD_RESAMPLE_MAX_TAPS: floats of one conversion's table
+RESAMPLE_MAX_SPAN = 33281   # SPKD_RESAMPLE_MAX_SPAN: input frames a tile may read
 REC = 820
 DIM = 39
 
 EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_destroy', 'spkd_last_error', 'spkd_sync',
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_set_stats', 'spkd_pair_terms',
-           'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_sum_stats', 'spkd_mfcc', 'spkd_mfcc_batch',
+           'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_sum_stats', 'spkd_mfcc', 'spkd_mfcc_batch', 'spkd_resample_batch',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
@@ -81,6 +87,12 @@ class MfccParams(C.Structure):
                 ('n_fft', C.c_int32), ('n_mel', C.c_int32), ('n_cep', C.c_int32), ('cms_left', C.c_int32),
                 ('cms_right', C.c_int32), ('delta_width', C.c_int32 * 2), ('pre_emph', C.c_float),
                 ('delta_norm', C.c_float * 2)]
+
+
+class ResampleConv(C.Structure):
+    """spkd_resample_conv: up / down of a conversion, the taps to either side of an output instant
+    and where its table [up][2 half_taps] starts in the concatenated tables."""
+    _fields_ = [('up', C.c_int32), ('down', C.c_int32), ('half_taps', C.c_int32), ('taps_off', C.c_int64)]
 
 
 class GmmParams(C.Structure):
@@ -206,6 +218,7 @@ def load_library(path=None):
     lib.spkd_sum_stats.argtypes = [vp, vp, i64, vp, vp, i64, vp]
     lib.spkd_mfcc.argtypes = [vp, vp, i64, P(MfccParams), vp, vp, vp, vp, vp, vp, P(i64)]
     lib.spkd_mfcc_batch.argtypes = [vp, vp, i64, vp, P(MfccParams), vp, vp, vp, vp, vp, vp, vp]
+    lib.spkd_resample_batch.argtypes = [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.spkd_sw_window_count.argtypes = [i64, dbl, dbl]
     lib.spkd_sw_window_count.restype = i64
     lib.spkd_sw.argtypes = [vp, vp, i64, vp, vp, i64, P(CdParams), vp, vp]
@@ -745,6 +758,29 @@ class Context(object):
         self.check(self.lib.spkd_mfcc_batch(self.h, C.c_void_p(d_pcm), len(off) - 1, _ptr(off), C.byref(params),
                                             *[_ptr(a) for a in arrs], C.c_void_p(d_features), _ptr(frame_off)))
         return frame_off
+
+    # ---- (6b)
+    def resample_batch(self, d_in, in_off, channels, conv, convs, taps, d_out):
+        """Interleaved int16 files on the device -> mono int16 at one rate (spkd_resample_batch):
+        file f owns the elements [in_off[f], in_off[f+1]) of d_in, has channels[f] channels and the
+        conversion convs[conv[f]] (ResampleConv, or (up, down, half_taps, taps_off)); taps: every
+        conversion's float32 table, concatenated.  Its samples land at [out_off[f], out_off[f+1])
+        of d_out.  Returns out_off (int64, one entry per file and the total)."""
+        off = np.ascontiguousarray(in_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1:
+            raise SpkdError(SPKD_EINVAL, 'in_off: one entry per file and the total')
+        ch = np.ascontiguousarray(channels, dtype=np.int32)
+        cv = np.ascontiguousarray(conv, dtype=np.int32)
+        if ch.shape != (len(off) - 1,) or cv.shape != ch.shape:
+            raise SpkdError(SPKD_EINVAL, 'channels, conv: one entry per file')
+        table = (ResampleConv * max(len(convs), 1))(*[v if isinstance(v, ResampleConv) else ResampleConv(*[int(x) for x in v])
+                                                      for v in convs])
+        taps = np.ascontiguousarray(taps, dtype=np.float32).ravel()
+        out_off = np.zeros(len(off), dtype=np.int64)
+        self.check(self.lib.spkd_resample_batch(self.h, C.c_void_p(d_in), len(off) - 1, _ptr(off), _ptr(ch), _ptr(cv),
+                                                len(convs), table, _ptr(taps) if taps.size else None,
+                                                C.c_void_p(d_out), _ptr(out_off)))
+        return out_off
 
     # ---- (7)
     def gmm_loglik(self, d_features, n_frames, gmm, d_scores):

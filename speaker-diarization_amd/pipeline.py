@@ -100,23 +100,42 @@ def features_batch(ctx, cfg, pcms=None, uploaded=None, timings=None):
     return d_frames, int(frame_off[-1]), frame_off
 
 
-def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=None, **kw):
-    """From samples to speakers for a batch of files: one upload of the int16 samples, the VAD
-    chain (vad_batch with the model's own feature configuration) and the diarization features
-    (features_batch with cfg, the fconfig.cfg chain) both from it, then diarize_batch with the
-    turns and the frames as they lie on the device.  kw: diarize_batch's text_contract, fused,
-    handoff, link, reseg, detail.  Returns its rows."""
-    from . import frontend
+def _one_clock(model, cfg):
+    """The VAD chain and the diarization features read the same samples on one frame clock."""
     if model.cfg.sample_rate != cfg.sample_rate:
         raise ValueError('the VAD model wants %d Hz, the feature configuration %d Hz' % (model.cfg.sample_rate, cfg.sample_rate))
     if model.cfg.hop != cfg.hop:
         raise ValueError('the VAD model steps %d samples a frame, the feature configuration %d: one frame '
                          'clock for the turns and the features' % (model.cfg.hop, cfg.hop))
-    uploaded = frontend.upload_batch(ctx, pcms, timings)
+
+
+def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=None, uploaded=None, **kw):
+    """From samples to speakers for a batch of files: one upload of the int16 samples, the VAD
+    chain (vad_batch with the model's own feature configuration) and the diarization features
+    (features_batch with cfg, the fconfig.cfg chain) both from it, then diarize_batch with the
+    turns and the frames as they lie on the device.  uploaded: the samples already on the device
+    (frontend.upload_batch or frontend.resample_batch; pcms is not read then).  kw: diarize_batch's
+    text_contract, fused, handoff, link, reseg, detail.  Returns its rows."""
+    from . import frontend
+    _one_clock(model, cfg)
+    if uploaded is None:
+        uploaded = frontend.upload_batch(ctx, pcms, timings)
     vad = vad_batch(ctx, model, None, text_contract=kw.get('text_contract', True), timings=timings, uploaded=uploaded)
     d_frames, total, frame_off = features_batch(ctx, cfg, uploaded=uploaded, timings=timings)
     files = [BatchFile(frame_off[f], frame_off[f + 1] - frame_off[f], vad[f]) for f in range(len(vad))]
     return diarize_batch(ctx, d_frames, total, files, rate=float(cfg.frame_rate), cd=cd, cl=cl, timings=timings, **kw)
+
+
+def diarize_audio_batch(ctx, model, cfg, audios, cd=DIA2_CD, cl=DIA2_CL, timings=None, group_bytes=None, **kw):
+    """From recordings to speakers: audios = [(samples, rate)], int16 [n] or [n, channels] at any
+    rate (frontend.read_audio), resampled and downmixed to cfg.sample_rate on the device
+    (frontend.resample_batch; group_bytes: its bound on the raw audio held there), then exactly
+    diarize_pcm_batch from its upload on.  Returns its rows."""
+    from . import frontend
+    _one_clock(model, cfg)
+    group = {} if group_bytes is None else {'group_bytes': group_bytes}
+    uploaded = frontend.resample_batch(ctx, audios, cfg.sample_rate, timings=timings, **group)
+    return diarize_pcm_batch(ctx, model, cfg, None, cd=cd, cl=cl, timings=timings, uploaded=uploaded, **kw)
 
 
 def _turn_table(files, rate):
