@@ -8,8 +8,8 @@
 //
 // The recursion, in fp64 (include/spkd.h (8) states it as the contract; it fixes values, not the
 // order of the operations), n the sequence's word count, k < n:
-//   o_t(k)   the cleaned score: NaN counts as -inf; a frame whose n words are all -inf counts as 0 for
-//            every word.  m_t = max_k o_t(k), b_t(k) = exp(scale (o_t(k) - m_t)).
+//   o_t(k)   the cleaned score (spkd_lanegroup.hpp, over the sequence's n words).  m_t = max_k o_t(k),
+//            b_t(k) = exp(scale (o_t(k) - m_t)).
 //   q, r     q = exp(-scale penalty), r = 1 - q: a step keeps its word with weight r + q = 1 and
 //            reaches any other with weight q.
 //   forward  u_0 = b_0, u_t(k) = b_t(k) (r a_{t-1}(k) + q), s_t = sum_k u_t(k), a_t = u_t / s_t,
@@ -18,9 +18,9 @@
 //            beta_t = w / sum_k w(k).
 //   gamma    gamma_t(k) = a_t(k) beta_t(k) / sum_j a_t(j) beta_t(j).
 //
-//   k_fb_posterior : k_vad_viterbi's shape -- a group of G lanes (the power of two >= n_cols) per
-//                    sequence, a lane per word, 64 / G sequences per wave, one wave per workgroup, the
-//                    scores a tile of FB_TILE frames in registers with the next tile in flight.  One
+//   k_fb_posterior : the lane-group frame of spkd_lanegroup.hpp -- a group of lanes (the power of two >=
+//                    n_cols) per sequence, a lane per word, the scores a tile of FB_TILE frames in
+//                    registers with the next tile in flight, in the backward sweep the tile below.  One
 //                    launch, two sweeps by the same lanes.  Forward: the a recursion and logz; stored
 //                    is only the a that enters each tile, in fp64 (a forward value that would flush to 0
 //                    in float32 can belong to the word the backward pass favours): 8 G bytes a tile.  A
@@ -37,11 +37,11 @@
 #include <stdint.h>
 
 #include "spkd_device.hpp"
+#include "spkd_lanegroup.hpp"
 
 namespace spkd {
 
 constexpr int FB_TILE = 32;          // frames per score tile and per stored forward vector (SPKD_FB_TILE)
-constexpr int FB_MAX = 16;           // words (GM_MAX_S)
 
 template <int G>
 __device__ inline double fb_sum(double v) {
@@ -67,7 +67,8 @@ __device__ inline void fb_add(double& sum, double& c, double x) {
     sum = t;
 }
 
-// b_t(k) and m_t from the lane's raw score: the cleaning of the header inside
+// b_t(k) and m_t from the lane's raw score: the cleaning of spkd_lanegroup.hpp inside, through the
+// group's maximum, which is needed anyway
 template <int G>
 __device__ inline double fb_emit(float s, bool word, double scale, double& m) {
     double o = (!word || s != s) ? -INFINITY : (double)s;                    // NaN counts as -inf
@@ -88,6 +89,9 @@ __global__ __launch_bounds__(WAVE) void k_fb_posterior(
         double* fwd /* [tiles][G]: stored and read back, no restrict */, float* __restrict__ post /* [sum T][S] or null */,
         double* __restrict__ conf /* [n_tok] */, double* __restrict__ logz /* [n_seq] */) {
 #pragma clang fp contract(off)
+    // The group as lg_setup states it, the tile hand-over as lg_take and the last tile's load as lg_score,
+    // spelt out: through those helpers the compiler schedules this kernel's sweeps differently and it
+    // measures slower than the spread of its runs (profiles/decoder_frame.json).
     const int lane = threadIdx.x, j = lane % G;
     const long long f = (long long)blockIdx.x * (WAVE / G) + lane / G;
     const bool has = f < n_seq;
@@ -108,14 +112,11 @@ __global__ __launch_bounds__(WAVE) void k_fb_posterior(
 
     // ---- forward: a, logz, the a that enters each tile
 #pragma unroll
-    for (int k = 0; k < FB_TILE; ++k) cur[k] = (word && k < T) ? sc[(long long)k * S] : 0.0f;
+    for (int k = 0; k < FB_TILE; ++k) cur[k] = lg_score(sc, S, word, k, T);
     double a = 0.0, lz = 0.0, lz_c = 0.0;
     for (long long t0 = 0; t0 < Tmax; t0 += FB_TILE) {
 #pragma unroll
-        for (int k = 0; k < FB_TILE; ++k) {
-            const long long t = t0 + FB_TILE + k;
-            nxt[k] = (word && t < T) ? sc[t * S] : 0.0f;
-        }
+        for (int k = 0; k < FB_TILE; ++k) nxt[k] = lg_score(sc, S, word, t0 + FB_TILE + k, T);
         if (t0 < T) ck[t0 / FB_TILE * G] = a;
 #pragma unroll
         for (int k = 0; k < FB_TILE; ++k) {
@@ -152,10 +153,7 @@ __global__ __launch_bounds__(WAVE) void k_fb_posterior(
     }
     for (; t0 >= 0; t0 -= FB_TILE) {
 #pragma unroll
-        for (int k = 0; k < FB_TILE; ++k) {
-            const long long t = t0 - FB_TILE + k;
-            nxt[k] = (word && t >= 0 && t < T) ? sc[t * S] : 0.0f;
-        }
+        for (int k = 0; k < FB_TILE; ++k) nxt[k] = lg_score(sc, S, word, t0 - FB_TILE + k, T);
         double bt[FB_TILE], at[FB_TILE];
         double av = t0 < T ? ck[t0 / FB_TILE * G] : 0.0;
 #pragma unroll

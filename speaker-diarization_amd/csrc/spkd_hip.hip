@@ -2171,7 +2171,7 @@ spkd_status spkd_gmm_loglik(spkd_ctx* c, const float* d_features, int64_t n_fram
 // ------------------------------------------------------------------ (7b) the decision part for a batch
 namespace {
 static_assert(VB_TILE == SPKD_VAD_TILE, "the header states the kernels' tile");
-static_assert(VB_MAX == GM_MAX_S, "one limit for states and words");
+static_assert(LG_MAX == GM_MAX_S, "one limit for states and words, and for the lanes of a group");
 
 spkd_status vad_check_offsets(spkd_ctx* c, int64_t n_files, const int64_t* h_frame_off) {
     if (n_files < 0 || !h_frame_off) return fail(c, SPKD_EINVAL, "vad batch: null frame_off or a negative file count");
@@ -2213,22 +2213,34 @@ struct VadTables {
     int32_t* word_state;
     double *stay, *exit, *enter;
 };
-struct VadFiles {                // per file, device or pinned host
+struct DecodedSeqs {             // what a decoder leaves per sequence, device or pinned host
     int64_t *tok_off, *count;
     double* score;
     int32_t* final_word;
 };
 
 extern "C++" {
-// f(std::integral_constant<int, G>()) for the power of two G >= n_words (1 .. 16): the lanes that share a file
+// The lane-group frame of spkd_lanegroup.hpp, host side.  G: the power of two >= n_words (1 .. LG_MAX),
+// the lanes that share a sequence; it sizes the records and the scratch as well as the launch.
+int group_width(int n_words) {
+    int G = 1;
+    while (G < n_words) G *= 2;
+    return G;
+}
+// f(std::integral_constant<int, G>()) for that G
 template <class F>
 void with_group(int n_words, F f) {
-    if (n_words <= 1) f(std::integral_constant<int, 1>());
-    else if (n_words <= 2) f(std::integral_constant<int, 2>());
-    else if (n_words <= 4) f(std::integral_constant<int, 4>());
-    else if (n_words <= 8) f(std::integral_constant<int, 8>());
-    else f(std::integral_constant<int, 16>());
+    switch (group_width(n_words)) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 8: return f(std::integral_constant<int, 8>());
+    case 16: return f(std::integral_constant<int, 16>());
+    default: std::abort();       // (no caller passes n_words > LG_MAX: a launch sized for another G would write out of bounds)
+    }
 }
+// one wave a workgroup, WAVE / G sequences a wave
+dim3 group_grid(int64_t n_seq, int G) { return dim3((unsigned)((n_seq + WAVE / G - 1) / (WAVE / G))); }
 
 // How a decoder (spkd_vad_viterbi_batch, spkd_mindur_viterbi_batch) hands its tokens back: per file the
 // count, the score and the final word on the device and in pinned memory, the tokens compact behind
@@ -2239,9 +2251,9 @@ struct TokenHandBack {
     const double** const score;
     const int pin_files, pin_tokens, s_files, s_tokens;
     size_t nf = 0;
-    VadFiles h{}, d{};           // pinned: the results of the call; the device's
+    DecodedSeqs h{}, d{};           // pinned: the results of the call; the device's
 
-    size_t parts(Layout L, VadFiles& f) const {
+    size_t parts(Layout L, DecodedSeqs& f) const {
         return L.part(f.tok_off, nf + 1).part(f.count, nf).part(f.score, nf).part(f.final_word, nf).bytes();
     }
     // before any other check: false for a null output, else the four outputs nulled
@@ -2307,17 +2319,16 @@ std::vector<int64_t> tiled_offsets(const int64_t* h_frame_off, size_t nf, int64_
 
 template <int G>
 void vad_decode_launch(spkd_ctx* c, const float* d_scores, const VadTables& t, int64_t n_files, int S, int W, void* back,
-                       const VadFiles& d) {
+                       const DecodedSeqs& d) {
     typedef typename VbRecord<G>::type Rec;
-    const int64_t per_wave = WAVE / G;
-    hipLaunchKernelGGL(k_vad_viterbi<G>, dim3((unsigned)((n_files + per_wave - 1) / per_wave)), dim3(WAVE), 0, c->stream,
-                       d_scores, (const long long*)t.frame_off, (const long long*)t.back_off, (long long)n_files, S, W,
+    hipLaunchKernelGGL(k_vad_viterbi<G>, group_grid(n_files, G), dim3(WAVE), 0, c->stream, d_scores,
+                       (const long long*)t.frame_off, (const long long*)t.back_off, (long long)n_files, S, W,
                        (const int*)t.word_state, (const double*)t.stay, (const double*)t.exit, (const double*)t.enter,
                        (Rec*)back, (int*)d.final_word, d.score);
 }
 
 template <class Rec, bool WRITE>
-void vad_backtrack_launch(spkd_ctx* c, const void* back, const VadTables& t, int64_t n_files, int G, const VadFiles& d,
+void vad_backtrack_launch(spkd_ctx* c, const void* back, const VadTables& t, int64_t n_files, int G, const DecodedSeqs& d,
                           int64_t* tok_frame, int32_t* tok_word) {
     hipLaunchKernelGGL((k_vad_backtrack<Rec, WRITE>), dim3((unsigned)((n_files + WAVE - 1) / WAVE)), dim3(WAVE), 0,
                        c->stream, (const Rec*)back, (const long long*)t.frame_off, (const long long*)t.back_off,
@@ -2344,8 +2355,7 @@ spkd_status spkd_vad_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_t n
     if (h_frame_off[n_files] > 0 && !d_scores) return fail(c, SPKD_EINVAL, "vad_viterbi_batch: null device buffer");
     const size_t nf = (size_t)n_files, W = (size_t)n_words;
     const std::vector<int64_t> back_off = tiled_offsets(h_frame_off, nf, VB_TILE);
-    int G = 1;
-    while (G < n_words) G *= 2;
+    const int G = group_width(n_words);
     const size_t rec_bytes = G == 16 ? sizeof(VbRecord<16>::type) : sizeof(VbRecord<1>::type);
     TRY(r.open(c, n_files));
     if (n_files == 0) return SPKD_OK;
@@ -2369,11 +2379,11 @@ spkd_status spkd_vad_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_t n
     }
     HIPCHK(c, hipGetLastError());
     TRY(r.hand_back(c, SPKD_T_VAD_BACKTRACK,
-        [&](const VadFiles& d) {
+        [&](const DecodedSeqs& d) {
             if (G == 16) vad_backtrack_launch<VbRecord<16>::type, false>(c, back, t, n_files, G, d, nullptr, nullptr);
             else vad_backtrack_launch<VbRecord<1>::type, false>(c, back, t, n_files, G, d, nullptr, nullptr);
         },
-        [&](const VadFiles& d, int64_t* tok_frame, int32_t* tok_word) {
+        [&](const DecodedSeqs& d, int64_t* tok_frame, int32_t* tok_word) {
             if (G == 16) vad_backtrack_launch<VbRecord<16>::type, true>(c, back, t, n_files, G, d, tok_frame, tok_word);
             else vad_backtrack_launch<VbRecord<1>::type, true>(c, back, t, n_files, G, d, tok_frame, tok_word);
         }));
@@ -2382,7 +2392,6 @@ spkd_status spkd_vad_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_t n
 
 // ------------------------------------------------------------------ (8) the speaker loop with a minimum duration
 static_assert(MD_TILE == SPKD_MINDUR_TILE, "the header states the kernels' tile");
-static_assert(MD_MAX == GM_MAX_S, "one limit for states and words");
 
 namespace {
 struct MdTables { int64_t *frame_off, *rec_off; };
@@ -2395,9 +2404,8 @@ struct MdWork {                  // per frame, each sequence from a multiple of 
 extern "C++" {
 template <int G>
 void mindur_decode_launch(spkd_ctx* c, const float* d_scores, const MdTables& t, int64_t n_seq, int W, double penalty,
-                          int64_t D, const MdWork& w, const VadFiles& d) {
-    const int64_t per_wave = WAVE / G;
-    const dim3 grid((unsigned)((n_seq + per_wave - 1) / per_wave));
+                          int64_t D, const MdWork& w, const DecodedSeqs& d) {
+    const dim3 grid = group_grid(n_seq, G);
     if (D < MD_RING)
         hipLaunchKernelGGL((k_mindur_viterbi<G, true>), grid, dim3(WAVE), 0, c->stream, d_scores, (const long long*)t.frame_off,
                            (const long long*)t.rec_off, (long long)n_seq, W, W, penalty, (long long)D, w.rec, w.g, (int*)w.b,
@@ -2409,7 +2417,7 @@ void mindur_decode_launch(spkd_ctx* c, const float* d_scores, const MdTables& t,
 }
 
 template <bool WRITE>
-void mindur_backtrack_launch(spkd_ctx* c, const MdTables& t, int64_t n_seq, int64_t D, const MdWork& w, const VadFiles& d,
+void mindur_backtrack_launch(spkd_ctx* c, const MdTables& t, int64_t n_seq, int64_t D, const MdWork& w, const DecodedSeqs& d,
                              int64_t* tok_frame, int32_t* tok_word) {
     hipLaunchKernelGGL((k_mindur_backtrack<WRITE>), dim3((unsigned)((n_seq + WAVE - 1) / WAVE)), dim3(WAVE), 0, c->stream,
                        (const uint16_t*)w.rec, (const int*)w.b, (const long long*)t.frame_off, (const long long*)t.rec_off,
@@ -2459,8 +2467,8 @@ spkd_status spkd_mindur_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_
     }
     HIPCHK(c, hipGetLastError());
     TRY(r.hand_back(c, SPKD_T_MINDUR_BACKTRACK,
-        [&](const VadFiles& d) { mindur_backtrack_launch<false>(c, t, n_seq, min_frames, w, d, nullptr, nullptr); },
-        [&](const VadFiles& d, int64_t* tok_frame, int32_t* tok_word) {
+        [&](const DecodedSeqs& d) { mindur_backtrack_launch<false>(c, t, n_seq, min_frames, w, d, nullptr, nullptr); },
+        [&](const DecodedSeqs& d, int64_t* tok_frame, int32_t* tok_word) {
             mindur_backtrack_launch<true>(c, t, n_seq, min_frames, w, d, tok_frame, tok_word);
         }));
     return call.finish();
@@ -2468,7 +2476,6 @@ spkd_status spkd_mindur_viterbi_batch(spkd_ctx* c, const float* d_scores, int64_
 
 // ------------------------------------------------------------------ (8) the speaker loop's posteriors
 static_assert(FB_TILE == SPKD_FB_TILE, "the header states the kernel's tile");
-static_assert(FB_MAX == GM_MAX_S, "one limit for states and words");
 
 namespace {
 // The index and token table of spkd_fb_posterior_batch, as the kernel takes it: per sequence its first
@@ -2489,9 +2496,8 @@ extern "C++" {
 template <int G>
 void fb_launch(spkd_ctx* c, const float* d_scores, const FbTable& t, int64_t n_seq, int S, double penalty, double scale,
                double* fwd, float* d_post, double* d_conf, double* d_logz) {
-    const int64_t per_wave = WAVE / G;
-    hipLaunchKernelGGL(k_fb_posterior<G>, dim3((unsigned)((n_seq + per_wave - 1) / per_wave)), dim3(WAVE), 0, c->stream,
-                       d_scores, (const long long*)t.d.begin, (const long long*)t.d.tile_off, (const int*)t.d.seq_n,
+    hipLaunchKernelGGL(k_fb_posterior<G>, group_grid(n_seq, G), dim3(WAVE), 0, c->stream, d_scores,
+                       (const long long*)t.d.begin, (const long long*)t.d.tile_off, (const int*)t.d.seq_n,
                        (long long)n_seq, S, penalty, scale, t.tokens ? (const long long*)t.d.tok_off : nullptr,
                        (const long long*)t.d.tok_frame, (const int*)t.d.tok_word, fwd, d_post, d_conf, d_logz);
 }
@@ -2557,8 +2563,7 @@ spkd_status spkd_fb_posterior_batch(spkd_ctx* c, const float* d_scores, int64_t 
         std::memcpy(t.h.tok_frame, h_tok_frame, t.ntok * sizeof(int64_t));
         std::memcpy(t.h.tok_word, h_tok_word, t.ntok * sizeof(int32_t));
     }
-    int G = 1;
-    while (G < n_cols) G *= 2;
+    const int G = group_width(n_cols);
     Call call(c);
     TRY(call.opened);
     TRY(carve(c, scratch, S_FB_TAB, [&](Layout L) { return t.parts(L, t.d); }));

@@ -24,39 +24,42 @@
 // A sequence whose words all hold a -inf somewhere in every window has d = -inf throughout: it comes
 // out as the one token (0, 0) with score -inf.
 //
-//   k_mindur_viterbi   : k_vad_viterbi's shape -- a group of G lanes (the power of two >= W) per
-//                        sequence, a lane per word, 64 / G sequences per wave, one wave per workgroup.
-//                        Two score streams, each MD_TILE frames in registers with the next tile in
-//                        flight: the leading frame t and the trailing frame t - D.  The trailing
-//                        stream rebuilds P_{t-D} with the same additions in the same order, so it is
-//                        bit-equal to the leading sum of D frames earlier and nothing per word is
-//                        stored; of the counts only the difference C_t - C_{t-D} is kept.  What is
-//                        stored per frame is g_t (8 bytes) and b_t (4 bytes), by lane 0 of the group,
-//                        which is also the lane that reads g back D frames later and hands it to the
-//                        group by shuffle: no lane ever reads what another lane wrote.  D >= 2 MD_TILE
-//                        (FAR): g_{t-D} comes from the global scratch, a tile fetched one tile ahead
-//                        -- every frame of it was stored before the current tile began.  D < 2 MD_TILE
+//   k_mindur_viterbi   : the lane-group frame of spkd_lanegroup.hpp (a group of lanes per sequence, a
+//                        lane per word), spelt out here, with two score streams, each MD_TILE frames in registers
+//                        with the next tile in flight: the leading frame t and the trailing frame
+//                        t - D, the same load D frames back.  The trailing stream rebuilds P_{t-D}
+//                        with the same additions in the same order, so it is bit-equal to the
+//                        leading sum of D frames earlier and nothing per word is stored; of the
+//                        counts only the difference C_t - C_{t-D} is kept.  What is stored per frame
+//                        is g_t (8 bytes) and b_t (4 bytes), by lane 0 of the group, which is also
+//                        the lane that reads g back D frames later and hands it to the group by
+//                        shuffle: no lane ever reads what another lane wrote.  D >= 2 MD_TILE (FAR):
+//                        g_{t-D} comes from the global scratch, a tile fetched one tile ahead --
+//                        every frame of it was stored before the current tile began.  D < 2 MD_TILE
 //                        (NEAR): from a ring of 2 MD_TILE entries per group in LDS.  Only d + o, one
 //                        comparison and one select are on the dependent chain; the maximum over the
 //                        group is needed D frames later.  The back-pointer record is the group's
-//                        `entered` ballot, 2 bytes a frame, kept in registers by lane 0 and stored as
-//                        16-byte vectors per tile.  A sequence's records, g and b start at a multiple
-//                        of MD_TILE.
-//   k_mindur_backtrack : one lane per sequence walks the records from the last frame, a tile (the
-//                        tile below fetched ahead) at a time, and jumps D frames where the path
-//                        entered a word, reading b there.  COUNT and WRITE passes as k_vad_backtrack.
+//                        `entered` ballot, 2 bytes a frame.  A sequence's records, g and b start at a
+//                        multiple of MD_TILE.
+//   k_mindur_backtrack : the frame's walk, which jumps D frames where the path entered a word,
+//                        reading b there, and fetches the tile it lands in when that is not the
+//                        tile below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "spkd_device.hpp"
+#include "spkd_lanegroup.hpp"
 
 namespace spkd {
 
 constexpr int MD_TILE = 32;          // frames per score / record tile (SPKD_MINDUR_TILE)
 constexpr int MD_RING = 2 * MD_TILE; // entries of a group's LDS ring; D below it decodes NEAR
-constexpr int MD_MAX = 16;           // words (GM_MAX_S)
 
+// k_mindur_viterbi states the frame's rules itself (the group, the loads, the cleaning, the best, the
+// records), as spkd_lanegroup.hpp words them: built from the shared helpers the same arithmetic comes
+// out in another schedule, and the FAR form measures 1.3 - 3.5 % slower, outside the spread of its
+// runs (profiles/decoder_frame.json).  A change to a rule there is a change here.
 // max over the group's v with the lowest index among equals (no NaN comes here)
 template <int G>
 __device__ inline void md_best(double& v, int& idx) {
@@ -177,59 +180,36 @@ __global__ __launch_bounds__(WAVE) void k_mindur_backtrack(
         const long long* __restrict__ rec_off, long long n_seq, long long D, const int* __restrict__ final_word,
         long long* __restrict__ count /* [n_seq]: COUNT pass out */, const long long* __restrict__ tok_off /* [n_seq + 1] */,
         long long* __restrict__ tok_frame, int* __restrict__ tok_word) {
-    constexpr int NV = MD_TILE / 8;                      // 16-byte vectors per tile
-    const long long f = (long long)blockIdx.x * WAVE + threadIdx.x;
-    if (f >= n_seq) return;
-    const long long T = frame_off[f + 1] - frame_off[f];
-    const long long cap = WRITE ? tok_off[f + 1] - tok_off[f] : 0, end = WRITE ? tok_off[f + 1] : 0;
-    const uint4* src = reinterpret_cast<const uint4*>(rec + rec_off[f]);
-    const int* bs = bbuf + rec_off[f];
-    int j = final_word[f];
-    long long n = 0, tc = T - 1;                         // tc: the frame the path is at
-    uint4 cur[NV], nxt[NV];
+    LgWalk<WRITE> w;
+    if (!w.begin(frame_off, n_seq, final_word, tok_off, tok_frame, tok_word)) return;
+    const uint16_t* src = rec + rec_off[w.f];
+    const int* bs = bbuf + rec_off[w.f];
+    long long tc = w.T - 1;                              // tc: the frame the path is at
+    LgRecords<uint16_t, MD_TILE> cur, nxt;
     long long t0 = tc >= 0 ? tc / MD_TILE * MD_TILE : 0;
-    if (tc >= 0) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) cur[q] = src[t0 / MD_TILE * NV + q];
-    }
+    if (tc >= 0) cur.fetch(src, t0);
     while (tc >= 0) {
-        if (t0 >= MD_TILE) {
-#pragma unroll
-            for (int q = 0; q < NV; ++q) nxt[q] = src[(t0 / MD_TILE - 1) * NV + q];
-        }
+        if (t0 >= MD_TILE) nxt.fetch(src, t0 - MD_TILE);
 #pragma unroll
         for (int k = MD_TILE - 1; k >= 0; --k) {
             const long long t = t0 + k;
             if (t != tc) continue;                       // (behind T - 1, or jumped over)
-            const uint4 v4 = cur[k / 8];
-            const int w = (k / 2) % 4;
-            const unsigned word32 = w == 0 ? v4.x : w == 1 ? v4.y : w == 2 ? v4.z : v4.w;
-            const bool entered = ((word32 >> (16 * (k % 2))) >> j) & 1u;     // (set only for t >= D)
+            const bool entered = (cur.get(k) >> w.j) & 1u;                   // (set only for t >= D)
             long long first = -1;
             if (t <= D - 1) { first = 0; tc = -1; }
             else if (entered) { first = t - D + 1; tc = t - D; }
             else tc = t - 1;
             if (first >= 0) {
-                if (WRITE && n < cap) {
-                    tok_frame[end - 1 - n] = first;
-                    tok_word[end - 1 - n] = j;
-                }
-                ++n;
-                if (first > 0) j = bs[t - D];
+                w.emit(first);
+                if (first > 0) w.j = bs[t - D];
             }
         }
         if (tc < 0) break;
         const long long below = t0 - MD_TILE;
         t0 = tc / MD_TILE * MD_TILE;
-        if (t0 == below) {
-#pragma unroll
-            for (int q = 0; q < NV; ++q) cur[q] = nxt[q];
-        } else {
-#pragma unroll
-            for (int q = 0; q < NV; ++q) cur[q] = src[t0 / MD_TILE * NV + q];
-        }
+        if (t0 == below) cur = nxt; else cur.fetch(src, t0);
     }
-    if (!WRITE) count[f] = n;
+    w.finish(count);
 }
 
 }  // namespace spkd

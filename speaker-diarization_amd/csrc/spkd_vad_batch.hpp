@@ -10,37 +10,26 @@
 //                     order, log, rounded to float32.  A lane reads its S values before it writes
 //                     any, and nobody else touches them: the call may run in place.  Naive IEEE
 //                     on purpose (underflow gives -inf, 0 / 0 NaN), no contraction into FMAs.
-//   k_vad_viterbi   : a group of G lanes (G = the power of two >= W) per file, one lane per word,
-//                     64 / G files per wave, one wave per workgroup.  The recurrence of
-//                     include/spkd.h in fp64 sums and comparisons, in the header's order.  The max
-//                     over d(i) + exit_i is a butterfly over the group that keeps the lowest index
-//                     on ties and restates the host's scan for NaNs (a NaN at word 0 stays, a NaN
-//                     elsewhere never beats anything).  The scores are not on the dependent
-//                     chain: a lane loads its word's score of the next VB_TILE frames into
-//                     registers while the chain runs over the current tile (the S floats of a
-//                     frame are contiguous and the lanes of a group, and the groups' lines, share
-//                     cache lines).  Back-pointers: per frame one record -- bit j: word j was
+//   k_vad_viterbi   : the lane-group frame of spkd_lanegroup.hpp (a group of lanes per file, a lane
+//                     per word, the scores a tile of VB_TILE frames ahead of the chain) around the
+//                     recurrence of include/spkd.h in fp64 sums and comparisons, in the header's
+//                     order.  The max over d(i) + exit_i is the group's best with the host's scan
+//                     restated for NaNs.  Back-pointers: per frame one record -- bit j: word j was
 //                     entered, bits G..G+3: bi, the word left -- of 2 bytes (W <= 8) or 4 bytes
-//                     (W > 8), at most W + 1 bytes; the group's flags come from one ballot, lane
-//                     0 of the group keeps the tile's records in registers and stores them as
-//                     16-byte vectors.  A file's records start at a multiple of VB_TILE, so a
-//                     tile's store never crosses into the next file.
-//   k_vad_backtrack : one lane per file walks the records from the last frame, a tile (fetched one
-//                     tile ahead) at a time.  COUNT pass: the number of tokens; WRITE pass, after
-//                     the host has placed every file at its exact offset: first frame and word of
-//                     every word the path enters, written from the back so that they come out in
-//                     order.  A write is checked against the file's count.
+//                     (W > 8), at most W + 1 bytes; the group's flags come from one ballot.
+//   k_vad_backtrack : the frame's walk: a token where the path enters a word, and at frame 0; the
+//                     word left is the record's bi.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "spkd_device.hpp"
+#include "spkd_lanegroup.hpp"
 
 namespace spkd {
 
 constexpr int VB_TILE = 32;          // frames per score / back-pointer tile (SPKD_VAD_TILE)
 constexpr int VB_SHIFT_TPB = 256;
-constexpr int VB_MAX = 16;           // states, words (GM_MAX_S)
 
 template <int G> struct VbRecord { typedef uint16_t type; };
 template <> struct VbRecord<16> { typedef uint32_t type; };
@@ -58,31 +47,17 @@ __global__ __launch_bounds__(VB_SHIFT_TPB) void k_vad_shift(
     }
     const long long T = frame_off[lo + 1] - frame_off[lo], i = g - frame_off[lo];
     const long long base = frame_off[lo] * S + i;
-    double e[VB_MAX];
+    double e[LG_MAX];
 #pragma unroll
-    for (int r = 0; r < VB_MAX; ++r) e[r] = r < S ? exp((double)in[base + r * T]) : 0.0;
+    for (int r = 0; r < LG_MAX; ++r) e[r] = r < S ? exp((double)in[base + r * T]) : 0.0;
     e[1] = e[1] * shift;
     double sum = e[0];
 #pragma unroll
-    for (int r = 1; r < VB_MAX; ++r)
+    for (int r = 1; r < LG_MAX; ++r)
         if (r < S) sum = sum + e[r];
 #pragma unroll
-    for (int r = 0; r < VB_MAX; ++r)
+    for (int r = 0; r < LG_MAX; ++r)
         if (r < S) out[base + r * T] = (float)log(e[r] / sum);
-}
-
-// max over the group's v with the index it came from, as the host's scan `best = v[0]; for i = 1..:
-// if (v[i] > best) ...` leaves them: the lowest index among equals; the caller has replaced a NaN
-// at an index > 0 by -inf (the scan never takes it, and -inf at a higher index never wins), a NaN
-// at index 0 is what the scan keeps whatever follows.
-template <int G>
-__device__ inline void vb_best(double& v, int& idx) {
-#pragma unroll
-    for (int m = 1; m < G; m <<= 1) {
-        const double vo = __shfl_xor(v, m);
-        const int io = __shfl_xor(idx, m);
-        if (vo > v || (vo == v && io < idx) || vo != vo) { v = vo; idx = io; }
-    }
 }
 
 template <int G>
@@ -92,70 +67,37 @@ __global__ __launch_bounds__(WAVE) void k_vad_viterbi(
         const int* __restrict__ word_state, const double* __restrict__ c_stay, const double* __restrict__ c_exit,
         const double* __restrict__ c_enter, typename VbRecord<G>::type* __restrict__ back,
         int* __restrict__ final_word /* [n_files] */, double* __restrict__ final_score /* [n_files] */) {
-    typedef typename VbRecord<G>::type Rec;
-    constexpr int PER = 4 / (int)sizeof(Rec);            // records per 32-bit word
-    constexpr int NPK = VB_TILE / PER;
-    constexpr unsigned long long GMASK = (1ull << G) - 1ull;
-    const int lane = threadIdx.x, j = lane % G, sh = lane - j;
-    const long long f = (long long)blockIdx.x * (WAVE / G) + lane / G;
-    const bool has = f < n_files, word = j < W;
-    const long long T = has ? frame_off[f + 1] - frame_off[f] : 0;
-    const float* sc = scores + (has ? frame_off[f] * S : 0) + (word ? word_state[j] : 0);
+    const LaneGroup<G> g = lg_setup<G>(frame_off, n_files);
+    const int j = g.j;
+    const bool word = j < W;
+    const long long T = g.T;
+    const float* sc = scores + g.row0 * S + (word ? word_state[j] : 0);
     const double stay_c = word ? c_stay[j] : 0.0, exit_c = word ? c_exit[j] : 0.0, enter_c = word ? c_enter[j] : 0.0;
-    long long Tmax = T;                                  // the wave runs to its longest file
-#pragma unroll
-    for (int m = 1; m < WAVE; m <<= 1) {
-        const long long o = __shfl_xor(Tmax, m);
-        Tmax = o > Tmax ? o : Tmax;
-    }
     float cur[VB_TILE], nxt[VB_TILE];
 #pragma unroll
-    for (int k = 0; k < VB_TILE; ++k) cur[k] = (word && k < T) ? sc[(long long)k * S] : 0.0f;
+    for (int k = 0; k < VB_TILE; ++k) cur[k] = lg_score(sc, S, word, k, T);
     double d = 0.0, d_last = -INFINITY;
-    for (long long t0 = 0; t0 < Tmax; t0 += VB_TILE) {
+    for (long long t0 = 0; t0 < g.Tmax; t0 += VB_TILE) {
 #pragma unroll
-        for (int k = 0; k < VB_TILE; ++k) {
-            const long long t = t0 + VB_TILE + k;
-            nxt[k] = (word && t < T) ? sc[t * S] : 0.0f;
-        }
-        unsigned pk[NPK];
-#pragma unroll
-        for (int q = 0; q < NPK; ++q) pk[q] = 0u;
+        for (int k = 0; k < VB_TILE; ++k) nxt[k] = lg_score(sc, S, word, t0 + VB_TILE + k, T);
+        LgRecords<typename VbRecord<G>::type, VB_TILE> recs;
+        recs.clear();
 #pragma unroll
         for (int k = 0; k < VB_TILE; ++k) {
             const long long t = t0 + k;
-            const float s = cur[k];
-            double o = s != s ? -INFINITY : (double)s;                       // NaN counts as -inf
-            const unsigned long long ninf = __ballot(!word || o == -INFINITY);
-            if (((ninf >> sh) & GMASK) == GMASK) o = 0.0;                    // every word -inf: 0 for every word
-            double v = d + exit_c;
-            if (!word || (j > 0 && v != v)) v = -INFINITY;
-            int bi = j;
-            vb_best<G>(v, bi);
+            const double o = lg_clean<G>(cur[k], word, g.sh);
+            int bi;
+            const double v = lg_best<G, true>(d + exit_c, word, j, bi);
             const double stay = d + stay_c, sw = v + enter_c;
             const bool stays = stay >= sw, first = t == 0;
             d = (first ? enter_c : (stays ? stay : sw)) + o;
             if (t == T - 1) d_last = d;
-            const unsigned long long entered = __ballot(word && !first && !stays);
-            const unsigned rec = (unsigned)((entered >> sh) & GMASK) | ((unsigned)bi << G);
-            pk[k / PER] |= rec << (8 * (int)sizeof(Rec) * (k % PER));
+            recs.put(k, lg_bits<G>(__ballot(word && !first && !stays), g.sh) | ((unsigned)bi << G));
         }
-        if (j == 0 && t0 < T) {                          // (frames behind T - 1 of the tile: never read)
-            uint4* dst = reinterpret_cast<uint4*>(back + back_off[f] + t0);
-#pragma unroll
-            for (int q = 0; q < NPK / 4; ++q) dst[q] = make_uint4(pk[4 * q], pk[4 * q + 1], pk[4 * q + 2], pk[4 * q + 3]);
-        }
-#pragma unroll
-        for (int k = 0; k < VB_TILE; ++k) cur[k] = nxt[k];
+        if (j == 0 && t0 < T) recs.store(back + back_off[g.f], t0);
+        lg_take(cur, nxt);
     }
-    double v = d_last;                                   // max_j d_{T-1}(j), the lowest j among equals
-    if (!word || (j > 0 && v != v)) v = -INFINITY;
-    int bj = j;
-    vb_best<G>(v, bj);
-    if (has && j == 0) {
-        final_word[f] = bj;
-        final_score[f] = T > 0 ? v : -INFINITY;
-    }
+    lg_ending<G, true>(g, word, d_last, final_word, final_score);
 }
 
 template <class Rec, bool WRITE>
@@ -164,48 +106,26 @@ __global__ __launch_bounds__(WAVE) void k_vad_backtrack(
         long long n_files, int gbits /* G of the decoding launch */, const int* __restrict__ final_word,
         long long* __restrict__ count /* [n_files]: COUNT pass out */, const long long* __restrict__ tok_off /* [n_files + 1] */,
         long long* __restrict__ tok_frame, int* __restrict__ tok_word) {
-    constexpr int PER = 4 / (int)sizeof(Rec);
-    constexpr int NV = VB_TILE / PER / 4;                // 16-byte vectors per tile
-    const long long f = (long long)blockIdx.x * WAVE + threadIdx.x;
-    if (f >= n_files) return;
-    const long long T = frame_off[f + 1] - frame_off[f];
-    const long long cap = WRITE ? tok_off[f + 1] - tok_off[f] : 0, end = WRITE ? tok_off[f + 1] : 0;
-    const uint4* src = reinterpret_cast<const uint4*>(back + back_off[f]);
-    int j = final_word[f];
-    long long n = 0;
-    uint4 cur[NV], nxt[NV];
-    long long t0 = T > 0 ? (T - 1) / VB_TILE * VB_TILE : -1;
-    if (t0 >= 0) {
-#pragma unroll
-        for (int q = 0; q < NV; ++q) cur[q] = src[t0 / VB_TILE * NV + q];
-    }
+    LgWalk<WRITE> w;
+    if (!w.begin(frame_off, n_files, final_word, tok_off, tok_frame, tok_word)) return;
+    const Rec* src = back + back_off[w.f];
+    LgRecords<Rec, VB_TILE> cur, nxt;
+    long long t0 = w.T > 0 ? (w.T - 1) / VB_TILE * VB_TILE : -1;
+    if (t0 >= 0) cur.fetch(src, t0);
     for (; t0 >= 0; t0 -= VB_TILE) {
-        if (t0 >= VB_TILE) {
-#pragma unroll
-            for (int q = 0; q < NV; ++q) nxt[q] = src[(t0 / VB_TILE - 1) * NV + q];
-        }
+        if (t0 >= VB_TILE) nxt.fetch(src, t0 - VB_TILE);
 #pragma unroll
         for (int k = VB_TILE - 1; k >= 0; --k) {
             const long long t = t0 + k;
-            if (t >= T) continue;
-            const uint4 v4 = cur[k / PER / 4];
-            const int w = (k / PER) % 4;
-            const unsigned word32 = w == 0 ? v4.x : w == 1 ? v4.y : w == 2 ? v4.z : v4.w;
-            const unsigned rec = (word32 >> (8 * (int)sizeof(Rec) * (k % PER))) & (unsigned)(Rec)~(Rec)0;
-            const bool entered = (rec >> j) & 1u;
-            if (t == 0 || entered) {                     // a token where the path enters a word, and at frame 0
-                if (WRITE && n < cap) {
-                    tok_frame[end - 1 - n] = t;
-                    tok_word[end - 1 - n] = j;
-                }
-                ++n;
-            }
-            if (entered) j = (int)(rec >> gbits);
+            if (t >= w.T) continue;
+            const unsigned rec = cur.get(k);
+            const bool entered = (rec >> w.j) & 1u;
+            if (t == 0 || entered) w.emit(t);            // a token where the path enters a word, and at frame 0
+            if (entered) w.j = (int)(rec >> gbits);
         }
-#pragma unroll
-        for (int q = 0; q < NV; ++q) cur[q] = nxt[q];
+        cur = nxt;
     }
-    if (!WRITE) count[f] = n;
+    w.finish(count);
 }
 
 }  // namespace spkd
