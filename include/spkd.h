@@ -120,6 +120,14 @@ spkd_status spkd_last_gw_items(spkd_ctx *ctx, int64_t *items);
  * A set is the concatenation of one or more frame ranges [begin, end); ranges
  * of one set are contiguous in the arrays and set ids are non-decreasing.
  * d_stats receives n_sets records of SPKD_REC doubles.
+ *
+ * Accuracy domain.  A record holds RAW moments (n, sum x_i, sum x_i x_j); each entry is within
+ * (n + 64) 2^-53 sum_t |x_ti x_tj| of the exact sum (asserted against exact integer arithmetic,
+ * tests/test_conditioned_exact.py).  Every covariance downstream is (M - s s^T / n) / (n - 1),
+ * which cancels about 2 log10(mean / sigma) digits that np.cov, subtracting the mean first, keeps.
+ * With means within a few sigma of zero this is as accurate as the reference; a caller whose
+ * features are not centred subtracts one constant vector per file from every frame first
+ * (covariances do not change under a shift).  DESIGN.md section 4, "Accuracy domain".
  */
 spkd_status spkd_set_stats(spkd_ctx *ctx, const float *d_frames, int64_t n_frames,
                            const int64_t *h_range_begin, const int64_t *h_range_end,
@@ -137,6 +145,14 @@ spkd_status spkd_set_stats(spkd_ctx *ctx, const float *d_frames, int64_t n_frame
  *   [7] reserved
  * S = np.cov(rowvar=0) semantics (unbiased); log det = log of the LU
  * determinant: 0 -> -inf, negative -> NaN.
+ *
+ * Accuracy domain (against exact arithmetic on full-rank sets of 40 to 3 000 frames; measure
+ * |a - b| / max(1, |a|, |b|) over the log-dets and the BIC / GLR assembled from them; table in
+ * DESIGN.md section 4): covariances of cond <= 5e2 with means up to 8 sigma: 1e-9; means of 64 sigma,
+ * or cond 1e6 with means up to 64 sigma, or cond 1e9 with means up to 8 sigma: 1e-5 (at 8 sigma
+ * with little to spare: up to 2e-6 here, 7e-6 through spkd_gw's running sums); cond 1e9 with means
+ * of 64 sigma: outside 1e-5 (up to 8e-4, where the reference keeps 4e-8).  The limit is that of the raw-moment records (spkd_set_stats above), not of the
+ * elimination: the kernels stay within a small multiple of the same formulation in plain C.
  */
 #define SPKD_WANT_GLR 1
 #define SPKD_WANT_KL2 2
