@@ -979,6 +979,16 @@ spkd_status spkd_post_stats(spkd_ctx *ctx, const float *d_frames, int64_t n_fram
  *   h_set_off not starting at 0, a set without a range, a range outside [0, n_frames] or with
  *   end < begin, d_gmm not 16-byte aligned.  n_speakers = 0: SPKD_OK without a launch.
  *   Timer: SPKD_T_GMM_TRAIN (all launches of the call).
+ *   Accuracy domain (against this section stated at 50 digits with centred variances,
+ *   tests/test_mixture_exact.py; measure |a - b| / max(1, |a|, |b|); table in DESIGN.md section 5,
+ *   "Mixture speaker models"): var = B / G - mean^2 is a difference of raw moments and loses
+ *   mean^2 / var, so the error of 1 / var grows with the square of a component mean's distance from
+ *   the origin in sigma: 2e-14, 2e-13 and 8e-12 at 1, 8 and 64 sigma.  A trained model, its L, the
+ *   scores and spkd_ubm_stats' records are good to 1e-9 up to the 64 sigma that are tested; that law
+ *   continued reaches 1e-9 near 700 sigma and 1e-5 near 70 000 sigma (not tested).  A frame as large
+ *   as 3e38 is finite and leaves h_ok at 1, but every other value of its dimension is below half an
+ *   ulp beside it: such a frame decides nothing.  A caller whose features are not centred subtracts
+ *   one constant vector per file first, as for spkd_set_stats.
  *
  * spkd_gmm_loglik_seq: spkd_gauss_loglik with mixtures: column k < n_models(q) of a frame is
  *   m + ln sum_j exp(l_j - m) under the sequence's k-th speaker (n_models models of n_comp components

@@ -171,7 +171,9 @@ def test_one_component_is_the_maximum_likelihood_gaussian():
 
 @pytest.mark.parametrize('K', [2, 4])
 def test_restated_em_never_lowers_the_loglikelihood(K):
-    """Seed 909 (the first tried): the floor and the G_k < 2 rule stay inactive over the 5 steps."""
+    """Seed 909 (the first tried): the floor and the G_k < 2 rule stay inactive over the 5 steps.
+    (Where the two rules ARE exercised: tests/mixture_cases.py's floor, starved and K = 7 cases, on the
+    CPU in tests/test_exact_mixture.py and on the device in tests/test_mixture_exact.py.)"""
     x = pkg('synth').make_session(909, 60.0, 2)[0]
     assert len(x) == 7500
     floor = G.variance_floor(x, 0.01)[0]
