@@ -37,15 +37,10 @@ using namespace spkd;
 
 namespace {
 constexpr int N_SLOTS = 72;
-// pinned host buffers of the batch hand-off (spkd_gw_batch, spkd_ahc_fused); of the two decoders' results
-// (TokenHandBack: PIN_VAD_FILES / PIN_VAD_TOKENS of spkd_vad_viterbi_batch, PIN_MD_SEQS / PIN_MD_TOKENS of
-// spkd_mindur_viterbi_batch, so that neither call ends the other's); of the index arrays on their way up: spkd_sum_stats'
-// (PIN_SUM_IDX), the SeqTable of spkd_gauss_loglik (PIN_GAUSS_IDX) and of spkd_gmm_loglik_seq (PIN_GT_IDX), the
-// RangeTable of spkd_gmm_train (PIN_GT_TAB) and of spkd_ubm_stats (PIN_UBM_TAB), spkd_clr_link's ok flags (PIN_CLR_IN),
-// the FbTable of spkd_fb_posterior_batch (PIN_FB_TAB), the PostTable of spkd_post_stats (PIN_POST_TAB);
-// and of what comes down: spkd_gmm_train's ok flags and log-likelihoods (PIN_GT_OUT), spkd_ubm_stats' ok flags
-// (PIN_UBM_OUT), spkd_clr_link's merge log and statistics (PIN_CLR_OUT); spkd_clr_identify's flags and offsets on their
-// way up (PIN_ID_IN) and its decisions on their way down (PIN_ID_OUT), spkd_bw_accumulate's table (PIN_ACC_TAB)
+// Pinned host buffers, each named where it is used (stage(), TokenHandBack, the batch hand-off).  A slot belongs
+// to one block of one entry point: what a call leaves there for its caller (the hand-off's results, a decoder's
+// tokens) stays valid until that entry point is called again, so two calls whose results can be live together
+// never share a slot; nor do the block that goes up and the block that comes down in one call.
 enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
        PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, PIN_MD_SEQS, PIN_MD_TOKENS,
        PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, PIN_POST_TAB, N_PIN };
@@ -158,6 +153,7 @@ spkd_status upload(spkd_ctx* c, int slot, const T* h, size_t n, T** d) {
 // a base to measure, on one with the base to place the pointers.  Every part starts at a
 // multiple of its type's alignment.  With a staging area, part() also copies its source there:
 // the host image of a table that goes up in one copy.
+constexpr size_t IMAGE_ALIGN = 16;   // of the base of every buffer and image, so a part's offset is the same in each
 struct Layout {
     char* const base;
     char* const stage;
@@ -165,13 +161,15 @@ struct Layout {
     explicit Layout(void* b = nullptr, void* s = nullptr) : base((char*)b), stage((char*)s) {}
     template <class T>
     Layout& part(T*& p, size_t count, const T* src = nullptr) {
-        at = (at + alignof(T) - 1) / alignof(T) * alignof(T);
+        static_assert(alignof(T) <= IMAGE_ALIGN, "a base aligns every part");
+        align(alignof(T));
         p = base ? (T*)(base + at) : nullptr;
         if (stage && src) std::memcpy(stage + at, src, count * sizeof(T));
         at += count * sizeof(T);
         return *this;
     }
     size_t bytes() const { return at; }
+    Layout& align(size_t a) { at = (at + a - 1) / a * a; return *this; }
 };
 
 // such a buffer from scratch() or pinned(): the size is what the walk over its parts measured
@@ -183,8 +181,8 @@ spkd_status carve(spkd_ctx* c, spkd_status (*alloc)(spkd_ctx*, int, size_t, void
     return SPKD_OK;
 }
 
-// a table upload: the sources of the parts staged in `image` (declared before the Call), sent in
-// one copy, the parts placed on the device
+// The table upload of the older stages, which stage in pageable memory (`image`, declared before the
+// Call) and so stay off Mirror's pinned slots; the walk over the parts is the same one.
 template <class Parts>
 spkd_status upload_parts(spkd_ctx* c, int slot, std::vector<char>& image, Parts parts) {
     image.resize(parts(Layout()));
@@ -232,6 +230,47 @@ struct Call {
     }
 };
 
+// A mirrored block: one listing parts(Layout, Tab&), placed as h in a pinned slot and as d on the device, and one
+// copy between the two images -- up for a table of the caller's arguments, down for a block of results.  A block
+// is anything with `Tab h, d; Image host, dev;` and that parts(): a table struct with its checks and its fill
+// (SeqTable, RangeTable), or a Mirror around a listing written where it is used.  stage() comes before the Call and
+// takes none; what enqueues takes the Call.  So a copy's host side is a pinned slot of the context, staged, and for
+// a table filled, before the bracket opens: the rule over Call holds.
+struct Image { char* base = nullptr; size_t bytes = 0; };   // of a placed listing: where it starts, what it covers
+template <class Tab, class Parts>
+struct Mirror { const Parts parts; Tab h{}, d{}; Image host, dev; };
+template <class Tab, class Parts>
+Mirror<Tab, Parts> mirror(Parts parts) { return {parts}; }
+// One image of the block as the next region of the buffer that L walks, from a multiple of IMAGE_ALIGN to
+// one: the device's inside a scratch carve of the Call, whose own parts go on behind it; the host's for stage().
+enum Side { DEVICE, HOST };
+template <class Block>
+Layout& place(Layout& L, Block& b, Side side = DEVICE) {
+    Image& im = side == HOST ? b.host : b.dev;
+    im.base = L.align(IMAGE_ALIGN).base ? L.base + L.at : nullptr;
+    L.at += im.bytes = b.parts(Layout(im.base), side == HOST ? b.h : b.d);
+    return L.align(IMAGE_ALIGN);
+}
+// before the Call: the host image in pinned slot `pin`, for the caller to fill or, after finish(), to read
+template <class Block>
+spkd_status stage(spkd_ctx* c, int pin, Block& b) {
+    return carve(c, pinned, pin, [&](Layout L) { return place(L, b, HOST).bytes(); });
+}
+// the one copy of a staged and placed block, `kind` its direction
+template <class Block>
+spkd_status copy(Call& call, const Block& b, hipMemcpyKind kind) {
+    if (!b.host.base || b.host.bytes != b.dev.bytes) return fail(call.c, SPKD_EHIP, "internal error: a block is copied staged and placed");
+    const bool up = kind == hipMemcpyHostToDevice;
+    HIPCHK(call.c, hipMemcpyAsync(up ? b.dev.base : b.host.base, up ? b.host.base : b.dev.base, b.host.bytes, kind, call.c->stream));
+    return SPKD_OK;
+}
+// a table in scratch slot `slot` of its own, and up
+template <class Block>
+spkd_status send(Call& call, int slot, Block& b) {
+    TRY(carve(call.c, scratch, slot, [&](Layout L) { return place(L, b).bytes(); }));
+    return copy(call, b, hipMemcpyHostToDevice);
+}
+
 // The kind of a call that takes one: SPKD_KL2_PINV runs as SPKD_KL2 with the pseudo-inverse
 // workspace handed to the kernels (c->pinv_cur), every other kind with none.  Called after the
 // call's bracket is open (the first use clears the workspace's lock words on the stream).
@@ -252,6 +291,7 @@ spkd_status use_kind(spkd_ctx* c, int kind, int* base) {
 }
 
 bool bad_kind(int kind) { return kind < 0 || kind > 3; }
+bool bad_comp(int n_comp) { return n_comp < 1 || n_comp > GT_MAX_COMP; }   // (the entry points' messages say 8)
 
 // the caller's parameters with the kind as the kernels take it: Pk is the copy, P points to it
 template <class Params>
@@ -1527,20 +1567,18 @@ spkd_status spkd_sum_stats(spkd_ctx* c, const double* d_src, int64_t n_src, cons
     if (s0 % 16 || t0 % 16) return fail(c, SPKD_EINVAL, "sum_stats: record buffers must be 16-byte aligned");
     if (s0 < t1 && t0 < s1) return fail(c, SPKD_EINVAL, "sum_stats: the destination overlaps the source");
     const size_t ns = (size_t)n_sets, nm = (size_t)n_mem;
-    // the two arrays as one image in pinned memory: one copy up
-    int64_t *h_off = nullptr, *h_mem = nullptr, *d_off = nullptr, *d_mem = nullptr;
-    auto parts = [&](Layout L, int64_t*& off, int64_t*& mem) { return L.part(off, ns + 1).part(mem, nm).bytes(); };
-    TRY(carve(c, pinned, PIN_SUM_IDX, [&](Layout L) { return parts(L, h_off, h_mem); }));
-    std::memcpy(h_off, h_set_off, (ns + 1) * sizeof(int64_t));
-    std::memcpy(h_mem, h_member, nm * sizeof(int64_t));
+    struct Tab { int64_t *off, *member; };
+    auto tab = mirror<Tab>([&](Layout L, Tab& t) { return L.part(t.off, ns + 1).part(t.member, nm).bytes(); });
+    TRY(stage(c, PIN_SUM_IDX, tab));
+    std::memcpy(tab.h.off, h_set_off, (ns + 1) * sizeof(int64_t));
+    std::memcpy(tab.h.member, h_member, nm * sizeof(int64_t));
     Call call(c);
     TRY(call.opened);
-    TRY(carve(c, scratch, S_SUM_IDX, [&](Layout L) { return parts(L, d_off, d_mem); }));
-    HIPCHK(c, hipMemcpyAsync(d_off, h_off, (ns + 1 + nm) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    TRY(send(call, S_SUM_IDX, tab));
     {
         Timer t(c, SPKD_T_REDUCE_SETS);
         hipLaunchKernelGGL(k_sum_records, dim3((unsigned)n_sets), dim3(SUM_TPB), 0, c->stream, d_src,
-                           (const int64_t*)d_mem, (const int64_t*)d_off, d_dst);
+                           (const int64_t*)tab.d.member, (const int64_t*)tab.d.off, d_dst);
     }
     HIPCHK(c, hipGetLastError());
     return call.finish();
@@ -2480,26 +2518,17 @@ static_assert(FB_TILE == SPKD_FB_TILE, "the header states the kernel's tile");
 namespace {
 // The index and token table of spkd_fb_posterior_batch, as the kernel takes it: per sequence its first
 // frame, its first tile of stored forward vectors, its first token and its word count; per token its
-// first frame and word.  parts() is listed once and placed twice, as SeqTable's.
-struct FbTable {
-    struct Tab { long long *begin, *tile_off, *tok_off, *tok_frame; int *seq_n, *tok_word; } h{}, d{};
-    size_t ns = 0, ntok = 0, image = 0;
-    bool tokens = false;
-
-    size_t parts(Layout L, Tab& t) const {
-        return L.part(t.begin, ns + 1).part(t.tile_off, ns + 1).part(t.tok_off, ns + 1).part(t.tok_frame, ntok)
-            .part(t.seq_n, ns).part(t.tok_word, ntok).bytes();
-    }
-};
+// first frame and word.
+struct FbTab { long long *frame_off, *tile_off, *tok_off, *tok_frame; int *seq_n, *tok_word; };
 
 extern "C++" {
 template <int G>
-void fb_launch(spkd_ctx* c, const float* d_scores, const FbTable& t, int64_t n_seq, int S, double penalty, double scale,
-               double* fwd, float* d_post, double* d_conf, double* d_logz) {
+void fb_launch(spkd_ctx* c, const float* d_scores, const FbTab& t, bool tokens, int64_t n_seq, int S, double penalty,
+               double scale, double* fwd, float* d_post, double* d_conf, double* d_logz) {
     hipLaunchKernelGGL(k_fb_posterior<G>, group_grid(n_seq, G), dim3(WAVE), 0, c->stream, d_scores,
-                       (const long long*)t.d.begin, (const long long*)t.d.tile_off, (const int*)t.d.seq_n,
-                       (long long)n_seq, S, penalty, scale, t.tokens ? (const long long*)t.d.tok_off : nullptr,
-                       (const long long*)t.d.tok_frame, (const int*)t.d.tok_word, fwd, d_post, d_conf, d_logz);
+                       (const long long*)t.frame_off, (const long long*)t.tile_off, (const int*)t.seq_n,
+                       (long long)n_seq, S, penalty, scale, tokens ? (const long long*)t.tok_off : nullptr,
+                       (const long long*)t.tok_frame, (const int*)t.tok_word, fwd, d_post, d_conf, d_logz);
 }
 }  // extern "C++"
 }  // namespace
@@ -2548,40 +2577,42 @@ spkd_status spkd_fb_posterior_batch(spkd_ctx* c, const float* d_scores, int64_t 
     }
     if (!d_scores) return fail(c, SPKD_EINVAL, "fb_posterior_batch: null device buffer");
     if (n_seq > 0x7fffffff) return fail(c, SPKD_EINVAL, "fb_posterior_batch: too many sequences in one call");
-    FbTable t;
-    t.ns = (size_t)n_seq, t.ntok = (size_t)n_tok, t.tokens = tokens;
-    TRY(carve(c, pinned, PIN_FB_TAB, [&](Layout L) { return t.image = t.parts(L, t.h); }));
-    std::memcpy(t.h.begin, h_frame_off, (t.ns + 1) * sizeof(int64_t));
+    const size_t ns = (size_t)n_seq, ntok = (size_t)n_tok;
+    auto t = mirror<FbTab>([&](Layout L, FbTab& p) {
+        return L.part(p.frame_off, ns + 1).part(p.tile_off, ns + 1).part(p.tok_off, ns + 1).part(p.tok_frame, ntok)
+            .part(p.seq_n, ns).part(p.tok_word, ntok).bytes();
+    });
+    TRY(stage(c, PIN_FB_TAB, t));
+    std::memcpy(t.h.frame_off, h_frame_off, (ns + 1) * sizeof(int64_t));
     t.h.tile_off[0] = 0;
-    for (size_t q = 0; q < t.ns; ++q) {
+    for (size_t q = 0; q < ns; ++q) {
         t.h.tile_off[q + 1] = t.h.tile_off[q] + (h_frame_off[q + 1] - h_frame_off[q] + FB_TILE - 1) / FB_TILE;
         t.h.seq_n[q] = h_seq_n_cols ? h_seq_n_cols[q] : n_cols;
         t.h.tok_off[q + 1] = tokens ? h_tok_off[q + 1] : 0;
     }
     t.h.tok_off[0] = 0;
     if (n_tok) {
-        std::memcpy(t.h.tok_frame, h_tok_frame, t.ntok * sizeof(int64_t));
-        std::memcpy(t.h.tok_word, h_tok_word, t.ntok * sizeof(int32_t));
+        std::memcpy(t.h.tok_frame, h_tok_frame, ntok * sizeof(int64_t));
+        std::memcpy(t.h.tok_word, h_tok_word, ntok * sizeof(int32_t));
     }
     const int G = group_width(n_cols);
     Call call(c);
     TRY(call.opened);
-    TRY(carve(c, scratch, S_FB_TAB, [&](Layout L) { return t.parts(L, t.d); }));
-    HIPCHK(c, hipMemcpyAsync(t.d.begin, t.h.begin, t.image, hipMemcpyHostToDevice, c->stream));
+    TRY(send(call, S_FB_TAB, t));
     void* p = nullptr;
-    TRY(scratch(c, S_FB_FWD, (size_t)t.h.tile_off[t.ns] * (size_t)G * sizeof(double), &p));
+    TRY(scratch(c, S_FB_FWD, (size_t)t.h.tile_off[ns] * (size_t)G * sizeof(double), &p));
     double* fwd = (double*)p;
     double *d_conf = nullptr, *d_logz = nullptr;
-    TRY(carve(c, scratch, S_FB_OUT, [&](Layout L) { return L.part(d_logz, t.ns).part(d_conf, t.ntok).bytes(); }));
+    TRY(carve(c, scratch, S_FB_OUT, [&](Layout L) { return L.part(d_logz, ns).part(d_conf, ntok).bytes(); }));
     {
         Timer tm(c, SPKD_T_FB_POSTERIOR);
         with_group(n_cols, [&](auto g) {
-            fb_launch<decltype(g)::value>(c, d_scores, t, n_seq, n_cols, penalty, scale, fwd, d_post, d_conf, d_logz);
+            fb_launch<decltype(g)::value>(c, d_scores, t.d, tokens, n_seq, n_cols, penalty, scale, fwd, d_post, d_conf, d_logz);
         });
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h_logz, d_logz, t.ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (n_tok) HIPCHK(c, hipMemcpyAsync(h_conf, d_conf, t.ntok * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_logz, d_logz, ns * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (n_tok) HIPCHK(c, hipMemcpyAsync(h_conf, d_conf, ntok * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     return call.finish();
 }
 
@@ -2609,24 +2640,22 @@ spkd_status spkd_gauss_models(spkd_ctx* c, const double* d_stats, int64_t n, dou
 }
 
 namespace {
-extern "C++" {
-// An index table (SeqTable, RangeTable) goes up in one copy.  Its parts() are listed once and placed twice:
-// by build(), before the Call, as the image h in pinned memory that the checked arguments fill; by this,
-// inside the Call, as d on the device, with the copy enqueued.
-template <class Table>
-spkd_status send_table(spkd_ctx* c, int slot, Table& t) {
-    TRY(carve(c, scratch, slot, [&](Layout L) { return t.parts(L, t.d); }));
-    HIPCHK(c, hipMemcpyAsync(t.d.begin, t.h.begin, t.image, hipMemcpyHostToDevice, c->stream));
+// what spkd_gauss_loglik, spkd_gmm_loglik_seq and spkd_post_stats ask of each sequence (`name` opens the messages)
+spkd_status check_seq(spkd_ctx* c, const char* name, int64_t b, int64_t e, int64_t n_frames, int64_t m, int64_t k,
+                      int32_t n_cols, int64_t n_models) {
+    if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, std::string(name) + ": sequence outside [0, n_frames]");
+    if (k < 0 || k > n_cols) return fail(c, SPKD_EINVAL, std::string(name) + ": 0 <= models of a sequence <= n_cols");
+    if (m < 0 || m + k > n_models) return fail(c, SPKD_EINVAL, std::string(name) + ": model index out of range");
     return SPKD_OK;
 }
-}  // extern "C++"
 
 // The sequence table of spkd_gauss_loglik and spkd_gmm_loglik_seq, as the kernels take it: per sequence its
 // frames [begin, end), its first row of the scores, its first tile, its first model and its model count;
-// per model ok; per tile its sequence.
+// per model ok; per tile its sequence.  A mirrored block: build() stages and fills it, send() sends it.
 struct SeqTable {
     struct Tab { long long *begin, *end, *row, *tile; int *model, *n_models, *ok, *tile_seq; } h{}, d{};
-    size_t ns = 0, nm = 0, nt = 0, image = 0;  // sequences, models, tiles (0: no frame, nothing to do), bytes
+    Image host, dev;
+    size_t ns = 0, nm = 0, nt = 0;  // sequences, models, tiles (0: no frame, nothing to do)
 
     size_t parts(Layout L, Tab& t) const {
         return L.part(t.begin, ns).part(t.end, ns).part(t.row, ns).part(t.tile, ns).part(t.model, ns).part(t.n_models, ns)
@@ -2645,16 +2674,13 @@ struct SeqTable {
         int64_t n_tiles = 0;
         for (int64_t q = 0; q < n_seq; ++q) {
             const int64_t b = h_seq_begin[q], e = h_seq_end[q];
-            if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, name + ": sequence outside [0, n_frames]");
-            const int64_t m = h_seq_model[q], k = h_seq_n_models[q];
-            if (k < 0 || k > n_cols) return fail(c, SPKD_EINVAL, name + ": 0 <= models of a sequence <= n_cols");
-            if (m < 0 || m + k > n_models) return fail(c, SPKD_EINVAL, name + ": model index out of range");
+            TRY(check_seq(c, name.c_str(), b, e, n_frames, h_seq_model[q], h_seq_n_models[q], n_cols, n_models));
             n_tiles += (e - b + tile_frames - 1) / tile_frames;
         }
         if (n_tiles == 0) return SPKD_OK;
         if (n_tiles > 0x7fffffff) return fail(c, SPKD_EINVAL, name + ": too many frames in one call");
         ns = (size_t)n_seq, nm = (size_t)n_models, nt = (size_t)n_tiles;
-        TRY(carve(c, pinned, pin_slot, [&](Layout L) { return image = parts(L, h); }));
+        TRY(stage(c, pin_slot, *this));
         std::memcpy(h.begin, h_seq_begin, ns * sizeof(int64_t));
         std::memcpy(h.end, h_seq_end, ns * sizeof(int64_t));
         std::memcpy(h.model, h_seq_model, ns * sizeof(int32_t));
@@ -2689,7 +2715,7 @@ spkd_status spkd_gauss_loglik(spkd_ctx* c, const float* d_frames, int64_t n_fram
     if (!t.nt) return SPKD_OK;
     Call call(c);
     TRY(call.opened);
-    TRY(send_table(c, S_GAUSS_IDX, t));
+    TRY(send(call, S_GAUSS_IDX, t));
     {
         Timer tm(c, SPKD_T_GAUSS_LOGLIK);
         hipLaunchKernelGGL(k_gauss_loglik, dim3((unsigned)t.nt), dim3(WAVE), 0, c->stream, d_frames, d_models, t.d.ok,
@@ -2702,18 +2728,6 @@ spkd_status spkd_gauss_loglik(spkd_ctx* c, const float* d_frames, int64_t n_fram
 
 // ------------------------------------------------------------------ (8) speakers from posteriors
 static_assert(STATS_CHUNK == SPKD_POST_CHUNK, "the header states the kernel's chunk");
-
-namespace {
-// The work table of spkd_post_stats, as the kernels take it: per workgroup of k_post_chunk_stats its
-// chunk, column and partial record; per model the first of its partial records (k_reduce_sets' sets).
-// parts() is listed once and placed twice, as SeqTable's.
-struct PostTable {
-    struct Tab { PostItem* begin; long long* model_off; } h{}, d{};
-    size_t ni = 0, nm = 0, image = 0;
-
-    size_t parts(Layout L, Tab& t) const { return L.part(t.begin, ni).part(t.model_off, nm + 1).bytes(); }
-};
-}  // namespace
 
 spkd_status spkd_post_stats(spkd_ctx* c, const float* d_frames, int64_t n_frames, const float* d_post, int64_t n_seq,
                             const int64_t* h_seq_begin, const int64_t* h_seq_end, const int32_t* h_seq_model,
@@ -2731,11 +2745,8 @@ spkd_status spkd_post_stats(spkd_ctx* c, const float* d_frames, int64_t n_frames
     std::vector<int64_t> count((size_t)n_models, 0);
     int64_t n_items = 0;
     for (int64_t q = 0; q < n_seq; ++q) {
-        const int64_t b = h_seq_begin[q], e = h_seq_end[q];
-        if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, "post_stats: sequence outside [0, n_frames]");
-        const int64_t m = h_seq_model[q], k = h_seq_n_models[q];
-        if (k < 0 || k > n_cols) return fail(c, SPKD_EINVAL, "post_stats: 0 <= models of a sequence <= n_cols");
-        if (m < 0 || m + k > n_models) return fail(c, SPKD_EINVAL, "post_stats: model index out of range");
+        const int64_t b = h_seq_begin[q], e = h_seq_end[q], m = h_seq_model[q], k = h_seq_n_models[q];
+        TRY(check_seq(c, "post_stats", b, e, n_frames, m, k, n_cols, n_models));
         const int64_t chunks = (e - b + STATS_CHUNK - 1) / STATS_CHUNK;
         for (int64_t j = m; j < m + k; ++j) {
             int32_t* cv = &cover[(size_t)j * 2];
@@ -2748,14 +2759,17 @@ spkd_status spkd_post_stats(spkd_ctx* c, const float* d_frames, int64_t n_frames
     }
     if (n_items > 0x7fffffff) return fail(c, SPKD_EINVAL, "post_stats: too many frames in one call");
     if (n_models == 0) return SPKD_OK;
-    PostTable t;
-    t.ni = (size_t)n_items, t.nm = (size_t)n_models;
-    TRY(carve(c, pinned, PIN_POST_TAB, [&](Layout L) { return t.image = t.parts(L, t.h); }));
+    // the work table, as the kernels take it: per workgroup of k_post_chunk_stats its chunk, column and
+    // partial record; per model the first of its partial records (k_reduce_sets' sets)
+    const size_t ni = (size_t)n_items, nm = (size_t)n_models;
+    struct Tab { PostItem* item; long long* model_off; };
+    auto t = mirror<Tab>([&](Layout L, Tab& p) { return L.part(p.item, ni).part(p.model_off, nm + 1).bytes(); });
+    TRY(stage(c, PIN_POST_TAB, t));
     t.h.model_off[0] = 0;
-    for (size_t j = 0; j < t.nm; ++j) t.h.model_off[j + 1] = t.h.model_off[j] + count[j];
+    for (size_t j = 0; j < nm; ++j) t.h.model_off[j + 1] = t.h.model_off[j] + count[j];
     // a model's partial records: consecutive, in the order (sequence of the call, chunk); `count` turns cursor
-    for (size_t j = 0; j < t.nm; ++j) count[j] = t.h.model_off[j];
-    PostItem* it = t.h.begin;
+    for (size_t j = 0; j < nm; ++j) count[j] = t.h.model_off[j];
+    PostItem* it = t.h.item;
     int64_t row = 0;
     for (int64_t q = 0; q < n_seq; ++q) {
         const int64_t b = h_seq_begin[q], e = h_seq_end[q];
@@ -2772,14 +2786,14 @@ spkd_status spkd_post_stats(spkd_ctx* c, const float* d_frames, int64_t n_frames
     }
     Call call(c);
     TRY(call.opened);
-    TRY(send_table(c, S_POST_TAB, t));
+    TRY(send(call, S_POST_TAB, t));
     void* d_partial = nullptr;
-    TRY(scratch(c, S_POST_PARTIAL, t.ni * REC * sizeof(double), &d_partial));
+    TRY(scratch(c, S_POST_PARTIAL, ni * REC * sizeof(double), &d_partial));
     {
         Timer tm(c, SPKD_T_POST_STATS);
-        if (t.ni)
-            hipLaunchKernelGGL(k_post_chunk_stats, dim3((unsigned)t.ni), dim3(STATS_TPB), 0, c->stream, d_frames, d_post,
-                               (const PostItem*)t.d.begin, (int)n_cols, (double*)d_partial);
+        if (ni)
+            hipLaunchKernelGGL(k_post_chunk_stats, dim3((unsigned)ni), dim3(STATS_TPB), 0, c->stream, d_frames, d_post,
+                               (const PostItem*)t.d.item, (int)n_cols, (double*)d_partial);
         hipLaunchKernelGGL(k_reduce_sets, dim3((unsigned)n_models), dim3(STATS_TPB), 0, c->stream,
                            (const double*)d_partial, (const int64_t*)t.d.model_off, d_stats);
     }
@@ -2794,10 +2808,11 @@ static_assert(GT_COMP == SPKD_GMM_COMP && GT_MAX_COMP == SPKD_GMM_MAX_COMP && GT
 namespace {
 // The range-set table of spkd_gmm_train and spkd_ubm_stats, as the kernels take it: per range its first
 // frame and the ordinal of that frame among its speaker's; per speaker its ranges [set_off], its frame
-// count n and its chunks [chunk_off]; per chunk its speaker and its index within the speaker.
+// count n and its chunks [chunk_off]; per chunk its speaker and its index within the speaker.  A mirrored block.
 struct RangeTable {
     struct Tab { long long *begin, *ord, *set_off, *n, *chunk_off; int *chunk_spk, *chunk_idx; } h{}, d{};
-    size_t ns = 0, nr = 0, nc = 0, image = 0;  // speakers, ranges, chunks, bytes
+    Image host, dev;
+    size_t ns = 0, nr = 0, nc = 0;  // speakers, ranges, chunks
 
     size_t parts(Layout L, Tab& t) const {
         return L.part(t.begin, nr).part(t.ord, nr).part(t.set_off, ns + 1).part(t.n, ns).part(t.chunk_off, ns + 1)
@@ -2821,7 +2836,7 @@ struct RangeTable {
         }
         if (n_chunks > 0x7fffffff) return fail(c, SPKD_EINVAL, name + ": too many frames in one call");
         ns = (size_t)n_speakers, nr = (size_t)h_set_off[n_speakers], nc = (size_t)n_chunks;
-        TRY(carve(c, pinned, pin_slot, [&](Layout L) { return image = parts(L, h); }));
+        TRY(stage(c, pin_slot, *this));
         std::memcpy(h.begin, h_range_begin, nr * sizeof(int64_t));
         std::memcpy(h.set_off, h_set_off, (ns + 1) * sizeof(int64_t));
         long long chunk = 0;
@@ -2852,7 +2867,7 @@ spkd_status spkd_gmm_train(spkd_ctx* c, const float* d_frames, int64_t n_frames,
     if (n_speakers == 0) return SPKD_OK;
     if (!d_frames || !h_set_off || !h_range_begin || !h_range_end || !d_gmm || !h_ok || (n_iter > 0 && !h_loglik))
         return fail(c, SPKD_EINVAL, "null argument");
-    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "gmm_train: 1 <= n_comp <= 8");
+    if (bad_comp(n_comp)) return fail(c, SPKD_EINVAL, "gmm_train: 1 <= n_comp <= 8");
     if (n_iter < 0) return fail(c, SPKD_EINVAL, "gmm_train: n_iter >= 0");
     if (!(var_floor >= 0.0) || !std::isfinite(var_floor)) return fail(c, SPKD_EINVAL, "gmm_train: var_floor must be finite and >= 0");
     if (n_frames < 0 || n_speakers > 0x7fffffff) return fail(c, SPKD_EINVAL, "gmm_train: bad count");
@@ -2861,18 +2876,15 @@ spkd_status spkd_gmm_train(spkd_ctx* c, const float* d_frames, int64_t n_frames,
     TRY(t.build(c, "gmm_train", PIN_GT_TAB, n_frames, n_speakers, h_set_off, h_range_begin, h_range_end));
     const size_t ns = t.ns, nc = t.nc, nl = ns * (size_t)n_iter;
     // what comes back: the ok flags and the log-likelihoods, through pinned memory as well
-    struct Out { double* loglik; int32_t* ok; } ho, dout;
+    struct Out { double* loglik; int32_t* ok; };
+    auto out = mirror<Out>([&](Layout L, Out& o) { return L.part(o.loglik, nl).part(o.ok, ns).bytes(); });
     double *d_part = nullptr, *d_part_ll = nullptr, *d_floor = nullptr;
-    auto outs = [&](Layout L, Out& o) { return L.part(o.loglik, nl).part(o.ok, ns).bytes(); };
-    size_t out_bytes = 0;
-    TRY(carve(c, pinned, PIN_GT_OUT, [&](Layout L) { return out_bytes = outs(L, ho); }));
+    TRY(stage(c, PIN_GT_OUT, out));
     Call call(c);
     TRY(call.opened);
-    TRY(send_table(c, S_GT_TAB, t));
+    TRY(send(call, S_GT_TAB, t));
     TRY(carve(c, scratch, S_GT_WORK, [&](Layout L) {
-        outs(L, dout);                                                   // (first: one copy down)
-        L.at = out_bytes;
-        return L.part(d_part, nc * (size_t)n_comp * GT_COMP).part(d_part_ll, nc).part(d_floor, ns * WAVE).bytes();
+        return place(L, out).part(d_part, nc * (size_t)n_comp * GT_COMP).part(d_part_ll, nc).part(d_floor, ns * WAVE).bytes();
     }));
     {
         Timer tm(c, SPKD_T_GMM_TRAIN);
@@ -2885,7 +2897,7 @@ spkd_status spkd_gmm_train(spkd_ctx* c, const float* d_frames, int64_t n_frames,
         auto mstep = [&](int init, int iter) {
             hipLaunchKernelGGL(k_gmm_mstep, dim3((unsigned)ns), dim3(WAVE), 0, c->stream, d_part, d_part_ll, t.d.chunk_off,
                                t.d.n, (int)n_comp, init, from_model ? 0 : 1, var_floor, iter, (int)n_iter, d_gmm, d_floor,
-                               dout.ok, dout.loglik);
+                               out.d.ok, out.d.loglik);
         };
         // the whole loop in one go: the hard pass (floor, first ok, initial model), then n_iter EM steps
         estep(std::true_type());
@@ -2896,10 +2908,10 @@ spkd_status spkd_gmm_train(spkd_ctx* c, const float* d_frames, int64_t n_frames,
         }
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(ho.loglik, dout.loglik, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    TRY(copy(call, out, hipMemcpyDeviceToHost));
     TRY(call.finish());
-    std::memcpy(h_ok, ho.ok, ns * sizeof(int32_t));
-    if (nl) std::memcpy(h_loglik, ho.loglik, nl * sizeof(double));
+    std::memcpy(h_ok, out.h.ok, ns * sizeof(int32_t));
+    if (nl) std::memcpy(h_loglik, out.h.loglik, nl * sizeof(double));
     return SPKD_OK;
 }
 
@@ -2911,14 +2923,14 @@ spkd_status spkd_gmm_loglik_seq(spkd_ctx* c, const float* d_frames, int64_t n_fr
     if (n_seq == 0) return SPKD_OK;
     if (!d_frames || !d_gmm || !h_model_ok || !h_seq_begin || !h_seq_end || !h_seq_model || !h_seq_n_models || !d_scores)
         return fail(c, SPKD_EINVAL, "null argument");
-    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: 1 <= n_comp <= 8");
+    if (bad_comp(n_comp)) return fail(c, SPKD_EINVAL, "gmm_loglik_seq: 1 <= n_comp <= 8");
     SeqTable t;
     TRY(t.build(c, "gmm_loglik_seq", GT_TILE, PIN_GT_IDX, d_frames, n_frames, d_gmm, n_models, h_model_ok, n_seq,
                 h_seq_begin, h_seq_end, h_seq_model, h_seq_n_models, n_cols, d_scores));
     if (!t.nt) return SPKD_OK;
     Call call(c);
     TRY(call.opened);
-    TRY(send_table(c, S_GT_IDX, t));
+    TRY(send(call, S_GT_IDX, t));
     {
         Timer tm(c, SPKD_T_GMM_SEQ_LOGLIK);
         hipLaunchKernelGGL(k_gmm_loglik_seq, dim3((unsigned)t.nt), dim3(WAVE), 0, c->stream, d_frames, d_gmm, (int)n_comp,
@@ -2939,35 +2951,32 @@ spkd_status spkd_ubm_stats(spkd_ctx* c, const float* d_frames, int64_t n_frames,
     if (n_speakers == 0) return SPKD_OK;
     if (!d_frames || !d_ubm || !h_set_off || !h_range_begin || !h_range_end || !d_bw || !h_ok)
         return fail(c, SPKD_EINVAL, "null argument");
-    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "ubm_stats: 1 <= n_comp <= 8");
+    if (bad_comp(n_comp)) return fail(c, SPKD_EINVAL, "ubm_stats: 1 <= n_comp <= 8");
     if (n_frames < 0 || n_speakers > 0x7fffffff) return fail(c, SPKD_EINVAL, "ubm_stats: bad count");
     if ((uintptr_t)d_ubm % 16 || (uintptr_t)d_bw % 16 || (uintptr_t)d_frames % 4)
         return fail(c, SPKD_EINVAL, "ubm_stats: misaligned buffer (model and records: 16 bytes)");
     RangeTable t;
     TRY(t.build(c, "ubm_stats", PIN_UBM_TAB, n_frames, n_speakers, h_set_off, h_range_begin, h_range_end));
     const size_t ns = t.ns, nc = t.nc;
-    void* h_out = nullptr;
-    TRY(pinned(c, PIN_UBM_OUT, ns * sizeof(int32_t), &h_out));
+    auto ok = mirror<int32_t*>([&](Layout L, int32_t*& p) { return L.part(p, ns).bytes(); });   // (a block of one array)
+    TRY(stage(c, PIN_UBM_OUT, ok));
     Call call(c);
     TRY(call.opened);
-    TRY(send_table(c, S_UBM_TAB, t));
+    TRY(send(call, S_UBM_TAB, t));
     double* d_part = nullptr;
-    int32_t* d_ok = nullptr;
-    TRY(carve(c, scratch, S_UBM_WORK, [&](Layout L) {
-        return L.part(d_part, nc * (size_t)n_comp * BW_COMP).part(d_ok, ns).bytes();
-    }));
+    TRY(carve(c, scratch, S_UBM_WORK, [&](Layout L) { return place(L, ok).part(d_part, nc * (size_t)n_comp * BW_COMP).bytes(); }));
     {
         Timer tm(c, SPKD_T_UBM_STATS);
         if (nc)
             hipLaunchKernelGGL(k_ubm_estep, dim3((unsigned)nc), dim3(WAVE), 0, c->stream, d_frames, t.d.begin, t.d.ord,
                                t.d.set_off, t.d.n, t.d.chunk_spk, t.d.chunk_idx, d_ubm, (int)n_comp, d_part);
         hipLaunchKernelGGL(k_ubm_reduce, dim3((unsigned)ns), dim3(WAVE), 0, c->stream, d_part, t.d.chunk_off, t.d.n,
-                           (int)n_comp, d_bw, d_ok);
+                           (int)n_comp, d_bw, ok.d);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h_out, d_ok, ns * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    TRY(copy(call, ok, hipMemcpyDeviceToHost));
     TRY(call.finish());
-    std::memcpy(h_ok, h_out, ns * sizeof(int32_t));
+    std::memcpy(h_ok, ok.h, ns * sizeof(int32_t));
     return SPKD_OK;
 }
 
@@ -2980,7 +2989,7 @@ spkd_status spkd_clr_link(spkd_ctx* c, const double* d_bw, int64_t n, const int3
     if (!d_bw || !h_ok || !d_ubm || !h_merge_a || !h_merge_b || !h_merge_d || !h_n_merges || !h_stat_max || !h_stat_min)
         return fail(c, SPKD_EINVAL, "null argument");
     if (n > CL_MAX_N) return fail(c, SPKD_EINVAL, "clr_link: at most 4096 speakers");
-    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "clr_link: 1 <= n_comp <= 8");
+    if (bad_comp(n_comp)) return fail(c, SPKD_EINVAL, "clr_link: 1 <= n_comp <= 8");
     if (!(relevance > 0.0) || !std::isfinite(relevance)) return fail(c, SPKD_EINVAL, "clr_link: relevance must be finite and > 0");
     if (std::isnan(threshold)) return fail(c, SPKD_EINVAL, "clr_link: threshold is NaN");
     if (max_spk < 0) return fail(c, SPKD_EINVAL, "clr_link: max_spk >= 0");
@@ -2993,47 +3002,41 @@ spkd_status spkd_clr_link(spkd_ctx* c, const double* d_bw, int64_t n, const int3
         return SPKD_OK;
     }
     const size_t ns = (size_t)n, ne = ns * (size_t)n_comp * BW_COMP;
-    struct Out { double *d, *stat; int32_t *a, *b, *nm; } ho, dout;
-    auto outs = [&](Layout L, Out& o) { return L.part(o.d, ns).part(o.stat, 2).part(o.a, ns).part(o.b, ns).part(o.nm, 1).bytes(); };
-    size_t out_bytes = 0;
-    TRY(carve(c, pinned, PIN_CLR_OUT, [&](Layout L) { return out_bytes = outs(L, ho); }));
-    void* h_in = nullptr;
-    TRY(pinned(c, PIN_CLR_IN, ns * sizeof(int32_t), &h_in));
-    std::memcpy(h_in, h_ok, ns * sizeof(int32_t));
+    struct Out { double *d, *stat; int32_t *a, *b, *nm; };
+    auto out = mirror<Out>([&](Layout L, Out& o) { return L.part(o.d, ns).part(o.stat, 2).part(o.a, ns).part(o.b, ns).part(o.nm, 1).bytes(); });
+    auto ok = mirror<int32_t*>([&](Layout L, int32_t*& p) { return L.part(p, ns).bytes(); });   // (a block of one array)
+    TRY(stage(c, PIN_CLR_OUT, out));
+    TRY(stage(c, PIN_CLR_IN, ok));
+    std::memcpy(ok.h, h_ok, ns * sizeof(int32_t));
     Call call(c);
     TRY(call.opened);
     double *d_w = nullptr, *d_t = nullptr, *d_n = nullptr;
-    int32_t* d_ok = nullptr;
     void* d_mat = nullptr;
-    TRY(carve(c, scratch, S_CLR_WORK, [&](Layout L) {
-        outs(L, dout);                                                   // (first: one copy down)
-        L.at = out_bytes;
-        return L.part(d_w, ne).part(d_t, ne).part(d_n, ns).part(d_ok, ns).bytes();
-    }));
+    TRY(carve(c, scratch, S_CLR_WORK, [&](Layout L) { return place(place(L, out), ok).part(d_w, ne).part(d_t, ne).part(d_n, ns).bytes(); }));
     TRY(scratch(c, S_CLR_MAT, ns * ns * sizeof(double), &d_mat));
-    HIPCHK(c, hipMemcpyAsync(d_ok, h_in, ns * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    TRY(copy(call, ok, hipMemcpyHostToDevice));
     {
         Timer t(c, SPKD_T_CLR_LINK);
         hipLaunchKernelGGL(k_clr_prep, dim3((unsigned)ns), dim3(WAVE), 0, c->stream, d_bw, d_ubm, (int)n_comp, relevance,
                            d_w, d_t, d_n);
         hipLaunchKernelGGL(k_clr_matrix, dim3((unsigned)ns), dim3(CL_MAT_TPB), 0, c->stream, (const double*)d_w,
-                           (const double*)d_t, (const double*)d_n, (const int*)d_ok, (int)n, (int)n_comp, (double*)d_mat,
+                           (const double*)d_t, (const double*)d_n, (const int*)ok.d, (int)n, (int)n_comp, (double*)d_mat,
                            c->d_err);
         hipLaunchKernelGGL(k_clr_chain, dim3(1), dim3(CL_TPB), 0, c->stream, d_w, d_t, d_n, (double*)d_mat,
-                           (const int*)d_ok, (int)n, (int)n_comp, d_ubm, relevance, threshold, (int)max_spk, (int*)dout.a,
-                           (int*)dout.b, dout.d, (int*)dout.nm, dout.stat, c->d_err);
+                           (const int*)ok.d, (int)n, (int)n_comp, d_ubm, relevance, threshold, (int)max_spk, (int*)out.d.a,
+                           (int*)out.d.b, out.d.d, (int*)out.d.nm, out.d.stat, c->d_err);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(ho.d, dout.d, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    TRY(copy(call, out, hipMemcpyDeviceToHost));
     const spkd_status st = call.finish();
     if (st != SPKD_OK && st != SPKD_ENONFINITE) return st;
-    const int32_t nm = *ho.nm;                                           // (the log so far when a CLR was not finite)
+    const int32_t nm = *out.h.nm;                                        // (the log so far when a CLR was not finite)
     *h_n_merges = nm;
-    std::memcpy(h_merge_a, ho.a, (size_t)nm * sizeof(int32_t));
-    std::memcpy(h_merge_b, ho.b, (size_t)nm * sizeof(int32_t));
-    std::memcpy(h_merge_d, ho.d, (size_t)nm * sizeof(double));
-    *h_stat_max = ho.stat[0];
-    *h_stat_min = ho.stat[1];
+    std::memcpy(h_merge_a, out.h.a, (size_t)nm * sizeof(int32_t));
+    std::memcpy(h_merge_b, out.h.b, (size_t)nm * sizeof(int32_t));
+    std::memcpy(h_merge_d, out.h.d, (size_t)nm * sizeof(double));
+    *h_stat_max = out.h.stat[0];
+    *h_stat_min = out.h.stat[1];
     return st;
 }
 
@@ -3057,7 +3060,7 @@ spkd_status spkd_clr_identify(spkd_ctx* c, const double* d_probe_bw, int64_t n_p
         return fail(c, SPKD_EINVAL, "clr_identify: group_off runs from 0 to n_probe");
     for (int64_t g = 0; g < n_groups; ++g)
         if (h_group_off[g + 1] < h_group_off[g]) return fail(c, SPKD_EINVAL, "clr_identify: group_off must not go back");
-    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "clr_identify: 1 <= n_comp <= 8");
+    if (bad_comp(n_comp)) return fail(c, SPKD_EINVAL, "clr_identify: 1 <= n_comp <= 8");
     if (!(relevance > 0.0) || !std::isfinite(relevance)) return fail(c, SPKD_EINVAL, "clr_identify: relevance must be finite and > 0");
     if (std::isnan(threshold)) return fail(c, SPKD_EINVAL, "clr_identify: threshold is NaN");
     if (exclusive != 0 && exclusive != 1) return fail(c, SPKD_EINVAL, "clr_identify: exclusive is 0 or 1");
@@ -3072,26 +3075,20 @@ spkd_status spkd_clr_identify(spkd_ctx* c, const double* d_probe_bw, int64_t n_p
         }
         return SPKD_OK;
     }
-    struct In { int32_t *okp, *okg, *off; } hi, din;
-    struct Out { double *score, *second; int32_t* ident; } ho, dout;
-    auto ins = [&](Layout L, In& t) { return L.part(t.okp, S).part(t.okg, G).part(t.off, ng + 1).bytes(); };
-    auto outs = [&](Layout L, Out& o) { return L.part(o.score, S).part(o.second, S).part(o.ident, S).bytes(); };
-    size_t in_bytes = 0, out_bytes = 0;
-    TRY(carve(c, pinned, PIN_ID_IN, [&](Layout L) { return in_bytes = ins(L, hi); }));
-    TRY(carve(c, pinned, PIN_ID_OUT, [&](Layout L) { return out_bytes = outs(L, ho); }));
-    std::memcpy(hi.okp, h_probe_ok, S * sizeof(int32_t));
-    std::memcpy(hi.okg, h_gallery_ok, G * sizeof(int32_t));
-    for (size_t g = 0; g <= ng; ++g) hi.off[g] = (int32_t)h_group_off[g];
+    struct In { int32_t *okp, *okg, *off; };
+    struct Out { double *score, *second; int32_t* ident; };
+    auto in = mirror<In>([&](Layout L, In& t) { return L.part(t.okp, S).part(t.okg, G).part(t.off, ng + 1).bytes(); });
+    auto out = mirror<Out>([&](Layout L, Out& o) { return L.part(o.score, S).part(o.second, S).part(o.ident, S).bytes(); });
+    TRY(stage(c, PIN_ID_IN, in));
+    TRY(stage(c, PIN_ID_OUT, out));
+    std::memcpy(in.h.okp, h_probe_ok, S * sizeof(int32_t));
+    std::memcpy(in.h.okg, h_gallery_ok, G * sizeof(int32_t));
+    for (size_t g = 0; g <= ng; ++g) in.h.off[g] = (int32_t)h_group_off[g];
     Call call(c);
     TRY(call.opened);
     double *d_tp = nullptr, *d_np = nullptr, *d_tg = nullptr, *d_ng = nullptr;
-    char* d_in = nullptr;
     TRY(carve(c, scratch, S_ID_WORK, [&](Layout L) {
-        outs(L, dout);                                                   // (first: one copy down)
-        L.at = (out_bytes + 15) / 16 * 16;
-        L.part(d_in, in_bytes);                                          // (one copy up)
-        ins(Layout(d_in), din);
-        return L.part(d_tp, S * E).part(d_np, S).part(d_tg, G * E).part(d_ng, G).bytes();
+        return place(place(L, out), in).part(d_tp, S * E).part(d_np, S).part(d_tg, G * E).part(d_ng, G).bytes();
     }));
     double* d_mat = d_scores;
     if (!d_mat) {
@@ -3099,7 +3096,7 @@ spkd_status spkd_clr_identify(spkd_ctx* c, const double* d_probe_bw, int64_t n_p
         TRY(scratch(c, S_ID_MAT, S * G * sizeof(double), &p));
         d_mat = (double*)p;
     }
-    HIPCHK(c, hipMemcpyAsync(d_in, hi.okp, in_bytes, hipMemcpyHostToDevice, c->stream));
+    TRY(copy(call, in, hipMemcpyHostToDevice));
     {
         Timer t(c, SPKD_T_IDENT_SCORES);
         hipLaunchKernelGGL(k_ident_derive, dim3((unsigned)S), dim3(WAVE), 0, c->stream, d_probe_bw, d_ubm, (int)n_comp,
@@ -3108,22 +3105,22 @@ spkd_status spkd_clr_identify(spkd_ctx* c, const double* d_probe_bw, int64_t n_p
                            relevance, d_tg, d_ng);
         hipLaunchKernelGGL(k_ident_scores, dim3((unsigned)((S + ID_ROWS - 1) / ID_ROWS), (unsigned)((G + ID_COLS - 1) / ID_COLS)),
                            dim3(ID_TPB), 0, c->stream, d_probe_bw, (const double*)d_tp, (const double*)d_np,
-                           (const int*)din.okp, (int)S, d_gallery_bw, (const double*)d_tg, (const double*)d_ng,
-                           (const int*)din.okg, (int)G, (int)n_comp, d_mat, c->d_err);
+                           (const int*)in.d.okp, (int)S, d_gallery_bw, (const double*)d_tg, (const double*)d_ng,
+                           (const int*)in.d.okg, (int)G, (int)n_comp, d_mat, c->d_err);
     }
     {
         Timer t(c, SPKD_T_IDENT_ASSIGN);
         hipLaunchKernelGGL(k_ident_assign, dim3((unsigned)ng), dim3(CL_TPB), 0, c->stream, (const double*)d_mat,
-                           (const int*)din.okp, (const int*)din.okg, (const int*)din.off, (int)G, threshold, (int)exclusive,
-                           (int*)dout.ident, dout.score, dout.second, (const int*)c->d_err);
+                           (const int*)in.d.okp, (const int*)in.d.okg, (const int*)in.d.off, (int)G, threshold, (int)exclusive,
+                           (int*)out.d.ident, out.d.score, out.d.second, (const int*)c->d_err);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(ho.score, dout.score, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    TRY(copy(call, out, hipMemcpyDeviceToHost));
     const spkd_status st = call.finish();
     if (st != SPKD_OK && st != SPKD_ENONFINITE) return st;
-    std::memcpy(h_ident, ho.ident, S * sizeof(int32_t));                 // (every ident -1 when a score was not finite)
-    std::memcpy(h_score, ho.score, S * sizeof(double));
-    std::memcpy(h_second, ho.second, S * sizeof(double));
+    std::memcpy(h_ident, out.h.ident, S * sizeof(int32_t));              // (every ident -1 when a score was not finite)
+    std::memcpy(h_score, out.h.score, S * sizeof(double));
+    std::memcpy(h_second, out.h.second, S * sizeof(double));
     return st;
 }
 
@@ -3135,7 +3132,7 @@ spkd_status spkd_bw_accumulate(spkd_ctx* c, const double* d_src_bw, int64_t n_sr
     if (!d_src_bw || !h_set_off || !h_member || !h_dst || !h_keep || !d_dst_bw) return fail(c, SPKD_EINVAL, "null argument");
     if (n_src < 0 || n_dst < 0 || n_src > 0x7fffffff || n_dst > 0x7fffffff || n_sets > n_dst)
         return fail(c, SPKD_EINVAL, "bw_accumulate: bad count (a set per slot at most)");
-    if (n_comp < 1 || n_comp > GT_MAX_COMP) return fail(c, SPKD_EINVAL, "bw_accumulate: 1 <= n_comp <= 8");
+    if (bad_comp(n_comp)) return fail(c, SPKD_EINVAL, "bw_accumulate: 1 <= n_comp <= 8");
     if (h_set_off[0] != 0) return fail(c, SPKD_EINVAL, "bw_accumulate: set_off[0] must be 0");
     for (int64_t k = 0; k < n_sets; ++k)
         if (h_set_off[k + 1] < h_set_off[k]) return fail(c, SPKD_EINVAL, "bw_accumulate: set_off must not go back");
@@ -3153,23 +3150,21 @@ spkd_status spkd_bw_accumulate(spkd_ctx* c, const double* d_src_bw, int64_t n_sr
     if ((uintptr_t)d_src_bw % 16 || (uintptr_t)d_dst_bw % 16)
         return fail(c, SPKD_EINVAL, "bw_accumulate: misaligned buffer (records: 16 bytes)");
     const size_t ns = (size_t)n_sets, nm = (size_t)n_mem;
-    struct Tab { long long* off; int32_t *member, *slot, *keep; } ht, dt;
-    auto parts = [&](Layout L, Tab& t) { return L.part(t.off, ns + 1).part(t.member, nm).part(t.slot, ns).part(t.keep, ns).bytes(); };
-    size_t bytes = 0;
-    TRY(carve(c, pinned, PIN_ACC_TAB, [&](Layout L) { return bytes = parts(L, ht); }));
-    for (size_t k = 0; k <= ns; ++k) ht.off[k] = h_set_off[k];
-    std::memcpy(ht.member, h_member, nm * sizeof(int32_t));
-    std::memcpy(ht.slot, h_dst, ns * sizeof(int32_t));
-    std::memcpy(ht.keep, h_keep, ns * sizeof(int32_t));
+    struct Tab { long long* off; int32_t *member, *slot, *keep; };
+    auto tab = mirror<Tab>([&](Layout L, Tab& t) { return L.part(t.off, ns + 1).part(t.member, nm).part(t.slot, ns).part(t.keep, ns).bytes(); });
+    TRY(stage(c, PIN_ACC_TAB, tab));
+    for (size_t k = 0; k <= ns; ++k) tab.h.off[k] = h_set_off[k];
+    std::memcpy(tab.h.member, h_member, nm * sizeof(int32_t));
+    std::memcpy(tab.h.slot, h_dst, ns * sizeof(int32_t));
+    std::memcpy(tab.h.keep, h_keep, ns * sizeof(int32_t));
     Call call(c);
     TRY(call.opened);
-    TRY(carve(c, scratch, S_ACC_TAB, [&](Layout L) { return parts(L, dt); }));
-    HIPCHK(c, hipMemcpyAsync(dt.off, ht.off, bytes, hipMemcpyHostToDevice, c->stream));
+    TRY(send(call, S_ACC_TAB, tab));
     {
         Timer t(c, SPKD_T_BW_ACCUMULATE);
         hipLaunchKernelGGL(k_bw_accumulate, dim3((unsigned)ns), dim3(ID_ACC_TPB), 0, c->stream, d_src_bw,
-                           (const long long*)dt.off, (const int*)dt.member, (const int*)dt.slot, (const int*)dt.keep,
-                           (int)(n_comp * BW_COMP), d_dst_bw);
+                           (const long long*)tab.d.off, (const int*)tab.d.member, (const int*)tab.d.slot,
+                           (const int*)tab.d.keep, (int)(n_comp * BW_COMP), d_dst_bw);
     }
     HIPCHK(c, hipGetLastError());
     return call.finish();
