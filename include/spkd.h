@@ -510,6 +510,21 @@ spkd_status spkd_ahc(spkd_ctx *ctx, const double *d_stats, const int64_t *h_seg_
                      int32_t *h_n_merges, int32_t *h_merge_a, int32_t *h_merge_b,
                      double *h_merge_d, double *h_stat_max, double *h_stat_min);
 
+/* Head and rest of a MONO call that computes its matrices in full (spkd_ahc, spkd_ahc_fused; not
+ * SPKD_KL2_PINV): the K largest problems (ties by index) get their matrices first and run their
+ * merge loops on a side stream of the context, beside the matrices of the others; the call still
+ * returns with all of its work finished, whatever the status.  Results do not depend on K.
+ * SPKD_AHC_HEAD in the environment, read when the context is created: unset or -1 = the rule
+ * below decides, 0 = one launch of either kernel, k = the k largest (at most all).
+ * With K > 0, SPKD_T_MATRIX and SPKD_T_AHC are spans (first start to last end of the two
+ * launches of either kernel) that overlap.
+ * spkd_ahc_head_rule: the K in 0 .. 32 that the rule gives for these problem sizes (host only;
+ * -1: bad argument), a multiple of 32 (whole rounds of the shader engines: DESIGN.md par. 5),
+ * so 0 or 32; 0 for fewer than 16 problems, and where the predicted saving is under 1 %.
+ * spkd_last_ahc_head: the K of the context's most recent spkd_ahc / _matrix / _fused call. */
+int64_t spkd_ahc_head_rule(const int64_t *h_seg_off, int64_t n_problems);
+spkd_status spkd_last_ahc_head(spkd_ctx *ctx, int64_t *k);
+
 /* spkd_ahc for ONE problem of n records whose initial n x n matrix the caller supplies
  * (d_matrix, device, in exactly the form spkd_ahc would have computed: see
  * spkd_distance_rows): the merge loop of spk-clustering.py:201-240 alone.  stat_max_in /

@@ -661,6 +661,8 @@ constexpr int AHC_TPB = AHC_WAVES * WAVE;
 #ifdef SPKD_PROFILE
 __device__ unsigned long long g_step_prof[8];     // profiling builds: clocks inside the selection of k_ahc_step
 __device__ unsigned long long g_ahc_prof[8];      // profiling builds: rows rescanned, merges, 5 phase clocks of k_ahc
+constexpr int AHC_SPAN_PROBS = 4096;              // profiling builds: the wall clock (wall_clock64) at which the k_ahc
+__device__ unsigned long long g_ahc_span[2 * AHC_SPAN_PROBS];   // workgroup of problem p entered [2p] and left [2p + 1]
 #endif
 constexpr int NO_COL = 0x7fffffff;
 constexpr int AHC_MAX_N = 65536;       // records per problem (row-flag masks live in LDS)
@@ -822,7 +824,7 @@ __global__ __launch_bounds__(AHC_TPB) void k_ahc(
         int32_t* __restrict__ out_n, int32_t* __restrict__ out_a, int32_t* __restrict__ out_b,
         double* __restrict__ out_d, unsigned long long* stat_max, unsigned long long* stat_min,
         double* __restrict__ final_max, double* __restrict__ final_min, int* err,
-        double* pinv_ws) {
+        double* pinv_ws, const int32_t* __restrict__ prob_of_block) {
     extern __shared__ int32_t ids[];                    // alive partner slots of the merged cluster
     __shared__ double ldsA[QREC];
     __shared__ unsigned long long red3[AHC_WAVES][3];
@@ -833,7 +835,11 @@ __global__ __launch_bounds__(AHC_TPB) void k_ahc(
     __shared__ double s_tmax[AHC_WAVES];
     const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
     const QuadLane L = quad_lane();
-    const int p = blockIdx.x;
+    // (a launch over a subset of the problems names them: the head and the rest of ahc_impl)
+    const int p = prob_of_block ? prob_of_block[blockIdx.x] : (int)blockIdx.x;
+#ifdef SPKD_PROFILE
+    if (tid == 0 && p < AHC_SPAN_PROBS) g_ahc_span[2 * p] = wall_clock64();
+#endif
     const int64_t off = seg_off[p];
     const long long N = seg_off[p + 1] - off;
     double* Dm = mat + mat_off[p];
@@ -1054,6 +1060,9 @@ __global__ __launch_bounds__(AHC_TPB) void k_ahc(
         out_n[p] = n_merges;
         final_max[p] = mx;
         final_min[p] = fmin;
+#ifdef SPKD_PROFILE
+        if (p < AHC_SPAN_PROBS) g_ahc_span[2 * p + 1] = wall_clock64();
+#endif
     }
 }
 

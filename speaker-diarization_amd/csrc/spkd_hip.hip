@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <atomic>
 #include <thread>
@@ -57,6 +58,13 @@ struct spkd_ctx {
     int step_waves = 0;          // step chain: waves per workgroup (0 = by problem size, 4, 8)
     int step_partners = 0;       // step chain: partners per workgroup (0 = by problem size, 3, 7, 15)
     int64_t last_gw_items = 0;
+    // the head of a batch clustering call (ahc_impl): SPKD_AHC_HEAD (-1 = the rule decides, 0 = none, k = forced),
+    // the K of the most recent call, and the side stream its merge loops run on with the two events that order
+    // it against the call's stream (created by the first call that forks, destroyed with the context)
+    int ahc_head = -1;
+    int64_t last_ahc_head = 0;
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::string err;
     int* d_err = nullptr;
     unsigned long long* d_counter = nullptr;
@@ -202,8 +210,13 @@ struct Call {
     spkd_status opened;          // of the constructor: TRY(call.opened)
     int herr = 0;                // the device error word (a member: its copy may be in flight)
     bool drained = false;
+    bool forked = false, joined = false;   // the side stream: used by this call, and waited for by the call's stream
     explicit Call(spkd_ctx* ctx) : c(ctx) { opened = open(); }
-    ~Call() { if (!drained) (void)hipStreamSynchronize(c->stream); }
+    ~Call() {
+        if (drained) return;
+        (void)hipStreamSynchronize(c->stream);
+        if (forked) (void)hipStreamSynchronize(c->side);
+    }
     spkd_status open() {
         HIPCHK(c, hipSetDevice(c->device));
         for (int i = 0; i < SPKD_N_TIMERS; ++i) c->kused[i] = false;
@@ -212,11 +225,38 @@ struct Call {
         return SPKD_OK;
     }
 
-    // records the end event, waits, folds the device error word into a status
+    // The side stream of the context, for work of this call that may run beside what the call's stream
+    // does next: it starts behind everything the call's stream holds at this point (uploads, memsets and
+    // kernels of the call included).  Ordering is by the two events only; the bracket's promise covers
+    // the side stream from here on (join(), finish(), the destructor).
+    spkd_status fork() {
+        // (default priority: what it is gated on ends and its first workgroup starts within 20 us, with a
+        // k_matrix launch of the call's stream ready at the same moment -- profiles/ahc_head.json)
+        if (!c->side) HIPCHK(c, hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking));
+        if (!c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+        forked = true;                     // (from the first enqueue that names the side stream)
+        HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0));
+        return SPKD_OK;
+    }
+    // the call's stream goes on behind what the side stream holds: before the first copy of a result
+    spkd_status join() {
+        if (!forked || joined) return SPKD_OK;
+        HIPCHK(c, hipEventRecord(c->ev_join, c->side));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+        joined = true;
+        return SPKD_OK;
+    }
+
+    // records the end event, waits, folds the device error word into a status (both streams OR into
+    // the one word: it is copied behind the join, and read after both have drained)
     spkd_status finish() {
+        TRY(join());
         HIPCHK(c, hipEventRecord(c->ev1, c->stream));
         HIPCHK(c, hipMemcpyAsync(&herr, c->d_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (forked) HIPCHK(c, hipStreamSynchronize(c->side));
         drained = true;
         HIPCHK(c, hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1));
         c->kms[0] = c->last_ms;
@@ -375,6 +415,9 @@ static spkd_status create_ctx(int device, void* stream, bool borrow, spkd_ctx** 
     if (const char* e = getenv("SPKD_GW_WAVES")) c->gw_waves = atoi(e);
     if (const char* e = getenv("SPKD_STEP_WAVES")) { const int v = atoi(e); c->step_waves = (v == 4 || v == 8) ? v : 0; }
     if (const char* e = getenv("SPKD_STEP_PARTNERS")) { const int v = atoi(e); c->step_partners = (v == 3 || v == 7 || v == 15) ? v : 0; }
+    // problems of a batch clustering call whose merge loops start under the others' matrices: -1 = by the
+    // rule (ahc_head_rule), 0 = none, k = the k largest (results do not depend on it)
+    if (const char* e = getenv("SPKD_AHC_HEAD")) { const int v = atoi(e); c->ahc_head = v >= 0 ? v : -1; }
     *out = c;
     return SPKD_OK;
 }
@@ -391,6 +434,12 @@ void spkd_destroy(spkd_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->side) {
+        (void)hipStreamSynchronize(c->side);
+        (void)hipStreamDestroy(c->side);
+    }
+    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     for (int i = 0; i < N_SLOTS; ++i)
         if (c->slot[i]) (void)hipFree(c->slot[i]);
     if (c->d_err) (void)hipFree(c->d_err);
@@ -568,8 +617,62 @@ struct AhcPrep {
     int64_t n_total = 0;
     int64_t grid_rows = 0;           // k_matrix's grid
     std::vector<char> offs;          // seg_off | mat_off
-    std::vector<char> prob_of;       // record -> its problem | k_matrix's launch order
+    std::vector<char> prob_of;       // record -> its problem | k_matrix's launch order (| the head's: below)
+    // Head and rest (ahc_impl sets head_k before ahc_prepare; 0: one launch over all problems, none of this).
+    // The head is the head_k largest problems, ties by index.  ahc_prepare then leaves the rest's k_matrix to its
+    // caller (matrix_launch): grid_rows and d_sched are the rest's, grid_head and d_sched_head the head's, and
+    // k_ahc's two launches take their problems from d_block_head (head_k of them) and d_block_rest.
+    int64_t head_k = 0;
+    int64_t grid_head = 0;
+    int64_t n_max_head = 0, n_max_rest = 0;     // the largest problem of either launch (k_ahc's dynamic LDS)
+    int32_t *d_prob = nullptr, *d_sched = nullptr, *d_sched_head = nullptr, *d_block_head = nullptr, *d_block_rest = nullptr;
+    int variant = 1, kind = 0;
+    double lambdac = 0.0;
 };
+
+// k_matrix's launch order over a subset of the problems (`order`: largest first), in the form the
+// kernel takes: block b computes the matrix row of record sched[b] (-1: nothing).  Workgroups go to
+// the eight XCDs round-robin by block index and every XCD has an L2 of its own, so the rows of one
+// problem -- they all read that problem's records as partners -- are given to ONE XCD: its working
+// set is then a problem or two (2.5 MB each at N = 390) instead of a slice of all of them.  Whole
+// problems are dealt to the least-loaded XCD, largest first; with fewer problems than XCDs the rows
+// are dealt round-robin instead.  by_xcd (optional): the problems in the order in which a launch of one
+// block per problem meets the same dealing (block b on XCD b mod 8, as far as the lists are even).
+constexpr int N_XCD = 8;
+void deal_to_xcds(const int64_t* h_seg_off, const std::vector<int64_t>& order, std::vector<int32_t>& sched,
+                  std::vector<int32_t>* by_xcd = nullptr) {
+    const int X = N_XCD;
+    std::vector<std::vector<int32_t>> lists(X), probs(X);
+    if ((int64_t)order.size() >= X) {
+        double load[X] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int64_t p : order) {
+            int x = 0;
+            for (int i = 1; i < X; ++i) if (load[i] < load[x]) x = i;
+            const double n = (double)(h_seg_off[p + 1] - h_seg_off[p]);
+            load[x] += n * n;
+            probs[x].push_back((int32_t)p);
+            for (int64_t r = h_seg_off[p]; r < h_seg_off[p + 1]; ++r) lists[x].push_back((int32_t)r);
+        }
+    } else {
+        std::vector<int64_t> asc(order);                 // (the rows in record order; a problem per XCD)
+        std::sort(asc.begin(), asc.end());
+        int64_t i = 0;
+        for (size_t k = 0; k < order.size(); ++k) {
+            probs[k].push_back((int32_t)order[k]);
+            for (int64_t r = h_seg_off[asc[k]]; r < h_seg_off[asc[k] + 1]; ++r) lists[(size_t)(i++ % X)].push_back((int32_t)r);
+        }
+    }
+    size_t longest = 0;
+    for (auto& l : lists) longest = std::max(longest, l.size());
+    sched.assign(longest * X, -1);
+    for (int x = 0; x < X; ++x)
+        for (size_t i = 0; i < lists[x].size(); ++i) sched[i * X + x] = lists[x][i];
+    if (by_xcd) {
+        by_xcd->clear();
+        for (size_t i = 0; by_xcd->size() < order.size(); ++i)
+            for (int x = 0; x < X; ++x) if (i < probs[x].size()) by_xcd->push_back(probs[x][i]);
+    }
+}
 
 unsigned long long host_dkey(double v) {                      // dkey() of spkd_cluster.hpp, on the host
     unsigned long long b;
@@ -607,6 +710,58 @@ void cluster_prep(spkd_ctx* c, const double* ex, int64_t n, int kind, double* ld
                        c->pinv_cur);
 }
 
+// one k_matrix launch over the rows of a schedule that ahc_prepare uploaded, on the call's stream
+void matrix_launch(spkd_ctx* c, const AhcPrep& B, const int32_t* d_sched, int64_t grid) {
+    if (grid <= 0) return;
+    auto kmat = B.kind == SPKD_GLR ? k_matrix<true> : k_matrix<false>;   // GLR has a second rank-one term
+    hipLaunchKernelGGL(kmat, dim3((unsigned)grid), dim3(MX_WAVES * WAVE), 0, c->stream,
+                       (const double*)B.ex, (const double*)B.pk, (const int64_t*)B.seg_off, (const int32_t*)B.d_prob,
+                       d_sched, B.variant, B.kind, B.lambdac,
+                       (const double*)B.ld, (const double*)B.aux, B.mat, (const int64_t*)B.mat_off,
+                       B.smax, B.smin, c->d_err);
+}
+
+// How many of the largest problems of a batch start their merge loops under the others' matrices
+// (ahc_impl).  k_ahc gives a problem one CU, so its launch ends with its largest problem; with the K
+// largest as the head, the stage ends at about
+//     max( M_head + t(largest head problem),
+//          M_head + M_rest * CUs / (CUs - K) + t(largest rest problem) )
+// where t(N) = AHC_MS_PER_N2 * N^2 is a lone problem's merge loop and M = MATRIX_MS_PER_N2 * (sum of N^2)
+// a k_matrix launch on the whole chip, of which the rest's has K CUs less.  n: the sizes, largest first.
+// Returns the K in 0 .. 32 that minimises this (the smallest of equals); 0 when that saves less than 1 %
+// of the stage with K = 0, and for fewer than 16 problems.  Only whole rounds of the chip's 32 shader
+// engines are candidates, which leaves K = 32: a k_ahc workgroup takes a CU, and the workgroups of a
+// launch are dealt in order to the eight XCDs and there to the four engines of eight CUs each, whatever
+// those hold already.  A workgroup of the rest whose engine is full -- a head problem on one of its CUs --
+// waits for that problem's exit, and the ones behind it on that XCD wait with it, while CUs elsewhere
+// idle.  Measured (profiles/ahc_head.json): K = 8 leaves 24 of the rest's workgroups waiting up to 18 ms
+// and the step 10 ms SLOWER than K = 0, K = 16 sixteen (+ 7 ms), K = 24 eight; with K = 32 every engine
+// holds one head problem, seven of the rest's fit beside it, none waits, and the step is 6.7 ms faster.
+// The two constants are the benchmark batch's, measured: the same file.
+constexpr int AHC_HEAD_ROUND = 32;             // XCDs x shader engines per XCD
+constexpr double AHC_MS_PER_N2 = 2.095e-4;
+constexpr double MATRIX_MS_PER_N2 = 6.00e-7;
+constexpr int AHC_HEAD_MAX = 32;
+constexpr int AHC_RULE_CUS = 256;              // of the MI355X
+int64_t ahc_head_rule(const std::vector<int64_t>& n, int cus) {
+    const int64_t n_prob = (int64_t)n.size();
+    if (n_prob < 16) return 0;
+    auto t = [](int64_t N) { return AHC_MS_PER_N2 * (double)N * (double)N; };
+    double sum_all = 0.0;
+    for (int64_t N : n) sum_all += (double)N * (double)N;
+    const double stage0 = MATRIX_MS_PER_N2 * sum_all + t(n[0]);
+    double best = stage0, sum_head = 0.0;
+    int64_t best_k = 0;
+    for (int64_t k = 1; k <= std::min<int64_t>(AHC_HEAD_MAX, n_prob) && k < cus; ++k) {
+        sum_head += (double)n[(size_t)k - 1] * (double)n[(size_t)k - 1];
+        const double m_head = MATRIX_MS_PER_N2 * sum_head, m_rest = MATRIX_MS_PER_N2 * (sum_all - sum_head);
+        const double rest = k < n_prob ? m_rest * cus / (double)(cus - k) + t(n[(size_t)k]) : 0.0;
+        const double stage = m_head + std::max(t(n[0]), rest);
+        if (k % AHC_HEAD_ROUND == 0 && stage < best) { best = stage; best_k = k; }
+    }
+    return stage0 - best < 0.01 * stage0 ? 0 : best_k;
+}
+
 spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_off, int64_t n_prob,
                         int variant, int kind, double lambdac, AhcPrep& B, const MatrixPlan& plan = MatrixPlan()) {
     const int64_t n_total = B.n_total = h_seg_off[n_prob];
@@ -623,50 +778,45 @@ spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg
     std::vector<int32_t> prob((size_t)n_total, 0);   // record -> its problem
     for (int64_t p = 0; p < n_prob; ++p)
         for (int64_t r = h_seg_off[p]; r < h_seg_off[p + 1]; ++r) prob[(size_t)r] = (int32_t)p;
-    // k_matrix's launch order, in the same upload: block b computes the matrix row
-    // of record sched[b] (-1: nothing).  Workgroups go to the eight XCDs round-robin by block
-    // index and every XCD has an L2 of its own, so the rows of one problem -- they all read
-    // that problem's records as partners -- are given to ONE XCD: its working set is then a
-    // problem or two (2.5 MB each at N = 390) instead of a slice of all of them.  Whole
-    // problems are dealt to the least-loaded XCD, largest first; with fewer problems than
-    // XCDs the rows are dealt round-robin instead.
-    int32_t *d_prob = nullptr, *d_sched = nullptr;
+    // k_matrix's launch order (deal_to_xcds), in the same upload; with a head, a schedule of its own for
+    // either launch, and the problems of k_ahc's two launches behind them
     {
-        const int X = 8;
-        std::vector<std::vector<int32_t>> lists(X);
+        std::vector<int32_t> sched, sched_head, block_head, block_rest;
         if (plan.row_begin >= 0) {
             // a block of rows of the one problem: dealt round-robin (every XCD holds the records)
-            for (int64_t r = plan.row_begin; r < plan.row_end; ++r) lists[(size_t)((r - plan.row_begin) % X)].push_back((int32_t)r);
-        } else if (n_prob >= X) {
+            const int64_t rows = plan.row_end - plan.row_begin;
+            sched.assign((size_t)((rows + N_XCD - 1) / N_XCD * N_XCD), -1);
+            for (int64_t i = 0; i < rows; ++i) sched[(size_t)i] = (int32_t)(plan.row_begin + i);
+        } else {
             std::vector<int64_t> order((size_t)n_prob);
             for (int64_t p = 0; p < n_prob; ++p) order[(size_t)p] = p;
             std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
                 return h_seg_off[a + 1] - h_seg_off[a] > h_seg_off[b + 1] - h_seg_off[b];
             });
-            double load[X] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int64_t p : order) {
-                int x = 0;
-                for (int i = 1; i < X; ++i) if (load[i] < load[x]) x = i;
-                const double n = (double)(h_seg_off[p + 1] - h_seg_off[p]);
-                load[x] += n * n;
-                for (int64_t r = h_seg_off[p]; r < h_seg_off[p + 1]; ++r) lists[x].push_back((int32_t)r);
+            const std::vector<int64_t> head(order.begin(), order.begin() + B.head_k), rest(order.begin() + B.head_k, order.end());
+            deal_to_xcds(h_seg_off, rest, sched);
+            if (B.head_k > 0) {
+                deal_to_xcds(h_seg_off, head, sched_head, &block_head);
+                // (the rest's merge loops in the order of the problems, as the single launch has them)
+                std::vector<char> in_head((size_t)n_prob, 0);
+                for (int64_t p : head) in_head[(size_t)p] = 1;
+                for (int64_t p = 0; p < n_prob; ++p) if (!in_head[(size_t)p]) block_rest.push_back((int32_t)p);
+                B.n_max_head = h_seg_off[head[0] + 1] - h_seg_off[head[0]];
+                B.n_max_rest = rest.empty() ? 0 : h_seg_off[rest[0] + 1] - h_seg_off[rest[0]];
             }
-        } else {
-            for (int64_t r = 0; r < n_total; ++r) lists[(size_t)(r % X)].push_back((int32_t)r);
         }
-        size_t longest = 0;
-        for (auto& l : lists) longest = std::max(longest, l.size());
-        B.grid_rows = (int64_t)longest * X;
-        std::vector<int32_t> sched((size_t)B.grid_rows, -1);
-        for (int x = 0; x < X; ++x)
-            for (size_t i = 0; i < lists[x].size(); ++i) sched[i * X + x] = lists[x][i];
+        B.grid_rows = (int64_t)sched.size();
+        B.grid_head = (int64_t)sched_head.size();
         TRY(upload_parts(c, S_AHC_OFF, B.offs, [&](Layout L) {
             return L.part(B.seg_off, np + 1, h_seg_off).part(B.mat_off, np + 1, mat_off.data()).bytes();
         }));
         TRY(upload_parts(c, S_AHC_PROB, B.prob_of, [&](Layout L) {
-            return L.part(d_prob, prob.size(), prob.data()).part(d_sched, sched.size(), sched.data()).bytes();
+            return L.part(B.d_prob, prob.size(), prob.data()).part(B.d_sched, sched.size(), sched.data())
+                .part(B.d_sched_head, sched_head.size(), sched_head.data()).part(B.d_block_head, block_head.size(), block_head.data())
+                .part(B.d_block_rest, block_rest.size(), block_rest.data()).bytes();
         }));
     }
+    B.variant = variant; B.kind = kind; B.lambdac = lambdac;
     const size_t nt = (size_t)n_total;
     TRY(carve(c, scratch, S_AHC_LD, [&](Layout L) { return L.part(B.ld, nt).bytes(); }));
     TRY(carve(c, scratch, S_AHC_AUX, [&](Layout L) { return L.part(B.aux, nt * AUX).bytes(); }));
@@ -709,16 +859,15 @@ spkd_status ahc_prepare(spkd_ctx* c, const double* d_stats, const int64_t* h_seg
             Timer t(c, SPKD_T_CLUSTER_PREP);
             cluster_prep(c, B.ex, n_total, kind, B.ld, B.aux);
         }
-        auto kmat = kind == SPKD_GLR ? k_matrix<true> : k_matrix<false>;   // GLR has a second rank-one term
         if (plan.d_init) {
             HIPCHK(c, hipMemcpyAsync(B.mat, plan.d_init, (size_t)cells * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        } else if (B.head_k > 0) {
+            // the head's rows; the rest's are the caller's, behind the fork (SPKD_T_MATRIX spans both launches)
+            (void)hipEventRecord(c->ka[SPKD_T_MATRIX], c->stream);
+            matrix_launch(c, B, B.d_sched_head, B.grid_head);
         } else if (B.grid_rows > 0) {
             Timer t(c, SPKD_T_MATRIX);
-            hipLaunchKernelGGL(kmat, dim3((unsigned)B.grid_rows), dim3(MX_WAVES * WAVE), 0, c->stream,
-                               (const double*)B.ex, (const double*)B.pk, (const int64_t*)B.seg_off, (const int32_t*)d_prob,
-                               (const int32_t*)d_sched, variant, kind, lambdac,
-                               (const double*)B.ld, (const double*)B.aux, B.mat, (const int64_t*)B.mat_off,
-                               B.smax, B.smin, c->d_err);
+            matrix_launch(c, B, B.d_sched, B.grid_rows);
         }
     }
     HIPCHK(c, hipGetLastError());
@@ -951,6 +1100,17 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
     if (path == SPKD_AHC_WIDE && n_max > STEP_MAX_N)
         return fail(c, SPKD_EINVAL, "clustering problem larger than 16384 records (wide merge loop)");
     AhcPrep B;
+    // Head and rest.  One workgroup per problem leaves the CUs of the smaller problems idle until the largest
+    // is through; a problem's merge loop needs only its own matrix.  So the matrices of the few largest
+    // problems are computed first, their merge loops start at once on the side stream, and the other
+    // matrices are computed beside them (k_matrix is bound by fp64 issue, k_ahc waits for memory).  Only
+    // the order of the launches changes: every problem runs the same code on the same data.
+    c->last_ahc_head = 0;
+    // (the pseudo-inverse's waves share one workspace under lock words: that mode stays on one stream)
+    if (path == SPKD_AHC_MONO && !plan.d_init && plan.row_begin < 0 && P->kind != SPKD_KL2_PINV) {
+        B.head_k = c->ahc_head >= 0 ? std::min<int64_t>(c->ahc_head, n_prob) : spkd_ahc_head_rule(h_seg_off, n_prob);
+        c->last_ahc_head = B.head_k;
+    }
     std::vector<unsigned long long> kmax((size_t)n_prob), kmin((size_t)n_prob);
     std::vector<double> fmax((size_t)n_prob), fmin((size_t)n_prob);
     Call call(c);
@@ -972,12 +1132,33 @@ spkd_status ahc_impl(spkd_ctx* c, const double* d_stats, const int64_t* h_seg_of
         auto kahc = P->kind == SPKD_GLR ? k_ahc<true> : k_ahc<false>;
         if (lds > 48 * 1024)
             (void)hipFuncSetAttribute((const void*)kahc, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        Timer t(c, SPKD_T_AHC);
-        hipLaunchKernelGGL(kahc, dim3((unsigned)n_prob), dim3(AHC_TPB), lds, c->stream,
-                           B.ex, B.pk, (const int64_t*)B.seg_off, P->variant, P->kind, P->max_spk, P->lambdac,
-                           P->threshold, B.ld, B.aux, B.mat, (const int64_t*)B.mat_off, d_alive, d_tmp,
-                           d_rmin, d_rcache, d_n, d_a, d_b, d_merge_d, B.smax, B.smin, d_fmax, d_fmin, c->d_err,
-                           c->pinv_cur);
+        // one launch over `grid` problems (`blocks`: which; nullptr: all, in order), its LDS by the largest of them
+        auto merge_loops = [&](hipStream_t on, int64_t grid, const int32_t* blocks, int64_t largest) {
+            hipLaunchKernelGGL(kahc, dim3((unsigned)grid), dim3(AHC_TPB), (size_t)(largest + 4) * sizeof(int32_t), on,
+                               B.ex, B.pk, (const int64_t*)B.seg_off, P->variant, P->kind, P->max_spk, P->lambdac,
+                               P->threshold, B.ld, B.aux, B.mat, (const int64_t*)B.mat_off, d_alive, d_tmp,
+                               d_rmin, d_rcache, d_n, d_a, d_b, d_merge_d, B.smax, B.smin, d_fmax, d_fmin, c->d_err,
+                               c->pinv_cur, blocks);
+        };
+        if (B.head_k > 0) {
+            // The fork is behind the head's k_matrix, and so behind every upload, memset and preparation
+            // kernel of the call: all that the head reads is ordered.  SPKD_T_AHC runs from the head's start
+            // on the side stream to the join on the call's stream, which is behind both launches.
+            TRY(call.fork());
+            (void)hipEventRecord(c->ka[SPKD_T_AHC], c->side);
+            merge_loops(c->side, B.head_k, B.d_block_head, B.n_max_head);
+            matrix_launch(c, B, B.d_sched, B.grid_rows);
+            (void)hipEventRecord(c->kb[SPKD_T_MATRIX], c->stream);
+            c->kused[SPKD_T_MATRIX] = true;
+            if (n_prob > B.head_k) merge_loops(c->stream, n_prob - B.head_k, B.d_block_rest, B.n_max_rest);
+            HIPCHK(c, hipGetLastError());
+            TRY(call.join());
+            (void)hipEventRecord(c->kb[SPKD_T_AHC], c->stream);
+            c->kused[SPKD_T_AHC] = true;
+        } else {
+            Timer t(c, SPKD_T_AHC);
+            merge_loops(c->stream, n_prob, nullptr, n_max);
+        }
     } else {
         // the step chain: one launch per merge, every workgroup selects for itself (spkd_cluster.hpp)
         StepArrays Q;
@@ -1084,6 +1265,20 @@ spkd_status spkd_ahc_matrix(spkd_ctx* c, const double* d_stats, int64_t n, const
     plan.init_max = stat_max_in;
     plan.init_min = stat_min_in;
     return ahc_impl(c, d_stats, seg_off, 1, P, plan, h_n_merges, h_merge_a, h_merge_b, h_merge_d, h_stat_max, h_stat_min);
+}
+
+spkd_status spkd_last_ahc_head(spkd_ctx* c, int64_t* k) {
+    if (!c || !k) return SPKD_EINVAL;
+    *k = c->last_ahc_head;
+    return SPKD_OK;
+}
+
+int64_t spkd_ahc_head_rule(const int64_t* h_seg_off, int64_t n_prob) {
+    if (!h_seg_off || n_prob < 0) return -1;
+    std::vector<int64_t> sizes((size_t)n_prob);
+    for (int64_t p = 0; p < n_prob; ++p) sizes[(size_t)p] = h_seg_off[p + 1] - h_seg_off[p];
+    std::sort(sizes.begin(), sizes.end(), std::greater<int64_t>());
+    return ahc_head_rule(sizes, AHC_RULE_CUS);
 }
 
 // ------------------------------------------------------------------ (3) change detection
@@ -3413,6 +3608,18 @@ extern "C" int spkd_debug_ahc_prof(unsigned long long* out4) {
     unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (hipMemcpyFromSymbol(out4, HIP_SYMBOL(spkd::g_ahc_prof), sizeof z) != hipSuccess) return 1;
     if (hipMemcpyToSymbol(HIP_SYMBOL(spkd::g_ahc_prof), z, sizeof z) != hipSuccess) return 1;
+    return 0;
+}
+
+// the wall clock at which the k_ahc workgroup of each of the first n_prob problems entered and left
+// (out[2p], out[2p + 1]), and the clock's rate in kHz; zeroes the array
+extern "C" int spkd_debug_ahc_span(unsigned long long* out, int n_prob, int* khz) {
+    if (n_prob < 0 || n_prob > spkd::AHC_SPAN_PROBS) return 1;
+    std::vector<unsigned long long> z(2 * (size_t)spkd::AHC_SPAN_PROBS, 0ull);
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(spkd::g_ahc_span), 2 * (size_t)n_prob * sizeof(unsigned long long)) != hipSuccess) return 1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(spkd::g_ahc_span), z.data(), z.size() * sizeof(unsigned long long)) != hipSuccess) return 1;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess) return 1;
     return 0;
 }
 

@@ -50,7 +50,7 @@ DIM = 39
 
 EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_destroy', 'spkd_last_error', 'spkd_sync',
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
-           'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_set_stats', 'spkd_pair_terms',
+           'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_last_ahc_head', 'spkd_ahc_head_rule', 'spkd_set_stats', 'spkd_pair_terms',
            'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_sum_stats', 'spkd_mfcc', 'spkd_mfcc_batch', 'spkd_resample_batch',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
@@ -198,6 +198,9 @@ def load_library(path=None):
     lib.spkd_memcpy_d2d.argtypes = [vp, vp, vp, C.c_size_t]
     lib.spkd_last_kernel_ms.argtypes = [vp, C.c_int, P(C.c_float)]
     lib.spkd_last_gw_items.argtypes = [vp, P(C.c_int64)]
+    lib.spkd_last_ahc_head.argtypes = [vp, P(C.c_int64)]
+    lib.spkd_ahc_head_rule.argtypes = [vp, i64]
+    lib.spkd_ahc_head_rule.restype = i64
     lib.spkd_set_stats.argtypes = [vp, vp, i64, vp, vp, vp, i64, i64, vp]
     lib.spkd_pair_terms.argtypes = [vp, vp, vp, vp, i64, C.c_int, vp]
     lib.spkd_distance_matrix.argtypes = [vp, C.c_int, dbl, vp, i64, vp]
@@ -444,6 +447,12 @@ class Context(object):
         n = C.c_int64()
         self.check(self.lib.spkd_last_gw_items(self.h, C.byref(n)))
         return int(n.value)
+
+    def last_ahc_head(self):
+        """Problems whose merge loops the most recent clustering call started under the others' matrices."""
+        k = C.c_int64()
+        self.check(self.lib.spkd_last_ahc_head(self.h, C.byref(k)))
+        return int(k.value)
 
     # ---- device memory for torch-less hosts
     def dev_alloc(self, nbytes):

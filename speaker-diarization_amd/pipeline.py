@@ -260,6 +260,7 @@ def _clustering_done(ctx, timings, seg_off, r):
     if timings is not None:
         for k in ('cluster_prep', 'matrix', 'ahc'):
             timings.setdefault(k, []).append(ctx.last_ms(k))
+        timings['ahc_head'] = ctx.last_ahc_head()     # (above 0: 'matrix' and 'ahc' are spans that overlap)
     if r['status'] == hipabi.SPKD_ENONFINITE:
         raise ValueError('array must not contain infs or NaNs')
     if timings is not None:
