@@ -609,8 +609,8 @@ __global__ __launch_bounds__(MX_WAVES * WAVE, 2) void k_matrix(
     const double ldA = ld[g];
     const int wave = threadIdx.x >> 6;
     const QuadLane L = quad_lane();
-    double wmax = __builtin_nan(""), wmin = __builtin_nan("");
     if (kind == SPKD_KL2) {
+        double wmax = __builtin_nan(""), wmin = __builtin_nan("");
         for (int64_t rc = ra + 1 + wave; rc < N; rc += MX_WAVES) {
             const double d = kl2_from_aux(aux + g * AUX, aux + (off + rc) * AUX);
             if (lane_id() == 0) {
@@ -622,28 +622,46 @@ __global__ __launch_bounds__(MX_WAVES * WAVE, 2) void k_matrix(
                 wmin = (wmin != wmin || d < wmin) ? d : wmin;
             }
         }
-    } else {
-        for (int64_t base = ra + 1 + 4 * wave; base < N; base += 4 * MX_WAVES) {
-            int64_t rc = base + L.m;
-            const bool valid = rc < N;
-            rc = valid ? rc : N - 1;
-            const double* C = ex + (off + rc) * QREC;
-            const double* Cp = pk + (off + rc) * REC;
-            const double ldx = log(quad_pair_det<TWO>(kind, ldsA, nA, A, C, Cp, false, L, err));
-            const double d = finish_distance(kind, lambdac, nA, ldA, Cp[REC - 1], ld[off + rc], ldx);
-            if (valid && L.t == 0) {
-                Dm[ra * N + rc] = d;
-                if (variant == 1) Dm[rc * N + ra] = d;
-            }
-            if (valid && stat_valid(d)) {
+        if (variant == 1 && lane_id() == 0) {
+            if (wmax == wmax) atomicMax(stat_max + p, dkey(wmax));
+            if (wmin == wmin) atomicMin(stat_min + p, dkey(wmin));
+        }
+        return;
+    }
+    // The passes keep the bare determinants, as k_gw's and k_ahc's do: a wave holds four, so a log
+    // taken here is a full fp64 sequence per four values.  A pass parks its determinant in the cell
+    // the distance will take, Dm[ra][rc] (k_ahc parks its in tmp), and the distances are finished
+    // below, a thread per partner.
+    double* row = Dm + ra * N;
+    for (int64_t base = ra + 1 + 4 * wave; base < N; base += 4 * MX_WAVES) {
+        int64_t rc = base + L.m;
+        const bool valid = rc < N;
+        rc = valid ? rc : N - 1;
+        const double det = quad_pair_det<TWO>(kind, ldsA, nA, A, ex + (off + rc) * QREC, pk + (off + rc) * REC, false, L, err);
+        if (valid && L.t == 0) row[rc] = det;
+    }
+    __syncthreads();
+    double wmax = __builtin_nan(""), wmin = __builtin_nan("");
+    for (int64_t c = ra + 1 + threadIdx.x; c < N; c += MX_WAVES * WAVE) {
+        const double det = row[c];
+        const double nC = pk[(off + c) * REC + REC - 1];
+        const double d = finish_distance(kind, lambdac, nA, ldA, nC, ld[off + c], log(det));
+        row[c] = d;
+        if (variant == 1) {
+            Dm[c * N + ra] = d;
+            if (stat_valid(d)) {
                 wmax = (wmax != wmax || d > wmax) ? d : wmax;
                 wmin = (wmin != wmin || d < wmin) ? d : wmin;
             }
         }
     }
-    if (variant == 1 && (kind == SPKD_KL2 ? lane_id() == 0 : L.t == 0)) {
-        if (wmax == wmax) atomicMax(stat_max + p, dkey(wmax));
-        if (wmin == wmin) atomicMin(stat_min + p, dkey(wmin));
+    if (variant == 1) {                       // (a wave's fold in integers, as k_ahc's step 4)
+        const unsigned long long kmax = wave_red_u64<true>(wmax == wmax ? dkey(wmax) : 0ull);
+        const unsigned long long kmin = wave_red_u64<false>(wmin == wmin ? dkey(wmin) : ~0ull);
+        if (lane_id() == 0) {
+            if (kmax != 0ull) atomicMax(stat_max + p, kmax);
+            if (kmin != ~0ull) atomicMin(stat_min + p, kmin);
+        }
     }
 }
 

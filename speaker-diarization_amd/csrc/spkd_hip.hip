@@ -737,10 +737,12 @@ void matrix_launch(spkd_ctx* c, const AhcPrep& B, const int32_t* d_sched, int64_
 // idle.  Measured (profiles/ahc_head.json): K = 8 leaves 24 of the rest's workgroups waiting up to 18 ms
 // and the step 10 ms SLOWER than K = 0, K = 16 sixteen (+ 7 ms), K = 24 eight; with K = 32 every engine
 // holds one head problem, seven of the rest's fit beside it, none waits, and the step is 6.7 ms faster.
-// The two constants are the benchmark batch's, measured: the same file.
+// The two constants are the benchmark batch's, measured with single launches (tools/ahc_tail_profile.py,
+// SPKD_AHC_HEAD=0), both in one session: profiles/matrix_dense_finish.json (k_matrix with its dense
+// finish; before it 6.00e-7 and 2.095e-4, profiles/ahc_head.json).
 constexpr int AHC_HEAD_ROUND = 32;             // XCDs x shader engines per XCD
-constexpr double AHC_MS_PER_N2 = 2.095e-4;
-constexpr double MATRIX_MS_PER_N2 = 6.00e-7;
+constexpr double AHC_MS_PER_N2 = 2.122e-4;
+constexpr double MATRIX_MS_PER_N2 = 5.58e-7;
 constexpr int AHC_HEAD_MAX = 32;
 constexpr int AHC_RULE_CUS = 256;              // of the MI355X
 int64_t ahc_head_rule(const std::vector<int64_t>& n, int cus) {

@@ -2,7 +2,11 @@
 // distances of one row record (LDS) with a window of partner quad records (global):
 //   mode 0  the bare symmetric elimination (formation + tri_det_nopivot + log), as in
 //           blocked_bench.hip
-//   mode 1  the library's quad_pair_logdet<false> + finish_distance + the stores k_matrix does
+//   mode 1  the library's quad_pair_det<false> + log + finish_distance + a store, in every pass
+//           (k_matrix's pass until the dense finish)
+//   mode 2  the bare elimination from packed records;  mode 3  the same, register-pipelined
+//   mode 4  k_matrix's body: quad_pair_det<false> per pass, the determinant parked in the output
+//           cell; then a barrier and log + finish_distance by one thread per partner
 // each with the partner records L2-resident (n_rec = 387) and streaming from HBM
 // (n_rec = 40 000, every block a different window of 387 partners).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../speaker-diarization_amd/csrc -o pair_bench pair_bench.hip
@@ -73,6 +77,23 @@ __global__ __launch_bounds__(512) void k_pairs(const double* __restrict__ qr, in
             cnt = cnt_n;
         }
         if (L.t == 0) out[(size_t)blockIdx.x * WINDOW + wave * 4 + L.m] = acc;
+        return;
+    }
+    if (MODE == 4) {
+        double* row = out + (size_t)blockIdx.x * WINDOW;
+        for (int base = 4 * wave; base < WINDOW; base += 32) {
+            int w = base + L.m;
+            const bool valid = w < WINDOW;
+            w = valid ? w : WINDOW - 1;
+            const int rc = (a + 1 + w) % n_rec;
+            const double det = quad_pair_det<false>(SPKD_BIC, ldsA, nA, A, qr + (size_t)rc * QREC, pk + (size_t)rc * REC, false, L, err);
+            if (valid && L.t == 0) row[w] = det;
+        }
+        __syncthreads();
+        for (int w = threadIdx.x; w < WINDOW; w += blockDim.x) {
+            const int rc = (a + 1 + w) % n_rec;
+            row[w] = finish_distance(SPKD_BIC, 1.3, nA, ldA, pk[(size_t)rc * REC + REC - 1], ld[rc], log(row[w]));
+        }
         return;
     }
     for (int base = 4 * wave; base < WINDOW; base += 32) {
@@ -192,17 +213,18 @@ int main(int argc, char** argv) {
         hipMemcpy(dL, hld.data(), n_rec * 8, hipMemcpyHostToDevice);
         hipMemset(dErr, 0, 4);
         hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-        for (int mode = 0; mode < 4; ++mode)
+        for (int mode = 0; mode < 5; ++mode)
             for (int it = 0; it < 3; ++it) {
                 hipEventRecord(e0);
                 if (mode == 0) hipLaunchKernelGGL(k_pairs<0>, dim3(blocks), dim3(512), 0, 0, dE, n_rec, dL, dO, dErr, (const double*)nullptr);
                 else if (mode == 1) hipLaunchKernelGGL(k_pairs<1>, dim3(blocks), dim3(512), 0, 0, dE, n_rec, dL, dO, dErr, (const double*)dP);
                 else if (mode == 2) hipLaunchKernelGGL(k_pairs<2>, dim3(blocks), dim3(512), 0, 0, dE, n_rec, dL, dO, dErr, (const double*)dP);
-                else hipLaunchKernelGGL(k_pairs<3>, dim3(blocks), dim3(512), 0, 0, dE, n_rec, dL, dO, dErr, (const double*)dP);
+                else if (mode == 3) hipLaunchKernelGGL(k_pairs<3>, dim3(blocks), dim3(512), 0, 0, dE, n_rec, dL, dO, dErr, (const double*)dP);
+                else hipLaunchKernelGGL(k_pairs<4>, dim3(blocks), dim3(512), 0, 0, dE, n_rec, dL, dO, dErr, (const double*)dP);
                 hipEventRecord(e1); hipEventSynchronize(e1);
                 float ms; hipEventElapsedTime(&ms, e0, e1);
-                if (it == 2) printf("n_rec %6d  %-34s %.3f ms  %.1f M pairs/s\n", n_rec,
-                                    mode == 0 ? "bare elimination" : (mode == 1 ? "quad_pair_det + log + finish_distance" : (mode == 2 ? "bare elimination, packed records" : "bare, packed, register-pipelined")), ms,
+                if (it == 2) printf("n_rec %6d  %-37s %.3f ms  %.1f M pairs/s\n", n_rec,
+                                    mode == 0 ? "bare elimination" : (mode == 1 ? "quad_pair_det + log + finish_distance" : (mode == 2 ? "bare elimination, packed records" : (mode == 3 ? "bare, packed, register-pipelined" : "quad_pair_det parked + dense finish"))), ms,
                                     (double)blocks * WINDOW / ms / 1e3);
             }
         hipFree(dP); hipFree(dE); hipFree(dO); hipFree(dL); hipFree(dErr);
