@@ -1,4 +1,4 @@
-"""A gallery of enrolled speakers: the records of linking by cross-likelihood ratio (pipeline.LINK_CLR,
+"""A gallery of enrolled speakers: the records of linking by cross-likelihood ratio (clr_model.LINK_CLR,
 spkd_ubm_stats) kept on the device from one batch to the next, so that a global speaker label means
 the same person in every batch and known voices can be enrolled by name.
 
@@ -10,10 +10,14 @@ tests/gallery_numpy.py restates the flow in numpy.
 
 The default threshold is LINK_CLR's.  Like it, it rests on ONE synthetic fixture (tests/test_gallery.py),
 not on speech: tune it on real audio.
+
+Layers: this module stands on clr_model (the CLR settings, their parser, the training of the background
+model) and hipabi; linking and pipeline stand on it.
 """
 import numpy as np
 
 from . import hipabi
+from .clr_model import LINK_CLR, _link_model, train_ubm
 
 FORMAT_VERSION = 1
 _KEYS = ('version', 'components', 'relevance', 'threshold', 'ubm', 'records', 'ok', 'frames', 'names')
@@ -31,12 +35,11 @@ class Gallery(object):
     (to_arrays / from_arrays / save / load work, nothing that needs the device does)."""
 
     def __init__(self, ctx, link=None):
-        from . import pipeline
-        link = pipeline.LINK_CLR if link is None else link
-        model = pipeline._link_model(link)
-        if model[0] != 'clr':
+        model = _link_model(LINK_CLR if link is None else link)
+        if model.name != 'clr':
             raise ValueError('a gallery holds the records of link model clr')
-        _, self.components, self.iterations, self.var_floor, self.relevance, self.threshold, _, self.ubm_max_frames = model
+        self.components, self.iterations, self.var_floor = model.components, model.iterations, model.var_floor
+        self.relevance, self.threshold, self.ubm_max_frames = model.relevance, model.threshold, model.ubm_max_frames
         self.ctx = ctx
         self.ubm, self.d_ubm = None, None
         self.d_bw, self._cap, self._host = None, 0, None
@@ -69,11 +72,10 @@ class Gallery(object):
 
     def train_ubm(self, d_frames, total_frames, set_off, begin, end, iterations=None, var_floor=None,
                   ubm_max_frames=None):
-        """Trains the model as link_batch does under LINK_CLR: spkd_gmm_train's model of ONE speaker
-        that owns the ranges begin / end of all speakers (set_off: the speakers' offsets among them),
-        cut by pipeline.ubm_ranges.  Only while the gallery holds no identity.  Returns False, and
+        """Trains the model by the call link_batch makes under LINK_CLR (clr_model.train_ubm) on the
+        ranges begin / end of all speakers (set_off: the speakers' offsets among them); a setting that
+        is None is the gallery's own.  Only while the gallery holds no identity.  Returns False, and
         leaves the gallery without a model, when none can be trained."""
-        from . import pipeline
         self._no_identity('train_ubm')
         it = self.iterations if iterations is None else iterations
         fl = self.var_floor if var_floor is None else var_floor
@@ -81,9 +83,7 @@ class Gallery(object):
         if self.d_ubm is None:
             self.d_ubm = self.ctx.dev_alloc(self.components * hipabi.GMM_COMP * 8)
         self.ubm = None
-        ok, _ = self.ctx.gmm_train(d_frames, total_frames, [0, len(begin)], begin,
-                                   pipeline.ubm_ranges(set_off, begin, end, cap), self.components, it, fl, self.d_ubm)
-        if not ok[0]:
+        if not train_ubm(self.ctx, d_frames, total_frames, self.d_ubm, self.components, set_off, begin, end, it, fl, cap):
             return False
         self.ubm = np.empty((self.components, hipabi.GMM_COMP))
         self.ctx.d2h(self.ubm, self.d_ubm)
@@ -182,7 +182,6 @@ class Gallery(object):
     def from_arrays(cls, ctx, arrays):
         """A gallery from what to_arrays gave.  Another format version, a key that is missing, shapes
         that disagree: ValueError."""
-        from . import pipeline
         missing = [k for k in _KEYS if k not in arrays]
         if missing:
             raise ValueError('gallery: no %s' % ', '.join(missing))
@@ -191,7 +190,7 @@ class Gallery(object):
             raise ValueError('gallery: format version %s, not %d' % (a['version'], FORMAT_VERSION))
         if any(a[k].shape != () for k in ('components', 'relevance', 'threshold')):
             raise ValueError('gallery: components, relevance and threshold are scalars')
-        g = cls(ctx, dict(pipeline.LINK_CLR, components=int(a['components']), relevance=float(a['relevance']),
+        g = cls(ctx, dict(LINK_CLR, components=int(a['components']), relevance=float(a['relevance']),
                           threshold=float(a['threshold'])))
         k, n = g.components, len(a['ok'])
         if a['records'].shape != (n, k, hipabi.BW_COMP) or a['ok'].shape != (n,) or a['frames'].shape != (n,) or \

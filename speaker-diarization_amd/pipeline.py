@@ -15,13 +15,17 @@ import time
 
 import numpy as np
 
-from . import gallery as _gallery
-from . import hipabi
+from . import exp_generator, frontend, hipabi, voice_detection
+from . import linking as _linking
 from . import resegmentation as _resegmentation
 from .recipe import py2_float_str
+# the linking stage (linking.py, on clr_model.py and gallery.py): its settings and its entry point under their names here
+from .linking import LINK_CL, LINK_CLR, _link_model, link_batch, ubm_ranges
 # the resegmentation stage (resegmentation.py): its settings and its entry point under their names here
 from .resegmentation import (FB_MAX_SCALED_PENALTY, RESEG, RESEG_CONF, RESEG_GMM, RESEG_MAX_SPEAKERS, RESEG_MD,
                              RESEG_SOFT, RESEG_SOFT_SCALE, resegment_batch)
+# the tables every stage reads (tables.py), under their names here
+from .tables import BatchFile, _ahc_params, _segment_ranges, _turn_table, link_speakers
 
 DIA2_CD = dict(kind='BIC', lambdac=1.0, threshold=0.0, winsize_s=1.0, winstep_s=3.0, deltaws_s=0.1)
 DIA2_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
@@ -29,27 +33,6 @@ DIA2_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
 SW_CD = dict(method='sw', kind='GLR', lambdac=1.3, threshold=0.0, winsize_s=5.0, winstep_s=0.5, deltaws_s=0.05)
 # the same script in merge mode, -m m: its second pass, over a detector's output (the window flags are unused there)
 MERGE_CD = dict(method='m', kind='GLR', lambdac=1.3, threshold=0.0, winsize_s=5.0, winstep_s=0.5, deltaws_s=0.05)
-# linking the speakers of a batch's files (link_batch): the clustering script's own defaults
-LINK_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
-# linking by cross-likelihood ratio instead (link_batch, model 'clr'): a universal background model of
-# `components` diagonal Gaussians trained on the speakers' own frames (spkd_gmm_train: `iterations` EM
-# steps, `var_floor`; at most `ubm_max_frames` frames go in), every speaker's statistics under it
-# (spkd_ubm_stats), means MAP-adapted with `relevance`, and the agglomerative chain of spkd_clr_link:
-# merged while the ratio is above `threshold` (higher is more alike; max_spk as in LINK_CL).  The
-# threshold rests on ONE synthetic fixture (tests/test_link_clr.py), not on speech: tune it on real audio.
-LINK_CLR = dict(model='clr', components=8, iterations=5, var_floor=0.01, relevance=16.0,
-                threshold=-0.5, max_spk=0, ubm_max_frames=2_000_000)
-
-
-class BatchFile(object):
-    """One file of a batch: frame window in the resident array + its VAD turns
-    (start / end seconds as the VAD recipe states them)."""
-
-    def __init__(self, frame_off, n_frames, vad):
-        self.frame_off = int(frame_off)
-        self.n_frames = int(n_frames)
-        self.vad = [(float(s), float(e)) for (s, e) in vad]
-        self.vad_arr = np.array(self.vad, dtype=np.float64).reshape(-1, 2)     # (converted once, not per call)
 
 
 class FusedStats(object):
@@ -70,7 +53,6 @@ def vad_batch(ctx, model, pcms, opt=None, text_contract=True, timings=None, uplo
     the times are the ones the change detector reads back from the recipe the file path writes
     (py2_str, 12 significant digits: spkd_py2_roundtrip).  uploaded: the samples already on the
     device (frontend.upload_batch), as decode_batch takes them."""
-    from . import exp_generator, voice_detection
     opt = opt or voice_detection.VadOptions()
     _t0 = time.perf_counter()
     tokens, last_frames = exp_generator.decode_batch(ctx, model, pcms, timings, uploaded)
@@ -93,7 +75,6 @@ def features_batch(ctx, cfg, pcms=None, uploaded=None, timings=None):
     pair of a frontend.upload_batch): (d_frames, total_frames, frame_off), file f at the frames
     [frame_off[f], frame_off[f+1]).  The buffer is the context's and lives until its next batch of
     this window width."""
-    from . import frontend
     if uploaded is None:
         uploaded = frontend.upload_batch(ctx, pcms, timings)
     d_frames, frame_off = frontend.extract_batch(ctx, cfg, uploaded[0], uploaded[1], timings=timings)
@@ -116,7 +97,6 @@ def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=Non
     turns and the frames as they lie on the device.  uploaded: the samples already on the device
     (frontend.upload_batch or frontend.resample_batch; pcms is not read then).  kw: diarize_batch's
     text_contract, fused, handoff, link, reseg, detail.  Returns its rows."""
-    from . import frontend
     _one_clock(model, cfg)
     if uploaded is None:
         uploaded = frontend.upload_batch(ctx, pcms, timings)
@@ -131,40 +111,16 @@ def diarize_audio_batch(ctx, model, cfg, audios, cd=DIA2_CD, cl=DIA2_CL, timings
     rate (frontend.read_audio), resampled and downmixed to cfg.sample_rate on the device
     (frontend.resample_batch; group_bytes: its bound on the raw audio held there), then exactly
     diarize_pcm_batch from its upload on.  Returns its rows."""
-    from . import frontend
     _one_clock(model, cfg)
     group = {} if group_bytes is None else {'group_bytes': group_bytes}
     uploaded = frontend.resample_batch(ctx, audios, cfg.sample_rate, timings=timings, **group)
     return diarize_pcm_batch(ctx, model, cfg, None, cd=cd, cl=cl, timings=timings, uploaded=uploaded, **kw)
 
 
-def _turn_table(files, rate):
-    """Per VAD turn of the batch, in file order: owning file, that file's offset and length in
-    the resident array, start / end seconds (views), absolute frame range -- int() truncation
-    and the clamp of a slice (no lower clamp: spk-change-detection.py cuts feas[start:end]).
-    None when no file has a turn."""
-    nturn = [len(f.vad) for f in files]
-    if sum(nturn) == 0:
-        return None
-    vad = np.concatenate([f.vad_arr for f in files])
-    owner = np.repeat(np.arange(len(files)), nturn)
-    foff = np.array([f.frame_off for f in files], dtype=np.int64)[owner]
-    fn = np.array([f.n_frames for f in files], dtype=np.int64)[owner]
-    ls, le = vad[:, 0], vad[:, 1]
-    f0 = np.minimum((ls * rate).astype(np.int64), fn)
-    f1 = np.maximum(f0, np.minimum((le * rate).astype(np.int64), fn))
-    return owner, foff, fn, ls, le, foff + f0, foff + f1
-
-
 def _cd_params(cd, rate):
     return hipabi.CdParams(hipabi.KINDS[cd['kind']], 0, cd['lambdac'], cd['threshold'],
                            float(np.floor(cd['winsize_s'] * rate)), float(np.floor(cd['winstep_s'] * rate)),
                            float(np.floor(rate * cd['deltaws_s'])), rate)
-
-
-def _ahc_params(cl):
-    return hipabi.AhcParams(cl['variant'], hipabi.KINDS[cl['kind']], cl['max_spk'], cl.get('path', 0),
-                            cl['lambdac'], cl['threshold'])
 
 
 def _method(cl):
@@ -421,23 +377,6 @@ def _lines_per_file(lines, owner, n_files, timings, _t0, _t1, _t2):
     return out
 
 
-def _segment_ranges(files, segments, rate):
-    """The absolute frame range of every segment of a batch, in segment order (get_spk_features,
-    spk-clustering.py:46-52: int() truncation, the clamps of a slice) -> (seg_off per file, n,
-    begin, end)."""
-    cnt = [len(s) for s in segments]
-    seg_off = np.zeros(len(files) + 1, dtype=np.int64)
-    seg_off[1:] = np.cumsum(cnt)
-    n = int(seg_off[-1])
-    allseg = np.concatenate([np.asarray(s, dtype=np.float64).reshape(-1, 2) for s in segments]) if n else np.zeros((0, 2))
-    owner = np.repeat(np.arange(len(files)), cnt)
-    foff = np.array([f.frame_off for f in files], dtype=np.int64)[owner]
-    fn = np.array([f.n_frames for f in files], dtype=np.int64)[owner]
-    a0 = np.clip((allseg[:, 0] * rate).astype(np.int64), 0, fn)
-    a1 = np.maximum(a0, np.clip((allseg[:, 1] * rate).astype(np.int64), 0, fn))
-    return seg_off, n, foff + a0, foff + a1
-
-
 def segment_stats(ctx, d_frames, total_frames, files, segments, rate=125.0, timings=None, fused=None,
                   scratch_name='segment_stats'):
     """The statistics record of every segment (get_spk_features + the np.cov inputs,
@@ -525,285 +464,6 @@ def cluster_batch(ctx, d_frames, total_frames, files, segments, rate=125.0, cl=D
         timings.setdefault('wall_cl_ahc_call', []).append(1e3 * (_t3 - _t2))
         timings.setdefault('wall_cl_finish', []).append(1e3 * (_t4 - _t3))
     return out
-
-
-def link_speakers(seg_off, labels):
-    """The initial speakers of a batch's linking problem: the clusters of its files, file by file
-    and within a file by ascending label -- the list the reference would hold had every file's
-    final `speakers` been concatenated.  A label no segment carries is no speaker.  labels: per
-    file the 1-based label of each of its segments (seg_off: the files' offsets among all
-    segments).  Returns (member, set_off, spk_file, spk_label): speaker s owns the segments
-    member[set_off[s]:set_off[s + 1]], in segment order, and is label spk_label[s] of file
-    spk_file[s]."""
-    seg_off = np.asarray(seg_off, dtype=np.int64)
-    if len(labels) != len(seg_off) - 1:
-        raise ValueError('one label array per file')
-    labs = [np.asarray(l, dtype=np.int64).reshape(-1) for l in labels]
-    if [len(l) for l in labs] != np.diff(seg_off).tolist():
-        raise ValueError('one label per segment')
-    lab = np.concatenate(labs) if labs else np.zeros(0, dtype=np.int64)
-    if len(lab) == 0:
-        z = np.zeros(0, dtype=np.int64)
-        return z, np.zeros(1, dtype=np.int64), z, z
-    if int(lab.min()) < 1:
-        raise ValueError('labels are 1-based')
-    owner = np.repeat(np.arange(len(labs), dtype=np.int64), [len(l) for l in labs])
-    width = int(lab.max()) + 1
-    keys, spk = np.unique(owner * width + lab, return_inverse=True)
-    member = np.argsort(spk, kind='stable').astype(np.int64)
-    set_off = np.zeros(len(keys) + 1, dtype=np.int64)
-    set_off[1:] = np.cumsum(np.bincount(spk, minlength=len(keys)))
-    return member, set_off, keys // width, keys % width
-
-
-def _link_model(link):
-    """The model of a `link` dictionary: ('bic',) when the key is absent -- the clustering keys of
-    LINK_CL -- or ('clr', components, iterations, var_floor, relevance, threshold, max_spk,
-    ubm_max_frames), the keys LINK_CLR names (its values where one is absent)."""
-    if 'model' not in link:
-        return ('bic',)
-    if link['model'] != 'clr':
-        raise ValueError('link model: clr (or no model: the clustering keys of LINK_CL)')
-    get = lambda k: link.get(k, LINK_CLR[k])
-    k, it, cap, ms = get('components'), get('iterations'), get('ubm_max_frames'), get('max_spk')
-    fl, r, th = float(get('var_floor')), float(get('relevance')), float(get('threshold'))
-    if int(k) != k or not 1 <= k <= hipabi.GMM_MAX_COMP:
-        raise ValueError('link components: 1 .. %d' % hipabi.GMM_MAX_COMP)
-    if int(it) != it or it < 0:
-        raise ValueError('link iterations: an integer >= 0')
-    if not np.isfinite(fl) or fl < 0.0:
-        raise ValueError('link var_floor: a finite number >= 0 (a share of the variance of all the frames)')
-    if not np.isfinite(r) or r <= 0.0:
-        raise ValueError('link relevance: a finite number > 0')
-    if not np.isfinite(th):
-        raise ValueError('link threshold: a finite number (a ratio above it merges)')
-    if int(ms) != ms or ms < 0:
-        raise ValueError('link max_spk: an integer >= 0')
-    if int(cap) != cap or cap < (hipabi.DIM + 1) * k:
-        raise ValueError('link ubm_max_frames: an integer >= 40 per component')
-    return ('clr', int(k), int(it), fl, r, th, int(ms), int(cap))
-
-
-def ubm_ranges(set_off, begin, end, cap):
-    """What the speakers give to the training of the background model: the ends of their ranges, cut.
-    Speaker s owns the ranges set_off[s] .. set_off[s + 1] of begin / end, its frames numbered in that
-    order.  While the speakers hold at most `cap` frames every range stays whole; beyond that speaker s
-    gives its first floor(cap N_s / N_total) frames -- a range past them is left empty."""
-    set_off, begin, end = (np.asarray(a, dtype=np.int64) for a in (set_off, begin, end))
-    length = end - begin
-    owner = np.repeat(np.arange(len(set_off) - 1), np.diff(set_off))
-    n = np.zeros(len(set_off) - 1, dtype=np.int64)
-    np.add.at(n, owner, length)
-    total = int(n.sum())
-    if total <= cap:
-        return end.copy()
-    share = np.array([int(cap) * int(k) // total for k in n], dtype=np.int64)
-    before = np.concatenate([[0], np.cumsum(length)])[:-1]              # frames in the ranges before this one
-    ord0 = before - before[set_off[:-1]][owner]                         # the ordinal of the range's first frame
-    return begin + np.clip(share[owner] - ord0, 0, length)
-
-
-def _link_clr(ctx, model, set_off, rng_b, rng_e, d_frames, total_frames, timings, gallery=None, kept=None):
-    """The calls of link_batch under model 'clr' -> (n_merges, a, b, d, stat_max, stat_min), or None
-    when no background model could be trained.  gallery: its model is the background model -- trained
-    here, as without a gallery, when it has none yet.  kept: a dict that receives the speakers' records
-    (d_bw) and their flags (ok)."""
-    _, n_comp, n_iter, var_floor, relevance, threshold, max_spk, cap = model
-    n_spk = len(set_off) - 1
-    if n_spk > hipabi.CLR_MAX_N:
-        raise ValueError('clr_link: at most %d speakers' % hipabi.CLR_MAX_N)
-    if gallery is None:
-        d_ubm = ctx.dev_scratch('link_ubm', n_comp * hipabi.GMM_COMP * 8)
-        ok, _ = ctx.gmm_train(d_frames, total_frames, [0, len(rng_b)], rng_b, ubm_ranges(set_off, rng_b, rng_e, cap),
-                              n_comp, n_iter, var_floor, d_ubm)
-        if timings is not None:
-            timings.setdefault('link_ubm_train', []).append(ctx.last_ms('gmm_train'))
-        if not ok[0]:
-            return None
-    else:
-        if gallery.ubm is None:
-            trained = gallery.train_ubm(d_frames, total_frames, set_off, rng_b, rng_e, n_iter, var_floor, cap)
-            if timings is not None:
-                timings.setdefault('link_ubm_train', []).append(ctx.last_ms('gmm_train'))
-            if not trained:
-                return None
-        d_ubm = gallery.d_ubm
-    d_bw = ctx.dev_scratch('link_speaker_bw', n_spk * n_comp * hipabi.BW_COMP * 8)
-    spk_ok = ctx.ubm_stats(d_frames, total_frames, d_ubm, n_comp, set_off, rng_b, rng_e, d_bw)
-    if timings is not None:
-        timings.setdefault('link_ubm_stats', []).append(ctx.last_ms('ubm_stats'))
-    if kept is not None:
-        kept.update(d_bw=d_bw, ok=spk_ok)
-    r = ctx.clr_link(d_bw, spk_ok, d_ubm, n_comp, relevance, threshold, max_spk)
-    if timings is not None:
-        timings.setdefault('link_clr', []).append(ctx.last_ms('clr_link'))
-    if r['status'] == hipabi.SPKD_ENONFINITE:
-        raise ValueError('array must not contain infs or NaNs')
-    return r['n_merges'], r['a'], r['b'], r['d'], r['stat_max'], r['stat_min']
-
-
-def _link_gallery(link, model):
-    """The gallery keys of a `link` dictionary of model 'clr': (gallery or None, enrol, exclusive)."""
-    gal = link.get('gallery')
-    if model[0] != 'clr':
-        if gal is not None:
-            raise ValueError('link gallery: a gallery holds the records of link model clr')
-        return None, False, False
-    if gal is None:
-        return None, False, False
-    if not isinstance(gal, _gallery.Gallery):
-        raise ValueError('link gallery: a gallery.Gallery')
-    if gal.components != model[1]:
-        raise ValueError('link components: the gallery has %d' % gal.components)
-    if gal.relevance != model[4]:
-        raise ValueError('link relevance: the gallery has %r' % gal.relevance)
-    return gal, bool(link.get('enrol', True)), bool(link.get('exclusive', True))
-
-
-def _identify_clusters(ctx, gallery, enrol, exclusive, kept, glob, timings, detail):
-    """The gallery step of link_batch: the batch clusters of the chain (glob: the 1-based cluster of each
-    speaker) get their records, are identified against the gallery as ONE group and are labelled by
-    identity -> the global label of each speaker."""
-    n_spk, n_cl = len(glob), int(glob.max())
-    member = np.argsort(glob, kind='stable')                             # a cluster's speakers in ascending order
-    set_off = np.concatenate([[0], np.cumsum(np.bincount(glob - 1, minlength=n_cl))])
-    cl_ok = np.minimum.reduceat(np.asarray(kept['ok'], dtype=np.int32)[member], set_off[:-1]).astype(np.int32)
-    d_cl = ctx.dev_scratch('link_cluster_bw', n_cl * gallery.record_doubles * 8)
-    ctx.bw_accumulate(kept['d_bw'], n_spk, gallery.components, set_off, member, np.arange(n_cl), np.zeros(n_cl), d_cl, n_cl)
-    if timings is not None:
-        timings.setdefault('link_cluster_sum', []).append(ctx.last_ms('bw_accumulate'))
-    r = gallery.identify(d_cl, cl_ok, [0, n_cl], exclusive)
-    if timings is not None:
-        timings.setdefault('link_ident', []).append(
-            ctx.last_ms('ident_scores') + ctx.last_ms('ident_assign') if gallery.n else 0.0)
-    n_before = gallery.n
-    ident = r['ident'].astype(np.int64)
-    unknown = np.nonzero((cl_ok != 0) & (ident < 0))[0]
-    label = ident + 1
-    label[unknown] = n_before + 1 + np.arange(len(unknown))
-    bad = np.nonzero(cl_ok == 0)[0]                                      # (no record: a label that stands for nobody)
-    label[bad] = n_before + len(unknown) + 1 + np.arange(len(bad))
-    enrolled = []
-    if enrol:
-        after = gallery.update(d_cl, cl_ok, ident)
-        if timings is not None:
-            timings.setdefault('link_update', []).append(ctx.last_ms('bw_accumulate') if (cl_ok != 0).any() else 0.0)
-        enrolled = after[unknown].tolist()
-        ident = after.astype(np.int64)
-    elif timings is not None:
-        timings.setdefault('link_update', []).append(0.0)
-    if detail is not None:
-        detail.update(identity=ident.astype(np.int32), score=r['score'], second=r['second'], enrolled=enrolled)
-    return label[glob - 1].astype(np.int32)
-
-
-def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None, d_frames=None, total_frames=None,
-               files=None, segments=None, rate=125.0, detail=None):
-    """Which speaker of one file is which speaker of another: spk_cluster_hi over the speakers of
-    all files of a batch (spk-clustering.py:178-240 takes `speakers` of any length per entry; the
-    command line never gets there, :289).  d_stats, seg_off: the segment records and the files'
-    offsets as segment_stats leaves them (cluster_batch's stats_out); labels: per file the labels
-    cluster_batch returned.  The speakers (link_speakers) get their records as the sums of their
-    segments' records, in segment order (spkd_sum_stats: no frame is read again), and are one
-    clustering problem of `link` (the keys of DIA2_CL).
-    Returns (maps, merges, stat_max, stat_min): maps[f][l] is the global 1-based speaker of label
-    l of file f (0 for a label no segment carries; length 0 for a file without segments), merges
-    the log [(a, b, d)] over the speaker list, stat_max / stat_min as spkd_ahc states them.
-    More than 16 384 speakers: ValueError.  timings: link_sum (the sum kernel, ms), link_ahc (the
-    clustering call, ms), link_speakers, link_merges.
-    link['model'] = 'clr' (LINK_CLR): the speakers are compared by cross-likelihood ratio under a
-    universal background model instead -- one Gaussian is the wrong model of a whole speaker, whose
-    frames fall into several modes in shares that differ from file to file.  This mode trains and
-    scores on frames: it takes d_frames, total_frames, files, segments (the arrays cluster_batch took;
-    the ranges are the ones segment_stats summed) and rate; d_stats is not read.  A speaker's frames
-    are those of its segments in member order.  The background model is spkd_gmm_train's model of ONE
-    speaker that owns the ranges of all speakers in speaker order (cut by ubm_ranges beyond
-    link['ubm_max_frames'] frames); spkd_ubm_stats gives every speaker's record under it from all its
-    frames, spkd_clr_link walks the chain.  Same return; stat_max / stat_min are the extremes of the
-    initial ratios.  When no background model can be trained (too few frames, constant or non-finite
-    frames) every speaker keeps a global label of its own and merges = [].  More than 4 096 speakers,
-    a key out of range, a missing array: ValueError.  timings: link_ubm_train, link_ubm_stats,
-    link_clr (kernel ms), link_speakers, link_merges.
-    A link dictionary of model 'clr' may carry gallery=<gallery.Gallery>, enrol (default True) and
-    exclusive (default True); the global labels then mean the same person in every batch.  The
-    gallery's model is the background model: it is trained on this batch, as above, only when the
-    gallery has none yet, and link['components'] and link['relevance'] must equal the gallery's
-    (ValueError).  The statistics and the chain run within the batch as above.  The records of the
-    resulting batch clusters are the sums of their speakers' records in ascending speaker order
-    (spkd_bw_accumulate); the clusters are identified against the gallery as ONE group
-    (Gallery.identify with the gallery's threshold: the chain declined to merge them, so they are
-    distinct people, and under `exclusive` they get distinct identities).  The global label of a
-    cluster is its identity's index + 1.  With enrol the unknown clusters are appended to the gallery
-    in cluster order and the matched identities take the cluster's record (Gallery.update); without it
-    the gallery is left untouched and the k-th unknown cluster is labelled gallery.n + 1 + k -- the
-    label it would have got.  (A cluster without a usable record is labelled behind those; its label
-    stands for nobody.)  maps, merges, stat_max and stat_min as above; detail: a dict that receives
-    identity, score and second per batch cluster (Gallery.identify's, identity after enrolment) and
-    enrolled, the new identities.  timings gain link_cluster_sum, link_ident (both identify kernels,
-    ms) and link_update.  When no background model can be trained the fallback is the one above and
-    the gallery is unchanged.  The identification threshold, like LINK_CLR's, rests on a synthetic
-    fixture and not on speech."""
-    model = _link_model(link)
-    gal, enrol, exclusive = _link_gallery(link, model)
-    if model[0] == 'clr':
-        if d_frames is None or total_frames is None or files is None or segments is None:
-            raise ValueError('link model clr trains on the frames: it takes d_frames, total_frames, files and '
-                             'segments, the arrays cluster_batch took')
-        if len(segments) != len(files):
-            raise ValueError('one segment array per file')
-        seg_off_s, _, seg_b, seg_e = _segment_ranges(files, segments, float(rate))
-        if seg_off_s.tolist() != np.asarray(seg_off, dtype=np.int64).tolist():
-            raise ValueError('segments: one per label, file by file')
-    member, set_off, spk_file, spk_label = link_speakers(seg_off, labels)
-    n_spk = len(spk_file)
-    maps = [np.zeros(int(np.max(l)) + 1 if len(l) else 0, dtype=np.int32) for l in labels]
-    if n_spk == 0:
-        return maps, [], float('nan'), float('nan')
-    if model[0] == 'clr':
-        try:
-            kept = None if gal is None else {}
-            r = _link_clr(ctx, model, set_off, seg_b[member], seg_e[member], d_frames, total_frames, timings, gal, kept)
-        except hipabi.SpkdError as e:
-            if e.status == hipabi.SPKD_EINVAL:
-                raise ValueError(str(e))
-            raise
-        nm, a, b, d, smax, smin = r if r is not None else (0, [], [], [], float('nan'), float('nan'))
-        if timings is not None:
-            timings['link_speakers'] = n_spk
-            timings['link_merges'] = nm
-        glob = hipabi.labels_from_merges(n_spk, a, b)
-        if gal is not None and r is not None:
-            try:
-                glob = _identify_clusters(ctx, gal, enrol, exclusive, kept, glob, timings, detail)
-            except hipabi.SpkdError as e:
-                if e.status == hipabi.SPKD_EINVAL:
-                    raise ValueError(str(e))
-                raise
-        for f, l, g in zip(spk_file.tolist(), spk_label.tolist(), glob.tolist()):
-            maps[f][l] = g
-        return maps, list(zip(np.asarray(a).tolist(), np.asarray(b).tolist(), np.asarray(d).tolist())), smax, smin
-    d_spk = ctx.dev_scratch('link_speaker_stats', n_spk * hipabi.REC * 8)
-    ctx.sum_stats(d_stats, int(seg_off[-1]), member, set_off, d_spk)
-    if timings is not None:
-        timings.setdefault('link_sum', []).append(ctx.last_ms('reduce_sets'))
-    try:
-        r = ctx.ahc(d_spk, np.array([0, n_spk], dtype=np.int64), _ahc_params(link))
-    except hipabi.SpkdError as e:
-        if e.status == hipabi.SPKD_EINVAL:
-            raise ValueError(str(e))
-        raise
-    nm = int(r['n_merges'][0])
-    if timings is not None:
-        timings.setdefault('link_ahc', []).append(ctx.last_ms('call'))
-        timings['link_speakers'] = n_spk
-        timings['link_merges'] = nm
-    if r['status'] == hipabi.SPKD_ENONFINITE:
-        raise ValueError('array must not contain infs or NaNs')
-    glob = hipabi.labels_from_merges(n_spk, r['a'][:nm], r['b'][:nm])
-    for f, l, g in zip(spk_file.tolist(), spk_label.tolist(), glob.tolist()):
-        maps[f][l] = g
-    merges = list(zip(r['a'][:nm].tolist(), r['b'][:nm].tolist(), r['d'][:nm].tolist()))
-    return maps, merges, float(r['stat_max'][0]), float(r['stat_min'][0])
 
 
 def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl=DIA2_CL, timings=None,
@@ -904,20 +564,23 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     A dictionary like RESEG_SOFT retrains the speakers between the passes on frame posteriors instead of
     decoded rows (reseg['soft'], reseg['soft_scale']; detail['soft_mass'] as there)."""
     method = _method(cl)
+    # the hand-off this call gets: the one asked for, else the device's where it can serve (a detector that
+    # passes its refusal below is neither fused nor on the device, so the rule reads the same behind it)
+    device = handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi')
     if reseg is not None:
         reseg_opts = _resegmentation._reseg_options(reseg, rate, detail)
-        if handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi'):
+        if device:
             raise ValueError('reseg takes the host hand-off')
     if _cd_method(cd) in ('sw', 'm'):
         if fused or handoff == 'device':
             raise ValueError('cd method %s takes the host hand-off and is not fused' % _cd_method(cd))
         handoff = 'host'
     if link is not None:
-        _link_gallery(link, _link_model(link))
-    if link is not None and (handoff == 'device' or (handoff is None and fused and text_contract and method == 'hi')):
-        raise ValueError('link takes the host hand-off')
+        _linking._link_options(link)                 # (its refusals come before any work; link_batch parses for itself)
+        if device:
+            raise ValueError('link takes the host hand-off')
     if handoff is None:
-        handoff = 'device' if fused and text_contract and method == 'hi' else 'host'
+        handoff = 'device' if device else 'host'
     if handoff == 'device':
         if method == 'in':
             raise ValueError('the device hand-off clusters with spk_cluster_hi: method in takes the host hand-off')
@@ -947,29 +610,23 @@ def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timin
     cnt = [len(s) for s in segs]
     if sum(cnt) == 0:
         return [np.zeros((0, 3)) for _ in segs]
+    own = [lab for (lab, _) in res]
     if reseg is not None:
-        own = [lab for (lab, _) in res]
         rows = resegment_batch(ctx, d_frames, total_frames, files, box[0][0], box[0][1], own, rate, reseg,
                                text_contract, timings, detail, segs)
-        if link is not None:
-            more = {}
-            maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], own, link, timings, d_frames, total_frames,
-                                                  files, segs, rate, more)
-            for r, m in zip(rows, maps):
-                r[:, 2] = m[r[:, 2].astype(np.int64)] if len(r) else r[:, 2]
-            if detail is not None:
-                detail['link'] = dict(maps=maps, merges=merges, stat_max=smax, stat_min=smin, **more)
-        return rows
-    allseg = np.concatenate([np.asarray(s, dtype=np.float64).reshape(-1, 2) for s in segs])
-    if link is None:
-        labels = np.concatenate([lab for (lab, _) in res])
-    else:
+    if link is not None:                             # (on the clustering segments, with or without reseg)
         more = {}
-        maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], [lab for (lab, _) in res], link, timings,
-                                              d_frames, total_frames, files, segs, rate, more)
-        labels = np.concatenate([m[lab] for m, (lab, _) in zip(maps, res)])
+        maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], own, link, timings, d_frames, total_frames,
+                                              files, segs, rate, more)
         if detail is not None:
             detail['link'] = dict(maps=maps, merges=merges, stat_max=smax, stat_min=smin, **more)
+    if reseg is not None:
+        if link is not None:
+            for r, m in zip(rows, maps):
+                r[:, 2] = m[r[:, 2].astype(np.int64)] if len(r) else r[:, 2]
+        return rows
+    allseg = np.concatenate([np.asarray(s, dtype=np.float64).reshape(-1, 2) for s in segs])
+    labels = np.concatenate(own if link is None else [m[lab] for m, lab in zip(maps, own)])
     bounds = np.zeros(len(segs) + 1, dtype=np.int64)
     bounds[1:] = np.cumsum(cnt)
     if _method(cl) == 'in':

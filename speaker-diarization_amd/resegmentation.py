@@ -2,13 +2,14 @@
 modelled from what clustering left, every VAD turn scored under them and decoded frame by frame.  A `reseg`
 dictionary is parsed once (_reseg_options); the two speaker models (_GaussSpeakers, _GmmSpeakers) share
 one interface, train(tokens) -> ok and score(ok) -> frame_off, and own their device buffers.  The turn
-table, the segment ranges and the speaker list are pipeline's (_turn_table, _segment_ranges,
-link_speakers), which other stages use too."""
+table, the segment ranges and the speaker list are those of tables (_turn_table, _segment_ranges,
+link_speakers), the layer below every stage; this module imports nothing else of the package but hipabi."""
 import collections
 
 import numpy as np
 
 from . import hipabi
+from .tables import _segment_ranges, _turn_table, link_speakers
 
 # Viterbi resegmentation (resegment_batch): the cost of a speaker switch inside a turn, in natural-log
 # units.  On the synthetic generator every value from 10 to 200 decodes the same paths; real audio,
@@ -371,12 +372,11 @@ def _confidences(speakers, tokens, penalty, conf_scale):
 def _speaker_segments(files, segments, seg_off, rate):
     """The frame ranges of the clustering segments the mixtures train on in pass 1 -> (begin, end), one per
     label, file by file: the ranges segment_stats summed (_segment_ranges)."""
-    from . import pipeline
     if segments is None:
         raise ValueError('reseg model gmm trains on the frames: it takes segments, the arrays cluster_batch took')
     if len(segments) != len(files):
         raise ValueError('one segment array per file')
-    seg_off_s, _, seg_b, seg_e = pipeline._segment_ranges(files, segments, rate)
+    seg_off_s, _, seg_b, seg_e = _segment_ranges(files, segments, rate)
     if seg_off_s.tolist() != np.asarray(seg_off, dtype=np.int64).tolist():
         raise ValueError('segments: one per label, file by file')
     return seg_b, seg_e
@@ -437,12 +437,11 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     the rows are those described above, to the byte.  A soft that is not a bool, a soft_scale that is not a
     finite number > 0, soft_scale * penalty above 600, soft with model gmm: ValueError before any device
     work."""
-    from . import pipeline
     rate = float(rate)
     opts = _reseg_options(reseg, rate, detail)
     if opts.model[0] == 'gmm':
         seg_b, seg_e = _speaker_segments(files, segments, seg_off, rate)
-    member, set_off, spk_file, spk_label = pipeline.link_speakers(seg_off, labels)
+    member, set_off, spk_file, spk_label = link_speakers(seg_off, labels)
     n_files = len(files)
     if len(labels) != n_files:
         raise ValueError('one label array per file')
@@ -452,7 +451,7 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
                          % (RESEG_MAX_SPEAKERS, int(n_spk_file.argmax()), int(n_spk_file.max())))
     out = [np.zeros((0, 3)) for _ in files]
     _empty_detail(detail, opts, n_files)
-    table = pipeline._turn_table(files, rate)
+    table = _turn_table(files, rate)
     if table is None or len(spk_file) == 0:
         return out
     owner, _, _, ls, le, tb, te = table

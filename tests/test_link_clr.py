@@ -186,6 +186,64 @@ def test_refusals_of_the_pipeline_need_no_device():
     assert [m.tolist() for m in maps] == [[]] and merges == []
 
 
+def test_a_dictionary_wrong_in_two_ways_is_refused_for_the_same_reason_as_ever():
+    """The order of the refusals, as recorded before linking got a module and one parser of its own: the
+    model keys in _link_model's order, then the gallery keys, then link_batch's arrays / diarize_batch's
+    hand-off; in diarize_batch the reseg, cl and cd refusals come before any of them.  Whole texts."""
+    pipeline, gallery = pkg('pipeline'), pkg('gallery')
+    files = [pipeline.BatchFile(0, 1000, [(0.0, 8.0)])]
+    segments = [np.array([(0.0, 4.0), (4.0, 8.0)])]
+    labels = [np.array([1, 2])]
+    nan, held = float('nan'), gallery.Gallery(None)
+    both = [
+        (pipeline.LINK_CLR, dict(components=0, threshold=nan), 'link components: 1 .. 8'),
+        (pipeline.LINK_CLR, dict(iterations=-1, ubm_max_frames=1), 'link iterations: an integer >= 0'),
+        (pipeline.LINK_CLR, dict(model='ubm', components=0), 'link model: clr (or no model: the clustering keys of LINK_CL)'),
+        (pipeline.LINK_CLR, dict(var_floor=-1.0, max_spk=-1),
+         'link var_floor: a finite number >= 0 (a share of the variance of all the frames)'),
+        (pipeline.LINK_CLR, dict(gallery=object(), relevance=0.0), 'link relevance: a finite number > 0'),
+        (pipeline.LINK_CLR, dict(gallery=object(), max_spk=2.5), 'link max_spk: an integer >= 0'),
+        (pipeline.LINK_CLR, dict(gallery=held, components=4, relevance=2.0), 'link components: the gallery has 8'),
+        (pipeline.LINK_CL, dict(gallery=object(), components=0), 'link gallery: a gallery holds the records of link model clr'),
+    ]
+    for base, change, text in both:
+        link = dict(base, **change)
+        with pytest.raises(ValueError) as ei:
+            pipeline.link_batch(None, 0, [0, 2], labels, link, d_frames=0, total_frames=1000, files=files, segments=segments)
+        assert str(ei.value) == text, change
+        with pytest.raises(ValueError) as ei:
+            pipeline.diarize_batch(None, 0, 0, [], link=link)
+        assert str(ei.value) == text, change
+    # a bad key together with a missing array (link_batch) or the wrong hand-off (diarize_batch): the key first
+    for change, text in ((dict(gallery=object()), 'link gallery: a gallery.Gallery'),
+                         (dict(threshold=nan), 'link threshold: a finite number (a ratio above it merges)')):
+        link = dict(pipeline.LINK_CLR, **change)
+        with pytest.raises(ValueError) as ei:
+            pipeline.link_batch(None, 0, [0, 2], labels, link, d_frames=None, total_frames=1000, files=files, segments=None)
+        assert str(ei.value) == text, change
+        with pytest.raises(ValueError) as ei:
+            pipeline.diarize_batch(None, 0, 0, [], link=link, fused=True)
+        assert str(ei.value) == text, change
+    # diarize_batch: reseg, the clustering method and the detector are refused before a bad link dictionary
+    bad = dict(pipeline.LINK_CLR, components=0)
+    for kw, text in ((dict(reseg=dict(penalty=-1.0)), 'reseg penalty: a finite number >= 0 (natural-log units)'),
+                     (dict(reseg=pipeline.RESEG, handoff='device'), 'reseg takes the host hand-off'),
+                     (dict(cl=dict(pipeline.DIA2_CL, method='x')), 'cl method: hi or in'),
+                     (dict(cd=dict(pipeline.DIA2_CD, method='x')), 'cd method: gw, sw or m'),
+                     (dict(cd=pipeline.SW_CD, fused=True), 'cd method sw takes the host hand-off and is not fused')):
+        with pytest.raises(ValueError) as ei:
+            pipeline.diarize_batch(None, 0, 0, [], link=bad, **kw)
+        assert str(ei.value) == text, kw
+    # ... and a good one's hand-off before the device-mode checks and the name of the hand-off
+    for base in (pipeline.LINK_CLR, pipeline.LINK_CL):
+        with pytest.raises(ValueError) as ei:
+            pipeline.diarize_batch(None, 0, 0, [], link=base, handoff='device', fused=False)
+        assert str(ei.value) == 'link takes the host hand-off'
+        with pytest.raises(ValueError) as ei:
+            pipeline.diarize_batch(None, 0, 0, [], link=base, handoff='x')
+        assert str(ei.value) == 'handoff: device or host'
+
+
 def test_restated_clr_links_the_people_where_bic_does_not():
     """What the mode is for.  Seeds 11, 12, 13 over the sources of seed 777 (the first tried): per file
     the share of a speaker's frames from its first source runs from 0 to 1.  BIC over one Gaussian a
