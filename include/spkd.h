@@ -487,6 +487,14 @@ spkd_status spkd_merge_batch(spkd_ctx *ctx, const float *d_frames, int64_t n_fra
  *   h_stat_max[p], h_stat_min[p]: variant 1 = running max / min over every
  *   finite distance evaluated (NaN when never updated from the reference's
  *   initial 0 / maxint); variant 2 = max / min of the final matrix.
+ * The minimum and its position are numpy's distances.min() / distances.argmin(): the first
+ * occurrence in row-major order; with a NaN present the minimum is NaN and the position the
+ * first NaN.  -0.0 and +0.0 are equal, as to numpy: the first of them wins whatever its sign,
+ * and a zero minimum comes back as +0.0 in h_merge_d (and as variant 2's h_stat_min, which is
+ * that minimum; its h_stat_max is a plain fp64 maximum and keeps the sign of the zero it finds).
+ * A forced merge (max_spk) of variant 2 whose minimum is +inf lands, like numpy's argmin, on the
+ * first +inf in row-major order, the diagonal of the first alive row: the call fails as a
+ * degenerate merge (variant 1's diagonal, 2^63, is below +inf: it ends the same way).
  */
 /* Launch shape of the merge loop.  MONO: one launch, one workgroup per problem, the whole
  * loop inside it (many files per call).  WIDE: one launch per merge, its log-det work spread

@@ -29,8 +29,11 @@ constexpr double PEN_UNIT = 39.0 + 0.5 * 39.0 * 40.0;  // p + 0.5 p (p + 1), p =
 constexpr int AUX = 3 * DA;                            // diag S | diag pinv S | mean (as f32 value)
 constexpr int ERR_DEGENERATE_MERGE = 2;
 
+// The order-preserving integer key of a distance.  -0.0 and +0.0 are one value to numpy (the first
+// occurrence wins among them), so they are one key, that of +0.0: dkey_inv gives a zero back as +0.0.
 __device__ __forceinline__ unsigned long long dkey(double v) {
     unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    b = (b << 1) ? b : 0ull;
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 __device__ __forceinline__ double dkey_inv(unsigned long long k) {
@@ -697,9 +700,9 @@ struct RowMin { double mv; int mc, nc; };
 // (the caller's own fresh write).  A lane meets its columns in ascending order, four loads in
 // flight, and compares in fp64; the lanes' results meet as integers (wave_argmin_key on the
 // order-preserving key and the column, ~0 for a lane that found nothing).
-// Where the minimum of a row is a zero that occurs with both signs in different lanes, the key
-// order puts -0.0 first, where an fp64 compare would call the two equal and take the lower
-// column.  The selection over the rows (both launch shapes) orders by key as well.
+// Zeros of either sign share a key (dkey), so the key order is the fp64 order and the lower column
+// wins among equals here, in the selection over the rows (both launch shapes) and in
+// row_cache_after_merge alike: an entry is the same whether rescanned or updated in place.
 template <class Alive>
 __device__ __forceinline__ RowMin scan_row(const double* __restrict__ row, long long N, Alive alive,
                                            long long sub_col, double sub_val, int lane) {

@@ -677,6 +677,7 @@ void deal_to_xcds(const int64_t* h_seg_off, const std::vector<int64_t>& order, s
 unsigned long long host_dkey(double v) {                      // dkey() of spkd_cluster.hpp, on the host
     unsigned long long b;
     std::memcpy(&b, &v, sizeof b);
+    b = (b << 1) ? b : 0ull;                                  // (zeros of either sign: one key)
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 
