@@ -99,7 +99,7 @@ enum {
     SPKD_T_CALL = 0, SPKD_T_CHUNK_STATS, SPKD_T_REDUCE_SETS, SPKD_T_PAIR_TERMS,
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
-    SPKD_T_POST_STATS, SPKD_T_RESAMPLE,
+    SPKD_T_POST_STATS, SPKD_T_RESAMPLE, SPKD_T_FRAME_ENERGY, SPKD_T_ENERGY_SEEDS,
     SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
     SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK, SPKD_T_FB_POSTERIOR,
     SPKD_T_IDENT_SCORES, SPKD_T_IDENT_ASSIGN, SPKD_T_BW_ACCUMULATE,
@@ -695,6 +695,69 @@ spkd_status spkd_resample_batch(spkd_ctx *ctx, const int16_t *d_in, int64_t n_fi
                                 const int32_t *h_conv /* [n_files] -> h_convs */, int32_t n_conv,
                                 const spkd_resample_conv *h_convs, const float *h_taps /* all tables, concatenated */,
                                 int16_t *d_out, int64_t *h_out_off /* out [n_files + 1] */);
+
+/* ---------------------------------------------------------------------------
+ * (6c) The seed stage of a speech / non-speech detector trained on the recording itself: frame
+ * energies from the samples and, per file, two order statistics of them with the runs of frames at
+ * or beyond each -- the quietest frames seed a non-speech model, the loudest a speech model
+ * (spkd_gmm_train on the runs, spkd_gmm_loglik_seq and spkd_mindur_viterbi_batch behind it:
+ * self_vad.py).  It stands where the reference loads a VAD model (generate_exp.py:94-97).
+ * PARITY: no reference counterpart; tests/self_vad_numpy.py restates both calls in numpy.
+ *
+ * spkd_frame_energy_batch: the samples lie as frontend.upload_batch leaves them and spkd_mfcc_batch
+ *   reads them: file f owns d_pcm[h_sample_off[f] .. h_sample_off[f+1]) (h_sample_off[0] = 0,
+ *   non-decreasing; a file may be empty; offsets of any parity) and has T_f = n_f / hop frames, the
+ *   frame clock of spkd_mfcc_batch: h_frame_off (out, n_files + 1 entries) equals that call's.  Frame t
+ *   of a file covers the file's samples t hop .. t hop + window - 1; a sample past the file's end
+ *   counts as 0 and is never read from the neighbouring file (a workgroup's tile never crosses a file).
+ *     d_energy[h_frame_off[f] + t] = window * sum s^2 - (sum s)^2           as int64
+ *   which is window^2 times the frame's variance: a DC offset cancels.  Limits: 1 <= hop <= window <=
+ *   SPKD_ENERGY_MAX_WINDOW = 4096.  With these |sum s| <= 2^12 2^15 = 2^27 and sum s^2 <= 2^12 2^30 =
+ *   2^42, so both terms are at most 2^54 and the value lies in [0, 2^54] (below 2^55): every
+ *   operation is an exact integer operation and no rounding occurs anywhere.  The value does not
+ *   depend on the grid, on the other files or on their order.
+ *   One launch for the batch and one wait.  A workgroup takes the frames whose hops fill
+ *   SPKD_ENERGY_TILE samples; each sample is added once, into the sums of its 16-byte cell, the cells
+ *   are scanned in LDS and a frame is the difference of two prefixes, so neighbouring frames share
+ *   their common pieces.  The batch is read once from memory; the window - hop samples two tiles share
+ *   are read a second time through L2.
+ *   SPKD_EINVAL before any device work: hop or window outside the limits, n_files < 0, a null
+ *   h_sample_off / h_frame_off, offsets that do not start at 0 or decrease; null or misaligned device
+ *   pointers only when there is a frame.  No file, or no frame in any: SPKD_OK, h_frame_off filled,
+ *   nothing launched.  Timer: SPKD_T_FRAME_ENERGY.
+ *
+ * spkd_energy_seeds: file f owns the energies d_energy[h_frame_off[f] .. h_frame_off[f+1]) (any int64
+ *   values >= 0), T_f of them.  h_lo[f] is the h_k_low[f]-th smallest of them (1-based), h_hi[f] the
+ *   h_k_high[f]-th largest; the selection is on the integer keys, so it is exact.  h_seeded[f] = 1 when
+ *   both k are >= 1, both are <= T_f, and lo < hi; otherwise 0, which is no error: the file gets no
+ *   runs (a k outside [1, T_f] leaves lo = hi = 0).  For a seeded file class 0 is every maximal run of
+ *   consecutive frames with E <= lo, class 1 every maximal run with E >= hi; ties at a threshold are
+ *   all taken, and a run never crosses a file.
+ *   Out, in pinned memory of the context, valid until its next spkd_energy_seeds (the way
+ *   spkd_vad_viterbi_batch hands back its tokens): (*h_run_off)[2 n_files + 1], the runs of file f and
+ *   class c at [run_off[2 f + c], run_off[2 f + c + 1]) of *h_run_begin / *h_run_end, absolute frame
+ *   numbers of the batch [begin, end), ascending -- what spkd_gmm_train takes as (h_set_off,
+ *   h_range_begin, h_range_end) with speaker 2 f + c when every file is seeded (it refuses a set
+ *   without a range: the caller leaves the unseeded files' sets out).
+ *   A workgroup per file: eight passes of a 256-bin histogram in LDS find both order statistics at
+ *   once and the runs are counted; after one wait for the counts a second launch flags, scans and
+ *   compacts the runs to their exact offsets: run memory is 16 bytes a run, not per frame.
+ *   SPKD_EINVAL before any device work: a null output or host array, n_files < 0, offsets that do not
+ *   start at 0 or decrease, a file of more than 2^31 - 1 frames; a null or misaligned d_energy only
+ *   when there is a frame.  n_files = 0: SPKD_OK, run_off = {0}.  Timer: SPKD_T_ENERGY_SEEDS (both
+ *   launches and the wait between them). */
+#define SPKD_ENERGY_MAX_WINDOW 4096
+#define SPKD_ENERGY_TILE 16384
+spkd_status spkd_frame_energy_batch(spkd_ctx *ctx, const int16_t *d_pcm,
+                                    const int64_t *h_sample_off /* [n_files + 1] */, int64_t n_files,
+                                    int32_t hop, int32_t window, int64_t *d_energy,
+                                    int64_t *h_frame_off /* out [n_files + 1] */);
+spkd_status spkd_energy_seeds(spkd_ctx *ctx, const int64_t *d_energy,
+                              const int64_t *h_frame_off /* [n_files + 1] */, int64_t n_files,
+                              const int64_t *h_k_low, const int64_t *h_k_high /* [n_files] each */,
+                              int64_t *h_lo, int64_t *h_hi, int32_t *h_seeded /* [n_files] each */,
+                              const int64_t **h_run_off, const int64_t **h_run_begin,
+                              const int64_t **h_run_end);
 
 /* ---------------------------------------------------------------------------
  * (7) Speech / non-speech frame scoring: the per-frame state log-likelihoods that AaltoASR's

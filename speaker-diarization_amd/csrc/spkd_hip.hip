@@ -24,6 +24,7 @@
 #include "spkd_mfcc.hpp"
 #include "spkd_mfcc_batch.hpp"
 #include "spkd_resample.hpp"
+#include "spkd_energy.hpp"
 #include "spkd_vad.hpp"
 #include "spkd_vad_batch.hpp"
 #include "spkd_mindur.hpp"
@@ -44,7 +45,7 @@ constexpr int N_SLOTS = 72;
 // never share a slot; nor do the block that goes up and the block that comes down in one call.
 enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
        PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, PIN_MD_SEQS, PIN_MD_TOKENS,
-       PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, PIN_POST_TAB, N_PIN };
+       PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, PIN_POST_TAB, PIN_ES_FILES, PIN_ES_RUNS, N_PIN };
 }
 
 struct spkd_ctx {
@@ -358,7 +359,7 @@ enum {
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
     S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT,
     S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_FB_TAB, S_FB_FWD, S_FB_OUT,
-    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_COUNT
+    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_EN_TAB, S_ES_TAB, S_ES_FILES, S_ES_RUNS, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -2354,6 +2355,132 @@ spkd_status spkd_resample_batch(spkd_ctx* c, const int16_t* d_in, int64_t n_file
                            (const int*)d_ch, (const int*)d_conv, (const RsConv*)d_convs, (const float*)d_taps, d_out);
     }
     if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "resample_batch: kernel launch failed");
+    return call.finish();
+}
+
+// ------------------------------------------------------------------ (6c) frame energies and their seeds
+static_assert(EN_TILE == SPKD_ENERGY_TILE && EN_MAX_WINDOW == SPKD_ENERGY_MAX_WINDOW,
+              "the header states the energy kernel's tile and limit");
+
+namespace {
+// the offsets of a batch: n + 1 entries from 0 on that never decrease
+spkd_status energy_check_offsets(spkd_ctx* c, int64_t n_files, const int64_t* off, const char* what) {
+    if (n_files < 0 || !off) return fail(c, SPKD_EINVAL, std::string(what) + ": null offsets or a negative file count");
+    if (off[0] != 0) return fail(c, SPKD_EINVAL, std::string(what) + ": the offsets must start at 0");
+    for (int64_t f = 0; f < n_files; ++f)
+        if (off[f + 1] < off[f]) return fail(c, SPKD_EINVAL, std::string(what) + ": the offsets must be non-decreasing");
+    return SPKD_OK;
+}
+}  // namespace
+
+spkd_status spkd_frame_energy_batch(spkd_ctx* c, const int16_t* d_pcm, const int64_t* h_sample_off, int64_t n_files,
+                                    int32_t hop, int32_t window, int64_t* d_energy, int64_t* h_frame_off) {
+    if (hop < 1 || window < hop || window > EN_MAX_WINDOW)
+        return fail(c, SPKD_EINVAL, "frame_energy_batch: 1 <= hop <= window <= 4096");
+    TRY(energy_check_offsets(c, n_files, h_sample_off, "frame_energy_batch"));
+    if (!h_frame_off) return fail(c, SPKD_EINVAL, "frame_energy_batch: null frame_off");
+    if (!c) return SPKD_EINVAL;
+    // the frame layout (spkd_mfcc_batch's), and the running count of tiles: a tile lies in one file
+    const size_t n1 = (size_t)n_files + 1;
+    const int64_t per_tile = en_tile_frames(hop);
+    std::vector<int64_t> tiles(n1, 0);
+    h_frame_off[0] = 0;
+    for (int64_t f = 0; f < n_files; ++f) {
+        const int64_t T = (h_sample_off[f + 1] - h_sample_off[f]) / hop;
+        h_frame_off[f + 1] = h_frame_off[f] + T;
+        tiles[(size_t)f + 1] = tiles[(size_t)f] + (T + per_tile - 1) / per_tile;
+    }
+    if (h_frame_off[n_files] == 0) return SPKD_OK;
+    if (!d_pcm || !d_energy) return fail(c, SPKD_EINVAL, "frame_energy_batch: null device buffer");
+    if ((uintptr_t)d_pcm % 2 || (uintptr_t)d_energy % 8)
+        return fail(c, SPKD_EINVAL, "frame_energy_batch: samples 2-byte and energies 8-byte aligned");
+    if (tiles[(size_t)n_files] > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "frame_energy_batch: too many samples in one call");
+    int64_t *d_soff, *d_foff, *d_tiles;
+    std::vector<char> tab;
+    Call call(c);
+    TRY(call.opened);
+    TRY(upload_parts(c, S_EN_TAB, tab, [&](Layout L) {
+        return L.part(d_soff, n1, h_sample_off).part(d_foff, n1, (const int64_t*)h_frame_off)
+            .part(d_tiles, n1, (const int64_t*)tiles.data()).bytes();
+    }));
+    {
+        Timer t(c, SPKD_T_FRAME_ENERGY);
+        hipLaunchKernelGGL(k_frame_energy, dim3((unsigned)tiles[(size_t)n_files]), dim3(EN_TPB), 0, c->stream, d_pcm,
+                           (const long long*)d_soff, (const long long*)d_foff, (const long long*)d_tiles, (long long)n_files,
+                           (int)hop, (int)window, (long long*)d_energy);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "frame_energy_batch: kernel launch failed");
+    return call.finish();
+}
+
+spkd_status spkd_energy_seeds(spkd_ctx* c, const int64_t* d_energy, const int64_t* h_frame_off, int64_t n_files,
+                              const int64_t* h_k_low, const int64_t* h_k_high, int64_t* h_lo, int64_t* h_hi,
+                              int32_t* h_seeded, const int64_t** h_run_off, const int64_t** h_run_begin,
+                              const int64_t** h_run_end) {
+    if (!h_run_off || !h_run_begin || !h_run_end) return fail(c, SPKD_EINVAL, "energy_seeds: null output");
+    *h_run_off = nullptr;
+    *h_run_begin = nullptr;
+    *h_run_end = nullptr;
+    TRY(energy_check_offsets(c, n_files, h_frame_off, "energy_seeds"));
+    if (n_files > 0 && (!h_k_low || !h_k_high || !h_lo || !h_hi || !h_seeded))
+        return fail(c, SPKD_EINVAL, "energy_seeds: null argument");
+    if (n_files > 0x3fffffff) return fail(c, SPKD_EINVAL, "energy_seeds: too many files in one call");
+    for (int64_t f = 0; f < n_files; ++f)
+        if (h_frame_off[f + 1] - h_frame_off[f] > 0x7fffffffLL)
+            return fail(c, SPKD_EINVAL, "energy_seeds: a file of more than 2^31 - 1 frames");
+    if (h_frame_off[n_files] > 0 && !d_energy) return fail(c, SPKD_EINVAL, "energy_seeds: null device buffer");
+    if ((uintptr_t)d_energy % 8) return fail(c, SPKD_EINVAL, "energy_seeds: energies 8-byte aligned");
+    if (!c) return SPKD_EINVAL;
+    const size_t nf = (size_t)n_files;
+    // pinned, the context's until its next spkd_energy_seeds: the offsets of the runs and, in front of
+    // them, what the selection left per file
+    int64_t* run_off = nullptr;
+    EsFile* h_files = nullptr;
+    TRY(carve(c, pinned, PIN_ES_FILES, [&](Layout L) { return L.part(run_off, 2 * nf + 1).part(h_files, nf).bytes(); }));
+    run_off[0] = 0;
+    *h_run_off = run_off;
+    if (n_files == 0) return SPKD_OK;
+    int64_t *d_foff, *d_klow, *d_khigh, *d_run_off, *d_begin = nullptr, *d_end = nullptr, *h_begin = nullptr, *h_end = nullptr;
+    EsFile* d_files = nullptr;
+    std::vector<char> tab;
+    Call call(c);
+    TRY(call.opened);
+    TRY(upload_parts(c, S_ES_TAB, tab, [&](Layout L) {
+        return L.part(d_foff, nf + 1, h_frame_off).part(d_klow, nf, h_k_low).part(d_khigh, nf, h_k_high).bytes();
+    }));
+    TRY(carve(c, scratch, S_ES_FILES, [&](Layout L) { return L.part(d_run_off, 2 * nf + 1).part(d_files, nf).bytes(); }));
+    {
+        // both kernels and, between them, the wait for the counts that place the runs (as a decoder's backtrack)
+        Timer t(c, SPKD_T_ENERGY_SEEDS);
+        hipLaunchKernelGGL(k_energy_select, dim3((unsigned)n_files), dim3(ES_TPB), 0, c->stream, (const long long*)d_energy,
+                           (const long long*)d_foff, (const long long*)d_klow, (const long long*)d_khigh, d_files);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h_files, d_files, nf * sizeof(EsFile), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (size_t f = 0; f < nf; ++f) {
+            run_off[2 * f + 1] = run_off[2 * f] + h_files[f].n_runs[0];
+            run_off[2 * f + 2] = run_off[2 * f + 1] + h_files[f].n_runs[1];
+        }
+        const size_t n_runs = (size_t)run_off[2 * nf];
+        TRY(carve(c, scratch, S_ES_RUNS, [&](Layout L) { return L.part(d_begin, n_runs).part(d_end, n_runs).bytes(); }));
+        TRY(carve(c, pinned, PIN_ES_RUNS, [&](Layout L) { return L.part(h_begin, n_runs).part(h_end, n_runs).bytes(); }));
+        if (n_runs) {
+            HIPCHK(c, hipMemcpyAsync(d_run_off, run_off, (2 * nf + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(k_energy_runs, dim3((unsigned)n_files), dim3(ES_TPB), 0, c->stream, (const long long*)d_energy,
+                               (const long long*)d_foff, (const EsFile*)d_files, (const long long*)d_run_off,
+                               (long long*)d_begin, (long long*)d_end);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(h_begin, d_begin, n_runs * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(h_end, d_end, n_runs * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        }
+    }
+    for (size_t f = 0; f < nf; ++f) {
+        h_lo[f] = h_files[f].lo;
+        h_hi[f] = h_files[f].hi;
+        h_seeded[f] = h_files[f].seeded;
+    }
+    *h_run_begin = h_begin;
+    *h_run_end = h_end;
     return call.finish();
 }
 

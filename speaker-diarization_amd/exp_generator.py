@@ -18,6 +18,9 @@ border shift, `<exppath>/<base>.last_frame` and the decoded token stream `<exppa
   .exp      "<first frame> <word>" per word of the best path, single spaces, no newline
             (_clean_decoder_output, generate_exp.py:134-137)
 
+  --self-trained FCONFIG   no model at all: the detector is trained on each recording itself over the
+            features of that configuration file (self_vad.py); .exp and .last_frame as ever, no .lna
+
 PARITY UNPINNED where AaltoASR computes (front-end, likelihood convention, decoder): each
 choice is listed in INTEGRATION.md and restated in the test suite's numpy file.  The .lna
 layout, the shift, .last_frame and the file naming are the reference's own.
@@ -29,7 +32,7 @@ import re
 
 import numpy as np
 
-from . import frontend, hipabi
+from . import feaconfig, frontend, hipabi, self_vad
 from .vad_model import VadModel
 
 SHIFT_BORD = 0.2
@@ -187,6 +190,37 @@ def run(recipe, lnapath, exppath, model_path, device=0):
     return [lna for _, lna in lnas]
 
 
+def run_self_trained(recipe, exppath, fcfg, opts=self_vad.SELF_VAD, device=0):
+    """Every file of the recipe without a model (self_vad.decode_batch on the features of the
+    configuration file fcfg, all files as one batch): .exp and .last_frame as run() leaves them, no
+    .lna (there are no state scores of a model to keep).  A file the detector could not be trained on
+    gets an empty .exp.  Returns the exp paths."""
+    wavs = [wav for wav, _ in get_lnas(recipe, exppath)]
+    cfg = feaconfig.FeatureConfig.load(fcfg)
+    pcms = []
+    for wav in wavs:
+        pcm, rate = frontend.read_wav(wav)
+        if rate != cfg.sample_rate:
+            raise ValueError('%s is sampled at %d Hz, the feature configuration wants %d' % (wav, rate, cfg.sample_rate))
+        pcms.append(pcm)
+    ctx = hipabi.Context(device)
+    try:
+        d_pcm, sample_off = frontend.upload_batch(ctx, pcms)
+        d_frames, frame_off = frontend.extract_batch(ctx, cfg, d_pcm, sample_off)
+        tokens, last_frames = self_vad.decode_batch(ctx, opts, cfg, d_pcm, sample_off, d_frames, frame_off)
+    finally:
+        ctx.close()
+    out = []
+    for wav, toks, last in zip(wavs, tokens, last_frames):
+        stem = op.join(exppath, op.splitext(op.basename(wav))[0])
+        with open(stem + '.last_frame', 'w') as f:
+            f.write('%d' % last)
+        with open(stem + '.exp', 'w') as f:
+            f.write(' '.join('%d %s' % (t, w) for t, w in toks))
+        out.append(stem + '.exp')
+    return out
+
+
 def _create_argpath(argpath, say, ask):
     """generate_exp.py:78-91."""
     say('ERROR:', argpath, 'is not a valid directory.')
@@ -211,17 +245,32 @@ def main(argv=None, say=None, ask=input):
     ap = argparse.ArgumentParser(prog='generate_exp.py', description='Generate exp files: speech / non-speech '
                                  'scoring and decoding of the audio files of a recipe.')
     ap.add_argument('RECIPE', help='Recipe with audio files to process.')
-    ap.add_argument('-l', '--lnapath', default='./lna', help='Choose a folder to drop the lna files [default: ./lna]')
+    ap.add_argument('-l', '--lnapath', default='./lna', help='Choose a folder to drop the lna files [default: ./lna]; '
+                    'accepted and unused with --self-trained, which writes no .lna')
     ap.add_argument('-e', '--exppath', default='./exp', help='Choose a folder to drop the exp files [default: ./exp]')
     ap.add_argument('-m', '--model', default='./hmms/mfcc_16g_11.10.2007_10',
                     help='Choose a model [default: ./hmms/mfcc_16g_11.10.2007_10]')
     ap.add_argument('-a', '--asrpath', default='./AaltoASR', help='Accepted and ignored (no AaltoASR needed)')
     ap.add_argument('-t', '--tokenpass', default='./VAD/tokenpass/test_token_pass',
                     help='Accepted and ignored (no test_token_pass needed)')
+    ap.add_argument('--self-trained', dest='self_trained', metavar='FCONFIG', default=None,
+                    help='No model: train the speech / non-speech detector on each recording itself, over the '
+                         'features of this feature configuration file (fconfig.cfg); -m is not read, no .lna is written')
     ap.add_argument('--version', action='version', version='1.0')
     a = ap.parse_args(argv)
     if not op.exists(a.RECIPE):
         say('ERROR:', a.RECIPE, 'does not exist.')
+        return 0
+    if a.self_trained is not None:
+        if not op.isdir(a.exppath) and not _create_argpath(a.exppath, say, ask):
+            return 0
+        if not op.isfile(a.self_trained):
+            say('ERROR:', a.self_trained, 'does not exist.')
+            return 0
+        say('Reading recipe:', a.RECIPE)
+        say('Self-trained detector on the features of:', a.self_trained)
+        say('Writing `.exp` files in:', a.exppath)
+        run_self_trained(a.RECIPE, a.exppath, a.self_trained)
         return 0
     for path in (a.lnapath, a.exppath):
         if not op.isdir(path) and not _create_argpath(path, say, ask):

@@ -17,7 +17,7 @@ MERGE_NO_AHEAD = 1
 TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pair_terms',
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
-                                        'post_stats', 'resample',
+                                        'post_stats', 'resample', 'frame_energy', 'energy_seeds',
                                         'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
                                         'mindur_viterbi', 'mindur_backtrack', 'fb_posterior',
                                         'ident_scores', 'ident_assign', 'bw_accumulate',
@@ -45,6 +45,8 @@ RESAMPLE_MAX_HALF = 256     # SPKD_RESAMPLE_MAX_HALF: taps to either side of an 
 RESAMPLE_MAX_TERM = 1 << 20     # SPKD_RESAMPLE_MAX_TERM: up and down of a conversion
 RESAMPLE_MAX_TAPS = 1 << 22     # SPKD_RESAMPLE_MAX_TAPS: floats of one conversion's table
 RESAMPLE_MAX_SPAN = 33281   # SPKD_RESAMPLE_MAX_SPAN: input frames a tile may read
+ENERGY_MAX_WINDOW = 4096    # SPKD_ENERGY_MAX_WINDOW: samples of a frame of k_frame_energy (hop <= window)
+ENERGY_TILE = 16384         # SPKD_ENERGY_TILE: samples whose hops make the frames of a workgroup of k_frame_energy
 REC = 820
 DIM = 39
 
@@ -57,7 +59,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
            'spkd_gauss_models', 'spkd_gauss_loglik', 'spkd_gmm_train', 'spkd_gmm_loglik_seq',
            'spkd_ubm_stats', 'spkd_clr_link', 'spkd_mindur_viterbi_batch', 'spkd_fb_posterior_batch',
-           'spkd_clr_identify', 'spkd_bw_accumulate', 'spkd_post_stats']
+           'spkd_clr_identify', 'spkd_bw_accumulate', 'spkd_post_stats', 'spkd_frame_energy_batch', 'spkd_energy_seeds']
 
 
 class CdParams(C.Structure):
@@ -222,6 +224,8 @@ def load_library(path=None):
     lib.spkd_mfcc.argtypes = [vp, vp, i64, P(MfccParams), vp, vp, vp, vp, vp, vp, P(i64)]
     lib.spkd_mfcc_batch.argtypes = [vp, vp, i64, vp, P(MfccParams), vp, vp, vp, vp, vp, vp, vp]
     lib.spkd_resample_batch.argtypes = [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.spkd_frame_energy_batch.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
+    lib.spkd_energy_seeds.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, P(vp), P(vp), P(vp)]
     lib.spkd_sw_window_count.argtypes = [i64, dbl, dbl]
     lib.spkd_sw_window_count.restype = i64
     lib.spkd_sw.argtypes = [vp, vp, i64, vp, vp, i64, P(CdParams), vp, vp]
@@ -790,6 +794,43 @@ class Context(object):
                                                 len(convs), table, _ptr(taps) if taps.size else None,
                                                 C.c_void_p(d_out), _ptr(out_off)))
         return out_off
+
+    # ---- (6c) the seed stage of the self-trained detector
+    def frame_energy_batch(self, d_pcm, sample_off, hop, window, d_energy):
+        """The energy of every frame of concatenated device samples (spkd_frame_energy_batch): file f
+        owns the samples [sample_off[f], sample_off[f+1]) and has len // hop frames, mfcc_batch's
+        clock; frame t covers the file's samples t * hop .. t * hop + window - 1 (0 past its end) and
+        d_energy[frame] = window * sum s^2 - (sum s)^2 as int64, exact.  Returns frame_off (int64, one
+        entry per file and the total).  The kernel's time is last_ms('frame_energy')."""
+        off = np.ascontiguousarray(sample_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1:
+            raise SpkdError(SPKD_EINVAL, 'sample_off: one entry per file and the total')
+        frame_off = np.zeros(len(off), dtype=np.int64)
+        self.check(self.lib.spkd_frame_energy_batch(self.h, C.c_void_p(d_pcm), _ptr(off), len(off) - 1, int(hop), int(window),
+                                                    C.c_void_p(d_energy), _ptr(frame_off)))
+        return frame_off
+
+    def energy_seeds(self, d_energy, frame_off, k_low, k_high):
+        """Per file of concatenated device energies (int64 [sum T]) the k_low[f]-th smallest and the
+        k_high[f]-th largest (1-based) and the runs of frames at or beyond them (spkd_energy_seeds)
+        -> (lo int64 [n], hi int64 [n], seeded int32 [n], run_off int64 [2 n + 1], run_begin,
+        run_end): the runs of file f and class c (0: E <= lo, 1: E >= hi) at [run_off[2 f + c],
+        run_off[2 f + c + 1]), absolute frames [begin, end), ascending; a file with a k outside
+        [1, T] or lo >= hi is not seeded and has none.  Copies: the library's arrays live until the
+        next call.  The kernels' time is last_ms('energy_seeds')."""
+        off = self._frame_off(frame_off)
+        n = len(off) - 1
+        kl, kh = np.ascontiguousarray(k_low, dtype=np.int64), np.ascontiguousarray(k_high, dtype=np.int64)
+        if kl.shape != (n,) or kh.shape != (n,):
+            raise SpkdError(SPKD_EINVAL, 'k_low, k_high: one entry per file')
+        lo, hi, seeded = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        out = [C.c_void_p() for _ in range(3)]
+        self.check(self.lib.spkd_energy_seeds(self.h, C.c_void_p(d_energy), _ptr(off), n, _ptr(kl), _ptr(kh), _ptr(lo),
+                                              _ptr(hi), _ptr(seeded), *[C.byref(o) for o in out]))
+        run_off = _view(out[0].value, 2 * n + 1, np.int64).copy()
+        n_runs = int(run_off[-1])
+        return (lo, hi, seeded, run_off, _view(out[1].value, n_runs, np.int64).copy(),
+                _view(out[2].value, n_runs, np.int64).copy())
 
     # ---- (7)
     def gmm_loglik(self, d_features, n_frames, gmm, d_scores):

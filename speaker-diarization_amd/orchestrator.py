@@ -16,6 +16,10 @@ code is ignored, exactly like the reference: the stages ARE the interface.  All 
 drop-in executables in this repository: the two the reference takes from AaltoASR are
 stand-ins (./generate_exp.py with GPU scoring and an exact Viterbi, ./feacat with the GPU
 front-end; parity unpinned), the other five restate the reference's scripts.
+
+One option the reference does not have: --self-vad runs ./generate_exp.py with `--self-trained <-fcfg>`,
+the speech / non-speech detector trained on the recording itself (self_vad.py), so that no VAD model
+file is needed.  Without it every argv list is the reference's.
 """
 import argparse
 import os.path as op
@@ -60,6 +64,7 @@ EXPORT_STAGES = [                                  # only when the output is a f
     ('Calling aku2elan.py', ['./aku2elan.py', '{out}', '-o', '{stem}.eaf']),
 ]
 EXP_STAGE = ['./generate_exp.py', '{init}', '-e', '{exp}', '-l', '{lna}']
+SELF_VAD_ARGS = ['--self-trained', '{fcfg}']       # behind EXP_STAGE with --self-vad: no VAD model file
 FEACAT_STAGE = ['{feacat}', '-c', '{fcfg}', '-H', '--raw-output', '{wav}']
 VAD_STAGE = ['./voice-detection2.py', '{init}', '{exp}', '-o', '{vad}', '-ms', '0.5', '-mns', '1.5']
 FFMPEG_STAGE = ['ffmpeg', '-i', '{media}', '-ar', '16000', '-ac', '1', '-ab', '32k', '{wav}']
@@ -84,6 +89,9 @@ def main(argv=None, say=None):
     parser.add_argument('infile', type=str, help='Specifies the media file')
     for flag, dest, default, text in OPTIONS:
         parser.add_argument(flag, dest=dest, type=str, default=default(cwd), help=text)
+    parser.add_argument('--self-vad', dest='self_vad', action='store_true',
+                        help='Speech / non-speech detection trained on the recording itself (generate_exp.py '
+                             '--self-trained with the -fcfg configuration): no VAD model file is needed')
     o = parser.parse_args(argv)
 
     # ---- what must exist, said in the reference's words and order; a miss ends the run quietly
@@ -118,7 +126,7 @@ def main(argv=None, say=None):
 
     # ---- the two producers side by side; the VAD recipe as soon as the .exp files are there
     say('Performing exp generation and feacat concurrently')
-    decoder = Popen(_fill(EXP_STAGE, paths))
+    decoder = Popen(_fill(EXP_STAGE + (SELF_VAD_ARGS if o.self_vad else []), paths))
     fea_file = op.join(o.feapath, op.splitext(op.basename(paths['wav']))[0] + '.fea')
     with open(fea_file, 'w') as sink:
         extractor = Popen(_fill(FEACAT_STAGE, paths), stdout=sink)

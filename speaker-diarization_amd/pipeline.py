@@ -18,12 +18,15 @@ import numpy as np
 from . import exp_generator, frontend, hipabi, voice_detection
 from . import linking as _linking
 from . import resegmentation as _resegmentation
+from . import self_vad as _self_vad
 from .recipe import py2_float_str
 # the linking stage (linking.py, on clr_model.py and gallery.py): its settings and its entry point under their names here
 from .linking import LINK_CL, LINK_CLR, _link_model, link_batch, ubm_ranges
 # the resegmentation stage (resegmentation.py): its settings and its entry point under their names here
 from .resegmentation import (FB_MAX_SCALED_PENALTY, RESEG, RESEG_CONF, RESEG_GMM, RESEG_MAX_SPEAKERS, RESEG_MD,
                              RESEG_SOFT, RESEG_SOFT_SCALE, resegment_batch)
+# the self-trained speech / non-speech detector (self_vad.py): its settings under their name here
+from .self_vad import SELF_VAD
 # the tables every stage reads (tables.py), under their names here
 from .tables import BatchFile, _ahc_params, _segment_ranges, _turn_table, link_speakers
 
@@ -45,17 +48,48 @@ class FusedStats(object):
         self.d_buf, self.n_buf, self.index, self.begin, self.end = d_buf, n_buf, index, begin, end
 
 
-def vad_batch(ctx, model, pcms, opt=None, text_contract=True, timings=None, uploaded=None):
+_ABSENT = object()                      # a keyword of vad_batch that the caller did not write
+
+
+def vad_batch(ctx, model, pcms, opt=None, text_contract=True, timings=None, uploaded=None, cfg=_ABSENT, features=_ABSENT,
+              detail=None):
     """Speech / non-speech turns of a batch of files from their int16 samples, decided on the
     device (exp_generator.decode_batch: front-end, scores, border shift and decoding without the
     scores leaving it), then the turn state machine of voice-detection2.py over each file's tokens.
     One list of (start_s, end_s) per file, ready for BatchFile(..., vad=...).  With text_contract
     the times are the ones the change detector reads back from the recipe the file path writes
     (py2_str, 12 significant digits: spkd_py2_roundtrip).  uploaded: the samples already on the
-    device (frontend.upload_batch), as decode_batch takes them."""
+    device (frontend.upload_batch), as decode_batch takes them.
+    model: a VadModel, or a dictionary like SELF_VAD: then no model file is needed, the detector is
+    trained on each recording itself (self_vad.decode_batch) over the features of cfg, the diarization
+    feature configuration, which is required; features = (d_frames, total_frames, frame_off) are
+    those features when the caller has them (features_batch computes them otherwise); detail, a dict,
+    receives vad_untrained and vad_passes_run; opt's rate must be cfg.frame_rate (the default when
+    opt is None).  A file too short or too even to train on has no turns.  With a VadModel cfg and
+    features must be absent."""
+    self_trained = isinstance(model, dict)
+    if not self_trained and (cfg is not _ABSENT or features is not _ABSENT):
+        raise ValueError('cfg and features go with a dictionary like SELF_VAD, not with a VadModel')
+    if self_trained:
+        cfg = None if cfg is _ABSENT else cfg
+        features = None if features is _ABSENT else features
+        if cfg is None:
+            raise ValueError('the self-trained detector works on the features of cfg: cfg is required')
+        _self_vad._options(model)                   # (its refusals come before any device work)
+        opt = opt or voice_detection.VadOptions(rate=cfg.frame_rate)
+        if float(opt.rate) != float(cfg.frame_rate):
+            raise ValueError('the turns are counted at %g frames a second, the features at %g' % (opt.rate, cfg.frame_rate))
     opt = opt or voice_detection.VadOptions()
     _t0 = time.perf_counter()
-    tokens, last_frames = exp_generator.decode_batch(ctx, model, pcms, timings, uploaded)
+    if self_trained:
+        if uploaded is None:
+            uploaded = frontend.upload_batch(ctx, pcms, timings)
+        if features is None:
+            features = features_batch(ctx, cfg, uploaded=uploaded, timings=timings)
+        tokens, last_frames = _self_vad.decode_batch(ctx, model, cfg, uploaded[0], uploaded[1], features[0], features[2],
+                                                     timings, detail)
+    else:
+        tokens, last_frames = exp_generator.decode_batch(ctx, model, pcms, timings, uploaded)
     _t1 = time.perf_counter()
     out = []
     for toks, last in zip(tokens, last_frames):
@@ -96,12 +130,24 @@ def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=Non
     (features_batch with cfg, the fconfig.cfg chain) both from it, then diarize_batch with the
     turns and the frames as they lie on the device.  uploaded: the samples already on the device
     (frontend.upload_batch or frontend.resample_batch; pcms is not read then).  kw: diarize_batch's
-    text_contract, fused, handoff, link, reseg, detail.  Returns its rows."""
-    _one_clock(model, cfg)
+    text_contract, fused, handoff, link, reseg, detail.  Returns its rows.
+    model: a dictionary like SELF_VAD instead of a VadModel needs no model file: one upload, ONE
+    feature chain (cfg's), the self-trained turns on those features (vad_batch), then diarize_batch;
+    detail, if given, also receives vad_untrained and vad_passes_run."""
+    self_trained = isinstance(model, dict)
+    if self_trained:
+        _self_vad._options(model)
+    else:
+        _one_clock(model, cfg)
     if uploaded is None:
         uploaded = frontend.upload_batch(ctx, pcms, timings)
-    vad = vad_batch(ctx, model, None, text_contract=kw.get('text_contract', True), timings=timings, uploaded=uploaded)
-    d_frames, total, frame_off = features_batch(ctx, cfg, uploaded=uploaded, timings=timings)
+    if self_trained:
+        d_frames, total, frame_off = features_batch(ctx, cfg, uploaded=uploaded, timings=timings)
+        vad = vad_batch(ctx, model, None, text_contract=kw.get('text_contract', True), timings=timings, uploaded=uploaded,
+                        cfg=cfg, features=(d_frames, total, frame_off), detail=kw.get('detail'))
+    else:
+        vad = vad_batch(ctx, model, None, text_contract=kw.get('text_contract', True), timings=timings, uploaded=uploaded)
+        d_frames, total, frame_off = features_batch(ctx, cfg, uploaded=uploaded, timings=timings)
     files = [BatchFile(frame_off[f], frame_off[f + 1] - frame_off[f], vad[f]) for f in range(len(vad))]
     return diarize_batch(ctx, d_frames, total, files, rate=float(cfg.frame_rate), cd=cd, cl=cl, timings=timings, **kw)
 
@@ -110,8 +156,12 @@ def diarize_audio_batch(ctx, model, cfg, audios, cd=DIA2_CD, cl=DIA2_CL, timings
     """From recordings to speakers: audios = [(samples, rate)], int16 [n] or [n, channels] at any
     rate (frontend.read_audio), resampled and downmixed to cfg.sample_rate on the device
     (frontend.resample_batch; group_bytes: its bound on the raw audio held there), then exactly
-    diarize_pcm_batch from its upload on.  Returns its rows."""
-    _one_clock(model, cfg)
+    diarize_pcm_batch from its upload on (model: a VadModel, or a dictionary like SELF_VAD).
+    Returns its rows."""
+    if isinstance(model, dict):
+        _self_vad._options(model)
+    else:
+        _one_clock(model, cfg)
     group = {} if group_bytes is None else {'group_bytes': group_bytes}
     uploaded = frontend.resample_batch(ctx, audios, cfg.sample_rate, timings=timings, **group)
     return diarize_pcm_batch(ctx, model, cfg, None, cd=cd, cl=cl, timings=timings, uploaded=uploaded, **kw)
