@@ -99,7 +99,7 @@ enum {
     SPKD_T_CALL = 0, SPKD_T_CHUNK_STATS, SPKD_T_REDUCE_SETS, SPKD_T_PAIR_TERMS,
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
-    SPKD_T_POST_STATS, SPKD_T_RESAMPLE, SPKD_T_FRAME_ENERGY, SPKD_T_ENERGY_SEEDS,
+    SPKD_T_POST_STATS, SPKD_T_BF_GCC, SPKD_T_BF_TRACK, SPKD_T_BF_SUM, SPKD_T_RESAMPLE, SPKD_T_FRAME_ENERGY, SPKD_T_ENERGY_SEEDS,
     SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
     SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK, SPKD_T_FB_POSTERIOR,
     SPKD_T_IDENT_SCORES, SPKD_T_IDENT_ASSIGN, SPKD_T_BW_ACCUMULATE,
@@ -695,6 +695,121 @@ spkd_status spkd_resample_batch(spkd_ctx *ctx, const int16_t *d_in, int64_t n_fi
                                 const int32_t *h_conv /* [n_files] -> h_convs */, int32_t n_conv,
                                 const spkd_resample_conv *h_convs, const float *h_taps /* all tables, concatenated */,
                                 int16_t *d_out, int64_t *h_out_off /* out [n_files + 1] */);
+
+/* ---------------------------------------------------------------------------
+ * (6b2) Delay-and-sum beamforming of multi-microphone recordings, in front of the resampler: the
+ * channels of a table-top array carry the same voice at different delays, so their plain average
+ * (what (6b) forms, and `ffmpeg -ac 1`) comb-filters it.  Three calls, one per stage: the GCC-PHAT
+ * correlation of every channel against a reference channel and its best lags per analysis step
+ * (spkd_bf_gcc), a Viterbi over the steps that picks one lag per step and channel (spkd_bf_track),
+ * and the sum of the channels at those lags (spkd_bf_sum).  The stages are separate so that each can
+ * be checked exactly from the previous one's output, and because the delays are worth having on
+ * their own (a known array geometry skips stage 1).  PARITY UNPINNED: the reference has no such
+ * stage; BeamformIt, the usual program of this scheme, is not available and not restated, and no
+ * parity with it or any other beamformer is claimed.  tests/beamform_numpy.py restates all three
+ * stages.  Opt-in: nothing else in this header calls them.
+ *
+ * Layout.  A file has C channels of interleaved int16, n sample frames, and a geometry (hop H,
+ * window W, max_lag D) in samples.  The transform length is fixed: SPKD_BF_NFFT = 8192.  Geometry
+ * limits: 1 <= H <= SPKD_BF_MAX_HOP = 2^20; 1 <= W; 0 <= D; W + D <= 8192, so every lag in [-D, D]
+ * of the circular correlation is alias-free.  Files and geometries follow spkd_resample_batch's
+ * conventions: file f owns the int16 elements d_in[h_in_off[f] .. h_in_off[f+1]) (h_in_off[0] = 0,
+ * non-decreasing, offsets of any parity, the span a multiple of h_channels[f] in [1, 8]) and has
+ * the geometry h_geoms[h_geom[f]].
+ *
+ * Steps and reference channel.  The file has T = 1 step if n <= W, else T = (n - W) div H + 1.
+ * Step t reads frames [t H, t H + W), with zeros beyond the file.  Nothing of a neighbouring file
+ * ever enters.  C = 1 gives T = 0: the file is copied through.  A requested reference channel
+ * ref >= 0 is taken as given.  ref = -1 picks the channel with the largest exact int64 sum of
+ * squares, and a tie goes to the lowest index.  The sum fits: 10 h at 96 kHz full scale is
+ * 3.7e18.
+ *
+ * Stage 1, correlation.  For each step and each channel c != ref: a is the step's reference window
+ * and b is channel c's window, as float32 zero-padded to 8192 (the int16 samples are exact in
+ * float32).  A, B are their forward DFTs (e^{-2 pi i k n / N}).  P_k = B_k conj(A_k).
+ * G_k = P_k / |P_k| where |P_k| > 0, else 0.  r[m] = Re (1/N) sum_k G_k e^{+2 pi i k m / N}, and
+ * v[d] = r[d mod N] for d in [-D, D], as float32.  With x_c[n] = x_ref[n - d] this puts the peak at
+ * +d.  (The device forms both spectra from one float32 transform of a + i b and treats a window
+ * that is all zero as the exact zero spectrum it has; where one channel is far quieter than the
+ * other, its spectrum carries the louder one's rounding, about 1e-7 of it.)
+ * A lag is a candidate if both of these hold:  v[d] > v[d-1], or d = -D;  v[d] >= v[d+1], or d = D.
+ * The candidates are ranked by value descending, and ties go to the lower lag.  The first
+ * SPKD_BF_NBEST = 4 are kept as (lag int32, value float32).  Missing slots carry slot 0's lag and
+ * value -INFINITY.  The reference channel's own entry is (0, 1.0f) and three absent slots (lag 0),
+ * and its row of the curve is 1 at lag 0 and 0 elsewhere, by definition, not by a transform.
+ * Digital silence gives v = 0 everywhere, hence the single candidate (-D, 0).
+ *
+ * Stage 2, tracking, per file and channel, serially over the steps, with the options n_best in
+ * [1, 4] (only the first n_best slots are used; the others count as absent), min_peak (float32),
+ * jump_penalty lambda (double, >= 0, finite) and jump_cap (int32, >= 0).  A step is reliable if its
+ * slot-0 value is >= min_peak.  An unreliable step takes its lags from a reliable step of the same
+ * channel: the nearest earlier one, if there is one; else the nearest later one; else the single
+ * candidate lag 0, if the channel has none at all.  The present slots of a filled step get value 0,
+ * and absent slots stay -INFINITY.  Viterbi over the slots:
+ *   S[0][k] = (double)val[0][k];
+ *   S[t][k] = max_j (S[t-1][j] - lambda (double)min(|lag[t][k] - lag[t-1][j]|, cap)) + (double)val[t][k]:
+ *   one rounded multiply, one rounded subtract, one rounded add, in that order, with no contraction
+ *   into an FMA; ties in j go to the lower j.
+ * The end state is the best k, with ties to the lower k; then backtrack.  The output is
+ * delay[t][c], int32.  Given the same candidates, a host restatement reproduces this to the bit.
+ *
+ * Stage 3, sum.  The anchors are a_t = t H + W div 2.  For output sample n the pair (t0, t1, j) is:
+ *   n < a_0: (0, 0, 0);   n >= a_{T-1}: (T-1, T-1, 0);
+ *   else: t0 = (n - a_0) div H, t1 = t0 + 1, j = (n - a_0) mod H.
+ * num = sum_c [(H - j) x_c[n + delay[t0][c]] + j x_c[n + delay[t1][c]]] in int64; x_c outside
+ * [0, n) is 0.  y[n] = rint((double)num / (double)(C H)), saturated to int16: one correctly rounded
+ * division with half to even, as (6b) rounds.  The linear cross-fade between neighbouring steps'
+ * delays is what keeps a delay change from clicking.  num is exact, so the stage is bit-exact
+ * whoever computes it.
+ *
+ * spkd_bf_gcc: h_ref[n_files] is the requested reference channel of each file, -1 to pick.  Writes
+ *   d_ref int32 [n_files]; d_lag int32 and d_val float32 at cand_off[f] + ((t C + c) 4 + k), with
+ *   cand_off the running sum of 4 T C; h_step_off[n_files + 1], the running sum of T.  An optional
+ *   d_curve (null in production) receives every v as float32 [T][C][2 D + 1] per file, file f's at
+ *   h_curve_off[f] (out, n_files + 1 entries, the running sum of T C (2 D + 1); may be null with a
+ *   null d_curve).
+ *   Refusals (SPKD_EINVAL before any device work): n_files < 0 or n_geom < 0; a null host array;
+ *   offsets that do not start at 0 or decrease; a channel count outside [1, 8]; a span that is no
+ *   multiple of the file's channel count; a geometry index out of range; a hop outside
+ *   [1, SPKD_BF_MAX_HOP]; a window below 1; a negative max_lag; window + max_lag above
+ *   SPKD_BF_NFFT; a reference channel outside [-1, channels); more than 2^31 - 1 steps times
+ *   channels; null device pointers only when there is a sample.  No file, or no sample in any:
+ *   SPKD_OK, the host offsets filled, nothing launched, the device arrays untouched.
+ *   Timer: SPKD_T_BF_GCC (all launches of the call).
+ * spkd_bf_track: h_step_off and h_channels as above (the candidates lie as spkd_bf_gcc leaves
+ *   them), the options by value; d_delay int32 at delay_off[f] + t C + c, delay_off the running sum
+ *   of T C.  Refusals: n_files < 0; a null host array; step offsets that do not start at 0 or
+ *   decrease; a channel count outside [1, 8]; n_best outside [1, 4]; a min_peak that is not a
+ *   number; a jump_penalty that is negative or not finite; a negative jump_cap; null device pointers
+ *   only when there is a step.  No step: SPKD_OK, nothing launched.  Device scratch held by the
+ *   context: one byte per step and channel.  Timer: SPKD_T_BF_TRACK.
+ * spkd_bf_sum: the audio and geometries as for spkd_bf_gcc, d_delay as spkd_bf_track leaves it.
+ *   Mono int16 out at the file's own rate, n samples per file, laid out as spkd_resample_batch
+ *   reads a one-channel file; h_out_off (out, n_files + 1 entries) is their running sum.  Delays
+ *   are not limited to [-D, D]: a sample they point outside the file is 0.  Refusals: those of
+ *   spkd_bf_gcc on files and geometries; a null h_out_off; null device pointers only when there is
+ *   a sample.  No sample: SPKD_OK, h_out_off filled, nothing launched.  Timer: SPKD_T_BF_SUM. */
+typedef struct { int32_t hop, window, max_lag; } spkd_bf_geom;
+#define SPKD_BF_NFFT 8192
+#define SPKD_BF_NBEST 4
+#define SPKD_BF_MAX_HOP 1048576
+spkd_status spkd_bf_gcc(spkd_ctx *ctx, const int16_t *d_in, int64_t n_files,
+                        const int64_t *h_in_off /* [n_files + 1], int16 elements */,
+                        const int32_t *h_channels /* [n_files] */,
+                        const int32_t *h_geom /* [n_files] -> h_geoms */, int32_t n_geom,
+                        const spkd_bf_geom *h_geoms, const int32_t *h_ref /* [n_files], -1: pick */,
+                        int32_t *d_ref, int32_t *d_lag, float *d_val, float *d_curve /* or NULL */,
+                        int64_t *h_step_off /* out [n_files + 1] */, int64_t *h_curve_off /* out [n_files + 1] */);
+spkd_status spkd_bf_track(spkd_ctx *ctx, int64_t n_files, const int64_t *h_step_off /* [n_files + 1] */,
+                          const int32_t *h_channels /* [n_files] */, const int32_t *d_lag, const float *d_val,
+                          int32_t n_best, float min_peak, double jump_penalty, int32_t jump_cap,
+                          int32_t *d_delay);
+spkd_status spkd_bf_sum(spkd_ctx *ctx, const int16_t *d_in, int64_t n_files,
+                        const int64_t *h_in_off /* [n_files + 1], int16 elements */,
+                        const int32_t *h_channels /* [n_files] */,
+                        const int32_t *h_geom /* [n_files] -> h_geoms */, int32_t n_geom,
+                        const spkd_bf_geom *h_geoms, const int32_t *d_delay,
+                        int16_t *d_out, int64_t *h_out_off /* out [n_files + 1] */);
 
 /* ---------------------------------------------------------------------------
  * (6c) The seed stage of a speech / non-speech detector trained on the recording itself: frame

@@ -24,6 +24,7 @@
 #include "spkd_mfcc.hpp"
 #include "spkd_mfcc_batch.hpp"
 #include "spkd_resample.hpp"
+#include "spkd_beamform.hpp"
 #include "spkd_energy.hpp"
 #include "spkd_vad.hpp"
 #include "spkd_vad_batch.hpp"
@@ -38,7 +39,7 @@
 using namespace spkd;
 
 namespace {
-constexpr int N_SLOTS = 72;
+constexpr int N_SLOTS = 80;
 // Pinned host buffers, each named where it is used (stage(), TokenHandBack, the batch hand-off).  A slot belongs
 // to one block of one entry point: what a call leaves there for its caller (the hand-off's results, a decoder's
 // tokens) stays valid until that entry point is called again, so two calls whose results can be live together
@@ -54,6 +55,8 @@ struct spkd_ctx {
     bool own_stream = false;
     bool gw_lds_ok = false;
     int rs_lds_cap = 0;          // dynamic LDS bytes admitted for k_resample
+    bool bf_lds_ok = false;      // k_bf_gcc's dynamic LDS size is admitted
+    bool bf_tw_ready = false;    // the transform's twiddles are in their scratch slot (S_BF_TW)
     int gw_waves = 0;
     unsigned long long init_keys[2] = {0ull, ~0ull};
     int step_waves = 0;          // step chain: waves per workgroup (0 = by problem size, 4, 8)
@@ -359,7 +362,7 @@ enum {
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
     S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT,
     S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_FB_TAB, S_FB_FWD, S_FB_OUT,
-    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_EN_TAB, S_ES_TAB, S_ES_FILES, S_ES_RUNS, S_COUNT
+    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_BF_TAB, S_BF_TW, S_BF_ENERGY, S_BF_BACK, S_EN_TAB, S_ES_TAB, S_ES_FILES, S_ES_RUNS, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -412,6 +415,8 @@ static spkd_status create_ctx(int device, void* stream, bool borrow, spkd_ctx** 
         if (hipFuncSetAttribute((const void*)k_resample, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess)
             c->rs_lds_cap = want;
     }
+    c->bf_lds_ok = BF_LDS_BYTES <= lds_max &&
+                   hipFuncSetAttribute((const void*)k_bf_gcc, hipFuncAttributeMaxDynamicSharedMemorySize, BF_LDS_BYTES) == hipSuccess;
     // waves per turn of the growing-window kernel: 0 = by the number of turns (gw_impl)
     if (const char* e = getenv("SPKD_GW_WAVES")) c->gw_waves = atoi(e);
     if (const char* e = getenv("SPKD_STEP_WAVES")) { const int v = atoi(e); c->step_waves = (v == 4 || v == 8) ? v : 0; }
@@ -2355,6 +2360,208 @@ spkd_status spkd_resample_batch(spkd_ctx* c, const int16_t* d_in, int64_t n_file
                            (const int*)d_ch, (const int*)d_conv, (const RsConv*)d_convs, (const float*)d_taps, d_out);
     }
     if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "resample_batch: kernel launch failed");
+    return call.finish();
+}
+
+// ------------------------------------------------------------------ (6b2) delay-and-sum beamforming
+static_assert(BF_N == SPKD_BF_NFFT && BF_NBEST == SPKD_BF_NBEST && BF_MAX_HOP == SPKD_BF_MAX_HOP && BF_MAX_CH == SPKD_RESAMPLE_MAX_CH &&
+              sizeof(BfGeom) == sizeof(spkd_bf_geom), "the header states the beamformer's transform length and limits");
+
+namespace {
+// The files and geometries of a beamforming call, checked (the resampler's conventions), and what the
+// three stages derive from them: per file the steps T, and the running sums of T (step_off), T C (wg_off:
+// workgroups of k_bf_gcc, entries of d_delay, a quarter of the candidates) and C (lane_off).
+struct BfBatch {
+    std::vector<int64_t> steps, wg, lanes;
+    int64_t samples = 0;
+};
+spkd_status bf_check_files(spkd_ctx* c, const char* what, int64_t n_files, const int64_t* h_in_off, const int32_t* h_channels) {
+    const std::string w(what);
+    if (n_files < 0) return fail(c, SPKD_EINVAL, w + ": negative file count");
+    if (!h_in_off || (n_files > 0 && !h_channels)) return fail(c, SPKD_EINVAL, w + ": null host array");
+    if (h_in_off[0] != 0) return fail(c, SPKD_EINVAL, w + ": in_off must start at 0");
+    for (int64_t f = 0; f < n_files; ++f)
+        if (h_in_off[f + 1] < h_in_off[f]) return fail(c, SPKD_EINVAL, w + ": in_off must be non-decreasing");
+    for (int64_t f = 0; f < n_files; ++f) {
+        if (h_channels[f] < 1 || h_channels[f] > BF_MAX_CH) return fail(c, SPKD_EINVAL, w + ": channel count outside [1, 8]");
+        if ((h_in_off[f + 1] - h_in_off[f]) % h_channels[f] != 0)
+            return fail(c, SPKD_EINVAL, w + ": a file's span is not a multiple of its channel count");
+    }
+    return SPKD_OK;
+}
+spkd_status bf_batch(spkd_ctx* c, const char* what, int64_t n_files, const int64_t* h_in_off, const int32_t* h_channels,
+                     const int32_t* h_geom, int32_t n_geom, const spkd_bf_geom* h_geoms, BfBatch& B) {
+    const std::string w(what);
+    if (n_geom < 0) return fail(c, SPKD_EINVAL, w + ": negative geometry count");
+    TRY(bf_check_files(c, what, n_files, h_in_off, h_channels));
+    if ((n_files > 0 && !h_geom) || (n_geom > 0 && !h_geoms)) return fail(c, SPKD_EINVAL, w + ": null host array");
+    for (int64_t f = 0; f < n_files; ++f)
+        if (h_geom[f] < 0 || h_geom[f] >= n_geom) return fail(c, SPKD_EINVAL, w + ": geometry index out of range");
+    for (int32_t k = 0; k < n_geom; ++k) {
+        const spkd_bf_geom& g = h_geoms[k];
+        if (g.hop < 1 || g.hop > BF_MAX_HOP) return fail(c, SPKD_EINVAL, w + ": hop outside [1, 2^20]");
+        if (g.window < 1) return fail(c, SPKD_EINVAL, w + ": window below 1");
+        if (g.max_lag < 0) return fail(c, SPKD_EINVAL, w + ": negative max_lag");
+        if ((int64_t)g.window + g.max_lag > BF_N) return fail(c, SPKD_EINVAL, w + ": window + max_lag exceeds the transform length 8192");
+    }
+    const size_t n1 = (size_t)n_files + 1;
+    B.steps.assign(n1, 0);
+    B.wg.assign(n1, 0);
+    B.lanes.assign(n1, 0);
+    for (int64_t f = 0; f < n_files; ++f) {
+        const spkd_bf_geom& g = h_geoms[h_geom[f]];
+        const int C = h_channels[f];
+        const int64_t T = bf_steps((h_in_off[f + 1] - h_in_off[f]) / C, C, g.hop, g.window);
+        B.steps[(size_t)f + 1] = B.steps[(size_t)f] + T;
+        B.wg[(size_t)f + 1] = B.wg[(size_t)f] + T * C;
+        B.lanes[(size_t)f + 1] = B.lanes[(size_t)f] + C;
+    }
+    B.samples = h_in_off[n_files];
+    return SPKD_OK;
+}
+}  // namespace
+
+spkd_status spkd_bf_gcc(spkd_ctx* c, const int16_t* d_in, int64_t n_files, const int64_t* h_in_off, const int32_t* h_channels,
+                        const int32_t* h_geom, int32_t n_geom, const spkd_bf_geom* h_geoms, const int32_t* h_ref,
+                        int32_t* d_ref, int32_t* d_lag, float* d_val, float* d_curve, int64_t* h_step_off, int64_t* h_curve_off) {
+    if (!c) return SPKD_EINVAL;
+    BfBatch B;
+    TRY(bf_batch(c, "bf_gcc", n_files, h_in_off, h_channels, h_geom, n_geom, h_geoms, B));
+    if (!h_step_off || (n_files > 0 && !h_ref) || (d_curve && !h_curve_off)) return fail(c, SPKD_EINVAL, "bf_gcc: null host array");
+    for (int64_t f = 0; f < n_files; ++f)
+        if (h_ref[f] < -1 || h_ref[f] >= h_channels[f])
+            return fail(c, SPKD_EINVAL, "bf_gcc: reference channel outside [-1, channels)");
+    const size_t n1 = (size_t)n_files + 1;
+    std::vector<int64_t> en_tiles(n1, 0), curve_off(n1, 0);
+    for (int64_t f = 0; f < n_files; ++f) {
+        const int64_t n = (h_in_off[f + 1] - h_in_off[f]) / h_channels[f];
+        en_tiles[(size_t)f + 1] = en_tiles[(size_t)f] + (n + BF_EN_TILE - 1) / BF_EN_TILE;
+        curve_off[(size_t)f + 1] = curve_off[(size_t)f] +
+            (B.wg[(size_t)f + 1] - B.wg[(size_t)f]) * (2 * (int64_t)h_geoms[h_geom[f]].max_lag + 1);
+    }
+    std::copy(B.steps.begin(), B.steps.end(), h_step_off);
+    if (h_curve_off) std::copy(curve_off.begin(), curve_off.end(), h_curve_off);
+    if (B.samples == 0) return SPKD_OK;
+    if (!d_in || !d_ref || !d_lag || !d_val) return fail(c, SPKD_EINVAL, "bf_gcc: null device buffer");
+    if (B.wg[(size_t)n_files] > 0x7fffffffLL || en_tiles[(size_t)n_files] > 0x7fffffffLL)
+        return fail(c, SPKD_EINVAL, "bf_gcc: too many steps in one call");
+    if (!c->bf_lds_ok) return fail(c, SPKD_EHIP, "bf_gcc: the kernel's dynamic LDS size was not admitted on this device");
+    int64_t *d_ioff, *d_wg, *d_tiles, *d_coff;
+    int32_t *d_ch, *d_geom, *d_want;
+    BfGeom* d_geoms;
+    std::vector<char> tab;
+    Call call(c);
+    TRY(call.opened);
+    TRY(upload_parts(c, S_BF_TAB, tab, [&](Layout L) {
+        return L.part(d_ioff, n1, h_in_off).part(d_wg, n1, (const int64_t*)B.wg.data()).part(d_tiles, n1, (const int64_t*)en_tiles.data())
+            .part(d_coff, n1, (const int64_t*)curve_off.data()).part(d_ch, (size_t)n_files, h_channels).part(d_geom, (size_t)n_files, h_geom)
+            .part(d_want, (size_t)n_files, h_ref).part(d_geoms, (size_t)n_geom, (const BfGeom*)h_geoms).bytes();
+    }));
+    void *d_tw = nullptr, *d_energy = nullptr;
+    TRY(scratch(c, S_BF_TW, (size_t)(BF_N / 2) * sizeof(float2), &d_tw));
+    TRY(scratch(c, S_BF_ENERGY, (size_t)n_files * BF_MAX_CH * sizeof(unsigned long long), &d_energy));
+    HIPCHK(c, hipMemsetAsync(d_energy, 0, (size_t)n_files * BF_MAX_CH * sizeof(unsigned long long), c->stream));
+    {
+        Timer t(c, SPKD_T_BF_GCC);
+        if (!c->bf_tw_ready) hipLaunchKernelGGL(k_bf_twiddle, dim3(BF_N / 2 / 256), dim3(256), 0, c->stream, (float2*)d_tw);
+        c->bf_tw_ready = true;
+        if (en_tiles[(size_t)n_files] > 0)
+            hipLaunchKernelGGL(k_bf_energy, dim3((unsigned)en_tiles[(size_t)n_files]), dim3(BF_EN_TPB), 0, c->stream, d_in,
+                               (const long long*)d_ioff, (const long long*)d_tiles, (long long)n_files, (const int*)d_ch,
+                               (unsigned long long*)d_energy);
+        hipLaunchKernelGGL(k_bf_ref, dim3((unsigned)((n_files + 255) / 256)), dim3(256), 0, c->stream,
+                           (const unsigned long long*)d_energy, (const int*)d_ch, (const int*)d_want, (long long)n_files, d_ref);
+        if (B.wg[(size_t)n_files] > 0)
+            hipLaunchKernelGGL(k_bf_gcc, dim3((unsigned)B.wg[(size_t)n_files]), dim3(BF_TPB), BF_LDS_BYTES, c->stream, d_in,
+                               (const long long*)d_ioff, (const long long*)d_wg, (long long)n_files, (const int*)d_ch,
+                               (const int*)d_geom, (const BfGeom*)d_geoms, (const int*)d_ref, (const float2*)d_tw, d_lag, d_val,
+                               d_curve, (const long long*)d_coff);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "bf_gcc: kernel launch failed");
+    return call.finish();
+}
+
+spkd_status spkd_bf_track(spkd_ctx* c, int64_t n_files, const int64_t* h_step_off, const int32_t* h_channels,
+                          const int32_t* d_lag, const float* d_val, int32_t n_best, float min_peak, double jump_penalty,
+                          int32_t jump_cap, int32_t* d_delay) {
+    if (!c) return SPKD_EINVAL;
+    if (n_files < 0) return fail(c, SPKD_EINVAL, "bf_track: negative file count");
+    if (!h_step_off || (n_files > 0 && !h_channels)) return fail(c, SPKD_EINVAL, "bf_track: null host array");
+    if (h_step_off[0] != 0) return fail(c, SPKD_EINVAL, "bf_track: step_off must start at 0");
+    for (int64_t f = 0; f < n_files; ++f) {
+        if (h_step_off[f + 1] < h_step_off[f]) return fail(c, SPKD_EINVAL, "bf_track: step_off must be non-decreasing");
+        if (h_channels[f] < 1 || h_channels[f] > BF_MAX_CH) return fail(c, SPKD_EINVAL, "bf_track: channel count outside [1, 8]");
+    }
+    if (n_best < 1 || n_best > BF_NBEST) return fail(c, SPKD_EINVAL, "bf_track: n_best outside [1, 4]");
+    if (!(min_peak == min_peak)) return fail(c, SPKD_EINVAL, "bf_track: min_peak is not a number");
+    if (!(jump_penalty >= 0.0) || std::isinf(jump_penalty)) return fail(c, SPKD_EINVAL, "bf_track: jump_penalty must be finite and not negative");
+    if (jump_cap < 0) return fail(c, SPKD_EINVAL, "bf_track: negative jump_cap");
+    const size_t n1 = (size_t)n_files + 1;
+    std::vector<int64_t> wg(n1, 0), lanes(n1, 0);
+    for (int64_t f = 0; f < n_files; ++f) {
+        wg[(size_t)f + 1] = wg[(size_t)f] + (h_step_off[f + 1] - h_step_off[f]) * h_channels[f];
+        lanes[(size_t)f + 1] = lanes[(size_t)f] + h_channels[f];
+    }
+    if (wg[(size_t)n_files] == 0) return SPKD_OK;
+    if (!d_lag || !d_val || !d_delay) return fail(c, SPKD_EINVAL, "bf_track: null device buffer");
+    if (wg[(size_t)n_files] > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "bf_track: too many steps in one call");
+    int64_t *d_wg, *d_lanes;
+    int32_t* d_ch;
+    std::vector<char> tab;
+    Call call(c);
+    TRY(call.opened);
+    TRY(upload_parts(c, S_BF_TAB, tab, [&](Layout L) {
+        return L.part(d_wg, n1, (const int64_t*)wg.data()).part(d_lanes, n1, (const int64_t*)lanes.data())
+            .part(d_ch, (size_t)n_files, h_channels).bytes();
+    }));
+    void* d_back = nullptr;
+    TRY(scratch(c, S_BF_BACK, (size_t)wg[(size_t)n_files], &d_back));
+    {
+        Timer t(c, SPKD_T_BF_TRACK);
+        hipLaunchKernelGGL(k_bf_track, dim3((unsigned)((lanes[(size_t)n_files] + 63) / 64)), dim3(64), 0, c->stream,
+                           (const long long*)d_wg, (const long long*)d_lanes, (long long)n_files, (const int*)d_ch, d_lag, d_val,
+                           (int)n_best, min_peak, jump_penalty, (int)jump_cap, (unsigned char*)d_back, d_delay);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "bf_track: kernel launch failed");
+    return call.finish();
+}
+
+spkd_status spkd_bf_sum(spkd_ctx* c, const int16_t* d_in, int64_t n_files, const int64_t* h_in_off, const int32_t* h_channels,
+                        const int32_t* h_geom, int32_t n_geom, const spkd_bf_geom* h_geoms, const int32_t* d_delay,
+                        int16_t* d_out, int64_t* h_out_off) {
+    if (!c) return SPKD_EINVAL;
+    BfBatch B;
+    TRY(bf_batch(c, "bf_sum", n_files, h_in_off, h_channels, h_geom, n_geom, h_geoms, B));
+    if (!h_out_off) return fail(c, SPKD_EINVAL, "bf_sum: null host array");
+    const size_t n1 = (size_t)n_files + 1;
+    std::vector<int64_t> tiles(n1, 0);
+    h_out_off[0] = 0;
+    for (int64_t f = 0; f < n_files; ++f) {
+        const int64_t n = (h_in_off[f + 1] - h_in_off[f]) / h_channels[f];
+        h_out_off[f + 1] = h_out_off[f] + n;
+        tiles[(size_t)f + 1] = tiles[(size_t)f] + (n + BF_SUM_TILE - 1) / BF_SUM_TILE;
+    }
+    if (B.samples == 0) return SPKD_OK;
+    if (!d_in || !d_out || (B.wg[(size_t)n_files] > 0 && !d_delay)) return fail(c, SPKD_EINVAL, "bf_sum: null device buffer");
+    if (tiles[(size_t)n_files] > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "bf_sum: too many samples in one call");
+    int64_t *d_ioff, *d_ooff, *d_tiles, *d_wg;
+    int32_t *d_ch, *d_geom;
+    BfGeom* d_geoms;
+    std::vector<char> tab;
+    Call call(c);
+    TRY(call.opened);
+    TRY(upload_parts(c, S_BF_TAB, tab, [&](Layout L) {
+        return L.part(d_ioff, n1, h_in_off).part(d_ooff, n1, (const int64_t*)h_out_off).part(d_tiles, n1, (const int64_t*)tiles.data())
+            .part(d_wg, n1, (const int64_t*)B.wg.data()).part(d_ch, (size_t)n_files, h_channels).part(d_geom, (size_t)n_files, h_geom)
+            .part(d_geoms, (size_t)n_geom, (const BfGeom*)h_geoms).bytes();
+    }));
+    {
+        Timer t(c, SPKD_T_BF_SUM);
+        hipLaunchKernelGGL(k_bf_sum, dim3((unsigned)tiles[(size_t)n_files]), dim3(BF_SUM_TPB), 0, c->stream, d_in,
+                           (const long long*)d_ioff, (const long long*)d_ooff, (const long long*)d_tiles, (const long long*)d_wg,
+                           (long long)n_files, (const int*)d_ch, (const int*)d_geom, (const BfGeom*)d_geoms, d_delay, d_out);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "bf_sum: kernel launch failed");
     return call.finish();
 }
 

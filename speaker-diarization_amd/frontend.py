@@ -199,7 +199,144 @@ def _audio_files(audios):
     return files
 
 
-def resample_batch(ctx, audios, rate_out, group_bytes=RESAMPLE_GROUP_BYTES, timings=None):
+# Delay-and-sum beamforming (include/spkd.h (6b2)): the analysis step, window and largest delay in
+# seconds, and the tracking options of spkd_bf_track.  min_peak, jump_penalty and jump_cap rest on the
+# synthetic scenes of tests/beamform_numpy.py and are UNMEASURED on speech, as every other default of
+# this kind here is; parity with BeamformIt or any other beamformer is unpinned.  ref: the reference
+# channel, -1 for the loudest, or a list with one entry per file.
+BEAMFORM = dict(step_s=0.25, window_s=0.5, max_delay_s=0.01, n_best=4, min_peak=0.1, jump_penalty=0.02, jump_cap=25, ref=-1)
+BEAMFORM_MAX_LAG = hipabi.BF_NFFT // 2
+
+
+def beamform_geometry(rate, opts=BEAMFORM):
+    """(H, W, D) of spkd_bf_geom for audio at `rate` Hz: D = ceil(max_delay_s rate), H = rint(step_s
+    rate), W = min(rint(window_s rate), 8192 - D): the window and the largest lag share the fixed
+    8192-point transform.  At 16 kHz the defaults give (4000, 8000, 160); at 48 kHz (12000, 7712, 480):
+    there the window is shorter than the step, so a third of the audio is never looked at by the
+    delay estimate (the sum still covers every sample).  ValueError if that leaves W < 1, H outside
+    [1, 2^20] or D above 4096."""
+    rate = int(rate)
+    D = int(math.ceil(float(opts['max_delay_s']) * rate - 1e-9))
+    H = int(round(float(opts['step_s']) * rate))
+    if D < 0 or D > BEAMFORM_MAX_LAG:
+        raise ValueError('%d Hz: a largest delay of %d samples is outside [0, %d]' % (rate, D, BEAMFORM_MAX_LAG))
+    W = min(int(round(float(opts['window_s']) * rate)), hipabi.BF_NFFT - D)
+    if W < 1:
+        raise ValueError('%d Hz: a window of %d samples' % (rate, W))
+    if not 1 <= H <= hipabi.BF_MAX_HOP:
+        raise ValueError('%d Hz: a step of %d samples is outside [1, %d]' % (rate, H, hipabi.BF_MAX_HOP))
+    return H, W, D
+
+
+def _beamform_options(opts, n_files):
+    """A beamform dictionary, checked: every key of BEAMFORM and no other -> (opts, ref int32 [n_files])."""
+    if not isinstance(opts, dict) or set(opts) != set(BEAMFORM):
+        raise ValueError('beamform: a dictionary with the keys of BEAMFORM expected (%s)' % ', '.join(sorted(BEAMFORM)))
+    if not 1 <= int(opts['n_best']) <= hipabi.BF_NBEST:
+        raise ValueError('beamform: n_best outside [1, %d]' % hipabi.BF_NBEST)
+    if not float(opts['jump_penalty']) >= 0 or math.isinf(float(opts['jump_penalty'])) or int(opts['jump_cap']) < 0:
+        raise ValueError('beamform: jump_penalty and jump_cap must not be negative')
+    if math.isnan(float(opts['min_peak'])):
+        raise ValueError('beamform: min_peak is not a number')
+    ref = opts['ref']
+    if isinstance(ref, (int, np.integer)):
+        ref = [int(ref)] * n_files
+    ref = np.array([int(r) for r in ref], dtype=np.int32)
+    if ref.shape != (n_files,):
+        raise ValueError('beamform: ref is one channel or one per file (%d files, %d entries)' % (n_files, ref.size))
+    return opts, ref
+
+
+def _beamform_plan(files, opts):
+    """Geometries and reference channels of checked files -> (geoms, geom index int32, ref int32)."""
+    opts, ref = _beamform_options(opts, len(files))
+    rates = sorted(set(rate for _, rate in files))
+    geoms = [beamform_geometry(rate, opts) for rate in rates]
+    for i, ((a, _), r) in enumerate(zip(files, ref)):
+        if not -1 <= r < a.shape[1]:
+            raise ValueError('file %d: reference channel %d of %d channels' % (i, r, a.shape[1]))
+    return geoms, np.array([rates.index(rate) for _, rate in files], dtype=np.int32), ref
+
+
+def _beamform_group(ctx, d_raw, in_off, channels, geom, geoms, ref, opts, d_out, ms, detail=None):
+    """The three stages on one uploaded group -> out_off; ms[stage] += the stage's time."""
+    n_files = len(channels)
+    C = np.asarray(channels, dtype=np.int64)
+    frames = np.diff(in_off) // C
+    T = np.array([0 if c == 1 else (1 if n <= geoms[g][1] else (n - geoms[g][1]) // geoms[g][0] + 1)
+                  for n, c, g in zip(frames, C, geom)], dtype=np.int64)
+    wg_off = np.concatenate([[0], np.cumsum(T * C)]).astype(np.int64)
+    total = int(wg_off[-1])
+    d_ref = ctx.dev_scratch('bf_ref', max(4 * n_files, 16))
+    d_lag = ctx.dev_scratch('bf_lag', max(16 * total, 16))
+    d_val = ctx.dev_scratch('bf_val', max(16 * total, 16))
+    d_delay = ctx.dev_scratch('bf_delay', max(4 * total, 16))
+    step_off, _ = ctx.bf_gcc(d_raw, in_off, channels, geom, geoms, ref, d_ref, d_lag, d_val)
+    assert np.array_equal(np.diff(step_off), T)
+    some = int(in_off[-1]) > 0
+    if some:
+        ms['bf_gcc'] += ctx.last_ms('bf_gcc')
+        ctx.bf_track(step_off, channels, d_lag, d_val, opts['n_best'], opts['min_peak'], opts['jump_penalty'], opts['jump_cap'],
+                     d_delay)
+        if total:
+            ms['bf_track'] += ctx.last_ms('bf_track')
+    out_off = ctx.bf_sum(d_raw, in_off, channels, geom, geoms, d_delay, d_out)
+    if some:
+        ms['bf_sum'] += ctx.last_ms('bf_sum')
+    if detail is not None:
+        got_ref = np.zeros(n_files, dtype=np.int32)
+        delay = np.zeros(total, dtype=np.int32)
+        val = np.zeros(4 * total, dtype=np.float32)
+        if some:
+            ctx.d2h(got_ref, d_ref)
+        if some and total:
+            ctx.d2h(delay, d_delay)
+            ctx.d2h(val, d_val)
+        for f in range(n_files):
+            shape = (int(T[f]), int(C[f]))
+            detail.setdefault('ref', []).append(int(got_ref[f]))
+            detail.setdefault('delay', []).append(delay[wg_off[f]:wg_off[f + 1]].reshape(shape).copy())
+            detail.setdefault('reliable', []).append(
+                val[4 * wg_off[f]:4 * wg_off[f + 1]].reshape(shape + (4,))[:, :, 0] >= np.float32(opts['min_peak']))
+    return out_off
+
+
+def _note_beamform(timings, ms):
+    if timings is not None:
+        for k, v in ms.items():
+            timings.setdefault(k, []).append(v)
+
+
+def beamform_batch(ctx, audios, opts=BEAMFORM, timings=None, detail=None):
+    """The channels of every file aligned and summed on the device (spkd_bf_gcc, spkd_bf_track,
+    spkd_bf_sum; include/spkd.h (6b2)): audios as resample_batch takes them -> (d_mono, sample_off),
+    the mono int16 files at their own rates, still on the device in a buffer the context keeps, file f
+    at [sample_off[f], sample_off[f+1]).  A one-channel file is copied through.  opts: a dictionary
+    like BEAMFORM.  detail, if a dictionary, receives per file 'ref' (the reference channel), 'delay'
+    (int32 [T, C]) and 'reliable' (bool [T, C]).  Input errors are ValueErrors before the context is
+    touched."""
+    files = _audio_files(audios)
+    geoms, geom, ref = _beamform_plan(files, opts)
+    channels = np.array([a.shape[1] for a, _ in files], dtype=np.int32)
+    in_off = np.concatenate([[0], np.cumsum([a.size for a, _ in files])]).astype(np.int64)
+    sample_off = np.concatenate([[0], np.cumsum([len(a) for a, _ in files])]).astype(np.int64)
+    d_raw = ctx.dev_scratch('audio_batch', max(2 * int(in_off[-1]), 16))
+    d_out = ctx.dev_scratch('bf_mono', max(2 * int(sample_off[-1]), 16))
+    _t0 = time.perf_counter()
+    for (a, _), o in zip(files, in_off):
+        if a.size:
+            ctx.h2d(d_raw + 2 * int(o), a)
+    wall = time.perf_counter() - _t0
+    ms = dict(bf_gcc=0.0, bf_track=0.0, bf_sum=0.0)
+    got = _beamform_group(ctx, d_raw, in_off, channels, geom, geoms, ref, opts, d_out, ms, detail)
+    assert np.array_equal(got, sample_off)
+    if timings is not None:
+        timings.setdefault('wall_upload', []).append(1e3 * wall)
+    _note_beamform(timings, ms)
+    return d_out, sample_off
+
+
+def resample_batch(ctx, audios, rate_out, group_bytes=RESAMPLE_GROUP_BYTES, timings=None, beamform=None):
     """The audio of a batch of files, audios = [(samples, rate)] with int16 samples [n] or
     [n, channels], converted to mono at rate_out on the device (spkd_resample_batch) -> (d_pcm,
     sample_off), exactly what upload_batch returns for the converted files: vad_batch(uploaded=...)
@@ -208,11 +345,16 @@ def resample_batch(ctx, audios, rate_out, group_bytes=RESAMPLE_GROUP_BYTES, timi
     keeps, and each group is converted into its place of the 'pcm_batch' buffer, whose offsets are
     known beforehand (output_offsets): the raw scratch stays bounded, an hour of 48 kHz stereo being
     six times its 16 kHz mono.  Anything but integer samples that fit int16, one to eight channels
-    and a positive integer rate is a ValueError before the context is touched."""
+    and a positive integer rate is a ValueError before the context is touched.
+    beamform: None, or a dictionary like BEAMFORM: each uploaded group is then aligned and summed
+    (beamform_batch's three calls) into a second scratch, bounded like the first, and resampled from
+    there as one-channel files, instead of being averaged by the resampler's downmix."""
     files = _audio_files(audios)
     rate_out = int(rate_out)
     if group_bytes < 1:
         raise ValueError('group_bytes must be positive')
+    if beamform is not None:
+        geoms, geom, ref = _beamform_plan(files, beamform)
     rates = sorted(set(rate for _, rate in files))
     convs, tables, at = [], [], 0
     for rate in rates:
@@ -237,6 +379,10 @@ def resample_batch(ctx, audios, rate_out, group_bytes=RESAMPLE_GROUP_BYTES, timi
     d_pcm = ctx.dev_scratch('pcm_batch', max(2 * int(sample_off[-1]), 16))
     d_raw = ctx.dev_scratch('audio_batch', max(biggest, 16))
     wall, ms = 0.0, 0.0
+    if beamform is not None:
+        most = max([sum(len(files[f][0]) for f in range(lo, hi)) for lo, hi in groups] + [0])
+        d_mono = ctx.dev_scratch('bf_mono', max(2 * most, 16))
+        bf_ms = dict(bf_gcc=0.0, bf_track=0.0, bf_sum=0.0)
     for lo, hi in groups:
         in_off = np.concatenate([[0], np.cumsum([files[f][0].size for f in range(lo, hi)])]).astype(np.int64)
         _t0 = time.perf_counter()
@@ -244,13 +390,20 @@ def resample_batch(ctx, audios, rate_out, group_bytes=RESAMPLE_GROUP_BYTES, timi
             if files[f][0].size:
                 ctx.h2d(d_raw + 2 * int(o), files[f][0])
         wall += time.perf_counter() - _t0
-        got = ctx.resample_batch(d_raw, in_off, channels[lo:hi], conv[lo:hi], convs, taps, d_pcm + 2 * int(sample_off[lo]))
+        if beamform is not None:
+            mono_off = _beamform_group(ctx, d_raw, in_off, channels[lo:hi], geom[lo:hi], geoms, ref[lo:hi], beamform, d_mono, bf_ms)
+            got = ctx.resample_batch(d_mono, mono_off, np.ones(hi - lo, dtype=np.int32), conv[lo:hi], convs, taps,
+                                     d_pcm + 2 * int(sample_off[lo]))
+        else:
+            got = ctx.resample_batch(d_raw, in_off, channels[lo:hi], conv[lo:hi], convs, taps, d_pcm + 2 * int(sample_off[lo]))
         assert np.array_equal(got, sample_off[lo:hi + 1] - sample_off[lo])
         if got[-1]:
             ms += ctx.last_ms('resample')
     if timings is not None:
         timings.setdefault('wall_upload', []).append(1e3 * wall)
         timings.setdefault('resample', []).append(ms)
+    if beamform is not None:
+        _note_beamform(timings, bf_ms)
     return d_pcm, sample_off
 
 
@@ -311,7 +464,7 @@ def main(argv=None, stdout=None):
 
 
 def to16k_main(argv=None):
-    """./to16k.py IN.wav [-o OUT.wav] [-r 16000]: one 16-bit PCM .wav of any rate and channel count
+    """./to16k.py IN.wav [-o OUT.wav] [-r 16000] [--beamform]: one 16-bit PCM .wav of any rate and channel count
     -> 16-bit mono at the rate the pipeline wants, converted on the device (resample_batch).  What a
     user without ffmpeg runs in front of spk-diarization2.py for .wav input."""
     ap = argparse.ArgumentParser(description='Resample and downmix a 16-bit PCM .wav on the device (the step '
@@ -319,12 +472,15 @@ def to16k_main(argv=None):
     ap.add_argument('wav')
     ap.add_argument('-o', dest='out', default=None, help='output file (default: IN.16k.wav beside the input)')
     ap.add_argument('-r', dest='rate', type=int, default=16000, help='output sample rate')
+    ap.add_argument('--beamform', action='store_true',
+                    help='align the channels before summing them (delay-and-sum with the BEAMFORM defaults) '
+                         'instead of averaging them')
     args = ap.parse_args(argv)
     out = args.out or os.path.splitext(args.wav)[0] + '.16k.wav'
     samples, rate = read_audio(args.wav)
     ctx = hipabi.Context(0)
     try:
-        d_pcm, sample_off = resample_batch(ctx, [(samples, rate)], args.rate)
+        d_pcm, sample_off = resample_batch(ctx, [(samples, rate)], args.rate, beamform=BEAMFORM if args.beamform else None)
         pcm = np.zeros(int(sample_off[-1]), dtype=np.int16)
         if pcm.size:
             ctx.d2h(pcm, d_pcm)

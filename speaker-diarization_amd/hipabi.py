@@ -17,7 +17,7 @@ MERGE_NO_AHEAD = 1
 TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pair_terms',
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
-                                        'post_stats', 'resample', 'frame_energy', 'energy_seeds',
+                                        'post_stats', 'bf_gcc', 'bf_track', 'bf_sum', 'resample', 'frame_energy', 'energy_seeds',
                                         'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
                                         'mindur_viterbi', 'mindur_backtrack', 'fb_posterior',
                                         'ident_scores', 'ident_assign', 'bw_accumulate',
@@ -45,6 +45,9 @@ RESAMPLE_MAX_HALF = 256     # SPKD_RESAMPLE_MAX_HALF: taps to either side of an 
 RESAMPLE_MAX_TERM = 1 << 20     # SPKD_RESAMPLE_MAX_TERM: up and down of a conversion
 RESAMPLE_MAX_TAPS = 1 << 22     # SPKD_RESAMPLE_MAX_TAPS: floats of one conversion's table
 RESAMPLE_MAX_SPAN = 33281   # SPKD_RESAMPLE_MAX_SPAN: input frames a tile may read
+BF_NFFT = 8192              # SPKD_BF_NFFT: the transform length of k_bf_gcc; window + max_lag of a geometry fit it
+BF_NBEST = 4                # SPKD_BF_NBEST: candidate lags kept per step and channel
+BF_MAX_HOP = 1 << 20        # SPKD_BF_MAX_HOP: the largest hop of a geometry
 ENERGY_MAX_WINDOW = 4096    # SPKD_ENERGY_MAX_WINDOW: samples of a frame of k_frame_energy (hop <= window)
 ENERGY_TILE = 16384         # SPKD_ENERGY_TILE: samples whose hops make the frames of a workgroup of k_frame_energy
 REC = 820
@@ -53,7 +56,7 @@ DIM = 39
 EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_destroy', 'spkd_last_error', 'spkd_sync',
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_last_ahc_head', 'spkd_ahc_head_rule', 'spkd_set_stats', 'spkd_pair_terms',
-           'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_sum_stats', 'spkd_mfcc', 'spkd_mfcc_batch', 'spkd_resample_batch',
+           'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_sum_stats', 'spkd_mfcc', 'spkd_mfcc_batch', 'spkd_resample_batch', 'spkd_bf_gcc', 'spkd_bf_track', 'spkd_bf_sum',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
@@ -95,6 +98,11 @@ class ResampleConv(C.Structure):
     """spkd_resample_conv: up / down of a conversion, the taps to either side of an output instant
     and where its table [up][2 half_taps] starts in the concatenated tables."""
     _fields_ = [('up', C.c_int32), ('down', C.c_int32), ('half_taps', C.c_int32), ('taps_off', C.c_int64)]
+
+
+class BfGeom(C.Structure):
+    """spkd_bf_geom: hop, window and largest lag of a beamforming geometry, in samples."""
+    _fields_ = [('hop', C.c_int32), ('window', C.c_int32), ('max_lag', C.c_int32)]
 
 
 class GmmParams(C.Structure):
@@ -224,6 +232,9 @@ def load_library(path=None):
     lib.spkd_mfcc.argtypes = [vp, vp, i64, P(MfccParams), vp, vp, vp, vp, vp, vp, P(i64)]
     lib.spkd_mfcc_batch.argtypes = [vp, vp, i64, vp, P(MfccParams), vp, vp, vp, vp, vp, vp, vp]
     lib.spkd_resample_batch.argtypes = [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.spkd_bf_gcc.argtypes = [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.spkd_bf_track.argtypes = [vp, i64, vp, vp, vp, vp, i32, C.c_float, dbl, i32, vp]
+    lib.spkd_bf_sum.argtypes = [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.spkd_frame_energy_batch.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
     lib.spkd_energy_seeds.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, P(vp), P(vp), P(vp)]
     lib.spkd_sw_window_count.argtypes = [i64, dbl, dbl]
@@ -793,6 +804,58 @@ class Context(object):
         self.check(self.lib.spkd_resample_batch(self.h, C.c_void_p(d_in), len(off) - 1, _ptr(off), _ptr(ch), _ptr(cv),
                                                 len(convs), table, _ptr(taps) if taps.size else None,
                                                 C.c_void_p(d_out), _ptr(out_off)))
+        return out_off
+
+    # ---- (6b2) delay-and-sum beamforming
+    @staticmethod
+    def _bf_files(in_off, channels, geom, geoms):
+        off = np.ascontiguousarray(in_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1:
+            raise SpkdError(SPKD_EINVAL, 'in_off: one entry per file and the total')
+        ch = np.ascontiguousarray(channels, dtype=np.int32)
+        gi = np.ascontiguousarray(geom, dtype=np.int32)
+        if ch.shape != (len(off) - 1,) or gi.shape != ch.shape:
+            raise SpkdError(SPKD_EINVAL, 'channels, geom: one entry per file')
+        table = (BfGeom * max(len(geoms), 1))(*[g if isinstance(g, BfGeom) else BfGeom(*[int(x) for x in g]) for g in geoms])
+        return off, ch, gi, table
+
+    def bf_gcc(self, d_in, in_off, channels, geom, geoms, ref, d_ref, d_lag, d_val, d_curve=None):
+        """GCC-PHAT candidates of every step and channel (spkd_bf_gcc): file f owns the elements
+        [in_off[f], in_off[f+1]) of d_in, has channels[f] channels, the geometry geoms[geom[f]] (BfGeom,
+        or (hop, window, max_lag)) and the reference channel ref[f] (-1: the loudest).  d_ref gets the
+        reference channel per file, d_lag / d_val the BF_NBEST candidates at 4 (wg_off[f] + t C + c),
+        wg_off the running sum of T C; d_curve, if given, every correlation value.  Returns (step_off,
+        curve_off), int64 with one entry per file and the total.  Time: last_ms('bf_gcc')."""
+        off, ch, gi, table = self._bf_files(in_off, channels, geom, geoms)
+        rf = np.ascontiguousarray(ref, dtype=np.int32)
+        if rf.shape != ch.shape:
+            raise SpkdError(SPKD_EINVAL, 'ref: one entry per file')
+        step_off = np.zeros(len(off), dtype=np.int64)
+        curve_off = np.zeros(len(off), dtype=np.int64)
+        self.check(self.lib.spkd_bf_gcc(self.h, C.c_void_p(d_in), len(off) - 1, _ptr(off), _ptr(ch), _ptr(gi), len(geoms), table,
+                                        _ptr(rf), C.c_void_p(d_ref), C.c_void_p(d_lag), C.c_void_p(d_val),
+                                        C.c_void_p(d_curve) if d_curve else None, _ptr(step_off), _ptr(curve_off)))
+        return step_off, curve_off
+
+    def bf_track(self, step_off, channels, d_lag, d_val, n_best, min_peak, jump_penalty, jump_cap, d_delay):
+        """One delay per step and channel from the candidates (spkd_bf_track): d_delay int32 at
+        wg_off[f] + t C + c.  Time: last_ms('bf_track')."""
+        off = np.ascontiguousarray(step_off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1:
+            raise SpkdError(SPKD_EINVAL, 'step_off: one entry per file and the total')
+        ch = np.ascontiguousarray(channels, dtype=np.int32)
+        if ch.shape != (len(off) - 1,):
+            raise SpkdError(SPKD_EINVAL, 'channels: one entry per file')
+        self.check(self.lib.spkd_bf_track(self.h, len(off) - 1, _ptr(off), _ptr(ch), C.c_void_p(d_lag), C.c_void_p(d_val),
+                                          int(n_best), float(min_peak), float(jump_penalty), int(jump_cap), C.c_void_p(d_delay)))
+
+    def bf_sum(self, d_in, in_off, channels, geom, geoms, d_delay, d_out):
+        """The channels summed at their delays (spkd_bf_sum) -> mono int16 at d_out, a file's n frames at
+        [out_off[f], out_off[f+1]).  Returns out_off.  Time: last_ms('bf_sum')."""
+        off, ch, gi, table = self._bf_files(in_off, channels, geom, geoms)
+        out_off = np.zeros(len(off), dtype=np.int64)
+        self.check(self.lib.spkd_bf_sum(self.h, C.c_void_p(d_in), len(off) - 1, _ptr(off), _ptr(ch), _ptr(gi), len(geoms), table,
+                                        C.c_void_p(d_delay), C.c_void_p(d_out), _ptr(out_off)))
         return out_off
 
     # ---- (6c) the seed stage of the self-trained detector

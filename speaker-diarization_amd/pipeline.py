@@ -152,17 +152,25 @@ def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=Non
     return diarize_batch(ctx, d_frames, total, files, rate=float(cfg.frame_rate), cd=cd, cl=cl, timings=timings, **kw)
 
 
-def diarize_audio_batch(ctx, model, cfg, audios, cd=DIA2_CD, cl=DIA2_CL, timings=None, group_bytes=None, **kw):
+# delay-and-sum beamforming in front of the resampler (frontend.BEAMFORM has the words on its defaults:
+# min_peak, jump_penalty and jump_cap are unmeasured on speech)
+BEAMFORM = frontend.BEAMFORM
+
+
+def diarize_audio_batch(ctx, model, cfg, audios, cd=DIA2_CD, cl=DIA2_CL, timings=None, group_bytes=None, beamform=None, **kw):
     """From recordings to speakers: audios = [(samples, rate)], int16 [n] or [n, channels] at any
     rate (frontend.read_audio), resampled and downmixed to cfg.sample_rate on the device
     (frontend.resample_batch; group_bytes: its bound on the raw audio held there), then exactly
     diarize_pcm_batch from its upload on (model: a VadModel, or a dictionary like SELF_VAD).
-    Returns its rows."""
+    beamform: None (the channels are averaged), or a dictionary like BEAMFORM (they are aligned by
+    GCC-PHAT delays and summed: frontend.resample_batch).  Returns its rows."""
     if isinstance(model, dict):
         _self_vad._options(model)
     else:
         _one_clock(model, cfg)
     group = {} if group_bytes is None else {'group_bytes': group_bytes}
+    if beamform is not None:
+        group['beamform'] = beamform
     uploaded = frontend.resample_batch(ctx, audios, cfg.sample_rate, timings=timings, **group)
     return diarize_pcm_batch(ctx, model, cfg, None, cd=cd, cl=cl, timings=timings, uploaded=uploaded, **kw)
 

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Resample and downmix one 16-bit PCM .wav to 16 kHz mono on the MI355X: the step the reference
 leaves to `ffmpeg -i x -ar 16000 -ac 1` (spk-diarization2.py:83), for .wav input of any rate and
-channel count.  ./to16k.py IN.wav [-o OUT.wav] [-r 16000].  Parity with ffmpeg's resampler is
-unpinned (speaker-diarization_amd/frontend.py, resample_taps)."""
+channel count.  ./to16k.py IN.wav [-o OUT.wav] [-r 16000] [--beamform].  Parity with ffmpeg's
+resampler is unpinned (speaker-diarization_amd/frontend.py, resample_taps).  --beamform aligns the
+channels of a microphone array by their GCC-PHAT delays before summing them, instead of averaging
+them (frontend.BEAMFORM; parity with any other beamformer is unpinned)."""
 import importlib
 import os
 import sys
