@@ -100,7 +100,7 @@ enum {
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
     SPKD_T_POST_STATS, SPKD_T_BF_GCC, SPKD_T_BF_TRACK, SPKD_T_BF_SUM, SPKD_T_RESAMPLE, SPKD_T_FRAME_ENERGY, SPKD_T_ENERGY_SEEDS,
-    SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
+    SPKD_T_FEATURE_WARP, SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
     SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK, SPKD_T_FB_POSTERIOR,
     SPKD_T_IDENT_SCORES, SPKD_T_IDENT_ASSIGN, SPKD_T_BW_ACCUMULATE,
     SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
@@ -1279,6 +1279,55 @@ spkd_status spkd_clr_link(spkd_ctx *ctx, const double *d_bw, int64_t n, const in
                           const double *d_ubm, int32_t n_comp, double relevance, double threshold,
                           int32_t max_spk, int32_t *h_merge_a, int32_t *h_merge_b, double *h_merge_d,
                           int32_t *h_n_merges, double *h_stat_max, double *h_stat_min);
+
+/* ---------------------------------------------------------------------------
+ * (10b) Feature warping (Pelecanos & Sridharan 2001) ahead of section 10: over a sliding window of a
+ * file's speech every coefficient is replaced by the standard-normal quantile of its rank in the
+ * window.  The result does not change under any increasing distortion of a dimension -- the gain and
+ * offset by which two microphones differ at the least, which the background model, the adapted means
+ * and the ratio of section 10 all take for a speaker difference -- and it is N(0, 1)-like, the regime
+ * section 10's accuracy note calls far inside.
+ * PARITY: no reference counterpart; tests/warp_numpy.py restates the rule frame by frame.
+ *
+ * The rule.
+ *   Sets and runs.  A set is one file's speech: the frame ranges [begin, end) h_set_off[s] ..
+ *     h_set_off[s + 1] of h_range_begin / h_range_end, ascending and disjoint over the whole list (a
+ *     range may be empty, two may touch, a set may have none).  Concatenated they are the set's
+ *     compacted axis j = 0 .. L - 1.
+ *   Window.  With n = min(window, L), frame j sees the compacted frames [lo, lo + n),
+ *     lo = clamp(j - n / 2, 0, L - n) (integer division).  The window slides inside the set: it never
+ *     crosses into another set and never sees a frame that lies in no range.
+ *   Counts.  Per dimension d, with v the frame's value: lt is the number of window values < v, eq the
+ *     number == v, as float32 compares.  The frame counts itself, so eq >= 1 unless v is a NaN, and
+ *     -0.0 == 0.0.
+ *   Output.  out = table_n[2 lt + eq - 1] with table_n[k - 1] = float32(Phi^-1(k / (2 n))) for
+ *     k = 1 .. 2 n - 1.  Without ties that is Pelecanos' (rank - 1/2) / n; with ties it is the
+ *     mid-rank, symmetric and independent of order.
+ *   NaN and infinities.  A NaN value gives the quiet NaN 0x7fc00000 and counts in nobody's lt or eq; n
+ *     stays what it is.  +-inf compare as usual.
+ *   Frames outside the ranges.  A frame of d_out that lies in no range is not written.
+ *
+ * spkd_feature_warp: d_frames and d_out hold n_frames frames of 39 floats.  The caller supplies the
+ *   quantile tables: set s, when it has a frame, reads the 2 n - 1 floats at h_table + h_table_off[s]
+ *   (sets of the same n share a table; the entry of a set without a frame is not looked at).  The
+ *   library computes no inverse CDF: device and restatement read the same bits.
+ *   One workgroup per tile of SPKD_WARP_TILE compacted frames of one set; the tile and its halo go
+ *   through the run table into LDS once, dimension-major, and the counts run from there.  Integer
+ *   counts and one look-up, no atomics: the bits depend neither on the run nor on the tiling nor on
+ *   the other sets of the call.  The tables go up in one copy through pinned memory the context owns.
+ *   SPKD_EINVAL before any device work, outputs untouched: a null pointer, n_frames or n_sets < 0,
+ *   window outside [1, SPKD_WARP_MAX_WINDOW = 512], offsets that do not start at 0 or that decrease, a
+ *   range outside [0, n_frames] or with end < begin, ranges that are not ascending and disjoint over
+ *   the whole list, a set of more than 2^31 - 1 frames, a table slice that does not lie in
+ *   [0, table_len], d_frames or d_out not 16-byte aligned, d_out overlapping d_frames (in place cannot
+ *   work: neighbours are read).  No frame in any range: SPKD_OK without a launch.
+ *   Timer: SPKD_T_FEATURE_WARP. */
+#define SPKD_WARP_MAX_WINDOW 512
+#define SPKD_WARP_TILE 384
+spkd_status spkd_feature_warp(spkd_ctx *ctx, const float *d_frames, int64_t n_frames, int64_t n_sets,
+                              const int64_t *h_set_off, const int64_t *h_range_begin,
+                              const int64_t *h_range_end, int32_t window, const float *h_table,
+                              int64_t table_len, const int64_t *h_table_off, float *d_out);
 
 /* ---------------------------------------------------------------------------
  * (11) A gallery of enrolled speakers: the records of section 10, kept from one batch to the next,

@@ -1,6 +1,7 @@
 """The settings of linking by cross-likelihood ratio and the training of its universal background model:
 LINK_CLR, the parser of a `link` dictionary's model keys (_link_model), the cut of the training frames
-(ubm_ranges) and the one spelling of the training call (train_ubm).  Both the gallery, which owns a
+(ubm_ranges) and the one spelling of the training call (train_ubm); LINK_CLR_WARP and the parser of the
+feature-warping key (warp_window).  Both the gallery, which owns a
 background model, and linking, which refuses what is not a gallery.Gallery, need these four: they live
 below both (this module imports hipabi only), linking offers them under its own name, pipeline under its."""
 import collections
@@ -17,6 +18,14 @@ from . import hipabi
 # threshold rests on ONE synthetic fixture (tests/test_link_clr.py), not on speech: tune it on real audio.
 LINK_CLR = dict(model='clr', components=8, iterations=5, var_floor=0.01, relevance=16.0,
                 threshold=-0.5, max_spk=0, ubm_max_frames=2_000_000)
+
+# LINK_CLR on warped features (spkd_feature_warp, include/spkd.h section 10b): over `warp_s` seconds of a file's
+# speech every coefficient becomes the standard-normal quantile of its rank, which takes a per-dimension gain
+# and offset -- another microphone -- out of the comparison.  Warped features compress the ratios, so the mode
+# has a threshold of its own: -0.1 is the middle of the window [-0.28, 0.08] in which the ONE synthetic
+# fixture (tests/test_feature_warp.py: the people of tests/test_link_clr.py, each file through a channel of
+# its own) is linked correctly.  It is unmeasured on speech: tune it on real audio.
+LINK_CLR_WARP = dict(LINK_CLR, warp_s=3.0, threshold=-0.1)
 
 _Bic = collections.namedtuple('_Bic', 'name')
 _Clr = collections.namedtuple('_Clr', 'name components iterations var_floor relevance threshold max_spk ubm_max_frames')
@@ -48,6 +57,27 @@ def _link_model(link):
     if int(cap) != cap or cap < (hipabi.DIM + 1) * k:
         raise ValueError('link ubm_max_frames: an integer >= 40 per component')
     return _Clr('clr', int(k), int(it), fl, r, th, int(ms), int(cap))
+
+
+def warp_window(link, rate):
+    """The feature-warping window of a `link` dictionary in frames: round(link['warp_s'] * rate), 0 where
+    the key is absent or 0.  Only model 'clr' takes the key."""
+    w = link.get('warp_s', 0.0)
+    try:
+        w = float(w)
+    except (TypeError, ValueError):
+        w = float('nan')
+    if not np.isfinite(w) or w < 0.0:
+        raise ValueError('link warp_s: a finite number >= 0 (seconds of speech; 0: no warping)')
+    if w == 0.0:
+        return 0
+    if link.get('model') != 'clr':
+        raise ValueError('link warp_s: only link model clr warps its features')
+    n = int(round(w * float(rate)))
+    if not 2 <= n <= hipabi.WARP_MAX_WINDOW:
+        raise ValueError('link warp_s: a window of 2 .. %d frames (%r s at %r frames a second are %d)'
+                         % (hipabi.WARP_MAX_WINDOW, w, rate, n))
+    return n
 
 
 def ubm_ranges(set_off, begin, end, cap):

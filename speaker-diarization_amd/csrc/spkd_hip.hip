@@ -34,6 +34,7 @@
 #include "spkd_gmm_train.hpp"
 #include "spkd_ubm_stats.hpp"
 #include "spkd_clr.hpp"
+#include "spkd_warp.hpp"
 #include "spkd_ident.hpp"
 
 using namespace spkd;
@@ -46,7 +47,7 @@ constexpr int N_SLOTS = 80;
 // never share a slot; nor do the block that goes up and the block that comes down in one call.
 enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
        PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, PIN_MD_SEQS, PIN_MD_TOKENS,
-       PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, PIN_POST_TAB, PIN_ES_FILES, PIN_ES_RUNS, N_PIN };
+       PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, PIN_POST_TAB, PIN_ES_FILES, PIN_ES_RUNS, PIN_WARP_TAB, N_PIN };
 }
 
 struct spkd_ctx {
@@ -56,6 +57,7 @@ struct spkd_ctx {
     bool gw_lds_ok = false;
     int rs_lds_cap = 0;          // dynamic LDS bytes admitted for k_resample
     bool bf_lds_ok = false;      // k_bf_gcc's dynamic LDS size is admitted
+    bool warp_lds_ok = false;    // k_feature_warp's dynamic LDS size is admitted
     bool bf_tw_ready = false;    // the transform's twiddles are in their scratch slot (S_BF_TW)
     int gw_waves = 0;
     unsigned long long init_keys[2] = {0ull, ~0ull};
@@ -362,7 +364,7 @@ enum {
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
     S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT,
     S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_FB_TAB, S_FB_FWD, S_FB_OUT,
-    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_BF_TAB, S_BF_TW, S_BF_ENERGY, S_BF_BACK, S_EN_TAB, S_ES_TAB, S_ES_FILES, S_ES_RUNS, S_COUNT
+    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_BF_TAB, S_BF_TW, S_BF_ENERGY, S_BF_BACK, S_EN_TAB, S_ES_TAB, S_ES_FILES, S_ES_RUNS, S_WARP_TAB, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -417,6 +419,8 @@ static spkd_status create_ctx(int device, void* stream, bool borrow, spkd_ctx** 
     }
     c->bf_lds_ok = BF_LDS_BYTES <= lds_max &&
                    hipFuncSetAttribute((const void*)k_bf_gcc, hipFuncAttributeMaxDynamicSharedMemorySize, BF_LDS_BYTES) == hipSuccess;
+    c->warp_lds_ok = (int)WP_LDS_MAX <= lds_max &&
+                     hipFuncSetAttribute((const void*)k_feature_warp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WP_LDS_MAX) == hipSuccess;
     // waves per turn of the growing-window kernel: 0 = by the number of turns (gw_impl)
     if (const char* e = getenv("SPKD_GW_WAVES")) c->gw_waves = atoi(e);
     if (const char* e = getenv("SPKD_STEP_WAVES")) { const int v = atoi(e); c->step_waves = (v == 4 || v == 8) ? v : 0; }
@@ -3570,6 +3574,104 @@ spkd_status spkd_clr_link(spkd_ctx* c, const double* d_bw, int64_t n, const int3
     *h_stat_max = out.h.stat[0];
     *h_stat_min = out.h.stat[1];
     return st;
+}
+
+// ------------------------------------------------------------------ (10b) feature warping
+static_assert(WP_MAX_WINDOW == SPKD_WARP_MAX_WINDOW && WP_TILE == SPKD_WARP_TILE, "the header states the limit and the tile");
+
+namespace {
+// The tables of spkd_feature_warp as the kernel takes them: per run its first frame and the compacted ordinal
+// of that frame within its set; per set its runs [set_off], its frame count and where its quantile table
+// starts; per tile its set and its index within the set; the caller's quantile tables.  A mirrored block.
+struct WarpTable {
+    struct Tab { long long *begin, *ord, *set_off, *len, *table_off; int *tile_set, *tile_idx; float* table; } h{}, d{};
+    Image host, dev;
+    size_t ns = 0, nr = 0, nt = 0, nq = 0;   // sets, runs, tiles, floats of the quantile tables
+    int n_max = 0;                           // the widest window of a set: min(window, its frames)
+
+    size_t parts(Layout L, Tab& t) const {
+        return L.part(t.begin, nr).part(t.ord, nr).part(t.set_off, ns + 1).part(t.len, ns).part(t.table_off, ns)
+            .part(t.tile_set, nt).part(t.tile_idx, nt).part(t.table, nq).bytes();
+    }
+    // the checks of the sets, the runs and the table slices, the tiles counted, the image filled
+    spkd_status build(spkd_ctx* c, int64_t n_frames, int64_t n_sets, const int64_t* h_set_off, const int64_t* h_range_begin,
+                      const int64_t* h_range_end, int32_t window, const float* h_table, int64_t table_len,
+                      const int64_t* h_table_off) {
+        if (h_set_off[0] != 0) return fail(c, SPKD_EINVAL, "feature_warp: set_off[0] must be 0");
+        for (int64_t s = 0; s < n_sets; ++s)
+            if (h_set_off[s + 1] < h_set_off[s]) return fail(c, SPKD_EINVAL, "feature_warp: set_off must not decrease");
+        int64_t n_tiles = 0, last_end = 0;
+        for (int64_t s = 0; s < n_sets; ++s) {
+            int64_t n = 0;
+            for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
+                const int64_t b = h_range_begin[r], e = h_range_end[r];
+                if (b < 0 || e < b || e > n_frames) return fail(c, SPKD_EINVAL, "feature_warp: range outside [0, n_frames]");
+                if (b < last_end) return fail(c, SPKD_EINVAL, "feature_warp: the ranges must be ascending and disjoint");
+                last_end = e;
+                n += e - b;                  // (disjoint ranges inside [0, n_frames]: no overflow)
+            }
+            if (n > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "feature_warp: a set of more than 2^31 - 1 frames");
+            if (n == 0) continue;
+            const int64_t w = n < window ? n : window, off = h_table_off[s];
+            if (off < 0 || off > table_len || 2 * w - 1 > table_len - off)
+                return fail(c, SPKD_EINVAL, "feature_warp: a table slice outside [0, table_len]");
+            if (w > n_max) n_max = (int)w;
+            n_tiles += (n + WP_TILE - 1) / WP_TILE;
+        }
+        if (n_tiles > 0x7fffffff) return fail(c, SPKD_EINVAL, "feature_warp: too many frames in one call");
+        ns = (size_t)n_sets, nr = (size_t)h_set_off[n_sets], nt = (size_t)n_tiles, nq = (size_t)table_len;
+        if (!nt) return SPKD_OK;
+        TRY(stage(c, PIN_WARP_TAB, *this));
+        std::memcpy(h.begin, h_range_begin, nr * sizeof(int64_t));
+        std::memcpy(h.set_off, h_set_off, (ns + 1) * sizeof(int64_t));
+        std::memcpy(h.table_off, h_table_off, ns * sizeof(int64_t));
+        std::memcpy(h.table, h_table, nq * sizeof(float));
+        size_t tile = 0;
+        for (size_t s = 0; s < ns; ++s) {
+            long long n = 0;
+            for (int64_t r = h_set_off[s]; r < h_set_off[s + 1]; ++r) {
+                h.ord[r] = n;
+                n += h_range_end[r] - h_range_begin[r];
+            }
+            h.len[s] = n;
+            for (long long i = 0; i < (n + WP_TILE - 1) / WP_TILE; ++i, ++tile) {
+                h.tile_set[tile] = (int)s;
+                h.tile_idx[tile] = (int)i;
+            }
+        }
+        return SPKD_OK;
+    }
+};
+}  // namespace
+
+spkd_status spkd_feature_warp(spkd_ctx* c, const float* d_frames, int64_t n_frames, int64_t n_sets, const int64_t* h_set_off,
+                              const int64_t* h_range_begin, const int64_t* h_range_end, int32_t window, const float* h_table,
+                              int64_t table_len, const int64_t* h_table_off, float* d_out) {
+    if (!c) return SPKD_EINVAL;
+    if (!d_frames || !h_set_off || !h_range_begin || !h_range_end || !h_table || !h_table_off || !d_out)
+        return fail(c, SPKD_EINVAL, "feature_warp: null argument");
+    if (n_frames < 0 || n_sets < 0 || n_sets > 0x7fffffff || table_len < 0) return fail(c, SPKD_EINVAL, "feature_warp: bad count");
+    if (window < 1 || window > WP_MAX_WINDOW) return fail(c, SPKD_EINVAL, "feature_warp: 1 <= window <= 512");
+    if ((uintptr_t)d_frames % 16 || (uintptr_t)d_out % 16) return fail(c, SPKD_EINVAL, "feature_warp: frames and output 16-byte aligned");
+    {
+        const uintptr_t a = (uintptr_t)d_frames, b = (uintptr_t)d_out, bytes = (uintptr_t)n_frames * D * sizeof(float);
+        if (a < b + bytes && b < a + bytes) return fail(c, SPKD_EINVAL, "feature_warp: the output overlaps the frames");
+    }
+    WarpTable t;
+    TRY(t.build(c, n_frames, n_sets, h_set_off, h_range_begin, h_range_end, window, h_table, table_len, h_table_off));
+    if (!t.nt) return SPKD_OK;
+    if (!c->warp_lds_ok) return fail(c, SPKD_EHIP, "feature_warp: the kernel's dynamic LDS size was not admitted on this device");
+    Call call(c);
+    TRY(call.opened);
+    TRY(send(call, S_WARP_TAB, t));
+    {
+        Timer tm(c, SPKD_T_FEATURE_WARP);
+        hipLaunchKernelGGL(k_feature_warp, dim3((unsigned)t.nt), dim3(WP_TPB), wp_lds_bytes(t.n_max), c->stream, d_frames,
+                           t.d.begin, t.d.ord, t.d.set_off, t.d.len, t.d.table_off, (const float*)t.d.table, t.d.tile_set,
+                           t.d.tile_idx, (int)window, t.n_max, d_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    return call.finish();
 }
 
 // ------------------------------------------------------------------ (11) a gallery of enrolled speakers

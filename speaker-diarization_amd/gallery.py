@@ -17,7 +17,7 @@ model) and hipabi; linking and pipeline stand on it.
 import numpy as np
 
 from . import hipabi
-from .clr_model import LINK_CLR, _link_model, train_ubm
+from .clr_model import LINK_CLR, _link_model, train_ubm, warp_window
 
 FORMAT_VERSION = 1
 _KEYS = ('version', 'components', 'relevance', 'threshold', 'ubm', 'records', 'ok', 'frames', 'names')
@@ -31,13 +31,16 @@ class Gallery(object):
     """State: the UBM (`ubm`, a host copy [components, GMM_COMP], and `d_ubm` on the device; None
     without a model), `components`, `relevance`, `threshold`, the records of the `n` identities in
     one device buffer `d_bw` that grows by doubling, and per identity `ok`, the frame total `N` (the
-    sum of n_c over what was added to it) and `names`.  ctx=None: a gallery of host arrays only
-    (to_arrays / from_arrays / save / load work, nothing that needs the device does)."""
+    sum of n_c over what was added to it) and `names`; `warp`, the feature-warping window in frames its
+    records were collected under (link['warp_s'] at `rate`; 0: none) -- records of warped and of plain
+    frames do not compare, so link_batch refuses a link of another window.  ctx=None: a gallery of host
+    arrays only (to_arrays / from_arrays / save / load work, nothing that needs the device does)."""
 
-    def __init__(self, ctx, link=None):
+    def __init__(self, ctx, link=None, rate=125.0):
         model = _link_model(LINK_CLR if link is None else link)
         if model.name != 'clr':
             raise ValueError('a gallery holds the records of link model clr')
+        self.warp = warp_window(LINK_CLR if link is None else link, rate)
         self.components, self.iterations, self.var_floor = model.components, model.iterations, model.var_floor
         self.relevance, self.threshold, self.ubm_max_frames = model.relevance, model.threshold, model.ubm_max_frames
         self.ctx = ctx
@@ -171,17 +174,19 @@ class Gallery(object):
 
     # ---- the host side
     def to_arrays(self):
-        """The gallery as a dictionary of numpy arrays (what save writes)."""
+        """The gallery as a dictionary of numpy arrays (what save writes).  `warp` is among them only when
+        the gallery has a window: one without saves to the keys and bytes it always had."""
+        warp = dict(warp=np.array(self.warp, dtype=np.int64)) if self.warp else {}
         return dict(version=np.array(FORMAT_VERSION, dtype=np.int64), components=np.array(self.components, dtype=np.int64),
                     relevance=np.array(self.relevance, dtype=np.float64), threshold=np.array(self.threshold, dtype=np.float64),
                     ubm=(np.zeros((0, hipabi.GMM_COMP)) if self.ubm is None else self.ubm.copy()),
                     records=self.records(), ok=self.ok.astype(np.int32), frames=self.N.astype(np.float64),
-                    names=np.array(self.names, dtype=np.str_).reshape(len(self.names)))
+                    names=np.array(self.names, dtype=np.str_).reshape(len(self.names)), **warp)
 
     @classmethod
     def from_arrays(cls, ctx, arrays):
         """A gallery from what to_arrays gave.  Another format version, a key that is missing, shapes
-        that disagree: ValueError."""
+        that disagree: ValueError.  No `warp` among them: a gallery without a window."""
         missing = [k for k in _KEYS if k not in arrays]
         if missing:
             raise ValueError('gallery: no %s' % ', '.join(missing))
@@ -192,6 +197,10 @@ class Gallery(object):
             raise ValueError('gallery: components, relevance and threshold are scalars')
         g = cls(ctx, dict(LINK_CLR, components=int(a['components']), relevance=float(a['relevance']),
                           threshold=float(a['threshold'])))
+        warp = np.asarray(arrays['warp']) if 'warp' in arrays else np.array(0)
+        if warp.shape != () or warp.dtype.kind not in 'iu' or not (warp == 0 or 2 <= warp <= hipabi.WARP_MAX_WINDOW):
+            raise ValueError('gallery: warp is a scalar, 0 or a window of 2 .. %d frames' % hipabi.WARP_MAX_WINDOW)
+        g.warp = int(warp)
         k, n = g.components, len(a['ok'])
         if a['records'].shape != (n, k, hipabi.BW_COMP) or a['ok'].shape != (n,) or a['frames'].shape != (n,) or \
                 a['names'].shape != (n,) or a['ubm'].shape not in ((0, hipabi.GMM_COMP), (k, hipabi.GMM_COMP)):

@@ -18,7 +18,7 @@ TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pai
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
                                         'post_stats', 'bf_gcc', 'bf_track', 'bf_sum', 'resample', 'frame_energy', 'energy_seeds',
-                                        'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
+                                        'feature_warp', 'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
                                         'mindur_viterbi', 'mindur_backtrack', 'fb_posterior',
                                         'ident_scores', 'ident_assign', 'bw_accumulate',
                                         'mfcc_static', 'mfcc_post'])}
@@ -50,6 +50,8 @@ BF_NBEST = 4                # SPKD_BF_NBEST: candidate lags kept per step and ch
 BF_MAX_HOP = 1 << 20        # SPKD_BF_MAX_HOP: the largest hop of a geometry
 ENERGY_MAX_WINDOW = 4096    # SPKD_ENERGY_MAX_WINDOW: samples of a frame of k_frame_energy (hop <= window)
 ENERGY_TILE = 16384         # SPKD_ENERGY_TILE: samples whose hops make the frames of a workgroup of k_frame_energy
+WARP_MAX_WINDOW = 512       # SPKD_WARP_MAX_WINDOW: the widest window of spkd_feature_warp, in frames
+WARP_TILE = 384             # SPKD_WARP_TILE: compacted frames per workgroup of k_feature_warp
 REC = 820
 DIM = 39
 
@@ -61,7 +63,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
            'spkd_gauss_models', 'spkd_gauss_loglik', 'spkd_gmm_train', 'spkd_gmm_loglik_seq',
-           'spkd_ubm_stats', 'spkd_clr_link', 'spkd_mindur_viterbi_batch', 'spkd_fb_posterior_batch',
+           'spkd_ubm_stats', 'spkd_clr_link', 'spkd_feature_warp', 'spkd_mindur_viterbi_batch', 'spkd_fb_posterior_batch',
            'spkd_clr_identify', 'spkd_bw_accumulate', 'spkd_post_stats', 'spkd_frame_energy_batch', 'spkd_energy_seeds']
 
 
@@ -266,6 +268,7 @@ def load_library(path=None):
     lib.spkd_gmm_loglik_seq.argtypes = [vp, vp, i64, vp, i32, i64, vp, i64, vp, vp, vp, vp, i32, vp]
     lib.spkd_ubm_stats.argtypes = [vp, vp, i64, vp, i32, i64, vp, vp, vp, vp, vp]
     lib.spkd_clr_link.argtypes = [vp, vp, i64, vp, vp, i32, dbl, dbl, i32, vp, vp, vp, vp, vp, vp]
+    lib.spkd_feature_warp.argtypes = [vp, vp, i64, i64, vp, vp, vp, i32, vp, i64, vp, vp]
     lib.spkd_clr_identify.argtypes = [vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, i32, dbl, dbl, i32, vp, vp, vp, vp]
     lib.spkd_bw_accumulate.argtypes = [vp, vp, i64, i32, i64, vp, vp, vp, vp, vp, i64]
     lib.spkd_gw_lines.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, dbl, C.c_int, i64, vp, vp, vp, vp, vp]
@@ -294,6 +297,19 @@ def py2_roundtrip(values):
     if v.size:
         load_library().spkd_py2_roundtrip(_ptr(v), v.size)
     return v
+
+
+def warp_table(n):
+    """The quantile table of a feature-warping window of n frames (include/spkd.h, section 10b): float32
+    [2 n - 1], entry k - 1 = Phi^-1(k / (2 n)) for k = 1 .. 2 n - 1, from statistics.NormalDist in fp64 and
+    rounded once.  The middle entry is exactly 0 and the table is antisymmetric about it."""
+    import statistics
+    n = int(n)
+    if n < 1:
+        raise SpkdError(SPKD_EINVAL, 'warp_table: a window of at least one frame')
+    inv = statistics.NormalDist().inv_cdf
+    lower = np.array([inv(k / (2.0 * n)) for k in range(1, n)], dtype=np.float64)       # (below 1/2, where k / (2 n) is exact enough)
+    return np.concatenate([lower, [0.0], -lower[::-1]]).astype(np.float32)
 
 
 def labels_from_merges(n, a, b):
@@ -1105,6 +1121,35 @@ class Context(object):
         self.check(self.lib.spkd_ubm_stats(self.h, C.c_void_p(d_frames), int(n_frames), C.c_void_p(d_ubm), int(n_comp),
                                            *sets, C.c_void_p(d_bw), _ptr(ok)))
         return ok
+
+    def feature_warp(self, d_frames, n_frames, set_off, range_begin, range_end, window, d_out):
+        """Feature warping of the frames at d_frames into d_out (spkd_feature_warp; the rule is
+        include/spkd.h, section 10b): set s -- one file's speech -- owns the frame ranges set_off[s] ..
+        set_off[s + 1] of range_begin / range_end, ascending and disjoint over the whole list; within a set
+        every coefficient becomes the standard-normal quantile of its rank among the `window` compacted
+        frames around it.  The quantile tables (warp_table) are built here, one per distinct
+        min(window, frames of a set), and kept by the context.  A frame in no range is not written.  The
+        kernel's time is last_ms('feature_warp')."""
+        n_sets, p_off, p_b, p_e = self._range_sets(set_off, range_begin, range_end)
+        off, b, e = (np.asarray(a, dtype=np.int64) for a in (set_off, range_begin, range_end))
+        length = np.zeros(n_sets, dtype=np.int64)
+        owner = np.repeat(np.arange(n_sets), np.maximum(np.diff(off), 0))
+        if len(owner) == len(b):                 # (offsets that go back: the library refuses them, no table is needed)
+            np.add.at(length, owner, e - b)
+        cache = self.__dict__.setdefault('_warp_tables', {})
+        table, at, table_off = [], {}, np.zeros(n_sets, dtype=np.int64)
+        for s, n in enumerate(np.clip(length, 0, max(int(window), 0)).tolist()):
+            if n < 1:
+                continue
+            if n not in at:
+                if n not in cache:
+                    cache[n] = warp_table(n)
+                at[n] = sum(len(t) for t in table)
+                table.append(cache[n])
+            table_off[s] = at[n]
+        table = np.ascontiguousarray(np.concatenate(table + [np.zeros(1, dtype=np.float32)]))
+        self.check(self.lib.spkd_feature_warp(self.h, C.c_void_p(d_frames), int(n_frames), n_sets, p_off, p_b, p_e, int(window),
+                                              _ptr(table), len(table), _ptr(table_off), C.c_void_p(d_out)))
 
     def clr_link(self, d_bw, ok, d_ubm, n_comp, relevance, threshold, max_spk=0):
         """The agglomerative chain over the len(ok) records at d_bw by cross-likelihood ratio under

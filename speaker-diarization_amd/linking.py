@@ -1,8 +1,8 @@
 """Linking the speakers of a batch's files (link_batch): which speaker of one file is which speaker of
 another, by BIC over the speakers' summed records (LINK_CL) or by cross-likelihood ratio under a universal
-background model (LINK_CLR), the latter optionally against a gallery of enrolled speakers.  A `link`
-dictionary is parsed once (_link_options); the two chains (_bic_chain, _clr_chain) hand link_batch the same
-six values.
+background model (LINK_CLR), the latter optionally on warped features (LINK_CLR_WARP) and against a gallery
+of enrolled speakers.  A `link` dictionary is parsed once (_link_options); the two chains (_bic_chain,
+_clr_chain) hand link_batch the same six values.
 Layers: tables (the speaker list, the segment ranges) and clr_model (LINK_CLR, _link_model, ubm_ranges,
 train_ubm -- the four pieces the gallery needs too, offered here under their names) lie below, gallery
 stands on clr_model, this module on all three, pipeline on this one.  clr_model is a file of its own
@@ -14,33 +14,37 @@ import contextlib
 import numpy as np
 
 from . import hipabi
-from .clr_model import LINK_CLR, _link_model, train_ubm, ubm_ranges
+from .clr_model import LINK_CLR, LINK_CLR_WARP, _link_model, train_ubm, ubm_ranges, warp_window
 from .gallery import Gallery
 from .tables import _ahc_params, _segment_ranges, link_speakers
 
 # linking the speakers of a batch's files (link_batch): the clustering script's own defaults
 LINK_CL = dict(variant=1, kind='BIC', lambdac=1.3, threshold=0.0, max_spk=0)
 
-_Options = collections.namedtuple('_Options', 'model gallery enrol exclusive')
+_Options = collections.namedtuple('_Options', 'model gallery enrol exclusive warp')
 
 
-def _link_options(link):
+def _link_options(link, rate=125.0):
     """A `link` dictionary parsed once: model is _link_model's tuple, whose refusals come first, in its
-    order; then the gallery keys, which only model 'clr' takes: gallery (None without one), enrol and
+    order; then warp, the feature-warping window in frames at `rate` (clr_model.warp_window; 0: none);
+    then the gallery keys, which only model 'clr' takes: gallery (None without one), enrol and
     exclusive (both True where absent, False without a gallery)."""
     model = _link_model(link)
+    warp = warp_window(link, rate)
     gal = link.get('gallery')
     if model.name != 'clr' and gal is not None:
         raise ValueError('link gallery: a gallery holds the records of link model clr')
     if gal is None:
-        return _Options(model, None, False, False)
+        return _Options(model, None, False, False, warp)
     if not isinstance(gal, Gallery):
         raise ValueError('link gallery: a gallery.Gallery')
     if gal.components != model.components:
         raise ValueError('link components: the gallery has %d' % gal.components)
     if gal.relevance != model.relevance:
         raise ValueError('link relevance: the gallery has %r' % gal.relevance)
-    return _Options(model, gal, bool(link.get('enrol', True)), bool(link.get('exclusive', True)))
+    if gal.warp != warp:
+        raise ValueError('link warp_s: the gallery has a window of %d frames, the link one of %d' % (gal.warp, warp))
+    return _Options(model, gal, bool(link.get('enrol', True)), bool(link.get('exclusive', True)), warp)
 
 
 @contextlib.contextmanager
@@ -58,6 +62,39 @@ def _finite(r):
     """After a chain's call (result r): the reference's error for values that are not finite."""
     if r['status'] == hipabi.SPKD_ENONFINITE:
         raise ValueError('array must not contain infs or NaNs')
+
+
+def speech_runs(seg_off, begin, end):
+    """The speech of every file as feature warping takes it (include/spkd.h, section 10b): a file's
+    segment ranges (seg_off: the files' offsets among begin / end) sorted by their first frame, the
+    overlapping and the touching ones merged into runs, an empty range dropped; the files in the order of
+    their first run, so that the runs ascend over the whole list -> (set_off, run_begin, run_end), a set
+    per file that has a frame.  Host-side numpy; the one place this is stated."""
+    sets = []
+    for f in range(len(seg_off) - 1):
+        b, e = (np.asarray(a[seg_off[f]:seg_off[f + 1]], dtype=np.int64) for a in (begin, end))
+        keep = e > b
+        order = np.argsort(b[keep], kind='stable')
+        b, e = b[keep][order], np.maximum.accumulate(e[keep][order])
+        if len(b):
+            first = np.concatenate([[True], b[1:] > e[:-1]])             # a range that starts past all before it
+            sets.append((b[first], e[np.concatenate([first[1:], [True]])]))
+    sets.sort(key=lambda be: int(be[0][0]))
+    set_off = np.concatenate([[0], np.cumsum([len(b) for b, _ in sets])]).astype(np.int64)
+    cat = lambda k: np.concatenate([be[k] for be in sets] + [np.zeros(0, dtype=np.int64)])
+    return set_off, cat(0), cat(1)
+
+
+def warp_frames(ctx, d_frames, total_frames, seg_off, begin, end, window, d_out=None):
+    """The frames of the segments begin / end, warped file by file over `window` frames (speech_runs,
+    spkd_feature_warp), into d_out -- None: the context's buffer 'link_warped', one more copy of the
+    frames -> the device pointer.  A frame of no segment is not written."""
+    if d_out is None:
+        d_out = ctx.dev_scratch('link_warped', max(int(total_frames), 1) * hipabi.DIM * 4)
+    set_off, run_b, run_e = speech_runs(seg_off, begin, end)
+    with _einval_is_value_error():
+        ctx.feature_warp(d_frames, total_frames, set_off, run_b, run_e, window, d_out)
+    return d_out
 
 
 def _bic_chain(ctx, link, d_stats, n_segments, member, set_off, clock):
@@ -168,6 +205,13 @@ def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None, d_fram
     frames) every speaker keeps a global label of its own and merges = [].  More than 4 096 speakers,
     a key out of range, a missing array: ValueError.  timings: link_ubm_train, link_ubm_stats,
     link_clr (kernel ms), link_speakers, link_merges.
+    link['warp_s'] (LINK_CLR_WARP; model 'clr' only): the frames are feature-warped first, file by file
+    over round(warp_s * rate) frames of the file's speech -- its segment ranges, sorted and merged into
+    runs (speech_runs) -- by spkd_feature_warp; the background model, the statistics and a gallery's
+    training then read the warped frames.  They are written to a buffer the context keeps
+    ('link_warped'): device memory for one more copy of the frames, total_frames * 156 bytes.  A window
+    outside [2, 512] frames: ValueError.  With a gallery the window must be the gallery's.  timings gain
+    link_warp (kernel ms).  LINK_CLR_WARP's threshold, like LINK_CLR's, rests on a synthetic fixture.
     A link dictionary of model 'clr' may carry gallery=<gallery.Gallery>, enrol (default True) and
     exclusive (default True); the global labels then mean the same person in every batch.  The
     gallery's model is the background model: it is trained on this batch, as above, only when the
@@ -187,7 +231,7 @@ def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None, d_fram
     ms) and link_update.  When no background model can be trained the fallback is the one above and
     the gallery is unchanged.  The identification threshold, like LINK_CLR's, rests on a synthetic
     fixture and not on speech."""
-    opts = _link_options(link)
+    opts = _link_options(link, rate)
     clr = opts.model.name == 'clr'
     if clr:
         if d_frames is None or total_frames is None or files is None or segments is None:
@@ -210,6 +254,9 @@ def link_batch(ctx, d_stats, seg_off, labels, link=LINK_CL, timings=None, d_fram
             timings.setdefault(key, []).append(sum((ctx.last_ms(w) for w in which), 0.0))
 
     kept = {}
+    if clr and opts.warp:
+        d_frames = warp_frames(ctx, d_frames, total_frames, seg_off_s, seg_b, seg_e, opts.warp)
+        clock('link_warp', 'feature_warp')
     if clr:
         chain = _clr_chain(ctx, opts, set_off, seg_b[member], seg_e[member], d_frames, total_frames, clock, kept)
     else:

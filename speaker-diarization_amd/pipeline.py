@@ -21,7 +21,7 @@ from . import resegmentation as _resegmentation
 from . import self_vad as _self_vad
 from .recipe import py2_float_str
 # the linking stage (linking.py, on clr_model.py and gallery.py): its settings and its entry point under their names here
-from .linking import LINK_CL, LINK_CLR, _link_model, link_batch, ubm_ranges
+from .linking import LINK_CL, LINK_CLR, LINK_CLR_WARP, _link_model, link_batch, ubm_ranges
 # the resegmentation stage (resegmentation.py): its settings and its entry point under their names here
 from .resegmentation import (FB_MAX_SCALED_PENALTY, RESEG, RESEG_CONF, RESEG_GMM, RESEG_MAX_SPEAKERS, RESEG_MD,
                              RESEG_SOFT, RESEG_SOFT_SCALE, resegment_batch)
@@ -605,7 +605,9 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     links by cross-likelihood ratio (link_batch, model 'clr'): the frames and the clustering segments
     are passed through to it.  Such a dictionary may carry gallery=<gallery.Gallery>, enrol and
     exclusive (link_batch): the third column then holds identities of the gallery + 1, the same
-    person in every batch, and detail['link'] gains identity, score, second and enrolled.
+    person in every batch, and detail['link'] gains identity, score, second and enrolled.  A
+    dictionary like LINK_CLR_WARP feature-warps the frames first (link['warp_s'], link_batch; warp_batch
+    is that stage on its own).
     reseg: a dictionary like RESEG; the rows are then those of resegment_batch on the records and
     labels clustering left: every turn decoded frame by frame under the file's speaker models, so
     the boundaries sit where the evidence changes instead of on the detector's candidate grid.
@@ -634,7 +636,7 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
             raise ValueError('cd method %s takes the host hand-off and is not fused' % _cd_method(cd))
         handoff = 'host'
     if link is not None:
-        _linking._link_options(link)                 # (its refusals come before any work; link_batch parses for itself)
+        _linking._link_options(link, rate)           # (its refusals come before any work; link_batch parses for itself)
         if device:
             raise ValueError('link takes the host hand-off')
     if handoff is None:
@@ -659,6 +661,24 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
         return [np.zeros((0, 3)) for _ in files]
     return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail, reseg,
                               text_contract)
+
+
+def warp_batch(ctx, d_frames, total_frames, files, segments, rate, warp_s, d_out=None):
+    """Feature warping on its own (spkd_feature_warp; include/spkd.h, section 10b): the frames of every
+    file's segments (one array of (start_s, end_s) per file, cut into frame ranges as the clustering
+    stage cuts them), each coefficient replaced by the standard-normal quantile of its rank among the
+    round(warp_s * rate) frames of the file's speech around it -- what link_batch does first under
+    LINK_CLR_WARP.  Into d_out (total_frames * 39 floats, not d_frames; a frame of no segment is not
+    written), or, d_out=None, into a buffer the context keeps until the next call.  Returns the device
+    pointer.  A window outside [2, 512] frames, warp_s = 0: ValueError.  The kernel's time is
+    ctx.last_ms('feature_warp')."""
+    window = _linking.warp_window(dict(model='clr', warp_s=warp_s), rate)
+    if not window:
+        raise ValueError('link warp_s: warp_batch takes a window')
+    if len(segments) != len(files):
+        raise ValueError('one segment array per file')
+    seg_off, _, seg_b, seg_e = _segment_ranges(files, segments, float(rate))
+    return _linking.warp_frames(ctx, d_frames, total_frames, seg_off, seg_b, seg_e, window, d_out)
 
 
 def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link=None, detail=None,
