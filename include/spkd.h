@@ -100,7 +100,8 @@ enum {
     SPKD_T_CLUSTER_PREP, SPKD_T_MATRIX, SPKD_T_AHC, SPKD_T_GW, SPKD_T_SW, SPKD_T_MERGE,
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
     SPKD_T_POST_STATS, SPKD_T_BF_GCC, SPKD_T_BF_TRACK, SPKD_T_BF_SUM, SPKD_T_RESAMPLE, SPKD_T_FRAME_ENERGY, SPKD_T_ENERGY_SEEDS,
-    SPKD_T_FEATURE_WARP, SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
+    SPKD_T_FEATURE_WARP, SPKD_T_TDOA_PACK, SPKD_T_TDOA_STATS, SPKD_T_TDOA_MODELS, SPKD_T_TDOA_SCORE,
+    SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
     SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK, SPKD_T_FB_POSTERIOR,
     SPKD_T_IDENT_SCORES, SPKD_T_IDENT_ASSIGN, SPKD_T_BW_ACCUMULATE,
     SPKD_T_MFCC_STATIC, SPKD_T_MFCC_POST,
@@ -810,6 +811,92 @@ spkd_status spkd_bf_sum(spkd_ctx *ctx, const int16_t *d_in, int64_t n_files,
                         const int32_t *h_geom /* [n_files] -> h_geoms */, int32_t n_geom,
                         const spkd_bf_geom *h_geoms, const int32_t *d_delay,
                         int16_t *d_out, int64_t *h_out_off /* out [n_files + 1] */);
+
+/* ---------------------------------------------------------------------------
+ * (6b3) The delay stream: the per-step delays of spkd_bf_track, kept for a whole batch, as a second
+ * feature stream of the resegmentation stage (section 8).  A delay is where the talker sits; the
+ * stream's statistics are integers and exact, its models one Gaussian per (speaker, channel), and
+ * their weighted log-likelihood is added to the score matrix every decoder of section 8 reads.
+ * PARITY: no reference counterpart; tests/tdoa_numpy.py restates every rule.
+ *
+ * The stream.  One device array of int32.  File f owns the entries [off_f, off_f + T_f C_f); entry
+ *   off_f + t C_f + c is the tracked delay of step t on channel c, in input samples, |delay| <=
+ *   SPKD_TDOA_MAX_DELAY, or SPKD_TDOA_NONE where the step is not reliable on that channel (the first
+ *   candidate's value below min_peak, both float32).  A one-channel file has T = 0.
+ * The file table.  SPKD_TDOA_FILE int64 per file, on the host: off (entries before the file), T, C,
+ *   the reference channel, H (the step, in input samples), the input rate, the file's first frame in
+ *   the batch's frame numbering, 0.
+ * The step rule.  With hop and window the feature configuration's, in samples at rate_out, frame t
+ *   of file f (file-local) belongs to the step
+ *       min(T_f - 1, ((t * hop + window / 2) * rate_in_f) / (rate_out * H_f)),
+ *   in 64-bit integers with truncating division: the step whose first sample is the last at or
+ *   before the centre of the frame's window.  Stated once, in csrc/spkd_tdoa.hpp (tdoa_step), for the
+ *   host tables and the kernels.  The bound: (t * hop + window / 2) * rate_in < 2^63 for every frame
+ *   handed in, and T * rate_out * H < 2^63; a call that would pass either is refused.  A step is at
+ *   least a frame long (H * rate_out >= hop * rate_in), so consecutive frames differ by at most one
+ *   step; a file that breaks this is refused.
+ *
+ * spkd_tdoa_pack: d_out[i] = d_val[4 i] >= min_peak ? d_delay[i] : SPKD_TDOA_NONE for i < n; d_delay
+ *   and d_val as spkd_bf_track read and wrote them, d_out the place of these entries in the stream.
+ *   One lane per entry.  Refusals: n < 0, a min_peak that is not a number, a null or misaligned
+ *   device pointer when n > 0.  Timer: SPKD_T_TDOA_PACK.
+ * spkd_tdoa_stats: frame ranges [begin, end) in the batch's numbering, each with its file and its set,
+ *   the sets ascending (what spkd_set_stats takes, and the file).  d_stats int64 [n_sets][8][3]:
+ *   per channel (n, sum x, sum x^2) over the frames of the set's ranges whose step is reliable there;
+ *   the reference channel and channels >= C stay 0, as do one-channel files.  The work is per step:
+ *   the frames of a range in a step are one interval, whose length weighs the step; sums in the wave
+ *   and in LDS, then one 64-bit integer atomic add per (set, channel, moment) and workgroup: exact,
+ *   and the same bits in every run.  |x| <= 4096 keeps sum x^2 inside int64 for any n < 2^39; a set
+ *   whose ranges hold 2^31 frames or more is refused.  A range may run past the file's last step
+ *   (the clamp).  Refusals (SPKD_EINVAL before any device work): a bad file table (above), sets that
+ *   descend or lie outside [0, n_sets), a file index out of range, a range that starts before its
+ *   file's first frame or ends before it starts, null arrays.  Timer: SPKD_T_TDOA_STATS.
+ * spkd_tdoa_models: per (speaker, channel) of d_stats: ok_c = n >= min_frames, mean = (double)sum x /
+ *   (double)n, var = max((double)sum x^2 / (double)n - mean * mean, floor_f) with floor_f = (floor_s *
+ *   rate_in)^2, every operation rounded on its own (no contraction).  d_models double
+ *   [n_speakers][8][SPKD_TDOA_MODEL]: mean, var, 1 / (2 var), -1/2 log(2 pi var); a (speaker, channel)
+ *   that is not ok_c, the reference channel and channels >= C hold (0, floor_f, 0, 0), which adds 0
+ *   to a score.  h_spk_file: the file of every speaker, ascending; h_ok: the speakers' acoustic
+ *   models.  A channel is live in a file iff it is ok_c for every speaker of the file whose h_ok is
+ *   not 0; h_live [n_files] receives the bit mask (bit c: channel c), 0 for a one-channel file.
+ *   Refusals: min_frames < 1, a floor_s that is not a finite number > 0, speakers' files that
+ *   descend or lie outside [0, n_files), a bad file table, null arrays.  Timer: SPKD_T_TDOA_MODELS.
+ * spkd_tdoa_score: the sequences and d_scores [sum len, n_cols] as spkd_gauss_loglik left them, each
+ *   sequence with its file.  For every frame of every sequence and every column j < its model count
+ *       scores[frame, j] = (float)((double)scores[frame, j] + weight * ll),
+ *       ll = sum over c live in the file and reliable at step(frame), ascending, of
+ *            -1/2 log(2 pi var) - (x - mean)^2 * (1 / (2 var)),
+ *   in fp64, each operation rounded on its own.  An entry that is not finite (-inf, NaN) and the
+ *   columns past the model count keep their bits; a file without a live channel and a one-channel
+ *   file are not touched.  One workgroup per tile of SPKD_TDOA_TILE frames of a sequence: the tile's
+ *   steps and the sequence's models go into LDS once, the entries are read and written in 16-byte
+ *   pieces between the tile's first and last 16-byte border.  Refusals: n_cols outside [1, 16], a
+ *   weight that is not finite and >= 0, a sequence's models outside [0, n_models) or more than n_cols,
+ *   a live channel its file does not have, those of spkd_tdoa_stats on files and ranges.
+ *   Timer: SPKD_T_TDOA_SCORE. */
+#define SPKD_TDOA_NONE INT32_MIN
+#define SPKD_TDOA_MAX_CH 8
+#define SPKD_TDOA_MAX_DELAY 4096
+#define SPKD_TDOA_FILE 8
+#define SPKD_TDOA_MODEL 4
+#define SPKD_TDOA_TILE 256
+spkd_status spkd_tdoa_pack(spkd_ctx *ctx, const int32_t *d_delay, const float *d_val, float min_peak, int64_t n,
+                           int32_t *d_out);
+spkd_status spkd_tdoa_stats(spkd_ctx *ctx, const int32_t *d_stream, int64_t n_entries,
+                            const int64_t *h_files /* [n_files][SPKD_TDOA_FILE] */, int64_t n_files,
+                            int32_t hop, int32_t window, int32_t rate_out,
+                            const int64_t *h_begin, const int64_t *h_end, const int32_t *h_file,
+                            const int32_t *h_set, int64_t n_ranges, int64_t n_sets, int64_t *d_stats);
+spkd_status spkd_tdoa_models(spkd_ctx *ctx, const int64_t *d_stats, int64_t n_speakers,
+                             const int32_t *h_spk_file, const int32_t *h_ok, const int64_t *h_files,
+                             int64_t n_files, int32_t min_frames, double floor_s, double *d_models,
+                             int32_t *h_live /* out [n_files] */);
+spkd_status spkd_tdoa_score(spkd_ctx *ctx, const int32_t *d_stream, int64_t n_entries,
+                            const int64_t *h_files, int64_t n_files, int32_t hop, int32_t window,
+                            int32_t rate_out, const double *d_models, int64_t n_models,
+                            const int32_t *h_live, int64_t n_seq, const int64_t *h_seq_begin,
+                            const int64_t *h_seq_end, const int32_t *h_seq_file, const int32_t *h_seq_model,
+                            const int32_t *h_seq_n_models, int32_t n_cols, double weight, float *d_scores);
 
 /* ---------------------------------------------------------------------------
  * (6c) The seed stage of a speech / non-speech detector trained on the recording itself: frame

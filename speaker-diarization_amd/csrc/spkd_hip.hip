@@ -25,6 +25,7 @@
 #include "spkd_mfcc_batch.hpp"
 #include "spkd_resample.hpp"
 #include "spkd_beamform.hpp"
+#include "spkd_tdoa.hpp"
 #include "spkd_energy.hpp"
 #include "spkd_vad.hpp"
 #include "spkd_vad_batch.hpp"
@@ -47,7 +48,7 @@ constexpr int N_SLOTS = 80;
 // never share a slot; nor do the block that goes up and the block that comes down in one call.
 enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
        PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, PIN_MD_SEQS, PIN_MD_TOKENS,
-       PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, PIN_POST_TAB, PIN_ES_FILES, PIN_ES_RUNS, PIN_WARP_TAB, N_PIN };
+       PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, PIN_POST_TAB, PIN_ES_FILES, PIN_ES_RUNS, PIN_WARP_TAB, PIN_TD_TAB, N_PIN };
 }
 
 struct spkd_ctx {
@@ -269,6 +270,7 @@ struct Call {
         for (int i = 1; i < SPKD_N_TIMERS; ++i)
             if (c->kused[i]) HIPCHK(c, hipEventElapsedTime(&c->kms[i], c->ka[i], c->kb[i]));
         if (herr & ERR_SWEEP) return fail(c, SPKD_EHIP, "internal error: growing-window sweep order");
+        if (herr & ERR_TDOA_STEPS) return fail(c, SPKD_EHIP, "internal error: tdoa_score met a step shorter than a frame");
         if (herr & 4) return fail(c, SPKD_EOVERFLOW, "device scratch capacity exceeded");
         if (herr & ERR_DEGENERATE_MERGE) return fail(c, SPKD_EINVAL, "degenerate merge: a diagonal cell was the minimum");
         if (herr & ERR_NONFINITE) return fail(c, SPKD_ENONFINITE, "array must not contain infs or NaNs");
@@ -364,7 +366,7 @@ enum {
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
     S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT,
     S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_FB_TAB, S_FB_FWD, S_FB_OUT,
-    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_BF_TAB, S_BF_TW, S_BF_ENERGY, S_BF_BACK, S_EN_TAB, S_ES_TAB, S_ES_FILES, S_ES_RUNS, S_WARP_TAB, S_COUNT
+    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_BF_TAB, S_BF_TW, S_BF_ENERGY, S_BF_BACK, S_EN_TAB, S_ES_TAB, S_ES_FILES, S_ES_RUNS, S_WARP_TAB, S_TD_TAB, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -2566,6 +2568,248 @@ spkd_status spkd_bf_sum(spkd_ctx* c, const int16_t* d_in, int64_t n_files, const
                            (long long)n_files, (const int*)d_ch, (const int*)d_geom, (const BfGeom*)d_geoms, d_delay, d_out);
     }
     if (hipGetLastError() != hipSuccess) return fail(c, SPKD_EHIP, "bf_sum: kernel launch failed");
+    return call.finish();
+}
+
+// ------------------------------------------------------------------ (6b3) the delay stream
+static_assert(TD_NONE == SPKD_TDOA_NONE && TD_MAX_CH == SPKD_TDOA_MAX_CH && TD_MAX_DELAY == SPKD_TDOA_MAX_DELAY &&
+              TD_FILE == SPKD_TDOA_FILE && TD_MODEL == SPKD_TDOA_MODEL && TD_TPB == SPKD_TDOA_TILE,
+              "the header states the stream's layouts and the kernels' tile");
+
+namespace {
+// the clock and the per-file table of the three calls that read the stream (`name` opens the messages)
+spkd_status tdoa_files(spkd_ctx* c, const std::string& name, const int64_t* h_files, int64_t n_files, int64_t n_entries,
+                       int32_t hop, int32_t window, int32_t rate_out, TdoaClock* K) {
+    if (n_files < 0 || n_files > 0x7fffffff || n_entries < 0) return fail(c, SPKD_EINVAL, name + ": bad count");
+    if (n_files > 0 && !h_files) return fail(c, SPKD_EINVAL, name + ": null file table");
+    if (hop < 1 || window < 0 || rate_out < 1) return fail(c, SPKD_EINVAL, name + ": hop >= 1, window >= 0 and rate_out >= 1 required");
+    *K = TdoaClock{hop, window, rate_out};
+    for (int64_t f = 0; f < n_files; ++f) {
+        const int64_t* F = h_files + f * TD_FILE;
+        const int64_t off = F[TDF_OFF], T = F[TDF_T], C = F[TDF_C], ref = F[TDF_REF], H = F[TDF_H], rate = F[TDF_RATE];
+        if (C < 1 || C > TD_MAX_CH) return fail(c, SPKD_EINVAL, name + ": 1 to 8 channels a file");
+        if (off < 0 || off > n_entries || T < 0 || T > (n_entries - off) / C)
+            return fail(c, SPKD_EINVAL, name + ": a file's entries lie outside the stream");
+        if (C > 1 && (ref < 0 || ref >= C)) return fail(c, SPKD_EINVAL, name + ": reference channel out of range");
+        if (H < 1 || H > SPKD_BF_MAX_HOP || rate < 1 || rate > 0x7fffffff)
+            return fail(c, SPKD_EINVAL, name + ": step or input rate out of range");
+        if (F[TDF_FRAME0] < 0) return fail(c, SPKD_EINVAL, name + ": negative first frame");
+        if (C > 1 && H * rate_out < (int64_t)hop * rate) return fail(c, SPKD_EINVAL, name + ": a step shorter than a frame");
+        if (T > tdoa_step_limit(*K, H)) return fail(c, SPKD_EINVAL, name + ": too many steps for 64-bit sample positions");
+    }
+    return SPKD_OK;
+}
+
+// a frame range [b, e) of the batch in file f: inside the rule's 64-bit bound
+spkd_status tdoa_range(spkd_ctx* c, const std::string& name, const int64_t* h_files, int64_t n_files, const TdoaClock& K,
+                       int64_t f, int64_t b, int64_t e) {
+    if (f < 0 || f >= n_files) return fail(c, SPKD_EINVAL, name + ": file index out of range");
+    const int64_t* F = h_files + f * TD_FILE;
+    if (b < F[TDF_FRAME0] || e < b) return fail(c, SPKD_EINVAL, name + ": bad frame range");
+    if (e - F[TDF_FRAME0] > tdoa_frame_limit(K, F[TDF_RATE]))
+        return fail(c, SPKD_EINVAL, name + ": frame beyond 64-bit sample positions");
+    return SPKD_OK;
+}
+}  // namespace
+
+spkd_status spkd_tdoa_pack(spkd_ctx* c, const int32_t* d_delay, const float* d_val, float min_peak, int64_t n, int32_t* d_out) {
+    if (!c || n < 0) return SPKD_EINVAL;
+    if (min_peak != min_peak) return fail(c, SPKD_EINVAL, "tdoa_pack: min_peak is not a number");
+    if (n == 0) return SPKD_OK;
+    if (!d_delay || !d_val || !d_out) return fail(c, SPKD_EINVAL, "tdoa_pack: null device buffer");
+    if ((uintptr_t)d_delay % 4 || (uintptr_t)d_val % 4 || (uintptr_t)d_out % 4) return fail(c, SPKD_EINVAL, "tdoa_pack: misaligned buffer");
+    const int64_t blocks = (n + TD_TPB - 1) / TD_TPB;
+    if (blocks > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_pack: too many entries in one call");
+    Call call(c);
+    TRY(call.opened);
+    {
+        Timer tm(c, SPKD_T_TDOA_PACK);
+        hipLaunchKernelGGL(k_tdoa_pack, dim3((unsigned)blocks), dim3(TD_TPB), 0, c->stream, d_delay, d_val, min_peak, (long long)n, d_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    return call.finish();
+}
+
+spkd_status spkd_tdoa_stats(spkd_ctx* c, const int32_t* d_stream, int64_t n_entries, const int64_t* h_files, int64_t n_files,
+                            int32_t hop, int32_t window, int32_t rate_out, const int64_t* h_begin, const int64_t* h_end,
+                            const int32_t* h_file, const int32_t* h_set, int64_t n_ranges, int64_t n_sets, int64_t* d_stats) {
+    if (!c || n_ranges < 0 || n_sets < 0) return SPKD_EINVAL;
+    TdoaClock K;
+    TRY(tdoa_files(c, "tdoa_stats", h_files, n_files, n_entries, hop, window, rate_out, &K));
+    if (n_sets > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_stats: too many sets");
+    if (n_ranges > 0 && (!h_begin || !h_end || !h_file || !h_set)) return fail(c, SPKD_EINVAL, "tdoa_stats: null range arrays");
+    if (n_sets == 0 && n_ranges == 0) return SPKD_OK;
+    if (!d_stats || (uintptr_t)d_stats % 8) return fail(c, SPKD_EINVAL, "tdoa_stats: null or misaligned statistics");
+    int64_t n_items = 0, frames = 0;
+    for (int64_t r = 0; r < n_ranges; ++r) {
+        if (h_set[r] < 0 || h_set[r] >= n_sets || (r > 0 && h_set[r] < h_set[r - 1]))
+            return fail(c, SPKD_EINVAL, "tdoa_stats: set indices ascending and inside [0, n_sets)");
+        TRY(tdoa_range(c, "tdoa_stats", h_files, n_files, K, h_file[r], h_begin[r], h_end[r]));
+        if (r > 0 && h_set[r] != h_set[r - 1]) frames = 0;
+        frames += h_end[r] - h_begin[r];
+        if (frames > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "tdoa_stats: a set of 2^31 frames or more");
+        const int64_t* F = h_files + (int64_t)h_file[r] * TD_FILE;
+        if (h_end[r] == h_begin[r] || F[TDF_C] < 2 || F[TDF_T] < 1) continue;
+        const int64_t s0 = tdoa_step(h_begin[r] - F[TDF_FRAME0], K, F[TDF_H], F[TDF_RATE], F[TDF_T]);
+        const int64_t s1 = tdoa_step(h_end[r] - 1 - F[TDF_FRAME0], K, F[TDF_H], F[TDF_RATE], F[TDF_T]);
+        n_items += (s1 - s0) / TD_TPB + 1;
+    }
+    if (n_items > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_stats: too many steps in one call");
+    if (n_items > 0 && (!d_stream || (uintptr_t)d_stream % 4)) return fail(c, SPKD_EINVAL, "tdoa_stats: null or misaligned stream");
+    const size_t ni = (size_t)n_items, nf = (size_t)n_files;
+    struct Tab { long long* files; TdoaItem* item; };
+    auto t = mirror<Tab>([&](Layout L, Tab& p) { return L.part(p.files, nf * TD_FILE).part(p.item, ni).bytes(); });
+    if (ni) {
+        TRY(stage(c, PIN_TD_TAB, t));
+        std::memcpy(t.h.files, h_files, nf * TD_FILE * sizeof(int64_t));
+        TdoaItem* it = t.h.item;
+        for (int64_t r = 0; r < n_ranges; ++r) {
+            const int64_t* F = h_files + (int64_t)h_file[r] * TD_FILE;
+            if (h_end[r] == h_begin[r] || F[TDF_C] < 2 || F[TDF_T] < 1) continue;
+            const int64_t b = h_begin[r] - F[TDF_FRAME0], e = h_end[r] - F[TDF_FRAME0];
+            const int64_t s0 = tdoa_step(b, K, F[TDF_H], F[TDF_RATE], F[TDF_T]);
+            const int64_t s1 = tdoa_step(e - 1, K, F[TDF_H], F[TDF_RATE], F[TDF_T]);
+            for (int64_t s = s0; s <= s1; s += TD_TPB, ++it) {
+                it->b = b, it->e = e;
+                it->file = h_file[r], it->set = h_set[r];
+                it->step0 = (int)s;
+                it->n_steps = (int)std::min<int64_t>(TD_TPB, s1 - s + 1);
+            }
+        }
+    }
+    Call call(c);
+    TRY(call.opened);
+    HIPCHK(c, hipMemsetAsync(d_stats, 0, (size_t)n_sets * TD_MAX_CH * TD_MOM * sizeof(int64_t), c->stream));
+    if (ni) {
+        TRY(send(call, S_TD_TAB, t));
+        Timer tm(c, SPKD_T_TDOA_STATS);
+        hipLaunchKernelGGL(k_tdoa_stats, dim3((unsigned)ni), dim3(TD_TPB), 0, c->stream, d_stream, (const long long*)t.d.files, K,
+                           (const TdoaItem*)t.d.item, (unsigned long long*)d_stats);
+    }
+    HIPCHK(c, hipGetLastError());
+    return call.finish();
+}
+
+spkd_status spkd_tdoa_models(spkd_ctx* c, const int64_t* d_stats, int64_t n_speakers, const int32_t* h_spk_file,
+                             const int32_t* h_ok, const int64_t* h_files, int64_t n_files, int32_t min_frames, double floor_s,
+                             double* d_models, int32_t* h_live) {
+    if (!c || n_speakers < 0 || n_files < 0) return SPKD_EINVAL;
+    if (n_speakers > 0x7fffffff || n_files > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_models: bad count");
+    if (min_frames < 1) return fail(c, SPKD_EINVAL, "tdoa_models: min_frames >= 1");
+    if (!(floor_s > 0.0) || !(floor_s < INFINITY)) return fail(c, SPKD_EINVAL, "tdoa_models: floor_s a finite number > 0");
+    if (n_files == 0 && n_speakers == 0) return SPKD_OK;
+    if (!h_files || !h_live || (n_speakers > 0 && (!h_spk_file || !h_ok || !d_stats || !d_models)))
+        return fail(c, SPKD_EINVAL, "tdoa_models: null argument");
+    if ((uintptr_t)d_stats % 8 || (uintptr_t)d_models % 8) return fail(c, SPKD_EINVAL, "tdoa_models: misaligned buffer");
+    for (int64_t f = 0; f < n_files; ++f) {
+        const int64_t* F = h_files + f * TD_FILE;
+        if (F[TDF_C] < 1 || F[TDF_C] > TD_MAX_CH || (F[TDF_C] > 1 && (F[TDF_REF] < 0 || F[TDF_REF] >= F[TDF_C])) ||
+            F[TDF_RATE] < 1 || F[TDF_RATE] > 0x7fffffff)
+            return fail(c, SPKD_EINVAL, "tdoa_models: channels, reference channel or input rate of a file out of range");
+    }
+    for (int64_t s = 0; s < n_speakers; ++s)
+        if (h_spk_file[s] < 0 || h_spk_file[s] >= n_files || (s > 0 && h_spk_file[s] < h_spk_file[s - 1]))
+            return fail(c, SPKD_EINVAL, "tdoa_models: the speakers' files ascending and inside [0, n_files)");
+    if (n_files == 0) return SPKD_OK;
+    const size_t nf = (size_t)n_files, ns = (size_t)n_speakers;
+    struct Tab { long long *files, *spk_off; int *ok, *live; };
+    auto t = mirror<Tab>([&](Layout L, Tab& p) {
+        return L.part(p.files, nf * TD_FILE).part(p.spk_off, nf + 1).part(p.ok, ns).part(p.live, nf).bytes();
+    });
+    TRY(stage(c, PIN_TD_TAB, t));
+    std::memcpy(t.h.files, h_files, nf * TD_FILE * sizeof(int64_t));
+    if (ns) std::memcpy(t.h.ok, h_ok, ns * sizeof(int32_t));
+    std::memset(t.h.live, 0, nf * sizeof(int32_t));
+    {
+        size_t s = 0;
+        for (size_t f = 0; f < nf; ++f) {
+            t.h.spk_off[f] = (long long)s;
+            while (s < ns && (size_t)h_spk_file[s] == f) ++s;
+        }
+        t.h.spk_off[nf] = (long long)ns;
+    }
+    Call call(c);
+    TRY(call.opened);
+    TRY(send(call, S_TD_TAB, t));
+    {
+        Timer tm(c, SPKD_T_TDOA_MODELS);
+        hipLaunchKernelGGL(k_tdoa_models, dim3((unsigned)nf), dim3(WAVE), 0, c->stream, (const long long*)d_stats,
+                           (const long long*)t.d.files, (const long long*)t.d.spk_off, (const int*)t.d.ok, (int)min_frames, floor_s,
+                           d_models, t.d.live);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_live, t.d.live, nf * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    return call.finish();
+}
+
+spkd_status spkd_tdoa_score(spkd_ctx* c, const int32_t* d_stream, int64_t n_entries, const int64_t* h_files, int64_t n_files,
+                            int32_t hop, int32_t window, int32_t rate_out, const double* d_models, int64_t n_models,
+                            const int32_t* h_live, int64_t n_seq, const int64_t* h_seq_begin, const int64_t* h_seq_end,
+                            const int32_t* h_seq_file, const int32_t* h_seq_model, const int32_t* h_seq_n_models, int32_t n_cols,
+                            double weight, float* d_scores) {
+    if (!c || n_seq < 0) return SPKD_EINVAL;
+    TdoaClock K;
+    TRY(tdoa_files(c, "tdoa_score", h_files, n_files, n_entries, hop, window, rate_out, &K));
+    if (n_cols < 1 || n_cols > GS_MAX_COLS) return fail(c, SPKD_EINVAL, "tdoa_score: 1 <= n_cols <= 16");
+    if (!(weight >= 0.0) || !(weight < INFINITY)) return fail(c, SPKD_EINVAL, "tdoa_score: weight a finite number >= 0");
+    if (n_models < 0 || n_models > 0x7fffffff || n_seq > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_score: bad count");
+    if (n_seq == 0) return SPKD_OK;
+    if (!h_live || !h_seq_begin || !h_seq_end || !h_seq_file || !h_seq_model || !h_seq_n_models)
+        return fail(c, SPKD_EINVAL, "tdoa_score: null argument");
+    for (int64_t f = 0; f < n_files; ++f) {
+        const int64_t* F = h_files + f * TD_FILE;
+        const int32_t valid = F[TDF_C] > 1 ? (((1 << F[TDF_C]) - 1) & ~(1 << F[TDF_REF])) : 0;
+        if (h_live[f] & ~valid) return fail(c, SPKD_EINVAL, "tdoa_score: a live channel the file does not have");
+    }
+    int64_t n_tiles = 0;
+    for (int64_t q = 0; q < n_seq; ++q) {
+        const int64_t b = h_seq_begin[q], e = h_seq_end[q], m = h_seq_model[q], k = h_seq_n_models[q];
+        TRY(tdoa_range(c, "tdoa_score", h_files, n_files, K, h_seq_file[q], b, e));
+        if (k < 0 || k > n_cols) return fail(c, SPKD_EINVAL, "tdoa_score: 0 <= models of a sequence <= n_cols");
+        if (m < 0 || m + k > n_models) return fail(c, SPKD_EINVAL, "tdoa_score: model index out of range");
+        const int64_t* F = h_files + (int64_t)h_seq_file[q] * TD_FILE;
+        if (k > 0 && F[TDF_T] > 0 && h_live[h_seq_file[q]]) n_tiles += (e - b + TD_TPB - 1) / TD_TPB;
+    }
+    if (n_tiles == 0) return SPKD_OK;
+    if (n_tiles > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_score: too many frames in one call");
+    if (!d_stream || !d_models || !d_scores) return fail(c, SPKD_EINVAL, "tdoa_score: null device buffer");
+    if ((uintptr_t)d_stream % 4 || (uintptr_t)d_models % 8 || (uintptr_t)d_scores % 4)
+        return fail(c, SPKD_EINVAL, "tdoa_score: misaligned buffer");
+    const size_t ns = (size_t)n_seq, nf = (size_t)n_files, nt = (size_t)n_tiles;
+    struct Tab { long long *begin, *end, *row, *tile, *files; int *file, *model, *n_models, *tile_seq, *live; };
+    auto t = mirror<Tab>([&](Layout L, Tab& p) {
+        return L.part(p.begin, ns).part(p.end, ns).part(p.row, ns).part(p.tile, ns).part(p.files, nf * TD_FILE).part(p.file, ns)
+            .part(p.model, ns).part(p.n_models, ns).part(p.tile_seq, nt).part(p.live, nf).bytes();
+    });
+    TRY(stage(c, PIN_TD_TAB, t));
+    std::memcpy(t.h.begin, h_seq_begin, ns * sizeof(int64_t));
+    std::memcpy(t.h.end, h_seq_end, ns * sizeof(int64_t));
+    std::memcpy(t.h.files, h_files, nf * TD_FILE * sizeof(int64_t));
+    std::memcpy(t.h.file, h_seq_file, ns * sizeof(int32_t));
+    std::memcpy(t.h.model, h_seq_model, ns * sizeof(int32_t));
+    std::memcpy(t.h.n_models, h_seq_n_models, ns * sizeof(int32_t));
+    std::memcpy(t.h.live, h_live, nf * sizeof(int32_t));
+    long long row = 0, tile = 0;
+    for (size_t q = 0; q < ns; ++q) {
+        t.h.row[q] = row;
+        t.h.tile[q] = tile;
+        const long long len = t.h.end[q] - t.h.begin[q];
+        const int64_t* F = h_files + (int64_t)h_seq_file[q] * TD_FILE;
+        const long long k = (h_seq_n_models[q] > 0 && F[TDF_T] > 0 && h_live[h_seq_file[q]]) ? (len + TD_TPB - 1) / TD_TPB : 0;
+        for (long long i = 0; i < k; ++i) t.h.tile_seq[tile + i] = (int)q;
+        row += len;
+        tile += k;
+    }
+    Call call(c);
+    TRY(call.opened);
+    TRY(send(call, S_TD_TAB, t));
+    {
+        Timer tm(c, SPKD_T_TDOA_SCORE);
+        const TdoaSeqs S{t.d.begin, t.d.end, t.d.row, t.d.tile, t.d.file, t.d.model, t.d.n_models, t.d.tile_seq, t.d.live};
+        hipLaunchKernelGGL(k_tdoa_score, dim3((unsigned)nt), dim3(TD_TPB), 0, c->stream, d_stream, (const long long*)t.d.files, K,
+                           d_models, S, (int)n_cols, weight, d_scores, c->d_err);
+    }
+    HIPCHK(c, hipGetLastError());
     return call.finish();
 }
 

@@ -258,13 +258,21 @@ def _beamform_plan(files, opts):
     return geoms, np.array([rates.index(rate) for _, rate in files], dtype=np.int32), ref
 
 
-def _beamform_group(ctx, d_raw, in_off, channels, geom, geoms, ref, opts, d_out, ms, detail=None):
-    """The three stages on one uploaded group -> out_off; ms[stage] += the stage's time."""
+def _beamform_steps(frames, channels, geom, geoms):
+    """The steps of every file (spkd_bf_gcc's count): none for one channel, else one and one more for every
+    whole hop the window can move inside the file -> int64 [n_files]."""
+    return np.array([0 if c == 1 else (1 if n <= geoms[g][1] else (n - geoms[g][1]) // geoms[g][0] + 1)
+                     for n, c, g in zip(frames, channels, geom)], dtype=np.int64)
+
+
+def _beamform_group(ctx, d_raw, in_off, channels, geom, geoms, ref, opts, d_out, ms, detail=None, delays=None):
+    """The three stages on one uploaded group -> out_off; ms[stage] += the stage's time.  delays: None, or
+    (stream, first file): the group's delays are packed into their place of the DelayStream before the next
+    group reuses the scratch (spkd_tdoa_pack; one read-back of d_ref for the reference channels)."""
     n_files = len(channels)
     C = np.asarray(channels, dtype=np.int64)
     frames = np.diff(in_off) // C
-    T = np.array([0 if c == 1 else (1 if n <= geoms[g][1] else (n - geoms[g][1]) // geoms[g][0] + 1)
-                  for n, c, g in zip(frames, C, geom)], dtype=np.int64)
+    T = _beamform_steps(frames, C, geom, geoms)
     wg_off = np.concatenate([[0], np.cumsum(T * C)]).astype(np.int64)
     total = int(wg_off[-1])
     d_ref = ctx.dev_scratch('bf_ref', max(4 * n_files, 16))
@@ -283,6 +291,8 @@ def _beamform_group(ctx, d_raw, in_off, channels, geom, geoms, ref, opts, d_out,
     out_off = ctx.bf_sum(d_raw, in_off, channels, geom, geoms, d_delay, d_out)
     if some:
         ms['bf_sum'] += ctx.last_ms('bf_sum')
+    if delays is not None:
+        delays[0]._pack_group(delays[1], T, C, d_ref if some else None, ref, d_delay, d_val, opts['min_peak'], ms)
     if detail is not None:
         got_ref = np.zeros(n_files, dtype=np.int32)
         delay = np.zeros(total, dtype=np.int32)
@@ -301,23 +311,182 @@ def _beamform_group(ctx, d_raw, in_off, channels, geom, geoms, ref, opts, d_out,
     return out_off
 
 
+def frame_step(t, hop, window, rate_in, rate_out, H, T):
+    """The step of a file's feature frame t (file-local): the rule of csrc/spkd_tdoa.hpp (tdoa_step; include/spkd.h
+    (6b3)), mirrored here in Python integers: min(T - 1, ((t hop + window // 2) rate_in) // (rate_out H))."""
+    return min(int(T) - 1, ((int(t) * int(hop) + int(window) // 2) * int(rate_in)) // (int(rate_out) * int(H)))
+
+
+def step_first_frame(s, hop, window, rate_in, rate_out, H):
+    """The first frame of step s under frame_step without its clamp (tdoa_first_frame): the smallest t >= 0
+    with (t hop + window // 2) rate_in >= s rate_out H."""
+    if s <= 0:
+        return 0
+    q = -((-int(s) * int(rate_out) * int(H)) // int(rate_in)) - int(window) // 2
+    return 0 if q <= 0 else -((-q) // int(hop))
+
+
+class DelayStream(object):
+    """The delays the beamformer tracked, kept on the device for a whole batch (include/spkd.h (6b3)): one
+    array of packed int32, entry (f, t, c) at off_f + t C_f + c the delay of step t of file f on channel c in
+    input samples, or hipabi.TDOA_NONE where the step is not reliable there -- _beamform_group's test, the
+    first candidate's value >= min_peak as float32.  hop, window: the feature configuration's, in samples
+    at rate_out, the rate the features are computed at: they and the per-file table (off, T, C, reference
+    channel, H, input rate) take a feature frame to its step (frame_step).  resample_batch(..., beamform=b,
+    delays=stream) and beamform_batch(..., delays=stream) fill it; from_arrays builds one from host arrays;
+    resegment_batch(..., delays=stream) reads it.  A one-channel file has T = 0.  The buffer is a scratch
+    slot of the context: a stream lives until the next one is laid out on the same context, and says so
+    (ValueError) when it is used after that."""
+
+    def __init__(self, ctx, hop, window, rate_out=16000):
+        hop, window, rate_out = int(hop), int(window), int(rate_out)
+        if hop < 1 or window < 0 or rate_out < 1:
+            raise ValueError('DelayStream: hop >= 1, window >= 0 and rate_out >= 1, in samples and Hz')
+        self.ctx, self.hop, self.window, self.rate_out = ctx, hop, window, rate_out
+        self.d_stream, self.n_entries, self._generation = None, 0, 0
+        self.files = np.zeros((0, 6), dtype=np.int64)      # off, T, C, ref, H, rate_in
+
+    @property
+    def n_files(self):
+        return len(self.files)
+
+    def _check_steps(self, C, H, rates):
+        """A step is at least a feature frame long (include/spkd.h (6b3)); an input error, before any device work."""
+        for f, (h, rate, c) in enumerate(zip(H, rates, C)):
+            if c > 1 and int(h) * self.rate_out < self.hop * int(rate):
+                raise ValueError('file %d: a step of %d samples at %d Hz is shorter than a feature frame' % (f, h, rate))
+
+    def _check_plan(self, files, geom, geoms):
+        self._check_steps([a.shape[1] for a, _ in files], [geoms[g][0] for g in geom], [rate for _, rate in files])
+
+    def _current(self):
+        """The buffer is the context's one slot: a stream laid out later on the same context took it over."""
+        if self.d_stream is not None and getattr(self.ctx, '_tdoa_generation', self._generation) != self._generation:
+            raise ValueError('delays: a later stream was laid out on this context, which holds one at a time')
+
+    def _lay_out(self, ctx, T, C, ref, H, rates):
+        T, C = np.asarray(T, dtype=np.int64).reshape(-1), np.asarray(C, dtype=np.int64).reshape(-1)
+        self._check_steps(C, H, rates)
+        off = np.concatenate([[0], np.cumsum(T * C)]).astype(np.int64)
+        self.files = np.column_stack([off[:-1], T, C, np.asarray(ref, dtype=np.int64).reshape(-1),
+                                      np.asarray(H, dtype=np.int64).reshape(-1),
+                                      np.asarray(rates, dtype=np.int64).reshape(-1)]).astype(np.int64).reshape(-1, 6)
+        self.ctx, self.n_entries = ctx, int(off[-1])
+        self.d_stream = ctx.dev_scratch('tdoa_stream', max(4 * self.n_entries, 16))
+        self._generation = ctx._tdoa_generation = getattr(ctx, '_tdoa_generation', 0) + 1
+
+    def _reserve(self, ctx, files, geom, geoms):
+        """The layout of a batch of checked files, before its first group: every file's steps are known from
+        its length (_beamform_steps); the reference channels arrive with the groups."""
+        C = np.array([a.shape[1] for a, _ in files], dtype=np.int64)
+        T = _beamform_steps([len(a) for a, _ in files], C, geom, geoms)
+        self._lay_out(ctx, T, C, np.full(len(files), -1), [geoms[g][0] for g in geom], [rate for _, rate in files])
+
+    def _pack_group(self, first, T, C, d_ref, want_ref, d_delay, d_val, min_peak, ms):
+        n_files, total = len(T), int((T * C).sum())
+        assert np.array_equal(self.files[first:first + n_files, 1], T) and np.array_equal(self.files[first:first + n_files, 2], C)
+        at = self.d_stream + 4 * int(self.files[first, 0])
+        if d_ref is None:
+            # a group without a sample: the beamformer launched nothing.  Its files' one step holds what the kernels
+            # define for it in any other grouping: the requested reference channel, else channel 0, at lag 0 with
+            # value 1, and no other channel
+            got_ref = np.where(np.asarray(want_ref) >= 0, want_ref, 0).astype(np.int32)
+            entries = np.full(total, hipabi.TDOA_NONE, dtype=np.int32)
+            if np.float32(1.0) >= np.float32(min_peak):
+                entries[(self.files[first:first + n_files, 0] - self.files[first, 0] + got_ref)[T > 0]] = 0
+            if total:
+                self.ctx.h2d(at, entries)
+        else:
+            got_ref = np.zeros(n_files, dtype=np.int32)
+            self.ctx.d2h(got_ref, d_ref)
+            if total:
+                self.ctx.tdoa_pack(d_delay, d_val, min_peak, total, at)
+                ms['tdoa_pack'] += self.ctx.last_ms('tdoa_pack')
+        self.files[first:first + n_files, 3] = got_ref
+
+    @classmethod
+    def from_arrays(cls, ctx, hop, window, files, rate_out=16000):
+        """The same stream from host arrays, for known geometries and for tests: files = [(delay int32 [T, C],
+        reliable bool [T, C], ref, H, rate_in)]; a delay beyond +-4096 samples on a reliable entry, a reference
+        channel outside the file's, shapes that differ: ValueError."""
+        self = cls(ctx, hop, window, rate_out)
+        packed, T, C, refs, Hs, rates = [], [], [], [], [], []
+        for f, (delay, reliable, ref, H, rate_in) in enumerate(files):
+            d, r = np.asarray(delay), np.asarray(reliable)
+            if d.ndim != 2 or d.shape != r.shape or d.dtype.kind not in 'iu' or r.dtype != np.bool_:
+                raise ValueError('file %d: delay int32 [T, C] and reliable bool [T, C] expected' % f)
+            if not 1 <= d.shape[1] <= hipabi.TDOA_MAX_CH:
+                raise ValueError('file %d: 1 to %d channels expected' % (f, hipabi.TDOA_MAX_CH))
+            if d.shape[1] == 1 and d.shape[0]:
+                raise ValueError('file %d: a one-channel file has no steps' % f)
+            if d.shape[1] > 1 and not 0 <= int(ref) < d.shape[1]:
+                raise ValueError('file %d: reference channel %d of %d channels' % (f, ref, d.shape[1]))
+            if int(H) < 1 or int(H) > hipabi.BF_MAX_HOP or int(rate_in) < 1:
+                raise ValueError('file %d: a step of 1 to %d samples and a positive rate expected' % (f, hipabi.BF_MAX_HOP))
+            if r.any() and int(np.abs(d[r].astype(np.int64)).max()) > hipabi.TDOA_MAX_DELAY:
+                raise ValueError('file %d: a delay beyond %d samples' % (f, hipabi.TDOA_MAX_DELAY))
+            packed.append(np.where(r, d.astype(np.int64), hipabi.TDOA_NONE).astype(np.int32).ravel())
+            T.append(d.shape[0]), C.append(d.shape[1]), refs.append(int(ref)), Hs.append(int(H)), rates.append(int(rate_in))
+        self._lay_out(ctx, T, C, refs, Hs, rates)
+        if self.n_entries:
+            ctx.h2d(self.d_stream, np.concatenate(packed))
+        return self
+
+    def table(self, frame_off):
+        """The file table of the C calls (hipabi.TDOA_FILE int64 per file): the six columns and frame_off[f], the
+        file's first frame in the batch's numbering."""
+        frame_off = np.asarray(frame_off, dtype=np.int64).reshape(-1)
+        if len(frame_off) != self.n_files:
+            raise ValueError('delays: a stream of %d files, a batch of %d' % (self.n_files, len(frame_off)))
+        return np.column_stack([self.files, frame_off, np.zeros(self.n_files, dtype=np.int64)]).astype(np.int64).reshape(-1, hipabi.TDOA_FILE)
+
+    def handle(self, frame_off):
+        """What hipabi's tdoa_stats and tdoa_score take as `stream`.  ValueError when a later stream of the
+        context has taken the buffer."""
+        self._current()
+        return self.d_stream, self.n_entries, self.table(frame_off), (self.hop, self.window, self.rate_out)
+
+    def step_of(self, f, t):
+        """The step of file f's frame t (frame_step with the file's table entry); the file has steps."""
+        _, T, _, _, H, rate_in = (int(v) for v in self.files[f])
+        return frame_step(t, self.hop, self.window, rate_in, self.rate_out, H, T)
+
+    def to_host(self):
+        """Per file (delay int32 [T, C], reliable bool [T, C]): delay is 0 where not reliable."""
+        self._current()
+        packed = np.zeros(self.n_entries, dtype=np.int32)
+        if self.n_entries:
+            self.ctx.d2h(packed, self.d_stream)
+        out = []
+        for off, T, C, _, _, _ in self.files.tolist():
+            p = packed[off:off + T * C].reshape(T, C)
+            ok = p != hipabi.TDOA_NONE
+            out.append((np.where(ok, p, 0).astype(np.int32), ok))
+        return out
+
+
 def _note_beamform(timings, ms):
     if timings is not None:
         for k, v in ms.items():
             timings.setdefault(k, []).append(v)
 
 
-def beamform_batch(ctx, audios, opts=BEAMFORM, timings=None, detail=None):
+def beamform_batch(ctx, audios, opts=BEAMFORM, timings=None, detail=None, delays=None):
     """The channels of every file aligned and summed on the device (spkd_bf_gcc, spkd_bf_track,
     spkd_bf_sum; include/spkd.h (6b2)): audios as resample_batch takes them -> (d_mono, sample_off),
     the mono int16 files at their own rates, still on the device in a buffer the context keeps, file f
     at [sample_off[f], sample_off[f+1]).  A one-channel file is copied through.  opts: a dictionary
     like BEAMFORM.  detail, if a dictionary, receives per file 'ref' (the reference channel), 'delay'
     (int32 [T, C]) and 'reliable' (bool [T, C]).  Input errors are ValueErrors before the context is
-    touched."""
+    touched.  delays: None, or a DelayStream, which is filled with the batch's delays (the files stay at
+    their own rates here, so every file's rate must be the stream's rate_out)."""
     files = _audio_files(audios)
     geoms, geom, ref = _beamform_plan(files, opts)
     channels = np.array([a.shape[1] for a, _ in files], dtype=np.int32)
+    if delays is not None:
+        if any(rate != delays.rate_out for _, rate in files):
+            raise ValueError('delays: beamform_batch does not resample, every file must be at the stream\'s %d Hz' % delays.rate_out)
+        delays._check_plan(files, geom, geoms)
     in_off = np.concatenate([[0], np.cumsum([a.size for a, _ in files])]).astype(np.int64)
     sample_off = np.concatenate([[0], np.cumsum([len(a) for a, _ in files])]).astype(np.int64)
     d_raw = ctx.dev_scratch('audio_batch', max(2 * int(in_off[-1]), 16))
@@ -328,7 +497,11 @@ def beamform_batch(ctx, audios, opts=BEAMFORM, timings=None, detail=None):
             ctx.h2d(d_raw + 2 * int(o), a)
     wall = time.perf_counter() - _t0
     ms = dict(bf_gcc=0.0, bf_track=0.0, bf_sum=0.0)
-    got = _beamform_group(ctx, d_raw, in_off, channels, geom, geoms, ref, opts, d_out, ms, detail)
+    if delays is not None:
+        ms['tdoa_pack'] = 0.0
+        delays._reserve(ctx, files, geom, geoms)
+    got = _beamform_group(ctx, d_raw, in_off, channels, geom, geoms, ref, opts, d_out, ms, detail,
+                          None if delays is None else (delays, 0))
     assert np.array_equal(got, sample_off)
     if timings is not None:
         timings.setdefault('wall_upload', []).append(1e3 * wall)
@@ -336,7 +509,7 @@ def beamform_batch(ctx, audios, opts=BEAMFORM, timings=None, detail=None):
     return d_out, sample_off
 
 
-def resample_batch(ctx, audios, rate_out, group_bytes=RESAMPLE_GROUP_BYTES, timings=None, beamform=None):
+def resample_batch(ctx, audios, rate_out, group_bytes=RESAMPLE_GROUP_BYTES, timings=None, beamform=None, delays=None):
     """The audio of a batch of files, audios = [(samples, rate)] with int16 samples [n] or
     [n, channels], converted to mono at rate_out on the device (spkd_resample_batch) -> (d_pcm,
     sample_off), exactly what upload_batch returns for the converted files: vad_batch(uploaded=...)
@@ -348,13 +521,21 @@ def resample_batch(ctx, audios, rate_out, group_bytes=RESAMPLE_GROUP_BYTES, timi
     and a positive integer rate is a ValueError before the context is touched.
     beamform: None, or a dictionary like BEAMFORM: each uploaded group is then aligned and summed
     (beamform_batch's three calls) into a second scratch, bounded like the first, and resampled from
-    there as one-channel files, instead of being averaged by the resampler's downmix."""
+    there as one-channel files, instead of being averaged by the resampler's downmix.
+    delays: None, or a DelayStream (with beamform only), which is filled group by group with the delays the
+    beamformer tracked: they survive the groups there, for resegment_batch(delays=...)."""
     files = _audio_files(audios)
     rate_out = int(rate_out)
     if group_bytes < 1:
         raise ValueError('group_bytes must be positive')
+    if delays is not None and beamform is None:
+        raise ValueError('delays: the delay stream is filled by the beamformer, which takes beamform=')
+    if delays is not None and delays.rate_out != rate_out:
+        raise ValueError('delays: the stream counts its frames at %d Hz, the conversion is to %d Hz' % (delays.rate_out, rate_out))
     if beamform is not None:
         geoms, geom, ref = _beamform_plan(files, beamform)
+        if delays is not None:
+            delays._check_plan(files, geom, geoms)
     rates = sorted(set(rate for _, rate in files))
     convs, tables, at = [], [], 0
     for rate in rates:
@@ -383,6 +564,9 @@ def resample_batch(ctx, audios, rate_out, group_bytes=RESAMPLE_GROUP_BYTES, timi
         most = max([sum(len(files[f][0]) for f in range(lo, hi)) for lo, hi in groups] + [0])
         d_mono = ctx.dev_scratch('bf_mono', max(2 * most, 16))
         bf_ms = dict(bf_gcc=0.0, bf_track=0.0, bf_sum=0.0)
+        if delays is not None:
+            bf_ms['tdoa_pack'] = 0.0
+            delays._reserve(ctx, files, geom, geoms)
     for lo, hi in groups:
         in_off = np.concatenate([[0], np.cumsum([files[f][0].size for f in range(lo, hi)])]).astype(np.int64)
         _t0 = time.perf_counter()
@@ -391,7 +575,8 @@ def resample_batch(ctx, audios, rate_out, group_bytes=RESAMPLE_GROUP_BYTES, timi
                 ctx.h2d(d_raw + 2 * int(o), files[f][0])
         wall += time.perf_counter() - _t0
         if beamform is not None:
-            mono_off = _beamform_group(ctx, d_raw, in_off, channels[lo:hi], geom[lo:hi], geoms, ref[lo:hi], beamform, d_mono, bf_ms)
+            mono_off = _beamform_group(ctx, d_raw, in_off, channels[lo:hi], geom[lo:hi], geoms, ref[lo:hi], beamform, d_mono, bf_ms,
+                                       delays=None if delays is None else (delays, lo))
             got = ctx.resample_batch(d_mono, mono_off, np.ones(hi - lo, dtype=np.int32), conv[lo:hi], convs, taps,
                                      d_pcm + 2 * int(sample_off[lo]))
         else:

@@ -18,7 +18,7 @@ TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pai
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
                                         'post_stats', 'bf_gcc', 'bf_track', 'bf_sum', 'resample', 'frame_energy', 'energy_seeds',
-                                        'feature_warp', 'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
+                                        'feature_warp', 'tdoa_pack', 'tdoa_stats', 'tdoa_models', 'tdoa_score', 'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
                                         'mindur_viterbi', 'mindur_backtrack', 'fb_posterior',
                                         'ident_scores', 'ident_assign', 'bw_accumulate',
                                         'mfcc_static', 'mfcc_post'])}
@@ -50,6 +50,12 @@ BF_NBEST = 4                # SPKD_BF_NBEST: candidate lags kept per step and ch
 BF_MAX_HOP = 1 << 20        # SPKD_BF_MAX_HOP: the largest hop of a geometry
 ENERGY_MAX_WINDOW = 4096    # SPKD_ENERGY_MAX_WINDOW: samples of a frame of k_frame_energy (hop <= window)
 ENERGY_TILE = 16384         # SPKD_ENERGY_TILE: samples whose hops make the frames of a workgroup of k_frame_energy
+TDOA_NONE = -(1 << 31)      # SPKD_TDOA_NONE: a step of the delay stream that is not reliable on a channel
+TDOA_MAX_CH = 8             # SPKD_TDOA_MAX_CH: channels of a file of the delay stream
+TDOA_MAX_DELAY = 4096       # SPKD_TDOA_MAX_DELAY: the largest |delay| of an entry
+TDOA_FILE = 8               # SPKD_TDOA_FILE: int64 per file of the stream's host table
+TDOA_MODEL = 4              # SPKD_TDOA_MODEL: doubles per (speaker, channel): mean, var, 1 / (2 var), -1/2 log(2 pi var)
+TDOA_TILE = 256             # SPKD_TDOA_TILE: frames per workgroup of k_tdoa_score, steps per workgroup of k_tdoa_stats
 WARP_MAX_WINDOW = 512       # SPKD_WARP_MAX_WINDOW: the widest window of spkd_feature_warp, in frames
 WARP_TILE = 384             # SPKD_WARP_TILE: compacted frames per workgroup of k_feature_warp
 REC = 820
@@ -59,6 +65,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_last_ahc_head', 'spkd_ahc_head_rule', 'spkd_set_stats', 'spkd_pair_terms',
            'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_sum_stats', 'spkd_mfcc', 'spkd_mfcc_batch', 'spkd_resample_batch', 'spkd_bf_gcc', 'spkd_bf_track', 'spkd_bf_sum',
+           'spkd_tdoa_pack', 'spkd_tdoa_stats', 'spkd_tdoa_models', 'spkd_tdoa_score',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
@@ -237,6 +244,10 @@ def load_library(path=None):
     lib.spkd_bf_gcc.argtypes = [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.spkd_bf_track.argtypes = [vp, i64, vp, vp, vp, vp, i32, C.c_float, dbl, i32, vp]
     lib.spkd_bf_sum.argtypes = [vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.spkd_tdoa_pack.argtypes = [vp, vp, vp, C.c_float, i64, vp]
+    lib.spkd_tdoa_stats.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp, i64, i64, vp]
+    lib.spkd_tdoa_models.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, dbl, vp, vp]
+    lib.spkd_tdoa_score.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, dbl, vp]
     lib.spkd_frame_energy_batch.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
     lib.spkd_energy_seeds.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, P(vp), P(vp), P(vp)]
     lib.spkd_sw_window_count.argtypes = [i64, dbl, dbl]
@@ -873,6 +884,70 @@ class Context(object):
         self.check(self.lib.spkd_bf_sum(self.h, C.c_void_p(d_in), len(off) - 1, _ptr(off), _ptr(ch), _ptr(gi), len(geoms), table,
                                         C.c_void_p(d_delay), C.c_void_p(d_out), _ptr(out_off)))
         return out_off
+
+    # ---- (6b3) the delay stream
+    def tdoa_pack(self, d_delay, d_val, min_peak, n, d_out):
+        """n entries of the delay stream from what spkd_bf_track read and wrote (spkd_tdoa_pack): d_out[i] =
+        d_delay[i] where the first candidate's value d_val[4 i] >= min_peak, TDOA_NONE elsewhere.  Time:
+        last_ms('tdoa_pack')."""
+        self.check(self.lib.spkd_tdoa_pack(self.h, C.c_void_p(d_delay), C.c_void_p(d_val), float(min_peak), int(n),
+                                           C.c_void_p(d_out)))
+
+    @staticmethod
+    def _tdoa_stream(stream):
+        """(d_stream, n_entries, file table [n_files, TDOA_FILE] int64, (hop, window, rate_out)) -> the arguments of
+        spkd_tdoa_stats from d_stream to rate_out; a pointer keeps its array."""
+        d_stream, n_entries, table, clock = stream
+        table = np.ascontiguousarray(table, dtype=np.int64)
+        if table.ndim != 2 or table.shape[1] != TDOA_FILE:
+            raise SpkdError(SPKD_EINVAL, 'the delay stream\'s file table: [n_files, %d] int64' % TDOA_FILE)
+        hop, window, rate_out = (int(v) for v in clock)
+        return (C.c_void_p(d_stream), int(n_entries), _ptr(table), len(table), hop, window, rate_out), table
+
+    def tdoa_stats(self, stream, begins, ends, files, sets, n_sets, d_stats):
+        """The exact delay statistics of frame sets (spkd_tdoa_stats): stream as _tdoa_stream takes it; the frame
+        ranges [begins, ends) of the batch, each with its file and its set, the sets ascending; d_stats int64
+        [n_sets, 8, 3], per channel (n, sum x, sum x^2).  Time: last_ms('tdoa_stats')."""
+        args, _keep = self._tdoa_stream(stream)
+        b, e = np.ascontiguousarray(begins, dtype=np.int64), np.ascontiguousarray(ends, dtype=np.int64)
+        f, s = np.ascontiguousarray(files, dtype=np.int32), np.ascontiguousarray(sets, dtype=np.int32)
+        if any(a.ndim != 1 for a in (b, e, f, s)) or not (len(b) == len(e) == len(f) == len(s)):
+            raise SpkdError(SPKD_EINVAL, 'one begin, end, file and set per range')
+        self.check(self.lib.spkd_tdoa_stats(self.h, *args, _ptr(b), _ptr(e), _ptr(f), _ptr(s), len(b), int(n_sets),
+                                            C.c_void_p(d_stats)))
+
+    def tdoa_models(self, d_stats, spk_file, ok, table, min_frames, floor_s, d_models):
+        """One Gaussian per (speaker, channel) from d_stats (spkd_tdoa_models) into d_models double [n, 8,
+        TDOA_MODEL]; spk_file: the speakers' files, ascending; ok: their acoustic models; table: the stream's file
+        table.  Returns live (int32 [n_files]): bit c set where channel c has min_frames reliable frames for every
+        speaker of the file that is ok.  Time: last_ms('tdoa_models')."""
+        table = np.ascontiguousarray(table, dtype=np.int64)
+        if table.ndim != 2 or table.shape[1] != TDOA_FILE:
+            raise SpkdError(SPKD_EINVAL, 'the delay stream\'s file table: [n_files, %d] int64' % TDOA_FILE)
+        sf, ok = np.ascontiguousarray(spk_file, dtype=np.int32), np.ascontiguousarray(ok, dtype=np.int32)
+        if sf.ndim != 1 or sf.shape != ok.shape:
+            raise SpkdError(SPKD_EINVAL, 'one file and one ok flag per speaker')
+        live = np.zeros(len(table), dtype=np.int32)
+        self.check(self.lib.spkd_tdoa_models(self.h, C.c_void_p(d_stats), len(sf), _ptr(sf), _ptr(ok), _ptr(table), len(table),
+                                             int(min_frames), float(floor_s), C.c_void_p(d_models), _ptr(live)))
+        return live
+
+    def tdoa_score(self, stream, d_models, n_models, live, seq_begin, seq_end, seq_file, seq_model, seq_n_models, n_cols,
+                   weight, d_scores):
+        """weight times the delay log-likelihood added to the scores gauss_loglik (or gmm_loglik_seq) left at
+        d_scores (spkd_tdoa_score): the same sequences, each with its file; live as tdoa_models returned it.  Entries
+        that are not finite and columns past a sequence's models keep their bits.  Time: last_ms('tdoa_score')."""
+        args, _keep = self._tdoa_stream(stream)
+        c = np.ascontiguousarray
+        lv = c(live, dtype=np.int32)
+        b, e = c(seq_begin, dtype=np.int64), c(seq_end, dtype=np.int64)
+        f, m, k = c(seq_file, dtype=np.int32), c(seq_model, dtype=np.int32), c(seq_n_models, dtype=np.int32)
+        if any(a.ndim != 1 for a in (lv, b, e, f, m, k)) or not (len(b) == len(e) == len(f) == len(m) == len(k)) \
+                or len(lv) != len(_keep):
+            raise SpkdError(SPKD_EINVAL, 'one begin, end, file, first model and model count per sequence; one live mask per file')
+        self.check(self.lib.spkd_tdoa_score(self.h, *args, C.c_void_p(d_models), int(n_models), _ptr(lv), len(b), _ptr(b),
+                                            _ptr(e), _ptr(f), _ptr(m), _ptr(k), int(n_cols), float(weight),
+                                            C.c_void_p(d_scores)))
 
     # ---- (6c) the seed stage of the self-trained detector
     def frame_energy_batch(self, d_pcm, sample_off, hop, window, d_energy):

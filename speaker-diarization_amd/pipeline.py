@@ -24,7 +24,7 @@ from .recipe import py2_float_str
 from .linking import LINK_CL, LINK_CLR, LINK_CLR_WARP, _link_model, link_batch, ubm_ranges
 # the resegmentation stage (resegmentation.py): its settings and its entry point under their names here
 from .resegmentation import (FB_MAX_SCALED_PENALTY, RESEG, RESEG_CONF, RESEG_GMM, RESEG_MAX_SPEAKERS, RESEG_MD,
-                             RESEG_SOFT, RESEG_SOFT_SCALE, resegment_batch)
+                             RESEG_SOFT, RESEG_SOFT_SCALE, RESEG_TDOA, TDOA, resegment_batch)
 # the self-trained speech / non-speech detector (self_vad.py): its settings under their name here
 from .self_vad import SELF_VAD
 # the tables every stage reads (tables.py), under their names here
@@ -130,7 +130,7 @@ def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=Non
     (features_batch with cfg, the fconfig.cfg chain) both from it, then diarize_batch with the
     turns and the frames as they lie on the device.  uploaded: the samples already on the device
     (frontend.upload_batch or frontend.resample_batch; pcms is not read then).  kw: diarize_batch's
-    text_contract, fused, handoff, link, reseg, detail.  Returns its rows.
+    text_contract, fused, handoff, link, reseg, detail, delays (the frontend.DelayStream of reseg['tdoa']).  Returns its rows.
     model: a dictionary like SELF_VAD instead of a VadModel needs no model file: one upload, ONE
     feature chain (cfg's), the self-trained turns on those features (vad_batch), then diarize_batch;
     detail, if given, also receives vad_untrained and vad_passes_run."""
@@ -157,20 +157,31 @@ def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=Non
 BEAMFORM = frontend.BEAMFORM
 
 
-def diarize_audio_batch(ctx, model, cfg, audios, cd=DIA2_CD, cl=DIA2_CL, timings=None, group_bytes=None, beamform=None, **kw):
+def diarize_audio_batch(ctx, model, cfg, audios, cd=DIA2_CD, cl=DIA2_CL, timings=None, group_bytes=None, beamform=None,
+                        delays=None, **kw):
     """From recordings to speakers: audios = [(samples, rate)], int16 [n] or [n, channels] at any
     rate (frontend.read_audio), resampled and downmixed to cfg.sample_rate on the device
     (frontend.resample_batch; group_bytes: its bound on the raw audio held there), then exactly
     diarize_pcm_batch from its upload on (model: a VadModel, or a dictionary like SELF_VAD).
     beamform: None (the channels are averaged), or a dictionary like BEAMFORM (they are aligned by
-    GCC-PHAT delays and summed: frontend.resample_batch).  Returns its rows."""
+    GCC-PHAT delays and summed: frontend.resample_batch).  reseg=dict(..., tdoa=...) with beamform: the
+    delays the beamformer tracks are kept (a frontend.DelayStream on cfg's frame clock, made here unless
+    delays= hands one in) and the resegmentation stage reads them as a second stream (resegment_batch);
+    tdoa without beamform is a ValueError.  Returns its rows."""
     if isinstance(model, dict):
         _self_vad._options(model)
     else:
         _one_clock(model, cfg)
     group = {} if group_bytes is None else {'group_bytes': group_bytes}
+    if kw.get('reseg') is not None and _resegmentation._reseg_tdoa(kw['reseg']) is not None:
+        if beamform is None:
+            raise ValueError('reseg tdoa: the delays are the beamformer\'s, which takes beamform=')
+        if delays is None:
+            delays = frontend.DelayStream(ctx, cfg.hop, cfg.window_width, cfg.sample_rate)
     if beamform is not None:
         group['beamform'] = beamform
+        if delays is not None:
+            group['delays'] = kw['delays'] = delays
     uploaded = frontend.resample_batch(ctx, audios, cfg.sample_rate, timings=timings, **group)
     return diarize_pcm_batch(ctx, model, cfg, None, cd=cd, cl=cl, timings=timings, uploaded=uploaded, **kw)
 
@@ -581,7 +592,7 @@ def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2
 
 
 def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl=DIA2_CL, timings=None,
-                  text_contract=True, fused=False, handoff=None, link=None, detail=None, reseg=None):
+                  text_contract=True, fused=False, handoff=None, link=None, detail=None, reseg=None, delays=None):
     """CD (gw/BIC) + CL (hi/BIC) for a batch; returns per file an array of rows
     [start_s, end_s, speaker] in recipe order.
     cl['method'] = 'in' clusters with spk_cluster_in (cluster_batch): host hand-off only; the
@@ -622,7 +633,10 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     (reseg['confidence'], reseg['conf_scale']; detail['confidence'] and detail['log_evidence'] as there):
     it takes a detail dictionary.  With link the confidences stay those of the file's own speakers.
     A dictionary like RESEG_SOFT retrains the speakers between the passes on frame posteriors instead of
-    decoded rows (reseg['soft'], reseg['soft_scale']; detail['soft_mass'] as there)."""
+    decoded rows (reseg['soft'], reseg['soft_scale']; detail['soft_mass'] as there).  A dictionary like
+    RESEG_TDOA adds the microphone array's delays as a second stream (reseg['tdoa'], with delays=<the
+    frontend.DelayStream the beamformer filled>; detail['tdoa_channels'] as there); clustering and linking
+    stay acoustic."""
     method = _method(cl)
     # the hand-off this call gets: the one asked for, else the device's where it can serve (a detector that
     # passes its refusal below is neither fused nor on the device, so the rule reads the same behind it)
@@ -631,6 +645,8 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
         reseg_opts = _resegmentation._reseg_options(reseg, rate, detail)
         if device:
             raise ValueError('reseg takes the host hand-off')
+        if reseg_opts.tdoa:
+            _resegmentation._check_delays(delays, reseg_opts, files, float(rate), True)
     if _cd_method(cd) in ('sw', 'm'):
         if fused or handoff == 'device':
             raise ValueError('cd method %s takes the host hand-off and is not fused' % _cd_method(cd))
@@ -660,7 +676,7 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
             _resegmentation._empty_detail(detail, reseg_opts, len(files))
         return [np.zeros((0, 3)) for _ in files]
     return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail, reseg,
-                              text_contract)
+                              text_contract, delays)
 
 
 def warp_batch(ctx, d_frames, total_frames, files, segments, rate, warp_s, d_out=None):
@@ -682,7 +698,7 @@ def warp_batch(ctx, d_frames, total_frames, files, segments, rate, warp_s, d_out
 
 
 def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link=None, detail=None,
-                       reseg=None, text_contract=True):
+                       reseg=None, text_contract=True, delays=None):
     box = None if link is None and reseg is None else []
     res = cluster_batch(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fused=fs, stats_out=box)
     cnt = [len(s) for s in segs]
@@ -691,7 +707,7 @@ def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timin
     own = [lab for (lab, _) in res]
     if reseg is not None:
         rows = resegment_batch(ctx, d_frames, total_frames, files, box[0][0], box[0][1], own, rate, reseg,
-                               text_contract, timings, detail, segs)
+                               text_contract, timings, detail, segs, delays)
     if link is not None:                             # (on the clustering segments, with or without reseg)
         more = {}
         maps, merges, smax, smin = link_batch(ctx, box[0][0], box[0][1], own, link, timings, d_frames, total_frames,

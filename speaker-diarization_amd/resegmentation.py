@@ -43,6 +43,13 @@ FB_MAX_SCALED_PENALTY = 600.0    # conf_scale * penalty, soft_scale * penalty: t
 # collapses (DESIGN.md has the table).  On speech it is unmeasured, like conf_scale and the linking thresholds.
 RESEG_SOFT = dict(penalty=50.0, passes=5, soft=True)
 RESEG_SOFT_SCALE = 0.1
+# the same stage with the microphone array's delays as a second stream (frontend.DelayStream; include/spkd.h
+# (6b3)): per speaker and channel one Gaussian over the delays of the speaker's frames, and weight times its
+# log-likelihood added to every score before anything reads them.  Any reseg dictionary may carry tdoa=.  floor_s
+# is the smallest standard deviation of a delay in seconds (one sample at 16 kHz), min_frames the reliable frames
+# a speaker needs on a channel.  All three rest on synthetic fixtures and are UNMEASURED on speech.
+TDOA = dict(weight=1.0, floor_s=1.0 / 16000.0, min_frames=40)
+RESEG_TDOA = dict(penalty=50.0, tdoa=TDOA)
 
 
 def _reseg_penalty(reseg):
@@ -132,20 +139,46 @@ def _reseg_soft(reseg, model):
     return bool(on), scale
 
 
-_Options = collections.namedtuple('_Options', 'penalty model min_frames passes confidence conf_scale soft soft_scale')
+def _reseg_tdoa(reseg):
+    """None without reseg['tdoa'], else (weight, floor_s, min_frames): the keys of TDOA, its values where one is
+    absent."""
+    t = reseg.get('tdoa')
+    if t is None:
+        return None
+    if not isinstance(t, dict) or set(t) - set(TDOA):
+        raise ValueError('reseg tdoa: a dictionary with keys of TDOA (%s)' % ', '.join(sorted(TDOA)))
+    try:
+        weight, floor_s = float(t.get('weight', TDOA['weight'])), float(t.get('floor_s', TDOA['floor_s']))
+    except (TypeError, ValueError):
+        weight = floor_s = float('nan')
+    if not np.isfinite(weight) or weight < 0.0:
+        raise ValueError('reseg tdoa weight: a finite number >= 0')
+    if not np.isfinite(floor_s) or floor_s <= 0.0:
+        raise ValueError('reseg tdoa floor_s: a finite number > 0 (seconds)')
+    n = t.get('min_frames', TDOA['min_frames'])
+    try:
+        whole = not isinstance(n, bool) and int(n) == n
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole or n < 1 or n > 0x7fffffff:
+        raise ValueError('reseg tdoa min_frames: an integer >= 1')
+    return weight, floor_s, int(n)
+
+
+_Options = collections.namedtuple('_Options', 'penalty model min_frames passes confidence conf_scale soft soft_scale tdoa')
 
 
 def _reseg_options(reseg, rate, detail):
     """A `reseg` dictionary parsed once, each key by its validator: the first ValueError of a dictionary that
     is wrong in several ways is that of the first key in the order penalty, model, min_dur_s, passes,
-    confidence, soft.  model is _reseg_model's tuple, min_frames the decoder's D (0: the plain decoder)."""
+    confidence, soft, tdoa.  model is _reseg_model's tuple, min_frames the decoder's D (0: the plain decoder)."""
     penalty = _reseg_penalty(reseg)
     model = _reseg_model(reseg)
     min_frames = _reseg_min_frames(reseg, rate)
     passes = _reseg_passes(reseg)
     confidence, conf_scale = _reseg_confidence(reseg, detail)
     soft, soft_scale = _reseg_soft(reseg, model)
-    return _Options(penalty, model, min_frames, passes, confidence, conf_scale, soft, soft_scale)
+    return _Options(penalty, model, min_frames, passes, confidence, conf_scale, soft, soft_scale, _reseg_tdoa(reseg))
 
 
 def _no_confidence(detail, n_files):
@@ -164,6 +197,8 @@ def _empty_detail(detail, opts, n_files):
         _no_confidence(detail, n_files)
     if opts.soft:
         detail['soft_mass'] = []
+    if opts.tdoa:
+        detail['tdoa_channels'] = [[] for _ in range(n_files)]
 
 
 def _token_spans(tok_off, offset, turn_begin, turn_end):
@@ -336,6 +371,62 @@ class _GmmSpeakers(_Speakers):
                                     t.spk_count, t.n_cols, self.d_scores)
 
 
+def _check_delays(delays, opts, files, rate, segments):
+    """reseg['tdoa'] takes a stream of the batch's files on the batch's frame clock, and the clustering segments."""
+    if delays is None:
+        raise ValueError('reseg tdoa: it reads the delays the beamformer tracked, delays=<frontend.DelayStream>')
+    if delays.n_files != len(files):
+        raise ValueError('delays: a stream of %d files, a batch of %d' % (delays.n_files, len(files)))
+    if float(delays.rate_out) != float(rate) * delays.hop:
+        raise ValueError('delays: the stream steps %d samples a frame at %d Hz, the batch has %g frames a second'
+                         % (delays.hop, delays.rate_out, rate))
+    if segments is None:
+        raise ValueError('reseg tdoa trains on the frames of the clustering segments: it takes segments, the arrays '
+                         'cluster_batch took')
+
+
+class _DelayModels(object):
+    """The second stream of reseg['tdoa'] (RESEG_TDOA): per (speaker, channel) the exact moments of the delays of the
+    speaker's frames (spkd_tdoa_stats), one Gaussian from them (spkd_tdoa_models), and weight times their
+    log-likelihood added to the scores the acoustic models left (spkd_tdoa_score), which every decoder, the
+    confidences and the soft retraining then read.  train(tokens, ok): in pass 1 on the clustering segments' frame
+    ranges, afterwards on the decoded tokens' ranges -- also under soft=True: the soft retraining reads the fused
+    scores, the delay models stay hard-trained.  A channel is used in a file only when every speaker of the file
+    whose acoustic model is ok has min_frames reliable frames on it (live)."""
+
+    def __init__(self, turns, delays, tdoa, files, owner, spk_file, set_off, seg_b, seg_e):
+        self.turns, self.owner, self.spk_file = turns, owner.astype(np.int32), spk_file.astype(np.int32)
+        self.weight, self.floor_s, self.min_frames = tdoa
+        self.stream = delays.handle([f.frame_off for f in files])
+        self.seg = (seg_b, seg_e, np.repeat(np.arange(turns.n_spk), np.diff(set_off)))
+        self.d_stats = turns.ctx.dev_scratch('reseg_tdoa_stats', max(turns.n_spk, 1) * hipabi.TDOA_MAX_CH * 3 * 8)
+        self.d_models = turns.ctx.dev_scratch('reseg_tdoa_models', max(turns.n_spk, 1) * hipabi.TDOA_MAX_CH * hipabi.TDOA_MODEL * 8)
+        self.live = None
+
+    def train(self, tokens, ok):
+        t = self.turns
+        if tokens is None:
+            rb, re_, spk = self.seg
+        else:
+            rb, re_, spk = _token_ranges(*tokens, t.tb, t.te, t.spk_first)
+            order = np.argsort(spk, kind='stable')
+            rb, re_, spk = rb[order], re_[order], spk[order]
+        t.ctx.tdoa_stats(self.stream, rb, re_, self.spk_file[spk], spk, t.n_spk, self.d_stats)
+        t.clock('reseg_tdoa_stats', 'tdoa_stats')
+        self.live = t.ctx.tdoa_models(self.d_stats, self.spk_file, ok, self.stream[2], self.min_frames, self.floor_s,
+                                      self.d_models)
+        t.clock('reseg_tdoa_models', 'tdoa_models')
+
+    def score(self, speakers):
+        t = self.turns
+        t.ctx.tdoa_score(self.stream, self.d_models, t.n_spk, self.live, t.tb, t.te, self.owner, t.spk_first, t.spk_count,
+                         t.n_cols, self.weight, speakers.d_scores)
+        t.clock('reseg_tdoa_score', 'tdoa_score')
+
+    def channels(self, n_files):
+        return [[c for c in range(hipabi.TDOA_MAX_CH) if (int(self.live[f]) >> c) & 1] for f in range(n_files)]
+
+
 def _decode(speakers, penalty, min_frames):
     """The best speaker sequence of every turn on the scores `speakers` holds -> (tok_off, tok_frame,
     tok_word).  One spkd_vad_viterbi_batch with the penalty taken off at every switch (stay = exit = 0,
@@ -383,7 +474,7 @@ def _speaker_segments(files, segments, seg_off, rate):
 
 
 def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels, rate=125.0, reseg=RESEG,
-                    text_contract=True, timings=None, detail=None, segments=None):
+                    text_contract=True, timings=None, detail=None, segments=None, delays=None):
     """Viterbi resegmentation of a clustered batch on the device: the closing pass of a BIC
     segmentation + agglomerative clustering system (the reference has none).  d_stats, seg_off,
     labels: the segment records, the files' offsets and the per-file labels of a cluster_batch
@@ -436,10 +527,24 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
     synthetic generator only and is unmeasured on speech.  Without soft, or with soft=False, the calls and
     the rows are those described above, to the byte.  A soft that is not a bool, a soft_scale that is not a
     finite number > 0, soft_scale * penalty above 600, soft with model gmm: ValueError before any device
-    work."""
+    work.
+    reseg['tdoa'] = a dictionary like TDOA (RESEG_TDOA; either model, either decoder, any passes, confidence
+    and soft), with delays=<frontend.DelayStream> of the same files on the same frame clock, and segments: in
+    every pass, after the speakers are trained, the delay models are (_DelayModels: spkd_tdoa_stats,
+    spkd_tdoa_models), and after the turns are scored, weight times the delay log-likelihood is added to the
+    scores (spkd_tdoa_score).  The delay models train on the clustering segments' frame ranges in pass 1 and on
+    the decoded tokens' ranges afterwards, under soft=True too: soft retraining reads the fused scores, the
+    delay models stay hard-trained.  detail['tdoa_channels']: per file the channels used in the last pass (none
+    for a one-channel file).  timings: reseg_tdoa_stats, reseg_tdoa_models, reseg_tdoa_score, one entry per
+    pass.  Without tdoa the calls and the rows are those described above, to the byte; delays is then not
+    looked at.  tdoa without delays, a stream of another file count or frame clock, no segments, unknown keys,
+    a weight that is not finite and >= 0, a floor_s that is not finite and > 0, min_frames < 1: ValueError
+    before any device work.  The defaults rest on synthetic fixtures and are unmeasured on speech."""
     rate = float(rate)
     opts = _reseg_options(reseg, rate, detail)
-    if opts.model[0] == 'gmm':
+    if opts.tdoa:
+        _check_delays(delays, opts, files, rate, segments)
+    if opts.model[0] == 'gmm' or opts.tdoa:
         seg_b, seg_e = _speaker_segments(files, segments, seg_off, rate)
     member, set_off, spk_file, spk_label = link_speakers(seg_off, labels)
     n_files = len(files)
@@ -472,6 +577,8 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
         speakers = _GmmSpeakers(turns, opts.model, set_off, seg_b[member], seg_e[member], detail)
     else:
         speakers = _GaussSpeakers(turns, d_stats, int(seg_off[-1]), member, set_off)
+    second = _DelayModels(turns, delays, opts.tdoa, files, owner, spk_file, set_off, seg_b[member], seg_e[member]) \
+        if opts.tdoa else None
     tokens = None
     for p in range(opts.passes):
         if opts.soft and tokens is not None:
@@ -480,7 +587,13 @@ def resegment_batch(ctx, d_frames, total_frames, files, d_stats, seg_off, labels
             ok = speakers.train(tokens)
         if detail is not None:
             detail['dropped'] = [(int(spk_file[s]), int(spk_label[s])) for s in np.nonzero(ok == 0)[0]]
+        if second is not None:
+            second.train(tokens, ok)
         speakers.score(ok)
+        if second is not None:
+            second.score(speakers)
+            if detail is not None:
+                detail['tdoa_channels'] = second.channels(n_files)
         decoded = _decode(speakers, opts.penalty, opts.min_frames)
         if detail is not None:
             detail['passes_run'] = p + 1
