@@ -408,11 +408,22 @@ struct SweepOut {
 // of the records built ahead is nothing: the next epoch starts from slot 0.
 // The running sums at the rest position ARE P(c) of the scan before, which sits in LDS:
 // the sweep picks them up there (fresh: a new epoch, the sums start from zero).
+//
+// The rule of the three sweep functions (GW_SWEEP_FN): for the duration of the call they own
+// the whole register file, and k_gw keeps nothing live across it -- its decision state is
+// in LDS (GwState), what it needs after the call it reads again.  With the default
+// linkage of a template the compiler must honour the calling convention's callee-saved
+// half of the VGPRs for callers it cannot see: at 248 VGPRs that was a frame of 100 / 96 /
+// 72 scratch stores at entry and as many loads (and an s_waitcnt vmcnt(0)) before the
+// return, once per scan.  It drops the frame only for a function with internal linkage
+// that is never the target of a tail call: hence `static` and `not_tail_called`, both
+// needed.  tests/test_gw_sweep_frame.py holds the ScratchSize of all twelve at 0.
+#define GW_SWEEP_FN static __device__ __noinline__ __attribute__((not_tail_called))
 template <int NW>
-__device__ __noinline__ SweepOut gw_sweep_coarse(const float* __restrict__ fr, double* __restrict__ cache,
-                                                 double start, double istep, double built_i,
-                                                 long long built_k, long long cap, long long sweep_pos,
-                                                 long long c, int fresh, int* err) {
+GW_SWEEP_FN SweepOut gw_sweep_coarse(const float* __restrict__ fr, double* __restrict__ cache,
+                                     double start, double istep, double built_i,
+                                     long long built_k, long long cap, long long sweep_pos,
+                                     long long c, int fresh, int* err) {
     using G = Gw<NW>;
     extern __shared__ double gw_lds[];
     double* ldsEnd = gw_lds;
@@ -455,10 +466,10 @@ __device__ __noinline__ SweepOut gw_sweep_coarse(const float* __restrict__ fr, d
 // -> cache records first_slot + k, starting from the sums `base` (a cache record, or
 // nullptr for zero) that stand at base_pos.
 template <int NW>
-__device__ __noinline__ void gw_sweep_fine(const float* __restrict__ fr, double* __restrict__ cache,
-                                           const double* __restrict__ base, long long base_pos,
-                                           double start, double fine_i0, long long F,
-                                           long long first_slot, int* err) {
+GW_SWEEP_FN void gw_sweep_fine(const float* __restrict__ fr, double* __restrict__ cache,
+                               const double* __restrict__ base, long long base_pos,
+                               double start, double fine_i0, long long F,
+                               long long first_slot, int* err) {
     using G = Gw<NW>;
     extern __shared__ double gw_lds[];
     float* xs = (float*)(gw_lds + TREC);
@@ -483,8 +494,8 @@ __device__ __noinline__ void gw_sweep_fine(const float* __restrict__ fr, double*
 
 // fused mode, tail segment: the moments of the turn frames [from, to) -> one packed record
 template <int NW>
-__device__ __noinline__ void gw_sweep_tail(const float* __restrict__ fr, long long from, long long to,
-                                           double* __restrict__ out, int* err) {
+GW_SWEEP_FN void gw_sweep_tail(const float* __restrict__ fr, long long from, long long to,
+                               double* __restrict__ out, int* err) {
     using G = Gw<NW>;
     extern __shared__ double gw_lds[];
     float* xs = (float*)(gw_lds + TREC);

@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Where k_gw spends its cycles: runs change detection on a synthetic batch through the
 profiling build of the library (make -C speaker-diarization_amd/csrc libspkd_hip_prof.so)
-and prints the per-phase clocks summed over workgroups.  Development tool only."""
+and prints the per-phase clocks summed over workgroups.  Development tool only.
+
+    python tools/gw_phase_profile.py [FILES [LIBRARY]]
+
+LIBRARY: another profiling build than csrc/libspkd_hip_prof.so (the parent's, for a before /
+after in one session)."""
 import ctypes as C
 import importlib
 import os
@@ -18,7 +23,8 @@ def main():
     files_n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
     import torch
     hipabi = importlib.import_module(PKG + '.hipabi')
-    lib = hipabi.load_library(os.path.join(ROOT, PKG, 'csrc', 'libspkd_hip_prof.so'))
+    lib = hipabi.load_library(os.path.abspath(sys.argv[2]) if len(sys.argv) > 2
+                              else os.path.join(ROOT, PKG, 'csrc', 'libspkd_hip_prof.so'))
     hipabi._lib = lib                      # every Context of this process uses the profiling build
     synth = importlib.import_module(PKG + '.synth')
     pipeline = importlib.import_module(PKG + '.pipeline')
