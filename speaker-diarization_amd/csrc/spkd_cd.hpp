@@ -560,13 +560,15 @@ __device__ __forceinline__ void single_split_matrix(int pass, const double* ldsE
 //   pooled [a, c): al =  0, ga = 1; v1 = s_c,       c1 = -v1 / N;   f = 1 / (N - 1)
 //                  (rec_b: any valid record, it is multiplied by zero)
 //   GLR: al1 P(b) + al2 (P(c) - P(b)) - be1 s1 s1^T - be2 s2 s2^T;  f = 1
-// two: the launch has GLR items (wave-uniform; the second rank-one term is skipped
-// otherwise).  DPP rows that name the same record (the left and the right item of a
-// new candidate sit side by side) fetch it once: their loads coalesce.
+// TWO: the launch has GLR items (a constant of the kernel instance: without it the second
+// rank-one term, its operands and the GLR weights are not compiled at all).  DPP rows that
+// name the same record (the left and the right item of a new candidate sit side by side)
+// fetch it once: their loads coalesce.
 // The split point b = (long long)(start + ik) is formed HERE, behind the record loads: ik is a
 // global load of the caller's (the candidate's i value), and a pass that needed it before it
 // could issue its record loads waited for two memory round trips, one after the other.
-__device__ __forceinline__ double quad_split_det(int pass, bool two, const double* ldsEnd,
+template <bool TWO>
+__device__ __forceinline__ double quad_split_det(int pass, const double* ldsEnd,
                                                     const double* __restrict__ rec_b,
                                                     double ik, double start, long long a, long long c,
                                                     const QuadLane& L, int* err) {
@@ -605,9 +607,9 @@ __device__ __forceinline__ double quad_split_det(int pass, bool two, const doubl
     {
         // (an IEEE fp64 division is ~25 instructions: the GLR weights are only formed in
         // launches that have GLR items, the covariance scale uses the Newton reciprocal)
-        const bool glr = two && pass == PASS_GLR;
+        const bool glr = TWO && pass == PASS_GLR;
         double al1 = 0.0, al2 = 0.0, b1 = 0.0, b2 = 0.0;
-        if (two) {                          // wave-uniform
+        if constexpr (TWO) {
             al1 = (n1 / n) / (n1 - 1.0);
             al2 = (n2 / n) / (n2 - 1.0);
             b1 = al1 / n1;
@@ -642,7 +644,7 @@ __device__ __forceinline__ double quad_split_det(int pass, bool two, const doubl
         __builtin_amdgcn_sched_barrier(0);
     }
     TriRank1<0>::run(q, c1, v1);
-    if (two) TriRank1<0>::run(q, c2, v2);
+    if constexpr (TWO) TriRank1<0>::run(q, c2, v2);
     auto form_single = [&](int mi, double (&arr)[DA]) {
         const double* rm = (const double*)__shfl((unsigned long long)rec_b, 16 * mi);
         single_split_matrix(__shfl(pass, 16 * mi), ldsEnd, rm, __shfl(n1, 16 * mi), __shfl(n2, 16 * mi), arr);
@@ -703,15 +705,28 @@ struct GwState {
     int tail_in_lds;       // the loop ended on a negative scan whose window end is the turn end
 };
 
-template <int NW>
-__global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void k_gw(
-        const float* __restrict__ frames, const TurnDesc* __restrict__ turns, spkd_cd_params P,
-        double* __restrict__ cache_all, double* __restrict__ cand_all,
-        int32_t* __restrict__ n_win, double* __restrict__ win_maxd, int32_t* __restrict__ win_det,
-        double* __restrict__ det_start, double* __restrict__ det_maxi, double* __restrict__ det_d,
-        double* __restrict__ final_start, double* __restrict__ seg_stats, spkd_cand_log* clog,
-        long long log_cap, unsigned long long* log_count, int* err,
-        double* pinv_ws) {
+// The distance kind is a constant of the instance (KIND: SPKD_BIC, SPKD_GLR or SPKD_KL2), as
+// it is in k_matrix<TWO> and k_ahc<TWO>: the one-wave BIC kernel sits at the register limit,
+// and with the kind as a runtime value it carried GLR's second rank-one term and weights and
+// KL2's whole single-matrix branch through the same register allocation -- spills in the
+// candidate-list loop, in the item loop's fast path and in phase (D) that BIC never needs.
+// The arithmetic of a kind is the same operations in the same order in every instance.
+// gw_body is the one body; the kernels below it (k_gw<NW>: BIC, k_gw_glr<NW>, k_gw_kl2<NW>)
+// are wrappers that name the kind.
+#define GW_KERNEL_PARAMS                                                                                    \
+        const float* __restrict__ frames, const TurnDesc* __restrict__ turns, spkd_cd_params P,             \
+        double* __restrict__ cache_all, double* __restrict__ cand_all,                                      \
+        int32_t* __restrict__ n_win, double* __restrict__ win_maxd, int32_t* __restrict__ win_det,          \
+        double* __restrict__ det_start, double* __restrict__ det_maxi, double* __restrict__ det_d,          \
+        double* __restrict__ final_start, double* __restrict__ seg_stats, spkd_cand_log* clog,              \
+        long long log_cap, unsigned long long* log_count, int* err, double* pinv_ws
+#define GW_KERNEL_ARGS                                                                                      \
+        frames, turns, P, cache_all, cand_all, n_win, win_maxd, win_det, det_start, det_maxi, det_d,        \
+        final_start, seg_stats, clog, log_cap, log_count, err, pinv_ws
+
+template <int NW, int KIND>
+__device__ __forceinline__ void gw_body(GW_KERNEL_PARAMS) {
+    static_assert(KIND == SPKD_BIC || KIND == SPKD_GLR || KIND == SPKD_KL2, "distance kind");
     extern __shared__ double gw_lds[];
     double* ldsEnd = gw_lds;                         // P(c), tri record
     constexpr int GW_WAVES = NW, GW_TPB = Gw<NW>::TPB;
@@ -730,7 +745,7 @@ __global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void k_gw(
     double* c_i = cand_all + 4 * T.cand_off;
     double* c_left = c_i + cap;
     double* c_x = c_left + cap;
-    double* c_w = c_x + cap;             // GLR: log det of the pooled-within matrix
+    [[maybe_unused]] double* c_w = c_x + cap;     // GLR: determinant of the pooled-within matrix
 
 #ifdef SPKD_PROFILE
     unsigned long long prof_acc[4] = {0ull, 0ull, 0ull, 0ull}, prof_t = clock64(), prof_scans = 0ull;
@@ -740,7 +755,7 @@ __global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void k_gw(
     // record 0 is read (times zero) by the pooled item even before it is built
     for (int e = tid; e < REC; e += GW_TPB) cache[e] = 0.0;
 
-    const int kind = P.kind;
+    constexpr int kind = KIND;
     const double winsize = P.winsize, winstep = P.winstep, rate = P.rate;
     const double minfeas = rate / 2;
     const double istep = rate / 10;
@@ -847,9 +862,8 @@ __global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void k_gw(
         const long long a = (long long)start, c = (long long)S.end;
         const long long base = S.base, count = S.count;
         {
-        const long long n_memo = S.n_memo;
-        const bool pooled = (kind == SPKD_BIC && !fine);
-        if (kind == SPKD_KL2) {
+        [[maybe_unused]] const long long n_memo = S.n_memo;
+        if constexpr (kind == SPKD_KL2) {
             // one wave per split point, single-matrix layout (Gauss-Jordan inverses)
             for (long long job = wave; job < count; job += GW_WAVES) {
                 const double ik = c_i[base + job];
@@ -884,7 +898,8 @@ __global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void k_gw(
             // GLR: (right, W) of every candidate | left of the new ones.
             const long long left0 = fine ? 0 : (n_memo < count ? n_memo : count);
             const long long nnew = count - left0;
-            const bool glr_kind = kind == SPKD_GLR;
+            constexpr bool glr_kind = kind == SPKD_GLR;
+            const bool pooled = (kind == SPKD_BIC && !fine);
             const long long padA = glr_kind ? 0 : (left0 & 1);
             const long long base2 = left0 + padA;
             const long long M = glr_kind ? 2 * count + nnew
@@ -935,13 +950,13 @@ __global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void k_gw(
                 // finite record of this or an earlier epoch, or zero-initialised scratch)
                 const double ik = count > 0 ? c_i[slot] : 0.0;
                 // determinants; their logs are taken in phase (D), one thread per candidate
-                const double v = quad_split_det(pass, glr_kind, ldsEnd, cache + slot * REC, ik, start, a, c, L, err);
+                const double v = quad_split_det<glr_kind>(pass, ldsEnd, cache + slot * REC, ik, start, a, c, L, err);
                 if (valid && L.t == 0) {
                     if (pass == PASS_POOLED) s_ldS = v;
                     else if (pass == PASS_RIGHT) c_x[slot] = v;
                     // left term, memoised per i inside an epoch (CD:84-90)
                     else if (pass == PASS_LEFT) c_left[slot] = v;
-                    else c_w[slot] = v;
+                    else if constexpr (glr_kind) c_w[slot] = v;
                 }
             }
         }
@@ -982,17 +997,19 @@ __global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void k_gw(
                 const double n1 = (double)(b - a), n2 = (double)(c - b);
                 double d = on ? c_x[slot] : 1.0;
                 double lgL = 0.0, lgR = 0.0, lgW = 0.0;
-                if (on && kind != SPKD_KL2) {
-                    lgL = log(c_left[slot]);
-                    lgR = log(d);
-                    if (kind == SPKD_GLR) lgW = log(c_w[slot]);
+                if constexpr (kind != SPKD_KL2) {
+                    if (on) {
+                        lgL = log(c_left[slot]);
+                        lgR = log(d);
+                        if constexpr (kind == SPKD_GLR) lgW = log(c_w[slot]);
+                    }
                 }
                 if (k0 == 0) __syncthreads();                          // s_common is there
                 if (!on) continue;
                 const double ldS = s_common[0], corr = s_common[1];
-                if (kind == SPKD_GLR) {
+                if constexpr (kind == SPKD_GLR) {
                     d = -(N / 2.0) * ((n1 / N) * lgL + (n2 / N) * lgR - lgW);
-                } else if (kind == SPKD_BIC) {
+                } else if constexpr (kind == SPKD_BIC) {
                     const double left = 0.5 * n1 * lgL;                   // BIC's memoised 0.5 N1 log det S1
                     d = 0.5 * N * ldS - left - 0.5 * n2 * lgR;
                     d -= corr;
@@ -1137,6 +1154,20 @@ __global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void k_gw(
     if (lane == 0) atomicAdd(&g_gw_prof[6], prof_passes);
 #endif
 }
+
+// The kernels: BIC keeps the name k_gw<NW> (the tools and the listing tests look it up by
+// that symbol); the other two kinds are kernels of their own names.
+#define GW_KERNEL(NAME, KIND)                                                                       \
+    template <int NW>                                                                               \
+    __global__ __launch_bounds__(Gw<NW>::TPB, NW == 8 ? 1 : 2) void NAME(GW_KERNEL_PARAMS) {        \
+        gw_body<NW, KIND>(GW_KERNEL_ARGS);                                                          \
+    }
+GW_KERNEL(k_gw, SPKD_BIC)
+GW_KERNEL(k_gw_glr, SPKD_GLR)
+GW_KERNEL(k_gw_kl2, SPKD_KL2)
+#undef GW_KERNEL
+#undef GW_KERNEL_ARGS
+#undef GW_KERNEL_PARAMS
 
 // ---------------------------------------------------------------------------
 // Sliding window, batch form.

@@ -405,13 +405,20 @@ static spkd_status create_ctx(int device, void* stream, bool borrow, spkd_ctx** 
         }
     // k_gw carves its LDS dynamically: the size must fit the device and be admitted
     // for the kernel, or every later launch fails -- checked once, reported by spkd_gw
+    // (twelve kernels: a wave shape times a distance kind)
     int lds_max = 0;
+    const struct { const void* fn; int bytes; } gw_kernels[] = {
+#define SPKD_GW_SHAPE(NW_)                                                                                  \
+        {(const void*)k_gw<NW_>, Gw<NW_>::LDS_BYTES}, {(const void*)k_gw_glr<NW_>, Gw<NW_>::LDS_BYTES},     \
+        {(const void*)k_gw_kl2<NW_>, Gw<NW_>::LDS_BYTES}
+        SPKD_GW_SHAPE(8), SPKD_GW_SHAPE(4), SPKD_GW_SHAPE(2), SPKD_GW_SHAPE(1)
+#undef SPKD_GW_SHAPE
+    };
     c->gw_lds_ok = hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess &&
-                   Gw<4>::LDS_BYTES <= lds_max &&
-                   hipFuncSetAttribute((const void*)k_gw<8>, hipFuncAttributeMaxDynamicSharedMemorySize, Gw<8>::LDS_BYTES) == hipSuccess &&
-                   hipFuncSetAttribute((const void*)k_gw<4>, hipFuncAttributeMaxDynamicSharedMemorySize, Gw<4>::LDS_BYTES) == hipSuccess &&
-                   hipFuncSetAttribute((const void*)k_gw<2>, hipFuncAttributeMaxDynamicSharedMemorySize, Gw<2>::LDS_BYTES) == hipSuccess &&
-                   hipFuncSetAttribute((const void*)k_gw<1>, hipFuncAttributeMaxDynamicSharedMemorySize, Gw<1>::LDS_BYTES) == hipSuccess;
+                   Gw<4>::LDS_BYTES <= lds_max;
+    for (const auto& k : gw_kernels)
+        c->gw_lds_ok = c->gw_lds_ok &&
+                       hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes) == hipSuccess;
     // k_resample carves a tile's span and table dynamically, up to the whole LDS where the device admits it
     c->rs_lds_cap = 64 * 1024;
     if (lds_max > c->rs_lds_cap) {
@@ -1578,8 +1585,11 @@ spkd_status gw_impl(spkd_ctx* c, const GwIn& in, const GwOut& out, GwBatch* batc
     int nw = c->gw_waves;
     if (nw != 1 && nw != 2 && nw != 4 && nw != 8)
         nw = n_turns >= GW_WAVE_PER_TURN_FROM ? 1 : (n_turns <= GW_EIGHT_WAVES_UP_TO ? 8 : 4);
+    // the kernel instance of the call's kind (kernel_params: SPKD_KL2_PINV runs as SPKD_KL2);
+    // BIC is k_gw itself
 #define SPKD_GW_LAUNCH(NW_)                                                                                     \
-    hipLaunchKernelGGL(k_gw<NW_>, dim3((unsigned)n_turns), dim3(Gw<NW_>::TPB), Gw<NW_>::LDS_BYTES, c->stream, \
+    hipLaunchKernelGGL((P->kind == SPKD_GLR ? k_gw_glr<NW_> : P->kind == SPKD_KL2 ? k_gw_kl2<NW_> : k_gw<NW_>), \
+                       dim3((unsigned)n_turns), dim3(Gw<NW_>::TPB), Gw<NW_>::LDS_BYTES, c->stream,             \
                        in.d_frames, (const TurnDesc*)d_turns, *P, (double*)d_snap, (double*)d_cand,            \
                        ev.n_win, ev.win_maxd, ev.win_det, ev.det_start, ev.det_maxi, ev.det_d, ev.final_start,  \
                        in.d_seg_stats, (spkd_cand_log*)d_log, (long long)log_cap, c->d_counter, c->d_err,      \
