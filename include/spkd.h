@@ -101,6 +101,7 @@ enum {
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
     SPKD_T_POST_STATS, SPKD_T_BF_GCC, SPKD_T_BF_TRACK, SPKD_T_BF_SUM, SPKD_T_RESAMPLE, SPKD_T_FRAME_ENERGY, SPKD_T_ENERGY_SEEDS,
     SPKD_T_FEATURE_WARP, SPKD_T_TDOA_PACK, SPKD_T_TDOA_STATS, SPKD_T_TDOA_MODELS, SPKD_T_TDOA_SCORE,
+    SPKD_T_TDOA_CUTS, SPKD_T_TDOA_SPLIT,
     SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
     SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK, SPKD_T_FB_POSTERIOR,
     SPKD_T_IDENT_SCORES, SPKD_T_IDENT_ASSIGN, SPKD_T_BW_ACCUMULATE,
@@ -897,6 +898,72 @@ spkd_status spkd_tdoa_score(spkd_ctx *ctx, const int32_t *d_stream, int64_t n_en
                             const int32_t *h_live, int64_t n_seq, const int64_t *h_seq_begin,
                             const int64_t *h_seq_end, const int32_t *h_seq_file, const int32_t *h_seq_model,
                             const int32_t *h_seq_n_models, int32_t n_cols, double weight, float *d_scores);
+
+/* ---------------------------------------------------------------------------
+ * (6b4) Seats from the delay stream: where the delays of a file change, a talker has moved or another one
+ * speaks from another place.  Two calls on the exact integer records of spkd_tdoa_stats: the best cut of a
+ * frame range (behind change detection) and an agglomerative chain over the records of a group of segments
+ * (behind clustering).  Stated once in csrc/spkd_seat.hpp, for both kernels.
+ * PARITY: no reference counterpart; tests/seat_numpy.py restates every rule.
+ *
+ * The statistic.  A record is int64 [8][3], per channel (n, sum x, sum x^2), in frames.  For a file
+ *       w       = (double)(H * rate_out) / (double)(hop * rate_in)      (frames per step: an observation is a
+ *                                                                        step, the sums are in frames only
+ *                                                                        because ranges cut steps)
+ *       floor_f = (floor_s * (double)rate_in)^2                          (as spkd_tdoa_models)
+ *   and one channel of a record gives, every operation rounded on its own (no contraction), in this order,
+ *       dn = (double)n;  mean = (double)sx / dn;  v = (double)sxx / dn - mean * mean;
+ *       var = v > floor_f ? v : floor_f;  g = dn * log(var).
+ *   For two records A and B of one file, channel c counts iff n_A,c >= min_frames and n_B,c >= min_frames;
+ *   the reference channel and channels >= C never count.  Over the counted channels, ascending, from d = 0.0:
+ *       t = g(A_c + B_c) - g(A_c);  t = t - g(B_c);  t = 0.5 * t;  t = t / w;     (A_c + B_c: exact integer sums)
+ *       p = (double)(n_A,c + n_B,c) / w;  p = log(p);  p = lambdac * p;
+ *       d = d + (t - p).
+ *   Delta(A, B) = d, undefined when no channel counts.  Delta > threshold means two seats.  The earlier
+ *   record (the left side of a cut, the lower position of a pair) is A.
+ *
+ * spkd_tdoa_cuts: the stream, the file table and the clock as spkd_tdoa_stats takes them; n_ranges frame
+ *   ranges [begin, end) in the batch's numbering, each with its file.  The candidates of a range are the frames
+ *   t in (begin, end) with step(t) != step(t - 1), t - begin >= min_piece and end - t >= min_piece; a
+ *   candidate's value is Delta(record of [begin, t), record of [t, end)), the records weighted by frames
+ *   exactly as spkd_tdoa_stats weighs a step; a range may run past the file's last step (the clamp).
+ *   h_cut[r]: the candidate with the highest defined Delta, the lowest frame among equals, if that Delta >
+ *   threshold, else -1.  h_delta[r]: that highest Delta, cut or not; NaN when no candidate has a defined one
+ *   (a range inside one step, a one-channel file, an empty range).  A workgroup per range: totals first,
+ *   then tiles of 256 steps staged in LDS, exact int64 prefix sums carried tile to tile, a lane per candidate,
+ *   an arg-max with the tie rule.  No atomics; the bits do not depend on the other ranges of the call.
+ *   Refusals (SPKD_EINVAL before any device work): every argument spkd_tdoa_stats refuses, a range of 2^31
+ *   frames or more, min_piece < 1, min_frames < 1, a floor_s that is not finite and > 0, a lambdac that is
+ *   not finite, a NaN threshold.  n_ranges = 0: SPKD_OK without a launch.  Timer: SPKD_T_TDOA_CUTS.
+ * spkd_tdoa_split: problem p owns the records [h_off[p], h_off[p + 1]) of d_stats, int64 [n][8][3], and is of
+ *   file h_prob_file[p] of the file table (the clock gives w).  A record is placed iff some channel of it that
+ *   can count has n >= min_frames; unplaced records take no part.  A step looks over the live placed
+ *   clusters of the problem for the pair a < b with the lowest defined Delta, the first in row-major order on
+ *   a tie; the pair is merged iff not (Delta > threshold), otherwise the chain stops, as it does when no pair
+ *   has a defined Delta.  A merge is record[a] += record[b] in exact integers, then pop(b): spkd_ahc's log
+ *   convention, which spkd_labels_from_merges replays; only row and column a are computed again.  The log of
+ *   problem p (a, b, Delta; up to n_p - 1 entries) starts at h_off[p], as spkd_ahc's does, and has
+ *   h_n_merges[p] entries; h_placed [n]: 1 for a placed record.  d_stats is not modified.  One workgroup per
+ *   problem, all problems in one launch; the matrix is n_p^2 doubles of device scratch, the per-row best
+ *   waits in LDS.  The bits of a problem's log depend neither on the grid nor on the other problems.
+ *   Limit: n_p <= SPKD_SEAT_MAX_N = 4096, above that SPKD_EINVAL.  Problems of 0 or 1 records: no merges.
+ *   Refusals: a bad file table or clock, offsets that do not start at 0 or descend, a file index out of
+ *   range, the four settings as above, null arrays.  n_problems = 0: SPKD_OK without a launch.
+ *   Timer: SPKD_T_TDOA_SPLIT. */
+#define SPKD_SEAT_MAX_N 4096
+spkd_status spkd_tdoa_cuts(spkd_ctx *ctx, const int32_t *d_stream, int64_t n_entries,
+                           const int64_t *h_files /* [n_files][SPKD_TDOA_FILE] */, int64_t n_files,
+                           int32_t hop, int32_t window, int32_t rate_out,
+                           const int64_t *h_begin, const int64_t *h_end, const int32_t *h_file,
+                           int64_t n_ranges, int64_t min_piece, int32_t min_frames, double floor_s,
+                           double lambdac, double threshold, int64_t *h_cut /* out [n_ranges] */,
+                           double *h_delta /* out [n_ranges] */);
+spkd_status spkd_tdoa_split(spkd_ctx *ctx, const int64_t *d_stats, int64_t n_problems,
+                            const int64_t *h_off /* [n_problems + 1] */, const int32_t *h_prob_file,
+                            const int64_t *h_files, int64_t n_files, int32_t hop, int32_t window,
+                            int32_t rate_out, int32_t min_frames, double floor_s, double lambdac,
+                            double threshold, int32_t *h_merge_a, int32_t *h_merge_b, double *h_merge_d,
+                            int32_t *h_n_merges /* out [n_problems] */, int32_t *h_placed /* out [n] */);
 
 /* ---------------------------------------------------------------------------
  * (6c) The seed stage of a speech / non-speech detector trained on the recording itself: frame

@@ -26,6 +26,7 @@
 #include "spkd_resample.hpp"
 #include "spkd_beamform.hpp"
 #include "spkd_tdoa.hpp"
+#include "spkd_seat.hpp"
 #include "spkd_energy.hpp"
 #include "spkd_vad.hpp"
 #include "spkd_vad_batch.hpp"
@@ -41,14 +42,14 @@
 using namespace spkd;
 
 namespace {
-constexpr int N_SLOTS = 80;
+constexpr int N_SLOTS = 88;
 // Pinned host buffers, each named where it is used (stage(), TokenHandBack, the batch hand-off).  A slot belongs
 // to one block of one entry point: what a call leaves there for its caller (the hand-off's results, a decoder's
 // tokens) stays valid until that entry point is called again, so two calls whose results can be live together
 // never share a slot; nor do the block that goes up and the block that comes down in one call.
 enum { PIN_GW_TURNS = 0, PIN_GW_LINES, PIN_AHC_OUT, PIN_VAD_FILES, PIN_VAD_TOKENS, PIN_SUM_IDX, PIN_GAUSS_IDX,
        PIN_GT_TAB, PIN_GT_OUT, PIN_GT_IDX, PIN_UBM_TAB, PIN_UBM_OUT, PIN_CLR_IN, PIN_CLR_OUT, PIN_MD_SEQS, PIN_MD_TOKENS,
-       PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, PIN_POST_TAB, PIN_ES_FILES, PIN_ES_RUNS, PIN_WARP_TAB, PIN_TD_TAB, N_PIN };
+       PIN_FB_TAB, PIN_ID_IN, PIN_ID_OUT, PIN_ACC_TAB, PIN_POST_TAB, PIN_ES_FILES, PIN_ES_RUNS, PIN_WARP_TAB, PIN_TD_TAB, PIN_SEAT_OUT, N_PIN };
 }
 
 struct spkd_ctx {
@@ -366,7 +367,7 @@ enum {
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
     S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT,
     S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_FB_TAB, S_FB_FWD, S_FB_OUT,
-    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_BF_TAB, S_BF_TW, S_BF_ENERGY, S_BF_BACK, S_EN_TAB, S_ES_TAB, S_ES_FILES, S_ES_RUNS, S_WARP_TAB, S_TD_TAB, S_COUNT
+    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_BF_TAB, S_BF_TW, S_BF_ENERGY, S_BF_BACK, S_EN_TAB, S_ES_TAB, S_ES_FILES, S_ES_RUNS, S_WARP_TAB, S_TD_TAB, S_SEAT_OUT, S_SEAT_WORK, S_SEAT_MAT, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -2821,6 +2822,143 @@ spkd_status spkd_tdoa_score(spkd_ctx* c, const int32_t* d_stream, int64_t n_entr
     }
     HIPCHK(c, hipGetLastError());
     return call.finish();
+}
+
+// ------------------------------------------------------------------ (6b4) seats from the delay stream
+static_assert(SEAT_MAX_N == SPKD_SEAT_MAX_N, "the header states the chain's limit");
+
+namespace {
+// the four settings of the statistic (`name` opens the messages)
+spkd_status seat_settings(spkd_ctx* c, const std::string& name, int32_t min_frames, double floor_s, double lambdac, double threshold) {
+    if (min_frames < 1) return fail(c, SPKD_EINVAL, name + ": min_frames >= 1");
+    if (!(floor_s > 0.0) || !(floor_s < INFINITY)) return fail(c, SPKD_EINVAL, name + ": floor_s a finite number > 0");
+    if (!std::isfinite(lambdac)) return fail(c, SPKD_EINVAL, name + ": lambdac a finite number");
+    if (std::isnan(threshold)) return fail(c, SPKD_EINVAL, name + ": threshold is NaN");
+    return SPKD_OK;
+}
+}  // namespace
+
+spkd_status spkd_tdoa_cuts(spkd_ctx* c, const int32_t* d_stream, int64_t n_entries, const int64_t* h_files, int64_t n_files,
+                           int32_t hop, int32_t window, int32_t rate_out, const int64_t* h_begin, const int64_t* h_end,
+                           const int32_t* h_file, int64_t n_ranges, int64_t min_piece, int32_t min_frames, double floor_s,
+                           double lambdac, double threshold, int64_t* h_cut, double* h_delta) {
+    if (!c || n_ranges < 0) return SPKD_EINVAL;
+    TdoaClock K;
+    TRY(tdoa_files(c, "tdoa_cuts", h_files, n_files, n_entries, hop, window, rate_out, &K));
+    if (min_piece < 1) return fail(c, SPKD_EINVAL, "tdoa_cuts: min_piece >= 1");
+    TRY(seat_settings(c, "tdoa_cuts", min_frames, floor_s, lambdac, threshold));
+    if (n_ranges > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_cuts: too many ranges in one call");
+    if (n_ranges == 0) return SPKD_OK;
+    if (!h_begin || !h_end || !h_file || !h_cut || !h_delta) return fail(c, SPKD_EINVAL, "tdoa_cuts: null range arrays");
+    bool steps = false;
+    for (int64_t r = 0; r < n_ranges; ++r) {
+        TRY(tdoa_range(c, "tdoa_cuts", h_files, n_files, K, h_file[r], h_begin[r], h_end[r]));
+        if (h_end[r] - h_begin[r] > 0x7fffffffLL) return fail(c, SPKD_EINVAL, "tdoa_cuts: a range of 2^31 frames or more");
+        const int64_t* F = h_files + (int64_t)h_file[r] * TD_FILE;
+        steps = steps || (h_end[r] > h_begin[r] && F[TDF_C] > 1 && F[TDF_T] > 0);
+    }
+    if (steps && (!d_stream || (uintptr_t)d_stream % 4)) return fail(c, SPKD_EINVAL, "tdoa_cuts: null or misaligned stream");
+    const size_t nr = (size_t)n_ranges, nf = (size_t)n_files;
+    struct Tab { long long *files, *begin, *end; int* file; };
+    auto t = mirror<Tab>([&](Layout L, Tab& p) { return L.part(p.files, nf * TD_FILE).part(p.begin, nr).part(p.end, nr).part(p.file, nr).bytes(); });
+    struct Out { long long* cut; double* delta; };
+    auto out = mirror<Out>([&](Layout L, Out& o) { return L.part(o.cut, nr).part(o.delta, nr).bytes(); });
+    TRY(stage(c, PIN_TD_TAB, t));
+    TRY(stage(c, PIN_SEAT_OUT, out));
+    std::memcpy(t.h.files, h_files, nf * TD_FILE * sizeof(int64_t));
+    std::memcpy(t.h.begin, h_begin, nr * sizeof(int64_t));
+    std::memcpy(t.h.end, h_end, nr * sizeof(int64_t));
+    std::memcpy(t.h.file, h_file, nr * sizeof(int32_t));
+    Call call(c);
+    TRY(call.opened);
+    TRY(send(call, S_TD_TAB, t));
+    TRY(carve(c, scratch, S_SEAT_OUT, [&](Layout L) { return place(L, out).bytes(); }));
+    {
+        Timer tm(c, SPKD_T_TDOA_CUTS);
+        hipLaunchKernelGGL(k_tdoa_cuts, dim3((unsigned)nr), dim3(SEAT_TPB), 0, c->stream, d_stream, (const long long*)t.d.files, K,
+                           (const long long*)t.d.begin, (const long long*)t.d.end, (const int*)t.d.file, (long long)min_piece,
+                           (int)min_frames, floor_s, lambdac, threshold, out.d.cut, out.d.delta);
+    }
+    HIPCHK(c, hipGetLastError());
+    TRY(copy(call, out, hipMemcpyDeviceToHost));
+    TRY(call.finish());
+    std::memcpy(h_cut, out.h.cut, nr * sizeof(int64_t));
+    std::memcpy(h_delta, out.h.delta, nr * sizeof(double));
+    return SPKD_OK;
+}
+
+spkd_status spkd_tdoa_split(spkd_ctx* c, const int64_t* d_stats, int64_t n_problems, const int64_t* h_off,
+                            const int32_t* h_prob_file, const int64_t* h_files, int64_t n_files, int32_t hop, int32_t window,
+                            int32_t rate_out, int32_t min_frames, double floor_s, double lambdac, double threshold,
+                            int32_t* h_merge_a, int32_t* h_merge_b, double* h_merge_d, int32_t* h_n_merges, int32_t* h_placed) {
+    if (!c || n_problems < 0) return SPKD_EINVAL;
+    TdoaClock K;
+    TRY(tdoa_files(c, "tdoa_split", h_files, n_files, INT64_MAX, hop, window, rate_out, &K));
+    TRY(seat_settings(c, "tdoa_split", min_frames, floor_s, lambdac, threshold));
+    if (n_problems > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_split: too many problems in one call");
+    if (n_problems == 0) return SPKD_OK;
+    if (!h_off || !h_prob_file || !h_n_merges) return fail(c, SPKD_EINVAL, "tdoa_split: null problem arrays");
+    if (h_off[0] != 0) return fail(c, SPKD_EINVAL, "tdoa_split: the offsets must start at 0");
+    size_t cells = 0;
+    for (int64_t p = 0; p < n_problems; ++p) {
+        const int64_t n = h_off[p + 1] - h_off[p];
+        if (n < 0) return fail(c, SPKD_EINVAL, "tdoa_split: the offsets must be non-decreasing");
+        if (n > SEAT_MAX_N) return fail(c, SPKD_EINVAL, "tdoa_split: at most 4096 records a problem");
+        if (h_prob_file[p] < 0 || h_prob_file[p] >= n_files) return fail(c, SPKD_EINVAL, "tdoa_split: file index out of range");
+        cells += n > 1 ? (size_t)n * (size_t)n : 0;
+    }
+    const int64_t n_rec = h_off[n_problems];
+    if (n_rec > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_split: too many records in one call");
+    const size_t np = (size_t)n_problems, ns = (size_t)n_rec, nf = (size_t)n_files;
+    if (ns == 0) {
+        std::memset(h_n_merges, 0, np * sizeof(int32_t));
+        return SPKD_OK;
+    }
+    if (!h_merge_a || !h_merge_b || !h_merge_d || !h_placed) return fail(c, SPKD_EINVAL, "tdoa_split: null result arrays");
+    if (!d_stats || (uintptr_t)d_stats % 8) return fail(c, SPKD_EINVAL, "tdoa_split: null or misaligned statistics");
+    struct Tab { long long *files, *off, *mat_off; int* file; };
+    auto t = mirror<Tab>([&](Layout L, Tab& p) { return L.part(p.files, nf * TD_FILE).part(p.off, np + 1).part(p.mat_off, np).part(p.file, np).bytes(); });
+    struct Out { double* d; int32_t *a, *b, *nm, *placed; };
+    auto out = mirror<Out>([&](Layout L, Out& o) { return L.part(o.d, ns).part(o.a, ns).part(o.b, ns).part(o.nm, np).part(o.placed, ns).bytes(); });
+    TRY(stage(c, PIN_TD_TAB, t));
+    TRY(stage(c, PIN_SEAT_OUT, out));
+    std::memcpy(t.h.files, h_files, nf * TD_FILE * sizeof(int64_t));
+    std::memcpy(t.h.off, h_off, (np + 1) * sizeof(int64_t));
+    std::memcpy(t.h.file, h_prob_file, np * sizeof(int32_t));
+    {
+        long long at = 0;
+        for (size_t p = 0; p < np; ++p) {
+            const long long n = h_off[p + 1] - h_off[p];
+            t.h.mat_off[p] = at;
+            at += n > 1 ? n * n : 0;
+        }
+    }
+    Call call(c);
+    TRY(call.opened);
+    TRY(send(call, S_TD_TAB, t));
+    long long* d_w = nullptr;
+    void* d_mat = nullptr;
+    TRY(carve(c, scratch, S_SEAT_WORK, [&](Layout L) { return place(L, out).part(d_w, ns * SEAT_REC).bytes(); }));
+    TRY(scratch(c, S_SEAT_MAT, cells * sizeof(double), &d_mat));
+    {
+        Timer tm(c, SPKD_T_TDOA_SPLIT);
+        hipLaunchKernelGGL(k_tdoa_split, dim3((unsigned)np), dim3(SEAT_CHAIN_TPB), 0, c->stream, (const long long*)d_stats,
+                           (const long long*)t.d.files, K, (const long long*)t.d.off, (const int*)t.d.file,
+                           (const long long*)t.d.mat_off, (int)min_frames, floor_s, lambdac, threshold, d_w, (double*)d_mat,
+                           (int*)out.d.a, (int*)out.d.b, out.d.d, (int*)out.d.nm, (int*)out.d.placed);
+    }
+    HIPCHK(c, hipGetLastError());
+    TRY(copy(call, out, hipMemcpyDeviceToHost));
+    TRY(call.finish());
+    std::memcpy(h_n_merges, out.h.nm, np * sizeof(int32_t));
+    std::memcpy(h_placed, out.h.placed, ns * sizeof(int32_t));
+    for (size_t p = 0; p < np; ++p) {                                    // (what lies behind a problem's log is not defined)
+        const size_t o = (size_t)h_off[p], k = (size_t)out.h.nm[p];
+        std::memcpy(h_merge_a + o, out.h.a + o, k * sizeof(int32_t));
+        std::memcpy(h_merge_b + o, out.h.b + o, k * sizeof(int32_t));
+        std::memcpy(h_merge_d + o, out.h.d + o, k * sizeof(double));
+    }
+    return SPKD_OK;
 }
 
 // ------------------------------------------------------------------ (6c) frame energies and their seeds

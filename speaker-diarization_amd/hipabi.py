@@ -18,7 +18,7 @@ TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pai
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
                                         'post_stats', 'bf_gcc', 'bf_track', 'bf_sum', 'resample', 'frame_energy', 'energy_seeds',
-                                        'feature_warp', 'tdoa_pack', 'tdoa_stats', 'tdoa_models', 'tdoa_score', 'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
+                                        'feature_warp', 'tdoa_pack', 'tdoa_stats', 'tdoa_models', 'tdoa_score', 'tdoa_cuts', 'tdoa_split', 'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
                                         'mindur_viterbi', 'mindur_backtrack', 'fb_posterior',
                                         'ident_scores', 'ident_assign', 'bw_accumulate',
                                         'mfcc_static', 'mfcc_post'])}
@@ -56,6 +56,7 @@ TDOA_MAX_DELAY = 4096       # SPKD_TDOA_MAX_DELAY: the largest |delay| of an ent
 TDOA_FILE = 8               # SPKD_TDOA_FILE: int64 per file of the stream's host table
 TDOA_MODEL = 4              # SPKD_TDOA_MODEL: doubles per (speaker, channel): mean, var, 1 / (2 var), -1/2 log(2 pi var)
 TDOA_TILE = 256             # SPKD_TDOA_TILE: frames per workgroup of k_tdoa_score, steps per workgroup of k_tdoa_stats
+SEAT_MAX_N = 4096           # SPKD_SEAT_MAX_N: records of one problem of spkd_tdoa_split
 WARP_MAX_WINDOW = 512       # SPKD_WARP_MAX_WINDOW: the widest window of spkd_feature_warp, in frames
 WARP_TILE = 384             # SPKD_WARP_TILE: compacted frames per workgroup of k_feature_warp
 REC = 820
@@ -65,7 +66,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_last_ahc_head', 'spkd_ahc_head_rule', 'spkd_set_stats', 'spkd_pair_terms',
            'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_sum_stats', 'spkd_mfcc', 'spkd_mfcc_batch', 'spkd_resample_batch', 'spkd_bf_gcc', 'spkd_bf_track', 'spkd_bf_sum',
-           'spkd_tdoa_pack', 'spkd_tdoa_stats', 'spkd_tdoa_models', 'spkd_tdoa_score',
+           'spkd_tdoa_pack', 'spkd_tdoa_stats', 'spkd_tdoa_models', 'spkd_tdoa_score', 'spkd_tdoa_cuts', 'spkd_tdoa_split',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
@@ -248,6 +249,8 @@ def load_library(path=None):
     lib.spkd_tdoa_stats.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp, i64, i64, vp]
     lib.spkd_tdoa_models.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, dbl, vp, vp]
     lib.spkd_tdoa_score.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, dbl, vp]
+    lib.spkd_tdoa_cuts.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, i64, i64, i32, dbl, dbl, dbl, vp, vp]
+    lib.spkd_tdoa_split.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, dbl, dbl, dbl, vp, vp, vp, vp, vp]
     lib.spkd_frame_energy_batch.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
     lib.spkd_energy_seeds.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, P(vp), P(vp), P(vp)]
     lib.spkd_sw_window_count.argtypes = [i64, dbl, dbl]
@@ -915,6 +918,44 @@ class Context(object):
             raise SpkdError(SPKD_EINVAL, 'one begin, end, file and set per range')
         self.check(self.lib.spkd_tdoa_stats(self.h, *args, _ptr(b), _ptr(e), _ptr(f), _ptr(s), len(b), int(n_sets),
                                             C.c_void_p(d_stats)))
+
+    def tdoa_cuts(self, stream, begins, ends, files, min_piece, min_frames, floor_s, lambdac, threshold):
+        """The best seat cut of every frame range (spkd_tdoa_cuts; include/spkd.h (6b4)): stream as _tdoa_stream takes
+        it, the ranges [begin, end) in the batch's numbering, each with its file.  Returns (cut int64 [n]: the frame,
+        -1 for none; delta float64 [n]: the highest Delta of the range, NaN when none is defined).  Time:
+        last_ms('tdoa_cuts')."""
+        args, _keep = self._tdoa_stream(stream)
+        b = np.ascontiguousarray(begins, dtype=np.int64)
+        e = np.ascontiguousarray(ends, dtype=np.int64)
+        f = np.ascontiguousarray(files, dtype=np.int32)
+        if not (b.ndim == 1 and len(b) == len(e) == len(f)):
+            raise SpkdError(SPKD_EINVAL, 'one begin, end and file per range')
+        cut, delta = np.full(len(b), -1, dtype=np.int64), np.full(len(b), np.nan)
+        self.check(self.lib.spkd_tdoa_cuts(self.h, *args, _ptr(b), _ptr(e), _ptr(f), len(b), int(min_piece), int(min_frames),
+                                           float(floor_s), float(lambdac), float(threshold), _ptr(cut), _ptr(delta)))
+        return cut, delta
+
+    def tdoa_split(self, d_stats, off, prob_file, table, clock, min_frames, floor_s, lambdac, threshold):
+        """One agglomerative chain per problem over the delay records at d_stats (spkd_tdoa_split): problem p owns the
+        records off[p] .. off[p + 1] and is of file prob_file[p] of table, the stream's file table; clock = (hop,
+        window, rate_out).  Returns dict(n_merges int32 [problems], a, b int32 [n], d float64 [n], placed int32 [n]):
+        the log of problem p at off[p], in spkd_ahc's convention (labels_from_merges_batch replays it).  Time:
+        last_ms('tdoa_split')."""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        pf = np.ascontiguousarray(prob_file, dtype=np.int32)
+        table = np.ascontiguousarray(table, dtype=np.int64)
+        if table.ndim != 2 or table.shape[1] != TDOA_FILE:
+            raise SpkdError(SPKD_EINVAL, 'the delay stream\'s file table: [n_files, %d] int64' % TDOA_FILE)
+        if off.ndim != 1 or len(off) != len(pf) + 1:
+            raise SpkdError(SPKD_EINVAL, 'one file per problem and one offset more')
+        n = max(int(off[-1]), 0)
+        a, b, d = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n)
+        nm, placed = np.zeros(len(pf), dtype=np.int32), np.zeros(n, dtype=np.int32)
+        hop, window, rate_out = (int(v) for v in clock)
+        self.check(self.lib.spkd_tdoa_split(self.h, C.c_void_p(d_stats), len(pf), _ptr(off), _ptr(pf), _ptr(table), len(table),
+                                            hop, window, rate_out, int(min_frames), float(floor_s), float(lambdac),
+                                            float(threshold), _ptr(a), _ptr(b), _ptr(d), _ptr(nm), _ptr(placed)))
+        return dict(n_merges=nm, a=a, b=b, d=d, placed=placed)
 
     def tdoa_models(self, d_stats, spk_file, ok, table, min_frames, floor_s, d_models):
         """One Gaussian per (speaker, channel) from d_stats (spkd_tdoa_models) into d_models double [n, 8,

@@ -18,6 +18,7 @@ import numpy as np
 from . import exp_generator, frontend, hipabi, voice_detection
 from . import linking as _linking
 from . import resegmentation as _resegmentation
+from . import seats as _seats
 from . import self_vad as _self_vad
 from .recipe import py2_float_str
 # the linking stage (linking.py, on clr_model.py and gallery.py): its settings and its entry point under their names here
@@ -25,6 +26,8 @@ from .linking import LINK_CL, LINK_CLR, LINK_CLR_WARP, _link_model, link_batch, 
 # the resegmentation stage (resegmentation.py): its settings and its entry point under their names here
 from .resegmentation import (FB_MAX_SCALED_PENALTY, RESEG, RESEG_CONF, RESEG_GMM, RESEG_MAX_SPEAKERS, RESEG_MD,
                              RESEG_SOFT, RESEG_SOFT_SCALE, RESEG_TDOA, TDOA, resegment_batch)
+# the seat stages behind change detection and clustering (seats.py): their settings and entry points under their names here
+from .seats import SEATS, seat_cut_batch, seat_split_batch
 # the self-trained speech / non-speech detector (self_vad.py): its settings under their name here
 from .self_vad import SELF_VAD
 # the tables every stage reads (tables.py), under their names here
@@ -130,7 +133,8 @@ def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=Non
     (features_batch with cfg, the fconfig.cfg chain) both from it, then diarize_batch with the
     turns and the frames as they lie on the device.  uploaded: the samples already on the device
     (frontend.upload_batch or frontend.resample_batch; pcms is not read then).  kw: diarize_batch's
-    text_contract, fused, handoff, link, reseg, detail, delays (the frontend.DelayStream of reseg['tdoa']).  Returns its rows.
+    text_contract, fused, handoff, link, reseg, seats, detail, delays (the frontend.DelayStream of reseg['tdoa'] and of
+    seats).  Returns its rows.
     model: a dictionary like SELF_VAD instead of a VadModel needs no model file: one upload, ONE
     feature chain (cfg's), the self-trained turns on those features (vad_batch), then diarize_batch;
     detail, if given, also receives vad_untrained and vad_passes_run."""
@@ -167,7 +171,8 @@ def diarize_audio_batch(ctx, model, cfg, audios, cd=DIA2_CD, cl=DIA2_CL, timings
     GCC-PHAT delays and summed: frontend.resample_batch).  reseg=dict(..., tdoa=...) with beamform: the
     delays the beamformer tracks are kept (a frontend.DelayStream on cfg's frame clock, made here unless
     delays= hands one in) and the resegmentation stage reads them as a second stream (resegment_batch);
-    tdoa without beamform is a ValueError.  Returns its rows."""
+    tdoa without beamform is a ValueError.  seats=<a dictionary like SEATS> with beamform takes the same stream (one
+    serves both) to the seat stages of diarize_batch; seats without beamform is a ValueError.  Returns its rows."""
     if isinstance(model, dict):
         _self_vad._options(model)
     else:
@@ -176,6 +181,12 @@ def diarize_audio_batch(ctx, model, cfg, audios, cd=DIA2_CD, cl=DIA2_CL, timings
     if kw.get('reseg') is not None and _resegmentation._reseg_tdoa(kw['reseg']) is not None:
         if beamform is None:
             raise ValueError('reseg tdoa: the delays are the beamformer\'s, which takes beamform=')
+        if delays is None:
+            delays = frontend.DelayStream(ctx, cfg.hop, cfg.window_width, cfg.sample_rate)
+    if kw.get('seats') is not None:
+        _seats._seat_options(kw['seats'], float(cfg.frame_rate))
+        if beamform is None:
+            raise ValueError('seats: the delays are the beamformer\'s, which takes beamform=')
         if delays is None:
             delays = frontend.DelayStream(ctx, cfg.hop, cfg.window_width, cfg.sample_rate)
     if beamform is not None:
@@ -592,7 +603,7 @@ def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2
 
 
 def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl=DIA2_CL, timings=None,
-                  text_contract=True, fused=False, handoff=None, link=None, detail=None, reseg=None, delays=None):
+                  text_contract=True, fused=False, handoff=None, link=None, detail=None, reseg=None, delays=None, seats=None):
     """CD (gw/BIC) + CL (hi/BIC) for a batch; returns per file an array of rows
     [start_s, end_s, speaker] in recipe order.
     cl['method'] = 'in' clusters with spk_cluster_in (cluster_batch): host hand-off only; the
@@ -635,8 +646,17 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     A dictionary like RESEG_SOFT retrains the speakers between the passes on frame posteriors instead of
     decoded rows (reseg['soft'], reseg['soft_scale']; detail['soft_mass'] as there).  A dictionary like
     RESEG_TDOA adds the microphone array's delays as a second stream (reseg['tdoa'], with delays=<the
-    frontend.DelayStream the beamformer filled>; detail['tdoa_channels'] as there); clustering and linking
-    stay acoustic."""
+    frontend.DelayStream the beamformer filled>; detail['tdoa_channels'] as there).
+    seats: a dictionary like SEATS, with delays=<the same stream>: the delays also reach the two stages that decide
+    how many talkers a file has.  The segments change detection returns are cut where their delays change
+    (seat_cut_batch) before clustering, and the labels clustering returns are split where an acoustic cluster sits at
+    two places (seat_split_batch) before resegmentation, linking or the rows read them; linking then runs on the
+    pieces' records and stays acoustic (seats do not carry from one room to another).  Host hand-off only and not
+    fused (the fused records belong to the uncut segments), cl method hi only; seats without delays, a stream of
+    another file count or frame clock, unknown keys or bad values: ValueError before any device work.  More than 16
+    speakers in a file after a split, under reseg, is resegment_batch's ValueError.  detail['seats'] = dict(cuts,
+    passes_run, split, unplaced) as the two stages leave them; timings: seat_cuts, seat_stats, seat_split.  A talker
+    who moves is split; two talkers who share a seat are left to the acoustics.  seats=None: today's calls and rows."""
     method = _method(cl)
     # the hand-off this call gets: the one asked for, else the device's where it can serve (a detector that
     # passes its refusal below is neither fused nor on the device, so the rule reads the same behind it)
@@ -647,6 +667,14 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
             raise ValueError('reseg takes the host hand-off')
         if reseg_opts.tdoa:
             _resegmentation._check_delays(delays, reseg_opts, files, float(rate), True)
+    if seats is not None:
+        _seats._seat_options(seats, rate)
+        if device or fused:
+            raise ValueError('seats take the host hand-off and are not fused: the fused records belong to the uncut segments')
+        if method != 'hi':
+            raise ValueError('seats split the clusters of cl method hi')
+        _seats._check_delays(delays, files, float(rate))
+        _seats._empty_detail(detail, len(files))
     if _cd_method(cd) in ('sw', 'm'):
         if fused or handoff == 'device':
             raise ValueError('cd method %s takes the host hand-off and is not fused' % _cd_method(cd))
@@ -675,8 +703,10 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
         if reseg is not None:
             _resegmentation._empty_detail(detail, reseg_opts, len(files))
         return [np.zeros((0, 3)) for _ in files]
+    if seats is not None:
+        segs = seat_cut_batch(ctx, files, segs, delays, rate, seats, text_contract, timings, detail)
     return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail, reseg,
-                              text_contract, delays)
+                              text_contract, delays, seats)
 
 
 def warp_batch(ctx, d_frames, total_frames, files, segments, rate, warp_s, d_out=None):
@@ -698,13 +728,15 @@ def warp_batch(ctx, d_frames, total_frames, files, segments, rate, warp_s, d_out
 
 
 def _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link=None, detail=None,
-                       reseg=None, text_contract=True, delays=None):
+                       reseg=None, text_contract=True, delays=None, seats=None):
     box = None if link is None and reseg is None else []
     res = cluster_batch(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fused=fs, stats_out=box)
     cnt = [len(s) for s in segs]
     if sum(cnt) == 0:
         return [np.zeros((0, 3)) for _ in segs]
     own = [lab for (lab, _) in res]
+    if seats is not None:
+        own = seat_split_batch(ctx, files, segs, own, delays, rate, seats, timings, detail)
     if reseg is not None:
         rows = resegment_batch(ctx, d_frames, total_frames, files, box[0][0], box[0][1], own, rate, reseg,
                                text_contract, timings, detail, segs, delays)
