@@ -101,7 +101,7 @@ enum {
     SPKD_T_VAD_SHIFT, SPKD_T_VAD_VITERBI, SPKD_T_VAD_BACKTRACK, SPKD_T_GAUSS_MODELS, SPKD_T_GAUSS_LOGLIK,
     SPKD_T_POST_STATS, SPKD_T_BF_GCC, SPKD_T_BF_TRACK, SPKD_T_BF_SUM, SPKD_T_RESAMPLE, SPKD_T_FRAME_ENERGY, SPKD_T_ENERGY_SEEDS,
     SPKD_T_FEATURE_WARP, SPKD_T_TDOA_PACK, SPKD_T_TDOA_STATS, SPKD_T_TDOA_MODELS, SPKD_T_TDOA_SCORE,
-    SPKD_T_TDOA_CUTS, SPKD_T_TDOA_SPLIT,
+    SPKD_T_TDOA_CUTS, SPKD_T_TDOA_SPLIT, SPKD_T_TDOA_SECOND, SPKD_T_TDOA_OVERLAP,
     SPKD_T_GMM_TRAIN, SPKD_T_GMM_SEQ_LOGLIK, SPKD_T_UBM_STATS, SPKD_T_CLR_LINK,
     SPKD_T_MINDUR_VITERBI, SPKD_T_MINDUR_BACKTRACK, SPKD_T_FB_POSTERIOR,
     SPKD_T_IDENT_SCORES, SPKD_T_IDENT_ASSIGN, SPKD_T_BW_ACCUMULATE,
@@ -964,6 +964,58 @@ spkd_status spkd_tdoa_split(spkd_ctx *ctx, const int64_t *d_stats, int64_t n_pro
                             int32_t rate_out, int32_t min_frames, double floor_s, double lambdac,
                             double threshold, int32_t *h_merge_a, int32_t *h_merge_b, double *h_merge_d,
                             int32_t *h_n_merges /* out [n_problems] */, int32_t *h_placed /* out [n] */);
+
+/* ---------------------------------------------------------------------------
+ * (6b5) Overlapped speech from the delay stream: when two talkers at two seats speak in one step, the tracked
+ * delay is one talker's seat and the runner-up among the step's GCC-PHAT candidates is the other's.  A second
+ * stream keeps the runner-up, and one call names, per step, the pair of speakers whose delay models the two lags
+ * fit on enough channels.  Opt-in; stated once in csrc/spkd_overlap.hpp.
+ * PARITY: no reference counterpart; tests/overlap_numpy.py restates every rule.
+ *
+ * The runner-up stream.  int32 with the layout of the delay stream (6b3): the same offsets, the same file table,
+ *   SPKD_TDOA_NONE where a step has no runner-up on a channel.
+ * spkd_tdoa_second: for entry i < n, with d_delay[i], d_lag[4 i + k] and d_val[4 i + k] as spkd_bf_track read and
+ *   wrote them: if d_val[4 i] < min_peak (the step is not reliable) d_out[i] = SPKD_TDOA_NONE.  Else the slots
+ *   k = 0 .. n_best - 1 are walked in order; the first with a finite value and |d_lag[4 i + k] - d_delay[i]| > guard
+ *   is the runner-up, and d_out[i] is its lag if its value >= min_second (float32), SPKD_TDOA_NONE if not, and
+ *   SPKD_TDOA_NONE when no slot qualifies.  The reference channel's entry holds one finite slot, at its own delay
+ *   (spkd_bf_gcc), so it is SPKD_TDOA_NONE by the same walk.  One lane per entry.  Refusals: n < 0, n_best outside
+ *   [1, 4], guard < 0, a min_peak or min_second that is not a number, a null or misaligned device pointer when
+ *   n > 0.  Timer: SPKD_T_TDOA_SECOND.
+ * spkd_tdoa_overlap: both streams and the file table as spkd_tdoa_stats takes them; d_models and h_live as
+ *   spkd_tdoa_models left them; h_spk_off [n_files + 1]: the speakers of file f are the consecutive models
+ *   [h_spk_off[f], h_spk_off[f + 1]), at most SPKD_OVERLAP_MAX_SPK.  d_pair: int32 [sum of T_f][2], the steps of the
+ *   files one after the other.
+ *   Near: a lag x is near speaker j on channel c iff ((double)x - mean) * ((double)x - mean) * inv2var <= gate, with
+ *   mean and inv2var = 1 / (2 var) the model's, every operation rounded on its own (no contraction).
+ *   Agreement: channel c agrees with the pair j < k at step t iff c is live in the file, is not the reference
+ *   channel, the tracked delay p and the runner-up q are both present, and one of {p, q} is near j while the other
+ *   is near k, in either assignment.
+ *   The raw pair of a step is the (j, k) with the most agreeing channels n_jk, the lexicographically smallest on a
+ *   tie, if n_jk >= min(min_channels, live non-reference channels of the file) and n_jk >= 1; else (-1, -1).  A
+ *   file with no live channel, with fewer than two speakers or with one channel yields only (-1, -1).
+ *   The run filter: a step keeps its raw pair iff it lies in a run of at least min_steps consecutive steps of its
+ *   file with the same raw pair; runs never cross files.  j and k count from the file's first model.
+ *   Two launches: the match (a workgroup per tile of SPKD_TDOA_TILE steps of one file, a lane per step, the file's
+ *   models staged in LDS once, per channel two 16-bit speaker masks from which the pairs are counted), then the
+ *   run filter (a lane per step, at most min_steps - 1 neighbours read on each side).  No atomics; the bits of a
+ *   file's steps do not depend on the other files of the call.
+ *   Refusals (SPKD_EINVAL before any device work): those of spkd_tdoa_stats on the file table and the clock,
+ *   speaker offsets that do not start at 0 or that descend, more than 16 speakers in a file, a live channel a
+ *   file does not have, a gate that is not finite and > 0, min_channels < 1, min_steps outside [1,
+ *   SPKD_OVERLAP_MAX_RUN], null arrays.  No step: SPKD_OK with nothing launched.  Timer: SPKD_T_TDOA_OVERLAP, over
+ *   both launches. */
+#define SPKD_OVERLAP_MAX_SPK 16
+#define SPKD_OVERLAP_MAX_RUN 64
+spkd_status spkd_tdoa_second(spkd_ctx *ctx, const int32_t *d_delay, const int32_t *d_lag, const float *d_val,
+                             int32_t n_best, float min_peak, float min_second, int32_t guard, int64_t n,
+                             int32_t *d_out);
+spkd_status spkd_tdoa_overlap(spkd_ctx *ctx, const int32_t *d_stream, int64_t n_entries,
+                              const int64_t *h_files /* [n_files][SPKD_TDOA_FILE] */, int64_t n_files,
+                              int32_t hop, int32_t window, int32_t rate_out, const int32_t *d_second,
+                              const double *d_models, const int32_t *h_live /* [n_files] */,
+                              const int64_t *h_spk_off /* [n_files + 1] */, double gate, int32_t min_channels,
+                              int32_t min_steps, int32_t *d_pair /* out [sum T][2] */);
 
 /* ---------------------------------------------------------------------------
  * (6c) The seed stage of a speech / non-speech detector trained on the recording itself: frame

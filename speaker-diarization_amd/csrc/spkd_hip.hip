@@ -27,6 +27,7 @@
 #include "spkd_beamform.hpp"
 #include "spkd_tdoa.hpp"
 #include "spkd_seat.hpp"
+#include "spkd_overlap.hpp"
 #include "spkd_energy.hpp"
 #include "spkd_vad.hpp"
 #include "spkd_vad_batch.hpp"
@@ -367,7 +368,7 @@ enum {
     S_CP_TURNS, S_CP_TIMES, S_CP_LINES, S_REDO_STATS, S_REDO_IDX, S_VAD_TAB, S_VAD_BACK, S_VAD_FILES, S_VAD_TOKENS, S_SUM_IDX, S_GAUSS_OK, S_GAUSS_IDX,
     S_GT_TAB, S_GT_WORK, S_GT_IDX, S_UBM_TAB, S_UBM_WORK, S_CLR_WORK, S_CLR_MAT,
     S_MD_TAB, S_MD_BACK, S_MD_G, S_MD_B, S_MD_SEQS, S_MD_TOKENS, S_FB_TAB, S_FB_FWD, S_FB_OUT,
-    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_BF_TAB, S_BF_TW, S_BF_ENERGY, S_BF_BACK, S_EN_TAB, S_ES_TAB, S_ES_FILES, S_ES_RUNS, S_WARP_TAB, S_TD_TAB, S_SEAT_OUT, S_SEAT_WORK, S_SEAT_MAT, S_COUNT
+    S_ID_WORK, S_ID_MAT, S_ACC_TAB, S_POST_TAB, S_POST_PARTIAL, S_RS_TAB, S_BF_TAB, S_BF_TW, S_BF_ENERGY, S_BF_BACK, S_EN_TAB, S_ES_TAB, S_ES_FILES, S_ES_RUNS, S_WARP_TAB, S_TD_TAB, S_SEAT_OUT, S_SEAT_WORK, S_SEAT_MAT, S_OVL_RAW, S_COUNT
 };
 static_assert(S_COUNT <= N_SLOTS, "scratch slot table too small");
 
@@ -2959,6 +2960,100 @@ spkd_status spkd_tdoa_split(spkd_ctx* c, const int64_t* d_stats, int64_t n_probl
         std::memcpy(h_merge_d + o, out.h.d + o, k * sizeof(double));
     }
     return SPKD_OK;
+}
+
+// ------------------------------------------------------------------ (6b5) overlapped speech from the delay stream
+static_assert(OVL_MAX_SPK == SPKD_OVERLAP_MAX_SPK && OVL_MAX_RUN == SPKD_OVERLAP_MAX_RUN && OVL_TPB == SPKD_TDOA_TILE,
+              "the header states the overlap kernels' limits and tile");
+
+spkd_status spkd_tdoa_second(spkd_ctx* c, const int32_t* d_delay, const int32_t* d_lag, const float* d_val, int32_t n_best,
+                             float min_peak, float min_second, int32_t guard, int64_t n, int32_t* d_out) {
+    if (!c || n < 0) return SPKD_EINVAL;
+    if (n_best < 1 || n_best > BF_NBEST) return fail(c, SPKD_EINVAL, "tdoa_second: n_best outside [1, 4]");
+    if (guard < 0) return fail(c, SPKD_EINVAL, "tdoa_second: guard >= 0");
+    if (min_peak != min_peak) return fail(c, SPKD_EINVAL, "tdoa_second: min_peak is not a number");
+    if (min_second != min_second) return fail(c, SPKD_EINVAL, "tdoa_second: min_second is not a number");
+    if (n == 0) return SPKD_OK;
+    if (!d_delay || !d_lag || !d_val || !d_out) return fail(c, SPKD_EINVAL, "tdoa_second: null device buffer");
+    if ((uintptr_t)d_delay % 4 || (uintptr_t)d_lag % 4 || (uintptr_t)d_val % 4 || (uintptr_t)d_out % 4)
+        return fail(c, SPKD_EINVAL, "tdoa_second: misaligned buffer");
+    const int64_t blocks = (n + TD_TPB - 1) / TD_TPB;
+    if (blocks > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_second: too many entries in one call");
+    Call call(c);
+    TRY(call.opened);
+    {
+        Timer tm(c, SPKD_T_TDOA_SECOND);
+        hipLaunchKernelGGL(k_tdoa_second, dim3((unsigned)blocks), dim3(TD_TPB), 0, c->stream, d_delay, d_lag, d_val, (int)n_best,
+                           min_peak, min_second, (int)guard, (long long)n, d_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    return call.finish();
+}
+
+spkd_status spkd_tdoa_overlap(spkd_ctx* c, const int32_t* d_stream, int64_t n_entries, const int64_t* h_files, int64_t n_files,
+                              int32_t hop, int32_t window, int32_t rate_out, const int32_t* d_second, const double* d_models,
+                              const int32_t* h_live, const int64_t* h_spk_off, double gate, int32_t min_channels,
+                              int32_t min_steps, int32_t* d_pair) {
+    if (!c) return SPKD_EINVAL;
+    TdoaClock K;
+    TRY(tdoa_files(c, "tdoa_overlap", h_files, n_files, n_entries, hop, window, rate_out, &K));
+    if (!(gate > 0.0) || !(gate < INFINITY)) return fail(c, SPKD_EINVAL, "tdoa_overlap: gate a finite number > 0");
+    if (min_channels < 1) return fail(c, SPKD_EINVAL, "tdoa_overlap: min_channels >= 1");
+    if (min_steps < 1 || min_steps > OVL_MAX_RUN) return fail(c, SPKD_EINVAL, "tdoa_overlap: min_steps outside [1, 64]");
+    if (n_files == 0) return SPKD_OK;
+    if (!h_live || !h_spk_off) return fail(c, SPKD_EINVAL, "tdoa_overlap: null arrays");
+    if (h_spk_off[0] != 0) return fail(c, SPKD_EINVAL, "tdoa_overlap: the speaker offsets must start at 0");
+    int64_t total = 0, n_tiles = 0;
+    for (int64_t f = 0; f < n_files; ++f) {
+        const int64_t* F = h_files + f * TD_FILE;
+        const int64_t k = h_spk_off[f + 1] - h_spk_off[f];
+        if (k < 0) return fail(c, SPKD_EINVAL, "tdoa_overlap: the speaker offsets must be non-decreasing");
+        if (k > OVL_MAX_SPK) return fail(c, SPKD_EINVAL, "tdoa_overlap: at most 16 speakers a file");
+        const int32_t valid = F[TDF_C] > 1 ? (((1 << F[TDF_C]) - 1) & ~(1 << F[TDF_REF])) : 0;
+        if (h_live[f] & ~valid) return fail(c, SPKD_EINVAL, "tdoa_overlap: a live channel the file does not have");
+        if (F[TDF_T] > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_overlap: too many steps in a file");
+        total += F[TDF_T];
+        n_tiles += (F[TDF_T] + OVL_TPB - 1) / OVL_TPB;
+    }
+    if (total == 0) return SPKD_OK;
+    if (n_tiles > 0x7fffffff || h_spk_off[n_files] > 0x7fffffff) return fail(c, SPKD_EINVAL, "tdoa_overlap: too many steps or speakers in one call");
+    if (!d_stream || !d_second || !d_pair || (h_spk_off[n_files] > 0 && !d_models)) return fail(c, SPKD_EINVAL, "tdoa_overlap: null device buffer");
+    if ((uintptr_t)d_stream % 4 || (uintptr_t)d_second % 4 || (uintptr_t)d_pair % 4 || (uintptr_t)d_models % 8)
+        return fail(c, SPKD_EINVAL, "tdoa_overlap: misaligned buffer");
+    const size_t nf = (size_t)n_files, nt = (size_t)n_tiles;
+    struct Tab { long long *files, *spk_off, *step_off; int* live; OvlTile* tile; };
+    auto t = mirror<Tab>([&](Layout L, Tab& p) {
+        return L.part(p.files, nf * TD_FILE).part(p.spk_off, nf + 1).part(p.step_off, nf).part(p.live, nf).part(p.tile, nt).bytes();
+    });
+    TRY(stage(c, PIN_TD_TAB, t));
+    std::memcpy(t.h.files, h_files, nf * TD_FILE * sizeof(int64_t));
+    std::memcpy(t.h.spk_off, h_spk_off, (nf + 1) * sizeof(int64_t));
+    std::memcpy(t.h.live, h_live, nf * sizeof(int32_t));
+    {
+        long long at = 0;
+        OvlTile* tl = t.h.tile;
+        for (size_t f = 0; f < nf; ++f) {
+            const int64_t T = h_files[f * TD_FILE + TDF_T];
+            t.h.step_off[f] = at;
+            for (int64_t s = 0; s < T; s += OVL_TPB, ++tl) tl->file = (int)f, tl->step0 = (int)s;
+            at += T;
+        }
+    }
+    Call call(c);
+    TRY(call.opened);
+    TRY(send(call, S_TD_TAB, t));
+    void* d_raw = nullptr;
+    TRY(scratch(c, S_OVL_RAW, (size_t)total * sizeof(int32_t), &d_raw));
+    {
+        Timer tm(c, SPKD_T_TDOA_OVERLAP);
+        const OvlFiles S{t.d.files, t.d.spk_off, t.d.step_off, t.d.live};
+        hipLaunchKernelGGL(k_ovl_match, dim3((unsigned)nt), dim3(OVL_TPB), 0, c->stream, d_stream, d_second, S,
+                           (const OvlTile*)t.d.tile, d_models, gate, (int)min_channels, (int32_t*)d_raw);
+        hipLaunchKernelGGL(k_ovl_runs, dim3((unsigned)nt), dim3(OVL_TPB), 0, c->stream, (const int32_t*)d_raw, S,
+                           (const OvlTile*)t.d.tile, (int)min_steps, d_pair);
+    }
+    HIPCHK(c, hipGetLastError());
+    return call.finish();
 }
 
 // ------------------------------------------------------------------ (6c) frame energies and their seeds

@@ -206,6 +206,10 @@ def _audio_files(audios):
 # channel, -1 for the loudest, or a list with one entry per file.
 BEAMFORM = dict(step_s=0.25, window_s=0.5, max_delay_s=0.01, n_best=4, min_peak=0.1, jump_penalty=0.02, jump_cap=25, ref=-1)
 BEAMFORM_MAX_LAG = hipabi.BF_NFFT // 2
+# The runner-up stream of a DelayStream(second=True) (include/spkd.h (6b5)): the smallest value of a runner-up candidate
+# and how many samples it lies from the tracked delay at the least.  Both rest on the white-noise scenes of
+# tests/beamform_numpy.py and are UNMEASURED on speech and in reverberation.
+SECOND = dict(min_second=0.1, guard=3)
 
 
 def beamform_geometry(rate, opts=BEAMFORM):
@@ -292,7 +296,8 @@ def _beamform_group(ctx, d_raw, in_off, channels, geom, geoms, ref, opts, d_out,
     if some:
         ms['bf_sum'] += ctx.last_ms('bf_sum')
     if delays is not None:
-        delays[0]._pack_group(delays[1], T, C, d_ref if some else None, ref, d_delay, d_val, opts['min_peak'], ms)
+        delays[0]._pack_group(delays[1], T, C, d_ref if some else None, ref, d_delay, d_val, opts['min_peak'], ms, d_lag,
+                              opts['n_best'])
     if detail is not None:
         got_ref = np.zeros(n_files, dtype=np.int32)
         delay = np.zeros(total, dtype=np.int32)
@@ -336,13 +341,24 @@ class DelayStream(object):
     delays=stream) and beamform_batch(..., delays=stream) fill it; from_arrays builds one from host arrays;
     resegment_batch(..., delays=stream) reads it.  A one-channel file has T = 0.  The buffer is a scratch
     slot of the context: a stream lives until the next one is laid out on the same context, and says so
-    (ValueError) when it is used after that."""
+    (ValueError) when it is used after that.
+    second=True: the stream also keeps, in a scratch slot of its own under the same rule, the runner-up lag of every
+    entry (include/spkd.h (6b5); spkd_tdoa_second with min_second and guard, SECOND's unless given): the other
+    talker's seat while two speak at once, which overlap.overlap_batch reads (handle_second, to_host_second).
+    second=False makes no call and no allocation for it."""
 
-    def __init__(self, ctx, hop, window, rate_out=16000):
+    def __init__(self, ctx, hop, window, rate_out=16000, second=False, min_second=None, guard=None):
         hop, window, rate_out = int(hop), int(window), int(rate_out)
         if hop < 1 or window < 0 or rate_out < 1:
             raise ValueError('DelayStream: hop >= 1, window >= 0 and rate_out >= 1, in samples and Hz')
+        if not isinstance(second, (bool, np.bool_)):
+            raise ValueError('DelayStream second: True or False')
         self.ctx, self.hop, self.window, self.rate_out = ctx, hop, window, rate_out
+        self.second, self.d_second, self.from_beamformer = bool(second), None, False
+        self.min_second = float(SECOND['min_second'] if min_second is None else min_second)
+        self.guard = int(SECOND['guard'] if guard is None else guard)
+        if self.second and (np.isnan(self.min_second) or self.guard < 0):
+            raise ValueError('DelayStream: min_second a number and guard >= 0')
         self.d_stream, self.n_entries, self._generation = None, 0, 0
         self.files = np.zeros((0, 6), dtype=np.int64)      # off, T, C, ref, H, rate_in
 
@@ -373,6 +389,8 @@ class DelayStream(object):
                                       np.asarray(rates, dtype=np.int64).reshape(-1)]).astype(np.int64).reshape(-1, 6)
         self.ctx, self.n_entries = ctx, int(off[-1])
         self.d_stream = ctx.dev_scratch('tdoa_stream', max(4 * self.n_entries, 16))
+        if self.second:
+            self.d_second = ctx.dev_scratch('tdoa_second', max(4 * self.n_entries, 16))
         self._generation = ctx._tdoa_generation = getattr(ctx, '_tdoa_generation', 0) + 1
 
     def _reserve(self, ctx, files, geom, geoms):
@@ -381,11 +399,19 @@ class DelayStream(object):
         C = np.array([a.shape[1] for a, _ in files], dtype=np.int64)
         T = _beamform_steps([len(a) for a, _ in files], C, geom, geoms)
         self._lay_out(ctx, T, C, np.full(len(files), -1), [geoms[g][0] for g in geom], [rate for _, rate in files])
+        self.from_beamformer = True                        # (its runner-ups are min_second's and guard's)
 
-    def _pack_group(self, first, T, C, d_ref, want_ref, d_delay, d_val, min_peak, ms):
+    def _pack_group(self, first, T, C, d_ref, want_ref, d_delay, d_val, min_peak, ms, d_lag=None, n_best=None):
         n_files, total = len(T), int((T * C).sum())
         assert np.array_equal(self.files[first:first + n_files, 1], T) and np.array_equal(self.files[first:first + n_files, 2], C)
         at = self.d_stream + 4 * int(self.files[first, 0])
+        if self.second and total:
+            at2 = self.d_second + 4 * int(self.files[first, 0])
+            if d_ref is None:                              # (a group without a sample has no candidates: no runner-up)
+                self.ctx.h2d(at2, np.full(total, hipabi.TDOA_NONE, dtype=np.int32))
+            else:
+                self.ctx.tdoa_second(d_delay, d_lag, d_val, n_best, min_peak, self.min_second, self.guard, total, at2)
+                ms['tdoa_second'] = ms.get('tdoa_second', 0.0) + self.ctx.last_ms('tdoa_second')
         if d_ref is None:
             # a group without a sample: the beamformer launched nothing.  Its files' one step holds what the kernels
             # define for it in any other grouping: the requested reference channel, else channel 0, at lag 0 with
@@ -405,11 +431,14 @@ class DelayStream(object):
         self.files[first:first + n_files, 3] = got_ref
 
     @classmethod
-    def from_arrays(cls, ctx, hop, window, files, rate_out=16000):
+    def from_arrays(cls, ctx, hop, window, files, rate_out=16000, second=None):
         """The same stream from host arrays, for known geometries and for tests: files = [(delay int32 [T, C],
         reliable bool [T, C], ref, H, rate_in)]; a delay beyond +-4096 samples on a reliable entry, a reference
-        channel outside the file's, shapes that differ: ValueError."""
-        self = cls(ctx, hop, window, rate_out)
+        channel outside the file's, shapes that differ: ValueError.  second: None, or per file the runner-up stream as
+        it lies on the device, int32 [T, C] with hipabi.TDOA_NONE for none (or None: none anywhere in the file)."""
+        self = cls(ctx, hop, window, rate_out, second=second is not None)
+        if second is not None and len(second) != len(files):
+            raise ValueError('second: one array, or None, per file')
         packed, T, C, refs, Hs, rates = [], [], [], [], [], []
         for f, (delay, reliable, ref, H, rate_in) in enumerate(files):
             d, r = np.asarray(delay), np.asarray(reliable)
@@ -426,10 +455,19 @@ class DelayStream(object):
             if r.any() and int(np.abs(d[r].astype(np.int64)).max()) > hipabi.TDOA_MAX_DELAY:
                 raise ValueError('file %d: a delay beyond %d samples' % (f, hipabi.TDOA_MAX_DELAY))
             packed.append(np.where(r, d.astype(np.int64), hipabi.TDOA_NONE).astype(np.int32).ravel())
+            if second is not None and second[f] is not None:
+                q = np.asarray(second[f])
+                if q.shape != d.shape or q.dtype.kind not in 'iu':
+                    raise ValueError('file %d: second int32 [T, C] expected' % f)
+                if ((q != hipabi.TDOA_NONE) & (np.abs(q.astype(np.int64)) > hipabi.TDOA_MAX_DELAY)).any():
+                    raise ValueError('file %d: a runner-up beyond %d samples' % (f, hipabi.TDOA_MAX_DELAY))
             T.append(d.shape[0]), C.append(d.shape[1]), refs.append(int(ref)), Hs.append(int(H)), rates.append(int(rate_in))
         self._lay_out(ctx, T, C, refs, Hs, rates)
         if self.n_entries:
             ctx.h2d(self.d_stream, np.concatenate(packed))
+            if second is not None:
+                ctx.h2d(self.d_second, np.concatenate([np.full(len(p), hipabi.TDOA_NONE, dtype=np.int32) if q is None else
+                                                       np.asarray(q).astype(np.int32).ravel() for p, q in zip(packed, second)]))
         return self
 
     def table(self, frame_off):
@@ -445,6 +483,27 @@ class DelayStream(object):
         context has taken the buffer."""
         self._current()
         return self.d_stream, self.n_entries, self.table(frame_off), (self.hop, self.window, self.rate_out)
+
+    def handle_second(self):
+        """The device pointer of the runner-up stream, what hipabi's tdoa_overlap takes as d_second.  ValueError for a
+        stream made without second=True, and when a later stream of the context has taken the buffers."""
+        if not self.second:
+            raise ValueError('delays: the stream keeps no runner-ups; make it with DelayStream(..., second=True)')
+        self._current()
+        return self.d_second
+
+    def to_host_second(self):
+        """Per file the runner-up stream, int32 [T, C], hipabi.TDOA_NONE where there is none."""
+        d_second = self.handle_second()
+        packed = np.full(self.n_entries, hipabi.TDOA_NONE, dtype=np.int32)
+        if self.n_entries and d_second is not None:
+            self.ctx.d2h(packed, d_second)
+        return [packed[off:off + T * C].reshape(T, C).copy() for off, T, C, _, _, _ in self.files.tolist()]
+
+    def first_frame_of(self, f, s):
+        """The first frame (file-local) of step s of file f (step_first_frame with the file's table entry)."""
+        _, _, _, _, H, rate_in = (int(v) for v in self.files[f])
+        return step_first_frame(s, self.hop, self.window, rate_in, self.rate_out, H)
 
     def step_of(self, f, t):
         """The step of file f's frame t (frame_step with the file's table entry); the file has steps."""

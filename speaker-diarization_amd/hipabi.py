@@ -18,7 +18,7 @@ TIMERS = {n: i for i, n in enumerate(['call', 'chunk_stats', 'reduce_sets', 'pai
                                         'cluster_prep', 'matrix', 'ahc', 'gw', 'sw', 'merge',
                                         'vad_shift', 'vad_viterbi', 'vad_backtrack', 'gauss_models', 'gauss_loglik',
                                         'post_stats', 'bf_gcc', 'bf_track', 'bf_sum', 'resample', 'frame_energy', 'energy_seeds',
-                                        'feature_warp', 'tdoa_pack', 'tdoa_stats', 'tdoa_models', 'tdoa_score', 'tdoa_cuts', 'tdoa_split', 'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
+                                        'feature_warp', 'tdoa_pack', 'tdoa_stats', 'tdoa_models', 'tdoa_score', 'tdoa_cuts', 'tdoa_split', 'tdoa_second', 'tdoa_overlap', 'gmm_train', 'gmm_seq_loglik', 'ubm_stats', 'clr_link',
                                         'mindur_viterbi', 'mindur_backtrack', 'fb_posterior',
                                         'ident_scores', 'ident_assign', 'bw_accumulate',
                                         'mfcc_static', 'mfcc_post'])}
@@ -57,6 +57,8 @@ TDOA_FILE = 8               # SPKD_TDOA_FILE: int64 per file of the stream's hos
 TDOA_MODEL = 4              # SPKD_TDOA_MODEL: doubles per (speaker, channel): mean, var, 1 / (2 var), -1/2 log(2 pi var)
 TDOA_TILE = 256             # SPKD_TDOA_TILE: frames per workgroup of k_tdoa_score, steps per workgroup of k_tdoa_stats
 SEAT_MAX_N = 4096           # SPKD_SEAT_MAX_N: records of one problem of spkd_tdoa_split
+OVERLAP_MAX_SPK = 16        # SPKD_OVERLAP_MAX_SPK: speakers of a file of spkd_tdoa_overlap
+OVERLAP_MAX_RUN = 64        # SPKD_OVERLAP_MAX_RUN: the largest min_steps of spkd_tdoa_overlap
 WARP_MAX_WINDOW = 512       # SPKD_WARP_MAX_WINDOW: the widest window of spkd_feature_warp, in frames
 WARP_TILE = 384             # SPKD_WARP_TILE: compacted frames per workgroup of k_feature_warp
 REC = 820
@@ -66,7 +68,7 @@ EXPORTS = ['spkd_abi_version', 'spkd_create', 'spkd_create_on_stream', 'spkd_des
            'spkd_malloc', 'spkd_free', 'spkd_memcpy_h2d', 'spkd_memcpy_d2h', 'spkd_memcpy_d2d',
            'spkd_last_kernel_ms', 'spkd_last_gw_items', 'spkd_last_ahc_head', 'spkd_ahc_head_rule', 'spkd_set_stats', 'spkd_pair_terms',
            'spkd_distance_matrix', 'spkd_gw_event_capacity', 'spkd_gw_event_capacity_p', 'spkd_gw', 'spkd_gw_ex', 'spkd_gw_fused', 'spkd_gw_batch', 'spkd_ahc_fused', 'spkd_gather_stats', 'spkd_sum_stats', 'spkd_mfcc', 'spkd_mfcc_batch', 'spkd_resample_batch', 'spkd_bf_gcc', 'spkd_bf_track', 'spkd_bf_sum',
-           'spkd_tdoa_pack', 'spkd_tdoa_stats', 'spkd_tdoa_models', 'spkd_tdoa_score', 'spkd_tdoa_cuts', 'spkd_tdoa_split',
+           'spkd_tdoa_pack', 'spkd_tdoa_stats', 'spkd_tdoa_models', 'spkd_tdoa_score', 'spkd_tdoa_cuts', 'spkd_tdoa_split', 'spkd_tdoa_second', 'spkd_tdoa_overlap',
            'spkd_sw_window_count', 'spkd_sw', 'spkd_sw_runs', 'spkd_sw_batch', 'spkd_merge_batch', 'spkd_ahc', 'spkd_ahc_matrix', 'spkd_distance_rows', 'spkd_cluster_in', 'spkd_cluster_in_batch', 'spkd_py2_roundtrip',
            'spkd_labels_from_merges', 'spkd_labels_from_merges_batch', 'spkd_count_flags', 'spkd_gw_lines',
            'spkd_gmm_loglik', 'spkd_vad_viterbi', 'spkd_vad_shift_batch', 'spkd_vad_viterbi_batch',
@@ -251,6 +253,8 @@ def load_library(path=None):
     lib.spkd_tdoa_score.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, i32, dbl, vp]
     lib.spkd_tdoa_cuts.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, i64, i64, i32, dbl, dbl, dbl, vp, vp]
     lib.spkd_tdoa_split.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, dbl, dbl, dbl, vp, vp, vp, vp, vp]
+    lib.spkd_tdoa_second.argtypes = [vp, vp, vp, vp, i32, C.c_float, C.c_float, i32, i64, vp]
+    lib.spkd_tdoa_overlap.argtypes = [vp, vp, i64, vp, i64, i32, i32, i32, vp, vp, vp, vp, dbl, i32, i32, vp]
     lib.spkd_frame_energy_batch.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp]
     lib.spkd_energy_seeds.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, P(vp), P(vp), P(vp)]
     lib.spkd_sw_window_count.argtypes = [i64, dbl, dbl]
@@ -989,6 +993,28 @@ class Context(object):
         self.check(self.lib.spkd_tdoa_score(self.h, *args, C.c_void_p(d_models), int(n_models), _ptr(lv), len(b), _ptr(b),
                                             _ptr(e), _ptr(f), _ptr(m), _ptr(k), int(n_cols), float(weight),
                                             C.c_void_p(d_scores)))
+
+    # ---- (6b5) overlapped speech from the delay stream
+    def tdoa_second(self, d_delay, d_lag, d_val, n_best, min_peak, min_second, guard, n, d_out):
+        """n entries of the runner-up stream from what spkd_bf_track read and wrote (spkd_tdoa_second): d_out[i] = the lag
+        of the first of the n_best candidates with a finite value that lies more than guard samples from d_delay[i],
+        if its value >= min_second and the step is reliable (d_val[4 i] >= min_peak); TDOA_NONE elsewhere.  Time:
+        last_ms('tdoa_second')."""
+        self.check(self.lib.spkd_tdoa_second(self.h, C.c_void_p(d_delay), C.c_void_p(d_lag), C.c_void_p(d_val), int(n_best),
+                                             float(min_peak), float(min_second), int(guard), int(n), C.c_void_p(d_out)))
+
+    def tdoa_overlap(self, stream, d_second, d_models, live, spk_off, gate, min_channels, min_steps, d_pair):
+        """The pair of speakers of every step (spkd_tdoa_overlap; include/spkd.h (6b5)): stream as _tdoa_stream takes it,
+        d_second the runner-up stream of the same layout, d_models and live as tdoa_models left them, spk_off int64
+        [n_files + 1] the first model of every file.  d_pair int32 [sum T, 2]: per step (j, k), j < k counted from the
+        file's first model, or (-1, -1).  Time: last_ms('tdoa_overlap'), both launches."""
+        args, _keep = self._tdoa_stream(stream)
+        lv = np.ascontiguousarray(live, dtype=np.int32)
+        so = np.ascontiguousarray(spk_off, dtype=np.int64)
+        if lv.shape != (len(_keep),) or so.shape != (len(_keep) + 1,):
+            raise SpkdError(SPKD_EINVAL, 'one live mask per file, and one speaker offset per file and the total')
+        self.check(self.lib.spkd_tdoa_overlap(self.h, *args, C.c_void_p(d_second), C.c_void_p(d_models), _ptr(lv), _ptr(so),
+                                              float(gate), int(min_channels), int(min_steps), C.c_void_p(d_pair)))
 
     # ---- (6c) the seed stage of the self-trained detector
     def frame_energy_batch(self, d_pcm, sample_off, hop, window, d_energy):

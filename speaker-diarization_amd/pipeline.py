@@ -17,12 +17,15 @@ import numpy as np
 
 from . import exp_generator, frontend, hipabi, voice_detection
 from . import linking as _linking
+from . import overlap as _overlap
 from . import resegmentation as _resegmentation
 from . import seats as _seats
 from . import self_vad as _self_vad
 from .recipe import py2_float_str
 # the linking stage (linking.py, on clr_model.py and gallery.py): its settings and its entry point under their names here
 from .linking import LINK_CL, LINK_CLR, LINK_CLR_WARP, _link_model, link_batch, ubm_ranges
+# the overlap stage behind the rows (overlap.py): its settings and its entry points under their names here
+from .overlap import OVERLAP, overlap_batch, second_rows
 # the resegmentation stage (resegmentation.py): its settings and its entry point under their names here
 from .resegmentation import (FB_MAX_SCALED_PENALTY, RESEG, RESEG_CONF, RESEG_GMM, RESEG_MAX_SPEAKERS, RESEG_MD,
                              RESEG_SOFT, RESEG_SOFT_SCALE, RESEG_TDOA, TDOA, resegment_batch)
@@ -133,8 +136,8 @@ def diarize_pcm_batch(ctx, model, cfg, pcms, cd=DIA2_CD, cl=DIA2_CL, timings=Non
     (features_batch with cfg, the fconfig.cfg chain) both from it, then diarize_batch with the
     turns and the frames as they lie on the device.  uploaded: the samples already on the device
     (frontend.upload_batch or frontend.resample_batch; pcms is not read then).  kw: diarize_batch's
-    text_contract, fused, handoff, link, reseg, seats, detail, delays (the frontend.DelayStream of reseg['tdoa'] and of
-    seats).  Returns its rows.
+    text_contract, fused, handoff, link, reseg, seats, overlap, detail, delays (the frontend.DelayStream of
+    reseg['tdoa'], of seats and of overlap).  Returns its rows.
     model: a dictionary like SELF_VAD instead of a VadModel needs no model file: one upload, ONE
     feature chain (cfg's), the self-trained turns on those features (vad_batch), then diarize_batch;
     detail, if given, also receives vad_untrained and vad_passes_run."""
@@ -172,23 +175,33 @@ def diarize_audio_batch(ctx, model, cfg, audios, cd=DIA2_CD, cl=DIA2_CL, timings
     delays the beamformer tracks are kept (a frontend.DelayStream on cfg's frame clock, made here unless
     delays= hands one in) and the resegmentation stage reads them as a second stream (resegment_batch);
     tdoa without beamform is a ValueError.  seats=<a dictionary like SEATS> with beamform takes the same stream (one
-    serves both) to the seat stages of diarize_batch; seats without beamform is a ValueError.  Returns its rows."""
+    serves both) to the seat stages of diarize_batch; seats without beamform is a ValueError.  overlap=<a dictionary
+    like OVERLAP> with beamform: the stream is made with second=True and the dictionary's min_second and guard, so it
+    also keeps the runner-up lags (one stream serves tdoa, seats and overlap), and diarize_batch runs the overlap stage
+    on its rows; overlap without beamform, or with a stream handed in that keeps no runner-ups, is a ValueError.
+    Returns its rows."""
     if isinstance(model, dict):
         _self_vad._options(model)
     else:
         _one_clock(model, cfg)
     group = {} if group_bytes is None else {'group_bytes': group_bytes}
-    if kw.get('reseg') is not None and _resegmentation._reseg_tdoa(kw['reseg']) is not None:
+    second = {}                                      # what a stream made here is made with
+    if kw.get('overlap') is not None:
+        o = _overlap._overlap_options(kw['overlap'])
         if beamform is None:
-            raise ValueError('reseg tdoa: the delays are the beamformer\'s, which takes beamform=')
-        if delays is None:
-            delays = frontend.DelayStream(ctx, cfg.hop, cfg.window_width, cfg.sample_rate)
+            raise ValueError('overlap: the delays are the beamformer\'s, which takes beamform=')
+        if delays is not None and not delays.second:
+            raise ValueError('overlap: the stream keeps no runner-ups; make it with frontend.DelayStream(..., second=True)')
+        second = dict(second=True, min_second=o.min_second, guard=o.guard)
+    tdoa = kw.get('reseg') is not None and _resegmentation._reseg_tdoa(kw['reseg']) is not None
+    if tdoa and beamform is None:
+        raise ValueError('reseg tdoa: the delays are the beamformer\'s, which takes beamform=')
     if kw.get('seats') is not None:
         _seats._seat_options(kw['seats'], float(cfg.frame_rate))
         if beamform is None:
             raise ValueError('seats: the delays are the beamformer\'s, which takes beamform=')
-        if delays is None:
-            delays = frontend.DelayStream(ctx, cfg.hop, cfg.window_width, cfg.sample_rate)
+    if (tdoa or second or kw.get('seats') is not None) and delays is None:     # one stream serves the three
+        delays = frontend.DelayStream(ctx, cfg.hop, cfg.window_width, cfg.sample_rate, **second)
     if beamform is not None:
         group['beamform'] = beamform
         if delays is not None:
@@ -603,7 +616,8 @@ def diarize_batch_device(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2
 
 
 def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl=DIA2_CL, timings=None,
-                  text_contract=True, fused=False, handoff=None, link=None, detail=None, reseg=None, delays=None, seats=None):
+                  text_contract=True, fused=False, handoff=None, link=None, detail=None, reseg=None, delays=None, seats=None,
+                  overlap=None):
     """CD (gw/BIC) + CL (hi/BIC) for a batch; returns per file an array of rows
     [start_s, end_s, speaker] in recipe order.
     cl['method'] = 'in' clusters with spk_cluster_in (cluster_batch): host hand-off only; the
@@ -656,7 +670,13 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
     another file count or frame clock, unknown keys or bad values: ValueError before any device work.  More than 16
     speakers in a file after a split, under reseg, is resegment_batch's ValueError.  detail['seats'] = dict(cuts,
     passes_run, split, unplaced) as the two stages leave them; timings: seat_cuts, seat_stats, seat_split.  A talker
-    who moves is split; two talkers who share a seat are left to the acoustics.  seats=None: today's calls and rows."""
+    who moves is split; two talkers who share a seat are left to the acoustics.  seats=None: today's calls and rows.
+    overlap: a dictionary like OVERLAP, with delays=<a stream made with second=True>: overlap_batch runs on the rows
+    this call is about to return -- after resegmentation, seats and linking -- and finds where a second speaker of the
+    file talks beside the row's own; the rows themselves are returned unchanged.  detail['overlap'] = dict(rows,
+    speakers, steps, seconds, unassigned) as overlap_batch leaves it (second_rows makes recipe rows of detail['overlap']
+    ['rows']); timings: overlap_stats, overlap_models, overlap_match.  Host hand-off only; overlap without such a
+    stream, unknown keys or bad values: ValueError before any device work.  overlap=None: today's calls and rows."""
     method = _method(cl)
     # the hand-off this call gets: the one asked for, else the device's where it can serve (a detector that
     # passes its refusal below is neither fused nor on the device, so the rule reads the same behind it)
@@ -675,6 +695,10 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
             raise ValueError('seats split the clusters of cl method hi')
         _seats._check_delays(delays, files, float(rate))
         _seats._empty_detail(detail, len(files))
+    if overlap is not None:
+        _overlap._check_delays(delays, _overlap._overlap_options(overlap), files, float(rate))
+        if device:
+            raise ValueError('overlap takes the host hand-off')
     if _cd_method(cd) in ('sw', 'm'):
         if fused or handoff == 'device':
             raise ValueError('cd method %s takes the host hand-off and is not fused' % _cd_method(cd))
@@ -702,11 +726,17 @@ def diarize_batch(ctx, d_frames, total_frames, files, rate=125.0, cd=DIA2_CD, cl
                                   stat_max=float('nan'), stat_min=float('nan'))
         if reseg is not None:
             _resegmentation._empty_detail(detail, reseg_opts, len(files))
-        return [np.zeros((0, 3)) for _ in files]
+        rows = [np.zeros((0, 3)) for _ in files]
+        if overlap is not None:
+            overlap_batch(ctx, files, rows, delays, rate, overlap, text_contract, timings, detail)
+        return rows
     if seats is not None:
         segs = seat_cut_batch(ctx, files, segs, delays, rate, seats, text_contract, timings, detail)
-    return _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail, reseg,
-                              text_contract, delays, seats)
+    rows = _cluster_and_order(ctx, d_frames, total_frames, files, segs, rate, cl, timings, fs, link, detail, reseg, text_contract,
+                              delays, seats)
+    if overlap is not None:
+        overlap_batch(ctx, files, rows, delays, rate, overlap, text_contract, timings, detail)
+    return rows
 
 
 def warp_batch(ctx, d_frames, total_frames, files, segments, rate, warp_s, d_out=None):
